@@ -2,7 +2,7 @@
 """
 bench.py — env steps/sec of the fused rendezvous step on MI355X (BASELINE.json metric).
 
-    python bench.py                      # 1 GPU, 65,536 envs, defaults finish in < 2 min
+    python bench.py                      # 1 GPU, 65,536 envs, the headline figure only (seconds); --full adds every other leg
     python bench.py --gpus N             # starts N ranks itself (a child `python -m torch.distributed.run`, before any GPU call),
                                          # relays rank 0's JSON line and exits with the child's code
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
@@ -11,22 +11,28 @@ bench.py — env steps/sec of the fused rendezvous step on MI355X (BASELINE.json
 A "step" is one pass of the hot path over one batch: ONE launch of the fused step kernel over the rank's 65,536 envs
 (rendezvous_env.py:160-221 + auto-reset :223-270), with the float32 action batch already resident in HBM
 (16 pre-generated U(-1,1) batches used round-robin).  W untimed warm-up steps, then exactly K timed steps between
-barrier + synchronize on both sides; the MAX over ranks is used.  The K launches are replayed from a HIP graph
-(captured after the warm-up) so that the stream, not the Python interpreter, paces them; --no-graph times eager calls.
-The K-step region is repeated R times back to back ("repeats": as many as fill >= 50 ms) and the MEDIAN region time is
-reported, each region timed with HIP events on the launch stream: a region of 20 steps lasts 0.15 ms, about as long as the
-host takes to launch a graph and synchronise, so a single region measures the host as much as the kernel (round 1's
-driver-run line, --steps 20: 10.9 us per step against 7.8 us in a 4,096-step run of the same build).
+barrier + synchronize on both sides; the MAX over ranks is used.  The K launches are replayed from HIP graphs of at most
+512 launches each, captured after the warm-up, so that the stream, not the Python interpreter, paces them (--no-graph times
+eager calls).  Between capture and timing the graphs run a fixed 8,192+ untimed steps ("settle_steps"): a graph's first replay
+and the shader clock's ramp stay out of the timed region.  The K-step region is timed with HIP events on the launch stream, and
+ms_per_step is that time over K.  Choose K so that the region lasts tens of milliseconds at least: a region of 20 steps lasts
+0.15 ms, about as long as the host takes to launch a graph and synchronise.
+
+A plain run measures that headline figure only.  --full adds the informational legs below (and, under torch.distributed, the
+timed gathers to rank 0); --dump-outputs DIR writes what the last timed step returned to its caller (DIR/<name>.npy).
 
 One JSON line is printed by rank 0.  Besides the contract keys it carries
   roofline     : HBM roofline of the step kernel.  achieved = 293 B (SURVEY §8d algorithmic bytes per env-step, fp32
                  storage) x envs per launch / the launch-to-launch period measured with HIP events over the timed
                  region on the launch stream; peak = 8 TB/s; traffic = PMC-measured bytes per launch (profiles/).
+and with --full
   cpu_baseline : the CPU oracle (kind "port", oracle/rdv_oracle.c, same arithmetic) timed on this host's cores on a
                  bounded sample of the same workload (rank 0, N=1 only).
   policy_rollout: informational — the same envs driven by the 17-64-64-6 tanh MLP policy (BASELINE config 3:
                  forward + Gaussian sample + clip in PyTorch-ROCm, then the step kernel), N=1 only.
   config1_single_env_gym_object: informational — BASELINE config 1 (one env, 1000 steps) through RendezvousEnv, the reference's Gym object.
+  f64_storage, large_n, config4_global_batch_on_one_gpu, open_loop_multi_step, vecenv_numpy_boundary: the same kernel family at
+                 other precisions, sizes and launch shapes, and the SB3-facing NumPy boundary (N=1 only).
 """
 import argparse
 import json
@@ -42,6 +48,8 @@ ALGO_BYTES_PER_ENV_STEP = 293      # read 32 words, write 41 word
 HBM_PEAK_GBPS = 8000.0             # MI355X_MICROARCH.md: HBM3E 8 TB/s
 RING = 16                          # distinct action batches resident in HBM
 GRAPH_STEPS = 512                  # launches per captured graph (multiple of RING)
+SETTLE_REPLAYS = 16                # untimed replays of the GRAPH_STEPS graph right before the timed region
+DUMP_BYTES = 60 * 10**6            # --dump-outputs: .npy payload over all ranks (64 MB at most, headers included)
 
 
 def parse():
@@ -52,7 +60,10 @@ def parse():
     ap.add_argument("--envs-per-gpu", type=int, default=65536)
     ap.add_argument("--storage", choices=["f32", "f64"], default="f32")
     ap.add_argument("--no-graph", action="store_true", help="time eager ctypes launches instead of HIP-graph replays")
-    ap.add_argument("--repeats", type=int, default=0, help="K-step regions timed back to back (0: as many as fill 50 ms); the median is reported")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the informational legs (CPU baseline, fp64 storage, large batches, policy rollout, gathers, ...)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (obs, reward, done, terminal rows, ...) as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="wall-clock budget of the all-core CPU sample")
     ap.add_argument("--no-policy", action="store_true", help="skip the informational MLP-policy rollout leg")
@@ -61,7 +72,7 @@ def parse():
                     help="run ONLY the large-batch leg at N envs (five fresh allocations) and print its JSON: the program of a per-size rocprofv3 run")
     ap.add_argument("--no-gather", action="store_true", help="under torch.distributed: skip timing the RCCL gathers of rollouts to rank 0")
     ap.add_argument("--gather-steps", type=int, default=64, help="steps per rollout of the per-rollout gather leg (one message per rank per rollout)")
-    ap.add_argument("--quick", action="store_true", help="the headline leg only (= --no-cpu-baseline --no-policy --no-large-n)")
+    ap.add_argument("--quick", action="store_true", help="with --full: skip the slow legs (= --no-cpu-baseline --no-policy --no-large-n)")
     # rehearsal of the N>1 path on a box with ONE GPU (not a measurement): all ranks on cuda:0, collectives over gloo on the host
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl")
     ap.add_argument("--shared-gpu", action="store_true", help="rehearsal only: every rank uses cuda:0")
@@ -106,6 +117,33 @@ def cpu_baseline(n, seconds):
                                  "what": "the unmodified reference RendezvousEnv.step() (rendezvous_env.py:160), 1 process, U(-1,1) actions, 1000 steps",
                                  "measured_on": "the build container (Intel Xeon KVM guest @ 2.1 GHz, 8 vCPU; NumPy 2.2.6, SciPy 1.15.3) — the reference "
                                                 "cannot travel to the GPU box, so this figure is quoted from BASELINE.md section 2, not measured in this run"}}
+
+
+def dump_outputs(env, out_dir, rank, world):
+    """--dump-outputs: what the caller of rdv_step holds after the last timed step — obs, reward, done and the terminal-row
+    attributes (terminal_obs, episode_return, episode_length: zero where the env did not finish, as they are valid only where done) —
+    as float32 / float64 .npy files.  Past the DUMP_BYTES budget (split over the ranks) a fixed, seeded sample of env rows is written,
+    its row indices in sample_rows.npy.  Ranks of a multi-rank run prefix their files with rank<r>_."""
+    import numpy as np
+    import torch
+    n = env.num_envs
+    done = env.done.bool()
+    arrays = {"obs": env.obs, "reward": env.reward, "done": env.done.float(),
+              "terminal_obs": torch.where(done[:, None], env.terminal_obs, 0.0),
+              "episode_return": torch.where(done, env.episode_return, 0.0),
+              "episode_length": torch.where(done, env.episode_length, 0).double(),
+              "done_reason": env.done_reason.float()}
+    row_bytes = sum(a[0].numel() * a.element_size() for a in arrays.values())
+    rows = min(n, DUMP_BYTES // world // (row_bytes + 8))
+    if rows < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, rows, replace=False))
+        sel = torch.from_numpy(idx).to(env.device)
+        arrays = {k: v.index_select(0, sel) for k, v in arrays.items()}
+        arrays["sample_rows"] = torch.from_numpy(idx.astype(np.float64))
+    os.makedirs(out_dir, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a.cpu().numpy())
 
 
 def rank_environment(env):
@@ -153,6 +191,8 @@ def spawn_ranks(args):
 
 def main():
     args = parse()
+    if args.steps < 1:
+        sys.exit("bench.py: --steps must be at least 1")
     if args.quick:
         args.no_cpu_baseline = args.no_policy = args.no_large_n = True
     if args.only_large_n:
@@ -199,70 +239,67 @@ def main():
         env.step(ring[t % RING])
     torch.cuda.synchronize()
 
-    # ---- capture: the K timed launches as a HIP graph, so that the stream, not the Python interpreter, paces the region.  A short
-    # region (the driver's --steps 20 is 0.15 ms) is captured M times over into one graph: a graph launch costs the GPU a few us of
-    # its own, which would otherwise be charged to every 20 steps.  M x K launches per replay, timed per replay, reported per region.
+    # ---- capture: the K timed launches as HIP graphs of at most GRAPH_STEPS launches, so that the stream, not the Python interpreter,
+    # paces the region.  Before the timed region the graphs are replayed a FIXED number of times (SETTLE_REPLAYS x GRAPH_STEPS steps,
+    # about 50 ms at 65,536 envs): a graph's first replay carries set-up work of the runtime, and the shader clock takes tens of ms of
+    # load to settle.  A fixed count, not a fixed time, so that the state the timed steps start from is the same in every run.
     use_graph = not args.no_graph
-    M = max(1, GRAPH_STEPS // K) if K < GRAPH_STEPS else 1
-    n_full, n_rem = (M * K) // GRAPH_STEPS, (M * K) % GRAPH_STEPS
+    n_full, n_rem = K // GRAPH_STEPS, K % GRAPH_STEPS
     g_full = g_rem = None
 
     def capture(count, first):
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
             for t in range(count):
-                env.step(ring[((first + t) % K) % RING])      # every region replays the same K-step action sequence
+                env.step(ring[(first + t) % RING])
         return g
 
     if use_graph:
         try:
-            g_full = capture(GRAPH_STEPS, 0) if n_full else None
+            g_full = capture(GRAPH_STEPS, 0)
             g_rem = capture(n_rem, n_full * GRAPH_STEPS) if n_rem else None
             torch.cuda.synchronize()
         except Exception as exc:  # pragma: no cover - depends on the runtime
             print(f"[bench] graph capture failed ({exc!r}); timing eager launches", file=sys.stderr)
             use_graph = False
+    settle_steps = 0
+    if use_graph:
+        for _ in range(SETTLE_REPLAYS):
+            g_full.replay()
+        settle_steps = SETTLE_REPLAYS * GRAPH_STEPS
+        if n_rem:
+            g_rem.replay(); settle_steps += n_rem
+        torch.cuda.synchronize()
 
-    def run_replay():
-        """M regions of exactly K steps"""
+    def run_steps():
+        """exactly K steps"""
         if use_graph:
             for _ in range(n_full):
                 g_full.replay()
             if n_rem:
                 g_rem.replay()
         else:
-            for t in range(M * K):
-                env.step(ring[(t % K) % RING])
+            for t in range(K):
+                env.step(ring[t % RING])
 
-    # how many replays fill >= 50 ms (probe: one replay, synchronised)
-    run_replay(); torch.cuda.synchronize()
-    p0 = time.perf_counter(); run_replay(); torch.cuda.synchronize()
-    probe = max(time.perf_counter() - p0, 1e-6)
-    reps = (-(-args.repeats // M)) if args.repeats > 0 else int(min(2000, max(5, -(-0.05 // probe))))
-    if distributed:
-        rr = torch.tensor([reps], dtype=torch.int64, device=coll_device)
-        dist.all_reduce(rr, op=dist.ReduceOp.MAX)
-        reps = int(rr.item())
-    R = reps * M            # K-step regions timed in all
-
-    stats0 = env.get_stats(reset=True)
-    del stats0
-    marks = [torch.cuda.Event(enable_timing=True) for _ in range(reps + 1)]
+    env.get_stats(reset=True)
+    marks = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
     if distributed:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     marks[0].record()
-    for r in range(reps):         # R = reps x M regions of exactly K steps each, back to back: the stream never drains between them
-        run_replay()
-        marks[r + 1].record()
+    run_steps()
+    marks[1].record()
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     if distributed:
         dist.barrier()
-    region_ms = sorted(marks[r].elapsed_time(marks[r + 1]) / M for r in range(reps))
-    elapsed = region_ms[reps // 2] * 1e-3                    # median K-step region, seconds (device time on the launch stream)
-    spread = (region_ms[0] * 1e-3, region_ms[-1] * 1e-3)
+    elapsed = marks[0].elapsed_time(marks[1]) * 1e-3          # the K-step region, seconds (device time on the launch stream)
+    stats = env.get_stats()
+    assert stats["env_steps"] == n * K, (stats["env_steps"], n * K)   # exactly K launches over n envs were timed
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, rank, world)
     per_rank_us = [elapsed / K * 1e6]
     if distributed:
         mine = torch.tensor([elapsed], dtype=torch.float64, device=coll_device)
@@ -283,20 +320,18 @@ def main():
         devices = [None] * world
         dist.all_gather_object(devices, me)                 # (a few hundred bytes, once, outside every timed region)
         rccl_world = dist.get_world_size()
-    stats = env.get_stats()
-    assert stats["env_steps"] == n * K * R, (stats["env_steps"], n * K * R)   # exactly R x K launches over n envs were executed
     global_stats = stats
     if distributed:
         from reinforcement_learning_rendezvous_amd.sharding import reduce_stats
         global_stats = reduce_stats(stats, device=coll_device)      # one 96-byte all-gather
-        assert global_stats["env_steps"] == n * K * R * world
+        assert global_stats["env_steps"] == n * K * world
 
     # ---- under torch.distributed: the two gathers to rank 0, timed separately from the step (never inside `value`).
     #   per rollout: ONE message per rank per rdv_rollout launch (obs | actions | reward | log_prob | done | last_obs, written in place by
     #                the kernel: sharding.RolloutBufferGather) — the single-learner flow of main.py:114;
     #   per step   : ONE message per rank per rdv_step (obs | reward | done, written in place: sharding.RolloutGather.bind).
     gather_info = None
-    if distributed and not args.no_gather:
+    if distributed and args.full and not args.no_gather:
         from reinforcement_learning_rendezvous_amd.sharding import RolloutBufferGather, RolloutGather
         from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
         on_dev = coll_device.type == "cuda"
@@ -370,13 +405,11 @@ def main():
                                   + (f" ({pmc[key]['collected']})" if "collected" in pmc[key] else ""))
         out = {
             "metric": "env steps/sec", "value": total_steps / elapsed, "unit": "env steps/s", "n_gpus": world,
-            "steps": K, "warmup": W, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak",
+            "steps": K, "warmup": W, "settle_steps": settle_steps, "ms_per_step": elapsed / K * 1e3, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-            "repeats": R, "regions_per_graph_replay": M,
-            "region_ms": {"median": elapsed * 1e3, "min": spread[0] * 1e3, "max": spread[1] * 1e3,
-                                        "all_regions_wall_ms": wall * 1e3,
-                                        "note": "R regions of exactly K steps, back to back, each timed with HIP events on the launch stream; "
-                                                "value and ms_per_step are the median region (max over ranks)"},
+            "region_ms": {"device": elapsed * 1e3, "host_wall": wall * 1e3,
+                          "note": "one region of exactly K steps, timed with HIP events on the launch stream (max over ranks); "
+                                  "host_wall: the host clock around it on rank 0, synchronised at both ends"},
             "config": {"workload": f"BASELINE config 4 per-GPU shard / config 3 env count: {n} envs per GPU, "
                                    "U(-1,1) float32 actions resident in HBM, default env parameters, in-kernel auto-reset",
                        "envs_per_gpu": n, "global_envs": n * world, "state_storage": args.storage, "arithmetic": "f64",
@@ -423,7 +456,7 @@ def main():
 
     # ---- informational: the SB3-facing NumPy boundary (actions H2D, obs/reward/done D2H, infos) — PCIe-inclusive, never the bench value.
     # (Runs before the large legs below: after they have churned the allocators the same loop measures 1.7-1.9 ms per step instead of 1.3.)
-    if rank == 0 and world == 1 and not args.no_policy:
+    if rank == 0 and world == 1 and args.full and not args.no_policy:
         from reinforcement_learning_rendezvous_amd.vec_env import RendezvousVecEnv
         vec = RendezvousVecEnv(n, engine=env)
         a_np = [r_.cpu().numpy() for r_ in ring[:4]]
@@ -482,7 +515,7 @@ def main():
         env.reset()
 
     # ---- the same metric with fp64 state storage (parity mode), N=1 only
-    if rank == 0 and world == 1 and args.storage == "f32" and not args.only_large_n:
+    if rank == 0 and world == 1 and args.full and args.storage == "f32" and not args.only_large_n:
         try:
             e64 = RendezvousBatch(n, device=device, storage="f64", seed=0)
             e64.reset()
@@ -538,7 +571,7 @@ def main():
         return
 
     # ---- the same kernel family beyond the Infinity Cache: fused layout at 4,194,304 envs (N=1 only)
-    if rank == 0 and world == 1 and not args.no_large_n:
+    if rank == 0 and world == 1 and args.full and not args.no_large_n:
         try:
             out["large_n"] = large_leg(4194304, 5, 16, 7, 99, 2)
             out["large_n"]["note"] = ("1.2 GB of state + I/O per launch: HBM, not Infinity Cache; value / launch_us / frac = the MEDIAN of five fresh "
@@ -549,7 +582,7 @@ def main():
             out["large_n"] = {"error": repr(exc)}
 
     # ---- informational: BASELINE config 4's GLOBAL batch (524,288 envs = 8 shards of 65,536) stepped by ONE GPU (fused kernel)
-    if rank == 0 and world == 1 and not args.no_large_n:
+    if rank == 0 and world == 1 and args.full and not args.no_large_n:
         try:
             out["config4_global_batch_on_one_gpu"] = large_leg(524288, 5, 64, 9, 77, 4)
             out["config4_global_batch_on_one_gpu"]["note"] = "154 MB of state + I/O per launch: within the 256 MiB Infinity Cache; median of five fresh allocations"
@@ -557,7 +590,7 @@ def main():
             out["config4_global_batch_on_one_gpu"] = {"error": repr(exc)}
 
     # ---- informational: the same open-loop workload as K steps per persistent launch (rdv_step_many) — NOT the headline shape
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         try:
             k_many = 64
             tape = torch.stack([ring[t % RING] for t in range(k_many)]).contiguous()
@@ -584,7 +617,7 @@ def main():
 
     # ---- informational: BASELINE config 1 — ONE env, 1000 steps, driven through the reference's own Gym object surface
     #      (RendezvousEnv: reset() / step(a) -> obs, rew, done, info, reset on done), every step a launch + host round trips
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         try:
             import numpy as np
             from reinforcement_learning_rendezvous_amd.gym_env import RendezvousEnv
@@ -610,7 +643,7 @@ def main():
             out["config1_single_env_gym_object"] = {"error": repr(exc)}
 
     # ---- informational: MLP-policy rollout (config 3), N=1 only
-    if rank == 0 and world == 1 and not args.no_policy:
+    if rank == 0 and world == 1 and args.full and not args.no_policy:
         from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
         npz = os.path.join(ROOT, "tests", "golden", "mlp_policy.npz")
         pol = (MlpPolicy.from_npz(npz) if os.path.exists(npz) else MlpPolicy()).to(device)
@@ -685,7 +718,7 @@ def main():
         out["policy_rollout"]["value"] = max(v for k_, v in out["policy_rollout"].items() if isinstance(v, float))
         pol.close()
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(n, args.cpu_seconds)
 
     if rank == 0:

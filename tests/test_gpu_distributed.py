@@ -102,7 +102,7 @@ def _result_line(stdout):
 @pytest.mark.gpu
 def test_bench_under_a_launcher_single_rank_nccl():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl", "--quick",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "1", "--backend", "nccl", "--full", "--quick",
            "--steps", "20", "--warmup", "5", "--gather-steps", "8"]
     env = {k: v for k, v in _env().items() if k != "HSA_ENABLE_IPC_MODE_LEGACY"}      # as a foreign launcher would start the ranks
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
@@ -127,7 +127,7 @@ def test_bench_under_a_launcher_single_rank_nccl():
 def test_bench_starts_its_own_ranks_from_a_plain_invocation():
     """`python bench.py --gpus 2` with no launcher: the ranks are a child torchrun (rehearsed here with both ranks on the one GPU and
     gloo collectives: the line says so itself and is not a multi-GPU measurement)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shared-gpu", "--backend", "gloo", "--steps", "20",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--shared-gpu", "--backend", "gloo", "--full", "--steps", "20",
            "--warmup", "5", "--gather-steps", "4"]
     env = {k: v for k, v in _env().items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
