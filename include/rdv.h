@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define RDV_ABI_VERSION 4
+#define RDV_ABI_VERSION 5
 #define RDV_OBS_DIM 17    /* rendezvous_env.py:133-137 */
 #define RDV_ACT_DIM 6     /* rendezvous_env.py:140-144 */
 #define RDV_STATE_DIM 20  /* rc3 vc3 qc4 wc3 qt4 wt3, the column order of results/data_monte_carlo_initial_conditions.csv */
@@ -175,6 +175,12 @@ int         rdv_device_error_code(uint32_t device_error_word);
  * detects a fault does — so that the host side of the contract (which calls read the word, which refuse afterwards) can be exercised
  * on hardware without provoking a real fault. */
 int         rdv_debug_set_device_error(rdv_handle h, uint32_t bits, void* stream);
+/* Test hook (ABI 5): the name of the step kernel that the last rdv_step, rdv_step_many or rdv_rollout on the handle launched, spelled
+ * as its instantiation, e.g. "step_kernel_split<float, true>", "step_kernel<double, true>" (the evaluator build),
+ * "step_kernel<float, false, false, true>" (the first step after rdv_set_state / rdv_restore), "step_kernel_parts<double, false>",
+ * "step_kernel_tiles<float>", "step_many_kernel<float, false>", "rollout_kernel<double, false>"; "" before the first.  Recorded on
+ * the host at the launch site: no device work, no synchronisation.  NULL for an invalid handle.  Static storage: do not free. */
+const char* rdv_debug_last_kernel(rdv_handle h);
 
 /* Reference ctor defaults (rendezvous_env.py:52-126, :313). Host-only, needs no GPU. */
 int rdv_params_default(RdvParams* out_host);
@@ -278,8 +284,9 @@ int rdv_get_aux(rdv_handle h, double* aux_out, void* stream);
  * handles of the same n_envs and storage: a snapshot starts with a 64-byte header (magic, version, n_envs, storage, payload bytes)
  * that rdv_restore reads back and checks against the handle and against `src_bytes`, the size of the caller's buffer, before
  * anything is overwritten (this synchronises `stream`).  Parameters, seed and rigid bodies are not part of it.  The halted flags of
- * a snapshot mean something to handles created with RDV_ON_DONE_HALT only: the step kernels of the other two modes never halt an env
- * and do not test the flag (an env restored as halted steps on there). */
+ * a snapshot mean something to handles created with RDV_ON_DONE_HALT only: restoring into a RESET or CONTINUE handle clears them, so
+ * that an env restored as halted steps on there, whichever kernel steps it (rdv_step in any variant, with or without diag / eval,
+ * rdv_step_many, rdv_rollout). */
 int64_t rdv_snapshot_bytes(rdv_handle h);
 int rdv_snapshot(rdv_handle h, void* dst, void* stream);
 int rdv_restore(rdv_handle h, const void* src, int64_t src_bytes, void* stream);

@@ -385,6 +385,15 @@ class RendezvousBatch:
                     torque=np.array(b.torque_chaser), torque_target=np.array(b.torque_target), rtol=b.rtol, atol=b.atol,
                     integrator={v: k for k, v in N.INTEGRATORS.items()}[b.integrator])
 
+    @property
+    def last_kernel(self):
+        """Name of the step kernel the last ``step`` / ``step_many`` / ``rollout`` launched (e.g. ``"step_kernel_split<float, true>"``),
+        "" before the first: which layout really ran, for tests (host-side record, no synchronisation)."""
+        name = self._lib.rdv_debug_last_kernel(self._h)
+        if name is None:
+            N.check(-5)           # RDV_ERR_BAD_HANDLE
+        return name.decode()
+
     def set_kernel_variant(self, variant):
         """Change the step kernel layout (``__init__``'s ``variant``); results do not depend on it.  ``clone()`` carries it over."""
         N.check(self._lib.rdv_set_kernel_variant(self._h, _VARIANT[variant]))

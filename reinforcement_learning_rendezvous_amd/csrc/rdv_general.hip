@@ -106,15 +106,16 @@ __global__ __launch_bounds__(kGenBlock) void step_kernel_general(void* ws_hot, c
   }
 }
 
-void launch_step_general(bool f32, bool diag, bool partner_waves, int64_t n, dim3 fused_grid, hipStream_t s, const DevParams* dev_params, const StepArgs& A) {
-#define RDV_LAUNCH_G(KERNEL, GRID, BLOCK) hipLaunchKernelGGL((KERNEL), GRID, BLOCK, 0, s, A.ws, A.actions, dev_params, A.n, A.stats, A.obs, A.reward, A)
+const char* launch_step_general(bool f32, bool diag, bool partner_waves, int64_t n, dim3 fused_grid, hipStream_t s, const DevParams* dev_params, const StepArgs& A) {
+#define RDV_LAUNCH_G(GRID, BLOCK, ...) do { hipLaunchKernelGGL((__VA_ARGS__), GRID, BLOCK, 0, s, A.ws, A.actions, dev_params, A.n, A.stats, A.obs, A.reward, A); \
+                                             return #__VA_ARGS__; } while (0)
   if (partner_waves && !diag) {
     const dim3 grid((unsigned)((n + kGenEnvs - 1) / kGenEnvs));
-    if (f32) RDV_LAUNCH_G(step_kernel_general<float>, grid, dim3(kGenBlock)); else RDV_LAUNCH_G(step_kernel_general<double>, grid, dim3(kGenBlock));
+    if (f32) RDV_LAUNCH_G(grid, dim3(kGenBlock), step_kernel_general<float>); else RDV_LAUNCH_G(grid, dim3(kGenBlock), step_kernel_general<double>);
   } else {
     const dim3 block(kBlock);
-    if (f32) { if (diag) RDV_LAUNCH_G((step_kernel<float, true, true>), fused_grid, block); else RDV_LAUNCH_G((step_kernel<float, false, true>), fused_grid, block); }
-    else { if (diag) RDV_LAUNCH_G((step_kernel<double, true, true>), fused_grid, block); else RDV_LAUNCH_G((step_kernel<double, false, true>), fused_grid, block); }
+    if (f32) { if (diag) RDV_LAUNCH_G(fused_grid, block, step_kernel<float, true, true>); else RDV_LAUNCH_G(fused_grid, block, step_kernel<float, false, true>); }
+    else { if (diag) RDV_LAUNCH_G(fused_grid, block, step_kernel<double, true, true>); else RDV_LAUNCH_G(fused_grid, block, step_kernel<double, false, true>); }
   }
 #undef RDV_LAUNCH_G
 }

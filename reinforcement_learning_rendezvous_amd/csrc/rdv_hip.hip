@@ -398,7 +398,7 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const DevParams* __restri
   refill_whole<ST>(A, P, i, counter + 1u);
 }
 
-enum { ACC_SET_STATE = 0, ACC_GET_STATE, ACC_GET_AUX, ACC_OBSERVE, ACC_DIAGNOSE, ACC_EVAL_BEGIN };
+enum { ACC_SET_STATE = 0, ACC_GET_STATE, ACC_GET_AUX, ACC_OBSERVE, ACC_DIAGNOSE, ACC_EVAL_BEGIN, ACC_CLEAR_HALTED };
 
 // state access / evaluator helpers (cold paths; one lane per env, row-major host-facing arrays)
 template <typename ST>
@@ -432,6 +432,9 @@ __global__ __launch_bounds__(kBlock) void access_kernel(const DevParams P, void*
     Derived d;
     derive<false>(P, e, d);
     diagnostics(P, e, d, out + i * RDV_DIAG_DIM);
+  } else if (what == ACC_CLEAR_HALTED) {   // rdv_restore into a RESET / CONTINUE handle: a halted flag of the snapshot is dropped
+    e.flags &= ~FLAG_HALTED;
+    store_env<ST>(ws, cs, i, e, true);
   } else {            // ACC_EVAL_BEGIN: the accumulators' k = 0 entries, from the state as it stands (after reset / set_state)
     Derived d;
     derive<false>(P, e, d);
@@ -664,6 +667,7 @@ struct RdvEnvBatch {
   RdvRigidBody body; // rdv_set_rigid_body
   bool general;      // step with the RK45 kernels (body is not isotropic / torque-free, or RK45 was asked for)
   bool raw_state;    // rdv_set_state since the last step: quaternions may be unnormalised (next step: kRaw kernel)
+  const char* last_kernel;  // name of the step kernel the last rdv_step / rdv_step_many / rdv_rollout launched (rdv_debug_last_kernel)
   void* prep;        // prepared next-episode states (rdv_slots.h): records, tags
   uint32_t* prep_tag;
   double* eval_partial;   // per-wave partial sums of rdv_eval_summary
@@ -735,6 +739,11 @@ int rdv_debug_set_device_error(rdv_handle h, uint32_t bits, void* stream) {
   hipLaunchKernelGGL(device_error_kernel, dim3(1), dim3(kWave), 0, static_cast<hipStream_t>(stream), h->dev_error, bits);
   RDV_HIP(hipGetLastError());
   return RDV_OK;
+}
+
+const char* rdv_debug_last_kernel(rdv_handle h) {
+  if (!h || h->magic != kMagic) { fail(RDV_ERR_BAD_HANDLE, "invalid rdv_handle"); return nullptr; }
+  return h->last_kernel;
 }
 
 int rdv_params_default(RdvParams* p) {
@@ -990,6 +999,7 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   const bool f32 = h->storage == RDV_STORAGE_F32;
   if (f32) hipLaunchKernelGGL((rollout_kernel<float, false>), grid, block, roll_lds_bytes<float>(), s, h->dev_params, p->weights, A);
   else hipLaunchKernelGGL((rollout_kernel<double, false>), grid, block, roll_lds_bytes<double>(), s, h->dev_params, p->weights, A);
+  h->last_kernel = f32 ? "rollout_kernel<float, false>" : "rollout_kernel<double, false>";
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }
@@ -1012,6 +1022,7 @@ int rdv_create(const RdvParams* params, int64_t n_envs, int device, int storage,
   h->magic = kMagic; h->params = *params; derive_params(*params, h->dev);
   (void)rdv_rigid_body_default(&h->body); h->general = false; apply_rigid_body(h);
   h->raw_state = false;
+  h->last_kernel = "";
 
   h->n = n_envs; h->cs = chunk_stride(n_envs, storage); h->device = device; h->storage = storage; h->on_done = on_done; h->seed = seed; h->env_id_offset = env_id_offset;
   h->tape = nullptr; h->tape_depth = 0; h->fresh = true; h->variant = RDV_VARIANT_AUTO;
@@ -1246,14 +1257,16 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
   const bool raw = h->raw_state && !h->general;   // (the RK45 kernels integrate the quaternion as given, like the reference)
   h->raw_state = false;
   const bool split = !A.diag && !A.eval && !h->general && !raw && (h->variant == RDV_VARIANT_SPLIT || (h->variant == RDV_VARIANT_AUTO && h->n <= kSplitAutoMaxEnvs));
-#define RDV_LAUNCH(KERNEL, GRID, BLOCK) hipLaunchKernelGGL((KERNEL), GRID, BLOCK, 0, s, A.ws, A.actions, h->dev_params, A.n, A.stats, A.obs, A.reward, A)
+  // every launch records the kernel's name, as spelled here, on the handle (host only: rdv_debug_last_kernel)
+#define RDV_LAUNCH(GRID, BLOCK, ...) do { hipLaunchKernelGGL((__VA_ARGS__), GRID, BLOCK, 0, s, A.ws, A.actions, h->dev_params, A.n, A.stats, A.obs, A.reward, A); \
+                                           h->last_kernel = #__VA_ARGS__; } while (0)
   const bool f32 = h->storage == RDV_STORAGE_F32, dg = A.diag != nullptr || A.eval != nullptr;   // either one: the evaluator build
   if (split) {
     const dim3 grid((unsigned)((h->n + kSplitEnvs - 1) / kSplitEnvs));
     const dim3 block(kSplitBlock);
     const bool all = h->on_done != RDV_ON_DONE_HALT;   // no halted envs: every lane runs the transition, the inputs travel together (advance_all)
-    if (f32) { if (all) RDV_LAUNCH((step_kernel_split<float, true>), grid, block); else RDV_LAUNCH((step_kernel_split<float, false>), grid, block); }
-    else { if (all) RDV_LAUNCH((step_kernel_split<double, true>), grid, block); else RDV_LAUNCH((step_kernel_split<double, false>), grid, block); }
+    if (f32) { if (all) RDV_LAUNCH(grid, block, step_kernel_split<float, true>); else RDV_LAUNCH(grid, block, step_kernel_split<float, false>); }
+    else { if (all) RDV_LAUNCH(grid, block, step_kernel_split<double, true>); else RDV_LAUNCH(grid, block, step_kernel_split<double, false>); }
   } else {
     dim3 grid = grid_for(h->n), block(kBlock);
     { static const int forced = [] { const char* x = getenv("RDV_STREAM_ROWS"); return x ? atoi(x) : -1; }();   // diagnostics
@@ -1267,10 +1280,10 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
     if (h->general) {
       // rdv_general.hip: a general TARGET is integrated on partner waves beside the chaser half of the transition (step_kernel_general);
       // the evaluator build, and a general chaser beside the reference's target, run the fused per-lane form
-      launch_step_general(f32, dg, h->dev.body_general[1] != 0 && h->split_general != 0, h->n, grid, s, h->dev_params, A);
+      h->last_kernel = launch_step_general(f32, dg, h->dev.body_general[1] != 0 && h->split_general != 0, h->n, grid, s, h->dev_params, A);
     } else if (raw) {
-      if (f32) { if (dg) RDV_LAUNCH((step_kernel<float, true, false, true>), grid, block); else RDV_LAUNCH((step_kernel<float, false, false, true>), grid, block); }
-      else { if (dg) RDV_LAUNCH((step_kernel<double, true, false, true>), grid, block); else RDV_LAUNCH((step_kernel<double, false, false, true>), grid, block); }
+      if (f32) { if (dg) RDV_LAUNCH(grid, block, step_kernel<float, true, false, true>); else RDV_LAUNCH(grid, block, step_kernel<float, false, false, true>); }
+      else { if (dg) RDV_LAUNCH(grid, block, step_kernel<double, true, false, true>); else RDV_LAUNCH(grid, block, step_kernel<double, false, false, true>); }
     } else if (!dg && h->variant != RDV_VARIANT_FUSED_INLANE) {
       const bool tiles = h->variant == RDV_VARIANT_FUSED_TILES && h->on_done != RDV_ON_DONE_HALT && h->tape_depth == 0;   // (halted envs skip the transition, a reset tape is a test device: step_kernel_parts)
       if (tiles) {
@@ -1279,15 +1292,15 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
         const unsigned need = A.xcd_per ? (unsigned)A.xcd_per * 8u : grid.x;
         if (g > need) g = need;
         grid = dim3(g);
-        launch_step_tiles(f32, grid, s, h->dev_params, A);
+        h->last_kernel = launch_step_tiles(f32, grid, s, h->dev_params, A);
       } else {
         const bool all = h->on_done != RDV_ON_DONE_HALT;   // (see the split branch)
-        if (f32) { if (all) RDV_LAUNCH((step_kernel_parts<float, true>), grid, block); else RDV_LAUNCH((step_kernel_parts<float, false>), grid, block); }
-        else { if (all) RDV_LAUNCH((step_kernel_parts<double, true>), grid, block); else RDV_LAUNCH((step_kernel_parts<double, false>), grid, block); }
+        if (f32) { if (all) RDV_LAUNCH(grid, block, step_kernel_parts<float, true>); else RDV_LAUNCH(grid, block, step_kernel_parts<float, false>); }
+        else { if (all) RDV_LAUNCH(grid, block, step_kernel_parts<double, true>); else RDV_LAUNCH(grid, block, step_kernel_parts<double, false>); }
       }
     } else {
-      if (f32) { if (dg) RDV_LAUNCH((step_kernel<float, true>), grid, block); else RDV_LAUNCH((step_kernel<float, false>), grid, block); }
-      else { if (dg) RDV_LAUNCH((step_kernel<double, true>), grid, block); else RDV_LAUNCH((step_kernel<double, false>), grid, block); }
+      if (f32) { if (dg) RDV_LAUNCH(grid, block, step_kernel<float, true>); else RDV_LAUNCH(grid, block, step_kernel<float, false>); }
+      else { if (dg) RDV_LAUNCH(grid, block, step_kernel<double, true>); else RDV_LAUNCH(grid, block, step_kernel<double, false>); }
     }
   }
 #undef RDV_LAUNCH
@@ -1338,6 +1351,7 @@ int rdv_step_many(rdv_handle h, const float* actions, int32_t n_steps, const Rdv
   const bool f32 = h->storage == RDV_STORAGE_F32;
   if (f32) hipLaunchKernelGGL((step_many_kernel<float, false>), grid, block, many_lds_bytes<float>(), s, h->dev_params, A);
   else hipLaunchKernelGGL((step_many_kernel<double, false>), grid, block, many_lds_bytes<double>(), s, h->dev_params, A);
+  h->last_kernel = f32 ? "step_many_kernel<float, false>" : "step_many_kernel<double, false>";
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }
@@ -1418,6 +1432,9 @@ int rdv_restore(rdv_handle h, const void* src, int64_t src_bytes, void* stream) 
     return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_restore: the buffer holds %lld bytes, the snapshot needs %lld", (long long)src_bytes,
                 (long long)(sizeof(SnapshotHeader) + snapshot_payload(h)));
   RDV_HIP(hipMemcpyAsync(h->ws, static_cast<const char*>(src) + sizeof(SnapshotHeader), (size_t)hd.payload_bytes, hipMemcpyDeviceToDevice, s));
+  // the halted flags of the snapshot mean something to a HALT handle only: elsewhere every kernel steps the env on (include/rdv.h)
+  if (h->on_done != RDV_ON_DONE_HALT)
+    if (int rc = access(h, ACC_CLEAR_HALTED, nullptr, nullptr, nullptr, stream)) return rc;
   h->fresh = false;
   h->raw_state = true;      // the snapshot may have been taken right after rdv_set_state
   h->prepared_ok = false;   // the episode counters changed: the slots are re-derived before the next launch that uses them

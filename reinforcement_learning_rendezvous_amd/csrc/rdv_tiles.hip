@@ -175,9 +175,10 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(S
 #endif
 }
 
-void launch_step_tiles(bool f32, dim3 grid, hipStream_t s, const DevParams* dev_params, const StepArgs& A) {
+const char* launch_step_tiles(bool f32, dim3 grid, hipStream_t s, const DevParams* dev_params, const StepArgs& A) {
   if (f32) hipLaunchKernelGGL(step_kernel_tiles<float>, grid, dim3(kBlock), 0, s, A.ws, A.actions, dev_params, A.n, A.stats, A.obs, A.reward, A);
   else hipLaunchKernelGGL(step_kernel_tiles<double>, grid, dim3(kBlock), 0, s, A.ws, A.actions, dev_params, A.n, A.stats, A.obs, A.reward, A);
+  return f32 ? "step_kernel_tiles<float>" : "step_kernel_tiles<double>";
 }
 
 }  // namespace rdv

@@ -42,3 +42,35 @@ def counter_actions(seed, step, n, lo=0):
         x = x ^ (x >> np.uint64(31))
         out[:, j] = ((x >> np.uint64(40)).astype(np.float64) * (2.0 / (1 << 24)) - 1.0).astype(np.float32)
     return out
+
+
+SPLIT_AUTO_MAX_ENVS = 65536      # include/rdv.h: AUTO runs SPLIT up to one 256-env workgroup per CU, FUSED above
+
+
+def expected_kernel(variant, n, storage, on_done, diag=False, tape=False, after_set_state=False):
+    """The step kernel rdv_step launches, from the dispatch rules as include/rdv.h documents them (not from the C++):
+      - the first step after rdv_set_state / rdv_restore: the kRaw instantiation of step_kernel (it renormalises the quaternions);
+      - diag or eval outputs: the evaluator build step_kernel<ST, true>, whatever the variant;
+      - AUTO: SPLIT up to 65,536 envs, FUSED above;
+      - SPLIT: step_kernel_split, FUSED: step_kernel_parts, both <ST, true> unless halt mode (<ST, false>: halted envs skip the step);
+      - FUSED_INLANE: step_kernel<ST, false>;
+      - FUSED_TILES: step_kernel_tiles<ST>, except with a reset tape or in halt mode, where it runs FUSED.
+    ``rdv_debug_last_kernel`` spells the names as the instantiations are written."""
+    st = "float" if storage in ("f32", 0) else "double"
+    if after_set_state:
+        return f"step_kernel<{st}, {'true' if diag else 'false'}, false, true>"
+    if diag:
+        return f"step_kernel<{st}, true>"
+    if variant == "auto":
+        variant = "split" if n <= SPLIT_AUTO_MAX_ENVS else "fused"
+    if variant == "fused_tiles" and (tape or on_done == "halt"):
+        variant = "fused"
+    every = "false" if on_done == "halt" else "true"
+    return {"split": f"step_kernel_split<{st}, {every}>", "fused": f"step_kernel_parts<{st}, {every}>",
+            "fused_inlane": f"step_kernel<{st}, false>", "fused_tiles": f"step_kernel_tiles<{st}>"}[variant]
+
+
+def persistent_kernel(which, storage):
+    """rdv_step_many / rdv_rollout (reference rigid bodies): one persistent kernel each."""
+    st = "float" if storage in ("f32", 0) else "double"
+    return f"{'step_many_kernel' if which == 'step_many' else 'rollout_kernel'}<{st}, false>"

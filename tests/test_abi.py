@@ -25,10 +25,13 @@ def _has_gpu():
         return False
 
 
-def test_library_is_built_and_loads():
+def test_library_is_built_and_loads_with_abi_5():
+    """ABI 5 added rdv_debug_last_kernel; the library, the header and the Python binding agree on the version."""
     N.build()
     assert os.path.exists(N.LIB_PATH)
-    assert N.lib().rdv_version() == 4
+    header = open(os.path.join(ROOT, "include", "rdv.h")).read()
+    assert int(re.search(r"#define RDV_ABI_VERSION (\d+)", header).group(1)) == 5
+    assert N.lib().rdv_version() == 5
 
 
 def test_every_declared_symbol_is_exported():

@@ -31,9 +31,11 @@ def test_monte_carlo_fp64_storage_reproduces_the_published_table():
     cols = [str(c) for c in pub["columns"]]
     tab = pub["table"]
     mism = {c: int((res[c] != tab[:, cols.index(c)]).sum()) for c in INT_COLS}
-    # the GPU evaluates the MLP with other GEMM kernels than torch-1.12-CPU did: actions differ in the last float32 bits,
-    # which can move a cosine across a 1e-5 rounding boundary (general.py:179) in a few of the 56,776 steps
-    assert all(v <= 3 for v in mism.values()), mism
+    # the GPU evaluates the MLP with other GEMM kernels than torch-1.12-CPU did: actions differ in the last float32 bits, which
+    # could move a cosine across a 1e-5 rounding boundary (general.py:179) in one of the 56,776 steps; observed on the MI355X:
+    # no row differs in any column
+    print("rows differing from the published table, per column:", mism)
+    assert all(v == 0 for v in mism.values()), f"rows differing from the published table, per column: {mism}"
     assert abs(int(res["succeeded"].sum()) - 545) <= 1 and abs(int(res["collided"].sum()) - 166) <= 1
     assert res["pos_error"].mean() == pytest.approx(0.4974, abs=2e-3)
     assert res["total_delta_v"].mean() == pytest.approx(2.1115, abs=1e-3)

@@ -14,7 +14,7 @@ import numpy as np
 import pytest
 
 import oracle
-from helpers import counter_actions, load_golden, params_from_note, to_oracle_params
+from helpers import counter_actions, expected_kernel, load_golden, params_from_note, to_oracle_params
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -31,10 +31,20 @@ def _np(t):
     return t.detach().cpu().numpy()
 
 
-@pytest.mark.parametrize("variant", ["fused", "split", "fused_inlane", "fused_tiles"])
-@pytest.mark.parametrize("name", SCENARIOS)
-def test_golden_transitions_fp64_storage(name, variant):
-    """HIP kernel (parity mode) vs the reference's own recorded transitions."""
+# Every variant runs the TRAINING path (no diag / eval outputs), so that it really launches its own kernel: a step with diag=True runs
+# the evaluator build step_kernel<ST, true> whatever the variant.  Each scenario and storage then has exactly one evaluator pass of
+# its own (the *_evaluator_build tests).  With a reset tape or in halt mode "fused_tiles" runs step_kernel_parts (include/rdv.h): those
+# cases assert that fallback through last_kernel.
+VARIANTS = ["fused", "split", "fused_inlane", "fused_tiles"]
+
+
+def _expect_kernel(env, variant, diag=False, tape=False, after_set_state=False, what=""):
+    want = expected_kernel(variant, env.num_envs, env._ctor["storage"], env._ctor["on_done"], diag=diag, tape=tape,
+                           after_set_state=after_set_state)
+    assert env.last_kernel == want, f"{what}: ran {env.last_kernel!r}, the dispatch rules say {want!r}"
+
+
+def _golden_run(name, variant, diag):
     g = load_golden(f"steps_{name}.npz")
     p, _ = params_from_note(g["env_kwargs_json"])
     T, E = g["actions"].shape[:2]
@@ -55,20 +65,27 @@ def test_golden_transitions_fp64_storage(name, variant):
         v = g["valid"][t].astype(bool)
         if not v.any():
             break
-        o, r, d = env.step(torch.from_numpy(g["actions"][t]).cuda(), diag=True)
+        o, r, d = env.step(torch.from_numpy(g["actions"][t]).cuda(), diag=diag)
+        _expect_kernel(env, variant, diag=diag, tape=not halt, after_set_state=halt and t == 0, what=f"step {t}")
         o, r, d = _np(o), _np(r), _np(d).astype(bool)
         gd = g["done"][t].astype(bool)
         np.testing.assert_array_equal(d[v], gd[v], err_msg=f"done, step {t}")
         np.testing.assert_array_equal(_np(env.done_reason)[v] & 7, g["reason"][t][v], err_msg=f"reason, step {t}")
         np.testing.assert_allclose(r[v], g["reward"][t][v].astype(np.float32), rtol=2e-7, atol=2e-7)
         np.testing.assert_allclose(o[v], g["obs_ret"][t][v], rtol=0, atol=1.2e-7, err_msg=f"obs, step {t}")
-        dg = _np(env.diag)
-        np.testing.assert_array_equal(dg[v][:, [4, 5, 7]], g["diag"][t][v][:, [4, 5, 7]], err_msg=f"flags, step {t}")
-        np.testing.assert_allclose(dg[v][:, [0, 1, 2, 3, 6]], g["diag"][t][v][:, [0, 1, 2, 3, 6]], rtol=0, atol=1e-9)
         keep = v if halt else (v & ~gd)          # after an auto-reset the terminal state is gone
+        fin = v & gd
+        # bit 4: the episode entered the KOZ (the latched flag), bit 5: it had a success step (the count of the terminal state)
+        flags = (g["diag"][t][:, 7] != 0) * 16 + (g["aux"][t][:, 3] > 0) * 32
+        np.testing.assert_array_equal(_np(env.done_reason)[fin] & 48, flags[fin], err_msg=f"reason flags, step {t}")
+        if diag:
+            dg, rows = _np(env.diag), v
+        else:                                    # the same numbers from the state as it stands (not done rows in reset mode)
+            dg, rows = _np(env.diagnose()), keep
+        np.testing.assert_array_equal(dg[rows][:, [4, 5, 7]], g["diag"][t][rows][:, [4, 5, 7]], err_msg=f"flags, step {t}")
+        np.testing.assert_allclose(dg[rows][:, [0, 1, 2, 3, 6]], g["diag"][t][rows][:, [0, 1, 2, 3, 6]], rtol=0, atol=1e-9)
         np.testing.assert_allclose(_np(env.get_state())[keep], g["state"][t][keep], rtol=0, atol=1e-10)
         np.testing.assert_allclose(_np(env.get_aux())[keep][:, :6], g["aux"][t][keep], rtol=0, atol=1e-10)
-        fin = v & gd
         np.testing.assert_allclose(_np(env.terminal_obs)[fin], g["obs_step"][t][fin], rtol=0, atol=1.2e-7)
         n_done += int(fin.sum())
     st = env.get_stats()
@@ -77,11 +94,21 @@ def test_golden_transitions_fp64_storage(name, variant):
     env.close()
 
 
-@pytest.mark.parametrize("variant", ["fused", "split", "fused_inlane", "fused_tiles"])
-@pytest.mark.parametrize("storage", ["f32", "f64"])
-@pytest.mark.parametrize("name", ["A_random", "C_variant", "D_stochastic"])
-def test_golden_actions_vs_oracle(name, storage, variant):
-    """Same tapes and action sequences, HIP vs oracle in the same storage precision (covers fp32 production mode)."""
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("name", SCENARIOS)
+def test_golden_transitions_fp64_storage(name, variant):
+    """HIP kernel (parity mode, training path) vs the reference's own recorded transitions.  B runs in halt mode from set_state:
+    its first step is the kRaw kernel, the rest the variant's own."""
+    _golden_run(name, variant, diag=False)
+
+
+@pytest.mark.parametrize("name", SCENARIOS)
+def test_golden_transitions_fp64_storage_evaluator_build(name):
+    """The evaluator build (diag outputs) vs the reference's recorded transitions and its evaluator helpers."""
+    _golden_run(name, "auto", diag=True)
+
+
+def _golden_vs_oracle(name, storage, variant):
     g = load_golden(f"steps_{name}.npz")
     p, op = params_from_note(g["env_kwargs_json"])
     T, E = g["actions"].shape[:2]
@@ -90,30 +117,47 @@ def test_golden_actions_vs_oracle(name, storage, variant):
     env.set_reset_tape(torch.from_numpy(tape))
     orc = oracle.OracleBatch(E, op, storage=oracle.STORAGE_F32 if storage == "f32" else oracle.STORAGE_F64, tape=tape)
     np.testing.assert_array_equal(_np(env.reset()), orc.reset())
-    _compare_run(env, orc, [g["actions"][t] for t in range(T)], storage)
+    return env, orc, [g["actions"][t] for t in range(T)]
 
 
-def _compare_run(env, orc, action_list, storage, check_every=1):
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("storage", ["f32", "f64"])
+@pytest.mark.parametrize("name", ["A_random", "C_variant", "D_stochastic"])
+def test_golden_actions_vs_oracle(name, storage, variant):
+    """Same tapes and action sequences, HIP (training path) vs oracle in the same storage precision (covers fp32 production mode)."""
+    env, orc, actions = _golden_vs_oracle(name, storage, variant)
+    _compare_run(env, orc, actions, storage, variant, tape=True)
+
+
+@pytest.mark.parametrize("storage", ["f32", "f64"])
+@pytest.mark.parametrize("name", ["A_random", "C_variant", "D_stochastic"])
+def test_golden_actions_vs_oracle_evaluator_build(name, storage):
+    env, orc, actions = _golden_vs_oracle(name, storage, "auto")
+    _compare_run_evaluator(env, orc, actions, storage)
+
+
+def _check_outputs(env, ref, o, r, d, t):
+    """What a step returns, against the oracle's step: exact where the reference compares, within the stated tolerances elsewhere."""
+    np.testing.assert_array_equal(_np(d), ref["done"], err_msg=f"done, step {t}")
+    np.testing.assert_array_equal(_np(env.done_reason), ref["done_reason"], err_msg=f"reason, step {t}")
+    np.testing.assert_allclose(_np(o), ref["obs"], rtol=0, atol=2.4e-7, err_msg=f"obs, step {t}")
+    np.testing.assert_allclose(_np(r), ref["reward"], rtol=2e-6, atol=2e-6, err_msg=f"reward, step {t}")
+    fin = ref["done"].astype(bool)
+    np.testing.assert_array_equal(_np(env.episode_length)[fin], ref["episode_length"][fin])
+    np.testing.assert_allclose(_np(env.episode_return)[fin], ref["episode_return"][fin], rtol=1e-5, atol=1e-5)
+    np.testing.assert_allclose(_np(env.terminal_obs)[fin], ref["terminal_obs"][fin], rtol=0, atol=2.4e-7)
+
+
+def _check_state(env, orc, storage, t):
     st_tol = 2.5e-7 if storage == "f32" else 1e-10     # relative to max(1,|x|): 2 float32 ulps
-    for t, a in enumerate(action_list):
-        o, r, d = env.step(torch.from_numpy(a).cuda(), diag=True)
-        ref = orc.step(a, want_diag=True)
-        np.testing.assert_array_equal(_np(d), ref["done"], err_msg=f"done, step {t}")
-        np.testing.assert_array_equal(_np(env.done_reason), ref["done_reason"], err_msg=f"reason, step {t}")
-        np.testing.assert_allclose(_np(o), ref["obs"], rtol=0, atol=2.4e-7, err_msg=f"obs, step {t}")
-        np.testing.assert_allclose(_np(r), ref["reward"], rtol=2e-6, atol=2e-6, err_msg=f"reward, step {t}")
-        fin = ref["done"].astype(bool)
-        np.testing.assert_array_equal(_np(env.episode_length)[fin], ref["episode_length"][fin])
-        np.testing.assert_allclose(_np(env.episode_return)[fin], ref["episode_return"][fin], rtol=1e-5, atol=1e-5)
-        np.testing.assert_allclose(_np(env.terminal_obs)[fin], ref["terminal_obs"][fin], rtol=0, atol=2.4e-7)
-        if t % check_every == 0:
-            dg = _np(env.diag)
-            np.testing.assert_array_equal(dg[:, [4, 5, 7]], ref["diag"][:, [4, 5, 7]], err_msg=f"flags, step {t}")
-            s_gpu, s_ref = _np(env.get_state()), orc.get_state()
-            np.testing.assert_allclose(s_gpu, s_ref, rtol=st_tol, atol=st_tol, err_msg=f"state, step {t}")
-            a_gpu, a_ref = _np(env.get_aux()), orc.get_aux()
-            np.testing.assert_array_equal(a_gpu[:, [0, 2, 3, 7]], a_ref[:, [0, 2, 3, 7]], err_msg=f"t/collided/success/episode, step {t}")
-            np.testing.assert_allclose(a_gpu[:, [1, 4, 5, 6]], a_ref[:, [1, 4, 5, 6]], rtol=1e-5, atol=1e-5)
+    s_gpu, s_ref = _np(env.get_state()), orc.get_state()
+    np.testing.assert_allclose(s_gpu, s_ref, rtol=st_tol, atol=st_tol, err_msg=f"state, step {t}")
+    a_gpu, a_ref = _np(env.get_aux()), orc.get_aux()
+    np.testing.assert_array_equal(a_gpu[:, [0, 2, 3, 7]], a_ref[:, [0, 2, 3, 7]], err_msg=f"t/collided/success/episode, step {t}")
+    np.testing.assert_allclose(a_gpu[:, [1, 4, 5, 6]], a_ref[:, [1, 4, 5, 6]], rtol=1e-5, atol=1e-5)
+
+
+def _check_stats(env, orc):
     sg, so = env.get_stats(), orc.get_stats()
     for k in ("env_steps", "episodes", "successes", "collisions", "reasons"):
         assert sg[k] == so[k], (k, sg[k], so[k])
@@ -121,33 +165,87 @@ def _compare_run(env, orc, action_list, storage, check_every=1):
         assert abs(sg[k] - so[k]) <= 1e-5 * max(1.0, abs(so[k])), (k, sg[k], so[k])
 
 
-@pytest.mark.parametrize("variant", ["fused", "split", "fused_inlane", "fused_tiles"])
-@pytest.mark.parametrize("storage", ["f32", "f64"])
-def test_config2_4096x512_random_actions_philox_resets(storage, variant):
-    """BASELINE config 2: 4096 envs x 512 steps, U(-1,1) actions keyed by (seed, step, env), in-kernel Philox resets."""
-    n, T = 4096, 512
+def _compare_run(env, orc, action_list, storage, variant, tape=False, check_every=1):
+    """Training path: steps without diag, so the variant's own kernel runs (asserted each step); the evaluator's flags and error
+    norms come from rdv_diagnose of the post-step state — every row in halt / continue mode, the rows that are not done in reset
+    mode (theirs was replaced by the next episode's)."""
+    reset_mode = env._ctor["on_done"] == "reset"
+    for t, a in enumerate(action_list):
+        o, r, d = env.step(torch.from_numpy(a).cuda())
+        _expect_kernel(env, variant, tape=tape, what=f"step {t}")
+        ref = orc.step(a)
+        _check_outputs(env, ref, o, r, d, t)
+        if t % check_every == 0:
+            rows = ~ref["done"].astype(bool) if reset_mode else np.ones(env.num_envs, bool)
+            dg, dr = _np(env.diagnose())[rows], orc.diagnose()[rows]
+            np.testing.assert_array_equal(dg[:, [4, 5, 7]], dr[:, [4, 5, 7]], err_msg=f"flags, step {t}")
+            np.testing.assert_allclose(dg[:, [0, 1, 2, 3, 6]], dr[:, [0, 1, 2, 3, 6]], rtol=1e-6, atol=1e-6, err_msg=f"errors, step {t}")
+            _check_state(env, orc, storage, t)
+    _check_stats(env, orc)
+
+
+def _compare_run_evaluator(env, orc, action_list, storage, check_every=1):
+    """Evaluator path: steps with diag, the evaluator build (asserted each step), its diag outputs against the oracle's."""
+    for t, a in enumerate(action_list):
+        o, r, d = env.step(torch.from_numpy(a).cuda(), diag=True)
+        _expect_kernel(env, "auto", diag=True, what=f"step {t}")
+        ref = orc.step(a, want_diag=True)
+        _check_outputs(env, ref, o, r, d, t)
+        if t % check_every == 0:
+            np.testing.assert_array_equal(_np(env.diag)[:, [4, 5, 7]], ref["diag"][:, [4, 5, 7]], err_msg=f"flags, step {t}")
+            _check_state(env, orc, storage, t)
+    _check_stats(env, orc)
+
+
+def _config2(storage, variant):
+    n = 4096
     env = _batch(n, storage=storage, seed=0, variant=variant)
     orc = oracle.OracleBatch(n, to_oracle_params(env.params), seed=0, n_threads=8,
                              storage=oracle.STORAGE_F32 if storage == "f32" else oracle.STORAGE_F64)
     np.testing.assert_array_equal(_np(env.reset()), orc.reset())
-    _compare_run(env, orc, [counter_actions(1, t, n) for t in range(T)], storage, check_every=16)
+    return env, orc, [counter_actions(1, t, n) for t in range(512)]
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+@pytest.mark.parametrize("storage", ["f32", "f64"])
+def test_config2_4096x512_random_actions_philox_resets(storage, variant):
+    """BASELINE config 2: 4096 envs x 512 steps, U(-1,1) actions keyed by (seed, step, env), in-kernel Philox resets, on the
+    variant's own kernel (the training path)."""
+    env, orc, actions = _config2(storage, variant)
+    _compare_run(env, orc, actions, storage, variant, check_every=16)
     assert env.get_stats()["episodes"] > 50_000     # ~5 % of envs end per step (bubble)
 
 
-@pytest.mark.parametrize("variant", ["fused", "split", "fused_inlane", "fused_tiles"])
-def test_ragged_sizes_and_masked_reset(variant):
-    """N not a multiple of the wave / block size, single env, and reset(mask)."""
+@pytest.mark.parametrize("storage", ["f32", "f64"])
+def test_config2_4096x512_random_actions_philox_resets_evaluator_build(storage):
+    env, orc, actions = _config2(storage, "auto")
+    _compare_run_evaluator(env, orc, actions, storage, check_every=16)
+    assert env.get_stats()["episodes"] > 50_000
+
+
+def _ragged(variant, diag):
     for n in (1, 63, 65, 129, 257, 1000):
         env = _batch(n, storage="f32", seed=11, variant=variant)
         orc = oracle.OracleBatch(n, to_oracle_params(env.params), seed=11, storage=oracle.STORAGE_F32)
         np.testing.assert_array_equal(_np(env.reset()), orc.reset())
-        _compare_run(env, orc, [counter_actions(5, t, n) for t in range(40)], "f32")
+        run = (lambda acts: _compare_run_evaluator(env, orc, acts, "f32")) if diag else (lambda acts: _compare_run(env, orc, acts, "f32", variant))
+        run([counter_actions(5, t, n) for t in range(40)])
         mask = (np.arange(n) % 3 == 0).astype(np.uint8)
         o_gpu = _np(env.reset(torch.from_numpy(mask)))
         o_ref = orc.reset(mask)
         np.testing.assert_allclose(o_gpu, o_ref, rtol=0, atol=2.4e-7)
-        _compare_run(env, orc, [counter_actions(6, t, n) for t in range(10)], "f32")
+        run([counter_actions(6, t, n) for t in range(10)])
         env.close()
+
+
+@pytest.mark.parametrize("variant", VARIANTS)
+def test_ragged_sizes_and_masked_reset(variant):
+    """N not a multiple of the wave / block size, single env, and reset(mask)."""
+    _ragged(variant, diag=False)
+
+
+def test_ragged_sizes_and_masked_reset_evaluator_build():
+    _ragged("auto", diag=True)
 
 
 def test_sharding_is_index_independent():
