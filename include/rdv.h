@@ -331,6 +331,24 @@ int64_t rdv_num_envs(rdv_handle h);
  * collect_rollouts / predict apply before every env.step.  Weights are HOST pointers in SB3's layout (nn.Linear [out, in]):
  * w1 [64,17], b1 [64], w2 [64,64], b2 [64], w3 [6,64], b3 [6], log_std [6].  obs [n,17] and actions [n,6] are device pointers.
  * Noise is Philox4x32-10 keyed by (seed, env_id_offset + i, counter): pass the step index as `counter`.
+ *
+ * The noise contract (what makes a run reproducible across shards, restarts and the two rollout forms; restated in NumPy by
+ * tests/policy_reference.py and checked value by value).  For row i let id = env_id_offset + i (64 bits).  The row draws two
+ * Philox4x32-10 blocks, h = 0 and h = 1, with
+ *     counter words (id_lo, id_hi, counter_lo, counter_hi * 2 + h)      key (seed_lo, seed_hi ^ 0x504F4C49)
+ * (lo / hi = low / high 32 bits; the key tweak keeps this stream apart from the reset stream of rdv_create's seed).  Each word w
+ * becomes u = ((w >> 8) + 0.5) / 2^24 in (0, 1); each word pair (w0, w1) and (w2, w3) of a block gives two standard normals by
+ * Box-Muller, (z0, z1) = sqrt(-2 ln u_first) * (cos, sin)(2 pi u_second).  Block 0 gives action components 0..3 (z0, z1 of its
+ * first pair, then of its second), block 1 components 4, 5 (its first pair; its second pair is not used).  The sample is
+ * mean + exp(log_std) * z, its log-density sum_c(-z_c^2 / 2 - log_std_c) - 3 ln(2 pi) is computed from z.  The kernel evaluates
+ * this in fp32 with fast logarithm / sine / cosine: a normal is within 2.5e-4 of the exact value of the same words (the maximum
+ * is at w >> 8 = 2^24 - 1, where the fp32 sum (w >> 8) + 0.5 rounds up, u becomes 1 and the pair is (0, 0) instead of 2^-12 (cos, sin)).
+ *
+ * Inputs: observations are clamped to [-63, 63] before the network (the fp16 range of the scaled operands; no effect inside the
+ * observation Box [-1, 1]; +-inf counts as +-63) — the one deviation from the PyTorch modules.  A NaN in a row makes that row's six
+ * actions (the critic: its value) NaN and changes no other row.  Weights must be finite; each layer's weights enter the matrix
+ * cores times 2^s, s the largest integer <= 10 with max|w| * 2^s < 2^15, so one very large weight costs the small weights of
+ * its layer significant bits (two fp16 terms of the scaled value).
  */
 typedef struct RdvPolicyNet* rdv_policy;
 int rdv_policy_create(const float* w1_host, const float* b1_host, const float* w2_host, const float* b2_host,
