@@ -14,11 +14,7 @@ namespace rdv {
 template <typename ST, bool kDiag, bool kGeneral = false, bool kRaw = false>
 __global__ __launch_bounds__(kBlock) void step_kernel(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
                                                        uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
-  // The seven arguments every wave needs first are top-level kernel parameters so that they can be preloaded into SGPRs
-  // at wave launch (-mllvm -amdgpu-kernarg-preload-count=16) instead of being fetched from the host-visible kernarg
-  // segment; the rest of the argument block is read later, off the critical path.
-  StepArgs A = A_rest;
-  A.ws = ws_hot; A.actions = actions_hot; A.n = n_hot; A.stats = stats_hot; A.obs = obs_hot; A.reward = reward_hot;
+  const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
   using V = typename Vec4<ST>::type;
   __shared__ __attribute__((aligned(16))) float lds[kBlock * RDV_OBS_DIM];   // 17,408 B: wave-private staging regions
   // The parameter block sits in device memory behind a top-level __restrict__ pointer: nothing the kernel stores can alias
@@ -55,7 +51,7 @@ __global__ __launch_bounds__(kBlock) void step_kernel(void* ws_hot, const float*
   if (fin) {
     if (A.on_done == RDV_ON_DONE_RESET) {
       // in-kernel auto-reset (SB3 DummyVecEnv semantics): the returned obs is the first obs of the next episode
-      const double* row = nullptr;
+      const double* row = nullptr;   // (tape_row_of, rdv_slots.h, without its opaque divisor, which would change this kernel's instruction stream)
       if (A.tape_depth > 0) row = A.tape + ((int64_t)(e.episode % (uint32_t)A.tape_depth) * n + i) * RDV_STATE_DIM;
       reset_env<ST>(P, e, A.seed, A.env_id_offset + (uint64_t)i, row);
       observation_to(P, e, my_row);

@@ -24,8 +24,7 @@ constexpr int kGenBlock = 512;
 template <typename ST>
 __global__ __launch_bounds__(kGenBlock) void step_kernel_general(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
                                                                  uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
-  StepArgs A = A_rest;
-  A.ws = ws_hot; A.actions = actions_hot; A.n = n_hot; A.stats = stats_hot; A.obs = obs_hot; A.reward = reward_hot;
+  const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
   using V = typename Vec4<ST>::type;
   __shared__ __attribute__((aligned(16))) float stage[kGenEnvs * RDV_OBS_DIM];   // observation rows
   __shared__ double handoff[7 * kGenEnvs];                                         // qt'[4], wt'[3] of every env, [component][env]

@@ -1,5 +1,18 @@
-// rdv_kernels.h — what the step kernels of rdv_hip.hip and rdv_tiles.hip share: the storage layout helpers (chunks <-> registers),
-// the kernel argument block, wave-level statistics, staged row I/O and the per-env output stores.  Device code only.
+// rdv_kernels.h — what the step kernels (rdv_step.h, rdv_fused.h, rdv_tiles.hip, rdv_general.hip) share: the storage layout helpers
+// (chunks <-> registers), the kernel argument block, wave-level statistics, staged row I/O and the per-env output stores.  Device code only.
+//
+// Data layout in HBM (per batch of N envs, storage type ST = float | double):
+//   7 "chunk" arrays of N x (4 x ST): chunk c of env i at ws[(c*N + i)], i.e. struct-of-arrays at 16-byte (float4)
+//   granularity, so that every wave64 load/store instruction moves one contiguous 1 KiB (16 B per lane):
+//     c0 = rc.x rc.y rc.z vc.x      c1 = vc.y vc.z wc.x wc.y      c2 = wc.z bubble sum_dv sum_dw
+//     c3 = qc.w qc.x qc.y qc.z      c4 = qt.w qt.x qt.y qt.z      c5 = ep_return k flags episode (ints bit-cast)
+//     c6 = wt.x wt.y wt.z -         (read-only during a step: written by reset/set_state only)
+//   + one 128-byte statistics slot per wavefront (no same-address atomics: each wave owns its slot; the host sums them).
+// The boundary tensors keep the SB3 layout (actions [N,6], obs [N,17] row-major float32); each wave stages its
+// 64 rows through a wave-private LDS region so that the global accesses are contiguous 8/16-byte-per-lane.
+//
+// One launch per timestep: rdv_step -> a step kernel fuses impulse, CW propagation, both attitude updates, the collision/success
+// latches, observation, termination, reward, episode statistics and the in-kernel auto-reset.
 #pragma once
 
 #include "rdv_device.h"
@@ -75,15 +88,8 @@ __device__ __forceinline__ void unpack_env(const typename Vec4<ST>::type* c, Env
 template <typename ST>
 __device__ __forceinline__ void load_env(const typename Vec4<ST>::type* __restrict__ ws, int64_t cs, int64_t i, Env& e) {
   using V = typename Vec4<ST>::type;
-  const V c0 = ws[0 * cs + i], c1 = ws[1 * cs + i], c2 = ws[2 * cs + i], c3 = ws[3 * cs + i], c4 = ws[4 * cs + i],
-          c5 = ws[5 * cs + i], c6 = ws[6 * cs + i];
-  e.rc[0] = c0.x; e.rc[1] = c0.y; e.rc[2] = c0.z; e.vc[0] = c0.w;
-  e.vc[1] = c1.x; e.vc[2] = c1.y; e.wc[0] = c1.z; e.wc[1] = c1.w;
-  e.wc[2] = c2.x; e.bubble = c2.y; e.sum_dv = c2.z; e.sum_dw = c2.w;
-  e.qc[0] = c3.x; e.qc[1] = c3.y; e.qc[2] = c3.z; e.qc[3] = c3.w;
-  e.qt[0] = c4.x; e.qt[1] = c4.y; e.qt[2] = c4.z; e.qt[3] = c4.w;
-  e.ep_ret = c5.x; e.k = (int32_t)s2u(c5.y); e.flags = s2u(c5.z); e.episode = s2u(c5.w);
-  e.wt[0] = c6.x; e.wt[1] = c6.y; e.wt[2] = c6.z;
+  const V c[kChunks] = {ws[0 * cs + i], ws[1 * cs + i], ws[2 * cs + i], ws[3 * cs + i], ws[4 * cs + i], ws[5 * cs + i], ws[6 * cs + i]};
+  unpack_env<ST>(c, e);
 }
 
 // registers -> the seven storage chunks of one env
@@ -137,6 +143,8 @@ __device__ __forceinline__ void store_env(typename Vec4<ST>::type* __restrict__ 
     stamp_[k] = __builtin_readcyclecounter();          \
     __builtin_amdgcn_sched_barrier(0);                 \
   } while (0)
+// a use of the loaded state: the stamped build waits for it here, in front of the stamp that follows
+#define RDV_STAMP_STATE(e) asm volatile("" : : "v"((e).rc[0]), "v"((e).vc[1]), "v"((e).wc[2]), "v"((e).qc[0]), "v"((e).qt[0]), "v"((e).ep_ret), "v"((e).wt[2]))
 #define RDV_STAMP_FLUSH(wave_id)                                                              \
   if (A.stamps && lane == 0) {                                                                \
     stamp_[9] = __builtin_amdgcn_s_memrealtime();                                           \
@@ -145,6 +153,7 @@ __device__ __forceinline__ void store_env(typename Vec4<ST>::type* __restrict__ 
 #else
 #define RDV_STAMP_DECL
 #define RDV_STAMP(k)
+#define RDV_STAMP_STATE(e)
 #define RDV_STAMP_FLUSH(wave_id)
 #endif
 
@@ -172,12 +181,31 @@ struct StepArgs {
   uint32_t* prep_tag;       // [N]
   int32_t xcd_per;          // fused kernels: workgroups per XCD region (0: plain block order)
   int32_t stream_rows;      // fused kernels: store the observation rows non-temporally (rdv_kernels.h: at every size since round 4)
-  int32_t stagger;          // step_kernel_parts: first-round workgroups start k x 2,048 cycles apart by their slot on the CU (0: off)
+  int32_t stagger;          // step_kernel_parts: first-round workgroups start k x 512 cycles apart by their slot on the CU (0: off)
 #ifdef RDV_STAMPS
   unsigned long long* stamps;
 #endif
 };
 
+// The seven arguments every wave of a step kernel needs first are top-level kernel parameters so that they can be preloaded into
+// SGPRs at wave launch (-mllvm -amdgpu-kernarg-preload-count=16) instead of being fetched from the host-visible kernarg segment; the
+// rest of the argument block is read later, off the critical path.  This puts them back into the block the kernel body works with.
+__device__ __forceinline__ StepArgs hot_args(const StepArgs& rest, void* ws, const float* actions, int64_t n, uint64_t* stats, float* obs,
+                                             float* reward) {
+  StepArgs A = rest;
+  A.ws = ws; A.actions = actions; A.n = n; A.stats = stats; A.obs = obs; A.reward = reward;
+  return A;
+}
+// one wave's slice of the per-env outputs: the lane is the index (null stays null)
+__device__ __forceinline__ StepArgs wave_outputs(const StepArgs& A, int64_t wave_base) {
+  StepArgs Aw = A;
+  Aw.reward = A.reward + wave_base; Aw.done = A.done + wave_base;
+  Aw.done_reason = A.done_reason ? A.done_reason + wave_base : nullptr;
+  Aw.terminal_obs = A.terminal_obs ? A.terminal_obs + wave_base * RDV_OBS_DIM : nullptr;
+  Aw.episode_return = A.episode_return ? A.episode_return + wave_base : nullptr;
+  Aw.episode_length = A.episode_length ? A.episode_length + wave_base : nullptr;
+  return Aw;
+}
 // LDS exchanged inside ONE wave (wave-private region): LDS operations of a wave execute in issue order, so only the
 // compiler has to be kept from moving the reads above the writes.
 __device__ __forceinline__ void wave_lds_fence() {
@@ -392,6 +420,28 @@ __device__ __forceinline__ void pinned_unpack(const PinnedInputs& in, Env& e) {
 #pragma unroll
   for (int j = 0; j < kChunks; ++j) c[j] = make_float4(in.c[j].x, in.c[j].y, in.c[j].z, in.c[j].w);
   unpack_env<float>(c, e);
+}
+
+// The protocol as the by-wave step kernels run it (step_kernel_parts, step_kernel_split; fp32 storage, no halted envs):
+//   pinned_state: the ten requests, the wait for the state, the state -> `e` (a wave without envs reads the batch's last wave and
+//     uses nothing);
+//   pinned_rest: the wait for the rest, action row -> `a`, statistics slot -> `slot_pre`.  The kernels hand it to advance_all as the
+//     hook that runs behind the chaser's rotation matrix.
+__device__ __forceinline__ void pinned_state(const StepArgs& A, int64_t wave_base, int lane, PinnedInputs& pin, Env& e) {
+  pinned_fetch(A, wave_base, lane, pin);
+  pinned_wait_state(pin);
+  pinned_unpack(pin, e);
+}
+__device__ __forceinline__ void pinned_rest(PinnedInputs& pin, double& after, float* a, uint64_t& slot_pre) {
+  pinned_wait_rest(pin, after);
+  a[0] = pin.a4.x; a[1] = pin.a4.y; a[2] = pin.a4.z; a[3] = pin.a4.w; a[4] = pin.a2.x; a[5] = pin.a2.y;
+  slot_pre = ((uint64_t)__float_as_uint(pin.sp.y) << 32) | __float_as_uint(pin.sp.x);
+}
+
+// an env whose episode ended under RDV_ON_DONE_HALT: flagged, in the registers and (fp32 storage) in the packed copy that is stored
+template <typename ST>
+__device__ __forceinline__ void halt_if_done(const StepArgs& A, bool fin, Env& e, typename Vec4<ST>::type* packed) {
+  if (fin && A.on_done == RDV_ON_DONE_HALT) { e.flags |= FLAG_HALTED; if (packed) packed[5].z = u2s(e.flags, ST(0)); }
 }
 
 // per-env outputs of a transition (coalesced 4-/1-byte stores; the sparse ones only where an episode ended).  `row`: the lane's

@@ -4,7 +4,7 @@
 // main.py:114 -> model.learn) for the shipped actor, writing the rows of its rollout buffer (observations, actions before
 // clipping, rewards, dones, log-probabilities) and the observation after the last step.
 //
-// Included by rdv_hip.hip after the step helpers.  Same arithmetic as rdv_policy_act + rdv_step called T times (the tests
+// Included by rdv_hip.hip after rdv_kernels.h, rdv_policy.h and rdv_slots.h.  Same arithmetic as rdv_policy_act + rdv_step called T times (the tests
 // require bit-identical observations, rewards, dones and final state); what changes is where the data lives between steps:
 //   - one 768-thread workgroup owns 256 envs for the whole rollout.  Waves 0-3 ("env waves", 64 envs each, one lane per env)
 //     keep the env state in registers from the first step to the last; waves 4-11 ("actor waves", 32 envs each) keep the

@@ -13,7 +13,7 @@
 // tag[i] == e.episode + 1 says that env i's slot in HBM holds reset(seed, id, counter = e.episode) (whose own episode field is
 // e.episode + 1); anything else is refilled before its first use.
 // Results are bit-identical to the in-lane reset (same expressions on the same inputs).
-// (The one-launch step kernels do NOT use slots: measured, round 2 — see step_kernel_split in rdv_hip.hip.)
+// (The one-launch step kernels do NOT use slots: measured, round 2 — see step_kernel_split in rdv_step.h.)
 #pragma once
 
 namespace rdv {
@@ -119,6 +119,7 @@ __device__ __forceinline__ void slot_copy(const SlotStore<ST>& D, int64_t di, co
   for (int v = 0; v < kSlotObsVecs; ++v) *D.ovec(v, di) = *S.ovec(v, si);
 }
 
+// the row of the reset tape [depth][N][20] that episode `counter` of env i starts from (null without a tape)
 __device__ __forceinline__ const double* tape_row_of(const double* tape, int32_t depth, int64_t n, int64_t i, uint32_t counter) {
   if (depth <= 0) return nullptr;
   // (the divisor passes through an empty asm: hoisted out of the callers' loops, the reciprocal of this test-only path's modulo cost a
@@ -135,6 +136,16 @@ __device__ __forceinline__ void reset_whole(const DevParams& P, Env& ne, float* 
   ne.episode = counter;
   reset_env<ST>(P, ne, seed, env_id, tape_row);     // ne.episode = counter + 1
   observation(P, ne, o);
+}
+
+// The whole reset of episode `counter` into env i's slot in HBM (one lane per env): prepare_kernel, reset_kernel.
+template <typename ST>
+__device__ __forceinline__ void refill_whole(const StepArgs& A, const DevParams& P, int64_t i, uint32_t counter) {
+  Env ne;
+  float o[RDV_OBS_DIM];
+  reset_whole<ST>(P, ne, o, A.seed, A.env_id_offset + (uint64_t)i, counter, tape_row_of(A.tape, A.tape_depth, A.n, i, counter));
+  slot_store_full<ST>(hbm_slot_store<ST>(A.prep), i, ne, o);
+  A.prep_tag[i] = counter + 1u;
 }
 
 // One PART of the slot of entry i (see ResetPart), written element-wise into the slot's chunks and observation vectors:

@@ -1,0 +1,310 @@
+// rdv_step.h — the one-launch step kernels that share the work of a reset inside the workgroup: step_kernel_parts (batches beyond one
+// workgroup per CU: the reset by part) and step_kernel_split (smaller batches: step waves beside service waves), and prepare_kernel,
+// which re-derives the slots of the persistent kernels after them.  Launched by rdv_step (rdv_hip.hip).  Device code only.
+#pragma once
+#include "rdv_kernels.h"
+#include "rdv_slots.h"
+
+namespace rdv {
+
+// Slots of all envs, re-derived from the envs' current episode indices: run before a persistent kernel (rdv_step_many, rdv_rollout)
+// whenever something outside them changed what a reset returns (parameters, tape, seed, restore) or advanced episodes without
+// them (rdv_step: its kernels compute resets in registers and do not touch the slots).
+template <typename ST>
+__global__ __launch_bounds__(kBlock) void prepare_kernel(const DevParams* __restrict__ Pp, const StepArgs A) {
+  using V = typename Vec4<ST>::type;
+  const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= A.n) return;
+  const V c5 = reinterpret_cast<const V*>(A.ws)[5 * A.cs + i];
+  refill_whole<ST>(A, *Pp, i, s2u(c5.w));
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Fused variant with the reset shared BY PART inside the workgroup (training build: no diagnostics, reference bodies, normalised
+// state).  Everything up to the reset is step_kernel; a lane whose episode ended lists its env in LDS instead of resetting it, and
+// after a workgroup barrier the four waves write the resets of the listed envs (~13 of 256 with random actions) together — wave w
+// does part w (rc+vc+bookkeeping | qc+wc | qt | wt: reset_fields<ST, kPart>) for all of them, ~13 active lanes, straight into the
+// envs' state chunks in HBM and their observation rows in LDS (LiveStore) — then a second barrier and the coalesced row stores.
+// The in-lane form runs the whole ~900-instruction reset with ~3 active lanes in 96 % of the waves: about half of that kernel's
+// vector instructions (SQ_INSTS_VALU 1,645 per wave, profiles/r02_sq_counters_4M.csv), and at three waves per SIMD they are not
+// hidden.  Here every wave issues one part (~150-350 instructions) and the four stay balanced — unlike the variant that left the
+// whole resets to the workgroup's last wave (profiles/r02_n_sweep_compacted_reset.csv), which held a wave slot and the LDS for a
+// lone serial chain.  Same expressions on the same inputs: bit-identical results.  (Forced to 128 VGPRs for four waves per SIMD it
+// spills 16 dwords and loses: 342 against 315 us at 4.2 M envs.)
+template <typename ST, bool kAll>   // kAll: on_done != HALT — every lane runs the transition (advance_all)
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 4 ? RDV_PARTS_WAVES : 3))) void step_kernel_parts(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
+                                                             uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+  const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
+  using V = typename Vec4<ST>::type;
+  __shared__ __attribute__((aligned(16))) float lds[kBlock * RDV_OBS_DIM];   // observation rows [256][17]; before that, per wave, the action rows
+  __shared__ uint32_t job_kind[kBlock];
+  __shared__ uint32_t job_counter[kBlock];
+  __shared__ uint16_t lists[kGroupWaves * kBlock];
+  static_assert(kBlock == kGroupEnvs, "refill_pass_lds is written for 256-env workgroups");
+  const DevParams& P = *Pp;
+  const int lane = threadIdx.x & (kWave - 1);
+  // Everything that is the same for the 64 lanes of a wave is computed on the scalar unit (readfirstlane tells the compiler that the wave
+  // index is uniform): the wave's first env, its row count, the bases of its slices of every array.  A lane then addresses memory as
+  // [uniform base in SGPRs] + [32-bit lane offset] — as 64-bit per-lane indices these held ~10 vector registers for the whole kernel.
+  const int wave_in_block = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  // XCD-aware block order: workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8); with A.xcd_per != 0 XCD x walks its own
+  // contiguous eighth of the envs in ascending order instead of every 8th workgroup of the whole batch (see kXcdOrderMaxEnvs)
+  const int64_t lblock = A.xcd_per ? (int64_t)(blockIdx.x & 7) * A.xcd_per + (blockIdx.x >> 3) : (int64_t)blockIdx.x;
+  const int64_t block_base = lblock * kBlock;
+  const int64_t wave_base = block_base + wave_in_block * kWave;
+  const int64_t n = A.n;
+  const int64_t rows = (n - wave_base) < kWave ? (n - wave_base) : kWave;    // valid envs of this wave (may be <= 0)
+  const bool active = lane < rows;
+  float* wl = lds + wave_in_block * (kWave * RDV_OBS_DIM);
+  V* ws = reinterpret_cast<V*>(A.ws);
+  const bool resets = A.on_done == RDV_ON_DONE_RESET;   // kernel-uniform: the barriers below are executed by all waves or by none
+  RDV_STAMP_DECL
+  RDV_STAMP(0);
+  // Staggered start (round 4): a launch of a few rounds of workgroups runs in lockstep — every resident wave loads at once (a 35 MB
+  // burst), then all compute, then the next round loads at once — so the memory system idles while the SIMDs work and vice versa.
+  // The first-round workgroups (the first 4 per CU) therefore start `stagger` x 512 cycles apart by their slot on the CU; their
+  // successors inherit the phase.  Pure delay, no effect on results; sized by kStagger* below (profiles/r04_stagger.txt).
+  if (A.stagger && blockIdx.x < 1024u) {
+    const int slot = (int)(blockIdx.x >> 8);             // the k-th workgroup of its CU (256 CUs, dealt round-robin)
+    for (int k = 0; k < slot * A.stagger; ++k) __builtin_amdgcn_s_sleep(8);   // 512 cycles each
+  }
+
+  {
+    V* wsw = ws + wave_base;                             // this wave's slice of every chunk array: chunk c of lane l at wsw[c * cs + l]
+    const StepArgs Aw = wave_outputs(A, wave_base);      // ... and of the per-env outputs
+    Env e;
+    uint64_t* slot = A.stats + (uint64_t)(wave_base / kWave) * kStatWords;
+    uint64_t slot_pre;
+    float a[RDV_ACT_DIM];
+    constexpr bool kPinned = kAll && sizeof(ST) == 4;
+    PinnedInputs pin;
+    if constexpr (kPinned) {
+      pinned_state(A, wave_base, lane, pin, e);          // state chunks, action row, statistics slot: all requested together (rdv_kernels.h: PinnedInputs)
+    } else if constexpr (kAll) {
+      TileInputs<ST> in;
+      tile_fetch<ST>(A, wave_base, lane, in);
+      unpack_env<ST>(in.c, e);
+      slot_pre = in.slot_pre;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { a[2 * k] = in.a[k].x; a[2 * k + 1] = in.a[k].y; }
+    } else {
+      if (active) load_env<ST>(wsw, A.cs, lane, e);
+      slot_pre = rows > 0 ? stats_preload(slot, lane) : 0ull;   // (a padding workgroup of the XCD order has no envs)
+      load_actions(A.actions + wave_base * RDV_ACT_DIM, 0, lane, active, a);
+    }
+    RDV_STAMP_STATE(e);
+    RDV_STAMP(1);
+    StepResult r;
+    const RowSink my_row{wl + lane * RDV_OBS_DIM};      // the observation is staged as it is formed
+    constexpr bool kPack = sizeof(ST) == 4;   // (see step_kernel_split)
+    V packed[kChunks];
+    bool stepped;
+    auto actions_ready = [&](double& after) { if constexpr (kPinned) pinned_rest(pin, after, a, slot_pre); };
+    if constexpr (kAll) { advance_all<ST>(P, e, a, r, my_row, kPack ? packed : nullptr, actions_ready); stepped = active; }
+    else stepped = advance<ST, false, false, false>(A, P, wave_base + lane, active, e, a, r, my_row, NoHook(), kPack ? packed : nullptr);
+    RDV_STAMP(2);
+    const bool fin = stepped && r.done;
+    stats_update(slot, slot_pre, lane, stepped, fin, r.reason, e.flags, e.k, e.ep_ret, e.sum_dv, e.sum_dw);
+    store_step_outputs<true>(Aw, lane, active, fin, r, e, my_row.row);
+    const bool to_reset = fin && resets;
+    halt_if_done<ST>(A, fin, e, kPack ? packed : nullptr);
+    if (resets) {
+      job_kind[threadIdx.x] = to_reset ? JOB_REFILL : JOB_NONE;
+      job_counter[threadIdx.x] = e.episode;
+    }
+    if (stepped && !to_reset) { if (kPack) store_chunks<ST>(wsw, A.cs, lane, packed, false); else store_env<ST>(wsw, A.cs, lane, e, false); }   // a listed env's state is written by the parts, all seven chunks
+  }
+  RDV_STAMP(3);
+  if (resets) {
+    __syncthreads();   // the workgroup's finished envs are listed, every observation row is staged
+    RDV_STAMP(4);
+    LiveStore<ST> L;
+    L.ws = ws; L.rows = lds; L.cs = A.cs; L.base = block_base;
+    refill_pass_lds<ST>(wave_in_block, lane, P, L, job_kind, job_counter, lists + wave_in_block * kBlock, block_base, n, A.seed,
+                        A.env_id_offset, A.tape, A.tape_depth);
+    RDV_STAMP(5);
+    __syncthreads();   // SB3 DummyVecEnv semantics: the rows of the listed envs now hold the first observation of the next episode
+  } else {
+    wave_lds_fence();
+  }
+  RDV_STAMP(6);
+  if (A.stream_rows) store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);   // kernel-uniform: see StepArgs::stream_rows
+  else store_obs_rows<false>(A.obs, wave_base, rows, lane, wl);
+  RDV_STAMP(7);
+  RDV_STAMP_FLUSH((uint64_t)blockIdx.x * (kBlock / kWave) + wave_in_block)
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Split-role variant for a chip that is NOT full (N <= ~98k envs: one transition wave per SIMD): a 512-thread workgroup owns 256
+// envs.  Waves 0-3 ("step waves") do the whole transition for their 64 envs exactly as the fused kernel does, except the in-lane
+// reset.  Waves 4-7 ("service waves") run beside them — an 8-wave workgroup places waves w and w+4 on the same SIMD, so every SIMD
+// holds one of each — and compute every env's NEXT initial state IN REGISTERS while the step runs (it depends only on seed, env id
+// and episode index).  After the single workgroup barrier a service lane whose env finished forms the observation of that state and
+// writes both straight to HBM; the step waves have nothing left to do.  Same arithmetic, same results as the fused variant.
+// The next-state work is done for every env and used by ~5 %.  Round 2 built the alternative the first review asked for — the next
+// state persisted in HBM per env (rdv_slots.h), copied where an episode ends and refilled once per episode by compacted passes —
+// for this kernel and for the fused one, and measured it (profiles/r02_*): 8.2 us per launch against 7.3 for this form at 65,536
+// envs, 437 us against 317 at 4 M envs.  At one wave per SIMD the launch is a latency chain (1.2 us until the inputs are in, 1.9 us of
+// transition, ~1 us of outputs, ~1.6 us of launch boundary: tools/ubench_stream.hip measures 4.0 us for the bare stream and
+// boundary); the service waves' arithmetic runs in issue slots that are idle anyway and their results are in registers at the
+// barrier, whereas a slot has to be fetched (a dependent, sparse access) exactly on that chain.  When the chip is full the step is
+// bound by memory latency and request rate (59 % of the wave-cycles parked on s_waitcnt, profiles/r02_sq_counters_4M.csv), and
+// slots add ~600 B of sparse traffic per reset where the in-lane reset adds none.  The slots stay where they do pay: in LDS, inside
+// the persistent kernels (rdv_step_many.h, rdv_rollout.h).  (Also measured: the service waves idle until the barrier and then write
+// the resets of the finished envs only, by part, as step_kernel_parts does, while the step waves do statistics and outputs — no
+// speculative work at all: 8.2 us against 7.8 at 65,536 envs, 6.7 against 5.8 at 16,384.  The part is serial work after the barrier;
+// the speculative reset costs nothing on the chain.  Wave priorities — s_setprio on the step waves, or on the service waves — change
+// nothing either: 7.81-7.85 us in every combination.)
+// The observation rows leave this kernel with non-temporal stores (store_obs_rows<true>): measured with tools/lib_ab.py, same box,
+// alternating child processes — 7.54 -> 7.13 us per launch at 65,536 envs, 6.24 -> 6.08 at 32,768; non-temporal LOADS of the actions
+// cost 0.4 us, non-temporal stores of reward / done / reason or of the state change nothing, and at 524,288 envs (fused kernel) streaming rows lose
+// 1 %.  With the actor kernel reading the rows in the next launch (rdv_policy_act + rdv_step per step) the pair is unchanged, 15.8 us.
+constexpr int kSplitEnvs = 256;      // envs per workgroup
+constexpr int kSplitBlock = 512;     // 8 waves
+
+// Round 3 measured three ways of shortening what stands in front of the barrier (all bit-identical, all SLOWER; code in commits
+// 794a540, 8ad2438 and 93382df, evidence under profiles/):
+//  - the speculative reset split over TWO service waves per step wave (12-wave workgroup, chaser half | target half in LDS): the
+//    halves' chains are shorter (5,356 and 6,436 cycles to the barrier against 6,596) and the launch takes 7.01 us against 6.78
+//    (profiles/r03_split_service_waves_stamps.txt).  What bounds the time to the barrier is not either wave's chain but the SIMD's
+//    vector issue: SQ_ACTIVE_INST_VALU has the step wave's ~940 and the service wave's ~900 instructions keep the VALU busy for nearly
+//    all of those cycles (profiles/r03_sq_counters_closed_loop.csv);
+//  - so the work itself would have to go: the step waves post, a quarter into the transition, which episodes CERTAINLY end (time limit,
+//    bubble) and the service waves reset only those, by part, beside the rest of the transition (step_kernel_hint): 7.99 us.  14 % of
+//    this workload's ends are attitude-error ends, known only after the chaser's attitude step — 83 % of the workgroups have one per
+//    step and pay a third barrier — and a dozen-lane by-part pass takes ~4,400 cycles beside the rest of the transition, not the
+//    ~1,200 its ~300 instructions suggest: its Philox blocks are quarter-rate integer multiplies on the same VALU the step wave is
+//    saturating (profiles/r03_split_hint_stamps.txt);
+//  - no reset arithmetic on the chain at all (step_kernel_slots, commit 93382df): prepared slots in HBM, requested by the ending lanes
+//    ~40 % into the transition (branch-free), copied at the end, refilled by part beside the NEXT launch's step; no barrier: 7.49 us.
+//    The step waves' transition is no faster beside nearly idle service waves (it is a dependency chain through the chaser side, not
+//    an issue count: removing the whole target side from it gains 0.17 us), and the slot copy is work they did not have before
+//    (profiles/r03_split_slots_hint.txt).
+template <typename ST, bool kAll>   // kAll: on_done != HALT — every lane of the step waves runs the transition (advance_all)
+__global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
+                                                       uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+  const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
+  using V = typename Vec4<ST>::type;
+  __shared__ __attribute__((aligned(16))) float stage[kSplitEnvs * RDV_OBS_DIM];   // observation rows
+  __shared__ unsigned long long fin_mask[kSplitEnvs / kWave];                        // per step wave: lanes to reset
+  const DevParams& P = *Pp;   // scalar loads: see step_kernel
+  const int lane = threadIdx.x & (kWave - 1);
+  const int wv = threadIdx.x >> 6;
+  const bool step_role = wv < kSplitEnvs / kWave;
+  const int slot_in_block = threadIdx.x & (kSplitEnvs - 1);          // both roles: the env this lane is responsible for
+  const int64_t i = (int64_t)blockIdx.x * kSplitEnvs + slot_in_block;
+  const int64_t wave_base = i - lane;
+  const int64_t n = A.n;
+  const bool active = i < n;
+  const int64_t rows = (n - wave_base) < kWave ? (n - wave_base) : kWave;
+  V* ws = reinterpret_cast<V*>(A.ws);
+  const bool resets = A.on_done == RDV_ON_DONE_RESET;
+  RDV_STAMP_DECL
+  RDV_STAMP(0);
+
+  if (step_role) {
+    // ------------------------------------------------------------------ step waves
+    __builtin_amdgcn_s_setprio(2);   // (the longer of the SIMD's two instruction streams first: 6.43 -> 6.41 us per launch; the service waves first: 7.03)
+    float* wl = stage + wv * (kWave * RDV_OBS_DIM);
+    Env e;
+    StepResult r;
+    uint64_t* slot = A.stats + (uint64_t)(wave_base / kWave) * kStatWords;
+    uint64_t slot_pre;
+    float a[RDV_ACT_DIM];
+    constexpr bool kPinned = kAll && sizeof(ST) == 4;
+    PinnedInputs pin;
+    if constexpr (kPinned) {
+      // state chunks, action row and statistics slot requested together (rdv_kernels.h: PinnedInputs); the state is waited for here, the
+      // action row behind the chaser's rotation matrix (actions_ready)
+      pinned_state(A, wave_base, lane, pin, e);
+    } else if constexpr (kAll) {
+      TileInputs<ST> in;
+      tile_fetch<ST>(A, wave_base, lane, in);
+      unpack_env<ST>(in.c, e);
+      slot_pre = in.slot_pre;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { a[2 * k] = in.a[k].x; a[2 * k + 1] = in.a[k].y; }
+    } else {
+      if (active) load_env<ST>(ws, A.cs, i, e);
+      slot_pre = stats_preload(slot, lane);
+      load_actions(A.actions, wave_base, lane, active, a);
+    }
+    RDV_STAMP_STATE(e);
+    RDV_STAMP(1);
+    // observation rows: own row -> LDS as it is formed (stride 17: conflict-free) -> contiguous stores.  If an env of this wave
+    // resets, the rows stay in LDS: the service wave swaps in the reset observation and stores the block — which is why this kernel
+    // also keeps the row in registers: after the barrier the LDS row may already hold the next episode's observation when the terminal
+    // one is stored (one wave per SIMD here: the 17 registers cost no occupancy).
+    float obs_r[RDV_OBS_DIM];
+    float* my_row = wl + lane * RDV_OBS_DIM;
+    constexpr bool kPack = sizeof(ST) == 4;   // fp32 storage: pack inside the stepped branch (advance()); fp64 storage has nothing to convert — there the
+    V packed[kChunks];                        // 56 extra registers of a packed copy cost 0.4 us per launch (8.75 -> 9.17 measured), so it stores from `e`
+    auto row_sink = [&](int j, float v) { obs_r[j] = v; my_row[j] = v; };
+    bool stepped;
+    auto actions_ready = [&](double& after) { if constexpr (kPinned) pinned_rest(pin, after, a, slot_pre); };
+    if constexpr (kAll) { advance_all<ST>(P, e, a, r, row_sink, kPack ? packed : nullptr, actions_ready); stepped = active; }
+    else stepped = advance<ST, false>(A, P, i, active, e, a, r, row_sink, NoHook(), kPack ? packed : nullptr);
+    RDV_STAMP(2);
+    const bool fin = stepped && r.done;
+    const bool to_reset = fin && resets;
+    const unsigned long long m_reset = __ballot(to_reset);
+    if (lane == 0) fin_mask[wv] = m_reset;
+    // The barrier comes HERE, as soon as the service waves have what they wait for (which envs ended, the observation rows), not at the
+    // end of the step wave: the statistics, the per-env outputs and the stores of the step wave (~1.1 us) then run beside the service
+    // waves' reset writes (~0.9 us) instead of in front of them (stamps: 5.7 -> ~5.0 us from the first wave's entry to the last exit).
+    // The state of the envs that go on is stored BEFORE the barrier (round 3): the step waves reach it ~700 cycles ahead of the service
+    // waves, and these 6 x 16-byte-per-lane stores drain inside that wait instead of after it (tools/lib_ab.py: 6.80 -> 6.73 us at
+    // 65,536 envs, 5.35 -> 5.29 at 16,384; moving the reward / done / terminal-row stores there as well loses: 6.89).  Reset lanes: service wave.
+    halt_if_done<ST>(A, fin, e, kPack ? packed : nullptr);
+    if (stepped && !to_reset) { if (kPack) store_chunks<ST, true>(ws, A.cs, i, packed, false); else store_env<ST>(ws, A.cs, i, e, false); }
+    RDV_STAMP(3);
+    __syncthreads();
+    RDV_STAMP(4);
+    stats_update(slot, slot_pre, lane, stepped, fin, r.reason, e.flags, e.k, e.ep_ret, e.sum_dv, e.sum_dw);
+    store_step_outputs<true>(A, i, active, fin, r, e, obs_r);
+    if (m_reset == 0ull) store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
+    RDV_STAMP(5);
+    RDV_STAMP(6);
+  } else {
+    // ------------------------------------------------------------------ service waves
+    // The observation and the storage packing of the next initial state are computed after the barrier, by the lanes that use them:
+    // since the action rows stopped travelling through LDS the service waves are the last to reach the barrier (stamps: ~7,100
+    // cycles after entry against ~5,800 for the step waves), and every instruction taken out of their path before it counts
+    // (tools/lib_ab.py: 6.88 -> 6.78 us per launch at 65,536 envs, 5.58 -> 5.36 at 16,384).  Deferring more — the target's rate, with
+    // its rotation matrix — overshoots: 7.05 us.
+    Env ne;
+    if (resets && active) {
+      const V c5 = ws[5 * A.cs + i];
+      ne.episode = s2u(c5.w);
+      RDV_STAMP(1);
+      const double* row = nullptr;   // (tape_row_of without its opaque divisor, which would change this wave's instruction stream)
+      if (A.tape_depth > 0) row = A.tape + ((int64_t)(ne.episode % (uint32_t)A.tape_depth) * n + i) * RDV_STATE_DIM;
+      reset_state<ST, false>(P, ne, A.seed, A.env_id_offset + (uint64_t)i, row);   // rounded to the storage type below, where a state is taken
+      reset_aux<ST>(P, ne);
+      RDV_STAMP(2);
+    }
+    RDV_STAMP(3);
+    __syncthreads();
+    RDV_STAMP(4);
+    const unsigned long long m_reset = fin_mask[wv - kSplitEnvs / kWave];
+    if (m_reset != 0ull) {   // wave-uniform: some env of the step wave we serve finished its episode
+      float* wl = stage + (wv - kSplitEnvs / kWave) * (kWave * RDV_OBS_DIM);
+      if (active && ((m_reset >> lane) & 1ull)) {
+        float robs[RDV_OBS_DIM];
+        canon_rest<ST>(ne);
+        observation(P, ne, robs);
+        store_env<ST, true>(ws, A.cs, i, ne, true);
+#pragma unroll
+        for (int j = 0; j < RDV_OBS_DIM; ++j) wl[lane * RDV_OBS_DIM + j] = robs[j];
+      }
+      wave_lds_fence();
+      RDV_STAMP(5);
+      store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
+    }
+    RDV_STAMP(6);
+  }
+  RDV_STAMP(7);
+  RDV_STAMP_FLUSH((uint64_t)blockIdx.x * 8 + wv)
+}
+
+}  // namespace rdv

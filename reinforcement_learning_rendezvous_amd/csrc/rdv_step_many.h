@@ -3,7 +3,7 @@
 // trips through HBM.  Not the closed loop (that is rdv_rollout, with the actor in the loop) and not the shape the headline
 // metric is quoted on (one launch per timestep, rdv_step); it shows what those boundaries cost.
 //
-// Included by rdv_hip.hip after the step helpers.  Same arithmetic as rdv_step (the tests require bit-identical outputs, state
+// Included by rdv_hip.hip after rdv_kernels.h and rdv_slots.h.  Same arithmetic as rdv_step (the tests require bit-identical outputs, state
 // and statistics).  A 512-thread workgroup owns 256 envs for all K steps:
 //   - waves 0-3 ("env waves", 64 envs each) keep the state in registers and do the transition; the actions of step t+1 are
 //     fetched into registers while step t computes.  A lane whose episode ends copies its prepared slot (rdv_slots.h) — the

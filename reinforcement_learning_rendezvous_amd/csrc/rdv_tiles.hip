@@ -36,8 +36,7 @@ __device__ __forceinline__ void tile_touch(TileInputs<ST>& in) {
 template <typename ST>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 4 ? RDV_TILES_WAVES : 2))) void step_kernel_tiles(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
                                                              uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
-  StepArgs A = A_rest;
-  A.ws = ws_hot; A.actions = actions_hot; A.n = n_hot; A.stats = stats_hot; A.obs = obs_hot; A.reward = reward_hot;
+  const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
   using V = typename Vec4<ST>::type;
   __shared__ __attribute__((aligned(16))) float lds[kBlock * RDV_OBS_DIM];   // observation rows [256][17]
   __shared__ uint32_t job_kind[kBlock];
@@ -111,12 +110,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(S
       };
 
       V* wsw = ws + wave_base;
-      StepArgs Aw = A;
-      Aw.reward = A.reward + wave_base; Aw.done = A.done + wave_base;
-      Aw.done_reason = A.done_reason ? A.done_reason + wave_base : nullptr;
-      Aw.terminal_obs = A.terminal_obs ? A.terminal_obs + wave_base * RDV_OBS_DIM : nullptr;
-      Aw.episode_return = A.episode_return ? A.episode_return + wave_base : nullptr;
-      Aw.episode_length = A.episode_length ? A.episode_length + wave_base : nullptr;
+      const StepArgs Aw = wave_outputs(A, wave_base);
       uint64_t* slot = A.stats + (uint64_t)(wave_base / kWave) * kStatWords;
       StepResult r;
       const RowSink my_row{wl + lane * RDV_OBS_DIM};

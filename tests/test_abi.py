@@ -218,3 +218,16 @@ def test_no_kernel_uses_scratch_and_the_fused_step_fits_four_waves_per_simd():
     # the RK45 kernels fit two waves per SIMD (<= 256 registers, nothing parked in AGPRs or scratch) and the tile loop three (<= 168)
     assert max(v for k, v in vgprs.items() if "step_kernel_general" in k or "step_kernelIfLb0ELb1" in k or "step_kernelIdLb0ELb1" in k) <= 256
     assert max(v for k, v in vgprs.items() if "step_kernel_tilesIf" in k) <= 168
+
+
+def test_the_stamped_diagnostic_build_compiles(tmp_path):
+    """-DRDV_STAMPS (tools/_build.py: the build behind tools/stamp_profile*.py and tools/rollout_stamps.py) compiles and links for all
+    three translation units with the Makefile's own flags, so the diagnostic path cannot break unnoticed beside the product build."""
+    csrc = os.path.join(os.path.dirname(N.__file__), "csrc")
+    out = tmp_path / "librdv_stamps.so"
+    r = subprocess.run(["make", "-C", csrc, "-j3", "EXTRA=-DRDV_STAMPS", f"OBJ={tmp_path}", f"OUT={out}"], capture_output=True, text=True, timeout=900)
+    assert r.returncode == 0, r.stderr[-2000:]
+    for unit in ("rdv_hip.o", "rdv_tiles.o", "rdv_general.o"):
+        assert (tmp_path / unit).exists(), unit
+    nm = subprocess.run(["nm", "-D", "--defined-only", str(out)], capture_output=True, text=True).stdout
+    assert " T rdv_debug_set_stamps" in nm and " T rdv_step" in nm

@@ -1,5 +1,5 @@
 """
-GPU tests (run with `-m gpu`) that pin the MFMA actor and critic (csrc/rdv_policy.h, packed by create_mlp in csrc/rdv_hip.hip)
+GPU tests (run with `-m gpu`) that pin the MFMA actor and critic (csrc/rdv_policy.h, packed by pack_policy_weights there)
 to the float64 NumPy reference of tests/policy_reference.py — beyond the one shipped checkpoint, beyond U(-1,1) inputs, and,
 for the exploration noise, value by value against Philox4x32-10 + Box-Muller restated from the contract in include/rdv.h.
 
