@@ -41,6 +41,17 @@ def _random_params(rng):
                            fuel_coef=float(rng.uniform(0, 1)), att_coef=float(rng.uniform(0, 2))))
 
 
+def _random_params_with_nominal_attitudes(rng):
+    """_random_params (same draws, in the same order), then nominal attitudes of both bodies drawn at random and NOT of unit length
+    (quat_product normalises its factors, quaternions.py:159-160) and a nominal chaser rate: with the constructor's identity
+    attitudes the factor order and signs of the quaternion product and the lvlh2chaser rotation (:255-258) cancel out of a reset."""
+    p = _random_params(rng)
+    qc0 = rng.normal(size=4) * float(rng.uniform(0.3, 3.0))
+    qt0 = rng.normal(size=4) * float(rng.uniform(0.3, 3.0))
+    p.update(nominal_qc0=qc0, nominal_qt0=qt0, nominal_wc0=np.radians(rng.uniform(-2, 2, 3)))
+    return p
+
+
 def _expect_kernel(env, variant, diag=False, what=""):
     want = expected_kernel(variant, env.num_envs, env._ctor["storage"], env._ctor["on_done"], diag=diag)
     assert env.last_kernel == want, f"{what}: ran {env.last_kernel!r}, the dispatch rules say {want!r}"
@@ -95,10 +106,11 @@ def _run_evaluator(env, orc, n, steps, seed, storage, scale=1.0):
     _check_end(env, orc)
 
 
-@pytest.mark.parametrize("case", range(6))
+@pytest.mark.parametrize("case", range(9))
 def test_random_parameter_sets(case):
+    """Cases 0-5 keep the constructor's identity nominal attitudes; 6-8 also draw qc0, qt0 (random, non-unit) and wc0."""
     rng = np.random.default_rng(1000 + case)
-    p = _random_params(rng)
+    p = _random_params(rng) if case < 6 else _random_params_with_nominal_attitudes(rng)
     n = int(rng.choice([96, 300, 777]))
     # every variant on the training path; one evaluator pass per storage (halt mode: its diag rows are all comparable)
     runs = [(v, st, od) for v in ("fused", "split", "fused_inlane") for st in ("f32", "f64") for od in ("reset", "halt")]
