@@ -6,8 +6,7 @@ tests/ on purpose: the product never imports the oracle.
 import numpy as np
 import torch
 
-import oracle
-from helpers import to_oracle_params
+from helpers import oracle_batch, to_numpy, to_oracle_params
 
 
 class OracleEngine:
@@ -16,10 +15,9 @@ class OracleEngine:
         self.num_envs = int(num_envs)
         self.params = params.copy()
         self.device = torch.device("cpu")
-        self._orc = oracle.OracleBatch(
-            self.num_envs, to_oracle_params(params),
-            storage=oracle.STORAGE_F32 if storage == "f32" else oracle.STORAGE_F64,
-            on_done={"halt": oracle.ON_DONE_HALT, "continue": oracle.ON_DONE_NOTHING}.get(on_done, oracle.ON_DONE_RESET),
+        self._ctor = dict(storage=storage, on_done=on_done)          # as RendezvousBatch records them (helpers.batch_modes)
+        self._orc = oracle_batch(
+            self.num_envs, params, storage, on_done,
             seed=seed, env_id_offset=env_id_offset, n_threads=n_threads, numpy_legacy=numpy_legacy,
             **({} if tape is None else {"tape": np.asarray(tape, dtype=np.float64)}))      # reset tape [depth, N, 20]: recorded initial states
         self._orc_halts = on_done == "halt"
@@ -91,7 +89,7 @@ class OracleEngine:
     def step(self, actions, diag=False, accumulate=False):
         stepped = ~self._halted
         diag = diag or accumulate
-        r = self._orc.step(actions.detach().cpu().numpy().astype(np.float32), want_diag=diag)
+        r = self._orc.step(to_numpy(actions).astype(np.float32), want_diag=diag)
         if self._orc_halts:
             self._halted |= r["done"].astype(bool)
         if accumulate:
@@ -107,7 +105,7 @@ class OracleEngine:
         return self.obs, self.reward, self.done
 
     def set_state(self, states):
-        self._orc.set_state(states.detach().cpu().numpy())
+        self._orc.set_state(to_numpy(states))
 
     def get_state(self):
         return torch.from_numpy(self._orc.get_state())
@@ -128,7 +126,7 @@ class OracleEngine:
         self._orc.seed(seed)
 
     def set_reset_tape(self, tape):
-        self._orc.set_reset_tape(None if tape is None else np.asarray(tape.detach().cpu().numpy() if hasattr(tape, "detach") else tape,
+        self._orc.set_reset_tape(None if tape is None else np.asarray(to_numpy(tape) if hasattr(tape, "detach") else tape,
                                                                     dtype=np.float64))
 
     def set_params(self, params):

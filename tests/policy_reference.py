@@ -65,7 +65,7 @@ def mlp32(net, obs):
 
 
 def error_floor(net):
-    """A = |W3|inf (d + |W2|inf (d + |W1|inf 6e-8)), d = 2.5e-7: what the kernel does not share with a correctly rounded fp32
+    """A = |W3|inf (d + |W2|inf (d + |W1|inf 6e-8)), d = TANH_ABS_ERR: what the kernel does not share with a correctly rounded fp32
     evaluation (its tanh's absolute error and the loss of subnormal lo terms of tiny inputs), propagated through the network
     with tanh' <= 1.  |.|inf is the largest absolute row sum."""
     n = lambda w: float(np.abs(w.astype(np.float64)).sum(axis=1).max())
@@ -162,9 +162,9 @@ def _dense(rng, s1=0.35, s2=0.18, s3=0.08, sb=0.1):
 
 def fresh_init(seed=11):
     """What a training run starts from: MlpPolicy(weights=None): orthogonal, gains sqrt 2, sqrt 2, 0.01, zero biases."""
+    from helpers import to_numpy as a
     from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
     p = MlpPolicy(weights=None, seed=seed)
-    a = lambda t: t.detach().cpu().numpy()
     return make_net(a(p.l1.weight), a(p.l1.bias), a(p.l2.weight), a(p.l2.bias), a(p.l3.weight), a(p.l3.bias))
 
 

@@ -3,12 +3,11 @@ GPU tests of the callers either side of the kernel (run with `-m gpu`): the batc
 SURVEY §8 f-1) against the table the reference publishes, the SB3 VecEnv surface on the HIP engine, and properties at
 the full BASELINE size (65,536 envs) that do not need the oracle to run at that size.
 """
-import os
-
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, counter_actions, load_golden
+import parity
+from helpers import counter_actions, load_golden, shipped_policy, to_numpy
 from oracle_engine import OracleEngine
 
 torch = pytest.importorskip("torch")
@@ -17,16 +16,11 @@ pytestmark = pytest.mark.gpu
 INT_COLS = ("ep_len", "num_collisions", "collided", "num_successes", "succeeded")
 
 
-def _policy():
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
-    return MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz"))
-
-
 def test_monte_carlo_fp64_storage_reproduces_the_published_table():
     """1000 ICs, deterministic MLP policy on the GPU, dt=1, t_max=60: 545 successes / 166 collisions, row by row."""
     from reinforcement_learning_rendezvous_amd import monte_carlo as mc
     ics = load_golden("mc_initial_conditions.npz")["states"]
-    res = mc.run(_policy(), ics, device="cuda:0", storage="f64")
+    res = mc.run(shipped_policy(), ics, device="cuda:0", storage="f64")
     pub = load_golden("mc_published_xlsx.npz")
     cols = [str(c) for c in pub["columns"]]
     tab = pub["table"]
@@ -48,7 +42,7 @@ def test_monte_carlo_fp32_storage_flip_budget_and_oracle_agreement():
     from reinforcement_learning_rendezvous_amd import monte_carlo as mc
     from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
     ics = load_golden("mc_initial_conditions.npz")["states"]
-    res = mc.run(_policy(), ics, device="cuda:0", storage="f32")
+    res = mc.run(shipped_policy(), ics, device="cuda:0", storage="f32")
     assert abs(int(res["succeeded"].sum()) - 545) <= 5 and abs(int(res["collided"].sum()) - 166) <= 3
     # replay: GPU env + GPU policy produce actions; the oracle consumes the same actions step by step
     p = mc.make_eval_params()
@@ -57,7 +51,7 @@ def test_monte_carlo_fp32_storage_flip_budget_and_oracle_agreement():
     s[:, 13:17] /= np.linalg.norm(s[:, 13:17], axis=1, keepdims=True)
     env = RendezvousBatch(1000, params=p, device="cuda:0", storage="f32", on_done="halt")
     orc = OracleEngine(1000, p, storage="f32", on_done="halt")
-    pol = _policy().to("cuda:0")
+    pol = shipped_policy().to("cuda:0")
     env.reset(); orc.reset()
     env.set_state(torch.from_numpy(s)); orc.set_state(torch.from_numpy(s))
     obs = env.observe()
@@ -66,10 +60,10 @@ def test_monte_carlo_fp32_storage_flip_budget_and_oracle_agreement():
         a = pol.act(obs, deterministic=True).contiguous()
         obs, rew, done = env.step(a, diag=True)
         o2, r2, d2 = orc.step(a.cpu(), diag=True)
-        np.testing.assert_array_equal(done.cpu().numpy(), d2.numpy(), err_msg=f"done, step {t}")
-        np.testing.assert_array_equal(env.diag.cpu().numpy()[:, [4, 5, 7]], orc.diag.numpy()[:, [4, 5, 7]], err_msg=f"flags, step {t}")
-        np.testing.assert_allclose(obs.cpu().numpy(), o2.numpy(), rtol=0, atol=2.4e-7)
-        np.testing.assert_allclose(rew.cpu().numpy(), r2.numpy(), rtol=2e-6, atol=2e-6)
+        np.testing.assert_array_equal(to_numpy(done), d2.numpy(), err_msg=f"done, step {t}")
+        np.testing.assert_array_equal(to_numpy(env.diag)[:, parity.DIAG_FLAGS], orc.diag.numpy()[:, parity.DIAG_FLAGS], err_msg=f"flags, step {t}")
+        np.testing.assert_allclose(to_numpy(obs), o2.numpy(), rtol=0, atol=parity.OBS_TOL)
+        np.testing.assert_allclose(to_numpy(rew), r2.numpy(), rtol=parity.REWARD_TOL, atol=parity.REWARD_TOL)
     assert bool(done.all())
 
 
@@ -86,13 +80,13 @@ def test_vecenv_on_hip_engine_matches_oracle_vecenv():
         og, rg, dg, ig = gpu.step(a)
         oc, rc, dc, ic = cpu.step(a)
         np.testing.assert_array_equal(dg, dc)
-        np.testing.assert_allclose(og, oc, rtol=0, atol=2.4e-7)
-        np.testing.assert_allclose(rg, rc, rtol=2e-6, atol=2e-6)
+        np.testing.assert_allclose(og, oc, rtol=0, atol=parity.OBS_TOL)
+        np.testing.assert_allclose(rg, rc, rtol=parity.REWARD_TOL, atol=parity.REWARD_TOL)
         for i in np.flatnonzero(dg):
             n_done += 1
             assert ig[i]["episode"]["l"] == ic[i]["episode"]["l"]
             assert ig[i]["end_reason"] == ic[i]["end_reason"] and ig[i]["collided"] == ic[i]["collided"]
-            np.testing.assert_allclose(ig[i]["terminal_observation"], ic[i]["terminal_observation"], rtol=0, atol=2.4e-7)
+            np.testing.assert_allclose(ig[i]["terminal_observation"], ic[i]["terminal_observation"], rtol=0, atol=parity.OBS_TOL)
         assert all(ig[i] == {} for i in np.flatnonzero(~dg))
     assert n_done > 100
     assert gpu.get_attr("t", 0) == cpu.get_attr("t", 0)
@@ -148,18 +142,18 @@ def test_monte_carlo_replicas_are_shard_invariant_and_agree_with_the_cpu_statist
     from reinforcement_learning_rendezvous_amd import monte_carlo as mc
     ics = load_golden("mc_initial_conditions.npz")["states"]
     R = 8
-    whole, span = mc.run_replicas(_policy(), ics, R, device="cuda:0", storage="f64", seed=11)
+    whole, span = mc.run_replicas(shipped_policy(), ics, R, device="cuda:0", storage="f64", seed=11)
     assert span == (0, R * len(ics))
-    parts = [mc.run_replicas(_policy(), ics, R, device="cuda:0", storage="f64", seed=11, rank=r, world=3)[0] for r in range(3)]
+    parts = [mc.run_replicas(shipped_policy(), ics, R, device="cuda:0", storage="f64", seed=11, rank=r, world=3)[0] for r in range(3)]
     for c in mc.REPLICA_COLUMNS:
         np.testing.assert_array_equal(np.concatenate([p[c] for p in parts]), whole[c], err_msg=c)
     s = mc.replica_summary(whole, len(ics))
     assert s["replicas"] == R and s["success_percent_std"] > 0.0                      # the replicas really differ
-    other = mc.replica_summary(mc.run_replicas(_policy(), ics, 2, device="cuda:0", storage="f64", seed=12)[0], len(ics))
+    other = mc.replica_summary(mc.run_replicas(shipped_policy(), ics, 2, device="cuda:0", storage="f64", seed=12)[0], len(ics))
     assert other["success_percent_mean"] != s["success_percent_mean"]               # and depend on the seed
     # CPU: oracle engine + torch policy, 2 replicas (independent noise): binomial sigma of a 2000-trajectory rate ~ 1.1 %
     torch.manual_seed(5)
-    cpu_cols, _ = mc.run_replicas(_policy(), ics, 2, seed=5,
+    cpu_cols, _ = mc.run_replicas(shipped_policy(), ics, 2, seed=5,
                                   engine_factory=lambda n, p: OracleEngine(n, p, storage="f64", on_done="halt", n_threads=8))
     cpu = mc.replica_summary(cpu_cols, len(ics))
     assert abs(cpu["success_percent_mean"] - s["success_percent_mean"]) < 4.0
@@ -180,7 +174,7 @@ def test_device_evaluation_accumulators_equal_their_numpy_restatement():
     s = mc._normalised(ics)
     env = RendezvousBatch(len(s), params=p, device="cuda:0", storage="f64", on_done="halt")
     orc = OracleEngine(len(s), p, storage="f64", on_done="halt", n_threads=8)
-    pol = _policy().to("cuda:0")
+    pol = shipped_policy().to("cuda:0")
     env.reset(); orc.reset()
     env.set_state(torch.from_numpy(s)); orc.set_state(torch.from_numpy(s))
     obs = env.observe()

@@ -6,29 +6,15 @@ code paths that must agree bit for bit whatever the size.
   config 5 : Monte Carlo replicas on 8 ranks        — 8-way run_replicas == the single batch
 (The small-size versions of the same equalities, against the oracle, are in test_gpu_parity / test_gpu_rollout / test_gpu_slots.)
 """
-import os
-
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, load_golden
+from helpers import gpu_batch, load_golden, shipped_policy
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 N3 = 65536
-
-
-def _batch(*a, **k):
-    from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
-    return RendezvousBatch(*a, device="cuda:0", **k)
-
-
-def _policy(seed=3):
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
-    p = MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz")).to("cuda:0")
-    p.noise_seed = seed
-    return p
 
 
 def _actions(n, t, seed=7):
@@ -38,8 +24,8 @@ def _actions(n, t, seed=7):
 
 def test_config3_rollout_kernel_equals_act_plus_step_at_65536():
     T = 16
-    roll, loop = _batch(N3, storage="f32", seed=9), _batch(N3, storage="f32", seed=9)
-    pr, pl = _policy(), _policy()
+    roll, loop = gpu_batch(N3, storage="f32", seed=9), gpu_batch(N3, storage="f32", seed=9)
+    pr, pl = shipped_policy("cuda:0", noise_seed=3), shipped_policy("cuda:0", noise_seed=3)
     assert torch.equal(roll.reset(), loop.reset())
     # start the comparison in the steady state of the reset mix (episodes end from step ~18 on with this actor and random starts)
     for t in range(24):
@@ -64,7 +50,7 @@ def test_config3_rollout_kernel_equals_act_plus_step_at_65536():
 
 def test_config3_step_many_equals_the_step_loop_at_65536():
     K = 16
-    many, loop = _batch(N3, storage="f32", seed=4), _batch(N3, storage="f32", seed=4)
+    many, loop = gpu_batch(N3, storage="f32", seed=4), gpu_batch(N3, storage="f32", seed=4)
     assert torch.equal(many.reset(), loop.reset())
     tape = torch.stack([_actions(N3, t, seed=11) for t in range(K)]).contiguous()
     for rep in range(3):                         # three tapes: episodes end from the second on
@@ -84,8 +70,8 @@ def test_config4_eight_shards_of_65536_equal_one_batch_of_524288():
     """The 8-GPU configuration rehearsed on one device: shard g = envs [g * 65,536, (g + 1) * 65,536) of the global batch, its
     reset RNG keyed by global env id.  The big batch runs the fused kernel (in-lane resets), the shards the split kernel."""
     G, T = 8, 32
-    full = _batch(G * N3, storage="f32", seed=17)
-    shards = [_batch(N3, storage="f32", seed=17, env_id_offset=g * N3) for g in range(G)]
+    full = gpu_batch(G * N3, storage="f32", seed=17)
+    shards = [gpu_batch(N3, storage="f32", seed=17, env_id_offset=g * N3) for g in range(G)]
     o = full.reset()
     for g, sh in enumerate(shards):
         assert torch.equal(o[g * N3:(g + 1) * N3], sh.reset()), f"reset obs, shard {g}"
@@ -115,10 +101,9 @@ def test_config4_eight_shards_of_65536_equal_one_batch_of_524288():
 
 def test_config5_monte_carlo_replicas_on_eight_ranks_equal_one_batch():
     from reinforcement_learning_rendezvous_amd import monte_carlo as mc
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
     ics = load_golden("mc_initial_conditions.npz")["states"]
     R, W = 20, 8
-    pol = lambda: MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz"))
+    pol = shipped_policy
     whole, span = mc.run_replicas(pol(), ics, R, device="cuda:0", storage="f32", seed=3)
     assert span == (0, R * len(ics))
     parts = [mc.run_replicas(pol(), ics, R, device="cuda:0", storage="f32", seed=3, rank=r, world=W)[0] for r in range(W)]
@@ -135,11 +120,10 @@ def test_config5_at_its_stated_size_1000_initial_conditions_x_1000_seeds():
     columns of every slice equal the single batch bit for bit — the trajectory set does not depend on the shard count.  Success
     rate of the stochastic policy over the 1000 replicas: 54.9 +- 1.5 % (the deterministic policy gives the published 54.5 %)."""
     from reinforcement_learning_rendezvous_amd import monte_carlo as mc
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
     ics = load_golden("mc_initial_conditions.npz")["states"]
     assert len(ics) == 1000
     R, W = 1000, 8
-    pol = lambda: MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz"))
+    pol = shipped_policy
     whole, span = mc.run_replicas(pol(), ics, R, device="cuda:0", storage="f32", seed=11)
     assert span == (0, 1_000_000) and all(len(v) == 1_000_000 for v in whole.values()) and set(whole) == set(mc.REPLICA_COLUMNS)
     for r in range(W):

@@ -6,41 +6,18 @@ only inside the keep-out-zone sphere and the velocity / rotation errors only nea
 derive_target<kLazy = true>); everything else stays +inf.  Collision flag, success count and bonus reward are computed from those
 values, so they are compared here with the CPU oracle on runs that enter the KOZ, dock and earn bonuses — not kernel against kernel,
 and never through the evaluator build (diag outputs), which derives everything.  Every step asserts the kernel that ran
-(rdv_debug_last_kernel) against the dispatch rules of tests/helpers.py.
+(rdv_debug_last_kernel) against the dispatch rules of tests/helpers.py; the comparison with the oracle is tests/parity.py's, with its
+full check set on every step.
 """
-import os
-
 import numpy as np
 import pytest
 
-import oracle
-from helpers import GOLDEN, counter_actions, expected_kernel, load_golden, to_oracle_params
+import parity
+from helpers import counter_actions, expect_kernel, gpu_batch, load_golden, oracle_batch, shipped_policy, to_numpy
 from reinforcement_learning_rendezvous_amd.params import make_params
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-_ORC_STORAGE = {"f32": oracle.STORAGE_F32, "f64": oracle.STORAGE_F64}
-_ORC_ON_DONE = {"reset": oracle.ON_DONE_RESET, "halt": oracle.ON_DONE_HALT, "continue": oracle.ON_DONE_NOTHING}
-
-
-def _batch(*a, **k):
-    from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
-    return RendezvousBatch(*a, device="cuda:0", **k)
-
-
-def _policy():
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
-    return MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz")).to("cuda:0")
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
-
-def _expect_kernel(env, variant, after_set_state=False, what=""):
-    want = expected_kernel(variant, env.num_envs, env._ctor["storage"], env._ctor["on_done"], after_set_state=after_set_state)
-    assert env.last_kernel == want, f"{what}: ran {env.last_kernel!r}, the dispatch rules say {want!r}"
 
 
 class Branches:
@@ -51,8 +28,8 @@ class Branches:
     def __init__(self, p):
         self.p, self.collisions, self.successes, self.bonus = p, 0, 0, 0
 
-    def add(self, orc, ref, reset_mode):
-        rows = ~ref["done"].astype(bool) if reset_mode else np.ones(len(ref["done"]), bool)   # reset rows hold the next episode
+    def add(self, orc, ref, rows):
+        """rows: parity.live_rows (reset rows hold the next episode)."""
         dg, aux, s = orc.diagnose()[rows], orc.get_aux()[rows], orc.get_state()[rows]
         self.collisions += int(dg[:, 4].sum())
         self.successes += int(dg[:, 5].sum())
@@ -64,36 +41,6 @@ class Branches:
         assert self.collisions > 0 and self.successes > 0 and self.bonus > 0, (what, self.collisions, self.successes, self.bonus)
 
 
-def _compare_step(env, orc, ref, o, r, d, storage, reset_mode, t, reward_tol=2e-6):
-    """One training-path step against the oracle's: outputs, evaluator quantities through rdv_diagnose, state and bookkeeping."""
-    np.testing.assert_array_equal(_np(d), ref["done"], err_msg=f"done, step {t}")
-    np.testing.assert_array_equal(_np(env.done_reason), ref["done_reason"], err_msg=f"reason, step {t}")
-    np.testing.assert_allclose(_np(o), ref["obs"], rtol=0, atol=2.4e-7, err_msg=f"obs, step {t}")
-    np.testing.assert_allclose(_np(r), ref["reward"], rtol=reward_tol, atol=reward_tol, err_msg=f"reward, step {t}")
-    fin = ref["done"].astype(bool)
-    new = fin & (ref["episode_length"] > 0)    # finished on this step (halt mode: a halted env reports done, its rows stay unwritten)
-    np.testing.assert_array_equal(_np(env.episode_length)[new], ref["episode_length"][new])
-    np.testing.assert_allclose(_np(env.episode_return)[new], ref["episode_return"][new], rtol=1e-5, atol=1e-5)
-    np.testing.assert_allclose(_np(env.terminal_obs)[new], ref["terminal_obs"][new], rtol=0, atol=2.4e-7)
-    rows = ~fin if reset_mode else np.ones(len(fin), bool)
-    dg, dr = _np(env.diagnose())[rows], orc.diagnose()[rows]
-    np.testing.assert_array_equal(dg[:, [4, 5, 7]], dr[:, [4, 5, 7]], err_msg=f"flags, step {t}")
-    np.testing.assert_allclose(dg[:, [0, 1, 2, 3, 6]], dr[:, [0, 1, 2, 3, 6]], rtol=1e-6, atol=1e-6, err_msg=f"errors, step {t}")
-    tol = 2.5e-7 if storage == "f32" else 1e-10
-    np.testing.assert_allclose(_np(env.get_state()), orc.get_state(), rtol=tol, atol=tol, err_msg=f"state, step {t}")
-    a_gpu, a_ref = _np(env.get_aux()), orc.get_aux()
-    np.testing.assert_array_equal(a_gpu[:, [0, 2, 3, 7]], a_ref[:, [0, 2, 3, 7]], err_msg=f"t/collided/success/episode, step {t}")
-    np.testing.assert_allclose(a_gpu[:, [1, 4, 5, 6]], a_ref[:, [1, 4, 5, 6]], rtol=1e-5, atol=1e-5)
-
-
-def _compare_stats(env, orc):
-    sg, so = env.get_stats(), orc.get_stats()
-    for k in ("env_steps", "episodes", "successes", "collisions", "reasons"):
-        assert sg[k] == so[k], (k, sg[k], so[k])
-    for k in ("sum_return", "sum_length", "sum_delta_v", "sum_delta_w"):
-        assert abs(sg[k] - so[k]) <= 1e-5 * max(1.0, abs(so[k])), (k, sg[k], so[k])
-
-
 # the parameters of test_gpu_random_params.py::test_states_inside_the_keep_out_zone_and_parameter_updates and of
 # test_gpu_slots.py CASES[5]: episodes start around the docking point, many inside the sphere, some collided / successful at reset
 KOZ_PARAMS = {
@@ -103,20 +50,13 @@ KOZ_PARAMS = {
 
 
 def _koz_run(p, n, storage, on_done, variant, steps, seed, n_threads=1):
-    env = _batch(n, params=p, storage=storage, on_done=on_done, seed=seed, variant=variant)
-    orc = oracle.OracleBatch(n, to_oracle_params(p), seed=seed, storage=_ORC_STORAGE[storage], on_done=_ORC_ON_DONE[on_done],
-                             n_threads=n_threads)
-    np.testing.assert_allclose(_np(env.reset()), orc.reset(), rtol=0, atol=1.2e-7)
-    np.testing.assert_array_equal(_np(env.get_aux())[:, [2, 3]], orc.get_aux()[:, [2, 3]])
+    env = gpu_batch(n, params=p, storage=storage, on_done=on_done, seed=seed, variant=variant)
+    orc = oracle_batch(n, p, storage, on_done, seed=seed, n_threads=n_threads)
+    parity.check_reset_obs(env.reset(), orc.reset())
+    np.testing.assert_array_equal(to_numpy(env.get_aux())[:, [2, 3]], orc.get_aux()[:, [2, 3]])
     br = Branches(p)
-    for t in range(steps):
-        a = (counter_actions(seed + 40, t, n) * 0.3).astype(np.float32)
-        o, r, d = env.step(torch.from_numpy(a).cuda())
-        _expect_kernel(env, variant, what=f"step {t}")
-        ref = orc.step(a)
-        _compare_step(env, orc, ref, o, r, d, storage, on_done == "reset", t)
-        br.add(orc, ref, on_done == "reset")
-    _compare_stats(env, orc)
+    actions = ((counter_actions(seed + 40, t, n) * 0.3).astype(np.float32) for t in range(steps))
+    parity.run_against_oracle(env, orc, actions, storage, variant, on_step=lambda orc, ref, t: br.add(orc, ref, parity.live_rows(env, ref)))
     env.close()
     return br
 
@@ -149,24 +89,26 @@ def test_closed_loop_policy_into_the_keep_out_zone(variant):
     s[:, 6:10] /= np.linalg.norm(s[:, 6:10], axis=1, keepdims=True)
     s[:, 13:17] /= np.linalg.norm(s[:, 13:17], axis=1, keepdims=True)
     n = len(s)
-    env = _batch(n, params=p, storage="f32", on_done="halt", variant=variant)
-    orc = oracle.OracleBatch(n, to_oracle_params(p), storage=oracle.STORAGE_F32, on_done=oracle.ON_DONE_HALT)
-    pol = _policy()
+    env = gpu_batch(n, params=p, storage="f32", on_done="halt", variant=variant)
+    orc = oracle_batch(n, p, "f32", "halt")
+    pol = shipped_policy("cuda:0")
     env.reset(); orc.reset()
     env.set_state(torch.from_numpy(s)); orc.set_state(s)
     obs = env.observe()
-    np.testing.assert_array_equal(_np(obs), orc.observe())
+    np.testing.assert_array_equal(to_numpy(obs), orc.observe())
     br = Branches(p)
     for t in range(int(round(p.t_max / p.dt))):
         a = pol.act(obs, deterministic=True).contiguous()
-        a_np = _np(a).copy()
+        a_np = to_numpy(a).copy()
         obs, r, d = env.step(a)
-        _expect_kernel(env, variant, after_set_state=t == 0, what=f"step {t}")
+        expect_kernel(env, variant, after_set_state=t == 0, what=f"step {t}")
         ref = orc.step(a_np)
-        _compare_step(env, orc, ref, obs, r, d, "f32", False, t)
-        br.add(orc, ref, False)
-    assert bool(_np(d).all())
-    _compare_stats(env, orc)
+        parity.check_outputs(env, ref, obs, r, d, t)
+        parity.check_diag(env, orc, parity.live_rows(env, ref), t, False)
+        parity.check_state(env, orc, "f32", t)
+        br.add(orc, ref, parity.live_rows(env, ref))
+    assert bool(to_numpy(d).all())
+    parity.check_stats(env, orc)
     st = orc.get_stats()
     print(f"closed loop {variant}: {st['successes']} successful / {st['collisions']} collided episodes of {n}")
     br.check(f"closed loop {variant}")
@@ -222,31 +164,31 @@ def test_limit_straddling_states_through_the_step_kernels(variant):
     kinds = [k for k, _, _ in rows]
     S = np.stack([s for _, _, s in rows])
     n = len(S)
-    env = _batch(n, params=p, storage="f64", on_done="continue", variant=variant)
-    orc = oracle.OracleBatch(n, to_oracle_params(p), storage=oracle.STORAGE_F64, on_done=oracle.ON_DONE_NOTHING)
+    env = gpu_batch(n, params=p, storage="f64", on_done="continue", variant=variant)
+    orc = oracle_batch(n, p, "f64", "continue")
     env.reset(); orc.reset()
     env.set_state(torch.from_numpy(S)); orc.set_state(S)
     zero = np.zeros((n, 6), np.float32)
     first = None
     for t in range(6):
         o, r, d = env.step(torch.from_numpy(zero).cuda())
-        _expect_kernel(env, variant, after_set_state=t == 0, what=f"step {t}")
+        expect_kernel(env, variant, after_set_state=t == 0, what=f"step {t}")
         ref = orc.step(zero)
-        state = _np(env.get_state())
+        state = to_numpy(env.get_state())
         if first is None:
             first = state
         else:
             bad = np.flatnonzero(~(state == first).all(axis=1))
             assert bad.size == 0, f"step {t}: not a fixed point: {[kinds[i] for i in bad]}"
         np.testing.assert_allclose(state, orc.get_state(), rtol=0, atol=1e-10, err_msg=f"state, step {t}")
-        aux, aux_ref = _np(env.get_aux()), orc.get_aux()
+        aux, aux_ref = to_numpy(env.get_aux()), orc.get_aux()
         for col, what in ((2, "collided"), (3, "success count")):
             bad = np.flatnonzero(aux[:, col] != aux_ref[:, col])
             assert bad.size == 0, (what, t, [(kinds[i], rows[i][1], aux[i, col], aux_ref[i, col]) for i in bad])
-        np.testing.assert_array_equal(_np(d), ref["done"], err_msg=f"done, step {t}")
-        np.testing.assert_array_equal(_np(env.done_reason), ref["done_reason"], err_msg=f"reason, step {t}")
-        bad = np.flatnonzero(np.abs(_np(r) - ref["reward"]) > 2e-6 * np.maximum(1.0, np.abs(ref["reward"])))
-        assert bad.size == 0, ("reward", t, [(kinds[i], rows[i][1], float(_np(r)[i]), float(ref["reward"][i])) for i in bad])
+        np.testing.assert_array_equal(to_numpy(d), ref["done"], err_msg=f"done, step {t}")
+        np.testing.assert_array_equal(to_numpy(env.done_reason), ref["done_reason"], err_msg=f"reason, step {t}")
+        bad = np.flatnonzero(np.abs(to_numpy(r) - ref["reward"]) > parity.REWARD_TOL * np.maximum(1.0, np.abs(ref["reward"])))
+        assert bad.size == 0, ("reward", t, [(kinds[i], rows[i][1], float(to_numpy(r)[i]), float(ref["reward"][i])) for i in bad])
     # both sides of every limit occur in the oracle's outcome (boundary_diag's "pos" rows all round to y = -2.5: on the limit)
     aux_ref, dg_ref = orc.get_aux(), orc.diagnose()
     kinds = np.array(kinds)
@@ -266,21 +208,21 @@ def test_restored_halted_envs_step_on_in_reset_and_continue_modes():
     envs on (include/rdv.h, rdv_restore), so every path agrees bit for bit — rdv_step in every variant, with and without diag,
     rdv_step_many, and rdv_rollout against act + step."""
     n, K = 1000, 8
-    src = _batch(n, storage="f32", on_done="halt", seed=13)
+    src = gpu_batch(n, storage="f32", on_done="halt", seed=13)
     src.reset()
     for t in range(18):                                 # about half the envs have finished (and halted) by then
         src.step(torch.from_numpy(counter_actions(8, t, n)).cuda())
-    halted = _np(src.done).astype(bool)
+    halted = to_numpy(src.done).astype(bool)
     assert 50 < halted.sum() < n
     snap = src.snapshot()
     acts = torch.from_numpy(np.stack([counter_actions(9, t, n) for t in range(K)])).cuda()
     for on_done in ("reset", "continue"):
         results = {}
         for path in ("fused", "split", "fused_inlane", "fused_tiles", "diag", "step_many"):
-            env = _batch(n, storage="f32", on_done=on_done, seed=13, variant="auto" if path in ("diag", "step_many") else path)
+            env = gpu_batch(n, storage="f32", on_done=on_done, seed=13, variant="auto" if path in ("diag", "step_many") else path)
             env.restore(snap)
-            before = _np(env.get_state())
-            t_before = _np(env.get_aux())[:, 0]
+            before = to_numpy(env.get_state())
+            t_before = to_numpy(env.get_aux())[:, 0]
             if path == "step_many":
                 out = env.step_many(acts)
                 assert env.last_kernel == "step_many_kernel<float, false>", env.last_kernel
@@ -290,8 +232,8 @@ def test_restored_halted_envs_step_on_in_reset_and_continue_modes():
                 for k in range(K):
                     o, r, d = env.step(acts[k], diag=path == "diag")
                     rows.append((o.clone(), r.clone(), d.clone(), env.done_reason.clone()))
-            rows = [[_np(x) for x in row] for row in rows]
-            after, aux = _np(env.get_state()), _np(env.get_aux())
+            rows = [[to_numpy(x) for x in row] for row in rows]
+            after, aux = to_numpy(env.get_state()), to_numpy(env.get_aux())
             # the restored-halted envs took transitions
             assert (after[halted] != before[halted]).any(axis=1).all(), (on_done, path)
             if on_done == "continue":
@@ -307,19 +249,19 @@ def test_restored_halted_envs_step_on_in_reset_and_continue_modes():
             np.testing.assert_array_equal(aux, ref_aux, err_msg=f"{on_done} {path}: aux")
             assert stats == ref_stats, (on_done, path)
         # rdv_rollout (its own actions) against act + step on the same restored snapshot
-        pol_a, pol_b = _policy(), _policy()
-        roll = _batch(n, storage="f32", on_done=on_done, seed=13)
-        loop = _batch(n, storage="f32", on_done=on_done, seed=13, variant="split")
+        pol_a, pol_b = shipped_policy("cuda:0"), shipped_policy("cuda:0")
+        roll = gpu_batch(n, storage="f32", on_done=on_done, seed=13)
+        loop = gpu_batch(n, storage="f32", on_done=on_done, seed=13, variant="split")
         roll.restore(snap); loop.restore(snap)
         out = roll.rollout(pol_a, K)
         assert roll.last_kernel == "rollout_kernel<float, false>", roll.last_kernel
         for k in range(K):
             a = loop.act(pol_b)                            # clipped, as SB3 passes it to the env; the rollout stores the sample
-            np.testing.assert_array_equal(_np(a), np.clip(_np(out["actions"][k]), -1, 1), err_msg=f"{on_done} rollout: actions, step {k}")
+            np.testing.assert_array_equal(to_numpy(a), np.clip(to_numpy(out["actions"][k]), -1, 1), err_msg=f"{on_done} rollout: actions, step {k}")
             o, r, d = loop.step(a)
-            np.testing.assert_array_equal(_np(r), _np(out["reward"][k]), err_msg=f"{on_done} rollout: reward, step {k}")
-            np.testing.assert_array_equal(_np(d), _np(out["done"][k]), err_msg=f"{on_done} rollout: done, step {k}")
-        np.testing.assert_array_equal(_np(roll.get_state()), _np(loop.get_state()), err_msg=f"{on_done} rollout: state")
-        assert (_np(roll.get_state())[halted] != _np(src.get_state())[halted]).any(axis=1).all()
+            np.testing.assert_array_equal(to_numpy(r), to_numpy(out["reward"][k]), err_msg=f"{on_done} rollout: reward, step {k}")
+            np.testing.assert_array_equal(to_numpy(d), to_numpy(out["done"][k]), err_msg=f"{on_done} rollout: done, step {k}")
+        np.testing.assert_array_equal(to_numpy(roll.get_state()), to_numpy(loop.get_state()), err_msg=f"{on_done} rollout: state")
+        assert (to_numpy(roll.get_state())[halted] != to_numpy(src.get_state())[halted]).any(axis=1).all()
         roll.close(); loop.close()
     src.close()

@@ -1,21 +1,14 @@
 """
 GPU tests (run with `-m gpu`) of the episode-level evaluation and of the in-kernel reset distribution.
 """
-import os
-
 import numpy as np
 import pytest
 
-from helpers import GOLDEN
+from helpers import shipped_policy
 from oracle_engine import OracleEngine
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-
-def _policy():
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
-    return MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz"))
 
 
 def test_evaluate_policy_on_gpu_matches_oracle_engine():
@@ -24,8 +17,8 @@ def test_evaluate_policy_on_gpu_matches_oracle_engine():
     from reinforcement_learning_rendezvous_amd.params import make_params
     p = make_params(t_max=60)
     n = 200
-    s_gpu, per_gpu = ev.evaluate_policy(_policy(), n_evals=n, params=p, device="cuda:0", storage="f64", seed=9)
-    s_cpu, per_cpu = ev.evaluate_policy_batch(_policy(), OracleEngine(n, p, storage="f64", on_done="halt", seed=9))
+    s_gpu, per_gpu = ev.evaluate_policy(shipped_policy(), n_evals=n, params=p, device="cuda:0", storage="f64", seed=9)
+    s_cpu, per_cpu = ev.evaluate_policy_batch(shipped_policy(), OracleEngine(n, p, storage="f64", on_done="halt", seed=9))
     assert list(s_gpu) == ev.SUMMARY_KEYS
     # the policy runs on different devices (GEMM order): actions differ in the last float32 bits, so a rare rounded-cosine
     # flip may move an integer outcome in a few of the 200 episodes
@@ -87,7 +80,7 @@ def test_reference_callback_metrics_and_trajectory_records_on_the_hip_engine():
     from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
     from reinforcement_learning_rendezvous_amd.params import make_params
     g = load_golden("eval_reference.npz")
-    pol = _policy().to("cuda:0")
+    pol = shipped_policy().to("cuda:0")
     env = RendezvousBatch(24, params=make_params(), device="cuda:0", storage="f64", on_done="halt")
     env.set_reset_tape(torch.from_numpy(g["cb_tape"][None]))
     summary, _ = ev.evaluate_policy_batch(pol, env)

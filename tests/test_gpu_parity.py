@@ -3,33 +3,19 @@ GPU parity tests (run with `-m gpu` on an MI355X): the HIP path, called through 
   (1) the golden transition tuples recorded from the unmodified reference (tests/golden/steps_*.npz), in fp64 storage, and
   (2) the CPU oracle on identical (seed, action) sequences, in both storage precisions.
 
-Tolerances.  Arithmetic is fp64 on both sides; the device uses fused multiply-adds and its own libm, the oracle
-neither, so agreement is to a few fp64 ulps per step, not bitwise:
-  fp64 storage: |dstate| <= 1e-10, reward <= 1e-9, obs (float32) <= 1 ulp (6e-8 .. 1.2e-7), flags/dones/reasons exact.
-  fp32 storage: the state is re-rounded to float32 after every step on both sides, which erases the ulp-level
-                differences except at rounding ties: |dstate| <= 2 float32 ulps, obs <= 2.4e-7, reward <= 2e-6 rel,
-                flags/dones exact.
+What is compared, at which tolerance and why: tests/parity.py (the step comparison against the oracle, and the golden replay; the
+numbers of the golden replay in fp64 storage are passed below).
 """
 import numpy as np
 import pytest
 
-import oracle
-from helpers import counter_actions, expected_kernel, load_golden, params_from_note, to_oracle_params
+import parity
+from helpers import counter_actions, gpu_batch, load_golden, oracle_batch, params_from_note, to_numpy
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
 SCENARIOS = ["A_random", "B_mc_policy", "C_variant", "D_stochastic", "E_spin"]
-
-
-def _batch(*a, **k):
-    from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
-    return RendezvousBatch(*a, device="cuda:0", **k)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
-
 
 # Every variant runs the TRAINING path (no diag / eval outputs), so that it really launches its own kernel: a step with diag=True runs
 # the evaluator build step_kernel<ST, true> whatever the variant.  Each scenario and storage then has exactly one evaluator pass of
@@ -38,59 +24,13 @@ def _np(t):
 VARIANTS = ["fused", "split", "fused_inlane", "fused_tiles"]
 
 
-def _expect_kernel(env, variant, diag=False, tape=False, after_set_state=False, what=""):
-    want = expected_kernel(variant, env.num_envs, env._ctor["storage"], env._ctor["on_done"], diag=diag, tape=tape,
-                           after_set_state=after_set_state)
-    assert env.last_kernel == want, f"{what}: ran {env.last_kernel!r}, the dispatch rules say {want!r}"
-
-
 def _golden_run(name, variant, diag):
     g = load_golden(f"steps_{name}.npz")
     p, _ = params_from_note(g["env_kwargs_json"])
-    T, E = g["actions"].shape[:2]
     halt = name.startswith("B")
-    env = _batch(E, params=p, storage="f64", on_done="halt" if halt else "reset", variant=variant)
-    if not halt:
-        env.set_reset_tape(torch.from_numpy(np.nan_to_num(g["tape"])))
-    obs = _np(env.reset())
-    if halt:
-        env.set_state(torch.from_numpy(g["state0"]))
-        obs = _np(env.observe())
-    np.testing.assert_allclose(_np(env.get_state()), g["state0"], rtol=0, atol=1e-15)
-    np.testing.assert_array_equal(obs, g["obs0"])
-    np.testing.assert_allclose(_np(env.get_aux())[:, :6], g["aux0"], rtol=0, atol=1e-15)
-    np.testing.assert_allclose(_np(env.diagnose()), g["diag0"], rtol=0, atol=1e-12)
-    n_done = 0
-    for t in range(T):
-        v = g["valid"][t].astype(bool)
-        if not v.any():
-            break
-        o, r, d = env.step(torch.from_numpy(g["actions"][t]).cuda(), diag=diag)
-        _expect_kernel(env, variant, diag=diag, tape=not halt, after_set_state=halt and t == 0, what=f"step {t}")
-        o, r, d = _np(o), _np(r), _np(d).astype(bool)
-        gd = g["done"][t].astype(bool)
-        np.testing.assert_array_equal(d[v], gd[v], err_msg=f"done, step {t}")
-        np.testing.assert_array_equal(_np(env.done_reason)[v] & 7, g["reason"][t][v], err_msg=f"reason, step {t}")
-        np.testing.assert_allclose(r[v], g["reward"][t][v].astype(np.float32), rtol=2e-7, atol=2e-7)
-        np.testing.assert_allclose(o[v], g["obs_ret"][t][v], rtol=0, atol=1.2e-7, err_msg=f"obs, step {t}")
-        keep = v if halt else (v & ~gd)          # after an auto-reset the terminal state is gone
-        fin = v & gd
-        # bit 4: the episode entered the KOZ (the latched flag), bit 5: it had a success step (the count of the terminal state)
-        flags = (g["diag"][t][:, 7] != 0) * 16 + (g["aux"][t][:, 3] > 0) * 32
-        np.testing.assert_array_equal(_np(env.done_reason)[fin] & 48, flags[fin], err_msg=f"reason flags, step {t}")
-        if diag:
-            dg, rows = _np(env.diag), v
-        else:                                    # the same numbers from the state as it stands (not done rows in reset mode)
-            dg, rows = _np(env.diagnose()), keep
-        np.testing.assert_array_equal(dg[rows][:, [4, 5, 7]], g["diag"][t][rows][:, [4, 5, 7]], err_msg=f"flags, step {t}")
-        np.testing.assert_allclose(dg[rows][:, [0, 1, 2, 3, 6]], g["diag"][t][rows][:, [0, 1, 2, 3, 6]], rtol=0, atol=1e-9)
-        np.testing.assert_allclose(_np(env.get_state())[keep], g["state"][t][keep], rtol=0, atol=1e-10)
-        np.testing.assert_allclose(_np(env.get_aux())[keep][:, :6], g["aux"][t][keep], rtol=0, atol=1e-10)
-        np.testing.assert_allclose(_np(env.terminal_obs)[fin], g["obs_step"][t][fin], rtol=0, atol=1.2e-7)
-        n_done += int(fin.sum())
-    st = env.get_stats()
-    assert st["episodes"] == n_done == int(g["done"].sum())
-    assert st["reasons"] == [int((g["reason"] == k).sum()) for k in (1, 2, 3, 4)]
+    env = gpu_batch(g["actions"].shape[1], params=p, storage="f64", on_done="halt" if halt else "reset", variant=variant)
+    # fp64 storage against the reference's own fp64 records: observations to 1 float32 ulp, the float32 reward to 2e-7
+    parity.replay_golden(env, g, halt=halt, diag=diag, variant=variant, obs_tol=1.2e-7, reward_kw=dict(rtol=2e-7, atol=2e-7))
     env.close()
 
 
@@ -110,13 +50,13 @@ def test_golden_transitions_fp64_storage_evaluator_build(name):
 
 def _golden_vs_oracle(name, storage, variant):
     g = load_golden(f"steps_{name}.npz")
-    p, op = params_from_note(g["env_kwargs_json"])
+    p, _ = params_from_note(g["env_kwargs_json"])
     T, E = g["actions"].shape[:2]
     tape = np.nan_to_num(g["tape"])
-    env = _batch(E, params=p, storage=storage, variant=variant)
+    env = gpu_batch(E, params=p, storage=storage, variant=variant)
     env.set_reset_tape(torch.from_numpy(tape))
-    orc = oracle.OracleBatch(E, op, storage=oracle.STORAGE_F32 if storage == "f32" else oracle.STORAGE_F64, tape=tape)
-    np.testing.assert_array_equal(_np(env.reset()), orc.reset())
+    orc = oracle_batch(E, p, storage, tape=tape)
+    np.testing.assert_array_equal(to_numpy(env.reset()), orc.reset())
     return env, orc, [g["actions"][t] for t in range(T)]
 
 
@@ -126,115 +66,54 @@ def _golden_vs_oracle(name, storage, variant):
 def test_golden_actions_vs_oracle(name, storage, variant):
     """Same tapes and action sequences, HIP (training path) vs oracle in the same storage precision (covers fp32 production mode)."""
     env, orc, actions = _golden_vs_oracle(name, storage, variant)
-    _compare_run(env, orc, actions, storage, variant, tape=True)
+    parity.run_against_oracle(env, orc, actions, storage, variant, tape=True)
 
 
+# The evaluator passes of this module compare the flags of the diag output, not its error norms (diag_errors=False): their set as
+# it has always been.
 @pytest.mark.parametrize("storage", ["f32", "f64"])
 @pytest.mark.parametrize("name", ["A_random", "C_variant", "D_stochastic"])
 def test_golden_actions_vs_oracle_evaluator_build(name, storage):
     env, orc, actions = _golden_vs_oracle(name, storage, "auto")
-    _compare_run_evaluator(env, orc, actions, storage)
-
-
-def _check_outputs(env, ref, o, r, d, t):
-    """What a step returns, against the oracle's step: exact where the reference compares, within the stated tolerances elsewhere."""
-    np.testing.assert_array_equal(_np(d), ref["done"], err_msg=f"done, step {t}")
-    np.testing.assert_array_equal(_np(env.done_reason), ref["done_reason"], err_msg=f"reason, step {t}")
-    np.testing.assert_allclose(_np(o), ref["obs"], rtol=0, atol=2.4e-7, err_msg=f"obs, step {t}")
-    np.testing.assert_allclose(_np(r), ref["reward"], rtol=2e-6, atol=2e-6, err_msg=f"reward, step {t}")
-    fin = ref["done"].astype(bool)
-    np.testing.assert_array_equal(_np(env.episode_length)[fin], ref["episode_length"][fin])
-    np.testing.assert_allclose(_np(env.episode_return)[fin], ref["episode_return"][fin], rtol=1e-5, atol=1e-5)
-    np.testing.assert_allclose(_np(env.terminal_obs)[fin], ref["terminal_obs"][fin], rtol=0, atol=2.4e-7)
-
-
-def _check_state(env, orc, storage, t):
-    st_tol = 2.5e-7 if storage == "f32" else 1e-10     # relative to max(1,|x|): 2 float32 ulps
-    s_gpu, s_ref = _np(env.get_state()), orc.get_state()
-    np.testing.assert_allclose(s_gpu, s_ref, rtol=st_tol, atol=st_tol, err_msg=f"state, step {t}")
-    a_gpu, a_ref = _np(env.get_aux()), orc.get_aux()
-    np.testing.assert_array_equal(a_gpu[:, [0, 2, 3, 7]], a_ref[:, [0, 2, 3, 7]], err_msg=f"t/collided/success/episode, step {t}")
-    np.testing.assert_allclose(a_gpu[:, [1, 4, 5, 6]], a_ref[:, [1, 4, 5, 6]], rtol=1e-5, atol=1e-5)
-
-
-def _check_stats(env, orc):
-    sg, so = env.get_stats(), orc.get_stats()
-    for k in ("env_steps", "episodes", "successes", "collisions", "reasons"):
-        assert sg[k] == so[k], (k, sg[k], so[k])
-    for k in ("sum_return", "sum_length", "sum_delta_v", "sum_delta_w"):
-        assert abs(sg[k] - so[k]) <= 1e-5 * max(1.0, abs(so[k])), (k, sg[k], so[k])
-
-
-def _compare_run(env, orc, action_list, storage, variant, tape=False, check_every=1):
-    """Training path: steps without diag, so the variant's own kernel runs (asserted each step); the evaluator's flags and error
-    norms come from rdv_diagnose of the post-step state — every row in halt / continue mode, the rows that are not done in reset
-    mode (theirs was replaced by the next episode's)."""
-    reset_mode = env._ctor["on_done"] == "reset"
-    for t, a in enumerate(action_list):
-        o, r, d = env.step(torch.from_numpy(a).cuda())
-        _expect_kernel(env, variant, tape=tape, what=f"step {t}")
-        ref = orc.step(a)
-        _check_outputs(env, ref, o, r, d, t)
-        if t % check_every == 0:
-            rows = ~ref["done"].astype(bool) if reset_mode else np.ones(env.num_envs, bool)
-            dg, dr = _np(env.diagnose())[rows], orc.diagnose()[rows]
-            np.testing.assert_array_equal(dg[:, [4, 5, 7]], dr[:, [4, 5, 7]], err_msg=f"flags, step {t}")
-            np.testing.assert_allclose(dg[:, [0, 1, 2, 3, 6]], dr[:, [0, 1, 2, 3, 6]], rtol=1e-6, atol=1e-6, err_msg=f"errors, step {t}")
-            _check_state(env, orc, storage, t)
-    _check_stats(env, orc)
-
-
-def _compare_run_evaluator(env, orc, action_list, storage, check_every=1):
-    """Evaluator path: steps with diag, the evaluator build (asserted each step), its diag outputs against the oracle's."""
-    for t, a in enumerate(action_list):
-        o, r, d = env.step(torch.from_numpy(a).cuda(), diag=True)
-        _expect_kernel(env, "auto", diag=True, what=f"step {t}")
-        ref = orc.step(a, want_diag=True)
-        _check_outputs(env, ref, o, r, d, t)
-        if t % check_every == 0:
-            np.testing.assert_array_equal(_np(env.diag)[:, [4, 5, 7]], ref["diag"][:, [4, 5, 7]], err_msg=f"flags, step {t}")
-            _check_state(env, orc, storage, t)
-    _check_stats(env, orc)
+    parity.run_against_oracle(env, orc, actions, storage, "auto", evaluator=True, diag_errors=False)
 
 
 def _config2(storage, variant):
     n = 4096
-    env = _batch(n, storage=storage, seed=0, variant=variant)
-    orc = oracle.OracleBatch(n, to_oracle_params(env.params), seed=0, n_threads=8,
-                             storage=oracle.STORAGE_F32 if storage == "f32" else oracle.STORAGE_F64)
-    np.testing.assert_array_equal(_np(env.reset()), orc.reset())
+    env = gpu_batch(n, storage=storage, seed=0, variant=variant)
+    orc = oracle_batch(n, env.params, storage, seed=0, n_threads=8)
+    np.testing.assert_array_equal(to_numpy(env.reset()), orc.reset())
     return env, orc, [counter_actions(1, t, n) for t in range(512)]
 
 
+# config 2 compares the outputs on every step, diag / state / aux on every 16th (512 steps of 4096 envs on the CPU oracle)
 @pytest.mark.parametrize("variant", VARIANTS)
 @pytest.mark.parametrize("storage", ["f32", "f64"])
 def test_config2_4096x512_random_actions_philox_resets(storage, variant):
     """BASELINE config 2: 4096 envs x 512 steps, U(-1,1) actions keyed by (seed, step, env), in-kernel Philox resets, on the
     variant's own kernel (the training path)."""
     env, orc, actions = _config2(storage, variant)
-    _compare_run(env, orc, actions, storage, variant, check_every=16)
+    parity.run_against_oracle(env, orc, actions, storage, variant, diag_every=16, state_every=16)
     assert env.get_stats()["episodes"] > 50_000     # ~5 % of envs end per step (bubble)
 
 
 @pytest.mark.parametrize("storage", ["f32", "f64"])
 def test_config2_4096x512_random_actions_philox_resets_evaluator_build(storage):
     env, orc, actions = _config2(storage, "auto")
-    _compare_run_evaluator(env, orc, actions, storage, check_every=16)
+    parity.run_against_oracle(env, orc, actions, storage, "auto", evaluator=True, diag_errors=False, diag_every=16, state_every=16)
     assert env.get_stats()["episodes"] > 50_000
 
 
 def _ragged(variant, diag):
     for n in (1, 63, 65, 129, 257, 1000):
-        env = _batch(n, storage="f32", seed=11, variant=variant)
-        orc = oracle.OracleBatch(n, to_oracle_params(env.params), seed=11, storage=oracle.STORAGE_F32)
-        np.testing.assert_array_equal(_np(env.reset()), orc.reset())
-        run = (lambda acts: _compare_run_evaluator(env, orc, acts, "f32")) if diag else (lambda acts: _compare_run(env, orc, acts, "f32", variant))
-        run([counter_actions(5, t, n) for t in range(40)])
+        env = gpu_batch(n, storage="f32", seed=11, variant=variant)
+        orc = oracle_batch(n, env.params, "f32", seed=11)
+        np.testing.assert_array_equal(to_numpy(env.reset()), orc.reset())
+        kw = dict(evaluator=True, diag_errors=False) if diag else {}
+        parity.run_against_oracle(env, orc, [counter_actions(5, t, n) for t in range(40)], "f32", variant, **kw)
         mask = (np.arange(n) % 3 == 0).astype(np.uint8)
-        o_gpu = _np(env.reset(torch.from_numpy(mask)))
-        o_ref = orc.reset(mask)
-        np.testing.assert_allclose(o_gpu, o_ref, rtol=0, atol=2.4e-7)
-        run([counter_actions(6, t, n) for t in range(10)])
+        np.testing.assert_allclose(to_numpy(env.reset(torch.from_numpy(mask))), orc.reset(mask), rtol=0, atol=parity.OBS_TOL)
+        parity.run_against_oracle(env, orc, [counter_actions(6, t, n) for t in range(10)], "f32", variant, **kw)
         env.close()
 
 
@@ -252,17 +131,17 @@ def test_sharding_is_index_independent():
     """Env i of a shard with env_id_offset=o behaves exactly as env o+i of the unsharded batch (RNG keyed by global id),
     and the two kernel variants give bit-identical outputs."""
     n = 512
-    full = _batch(n, storage="f32", seed=5, variant="fused")
-    lo = _batch(n // 2, storage="f32", seed=5, env_id_offset=0, variant="split")
-    hi = _batch(n // 2, storage="f32", seed=5, env_id_offset=n // 2, variant="split")
-    o = _np(full.reset())
-    np.testing.assert_array_equal(o[: n // 2], _np(lo.reset()))
-    np.testing.assert_array_equal(o[n // 2:], _np(hi.reset()))
+    full = gpu_batch(n, storage="f32", seed=5, variant="fused")
+    lo = gpu_batch(n // 2, storage="f32", seed=5, env_id_offset=0, variant="split")
+    hi = gpu_batch(n // 2, storage="f32", seed=5, env_id_offset=n // 2, variant="split")
+    o = to_numpy(full.reset())
+    np.testing.assert_array_equal(o[: n // 2], to_numpy(lo.reset()))
+    np.testing.assert_array_equal(o[n // 2:], to_numpy(hi.reset()))
     for t in range(64):
         a = counter_actions(2, t, n)
-        of, rf, df = [_np(x).copy() for x in full.step(torch.from_numpy(a).cuda())]
-        ol, rl, dl = [_np(x) for x in lo.step(torch.from_numpy(a[: n // 2]).cuda())]
-        oh, rh, dh = [_np(x) for x in hi.step(torch.from_numpy(a[n // 2:]).cuda())]
+        of, rf, df = [to_numpy(x).copy() for x in full.step(torch.from_numpy(a).cuda())]
+        ol, rl, dl = [to_numpy(x) for x in lo.step(torch.from_numpy(a[: n // 2]).cuda())]
+        oh, rh, dh = [to_numpy(x) for x in hi.step(torch.from_numpy(a[n // 2:]).cuda())]
         np.testing.assert_array_equal(of, np.concatenate([ol, oh]))
         np.testing.assert_array_equal(rf, np.concatenate([rl, rh]))
         np.testing.assert_array_equal(df, np.concatenate([dl, dh]))
@@ -270,7 +149,7 @@ def test_sharding_is_index_independent():
 
 def test_errors_are_loud():
     from reinforcement_learning_rendezvous_amd import RdvError
-    env = _batch(8)
+    env = gpu_batch(8)
     with pytest.raises(RdvError):
         env.step(torch.zeros((8, 6), device="cuda:0"))           # step before reset: state undefined (reference :44-49)
     env.reset()
@@ -279,9 +158,9 @@ def test_errors_are_loud():
     with pytest.raises(ValueError):
         env.step(torch.zeros((8, 6), dtype=torch.float64, device="cuda:0"))
     with pytest.raises(RdvError):
-        _batch(0)
+        gpu_batch(0)
     with pytest.raises(AssertionError):
-        _batch(4, koz_radius=1.5)                                 # reference assert :155
+        gpu_batch(4, koz_radius=1.5)                                 # reference assert :155
 
 
 def test_verification_script_scenarios_on_the_gpu():

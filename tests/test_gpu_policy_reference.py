@@ -5,7 +5,7 @@ for the exploration noise, value by value against Philox4x32-10 + Box-Muller res
 
 Deterministic bound, per (network class, input set), actor and critic:
     e_hip = max|kernel - clip(mlp64)|  <=  1.5 e32 + A,      e32 = max|mlp32 - mlp64| (a property of the reference alone),
-    A = |W3|inf (d + |W2|inf (d + |W1|inf 6e-8)), d = 2.5e-7 (the kernel's documented tanh and subnormal-input errors).
+    A = |W3|inf (d + |W2|inf (d + |W1|inf 6e-8)), d = policy_reference.TANH_ABS_ERR (the kernel's documented tanh and subnormal-input errors).
 The entrywise form of A (policy_reference.error_floor_entrywise, never larger) is asserted as well: the norm product is
 useless for shift_lt_10 (A ~ 10), whose large weights do not chain.
 The reference clamps observations to +-63 first: the kernel's documented deviation from PyTorch (rdv.h; nothing changes
@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import policy_reference as R
+from helpers import gpu_batch
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
@@ -133,11 +134,6 @@ def _zero_net():
     return R.make_net(z((64, 17)), z(64), z((64, 64)), z(64), z((6, 64)), z(6))
 
 
-def _batch(n, **k):
-    from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
-    return RendezvousBatch(n, device=DEV, **k)
-
-
 def test_fast_normals_against_fp64():
     """max|z_kernel - z_ref| over 2^22 envs x 6 normals (zero network, log_std 0: the unclipped action IS z), against the fp64
     normals of the same Philox words.  The sample contains words with u1 < 2^-20, u1 > 1 - 2^-20 and u2 within 2^-20 of 0, 1/4,
@@ -147,7 +143,7 @@ def test_fast_normals_against_fp64():
     u1 < 1 - 2^-20.  TOL_Z = 9.77e-4, under the hard cap of 1e-3."""
     assert R.TOL_Z <= 1e-3                             # a keying, ordering or sin/cos mistake moves z by O(1)
     n, T, seed = 65536, 64, 2024
-    env, pol = _batch(n, seed=2), _mlp_policy(_zero_net(), seed=seed)
+    env, pol = gpu_batch(n, seed=2), _mlp_policy(_zero_net(), seed=seed)
     env.reset()
     ro = env.rollout(pol, T)
     zk = ro["actions"].cpu().numpy().astype(np.float64)
@@ -242,7 +238,7 @@ def test_rollout_samples_and_log_prob_against_philox_reference(name, general):
     net = _stochastic_nets()[name]
     n, T = 33, 2
     for seed, off, ctr in CASES:
-        env, pol = _batch(n, seed=3, env_id_offset=off), _mlp_policy(net, seed=seed)
+        env, pol = gpu_batch(n, seed=3, env_id_offset=off), _mlp_policy(net, seed=seed)
         if general:
             env.set_rigid_body(inertia=[10.0, 20.0, 30.0])
         env.reset()

@@ -23,17 +23,16 @@ Tolerances.
   1.1e-16 of the same golden).  The first GPU run prints the figures; they belong here and in DESIGN.md section 3, item 9.
   f32 storage: the stored value is within one float32 ulp of float32(golden) (the fp64 error is far below half an ulp: the two roundings
   differ only next to a tie; the number of entries that differ at all is printed).
-  Observations: atol 1.2e-7, the project's reset-observation tolerance.
+  Observations: the project's reset-observation tolerance (tests/parity.py, RESET_OBS_TOL).
   collided / success: exact in fp64 storage; in f32 storage exact on the rows whose flag decisions have a margin in the reference's own
   numbers (flags_robust), and on all rows equal to the oracle's f32-storage flags.
 """
-import os
-
 import numpy as np
 import pytest
 
 import oracle
-from helpers import GOLDEN, counter_actions, expected_kernel, persistent_kernel
+import parity
+from helpers import counter_actions, expected_kernel, gpu_batch, persistent_kernel, shipped_policy, to_numpy
 from test_oracle_golden import RESET_SETS, load_reset_golden
 
 torch = pytest.importorskip("torch")
@@ -44,15 +43,6 @@ FP64_OBSERVED = 0.0                                       # largest value observ
 FP64_BOUND = max(16 * EPS, 8 * FP64_OBSERVED)
 assert FP64_BOUND <= 1e-10
 STORAGES = ["f64", "f32"]
-
-
-def _batch(*a, **k):
-    from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
-    return RendezvousBatch(*a, device="cuda:0", **k)
-
-
-def _np(t):
-    return t.detach().cpu().numpy()
 
 
 _cache = {}
@@ -103,7 +93,7 @@ def check_state(state, g, episode, storage, what, rows=None):
 def check_obs(obs, g, episode, what, rows=None):
     rows = np.arange(g["n"]) if rows is None else np.asarray(rows)
     ep = np.broadcast_to(np.asarray(episode), rows.shape)
-    np.testing.assert_allclose(obs, g["obs"][ep, rows], rtol=0, atol=1.2e-7, err_msg=f"{what}: obs")
+    parity.check_reset_obs(obs, g["obs"][ep, rows], f"{what}: obs")
 
 
 def check_flags(aux, g, episode, storage, what, rows=None, counter=True):
@@ -125,9 +115,9 @@ def check_all(env, obs, g, episode, storage, what, rows=None, tail=None):
     """obs, rdv_get_state and rdv_get_aux of `env` (its last `tail` rows, when it is larger than the golden) against one golden episode."""
     sl = slice(None) if tail is None else slice(env.num_envs - tail, env.num_envs)
     pick = (lambda x: x[sl]) if rows is None else (lambda x: x[sl][rows])
-    check_obs(pick(_np(obs)), g, episode, what, rows)
-    check_state(pick(_np(env.get_state())), g, episode, storage, what, rows)
-    check_flags(pick(_np(env.get_aux())), g, episode, storage, what, rows)
+    check_obs(pick(to_numpy(obs)), g, episode, what, rows)
+    check_state(pick(to_numpy(env.get_state())), g, episode, storage, what, rows)
+    check_flags(pick(to_numpy(env.get_aux())), g, episode, storage, what, rows)
 
 
 # ------------------------------------------------------------------------------------------------------- rdv_reset
@@ -137,12 +127,12 @@ def test_cold_reset_kernel(name, storage):
     """rdv_reset three times over: episodes 0, 1, 2.  Then a masked reset of alternate rows of a fresh batch: those move on to episode 1,
     the others keep their episode-0 state and their episode counter."""
     g = _golden(name)
-    env = _batch(g["n"], params=g["params"], storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
+    env = gpu_batch(g["n"], params=g["params"], storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
     for e in range(3):
         check_all(env, env.reset(), g, e, storage, f"{name}: reset_kernel, episode {e}")
     assert env.last_kernel == ""                     # no step kernel has run: these states are reset_kernel's
     env.close()
-    env = _batch(g["n"], params=g["params"], storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
+    env = gpu_batch(g["n"], params=g["params"], storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
     env.reset()
     mask = (np.arange(g["n"]) % 2 == 1)
     obs = env.reset(torch.from_numpy(mask.astype(np.uint8)).cuda())
@@ -156,7 +146,7 @@ def _auto_reset_run(g, name, storage, variant, n=None, diag=False, body=None, ke
     n_gold = g["n"]
     n = n_gold if n is None else n
     offset = g["env_id_offset"] - (n - n_gold)                      # the golden ids are the LAST 160 rows
-    env = _batch(n, params=_every_step_ends(g["params"]), storage=storage, seed=g["seed"], env_id_offset=offset, variant=variant)
+    env = gpu_batch(n, params=_every_step_ends(g["params"]), storage=storage, seed=g["seed"], env_id_offset=offset, variant=variant)
     if body:
         env.set_rigid_body(**body)
     tail = None if n == n_gold else n_gold
@@ -167,7 +157,7 @@ def _auto_reset_run(g, name, storage, variant, n=None, diag=False, body=None, ke
     for e in (1, 2):
         obs, _, done = env.step(zero, diag=diag)
         assert env.last_kernel == want_kernel, f"{who}: ran {env.last_kernel!r}, expected {want_kernel!r}"
-        assert _np(done).all(), f"{who}: every env finishes on every step"
+        assert to_numpy(done).all(), f"{who}: every env finishes on every step"
         check_all(env, obs, g, e, storage, f"{who}, episode {e}", tail=tail)
     env.close()
 
@@ -204,11 +194,6 @@ def test_auto_reset_in_the_general_body_kernels(name, storage):
 
 
 # ------------------------------------------------------------------------------------------------------- the prepared-state slots
-def _policy():
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
-    return MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz")).to("cuda:0")
-
-
 def _episode_after(done):
     """done [T,N] -> the episode each env is in AFTER step t (the number of episodes it has finished so far)."""
     return np.cumsum(done.astype(np.int64), axis=0)
@@ -232,8 +217,8 @@ def _check_final(env, done, g, storage, what):
     ep = _episode_after(done)[-1]
     rows = np.flatnonzero((done[-1] != 0) & (ep <= 2))
     assert rows.size >= g["n"] // 2, (what, rows.size)
-    check_state(_np(env.get_state())[rows], g, ep[rows], storage, what, rows)
-    check_flags(_np(env.get_aux())[rows], g, ep[rows], storage, what, rows)
+    check_state(to_numpy(env.get_state())[rows], g, ep[rows], storage, what, rows)
+    check_flags(to_numpy(env.get_aux())[rows], g, ep[rows], storage, what, rows)
 
 
 @pytest.mark.parametrize("storage", STORAGES)
@@ -246,7 +231,7 @@ def test_step_many_takes_and_refills_the_slots(name, storage):
     In set (c) the rc + vc part finds the state close to the target and leaves the flags to the lane that takes the slot."""
     g = _golden(name)
     n = g["n"]
-    mk = lambda p: _batch(n, params=p, storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
+    mk = lambda p: gpu_batch(n, params=p, storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
     kernel = persistent_kernel("step_many", storage)
     tape = lambda k0, K: torch.from_numpy(np.stack([0.5 * counter_actions(11, k0 + k, n) for k in range(K)])).cuda()
 
@@ -254,9 +239,9 @@ def test_step_many_takes_and_refills_the_slots(name, storage):
     env.reset()
     out = env.step_many(tape(0, 2))
     assert env.last_kernel == kernel, env.last_kernel
-    done = _np(out["done"])
+    done = to_numpy(out["done"])
     assert done.all()
-    assert _check_reset_rows(_np(out["obs"]), done, g, f"{name}: step_many") == 2 * n
+    assert _check_reset_rows(to_numpy(out["obs"]), done, g, f"{name}: step_many") == 2 * n
     _check_final(env, done, g, storage, f"{name}: step_many, final")
     env.close()
 
@@ -275,8 +260,8 @@ def test_step_many_takes_and_refills_the_slots(name, storage):
     env.reset()
     out = env.step_many(tape(0, 4))
     assert env.last_kernel == kernel, env.last_kernel
-    done = _np(out["done"])
-    assert _check_reset_rows(_np(out["obs"]), done, g, f"{name}: step_many, t_max = 2 dt") >= 2 * n
+    done = to_numpy(out["done"])
+    assert _check_reset_rows(to_numpy(out["obs"]), done, g, f"{name}: step_many, t_max = 2 dt") >= 2 * n
     env.close()
 
 
@@ -288,28 +273,28 @@ def test_rollout_takes_and_refills_the_slots(name, storage):
     g = _golden(name)
     n = g["n"]
     kernel = persistent_kernel("rollout", storage)
-    pol = _policy()
+    pol = shipped_policy("cuda:0")
 
-    env = _batch(n, params=_every_step_ends(g["params"]), storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
+    env = gpu_batch(n, params=_every_step_ends(g["params"]), storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
     env.reset()
     ro = env.rollout(pol, 2, deterministic=True)
     assert env.last_kernel == kernel, env.last_kernel
-    done = _np(ro["done"])
+    done = to_numpy(ro["done"])
     assert done.all()
-    check_obs(_np(ro["obs"][0]), g, 0, f"{name}: rollout, obs[0]")
-    after = np.concatenate([_np(ro["obs"])[1:], _np(ro["last_obs"])[None]])       # the observation AFTER step t
+    check_obs(to_numpy(ro["obs"][0]), g, 0, f"{name}: rollout, obs[0]")
+    after = np.concatenate([to_numpy(ro["obs"])[1:], to_numpy(ro["last_obs"])[None]])       # the observation AFTER step t
     assert _check_reset_rows(after, done, g, f"{name}: rollout") == 2 * n
     _check_final(env, done, g, storage, f"{name}: rollout, final")
     env.close()
 
     p = g["params"].copy()
     p.t_max = 2 * p.dt
-    env = _batch(n, params=p, storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
+    env = gpu_batch(n, params=p, storage=storage, seed=g["seed"], env_id_offset=g["env_id_offset"])
     env.reset()
     ro = env.rollout(pol, 4, deterministic=True)
     assert env.last_kernel == kernel, env.last_kernel
-    done = _np(ro["done"])
-    after = np.concatenate([_np(ro["obs"])[1:], _np(ro["last_obs"])[None]])
+    done = to_numpy(ro["done"])
+    after = np.concatenate([to_numpy(ro["obs"])[1:], to_numpy(ro["last_obs"])[None]])
     assert _check_reset_rows(after, done, g, f"{name}: rollout, t_max = 2 dt") >= 2 * n
     env.close()
     pol.close()

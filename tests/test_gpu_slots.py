@@ -7,29 +7,15 @@ ends copies it, and it is refilled once for the following episode, by part, on t
 the slots live in HBM and the host re-derives them whenever something outside those kernels changed what a reset returns.
 Whatever the path, results must agree bit for bit with each other, and with the oracle.
 """
-import os
-
 import numpy as np
 import pytest
 
-import oracle
-from helpers import GOLDEN, counter_actions, load_golden, params_from_note, to_oracle_params
+import parity
+from helpers import counter_actions, gpu_batch, load_golden, oracle_batch, params_from_note, shipped_policy, to_numpy
 from reinforcement_learning_rendezvous_amd.params import make_params
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-
-def _batch(*a, **k):
-    from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
-    return RendezvousBatch(*a, device="cuda:0", **k)
-
-
-def _policy(seed=3):
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
-    p = MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz")).to("cuda:0")
-    p.noise_seed = seed
-    return p
 
 
 def _same(a, b, what):
@@ -67,11 +53,11 @@ def test_step_layouts_and_persistent_kernels_agree(case):
     dones, reasons, terminal observations, episode returns / lengths, state, bookkeeping, statistics."""
     n, storage, T = case["n"], case["storage"], 60
     p = make_params(**case["kw"])
-    ref = _batch(n, params=p, storage=storage, seed=21, variant="fused")
-    other = _batch(n, params=p, storage=storage, seed=21, variant="split")
-    inlane = _batch(n, params=p, storage=storage, seed=21, variant="fused_inlane")
-    tiles = _batch(n, params=p, storage=storage, seed=21, variant="fused_tiles")
-    many = _batch(n - n % 4, params=p, storage=storage, seed=21)
+    ref = gpu_batch(n, params=p, storage=storage, seed=21, variant="fused")
+    other = gpu_batch(n, params=p, storage=storage, seed=21, variant="split")
+    inlane = gpu_batch(n, params=p, storage=storage, seed=21, variant="fused_inlane")
+    tiles = gpu_batch(n, params=p, storage=storage, seed=21, variant="fused_tiles")
+    many = gpu_batch(n - n % 4, params=p, storage=storage, seed=21)
     o0 = ref.reset().clone()
     _same(o0, other.reset(), "split: reset obs")
     _same(o0, inlane.reset(), "in-lane: reset obs")
@@ -123,25 +109,16 @@ def test_training_kernels_vs_oracle_with_philox_resets(storage, variant):
     for n, T, kw in ((4096, 128, {}), (1500, 64, dict(t_max=5.0)), (700, 24, dict(t_max=1.0)), (1, 40, dict(t_max=3.0)), (63, 24, dict(t_max=2.0)),
                      (65, 24, dict(t_max=2.0))):
         p = make_params(**kw)
-        env = _batch(n, params=p, storage=storage, seed=0, variant=variant)
-        orc = oracle.OracleBatch(n, to_oracle_params(p), seed=0, n_threads=8,
-                                 storage=oracle.STORAGE_F32 if storage == "f32" else oracle.STORAGE_F64)
-        np.testing.assert_array_equal(env.reset().cpu().numpy(), orc.reset())
+        env = gpu_batch(n, params=p, storage=storage, seed=0, variant=variant)
+        orc = oracle_batch(n, p, storage, seed=0, n_threads=8)
+        np.testing.assert_array_equal(to_numpy(env.reset()), orc.reset())
         for t in range(T):
             a = counter_actions(1, t, n)
             o, r, d = env.step(torch.from_numpy(a).cuda())
-            want = orc.step(a)
-            np.testing.assert_array_equal(d.cpu().numpy(), want["done"], err_msg=f"done, step {t}")
-            np.testing.assert_array_equal(env.done_reason.cpu().numpy(), want["done_reason"], err_msg=f"reason, step {t}")
-            np.testing.assert_allclose(o.cpu().numpy(), want["obs"], rtol=0, atol=2.4e-7, err_msg=f"obs, step {t}")
-            np.testing.assert_allclose(r.cpu().numpy(), want["reward"], rtol=2e-6, atol=2e-6, err_msg=f"reward, step {t}")
-        tol = 2.5e-7 if storage == "f32" else 1e-10
-        np.testing.assert_allclose(env.get_state().cpu().numpy(), orc.get_state(), rtol=tol, atol=tol)
-        a_gpu, a_ref = env.get_aux().cpu().numpy(), orc.get_aux()
-        np.testing.assert_array_equal(a_gpu[:, [0, 2, 3, 7]], a_ref[:, [0, 2, 3, 7]])        # t, collided, success, episode index
-        sg, so = env.get_stats(), orc.get_stats()
-        for k in ("env_steps", "episodes", "successes", "collisions", "reasons"):
-            assert sg[k] == so[k], (k, sg[k], so[k])
+            parity.check_outputs(env, orc.step(a), o, r, d, t, episode_rows=False)      # (the episode rows: bit for bit between the kernels, above)
+        parity.check_state(env, orc, storage, T, aux=False)                            # at the end of the run
+        np.testing.assert_array_equal(to_numpy(env.get_aux())[:, parity.AUX_EXACT], orc.get_aux()[:, parity.AUX_EXACT])
+        parity.check_stats(env, orc, sums=False)
         env.close()
 
 
@@ -149,21 +126,21 @@ def test_training_kernels_vs_oracle_with_philox_resets(storage, variant):
 def test_training_kernels_replay_the_reference_tape(variant):
     """Reset tape (the initial states the unmodified reference drew) through the training kernels (no diagnostics)."""
     g = load_golden("steps_A_random.npz")
-    p, op = params_from_note(g["env_kwargs_json"])
+    p, _ = params_from_note(g["env_kwargs_json"])
     T, E = g["actions"].shape[:2]
     tape = np.nan_to_num(g["tape"])
-    env = _batch(E, params=p, storage="f64", variant=variant)
+    env = gpu_batch(E, params=p, storage="f64", variant=variant)
     env.set_reset_tape(torch.from_numpy(tape))
-    obs = env.reset().cpu().numpy()
+    obs = to_numpy(env.reset())
     np.testing.assert_array_equal(obs, g["obs0"])
     for t in range(T):
         v = g["valid"][t].astype(bool)
         if not v.any():
             break
         o, r, d = env.step(torch.from_numpy(g["actions"][t]).cuda())
-        np.testing.assert_array_equal(d.cpu().numpy().astype(bool)[v], g["done"][t].astype(bool)[v], err_msg=f"done, step {t}")
-        np.testing.assert_allclose(o.cpu().numpy()[v], g["obs_ret"][t][v], rtol=0, atol=1.2e-7, err_msg=f"obs, step {t}")
-        np.testing.assert_allclose(r.cpu().numpy()[v], g["reward"][t][v].astype(np.float32), rtol=2e-7, atol=2e-7)
+        np.testing.assert_array_equal(to_numpy(d).astype(bool)[v], g["done"][t].astype(bool)[v], err_msg=f"done, step {t}")
+        np.testing.assert_allclose(to_numpy(o)[v], g["obs_ret"][t][v], rtol=0, atol=1.2e-7, err_msg=f"obs, step {t}")   # fp64 storage: 1 float32 ulp
+        np.testing.assert_allclose(to_numpy(r)[v], g["reward"][t][v].astype(np.float32), rtol=2e-7, atol=2e-7)
     env.close()
 
 
@@ -173,7 +150,7 @@ def test_slots_follow_parameter_seed_tape_and_restore_changes():
     put through the same sequence of such calls."""
     n = 900
     p = make_params(t_max=6.0)
-    a_env, b_env = _batch(n, params=p, seed=5), _batch(n, params=p, seed=5, variant="fused")
+    a_env, b_env = gpu_batch(n, params=p, seed=5), gpu_batch(n, params=p, seed=5, variant="fused")
     step = [0]
 
     def run(k, single=False):
@@ -218,8 +195,8 @@ def test_rollout_and_step_many_interleave_with_single_steps():
     """rdv_step (either layout), rdv_step_many and rdv_rollout on one handle, in turn, against a handle that only uses rdv_step."""
     n, storage = 1500, "f32"
     p = make_params(t_max=5.0)
-    pol_a, pol_b = _policy(), _policy()
-    a_env, b_env = _batch(n, params=p, storage=storage, seed=2, variant="split"), _batch(n, params=p, storage=storage, seed=2, variant="fused")
+    pol_a, pol_b = shipped_policy("cuda:0", noise_seed=3), shipped_policy("cuda:0", noise_seed=3)
+    a_env, b_env = gpu_batch(n, params=p, storage=storage, seed=2, variant="split"), gpu_batch(n, params=p, storage=storage, seed=2, variant="fused")
     _same(a_env.reset(), b_env.reset(), "reset")
     t0 = 0
     for rep in range(3):
@@ -255,9 +232,9 @@ def test_stochastic_rollout_and_act_are_shard_invariant():
     """the exploration noise must be keyed by GLOBAL env id on both entry points.  Two shards (env_id_offset 0 and n/2)
     reproduce the slices of one batch for ``rollout`` and for ``batch.act`` + ``step``."""
     n, T = 2048, 12
-    full = _batch(n, storage="f32", seed=6)
-    shards = [_batch(n // 2, storage="f32", seed=6, env_id_offset=g * (n // 2)) for g in range(2)]
-    pols = [_policy(seed=31) for _ in range(3)]
+    full = gpu_batch(n, storage="f32", seed=6)
+    shards = [gpu_batch(n // 2, storage="f32", seed=6, env_id_offset=g * (n // 2)) for g in range(2)]
+    pols = [shipped_policy("cuda:0", noise_seed=31) for _ in range(3)]
     o = full.reset()
     for g, sh in enumerate(shards):
         _same(o[g * (n // 2):(g + 1) * (n // 2)], sh.reset(), f"reset obs, shard {g}")
@@ -288,7 +265,7 @@ def test_xcd_contiguous_block_order_gives_the_same_results(monkeypatch):
     envs = {}
     for order in ("0", "1"):
         monkeypatch.setenv("RDV_XCD_ORDER", order)
-        envs[order] = [_batch(n, params=p, storage="f32", seed=8, variant=v) for v in ("fused", "fused_inlane")]
+        envs[order] = [gpu_batch(n, params=p, storage="f32", seed=8, variant=v) for v in ("fused", "fused_inlane")]
     monkeypatch.delenv("RDV_XCD_ORDER")
     ref = envs["0"][0]
     others = [envs["0"][1]] + envs["1"]
@@ -318,12 +295,12 @@ def test_tile_loop_walks_many_tiles_per_workgroup(monkeypatch):
     n, T = 40 * 256 + 130, 48
     p = make_params(t_max=9.0)
     for storage in ("f32", "f64"):
-        ref = _batch(n, params=p, storage=storage, seed=13, variant="fused")
+        ref = gpu_batch(n, params=p, storage=storage, seed=13, variant="fused")
         others = []
         for grid, order in (("8", "0"), ("8", "1"), ("16", "1")):
             monkeypatch.setenv("RDV_TILES_GRID", grid)
             monkeypatch.setenv("RDV_XCD_ORDER", order)
-            others.append(_batch(n, params=p, storage=storage, seed=13, variant="fused_tiles"))
+            others.append(gpu_batch(n, params=p, storage=storage, seed=13, variant="fused_tiles"))
         monkeypatch.delenv("RDV_TILES_GRID")
         monkeypatch.delenv("RDV_XCD_ORDER")
         o0 = ref.reset().clone()

@@ -8,7 +8,7 @@ GPU with the HIP engine (fp64 storage).
 import numpy as np
 import pytest
 
-from helpers import load_golden, params_from_note
+from helpers import load_golden, params_from_note, shipped_policy
 from reinforcement_learning_rendezvous_amd.gym_env import RendezvousEnv
 from reinforcement_learning_rendezvous_amd.vec_env import _STATE_ATTRS
 
@@ -161,20 +161,17 @@ def _oracle_env(params, **engine_kw):
     return RendezvousEnv(engine=OracleEngine(1, params, storage="f64", on_done="continue", **engine_kw), quiet=True)
 
 
-def _policy():
-    import os
+def _single_thread_policy():
     import torch
-    from helpers import GOLDEN
-    from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
     torch.set_num_threads(1)
-    return MlpPolicy.from_npz(os.path.join(GOLDEN, "mlp_policy.npz"))
+    return shipped_policy()
 
 
 def check_mc_evaluate(evaluate, rows=40):
     """``evaluate(model, env, initial_state)`` (the Monte Carlo episode loop, monte_carlo.py:94-207) drives ``RendezvousEnv``: its 12
     outputs for the first published initial conditions against the reference's own recorded re-run (tests/golden/mc_reference_run.npz)."""
     from reinforcement_learning_rendezvous_amd import monte_carlo as mc
-    model, env = _policy(), _oracle_env(mc.make_eval_params(), seed=0)
+    model, env = _single_thread_policy(), _oracle_env(mc.make_eval_params(), seed=0)
     ics = load_golden("mc_initial_conditions.npz")["states"]
     ref = load_golden("mc_reference_run.npz")
     cols = [str(c) for c in ref["columns"]]
@@ -197,7 +194,7 @@ def check_record_trajectory(record):
     """``record(model, env) -> data`` (the trajectory recorder's episode loop, save_new_trajectory.py:35-204) on ``RendezvousEnv``: every
     array of the three trajectories the reference recorded (tests/golden/eval_reference.npz; the env's reset replays their initial states)."""
     from reinforcement_learning_rendezvous_amd.params import make_params
-    model = _policy()
+    model = _single_thread_policy()
     g = load_golden("eval_reference.npz")
     for j in range(3):
         s0 = g[f"traj{j}_state0"]
@@ -219,7 +216,7 @@ def check_callback_evaluation(evaluate_policy):
     from reinforcement_learning_rendezvous_amd.params import make_params
     g = load_golden("eval_reference.npz")
     env = _oracle_env(make_params(), tape=g["cb_tape"][:, None, :])
-    out = evaluate_policy(_policy(), env, 24)
+    out = evaluate_policy(_single_thread_policy(), env, 24)
     ref = dict(zip([str(k) for k in g["cb_metric_names"]], g["cb_metrics"]))
     assert list(out) == list(ref)
     for k in ("ep_len", "ep_success", "ep_collision_percentage", "ep_time_of_first_collision", "%_collided_episodes", "%_successfull_episodes"):
