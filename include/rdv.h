@@ -326,6 +326,58 @@ int rdv_get_stats(rdv_handle h, RdvStats* out_host, int reset, void* stream);
 int64_t rdv_num_envs(rdv_handle h);
 
 /*
+ * Parameter groups (added within ABI version 5: additive exports, nothing existing changed): ONE batch, several parameter sets, ONE
+ * launch per step.  The batch is divided into n_groups contiguous groups; group g covers envs [start_g, start_g + size_g), start_g
+ * being the sum of the sizes in front of it, and has its own RdvParams.  What an env computes depends only on its group's
+ * parameters, its global env id, the seed and its actions: it is bit for bit what a stand-alone handle of size_g envs computes that was
+ * created with that group's parameters, the same seed and env_id_offset + start_g.  The use: sensitivity grids, reward tuning and
+ * domain randomisation over blocks of envs without one handle, and one launch boundary per step, for every parameter set.
+ *
+ * The 256-env boundary rule: every group but the last must be a multiple of 256 envs, so that every group BEGINS on a multiple of 256.
+ * The kernels read the parameter block with scalar loads, once per wave, and a workgroup of every step kernel owns 256 consecutive
+ * envs whose finished episodes its four waves reset together from one block; a group per workgroup therefore costs one scalar
+ * load (the group index of the workgroup's 256-env tile, from a table in device memory), a group boundary inside a workgroup
+ * would cost the scalar parameter path.  Only the last group may end anywhere.
+ *
+ * rdv_param_groups_check: host-only, needs no GPU.  RDV_ERR_INVALID_ARGUMENT, with a message naming the offending group, when
+ *   n_groups < 1 or there are more groups than the tile table can tell apart (one int32 index per tile, and no more groups than envs),
+ *   a size is not positive, a group but the last is not a multiple of 256, or the sizes do not sum to n_envs.
+ * rdv_param_groups_validate: host-only.  rdv_params_validate on each of the n_groups sets; RDV_ERR_BAD_PARAMS naming the first bad group.
+ * rdv_set_param_groups: makes the handle grouped (both checks above first).  The env states are kept, as with rdv_set_params.  The
+ *   G derived blocks and the tile table live in a side allocation of their own that this call makes (and frees, when a later call needs
+ *   a larger one): it is the ONE group call that allocates, synchronises `stream` and is not legal inside a stream capture.  rdv_step
+ *   still allocates nothing.  n_groups = 0 (the other arguments are ignored) returns the handle to its single block, the one
+ *   rdv_create / rdv_set_params gave it.  A handle cannot have both groups and a general rigid body: RDV_ERR_BAD_PARAMS here on a
+ *   general-body handle, and from rdv_set_rigid_body with a general body on a grouped handle.
+ * rdv_set_group_params / rdv_get_group_params: one group's set.  The setter is ordered on `stream` by a kernel write, like
+ *   rdv_set_params: legal inside a capture, no synchronisation.  On a grouped handle rdv_set_params and rdv_get_params are refused
+ *   (RDV_ERR_INVALID_ARGUMENT, the message points here).
+ * rdv_num_groups: 0 for an ungrouped handle (-1 for an invalid one).
+ * rdv_get_group_stats: out_host[n_groups]; each group's statistics slots summed on the host in ascending slot order, the order
+ *   rdv_get_stats of the stand-alone handle would use (counters exact, sums bit-equal).  Otherwise as rdv_get_stats, which keeps
+ *   returning the whole batch.
+ * rdv_eval_group_summary: rdv_eval_summary over one group's envs (rdv_eval_summary gives the whole batch, each env's times in its
+ *   own group's dt).
+ *
+ * Which kernel runs: rdv_step launches step_kernel_groups<ST, all> (the FUSED layout with the workgroup's own block) whichever
+ * RdvKernelVariant was asked for, and step_kernel_groups_lane<ST, diag, raw> for the evaluator build and the first step after
+ * rdv_set_state / rdv_restore; rdv_debug_last_kernel names it.  There are no grouped persistent kernels: rdv_step_many and
+ * rdv_rollout run the loop they are defined by (rdv_step, or rdv_policy_act + rdv_step, n_steps times on `stream`), as they do
+ * for general rigid bodies.  rdv_reset, state access and the evaluation calls use each env's own group.  Snapshots hold no
+ * parameters: rdv_restore into a grouped handle of the same n_envs and storage works as before.  A reset tape on a grouped handle is
+ * indexed with the batch's n_envs and global env index.
+ */
+int rdv_param_groups_check(int64_t n_envs, int32_t n_groups, const int64_t* group_sizes_host);
+int rdv_param_groups_validate(const RdvParams* params_host /*[n_groups]*/, int32_t n_groups);
+int rdv_set_param_groups(rdv_handle h, const RdvParams* params_host /*[n_groups]*/, const int64_t* group_sizes_host, int32_t n_groups,
+                         void* stream);
+int rdv_set_group_params(rdv_handle h, int32_t group, const RdvParams* params_host, void* stream);
+int rdv_get_group_params(rdv_handle h, int32_t group, RdvParams* out_host);
+int32_t rdv_num_groups(rdv_handle h);
+int rdv_get_group_stats(rdv_handle h, RdvStats* out_host /*[n_groups]*/, int reset, void* stream);
+int rdv_eval_group_summary(rdv_handle h, int32_t group, const double* eval, RdvEvalSummary* out_host, void* stream);
+
+/*
  * The actor of the reference's shipped checkpoint (SB3 MlpPolicy, 17-64-64-6, tanh; models/mlp_model_best.zip -> policy.pth,
  * built by main.py:36-46) as one kernel: actions = clip(mean(obs) [+ exp(log_std) * N(0,1)], -1, 1), the form SB3's
  * collect_rollouts / predict apply before every env.step.  Weights are HOST pointers in SB3's layout (nn.Linear [out, in]):

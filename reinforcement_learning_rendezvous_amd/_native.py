@@ -27,7 +27,10 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            "rdv_create", "rdv_destroy", "rdv_set_params", "rdv_get_params", "rdv_seed", "rdv_set_reset_tape",
            "rdv_set_kernel_variant", "rdv_rigid_body_default", "rdv_set_rigid_body", "rdv_get_rigid_body",
            "rdv_reset", "rdv_step", "rdv_step_many", "rdv_set_state", "rdv_get_state", "rdv_get_aux", "rdv_snapshot_bytes", "rdv_snapshot", "rdv_restore", "rdv_observe", "rdv_diagnose",
-           "rdv_eval_begin", "rdv_eval_summary", "rdv_get_stats", "rdv_num_envs", "rdv_policy_create", "rdv_policy_destroy", "rdv_policy_act", "rdv_critic_create", "rdv_policy_value", "rdv_rollout"]
+           "rdv_eval_begin", "rdv_eval_summary", "rdv_get_stats", "rdv_num_envs", "rdv_policy_create", "rdv_policy_destroy", "rdv_policy_act", "rdv_critic_create", "rdv_policy_value", "rdv_rollout",
+           # parameter groups (added within ABI 5)
+           "rdv_param_groups_check", "rdv_param_groups_validate", "rdv_set_param_groups", "rdv_set_group_params", "rdv_get_group_params",
+           "rdv_num_groups", "rdv_get_group_stats", "rdv_eval_group_summary"]
 
 
 class RdvError(RuntimeError):
@@ -81,10 +84,10 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the three translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip) for gfx950 and link librdv_hip.so
+    """Compile the four translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
-    cmd = ["make", "-C", CSRC, "-j3"] + (["-B"] if force else [])
+    cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
     subprocess.check_call(cmd, stdout=subprocess.DEVNULL if quiet else None)
     return LIB_PATH
 
@@ -144,6 +147,14 @@ def lib():
         "rdv_critic_create": (C.c_int, [vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]),
         "rdv_policy_value": (C.c_int, [vp, vp, vp, i64, vp]),
         "rdv_rollout": (C.c_int, [vp, vp, i32, C.POINTER(RolloutOut), C.c_int, u64, u64, vp]),
+        "rdv_param_groups_check": (C.c_int, [i64, i32, C.POINTER(i64)]),
+        "rdv_param_groups_validate": (C.c_int, [PP, i32]),
+        "rdv_set_param_groups": (C.c_int, [vp, PP, C.POINTER(i64), i32, vp]),
+        "rdv_set_group_params": (C.c_int, [vp, i32, PP, vp]),
+        "rdv_get_group_params": (C.c_int, [vp, i32, PP]),
+        "rdv_num_groups": (i32, [vp]),
+        "rdv_get_group_stats": (C.c_int, [vp, C.POINTER(Stats), C.c_int, vp]),
+        "rdv_eval_group_summary": (C.c_int, [vp, i32, vp, C.POINTER(EvalSummary), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

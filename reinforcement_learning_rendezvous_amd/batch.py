@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _native as N
-from .params import EnvParams, make_params
+from .params import EnvParams, group_tile_table, make_params
 
 _STORAGE = {"f32": N.STORAGE_F32, "f64": N.STORAGE_F64, N.STORAGE_F32: N.STORAGE_F32, N.STORAGE_F64: N.STORAGE_F64}
 _ON_DONE = {"reset": N.ON_DONE_RESET, "halt": N.ON_DONE_HALT, "continue": N.ON_DONE_CONTINUE}
@@ -24,11 +24,22 @@ _VARIANT = {"auto": N.VARIANT_AUTO, "fused": N.VARIANT_FUSED, "split": N.VARIANT
 
 class RendezvousBatch:
     def __init__(self, num_envs, params: EnvParams = None, device="cuda:0", storage="f32", on_done="reset", seed=0,
-                 env_id_offset=0, variant="auto", **env_kwargs):
+                 env_id_offset=0, variant="auto", group_sizes=None, **env_kwargs):
         """``env_kwargs`` are the keyword arguments of the reference constructor (rendezvous_env.py:17-37).
-        ``variant`` ("auto" | "fused" | "split" | "fused_inlane" | "fused_tiles") selects the step kernel layout; results do not depend on it."""
+        ``variant`` ("auto" | "fused" | "split" | "fused_inlane" | "fused_tiles") selects the step kernel layout; results do not depend on it.
+        ``params`` as a LIST of EnvParams with ``group_sizes`` makes the batch grouped (include/rdv.h, parameter groups): group g is
+        the next ``group_sizes[g]`` envs and steps with ``params[g]``, all groups in one launch; every group but the last must be a
+        multiple of 256 envs.  Each env computes what it would in a batch of its own with ``env_id_offset + start_g``."""
         if params is not None and env_kwargs:
             raise TypeError("pass either params or the reference constructor's keyword arguments, not both")
+        groups = None
+        if isinstance(params, (list, tuple)):
+            if group_sizes is None or len(group_sizes) != len(params):
+                raise TypeError("a list of params needs group_sizes of the same length")
+            group_tile_table(num_envs, group_sizes)          # the checks of rdv_param_groups_check, before anything is allocated
+            groups, params = [p.copy() for p in params], params[0]
+        elif group_sizes is not None:
+            raise TypeError("group_sizes goes with a list of params")
         self.params = params.copy() if params is not None else make_params(**env_kwargs)
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -53,6 +64,9 @@ class RendezvousBatch:
                                      C.c_uint64(seed), C.c_uint64(env_id_offset), self._ws.data_ptr(),
                                      C.byref(self._h)))
         N.check(self._lib.rdv_set_kernel_variant(self._h, _VARIANT[variant]))
+        self.group_params, self.group_sizes = None, None
+        if groups is not None:
+            self.set_param_groups(groups, group_sizes)
         n, dev = self.num_envs, self.device
         self._pending = None      # (source tensors) of a step_many / rollout whose last rows have not been copied into obs / reward / done yet
         self._obs = self._alloc("obs", (n, N.OBS_DIM), torch.float32)
@@ -202,11 +216,14 @@ class RendezvousBatch:
         N.check(self._lib.rdv_eval_begin(self._h, self.eval.data_ptr(), self._stream()))
         return self.eval
 
-    def eval_summary(self):
-        """The twelve means ``CustomWandbCallback.evaluate_policy`` logs (custom_callbacks.py:285-298) over the batch's envs, reduced
-        on the device (one wavefront reduction per 64 envs)."""
+    def eval_summary(self, group=None):
+        """The twelve means ``CustomWandbCallback.evaluate_policy`` logs (custom_callbacks.py:285-298) over the batch's envs — or over
+        the envs of parameter group ``group`` — reduced on the device (one wavefront reduction per 64 envs)."""
         st = N.EvalSummary()
-        N.check(self._lib.rdv_eval_summary(self._h, self.eval.data_ptr(), C.byref(st), self._stream()))
+        if group is None:
+            N.check(self._lib.rdv_eval_summary(self._h, self.eval.data_ptr(), C.byref(st), self._stream()))
+        else:
+            N.check(self._lib.rdv_eval_group_summary(self._h, int(group), self.eval.data_ptr(), C.byref(st), self._stream()))
         d = {k: float(getattr(st, k)) for k, _ in N.EvalSummary._fields_[:-1]}
         d["%_collided_episodes"] = d.pop("pct_collided_episodes")
         d["%_successfull_episodes"] = d.pop("pct_successful_episodes")
@@ -307,8 +324,8 @@ class RendezvousBatch:
         """An independent batch in the same state — what ``copy.deepcopy(env)`` gives the reference (utils/environment_utils.py:66-73;
         main.py:83 makes its ``eval_env`` that way): same parameters, rigid bodies, seed, reset tape and kernel variant; state,
         bookkeeping, episode counters and statistics through ``snapshot`` / ``restore``.  The two share nothing afterwards."""
-        other = RendezvousBatch(self.num_envs, params=self.params, device=self.device, seed=self._seed,
-                                env_id_offset=self.env_id_offset, **self._ctor)
+        other = RendezvousBatch(self.num_envs, params=self.group_params or self.params, group_sizes=self.group_sizes, device=self.device,
+                                seed=self._seed, env_id_offset=self.env_id_offset, **self._ctor)
         body = self.get_rigid_body()
         other.set_rigid_body(inertia=body["inertia"], inertia_target=body["inertia_target"], torque=body["torque"],
                              torque_target=body["torque_target"], integrator=body["integrator"], rtol=body["rtol"], atol=body["atol"])
@@ -349,6 +366,54 @@ class RendezvousBatch:
     def set_params(self, params: EnvParams):
         N.check(self._lib.rdv_set_params(self._h, C.byref(params), self._stream()))
         self.params = params.copy()
+
+    def get_params(self):
+        p = EnvParams()
+        N.check(self._lib.rdv_get_params(self._h, C.byref(p)))
+        return p
+
+    # ------------------------------------------------------------------------------------------------ parameter groups
+    def set_param_groups(self, params, group_sizes):
+        """Divide the batch into contiguous groups of ``group_sizes`` envs with the parameters ``params[g]`` (include/rdv.h,
+        rdv_set_param_groups: allocates, synchronises the stream; states are kept).  Empty lists return it to its single block."""
+        g = len(params)
+        if g != len(group_sizes):
+            raise TypeError("set_param_groups: params and group_sizes differ in length")
+        if g == 0:
+            N.check(self._lib.rdv_set_param_groups(self._h, None, None, 0, self._stream()))
+            self.group_params, self.group_sizes = None, None
+            return
+        block = (EnvParams * g)(*[p.copy() for p in params])
+        sizes = (C.c_int64 * g)(*[int(x) for x in group_sizes])
+        N.check(self._lib.rdv_set_param_groups(self._h, block, sizes, g, self._stream()))
+        self.group_params, self.group_sizes = [p.copy() for p in params], [int(x) for x in group_sizes]
+
+    @property
+    def num_groups(self):
+        """Number of parameter groups; 0 for a batch with one parameter set."""
+        return int(self._lib.rdv_num_groups(self._h))
+
+    @property
+    def group_slices(self):
+        """``slice(start_g, start_g + size_g)`` of every group, for indexing the [N, ...] tensors."""
+        starts = np.concatenate([[0], np.cumsum(self.group_sizes or [])])
+        return [slice(int(a), int(b)) for a, b in zip(starts[:-1], starts[1:])]
+
+    def set_group_params(self, group, params: EnvParams):
+        """One group's parameters, ordered on the current stream like ``set_params``."""
+        N.check(self._lib.rdv_set_group_params(self._h, int(group), C.byref(params), self._stream()))
+        self.group_params[int(group)] = params.copy()
+
+    def get_group_params(self, group):
+        p = EnvParams()
+        N.check(self._lib.rdv_get_group_params(self._h, int(group), C.byref(p)))
+        return p
+
+    def get_group_stats(self, reset=False):
+        """``get_stats`` per group: what a batch of that group alone would report."""
+        st = (N.Stats * self.num_groups)()
+        N.check(self._lib.rdv_get_group_stats(self._h, st, int(bool(reset)), self._stream()))
+        return [x.to_dict() for x in st]
 
     def set_rigid_body(self, inertia=None, inertia_target=None, torque=None, torque_target=None, integrator=None,
                        rtol=None, atol=None):
@@ -399,8 +464,13 @@ class RendezvousBatch:
         N.check(self._lib.rdv_set_kernel_variant(self._h, _VARIANT[variant]))
         self._ctor["variant"] = variant
 
-    def set_reward_kwargs(self, **kw):
-        """The reference passes these to get_bubble_reward on every step (rendezvous_env.py:211, :313)."""
+    def set_reward_kwargs(self, group=None, **kw):
+        """The reference passes these to get_bubble_reward on every step (rendezvous_env.py:211, :313).  ``group``: of that parameter
+        group (required on a grouped batch)."""
+        if group is not None:
+            p = self.get_group_params(group)
+            p.update(**kw)
+            return self.set_group_params(group, p)
         p = self.params.copy()
         p.update(**kw)
         self.set_params(p)

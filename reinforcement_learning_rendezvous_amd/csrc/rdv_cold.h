@@ -7,10 +7,11 @@
 namespace rdv {
 
 // reset() for all envs or where mask != 0; the env's prepared slot is refilled for the episode after the one that starts here
+// (the bodies of the cold kernels are functions of the parameter block so that the kernels of parameter groups, csrc/rdv_groups.hip,
+//  run the same code with their workgroup's own block)
 template <typename ST>
-__global__ __launch_bounds__(kBlock) void reset_kernel(const DevParams* __restrict__ Pp, const StepArgs A, const uint8_t* mask, float* obs, int fresh) {
+__device__ __forceinline__ void reset_lane(const DevParams& P, const StepArgs& A, const uint8_t* mask, float* obs, int fresh) {
   using V = typename Vec4<ST>::type;
-  const DevParams& P = *Pp;
   const int64_t n = A.n;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
@@ -29,13 +30,16 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const DevParams* __restri
   }
   refill_whole<ST>(A, P, i, counter + 1u);
 }
+template <typename ST>
+__global__ __launch_bounds__(kBlock) void reset_kernel(const DevParams* __restrict__ Pp, const StepArgs A, const uint8_t* mask, float* obs, int fresh) {
+  reset_lane<ST>(*Pp, A, mask, obs, fresh);
+}
 
 enum { ACC_SET_STATE = 0, ACC_GET_STATE, ACC_GET_AUX, ACC_OBSERVE, ACC_DIAGNOSE, ACC_EVAL_BEGIN, ACC_CLEAR_HALTED };
 
 // state access / evaluator helpers (cold paths; one lane per env, row-major host-facing arrays)
 template <typename ST>
-__global__ __launch_bounds__(kBlock) void access_kernel(const DevParams P, void* ws_, int64_t n, int64_t cs, int what, const double* in,
-                                                        double* out, float* out_f32) {
+__device__ __forceinline__ void access_lane(const DevParams& P, void* ws_, int64_t n, int64_t cs, int what, const double* in, double* out, float* out_f32) {
   using V = typename Vec4<ST>::type;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   if (i >= n) return;
@@ -75,13 +79,18 @@ __global__ __launch_bounds__(kBlock) void access_kernel(const DevParams P, void*
     eval_accumulate(P, e, d, dg, 0.0, true, out + i * kEvalDim);
   }
 }
+template <typename ST>
+__global__ __launch_bounds__(kBlock) void access_kernel(const DevParams P, void* ws_, int64_t n, int64_t cs, int what, const double* in,
+                                                        double* out, float* out_f32) {
+  access_lane<ST>(P, ws_, n, cs, what, in, out, out_f32);
+}
 
 // The means CustomWandbCallback.evaluate_policy logs (custom_callbacks.py:254-298) over the batch's envs, from the evaluation
 // accumulators and the final state: one wavefront reduction (DPP sums, fixed order) per 64 envs into that wave's 16-double slot; the
 // host adds the slots in index order.
 enum { EV_REW = 0, EV_LEN, EV_DIST, EV_DV, EV_DW, EV_SUCC, EV_COLLP, EV_TFIRST, EV_TFIRST_N, EV_MINPOS, EV_MINPOS_N, EV_AVGATT, EV_NCOLL, EV_NSUCC, EV_N, EV_SLOTS = 16 };
 template <typename ST>
-__global__ __launch_bounds__(kBlock) void eval_summary_kernel(const DevParams P, const void* ws_, int64_t n, int64_t cs, const double* eval, double* partial) {
+__device__ __forceinline__ void eval_summary_lane(const DevParams& P, const void* ws_, int64_t n, int64_t cs, const double* eval, double* partial) {
   using V = typename Vec4<ST>::type;
   const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
   const int lane = threadIdx.x & (kWave - 1);
@@ -111,7 +120,12 @@ __global__ __launch_bounds__(kBlock) void eval_summary_kernel(const DevParams P,
     if (lane == 0 && (i - lane) < n) slot[j] = s;
   }
 }
+template <typename ST>
+__global__ __launch_bounds__(kBlock) void eval_summary_kernel(const DevParams P, const void* ws_, int64_t n, int64_t cs, const double* eval, double* partial) {
+  eval_summary_lane<ST>(P, ws_, n, cs, eval, partial);
+}
 
+#ifndef RDV_COLD_LANES_ONLY   // (rdv_groups.hip takes the lane functions above; the kernels below belong to rdv_hip.hip)
 // The derived parameter block travels as a kernel argument and is written by the device: ordered on the caller's stream like
 // every other launch (a hipMemcpy from host memory is ordered against the legacy stream only, not against PyTorch's non-blocking
 // side streams) and legal inside a stream capture (the values are baked into the graph node).
@@ -125,5 +139,6 @@ __global__ __launch_bounds__(kWave) void device_error_kernel(uint32_t* word, uin
   if (threadIdx.x == 0) __hip_atomic_fetch_or(word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 static_assert(sizeof(DevParams) % 4 == 0 && sizeof(DevParams) <= 3072, "DevParams is passed by value to params_kernel");
+#endif
 
 }  // namespace rdv

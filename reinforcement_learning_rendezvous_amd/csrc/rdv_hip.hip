@@ -2,7 +2,8 @@
 // checks, launches, snapshot / restore, statistics), the derivation of the thresholds the kernels compare against (derive_params),
 // rigid-body validation and the workspace layout.  The kernels it launches live in the headers included below: rdv_step.h and
 // rdv_fused.h (one-launch step kernels), rdv_cold.h (reset, state access, evaluation summary), rdv_policy.h (actor / critic),
-// rdv_rollout.h and rdv_step_many.h (persistent kernels); rdv_tiles.hip and rdv_general.hip are translation units of their own.
+// rdv_rollout.h and rdv_step_many.h (persistent kernels); rdv_tiles.hip, rdv_general.hip and rdv_groups.hip (parameter groups) are
+// translation units of their own.
 // The data layout in HBM is described in rdv_kernels.h.
 #include "rdv_device.h"
 #include "rdv_policy.h"
@@ -28,6 +29,7 @@
 #include "rdv_step_many.h"
 #include "rdv_tiles.h"
 #include "rdv_general.h"
+#include "rdv_groups.h"
 
 namespace rdv {
 
@@ -232,6 +234,15 @@ struct RdvEnvBatch {
   unsigned long long* stamps = nullptr;
 #endif
   std::vector<uint64_t> host_slots;
+  // parameter groups (rdv_set_param_groups): n_groups == 0 is the single block above.  The G blocks and the tile table are a side
+  // allocation of their own (the workspace layout, which snapshots and caller-provided workspaces depend on, does not change).
+  int32_t n_groups = 0;
+  std::vector<RdvParams> group_params;
+  std::vector<DevParams> group_dev;
+  std::vector<int64_t> group_start;      // [G + 1]: group g is envs [group_start[g], group_start[g + 1])
+  void* group_mem = nullptr;             // device: G blocks, then the tile table
+  size_t group_mem_bytes = 0;
+  GroupTable group_table = {nullptr, nullptr};
 };
 static constexpr uint32_t kMagic = 0x52445631u;   // "RDV1"
 static void apply_rigid_body(RdvEnvBatch* h);
@@ -463,8 +474,8 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   RDV_CHECK_FAULT(h);
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->general) {
-    // General rigid bodies: rdv_policy_act + rdv_step, n_steps times, on `stream` — the definition of this call's results, used as
+  if (h->general || h->n_groups) {
+    // General rigid bodies and parameter groups (no grouped persistent kernel): rdv_policy_act + rdv_step, n_steps times, on `stream` — the definition of this call's results, used as
     // its implementation.  The per-lane RK45 inside the 168-register budget of the persistent kernel's 12-wave workgroup spilled 120
     // dwords per lane and ran SLOWER than this loop (72 against 58 us per step at 65,536 envs, round 2): not offered any more.
     const int64_t n = h->n;
@@ -590,6 +601,7 @@ int rdv_destroy(rdv_handle h) {
   DeviceGuard guard(h->device);
   (void)hipDeviceSynchronize();
   if (h->own_ws) (void)hipFree(h->ws);
+  if (h->group_mem) (void)hipFree(h->group_mem);
   h->magic = 0;
   delete h;
   return RDV_OK;
@@ -647,27 +659,40 @@ static int validate_rigid_body(const RdvRigidBody* b, bool* general) {
   *general = b->integrator == RDV_INTEGRATOR_RK45 || !closed;
   return RDV_OK;
 }
-static void apply_rigid_body(RdvEnvBatch* h) {   // h->body (validated) -> the kGeneral block of h->dev
-  const RdvRigidBody& b = h->body;
+static void apply_body(const RdvRigidBody& b, DevParams& dev) {   // a validated body -> the kGeneral block of `dev`
   const double* tensors[2] = {b.inertia_chaser, b.inertia_target};
   const double* torques[2] = {b.torque_chaser, b.torque_target};
   for (int k = 0; k < 2; ++k) {
-    for (int i = 0; i < 9; ++i) h->dev.body_inertia[k][i] = tensors[k][i];
-    (void)invert3(tensors[k], h->dev.body_inv_inertia[k]);
-    for (int i = 0; i < 3; ++i) h->dev.body_torque[k][i] = torques[k][i];
+    for (int i = 0; i < 9; ++i) dev.body_inertia[k][i] = tensors[k][i];
+    (void)invert3(tensors[k], dev.body_inv_inertia[k]);
+    for (int i = 0; i < 3; ++i) dev.body_torque[k][i] = torques[k][i];
   }
-  h->dev.rk_rtol = b.rtol; h->dev.rk_atol = b.atol;
+  dev.rk_rtol = b.rtol; dev.rk_atol = b.atol;
   // per body: RK45 where the closed form does not apply to THAT body (or was asked for): a tri-axial target leaves the chaser on it
-  for (int k = 0; k < 2; ++k) h->dev.body_general[k] = (b.integrator == RDV_INTEGRATOR_RK45 || !closed_form_applies(tensors[k], torques[k])) ? 1 : 0;
-  if (b.integrator == RDV_INTEGRATOR_EXACT) h->dev.body_general[0] = h->dev.body_general[1] = 0;
+  for (int k = 0; k < 2; ++k) dev.body_general[k] = (b.integrator == RDV_INTEGRATOR_RK45 || !closed_form_applies(tensors[k], torques[k])) ? 1 : 0;
+  if (b.integrator == RDV_INTEGRATOR_EXACT) dev.body_general[0] = dev.body_general[1] = 0;
+}
+static void apply_rigid_body(RdvEnvBatch* h) { apply_body(h->body, h->dev); }
+// one group's derived block -> its place in the device table, ordered on `s` (params_kernel, as upload_params)
+static int upload_group(RdvEnvBatch* h, int32_t g, hipStream_t s) {
+  hipLaunchKernelGGL(params_kernel, dim3(1), dim3(kWave), 0, s, h->group_dev[(size_t)g], const_cast<DevParams*>(h->group_table.params) + g);
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
 }
 int rdv_set_rigid_body(rdv_handle h, const RdvRigidBody* b, void* stream) {
   RDV_CHECK_HANDLE(h);
   bool general = false;
   if (int rc = validate_rigid_body(b, &general)) return rc;
+  if (general && h->n_groups)
+    return fail(RDV_ERR_BAD_PARAMS, "rdv_set_rigid_body: a general rigid body (RK45) cannot be combined with parameter groups: this handle has %d groups "
+                                    "(rdv_set_param_groups with n_groups = 0 returns it to one block)", h->n_groups);
   DeviceGuard guard(h->device);
   h->body = *b; h->general = general;
   apply_rigid_body(h);
+  for (int32_t g = 0; g < h->n_groups; ++g) {
+    apply_body(h->body, h->group_dev[(size_t)g]);
+    if (int rc = upload_group(h, g, static_cast<hipStream_t>(stream))) return rc;
+  }
   return upload_params(h, static_cast<hipStream_t>(stream));
 }
 int rdv_get_rigid_body(rdv_handle h, RdvRigidBody* out) {
@@ -679,6 +704,7 @@ int rdv_get_rigid_body(rdv_handle h, RdvRigidBody* out) {
 
 int rdv_set_params(rdv_handle h, const RdvParams* p, void* stream) {
   RDV_CHECK_HANDLE(h);
+  if (h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_set_params: this handle has %d parameter groups: use rdv_set_group_params (or rdv_set_param_groups)", h->n_groups);
   if (int rc = rdv_params_validate(p)) return rc;
   DeviceGuard guard(h->device);
   h->params = *p; derive_params(*p, h->dev);
@@ -690,6 +716,7 @@ int rdv_set_params(rdv_handle h, const RdvParams* p, void* stream) {
 int rdv_get_params(rdv_handle h, RdvParams* out) {
   RDV_CHECK_HANDLE(h);
   if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_params: null output");
+  if (h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_params: this handle has %d parameter groups: use rdv_get_group_params", h->n_groups);
   *out = h->params;
   return RDV_OK;
 }
@@ -730,7 +757,8 @@ int rdv_reset(rdv_handle h, const uint8_t* mask, float* obs_out, void* stream) {
   if (h->fresh && mask) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_reset: the first reset after create/seed must cover all envs (mask = NULL)");
   StepArgs A;
   base_args(h, A);
-  with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(reset_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev_params, A, mask, obs_out, fresh); });
+  if (h->n_groups) launch_reset_groups(h->storage == RDV_STORAGE_F32, grid_for(h->n), s, h->group_table, A, mask, obs_out, fresh);
+  else with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(reset_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev_params, A, mask, obs_out, fresh); });
   RDV_HIP(hipGetLastError());
   if (fresh) h->prepared_ok = true;   // reset_kernel refills the slot of every env it resets: after a full reset all are current
   h->fresh = false;
@@ -762,7 +790,7 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
   // the evaluator-diagnostics build and the first step after rdv_set_state (kRaw)
   const bool raw = h->raw_state && !h->general;   // (the RK45 kernels integrate the quaternion as given, like the reference)
   h->raw_state = false;
-  const bool split = !A.diag && !A.eval && !h->general && !raw && (h->variant == RDV_VARIANT_SPLIT || (h->variant == RDV_VARIANT_AUTO && h->n <= kSplitAutoMaxEnvs));
+  const bool split = !A.diag && !A.eval && !h->general && !raw && !h->n_groups && (h->variant == RDV_VARIANT_SPLIT || (h->variant == RDV_VARIANT_AUTO && h->n <= kSplitAutoMaxEnvs));
   // every launch records the kernel's name, as spelled here, on the handle (host only: rdv_debug_last_kernel)
 #define RDV_LAUNCH(GRID, BLOCK, ...) do { hipLaunchKernelGGL((__VA_ARGS__), GRID, BLOCK, 0, s, A.ws, A.actions, h->dev_params, A.n, A.stats, A.obs, A.reward, A); \
                                            h->last_kernel = #__VA_ARGS__; } while (0)
@@ -791,7 +819,12 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
       A.xcd_per = (int32_t)((grid.x + 7) / 8);
       grid = dim3((unsigned)A.xcd_per * 8u);   // up to 7 padding workgroups, which find no envs
     }
-    if (h->general) {
+    if (h->n_groups) {
+      // rdv_groups.hip: every workgroup binds the block of its tile's group.  The evaluator build and the first step after rdv_set_state run
+      // the in-lane form, everything else — whichever variant was asked for — the reset-by-part form
+      if (raw || dg) h->last_kernel = launch_step_groups_lane(f32, dg, raw, grid, s, h->group_table, A);
+      else h->last_kernel = launch_step_groups(f32, h->on_done != RDV_ON_DONE_HALT, grid, s, h->group_table, A);
+    } else if (h->general) {
       // rdv_general.hip: a general TARGET is integrated on partner waves beside the chaser half of the transition (step_kernel_general);
       // the evaluator build, and a general chaser beside the reference's target, run the fused per-lane form
       h->last_kernel = launch_step_general(f32, dg, h->dev.body_general[1] != 0 && h->split_general != 0, h->n, grid, s, h->dev_params, A);
@@ -839,8 +872,8 @@ int rdv_step_many(rdv_handle h, const float* actions, int32_t n_steps, const Rdv
     return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_step_many: actions must be 8-byte aligned and obs 16-byte aligned");
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->general) {
-    // General rigid bodies: n_steps launches of rdv_step on `stream` (the definition of this call's results, used as its
+  if (h->general || h->n_groups) {
+    // General rigid bodies and parameter groups: n_steps launches of rdv_step on `stream` (the definition of this call's results, used as its
     // implementation): the per-lane RK45 does not fit the persistent kernel's register budget without scratch (round 2: 60 spilled
     // dwords per lane), and a step is bound by the integrator, not by the launch boundary this call exists to remove.
     const int64_t n = h->n;
@@ -875,7 +908,8 @@ int rdv_step_many(rdv_handle h, const float* actions, int32_t n_steps, const Rdv
 static int access(rdv_handle h, int what, const double* in, double* out, float* out_f32, void* stream) {
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(access_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev, h->ws, h->n, h->cs, what, in, out, out_f32); });
+  if (h->n_groups) launch_access_groups(h->storage == RDV_STORAGE_F32, grid_for(h->n), s, h->group_table, h->ws, h->n, h->cs, what, in, out, out_f32);
+  else with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(access_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev, h->ws, h->n, h->cs, what, in, out, out_f32); });
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }
@@ -980,12 +1014,12 @@ int rdv_eval_begin(rdv_handle h, double* eval, void* stream) {
   if (h->fresh) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_begin: call rdv_reset first");
   return access(h, ACC_EVAL_BEGIN, nullptr, eval, nullptr, stream);
 }
-int rdv_eval_summary(rdv_handle h, const double* eval, RdvEvalSummary* out, void* stream) {
-  RDV_CHECK_HANDLE(h);
-  if (!eval || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_summary: null accumulators / output");
+// the evaluation summary of envs [first, last) (whole waves, or up to the batch's end): rdv_eval_summary, rdv_eval_group_summary
+static int eval_summary_of(rdv_handle h, const double* eval, RdvEvalSummary* out, int64_t first, int64_t last, void* stream) {
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(eval_summary_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev, h->ws, h->n, h->cs, eval, h->eval_partial); });
+  if (h->n_groups) launch_eval_summary_groups(h->storage == RDV_STORAGE_F32, grid_for(h->n), s, h->group_table, h->ws, h->n, h->cs, eval, h->eval_partial);
+  else with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(eval_summary_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev, h->ws, h->n, h->cs, eval, h->eval_partial); });
   RDV_HIP(hipGetLastError());
   const size_t waves = (size_t)((h->n + kWave - 1) / kWave);
   h->host_eval.resize(waves * EV_SLOTS);
@@ -993,7 +1027,7 @@ int rdv_eval_summary(rdv_handle h, const double* eval, RdvEvalSummary* out, void
   if (int rc = read_fault_word(h, s)) return rc;
   RDV_CHECK_FAULT(h);
   double t[EV_SLOTS] = {0};
-  for (size_t w = 0; w < waves; ++w)      // fixed order: reproducible sums
+  for (size_t w = (size_t)(first / kWave); w < (size_t)((last + kWave - 1) / kWave); ++w)      // fixed order: reproducible sums
     for (int j = 0; j <= EV_N; ++j) t[j] += h->host_eval[w * EV_SLOTS + j];
   const double m = t[EV_N];
   std::memset(out, 0, sizeof *out);
@@ -1006,25 +1040,145 @@ int rdv_eval_summary(rdv_handle h, const double* eval, RdvEvalSummary* out, void
   out->pct_collided_episodes = t[EV_NCOLL] / m * 100.0; out->pct_successful_episodes = t[EV_NSUCC] / m * 100.0;   // :270-271
   return RDV_OK;
 }
-
-int rdv_get_stats(rdv_handle h, RdvStats* out, int reset, void* stream) {
+int rdv_eval_summary(rdv_handle h, const double* eval, RdvEvalSummary* out, void* stream) {
   RDV_CHECK_HANDLE(h);
-  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_stats: null output");
-  DeviceGuard guard(h->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (!eval || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_summary: null accumulators / output");
+  return eval_summary_of(h, eval, out, 0, h->n, stream);
+}
+int rdv_eval_group_summary(rdv_handle h, int32_t group, const double* eval, RdvEvalSummary* out, void* stream) {
+  RDV_CHECK_HANDLE(h);
+  if (!eval || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_group_summary: null accumulators / output");
+  if (group < 0 || group >= h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_group_summary: group %d of %d", group, h->n_groups);
+  return eval_summary_of(h, eval, out, h->group_start[(size_t)group], h->group_start[(size_t)group + 1], stream);
+}
+
+// the statistics slots -> the host (synchronises `stream`, reads the device error word; reset: zeroes them behind the copy)
+static int fetch_slots(RdvEnvBatch* h, int reset, hipStream_t s) {
   const size_t bytes = h->host_slots.size() * sizeof(uint64_t);
   RDV_HIP(hipMemcpyAsync(h->host_slots.data(), h->stats, bytes, hipMemcpyDeviceToHost, s));
-  if (int rc = read_fault_word(h, s, reset ? bytes : 0)) return rc;
+  return read_fault_word(h, s, reset ? bytes : 0);
+}
+// the slots of waves [first, last) summed in ascending order: the sums are reproducible run to run
+static void sum_slots(const RdvEnvBatch* h, size_t first, size_t last, RdvStats* out) {
   std::memset(out, 0, sizeof *out);
-  const size_t waves = h->host_slots.size() / kStatWords;
-  for (size_t w = 0; w < waves; ++w) {   // fixed order: the sums are reproducible run to run
+  for (size_t w = first; w < last; ++w) {
     const uint64_t* sl = h->host_slots.data() + w * kStatWords;
     const double* sd = reinterpret_cast<const double*>(sl);
     out->env_steps += sl[ST_STEPS]; out->episodes += sl[ST_EPISODES]; out->successes += sl[ST_SUCCESS]; out->collisions += sl[ST_COLLIDED];
     for (int r = 0; r < 4; ++r) out->reasons[r] += sl[ST_REASON0 + r];
     out->sum_length += (double)sl[ST_SUM_LEN]; out->sum_return += sd[ST_SUM_RET]; out->sum_delta_v += sd[ST_SUM_DV]; out->sum_delta_w += sd[ST_SUM_DW];
   }
+}
+int rdv_get_stats(rdv_handle h, RdvStats* out, int reset, void* stream) {
+  RDV_CHECK_HANDLE(h);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_stats: null output");
+  DeviceGuard guard(h->device);
+  if (int rc = fetch_slots(h, reset, static_cast<hipStream_t>(stream))) return rc;
+  sum_slots(h, 0, h->host_slots.size() / kStatWords, out);
   return rdv_device_error_code(h->device_error);   // RDV_OK unless a kernel of this handle reported a fault (the statistics are filled either way)
 }
+int rdv_get_group_stats(rdv_handle h, RdvStats* out, int reset, void* stream) {
+  RDV_CHECK_HANDLE(h);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_group_stats: null output");
+  if (!h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_group_stats: this handle has no parameter groups (rdv_get_stats)");
+  DeviceGuard guard(h->device);
+  if (int rc = fetch_slots(h, reset, static_cast<hipStream_t>(stream))) return rc;
+  // a group begins on a 256-env boundary, so its waves are a range of slots: the range a stand-alone handle of that group would sum
+  for (int32_t g = 0; g < h->n_groups; ++g)
+    sum_slots(h, (size_t)(h->group_start[(size_t)g] / kWave), (size_t)((h->group_start[(size_t)g + 1] + kWave - 1) / kWave), out + g);
+  return rdv_device_error_code(h->device_error);
+}
+
+// ---- parameter groups ----------------------------------------------------------------------------------------------
+int rdv_param_groups_check(int64_t n_envs, int32_t n_groups, const int64_t* sizes) {
+  if (n_groups < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_check: n_groups = %d: a grouped batch has at least group 0", n_groups);
+  if (!sizes) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_check: null group sizes");
+  // the tile table holds one int32 group index per 256 envs; a group has at least one env, so no more groups than envs fit either
+  if ((int64_t)n_groups > n_envs) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_check: group %d does not fit: %d groups for %lld envs", n_groups - 1, n_groups, (long long)n_envs);
+  int64_t at = 0;
+  for (int32_t g = 0; g < n_groups; ++g) {
+    if (sizes[g] <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_check: group %d has size %lld: sizes must be positive", g, (long long)sizes[g]);
+    if (g + 1 < n_groups && sizes[g] % kGroupTile != 0)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_check: group %d has size %lld: every group but the last must be a multiple of %d envs "
+                                            "(a workgroup of 256 envs shares one parameter block)", g, (long long)sizes[g], kGroupTile);
+    at += sizes[g];
+    if (at > n_envs) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_check: group %d ends at env %lld, the batch has %lld envs", g, (long long)at, (long long)n_envs);
+  }
+  if (at != n_envs) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_check: group %d (the last) ends at env %lld, the batch has %lld envs", n_groups - 1, (long long)at, (long long)n_envs);
+  return RDV_OK;
+}
+int rdv_param_groups_validate(const RdvParams* params, int32_t n_groups) {
+  if (!params || n_groups < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_param_groups_validate: null params / no group");
+  for (int32_t g = 0; g < n_groups; ++g)
+    if (rdv_params_validate(params + g)) {
+      char why[400];
+      std::snprintf(why, sizeof why, "%s", g_err);
+      return fail(RDV_ERR_BAD_PARAMS, "parameters of group %d: %s", g, why);
+    }
+  return RDV_OK;
+}
+int rdv_set_param_groups(rdv_handle h, const RdvParams* params, const int64_t* sizes, int32_t n_groups, void* stream) {
+  RDV_CHECK_HANDLE(h);
+  if (n_groups == 0) {   // back to the handle's single block (the side allocation stays until rdv_destroy or the next grouping)
+    if (h->n_groups) h->prepared_ok = false;
+    h->n_groups = 0;
+    return RDV_OK;
+  }
+  if (h->general) return fail(RDV_ERR_BAD_PARAMS, "rdv_set_param_groups: parameter groups cannot be combined with a general rigid body (RK45): this handle has one (rdv_set_rigid_body)");
+  if (int rc = rdv_param_groups_check(h->n, n_groups, sizes)) return rc;
+  if (int rc = rdv_param_groups_validate(params, n_groups)) return rc;
+  DeviceGuard guard(h->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t tiles = (h->n + kGroupTile - 1) / kGroupTile, entries = align_up(tiles, 8);   // the XCD order pads the grid to a multiple of 8
+  const size_t block_bytes = (size_t)align_up((int64_t)n_groups * (int64_t)sizeof(DevParams), 256), bytes = block_bytes + (size_t)entries * sizeof(int32_t);
+  if (bytes > h->group_mem_bytes) {
+    h->n_groups = 0;
+    if (h->group_mem) { RDV_HIP(hipStreamSynchronize(s)); (void)hipFree(h->group_mem); h->group_mem = nullptr; h->group_mem_bytes = 0; }
+    hipError_t err = hipMalloc(&h->group_mem, bytes);
+    if (err != hipSuccess) { (void)hipGetLastError(); h->group_mem = nullptr; return fail(RDV_ERR_OUT_OF_MEMORY, "rdv_set_param_groups: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(err)); }
+    h->group_mem_bytes = bytes;
+  }
+  h->group_params.assign(params, params + n_groups);
+  h->group_dev.resize((size_t)n_groups);
+  h->group_start.assign((size_t)n_groups + 1, 0);
+  std::vector<int32_t> table((size_t)entries);
+  for (int32_t g = 0; g < n_groups; ++g) {
+    derive_params(params[g], h->group_dev[(size_t)g]);
+    h->group_dev[(size_t)g].acos_table = h->acos_table;
+    apply_body(h->body, h->group_dev[(size_t)g]);
+    h->group_start[(size_t)g + 1] = h->group_start[(size_t)g] + sizes[g];
+    for (int64_t t = h->group_start[(size_t)g] / kGroupTile; t < (h->group_start[(size_t)g + 1] + kGroupTile - 1) / kGroupTile; ++t) table[(size_t)t] = g;
+  }
+  for (int64_t t = tiles; t < entries; ++t) table[(size_t)t] = n_groups - 1;
+  char* const base = static_cast<char*>(h->group_mem);
+  // the copies leave pageable host memory that this call owns: ordered on `stream`, and waited for before it returns
+  RDV_HIP(hipMemcpyAsync(base, h->group_dev.data(), (size_t)n_groups * sizeof(DevParams), hipMemcpyHostToDevice, s));
+  RDV_HIP(hipMemcpyAsync(base + block_bytes, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  RDV_HIP(hipStreamSynchronize(s));
+  h->group_table.params = reinterpret_cast<const DevParams*>(base);
+  h->group_table.tile_group = reinterpret_cast<const int32_t*>(base + block_bytes);
+  h->n_groups = n_groups;
+  h->prepared_ok = false;
+  return RDV_OK;
+}
+int rdv_set_group_params(rdv_handle h, int32_t group, const RdvParams* p, void* stream) {
+  RDV_CHECK_HANDLE(h);
+  if (group < 0 || group >= h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_set_group_params: group %d of %d", group, h->n_groups);
+  if (int rc = rdv_params_validate(p)) return rc;
+  DeviceGuard guard(h->device);
+  DevParams& dev = h->group_dev[(size_t)group];
+  h->group_params[(size_t)group] = *p; derive_params(*p, dev);
+  dev.acos_table = h->acos_table;
+  apply_body(h->body, dev);
+  return upload_group(h, group, static_cast<hipStream_t>(stream));
+}
+int rdv_get_group_params(rdv_handle h, int32_t group, RdvParams* out) {
+  RDV_CHECK_HANDLE(h);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_group_params: null output");
+  if (group < 0 || group >= h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_group_params: group %d of %d", group, h->n_groups);
+  *out = h->group_params[(size_t)group];
+  return RDV_OK;
+}
+int32_t rdv_num_groups(rdv_handle h) { return (h && h->magic == kMagic) ? h->n_groups : -1; }
 
 }  // extern "C"

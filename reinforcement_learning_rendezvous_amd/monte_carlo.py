@@ -140,6 +140,41 @@ def run(policy, initial_states, device="cuda:0", storage="f32", config=None, det
     return out
 
 
+@torch.no_grad()
+def sweep(policy, initial_states, configs, device="cuda:0", storage="f32", deterministic=True, seed=0):
+    """``run`` for the same initial conditions under every config of ``configs`` (the reference's sensitivity_analysis.py varies rc0,
+    wt0, koz_radius, corridor_half_angle, h and dt this way, one run per value) in ONE halting batch with one parameter group per
+    config (include/rdv.h, parameter groups): one step launch per timestep for the whole grid.  Each group is padded to a multiple
+    of 256 rows by repeating its last row (groups begin on 256-env boundaries); the padding is dropped from the results.  Returns
+    one table per config, in the format ``run`` returns, equal to ``run(policy, initial_states, config=c)``.  Deterministic actor only
+    (the reference's sweep scripts use ``predict(deterministic=True)``)."""
+    from .batch import RendezvousBatch
+    from .evaluation import episode_steps_bound
+    from .params import GROUP_TILE
+    if not deterministic:
+        raise ValueError("sweep evaluates the deterministic actor (use run_replicas for exploration noise)")
+    params = [make_eval_params(c) for c in configs]
+    unit = _normalised(initial_states)
+    m = len(unit)
+    padded = -(-m // GROUP_TILE) * GROUP_TILE
+    rows = np.concatenate([unit, np.repeat(unit[-1:], padded - m, axis=0)])
+    env = RendezvousBatch(padded * len(params), params=params, group_sizes=[padded] * len(params), device=device, storage=storage,
+                          on_done="halt", seed=seed)
+    policy = policy.to(env.device)
+    env.reset()
+    env.set_state(torch.from_numpy(np.tile(rows, (len(params), 1))))
+    obs = env.observe()
+    env.eval_begin()
+    for _ in range(max(episode_steps_bound(p) for p in params)):      # a halted env is left untouched by the steps after its end
+        obs, _, _ = env.step(policy.act(obs, deterministic=True).contiguous(), accumulate=True)
+    if not bool(env.done.all()):
+        raise RuntimeError("an episode outlived t_max; the time-limit termination is broken")
+    aux = env.get_aux()
+    out = [columns_from_accumulators(env.eval[s][:m], aux[s][:m], p) for s, p in zip(env.group_slices, params)]
+    env.close()
+    return out
+
+
 REPLICA_COLUMNS = COLUMNS          # the stochastic replicas keep all twelve columns (the terminal errors need no error history)
 
 

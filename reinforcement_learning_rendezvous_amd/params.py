@@ -139,3 +139,32 @@ def params_from_config(reward_kwargs=None, config=None, stochastic=True) -> EnvP
         reward_kwargs=reward_kwargs, koz_radius=config.get("koz_radius"),
         corridor_half_angle=config.get("corridor_half_angle"), h=config.get("h"), dt=config.get("dt"),
         t_max=config.get("t_max"))
+
+
+GROUP_TILE = 256      # envs per tile of the group table: the workgroup of every step kernel (include/rdv.h, parameter groups)
+
+
+def group_tile_table(num_envs, group_sizes):
+    """Parameter groups on the host: the group index of every 256-env tile of a batch of ``num_envs`` envs divided into contiguous
+    groups of ``group_sizes`` envs — the table the grouped kernels read (int32, one entry per tile) — after the checks of
+    ``rdv_param_groups_check`` (include/rdv.h): raises ValueError with that call's message.  Every group but the last must be a
+    multiple of 256 envs, because a 256-env workgroup reads one parameter block."""
+    n, sizes = int(num_envs), [int(x) for x in group_sizes]
+    g_count = len(sizes)
+    if g_count < 1:
+        raise ValueError(f"rdv_param_groups_check: n_groups = {g_count}: a grouped batch has at least group 0")
+    if g_count > n:
+        raise ValueError(f"rdv_param_groups_check: group {g_count - 1} does not fit: {g_count} groups for {n} envs")
+    at = 0
+    for g, size in enumerate(sizes):
+        if size <= 0:
+            raise ValueError(f"rdv_param_groups_check: group {g} has size {size}: sizes must be positive")
+        if g + 1 < g_count and size % GROUP_TILE:
+            raise ValueError(f"rdv_param_groups_check: group {g} has size {size}: every group but the last must be a multiple of "
+                             f"{GROUP_TILE} envs (a workgroup of 256 envs shares one parameter block)")
+        at += size
+        if at > n:
+            raise ValueError(f"rdv_param_groups_check: group {g} ends at env {at}, the batch has {n} envs")
+    if at != n:
+        raise ValueError(f"rdv_param_groups_check: group {g_count - 1} (the last) ends at env {at}, the batch has {n} envs")
+    return np.repeat(np.arange(g_count, dtype=np.int32), [-(-size // GROUP_TILE) for size in sizes])
