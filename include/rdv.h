@@ -420,6 +420,44 @@ int rdv_critic_create(const float* w1_host, const float* b1_host, const float* w
 int rdv_policy_value(rdv_policy critic, const float* obs, float* values, int64_t n, void* stream);
 
 /*
+ * Other MLP architectures (added within ABI 5): what the reference's network sweep trains (tune_policy.py:30-34, :124-139:
+ * net_arch = [n_neurons] * n_layers, activation_fn in {ReLU, Sigmoid, Tanh}; custom/custom_networks.py:9-10: ReLU, [32, 32]) —
+ * separate actor and critic trunks of 1..4 hidden layers, each 16, 32 or 64 wide (layers may differ), ONE activation for the whole
+ * network (SB3's activation_fn), 17 inputs, 6 outputs (actor) or 1 (critic).  weights_host / biases_host are arrays of n_hidden + 1
+ * HOST pointers, hidden layers first, the head last, in SB3's layout (nn.Linear [out, in]): layer 0 [hidden[0], 17], layer l
+ * [hidden[l], hidden[l-1]], head [6 or 1, hidden[n_hidden-1]].  The handles are rdv_policy handles: rdv_policy_act, rdv_policy_value,
+ * rdv_rollout and rdv_policy_destroy take them; the noise contract, the +-63 input clamp, the NaN rule and the weight scaling above
+ * hold for them unchanged, and a non-finite weight is RDV_ERR_BAD_PARAMS.  The kernels (csrc/rdv_policy_mlp.h) use the scheme of the
+ * shipped actor's; a width of 64 is two 32-row MFMA tiles, 32 one, 16 one tile whose rows 16..31 have zero weights and are not
+ * read by the next layer.
+ *
+ * Activations, in fp32 on the accumulator: tanh as above (absolute error <= 2.5e-7); sigmoid = 1 / (1 + 2^(-x log2 e)), absolute
+ * error <= 2.0e-7; ReLU exact.  The second deviation from the PyTorch modules: hidden ReLU activations are clamped to [0, 63]
+ * (they enter the next layer as scaled fp16 terms, as the inputs do; a NaN stays NaN).  Nothing changes for a network whose hidden
+ * units stay below 63.
+ *
+ * With the default spec ({2, {64, 64}, RDV_ACT_TANH}) the two create calls below ARE rdv_policy_create / rdv_critic_create: the same
+ * parameter block, the same kernels, bit-identical outputs, the persistent rollout kernel.  rdv_policy_get_spec works on every
+ * rdv_policy handle (the default spec for handles of rdv_policy_create / rdv_critic_create).  rdv_mlp_spec_check needs no GPU and
+ * names the offending field in rdv_last_error.
+ */
+typedef enum RdvActivation { RDV_ACT_TANH = 0, RDV_ACT_RELU = 1, RDV_ACT_SIGMOID = 2 } RdvActivation;
+#define RDV_MLP_MAX_HIDDEN 4
+typedef struct RdvMlpSpec {
+  int32_t n_hidden;                     /* 1..4 */
+  int32_t hidden[RDV_MLP_MAX_HIDDEN];   /* each 16, 32 or 64; entries from n_hidden on are 0 */
+  int32_t activation;                   /* RdvActivation */
+  int32_t reserved;                     /* 0 */
+} RdvMlpSpec;
+int rdv_mlp_spec_default(RdvMlpSpec* out_host);
+int rdv_mlp_spec_check(const RdvMlpSpec* spec_host);
+int rdv_policy_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
+                          const float* log_std_host, int device, rdv_policy* out);
+int rdv_critic_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
+                          int device, rdv_policy* out);
+int rdv_policy_get_spec(rdv_policy p, RdvMlpSpec* out_host);
+
+/*
  * Closed-loop rollout collection in ONE launch: for t in [0, n_steps): a_t ~ actor(obs_t); obs_{t+1}, r_t, done_t =
  * step(clip(a_t)) — the inner loop of SB3's OnPolicyAlgorithm.collect_rollouts (what model.learn, main.py:114, spends its
  * env time in) with the actor above, writing the rows SB3's RolloutBuffer.add receives.  Results are those of
@@ -427,6 +465,9 @@ int rdv_policy_value(rdv_policy critic, const float* obs, float* values, int64_t
  * state stays in registers and the observations / actions in LDS in between.  Episode statistics accumulate as in rdv_step.
  * General rigid bodies (rdv_set_rigid_body with a non-isotropic tensor, a torque, or RK45 asked for): the call runs rdv_policy_act +
  * rdv_step itself, n_steps times on `stream` (2 launches per step; the one-launch form spilled and was slower than this loop).
+ * A policy of another architecture than the shipped one (rdv_policy_create_mlp with a spec that is not the default): the same loop,
+ * whatever the env handle; the persistent kernel's registers and LDS are laid out for 17-64-64-6 tanh.  rdv_debug_last_kernel then
+ * names the step kernel the loop launched.
  */
 typedef struct RdvRolloutOut {
   float*   obs;        /* [T,N,17] required: the observation the actor saw at step t (buffer.observations) */

@@ -30,7 +30,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            "rdv_eval_begin", "rdv_eval_summary", "rdv_get_stats", "rdv_num_envs", "rdv_policy_create", "rdv_policy_destroy", "rdv_policy_act", "rdv_critic_create", "rdv_policy_value", "rdv_rollout",
            # parameter groups (added within ABI 5)
            "rdv_param_groups_check", "rdv_param_groups_validate", "rdv_set_param_groups", "rdv_set_group_params", "rdv_get_group_params",
-           "rdv_num_groups", "rdv_get_group_stats", "rdv_eval_group_summary"]
+           "rdv_num_groups", "rdv_get_group_stats", "rdv_eval_group_summary",
+           # other MLP architectures (added within ABI 5)
+           "rdv_mlp_spec_default", "rdv_mlp_spec_check", "rdv_policy_create_mlp", "rdv_critic_create_mlp", "rdv_policy_get_spec"]
 
 
 class RdvError(RuntimeError):
@@ -72,6 +74,24 @@ class RolloutOut(C.Structure):
                 ("log_prob", C.c_void_p), ("last_obs", C.c_void_p)]
 
 
+ACT_TANH, ACT_RELU, ACT_SIGMOID = 0, 1, 2
+MLP_MAX_HIDDEN = 4
+
+
+class MlpSpec(C.Structure):
+    """RdvMlpSpec: 1..4 hidden layers of 16, 32 or 64, one RdvActivation for the whole network"""
+    _fields_ = [("n_hidden", C.c_int32), ("hidden", C.c_int32 * MLP_MAX_HIDDEN), ("activation", C.c_int32), ("reserved", C.c_int32)]
+
+    @classmethod
+    def make(cls, hidden, activation=ACT_TANH):
+        """(rdv_mlp_spec_check judges it: more than MLP_MAX_HIDDEN widths are cut to the array and keep their count)"""
+        hidden = [int(x) for x in hidden]
+        return cls(len(hidden), (C.c_int32 * MLP_MAX_HIDDEN)(*hidden[:MLP_MAX_HIDDEN]), int(activation), 0)
+
+    def to_tuple(self):
+        return self.n_hidden, list(self.hidden), self.activation
+
+
 INTEGRATORS = {"auto": 0, "exact": 1, "rk45": 2}
 
 
@@ -84,7 +104,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the four translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip) for gfx950 and link librdv_hip.so
+    """Compile the five translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -155,6 +175,11 @@ def lib():
         "rdv_num_groups": (i32, [vp]),
         "rdv_get_group_stats": (C.c_int, [vp, C.POINTER(Stats), C.c_int, vp]),
         "rdv_eval_group_summary": (C.c_int, [vp, i32, vp, C.POINTER(EvalSummary), vp]),
+        "rdv_mlp_spec_default": (C.c_int, [C.POINTER(MlpSpec)]),
+        "rdv_mlp_spec_check": (C.c_int, [C.POINTER(MlpSpec)]),
+        "rdv_policy_create_mlp": (C.c_int, [C.POINTER(MlpSpec), vp, vp, vp, C.c_int, C.POINTER(vp)]),
+        "rdv_critic_create_mlp": (C.c_int, [C.POINTER(MlpSpec), vp, vp, C.c_int, C.POINTER(vp)]),
+        "rdv_policy_get_spec": (C.c_int, [vp, C.POINTER(MlpSpec)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

@@ -258,7 +258,9 @@ class RendezvousBatch:
 
         Returns a dict of tensors shaped like SB3's RolloutBuffer rows: ``obs`` [T,N,17] (what the actor saw), ``actions``
         [T,N,6] (before clipping), ``reward`` [T,N], ``done`` [T,N] (uint8), ``log_prob`` [T,N], ``last_obs`` [N,17]; pass
-        the dict back as ``out`` to reuse the buffers.  ``policy`` is an MlpPolicy (its HIP handle and noise key are used)."""
+        the dict back as ``out`` to reuse the buffers.  ``policy`` is an MlpPolicy (its HIP handle and noise key are used).
+        A policy of another architecture than the shipped 17-64-64-6 tanh (``net_arch`` / ``activation_fn``) takes the loop
+        this call is defined by inside the library: rdv_policy_act + rdv_step, two launches per step, the same rows."""
         T, n, dev = int(n_steps), self.num_envs, self.device
         if out is None or out["obs"].shape[0] != T:
             out = dict(obs=torch.empty((T, n, N.OBS_DIM), dtype=torch.float32, device=dev),

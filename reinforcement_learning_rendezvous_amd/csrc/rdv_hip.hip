@@ -7,6 +7,7 @@
 // The data layout in HBM is described in rdv_kernels.h.
 #include "rdv_device.h"
 #include "rdv_policy.h"
+#include "rdv_policy_mlp.h"
 
 #include <hip/hip_runtime.h>
 
@@ -378,9 +379,13 @@ int64_t rdv_num_envs(rdv_handle h) { return (h && h->magic == kMagic) ? h->n : -
 struct RdvPolicyNet {
   uint32_t magic;
   int device;
-  float* weights;   // device, kPolFloats floats: the parameter block of csrc/rdv_policy.h
+  float* weights;   // device, kPolFloats floats: the parameter block of csrc/rdv_policy.h (shipped_arch) or block_floats of csrc/rdv_policy_mlp.h
   int out_dim;      // 6: the actor (rdv_policy_create), 1: the critic (rdv_critic_create)
+  RdvMlpSpec spec;
+  bool shipped_arch;   // 17-64-64-out tanh: policy_act_kernel / policy_value_kernel, and the persistent rollout_kernel
+  int block_floats;
 };
+static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
 static constexpr uint32_t kPolicyMagic = 0x52445650u;   // "RDVP"
 
 // A 17-64-64-out_dim tanh MLP of the checkpoint (out_dim <= 6) as a parameter block on the device
@@ -399,6 +404,7 @@ static int create_mlp(const float* w1, const float* b1, const float* w2, const f
   RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
   if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "rdv_policy_create: host allocation failed");
   p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim;
+  p->spec = kDefaultMlpSpec; p->shipped_arch = true; p->block_floats = kPolFloats;
   hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
   if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
   // the kernels keep the parameter block and the staged rows in 72 KiB of dynamic LDS (above the 64 KiB default limit)
@@ -419,6 +425,79 @@ int rdv_critic_create(const float* w1, const float* b1, const float* w2, const f
   return create_mlp(w1, b1, w2, b2, w3, b3, nullptr, 1, device, out);
 }
 
+// ---- other architectures (RdvMlpSpec): csrc/rdv_policy_mlp.h
+int rdv_mlp_spec_default(RdvMlpSpec* out_host) {
+  if (!out_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_mlp_spec_default: null argument");
+  *out_host = kDefaultMlpSpec;
+  return RDV_OK;
+}
+
+int rdv_mlp_spec_check(const RdvMlpSpec* spec) {
+  if (!spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_mlp_spec_check: null spec");
+  if (spec->n_hidden < 1 || spec->n_hidden > RDV_MLP_MAX_HIDDEN)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: n_hidden = %d is not in 1..%d", spec->n_hidden, RDV_MLP_MAX_HIDDEN);
+  for (int l = 0; l < RDV_MLP_MAX_HIDDEN; ++l) {
+    const int wd = spec->hidden[l];
+    if (l < spec->n_hidden ? (wd != 16 && wd != 32 && wd != 64) : wd != 0)
+      return fail(RDV_ERR_INVALID_ARGUMENT, l < spec->n_hidden ? "RdvMlpSpec: hidden[%d] = %d is not 16, 32 or 64" : "RdvMlpSpec: hidden[%d] = %d beyond n_hidden must be 0", l, wd);
+  }
+  if (spec->activation != RDV_ACT_TANH && spec->activation != RDV_ACT_RELU && spec->activation != RDV_ACT_SIGMOID)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: activation = %d is not an RdvActivation (0 tanh, 1 relu, 2 sigmoid)", spec->activation);
+  if (spec->reserved != 0) return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: reserved = %d must be 0", spec->reserved);
+  return RDV_OK;
+}
+
+static int create_mlp_spec(const RdvMlpSpec* spec, const float* const* weights, const float* const* biases, const float* log_std,
+                           int out_dim, int device, rdv_policy* out) {
+  if (!spec || !weights || !biases || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp / rdv_critic_create_mlp: null argument");
+  if (int rc = rdv_mlp_spec_check(spec)) return rc;
+  const int L = spec->n_hidden;
+  for (int l = 0; l <= L; ++l)
+    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp / rdv_critic_create_mlp: null weights or biases of layer %d", l);
+  // the shipped architecture IS rdv_policy_create / rdv_critic_create: same block, same kernels, the persistent rollout kernel
+#ifndef RDV_MLP_GENERAL_DEFAULT   // (diagnostic build, tools/mlp_arch_time.py: the shipped architecture through the general kernel, to time the two side by side)
+  if (std::memcmp(spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0)
+    return create_mlp(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, out_dim, device, out);
+#endif
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RDV_ERR_NO_DEVICE, "no HIP device available: this library has no CPU path");
+  if (device < 0 || device >= count) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp: device %d out of range [0,%d)", device, count);
+  DeviceGuard guard(device);
+  for (int l = 0; l <= L; ++l) {
+    const int in_w = l == 0 ? kPolIn : spec->hidden[l - 1], out_w = l < L ? spec->hidden[l] : out_dim;
+    for (int i = 0; i < out_w * in_w; ++i) if (!std::isfinite(weights[l][i])) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create_mlp: non-finite weight in layer %d", l);
+  }
+  std::vector<float> packed;
+  pack_mlp_weights(*spec, out_dim, weights, biases, log_std, packed);
+  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
+  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "rdv_policy_create_mlp: host allocation failed");
+  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim;
+  p->spec = *spec; p->shipped_arch = false; p->block_floats = (int)packed.size();
+  hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
+  if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = mlp_raise_lds_limit();   // up to 90,752 B of dynamic LDS (4 x 64), above the 64 KiB default limit
+  if (err != hipSuccess) { (void)hipGetLastError(); if (p->weights) (void)hipFree(p->weights); delete p; return fail(RDV_ERR_HIP, "rdv_policy_create_mlp: %s", hipGetErrorString(err)); }
+  *out = p;
+  return RDV_OK;
+}
+
+int rdv_policy_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
+                          const float* log_std_host, int device, rdv_policy* out) {
+  if (!log_std_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp: null argument");
+  return create_mlp_spec(spec_host, weights_host, biases_host, log_std_host, kPolOut, device, out);
+}
+int rdv_critic_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
+                          int device, rdv_policy* out) {
+  return create_mlp_spec(spec_host, weights_host, biases_host, nullptr, 1, device, out);
+}
+
+int rdv_policy_get_spec(rdv_policy p, RdvMlpSpec* out_host) {
+  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (!out_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_get_spec: null argument");
+  *out_host = p->spec;
+  return RDV_OK;
+}
+
 int rdv_policy_destroy(rdv_policy p) {
   if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
   DeviceGuard guard(p->device);
@@ -432,6 +511,11 @@ int rdv_policy_destroy(rdv_policy p) {
 // the actor on n observation rows: clipped actions for the env and, optionally, the unclipped sample and its log-probability
 static int launch_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
                              uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s) {
+  if (!p->shipped_arch) {
+    mlp_launch_act(p->spec.activation, p->weights, p->block_floats, obs, actions, n, deterministic, seed, counter, env_id_offset, raw_actions, log_prob, s);
+    RDV_HIP(hipGetLastError());
+    return RDV_OK;
+  }
   hipLaunchKernelGGL(policy_act_kernel, policy_grid(n), dim3(kPolBlock), kPolLdsBytes, s, p->weights, obs, actions, n, deterministic, seed,
                      counter, env_id_offset, raw_actions, log_prob);
   RDV_HIP(hipGetLastError());
@@ -454,6 +538,11 @@ int rdv_policy_value(rdv_policy p, const float* obs, float* values, int64_t n, v
   if (!obs || !values || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs, values and a positive n are required");
   if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs must be 16-byte aligned");
   DeviceGuard guard(p->device);
+  if (!p->shipped_arch) {
+    mlp_launch_value(p->spec.activation, p->weights, p->block_floats, obs, values, n, static_cast<hipStream_t>(stream));
+    RDV_HIP(hipGetLastError());
+    return RDV_OK;
+  }
   hipLaunchKernelGGL(policy_value_kernel, policy_grid(n), dim3(kPolBlock), kPolLdsBytes, static_cast<hipStream_t>(stream), p->weights, obs, values, n);
   RDV_HIP(hipGetLastError());
   return RDV_OK;
@@ -474,8 +563,9 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   RDV_CHECK_FAULT(h);
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->general || h->n_groups) {
-    // General rigid bodies and parameter groups (no grouped persistent kernel): rdv_policy_act + rdv_step, n_steps times, on `stream` — the definition of this call's results, used as
+  if (h->general || h->n_groups || !p->shipped_arch) {
+    // General rigid bodies, parameter groups (no grouped persistent kernel) and policies of another architecture than the shipped one (the
+    // persistent kernel's registers and LDS are laid out for 17-64-64-6 tanh): rdv_policy_act + rdv_step, n_steps times, on `stream` — the definition of this call's results, used as
     // its implementation.  The per-lane RK45 inside the 168-register budget of the persistent kernel's 12-wave workgroup spilled 120
     // dwords per lane and ran SLOWER than this loop (72 against 58 us per step at 65,536 envs, round 2): not offered any more.
     const int64_t n = h->n;

@@ -72,6 +72,47 @@ static_assert(kPolFloats % 4 == 0, "the parameter block is copied as float4");
 constexpr int kPolObsStage = kPolWaveEnvs * kPolIn, kPolActStage = kPolWaveEnvs * kPolOut;
 constexpr int kPolLdsBytes = (kPolFloats + (kPolBlock / 64) * (kPolObsStage + kPolActStage)) * 4;   // 57,040 B: two workgroups per CU
 
+// Host helpers of the parameter blocks (this header's and rdv_policy_mlp.h's).
+inline uint16_t pol_f16_rn(float x) {   // IEEE binary16, round to nearest even (|x| < 65504 here; subnormals kept)
+  uint32_t u; std::memcpy(&u, &x, 4);
+  const uint32_t sign = (u >> 16) & 0x8000u;
+  const uint32_t a = u & 0x7fffffffu;
+  if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);                  // NaN
+  if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                 // >= 65520: inf
+  if (a < 0x33000001u) return (uint16_t)sign;                              // < 2^-25: 0
+  int e = (int)(a >> 23) - 127;
+  uint32_t m = (a & 0x7fffffu) | 0x800000u;                                // 24-bit significand
+  int shift = e >= -14 ? 13 : 13 + (-14 - e);                              // normal: keep 11 bits; subnormal: fewer
+  uint32_t q = m >> shift;
+  const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
+  if (rem > half || (rem == half && (q & 1u))) ++q;
+  uint32_t out = e >= -14 ? (uint32_t)((e + 15) << 10) + (q - 0x400u) : q;   // (a carry out of the significand bumps the exponent)
+  return (uint16_t)(sign | out);
+}
+inline float pol_f16_f(uint16_t hbits) {
+  const uint32_t sign = (uint32_t)(hbits & 0x8000u) << 16, e = (hbits >> 10) & 0x1fu, m = hbits & 0x3ffu;
+  float mag;
+  if (e == 0) mag = std::ldexp((float)m, -24);
+  else if (e == 31) mag = m ? NAN : INFINITY;
+  else mag = std::ldexp((float)(m | 0x400u), (int)e - 25);
+  return sign ? -mag : mag;
+}
+// per-layer weight scale: the largest power of two (at most 2^10) that keeps every |w| * 2^s below 2^15
+inline int pol_layer_shift(const float* wts, int count) {
+  float mx = 0.0f;
+  for (int i = 0; i < count; ++i) mx = std::fmax(mx, std::fabs(wts[i]));
+  int sft = 10;
+  while (sft > -20 && std::ldexp(mx, sft) >= 32768.0f) --sft;
+  return sft;
+}
+// element j of lane `lane` of the two term fragments (q = hi, lo) of weight wv * 2^sft; a layer's fragments are laid out [q][mt][ks] from frag0
+inline void pol_put(uint16_t* frags, int frag0, int mt_count, int ks_count, int mt, int ks, int lane, int j, float wv, int sft) {
+  const float ws = std::ldexp(wv, sft);
+  const uint16_t hi = pol_f16_rn(ws);
+  const uint16_t term[2] = {hi, pol_f16_rn(ws - pol_f16_f(hi))};
+  for (int q = 0; q < 2; ++q) frags[((size_t)(frag0 + (q * mt_count + mt) * ks_count + ks) * 64 + (size_t)lane) * 8 + (size_t)j] = term[q];
+}
+
 // Host: the parameter block of a 17-64-64-out_dim tanh MLP of the checkpoint (out_dim <= 6, finite weights) — weight fragments in MFMA
 // A-operand order, each weight scaled by its layer's power of two and split into two fp16 terms (w * 2^s = hi + lo to 22 bits), then
 // the biases in accumulator order (times the accumulator's scale), exp(log_std), log_std and the inverse scales.  SB3 stores
@@ -80,44 +121,9 @@ inline void pack_policy_weights(const float* w1, const float* b1, const float* w
                                 const float* log_std, int out_dim, std::vector<float>& packed) {
   packed.assign((size_t)kPolFloats, 0.0f);
   uint16_t* frags = reinterpret_cast<uint16_t*>(packed.data());
-  auto f16_rn = [](float x) -> uint16_t {   // IEEE binary16, round to nearest even (|x| < 65504 here; subnormals kept)
-    uint32_t u; std::memcpy(&u, &x, 4);
-    const uint32_t sign = (u >> 16) & 0x8000u;
-    const uint32_t a = u & 0x7fffffffu;
-    if (a > 0x7f800000u) return (uint16_t)(sign | 0x7e00u);                  // NaN
-    if (a >= 0x477ff000u) return (uint16_t)(sign | 0x7c00u);                 // >= 65520: inf
-    if (a < 0x33000001u) return (uint16_t)sign;                              // < 2^-25: 0
-    int e = (int)(a >> 23) - 127;
-    uint32_t m = (a & 0x7fffffu) | 0x800000u;                                // 24-bit significand
-    int shift = e >= -14 ? 13 : 13 + (-14 - e);                              // normal: keep 11 bits; subnormal: fewer
-    uint32_t q = m >> shift;
-    const uint32_t rem = m & ((1u << shift) - 1u), half = 1u << (shift - 1);
-    if (rem > half || (rem == half && (q & 1u))) ++q;
-    uint32_t out = e >= -14 ? (uint32_t)((e + 15) << 10) + (q - 0x400u) : q;   // (a carry out of the significand bumps the exponent)
-    return (uint16_t)(sign | out);
-  };
-  auto f16_f = [](uint16_t hbits) -> float {
-    const uint32_t sign = (uint32_t)(hbits & 0x8000u) << 16, e = (hbits >> 10) & 0x1fu, m = hbits & 0x3ffu;
-    float mag;
-    if (e == 0) mag = std::ldexp((float)m, -24);
-    else if (e == 31) mag = m ? NAN : INFINITY;
-    else mag = std::ldexp((float)(m | 0x400u), (int)e - 25);
-    return sign ? -mag : mag;
-  };
-  // per-layer weight scale: the largest power of two (at most 2^10) that keeps every |w| * 2^s below 2^15
-  auto layer_shift = [](const float* wts, int count) {
-    float mx = 0.0f;
-    for (int i = 0; i < count; ++i) mx = std::fmax(mx, std::fabs(wts[i]));
-    int sft = 10;
-    while (sft > -20 && std::ldexp(mx, sft) >= 32768.0f) --sft;
-    return sft;
-  };
-  const int sh1 = layer_shift(w1, kPolHid * kPolIn), sh2 = layer_shift(w2, kPolHid * kPolHid), sh3 = layer_shift(w3, out_dim * kPolHid);
+  const int sh1 = pol_layer_shift(w1, kPolHid * kPolIn), sh2 = pol_layer_shift(w2, kPolHid * kPolHid), sh3 = pol_layer_shift(w3, out_dim * kPolHid);
   auto put = [&](int frag0, int mt_count, int ks_count, int mt, int ks, int lane, int j, float wv, int sft) {
-    const float ws = std::ldexp(wv, sft);
-    const uint16_t hi = f16_rn(ws);
-    const uint16_t term[2] = {hi, f16_rn(ws - f16_f(hi))};
-    for (int q = 0; q < 2; ++q) frags[((size_t)(frag0 + (q * mt_count + mt) * ks_count + ks) * 64 + (size_t)lane) * 8 + (size_t)j] = term[q];
+    pol_put(frags, frag0, mt_count, ks_count, mt, ks, lane, j, wv, sft);
   };
   for (int lane = 0; lane < 64; ++lane) {
     const int r = lane & 31, h = lane >> 5;
@@ -268,14 +274,12 @@ __device__ __forceinline__ void activate(const f32x16& d, float kexp, f16x8 (&lo
   split2(x, hi_step);
 }
 
-// The actor for the wave's 32 envs.  `rows`: LDS, the wave's observations [32][17] (stride 17).  Lane (r = l & 31, h = l >> 5) gets
-// the action means of env r: components 0..3 in the lower half (h = 0), components 4, 5 in mean[0], mean[1] of the upper half.
-__device__ __forceinline__ void actor_means(const float* w, const float* rows, int lane, float (&mean)[4]) {
+// The B fragments of the first layer's two k-steps from the wave's observation rows (LDS, [32][17]): times 2^10, clamped to +-63.
+__device__ __forceinline__ void actor_inputs(const float* rows, int lane, f16x8 (&x0)[2][2]) {
   const int r = lane & 31, h = lane >> 5;
   const float* row = rows + r * kPolIn;
   constexpr float xs = (float)(1 << kPolXShift), xmax = 63.0f * xs;       // inputs times 2^10, clamped into fp16's range
   auto in = [&](float v) { const float c = __builtin_amdgcn_fmed3f(v * xs, -xmax, xmax); return v != v ? v : c; };   // NaN stays NaN (as in PyTorch)
-  f16x8 x0[2][2];
   {
     float x[8];
 #pragma unroll
@@ -287,6 +291,13 @@ __device__ __forceinline__ void actor_means(const float* w, const float* rows, i
     x[0] = h == 0 ? last : 0.0f;                                    // k-step 1: feature 16 only (17 inputs, padded to 32)
     split2(x, x0[1]);
   }
+}
+
+// The actor for the wave's 32 envs.  `rows`: LDS, the wave's observations [32][17] (stride 17).  Lane (r = l & 31, h = l >> 5) gets
+// the action means of env r: components 0..3 in the lower half (h = 0), components 4, 5 in mean[0], mean[1] of the upper half.
+__device__ __forceinline__ void actor_means(const float* w, const float* rows, int lane, float (&mean)[4]) {
+  f16x8 x0[2][2];
+  actor_inputs(rows, lane, x0);
   constexpr float two_log2e = 2.8853900817779268f;
   f32x16 d1[2];
   layer<2, 2>(w, kPolW1Frag, w + kPolB1, x0, lane, d1);            // 17 -> 64
@@ -318,48 +329,33 @@ __device__ __forceinline__ void actor_noise(int lane, uint64_t seed, uint64_t id
 
 // mean -> sample (SB3 rollout form: mean + exp(log_std) z, z ~ N(0,1) from actor_noise; z = 0 when deterministic) for this lane's
 // components; returns the ENV's Gaussian log-density log N(a; mean, std) summed over the 6 components (both lanes of an env get it).
-__device__ __forceinline__ float actor_apply(const float* w, int lane, const float (&z)[4], float (&a)[4]) {
+// (`sd`: exp(log_std) [8], then log_std [8], as a parameter block holds them from kPolStd on)
+__device__ __forceinline__ float actor_apply_at(const float* sd, int lane, const float (&z)[4], float (&a)[4]) {
   const int h = lane >> 5;
   float lp = 0.0f;
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
     const bool valid = h == 0 || c < 2;                   // the upper half holds components 4, 5 only
-    a[c] = fmaf(w[kPolStd + 4 * h + c], z[c], a[c]);      // std entries 6, 7 are zero
-    lp += valid ? fmaf(-0.5f * z[c], z[c], -w[kPolLogStd + 4 * h + c]) : 0.0f;
+    a[c] = fmaf(sd[4 * h + c], z[c], a[c]);               // std entries 6, 7 are zero
+    lp += valid ? fmaf(-0.5f * z[c], z[c], -sd[kPolLogStd - kPolStd + 4 * h + c]) : 0.0f;
   }
   return (lp + __shfl_xor(lp, 32)) - 5.5136312f;          // - 6/2 log(2 pi)
 }
-__device__ __forceinline__ float actor_sample(const float* w, int lane, int deterministic, uint64_t seed, uint64_t id, uint64_t counter,
-                                              float (&a)[4]) {
+__device__ __forceinline__ float actor_apply(const float* w, int lane, const float (&z)[4], float (&a)[4]) {
+  return actor_apply_at(w + kPolStd, lane, z, a);
+}
+__device__ __forceinline__ float actor_sample_at(const float* sd, int lane, int deterministic, uint64_t seed, uint64_t id, uint64_t counter,
+                                                 float (&a)[4]) {
   float z[4] = {0.0f, 0.0f, 0.0f, 0.0f};
   if (!deterministic) actor_noise(lane, seed, id, counter, z);
-  return actor_apply(w, lane, z, a);
+  return actor_apply_at(sd, lane, z, a);
 }
 
 __device__ __forceinline__ float clip_action(float v) { return (v != v) ? v : fminf(fmaxf(v, -1.0f), 1.0f); }   // np.clip (NaN stays NaN)
 
-// raw_actions [n,6] / log_prob [n] (both nullable): the sample BEFORE clipping and its log-density, the rows SB3's RolloutBuffer keeps
-// (rdv_rollout's act + step form for general rigid bodies asks for them; rdv_policy_act does not).
-__global__ __launch_bounds__(kPolBlock) void policy_act_kernel(const float* __restrict__ W, const float* __restrict__ obs,
-                                                               float* __restrict__ actions, int64_t n, int deterministic,
-                                                               uint64_t seed, uint64_t counter, uint64_t env_id_offset,
-                                                               float* __restrict__ raw_actions, float* __restrict__ log_prob) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];   // [parameters][8 x obs rows][8 x action rows]
-  float* w = lds;
-  const int lane = threadIdx.x & 63;
-  const int wv = threadIdx.x >> 6;
-  float* rows = lds + kPolFloats + wv * kPolObsStage;
-  float* arows = lds + kPolFloats + (kPolBlock / 64) * kPolObsStage + wv * kPolActStage;
-  const int64_t wave_base = ((int64_t)blockIdx.x * (kPolBlock / 64) + wv) * kPolWaveEnvs;
-  const int64_t nrows = (n - wave_base) < kPolWaveEnvs ? (n - wave_base) : kPolWaveEnvs;   // <= 0 for trailing waves of the last workgroup
-
-  // ---- parameters -> LDS, once per workgroup (contiguous 16-byte-per-lane loads)
-#ifndef RDV_POL_NOSTAGE     // (diagnostic build: how long the staging takes — tools/policy_time.py with -DRDV_POL_NOSTAGE computes on whatever LDS holds)
-  for (int q = threadIdx.x; q < kPolFloats / 4; q += kPolBlock)
-    *reinterpret_cast<float4*>(w + 4 * q) = *reinterpret_cast<const float4*>(W + 4 * q);
-#endif
-
-  // ---- observations [32,17] of this wave: contiguous loads -> plain LDS rows of stride 17 (missing rows = 0)
+// Observations [32,17] of a wave (rows wave_base .. wave_base + nrows - 1 of obs): contiguous loads -> plain LDS rows of stride 17
+// (missing rows = 0; nrows <= 0: nothing)
+__device__ __forceinline__ void stage_obs_rows(const float* __restrict__ obs, int64_t wave_base, int64_t nrows, float* rows, int lane) {
   if (nrows > 0) {
     const float* src = obs + wave_base * kPolIn;
     if (nrows == kPolWaveEnvs) {
@@ -377,15 +373,15 @@ __global__ __launch_bounds__(kPolBlock) void policy_act_kernel(const float* __re
       }
     }
   }
-  __syncthreads();   // the parameters are in LDS (the only workgroup barrier; every wave reaches it)
-  if (nrows <= 0) return;
+}
 
+// Sample (or mean), log-density and the stores of a wave's actions: `a` = this lane's means (actor_means' order), `sd` as in
+// actor_apply_at, `arows` = the wave's LDS action rows [32][6].
+__device__ __forceinline__ void actor_outputs(const float* sd, int lane, int64_t wave_base, int64_t nrows, int deterministic, uint64_t seed,
+                                              uint64_t counter, uint64_t env_id_offset, float (&a)[4], float* arows, float* __restrict__ actions,
+                                              float* __restrict__ raw_actions, float* __restrict__ log_prob) {
   const int r = lane & 31, h = lane >> 5;
-  float a[4];
-  if (wv < 4) __builtin_amdgcn_s_setprio(1);   // one of the SIMD's two waves strictly first through the layers (see rollout_kernel's phase A)
-  actor_means(w, rows, lane, a);
-  if (wv < 4) __builtin_amdgcn_s_setprio(0);
-  const float logp = actor_sample(w, lane, deterministic, seed, env_id_offset + (uint64_t)(wave_base + r), counter, a);
+  const float logp = actor_sample_at(sd, lane, deterministic, seed, env_id_offset + (uint64_t)(wave_base + r), counter, a);
   if (log_prob && h == 0 && r < nrows) log_prob[wave_base + r] = logp;
   if (raw_actions && r < nrows) {      // kernel-uniform pointer test; the unclipped sample, written per lane (this form is not the hot one)
     float* dst = raw_actions + (wave_base + r) * kPolOut + 4 * h;
@@ -417,6 +413,40 @@ __global__ __launch_bounds__(kPolBlock) void policy_act_kernel(const float* __re
   }
 }
 
+#ifndef RDV_POLICY_FUNCTIONS_ONLY   // (rdv_policy_mlp.hip takes the functions above; the two kernels belong to rdv_hip.hip)
+// raw_actions [n,6] / log_prob [n] (both nullable): the sample BEFORE clipping and its log-density, the rows SB3's RolloutBuffer keeps
+// (rdv_rollout's act + step form for general rigid bodies asks for them; rdv_policy_act does not).
+__global__ __launch_bounds__(kPolBlock) void policy_act_kernel(const float* __restrict__ W, const float* __restrict__ obs,
+                                                               float* __restrict__ actions, int64_t n, int deterministic,
+                                                               uint64_t seed, uint64_t counter, uint64_t env_id_offset,
+                                                               float* __restrict__ raw_actions, float* __restrict__ log_prob) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];   // [parameters][8 x obs rows][8 x action rows]
+  float* w = lds;
+  const int lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6;
+  float* rows = lds + kPolFloats + wv * kPolObsStage;
+  float* arows = lds + kPolFloats + (kPolBlock / 64) * kPolObsStage + wv * kPolActStage;
+  const int64_t wave_base = ((int64_t)blockIdx.x * (kPolBlock / 64) + wv) * kPolWaveEnvs;
+  const int64_t nrows = (n - wave_base) < kPolWaveEnvs ? (n - wave_base) : kPolWaveEnvs;   // <= 0 for trailing waves of the last workgroup
+
+  // ---- parameters -> LDS, once per workgroup (contiguous 16-byte-per-lane loads)
+#ifndef RDV_POL_NOSTAGE     // (diagnostic build: how long the staging takes — tools/policy_time.py with -DRDV_POL_NOSTAGE computes on whatever LDS holds)
+  for (int q = threadIdx.x; q < kPolFloats / 4; q += kPolBlock)
+    *reinterpret_cast<float4*>(w + 4 * q) = *reinterpret_cast<const float4*>(W + 4 * q);
+#endif
+
+  // ---- observations [32,17] of this wave: contiguous loads -> plain LDS rows of stride 17 (missing rows = 0)
+  stage_obs_rows(obs, wave_base, nrows, rows, lane);
+  __syncthreads();   // the parameters are in LDS (the only workgroup barrier; every wave reaches it)
+  if (nrows <= 0) return;
+
+  float a[4];
+  if (wv < 4) __builtin_amdgcn_s_setprio(1);   // one of the SIMD's two waves strictly first through the layers (see rollout_kernel's phase A)
+  actor_means(w, rows, lane, a);
+  if (wv < 4) __builtin_amdgcn_s_setprio(0);
+  actor_outputs(w + kPolStd, lane, wave_base, nrows, deterministic, seed, counter, env_id_offset, a, arows, actions, raw_actions, log_prob);
+}
+
 // The critic of the same checkpoint (mlp_extractor.value_net 17-64-64 tanh + value_net 64 -> 1): the same parameter block with
 // one output row; values [n] for observations [n,17] (e.g. the [T*N,17] rows a rollout produced, for SB3's GAE).
 __global__ __launch_bounds__(kPolBlock) void policy_value_kernel(const float* __restrict__ W, const float* __restrict__ obs,
@@ -430,27 +460,13 @@ __global__ __launch_bounds__(kPolBlock) void policy_value_kernel(const float* __
   const int64_t nrows = (n - wave_base) < kPolWaveEnvs ? (n - wave_base) : kPolWaveEnvs;
   for (int q = threadIdx.x; q < kPolFloats / 4; q += kPolBlock)
     *reinterpret_cast<float4*>(w + 4 * q) = *reinterpret_cast<const float4*>(W + 4 * q);
-  if (nrows > 0) {
-    const float* src = obs + wave_base * kPolIn;
-    if (nrows == kPolWaveEnvs) {
-#pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const int q = k * 64 + lane;
-        if (q < kPolObsStage / 4) *reinterpret_cast<pol_f4*>(rows + 4 * q) = __builtin_nontemporal_load(reinterpret_cast<const pol_f4*>(src + 4 * q));
-      }
-    } else {
-      const int64_t valid = nrows * kPolIn;
-      for (int j = 0; j < 9; ++j) {
-        const int idx = j * 64 + lane;
-        if (idx < kPolObsStage) rows[idx] = idx < valid ? src[idx] : 0.0f;
-      }
-    }
-  }
+  stage_obs_rows(obs, wave_base, nrows, rows, lane);
   __syncthreads();
   if (nrows <= 0) return;
   float v[4];
   actor_means(w, rows, lane, v);
   if (lane < nrows) values[wave_base + lane] = v[0];   // lanes 0..31: row 0 of the head tile of env l
 }
+#endif
 
 }  // namespace rdv

@@ -5,9 +5,16 @@ The SB3 MlpPolicy actor of the reference's shipped checkpoint (models/mlp_model_
 ``activation_fn=Tanh``).  It is not part of the env kernel.  On the GPU the forward pass is ONE hand-written HIP kernel
 (csrc/rdv_policy.h, through the C ABI: rdv_policy_act); ``backend="torch"`` keeps the plain PyTorch modules (any device),
 which the tests use as the reference of that kernel.
+
+Other architectures of the reference's network sweep (tune_policy.py:30-34, :131-139: ``net_arch = [n_neurons] * n_layers``,
+``activation_fn`` in ReLU / Sigmoid / Tanh; custom/custom_networks.py:9-10: ReLU, [32, 32]) are held the same way: separate actor
+and critic trunks of 1..4 hidden layers, one activation for the whole network.  Their HIP kernels are csrc/rdv_policy_mlp.h
+(rdv_policy_create_mlp: widths 16, 32 and 64); the PyTorch modules hold any width.
 """
 import ctypes as C
 import io
+import json
+import re
 import zipfile
 
 import numpy as np
@@ -18,9 +25,64 @@ _KEYS = ["mlp_extractor.policy_net.0.weight", "mlp_extractor.policy_net.0.bias",
 _VKEYS = ["mlp_extractor.value_net.0.weight", "mlp_extractor.value_net.0.bias", "mlp_extractor.value_net.2.weight",
           "mlp_extractor.value_net.2.bias", "value_net.weight", "value_net.bias"]     # the critic trunk + head of the same checkpoint
 
+ACTIVATIONS = {"tanh": (0, torch.tanh, torch.nn.Tanh), "relu": (1, torch.relu, torch.nn.ReLU),
+               "sigmoid": (2, torch.sigmoid, torch.nn.Sigmoid)}       # name -> (RdvActivation, function, SB3's activation_fn class)
+MAX_HIDDEN = 4                                                          # RDV_MLP_MAX_HIDDEN
+
+
+def parse_activation(fn):
+    """"tanh" | "relu" | "sigmoid" (any case), the torch.nn class, or the class's string form as an SB3 zip's `data` JSON
+    carries it ("<class 'torch.nn.modules.activation.ReLU'>") -> the name."""
+    if isinstance(fn, type):
+        for name, (_, _, cls) in ACTIVATIONS.items():
+            if fn is cls:
+                return name
+        raise ValueError(f"activation_fn {fn!r} is not supported: one of torch.nn.Tanh, torch.nn.ReLU, torch.nn.Sigmoid")
+    text = str(fn)
+    m = re.fullmatch(r"<class '([\w.]+)'>", text.strip())
+    name = (m.group(1).rsplit(".", 1)[-1] if m else text.strip()).lower()
+    if name not in ACTIVATIONS or (m and not m.group(1).startswith("torch.nn.")):
+        raise ValueError(f"activation_fn {text!r} is not supported: one of 'tanh', 'relu', 'sigmoid' (or the torch.nn class)")
+    return name
+
+
+def parse_net_arch(net_arch):
+    """SB3's net_arch -> (pi, vf): a list of widths (the same for actor and critic), dict(pi=[...], vf=[...]), or the older
+    [dict(pi=..., vf=...)].  A shared trunk ([128, dict(...)]) is refused: the kernels hold separate trunks, as SB3 >= 1.8 does."""
+    if isinstance(net_arch, dict):
+        pi, vf = net_arch.get("pi", []), net_arch.get("vf", [])
+    else:
+        net_arch = list(net_arch)
+        if len(net_arch) == 1 and isinstance(net_arch[0], dict):
+            return parse_net_arch(net_arch[0])
+        if any(isinstance(x, dict) for x in net_arch):
+            raise ValueError(f"net_arch {net_arch!r} has a shared trunk in front of the pi / vf heads: not supported "
+                             "(separate actor and critic trunks only)")
+        pi = vf = net_arch
+    pi, vf = [int(x) for x in pi], [int(x) for x in vf]
+    for name, arch in (("pi", pi), ("vf", vf)):
+        if not 1 <= len(arch) <= MAX_HIDDEN or min(arch) <= 0:
+            raise ValueError(f"net_arch {name} = {arch!r}: 1..{MAX_HIDDEN} hidden layers of positive width")
+    return pi, vf
+
+
+def _trunk_keys(net, n_hidden):
+    """The state-dict keys of a trunk of n_hidden layers ('policy_net' + action_net, or 'value_net' + value_net) in layer order."""
+    head = "action_net" if net == "policy_net" else "value_net"
+    names = [f"mlp_extractor.{net}.{2 * l}" for l in range(n_hidden)] + [head]
+    return [(f"{n}.weight", f"{n}.bias") for n in names]
+
+
+def infer_arch(weights, net):
+    """Hidden widths from the keys mlp_extractor.<net>.{0,2,4,6}.weight and their shapes; None when the weights hold none."""
+    arch = []
+    while f"mlp_extractor.{net}.{2 * len(arch)}.weight" in weights:
+        arch.append(int(np.asarray(weights[f"mlp_extractor.{net}.{2 * len(arch)}.weight"]).shape[0]))
+    return arch or None
+
 
 class MlpPolicy(torch.nn.Module):
-    def __init__(self, weights=None, obs_dim=17, hidden=64, act_dim=6, seed=0, backend="auto"):
+    def __init__(self, weights=None, net_arch=None, activation_fn="tanh", obs_dim=17, hidden=64, act_dim=6, seed=0, backend="auto"):
         super().__init__()
         self.backend = backend          # "auto": HIP kernel for CUDA observations, PyTorch otherwise; "torch"; "hip"
         self.noise_seed = int(seed)     # HIP backend: Philox key of the exploration noise; the call counter is the step index
@@ -29,63 +91,122 @@ class MlpPolicy(torch.nn.Module):
         self._hip = {}                  # device index -> rdv_policy handle
         self._hip_critic = {}           # device index -> rdv_policy handle of the critic
         self._calls = 0
-        self.l1 = torch.nn.Linear(obs_dim, hidden)
-        self.l2 = torch.nn.Linear(hidden, hidden)
-        self.l3 = torch.nn.Linear(hidden, act_dim)
-        self.log_std = torch.nn.Parameter(torch.zeros(act_dim))
-        # critic (SB3 MlpPolicy: separate 17-64-64 tanh trunk + 64 -> 1 head); zero-initialised when the weights have none
-        self.v1 = torch.nn.Linear(obs_dim, hidden)
-        self.v2 = torch.nn.Linear(hidden, hidden)
-        self.v3 = torch.nn.Linear(hidden, 1)
+        self.activation = parse_activation(activation_fn)
+        self._fn = ACTIVATIONS[self.activation][1]
+        if net_arch is not None:
+            pi, vf = parse_net_arch(net_arch)
+        elif weights is not None:
+            pi = infer_arch(weights, "policy_net")
+            if pi is None:
+                raise KeyError("mlp_extractor.policy_net.0.weight: the weights hold no actor trunk")
+            vf = infer_arch(weights, "value_net") or pi
+            parse_net_arch(dict(pi=pi, vf=vf))
+        else:
+            pi = vf = [hidden, hidden]
+        self.pi_arch, self.vf_arch = list(pi), list(vf)
+        # actor: l1 .. l<n>, the last one the head (17-64-64-6: l1, l2, l3); critic (SB3 MlpPolicy: a separate trunk + a head of
+        # one row): v1 .. v<m>, left at PyTorch's initialisation when the weights have none
+        for prefix, arch, out in (("l", self.pi_arch, act_dim), ("v", self.vf_arch, 1)):
+            dims = [obs_dim] + arch + [out]
+            for i in range(len(dims) - 1):
+                setattr(self, f"{prefix}{i + 1}", torch.nn.Linear(dims[i], dims[i + 1]))
+            if prefix == "l":
+                self.log_std = torch.nn.Parameter(torch.zeros(act_dim))
         self.has_critic = False
         if weights is None:
-            # random init of the same architecture (bench.py when the checkpoint fixture is absent)
+            # random init of the architecture (bench.py when the checkpoint fixture is absent): SB3's orthogonal gains
             g = torch.Generator().manual_seed(seed)
-            for lin, gain in ((self.l1, 2 ** 0.5), (self.l2, 2 ** 0.5), (self.l3, 0.01)):
+            actor = self._layers("l")
+            for lin, gain in zip(actor, [2 ** 0.5] * (len(actor) - 1) + [0.01]):
                 torch.nn.init.orthogonal_(lin.weight, gain=gain, generator=g)
                 torch.nn.init.zeros_(lin.bias)
         else:
-            w = {k: torch.as_tensor(np.asarray(weights[k]), dtype=torch.float32) for k in _KEYS}
+            def load(layers, keys):
+                for lin, (kw, kb) in zip(layers, keys):
+                    w, b = (torch.as_tensor(np.asarray(weights[k]), dtype=torch.float32) for k in (kw, kb))
+                    if w.shape != lin.weight.shape or b.shape != lin.bias.shape:
+                        raise ValueError(f"{kw}: shape {tuple(w.shape)} does not fit net_arch (expected {tuple(lin.weight.shape)})")
+                    lin.weight.copy_(w); lin.bias.copy_(b)
             with torch.no_grad():
-                self.l1.weight.copy_(w[_KEYS[0]]); self.l1.bias.copy_(w[_KEYS[1]])
-                self.l2.weight.copy_(w[_KEYS[2]]); self.l2.bias.copy_(w[_KEYS[3]])
-                self.l3.weight.copy_(w[_KEYS[4]]); self.l3.bias.copy_(w[_KEYS[5]])
-                self.log_std.copy_(w[_KEYS[6]])
-                if all(k in weights for k in _VKEYS):
-                    v = {k: torch.as_tensor(np.asarray(weights[k]), dtype=torch.float32) for k in _VKEYS}
-                    self.v1.weight.copy_(v[_VKEYS[0]]); self.v1.bias.copy_(v[_VKEYS[1]])
-                    self.v2.weight.copy_(v[_VKEYS[2]]); self.v2.bias.copy_(v[_VKEYS[3]])
-                    self.v3.weight.copy_(v[_VKEYS[4]]); self.v3.bias.copy_(v[_VKEYS[5]])
+                load(self._layers("l"), _trunk_keys("policy_net", len(self.pi_arch)))
+                self.log_std.copy_(torch.as_tensor(np.asarray(weights["log_std"]), dtype=torch.float32))
+                vkeys = _trunk_keys("value_net", len(self.vf_arch))
+                if all(k in weights for pair in vkeys for k in pair):
+                    load(self._layers("v"), vkeys)
                     self.has_critic = True
         for p in self.parameters():
             p.requires_grad_(False)
 
-    @classmethod
-    def from_npz(cls, path):
-        """Weights extracted from policy.pth as plain arrays (tests/golden/mlp_policy.npz)."""
-        return cls(np.load(path, allow_pickle=False))
+    def _layers(self, prefix):
+        return [getattr(self, f"{prefix}{i + 1}") for i in range(len(self.pi_arch if prefix == "l" else self.vf_arch) + 1)]
+
+    @property
+    def shipped_arch(self):
+        """The architecture of the shipped checkpoint (actor): the specialised kernels and the one-launch rollout."""
+        return self.pi_arch == [64, 64] and self.activation == "tanh" and self.l1.in_features == 17
 
     @classmethod
-    def from_sb3_zip(cls, path):
-        """An SB3 checkpoint zip as `model.save()` writes it; policy.pth is read with weights_only=True (nothing is unpickled)."""
+    def from_npz(cls, path, **kwargs):
+        """Weights extracted from policy.pth as plain arrays (tests/golden/mlp_policy.npz); an optional string entry
+        ``activation_fn`` names the activation (absent: tanh)."""
+        w = dict(np.load(path, allow_pickle=False))
+        if "activation_fn" in w:
+            kwargs.setdefault("activation_fn", str(w.pop("activation_fn")))
+        return cls(w, **kwargs)
+
+    @classmethod
+    def from_sb3_zip(cls, path, **kwargs):
+        """An SB3 checkpoint zip as `model.save()` writes it; policy.pth is read with weights_only=True (nothing is unpickled).
+        The layers come from policy.pth, the activation from the zip's `data` JSON: policy_kwargs["activation_fn"], the string
+        form of the class that SB3 writes beside the pickled blob (absent: SB3's default, tanh)."""
         with zipfile.ZipFile(path) as z:
             sd = torch.load(io.BytesIO(z.read("policy.pth")), weights_only=True, map_location="cpu")
-        return cls({k: v.numpy() for k, v in sd.items()})
+            if "activation_fn" not in kwargs and "data" in z.namelist():
+                pk = json.loads(z.read("data").decode("utf-8")).get("policy_kwargs") or {}
+                fn = pk.get("activation_fn") if isinstance(pk, dict) else None
+                if fn is not None:
+                    kwargs["activation_fn"] = parse_activation(fn)
+        return cls({k: v.numpy() for k, v in sd.items()}, **kwargs)
+
+    def _forward(self, prefix, x):
+        layers = self._layers(prefix)
+        for lin in layers[:-1]:
+            x = self._fn(lin(x))
+        return layers[-1](x)
 
     @torch.no_grad()
     def mean(self, obs):
-        return self.l3(torch.tanh(self.l2(torch.tanh(self.l1(obs)))))
+        return self._forward("l", obs)
 
     def _hip_handle(self, device):
         from . import _native as N
         idx = device.index if device.index is not None else torch.cuda.current_device()
         if idx not in self._hip:
-            w = [t.detach().to("cpu", torch.float32).contiguous() for t in
-                 (self.l1.weight, self.l1.bias, self.l2.weight, self.l2.bias, self.l3.weight, self.l3.bias, self.log_std)]
-            h = C.c_void_p()
-            N.check(N.lib().rdv_policy_create(*[C.c_void_p(t.data_ptr()) for t in w], idx, C.byref(h)))
-            self._hip[idx] = h
+            self._hip[idx] = self._create_handle("l", self.pi_arch, idx)
         return self._hip[idx]
+
+    def _create_handle(self, prefix, arch, idx):
+        """rdv_policy_create / rdv_critic_create for the shipped architecture, their _mlp forms (RdvMlpSpec) for every other."""
+        from . import _native as N
+        host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
+        layers = self._layers(prefix)
+        ws, bs = [host(l.weight) for l in layers], [host(l.bias) for l in layers]
+        log_std = [host(self.log_std)] if prefix == "l" else []
+        h = C.c_void_p()
+        if arch == [64, 64] and self.activation == "tanh":
+            flat = [t for pair in zip(ws, bs) for t in pair] + log_std
+            create = N.lib().rdv_policy_create if prefix == "l" else N.lib().rdv_critic_create
+            N.check(create(*[C.c_void_p(t.data_ptr()) for t in flat], idx, C.byref(h)))
+            return h
+        spec = N.MlpSpec.make(arch, ACTIVATIONS[self.activation][0])
+        N.check(N.lib().rdv_mlp_spec_check(C.byref(spec)))        # a message naming the field, before any pointer is read
+        wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+        bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
+        if prefix == "l":
+            N.check(N.lib().rdv_policy_create_mlp(C.byref(spec), wp, bp, C.c_void_p(log_std[0].data_ptr()), idx, C.byref(h)))
+        else:
+            N.check(N.lib().rdv_critic_create_mlp(C.byref(spec), wp, bp, idx, C.byref(h)))
+        return h
 
     def _act_hip(self, obs, deterministic, out=None, env_id_offset=None):
         from . import _native as N
@@ -112,18 +233,14 @@ class MlpPolicy(torch.nn.Module):
             flat = flat.contiguous()
             idx = flat.device.index if flat.device.index is not None else torch.cuda.current_device()
             if idx not in self._hip_critic:
-                w = [t.detach().to("cpu", torch.float32).contiguous() for t in
-                     (self.v1.weight, self.v1.bias, self.v2.weight, self.v2.bias, self.v3.weight, self.v3.bias)]
-                h = C.c_void_p()
-                N.check(N.lib().rdv_critic_create(*[C.c_void_p(t.data_ptr()) for t in w], idx, C.byref(h)))
-                self._hip_critic[idx] = h
+                self._hip_critic[idx] = self._create_handle("v", self.vf_arch, idx)
             if out is None:
                 out = torch.empty((flat.shape[0],), dtype=torch.float32, device=flat.device)
             stream = C.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream)
             N.check(N.lib().rdv_policy_value(self._hip_critic[idx], C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
                                              flat.shape[0], stream))
             return out.reshape(shape)
-        return self.v3(torch.tanh(self.v2(torch.tanh(self.v1(flat))))).reshape(shape)
+        return self._forward("v", flat).reshape(shape)
 
     def close(self):
         if self._hip or self._hip_critic:
