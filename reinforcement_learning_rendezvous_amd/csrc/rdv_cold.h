@@ -1,5 +1,5 @@
-// rdv_cold.h — the kernels off the hot path: reset, state access / evaluator helpers, the evaluation summary, the upload of the
-// parameter block and the debug hook of the device error word.  One lane per env, launched by the C ABI (rdv_hip.hip).  Device code only.
+// rdv_cold.h — the kernels off the hot path: reset, state access / evaluator helpers, the evaluation summary.  One lane per env, launched
+// by the C ABI (rdv_hip.hip).  Device code only.
 #pragma once
 #include "rdv_kernels.h"
 #include "rdv_slots.h"
@@ -124,21 +124,5 @@ template <typename ST>
 __global__ __launch_bounds__(kBlock) void eval_summary_kernel(const DevParams P, const void* ws_, int64_t n, int64_t cs, const double* eval, double* partial) {
   eval_summary_lane<ST>(P, ws_, n, cs, eval, partial);
 }
-
-#ifndef RDV_COLD_LANES_ONLY   // (rdv_groups.hip takes the lane functions above; the kernels below belong to rdv_hip.hip)
-// The derived parameter block travels as a kernel argument and is written by the device: ordered on the caller's stream like
-// every other launch (a hipMemcpy from host memory is ordered against the legacy stream only, not against PyTorch's non-blocking
-// side streams) and legal inside a stream capture (the values are baked into the graph node).
-__global__ __launch_bounds__(kWave) void params_kernel(const DevParams src, DevParams* dst) {
-  const uint32_t* from = reinterpret_cast<const uint32_t*>(&src);
-  uint32_t* to = reinterpret_cast<uint32_t*>(dst);
-  for (int k = threadIdx.x; k < (int)(sizeof(DevParams) / 4); k += kWave) to[k] = from[k];
-}
-// rdv_debug_set_device_error: what a kernel that detects a fault does to the handle's error word
-__global__ __launch_bounds__(kWave) void device_error_kernel(uint32_t* word, uint32_t bits) {
-  if (threadIdx.x == 0) __hip_atomic_fetch_or(word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-static_assert(sizeof(DevParams) % 4 == 0 && sizeof(DevParams) <= 3072, "DevParams is passed by value to params_kernel");
-#endif
 
 }  // namespace rdv

@@ -11,9 +11,11 @@ namespace rdv {
 // kGeneral: general rigid bodies (rdv_set_rigid_body) — the attitude of both bodies is integrated with the reference's RK45
 // scheme instead of the closed form, and the target's rate is part of the state that is written back.
 // kRaw: the first step after rdv_set_state (quaternions that need not be normalised, see integrate_attitude).
-template <typename ST, bool kDiag, bool kGeneral = false, bool kRaw = false>
+// G: empty, or the type of the tile table of parameter groups as one more top-level argument (see step_kernel_parts, rdv_step.h).
+template <typename ST, bool kDiag, bool kGeneral = false, bool kRaw = false, typename... G>
 __global__ __launch_bounds__(kBlock) void step_kernel(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
-                                                       uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+                                                       uint64_t* stats_hot, float* obs_hot, float* reward_hot, G... tile_group, const StepArgs A_rest) {
+  static_assert(sizeof...(G) <= 1, "G is empty or the type of the tile table");
   const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
   using V = typename Vec4<ST>::type;
   __shared__ __attribute__((aligned(16))) float lds[kBlock * RDV_OBS_DIM];   // 17,408 B: wave-private staging regions
@@ -21,10 +23,12 @@ __global__ __launch_bounds__(kBlock) void step_kernel(void* ws_hot, const float*
   // it, so its fields are fetched with scalar loads from HBM/L2.  (By value it would travel in the kernarg segment, which
   // every wave reads from host-visible memory: +1 us per launch measured; behind a pointer inside a struct the compiler
   // cannot prove the no-alias and emits uniform-address VECTOR loads in the middle of the math.)
-  const DevParams& P = *Pp;
+  const DevParams* Pb = Pp;
   const int lane = threadIdx.x & (kWave - 1);
   const int wave_in_block = threadIdx.x >> 6;
   const int64_t lblock = A.xcd_per ? (int64_t)(blockIdx.x & 7) * A.xcd_per + (blockIdx.x >> 3) : (int64_t)blockIdx.x;   // XCD order: see step_kernel_parts
+  if constexpr (sizeof...(G) != 0) Pb = &group_block(Pp, tile_group..., lblock);
+  const DevParams& P = *Pb;
   const int64_t i = lblock * kBlock + threadIdx.x;
   const int64_t wave_base = i - lane;
   const int64_t n = A.n;

@@ -5,6 +5,7 @@
 // of scratch) and the fused form 236 instead of 256 + 20 spilled into AGPRs — two waves per SIMD instead of one.
 #include "rdv_fused.h"
 #include "rdv_slots.h"
+#include "rdv_launch.h"
 #include "rdv_general.h"
 
 namespace rdv {
@@ -106,17 +107,17 @@ __global__ __launch_bounds__(kGenBlock) void step_kernel_general(void* ws_hot, c
 }
 
 const char* launch_step_general(bool f32, bool diag, bool partner_waves, int64_t n, dim3 fused_grid, hipStream_t s, const DevParams* dev_params, const StepArgs& A) {
-#define RDV_LAUNCH_G(GRID, BLOCK, ...) do { hipLaunchKernelGGL((__VA_ARGS__), GRID, BLOCK, 0, s, A.ws, A.actions, dev_params, A.n, A.stats, A.obs, A.reward, A); \
-                                             return #__VA_ARGS__; } while (0)
+  const char* name;
   if (partner_waves && !diag) {
     const dim3 grid((unsigned)((n + kGenEnvs - 1) / kGenEnvs));
-    if (f32) RDV_LAUNCH_G(grid, dim3(kGenBlock), step_kernel_general<float>); else RDV_LAUNCH_G(grid, dim3(kGenBlock), step_kernel_general<double>);
+    if (f32) RDV_LAUNCH(name, (step_kernel_general<float>), grid, dim3(kGenBlock), s, RDV_HOT_ARGS(A, dev_params), A);
+    else RDV_LAUNCH(name, (step_kernel_general<double>), grid, dim3(kGenBlock), s, RDV_HOT_ARGS(A, dev_params), A);
   } else {
-    const dim3 block(kBlock);
-    if (f32) { if (diag) RDV_LAUNCH_G(fused_grid, block, step_kernel<float, true, true>); else RDV_LAUNCH_G(fused_grid, block, step_kernel<float, false, true>); }
-    else { if (diag) RDV_LAUNCH_G(fused_grid, block, step_kernel<double, true, true>); else RDV_LAUNCH_G(fused_grid, block, step_kernel<double, false, true>); }
+#define RDV_K_FUSED_GENERAL(ST, B) step_kernel<ST, B, true>
+    RDV_LAUNCH_BY(name, f32, diag, RDV_K_FUSED_GENERAL, fused_grid, dim3(kBlock), s, RDV_HOT_ARGS(A, dev_params), A);
+#undef RDV_K_FUSED_GENERAL
   }
-#undef RDV_LAUNCH_G
+  return name;
 }
 
 }  // namespace rdv

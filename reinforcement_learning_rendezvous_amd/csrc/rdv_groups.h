@@ -11,10 +11,10 @@ struct GroupTable {
   const DevParams* params;     // [G], device
   const int32_t* tile_group;   // [tiles rounded up to 8], device
 };
-// step_kernel_groups<ST, all>: step_kernel_parts with the workgroup's own block (`grid`, A.xcd_per, A.stagger, A.stream_rows as rdv_step
-// sets them for step_kernel_parts).  Returns the name of the kernel it launched.
+// step_kernel_groups<ST, all> = step_kernel_parts<ST, all, TileTable> (rdv_step.h): the reset-by-part kernel with the workgroup's own block (`grid`, A.xcd_per, A.stagger,
+// A.stream_rows as rdv_step sets them for step_kernel_parts).  Returns the name of the kernel it launched.
 const char* launch_step_groups(bool f32, bool all, dim3 grid, hipStream_t s, const GroupTable& T, const StepArgs& A);
-// step_kernel_groups_lane<ST, diag, raw>: the in-lane step_kernel (evaluator build, first step after rdv_set_state) likewise
+// step_kernel_groups_lane<ST, diag, raw> = step_kernel<ST, diag, false, raw, TileTable> (rdv_fused.h): the in-lane kernel (evaluator build, first step after rdv_set_state) likewise
 const char* launch_step_groups_lane(bool f32, bool diag, bool raw, dim3 grid, hipStream_t s, const GroupTable& T, const StepArgs& A);
 // reset_kernel / access_kernel / eval_summary_kernel with the workgroup's own block (arguments as in rdv_cold.h)
 void launch_reset_groups(bool f32, dim3 grid, hipStream_t s, const GroupTable& T, const StepArgs& A, const uint8_t* mask, float* obs, int fresh);

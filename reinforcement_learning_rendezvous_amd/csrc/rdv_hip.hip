@@ -1,9 +1,11 @@
-// rdv_hip.hip — the host side of the MI355X-native batched rendezvous environment: the C ABI of include/rdv.h (handles, argument
-// checks, launches, snapshot / restore, statistics), the derivation of the thresholds the kernels compare against (derive_params),
-// rigid-body validation and the workspace layout.  The kernels it launches live in the headers included below: rdv_step.h and
-// rdv_fused.h (one-launch step kernels), rdv_cold.h (reset, state access, evaluation summary), rdv_policy.h (actor / critic),
-// rdv_rollout.h and rdv_step_many.h (persistent kernels); rdv_tiles.hip, rdv_general.hip and rdv_groups.hip (parameter groups) are
-// translation units of their own.
+// rdv_hip.hip — the host side of the MI355X-native batched rendezvous environment: the C ABI of include/rdv.h (env handles, policy
+// handles, parameter groups, argument checks, launches, snapshot / restore, statistics), the derivation of the thresholds the kernels
+// compare against (derive_params), rigid-body validation and the workspace layout.  Its kernels are instantiated from the headers
+// included below: rdv_step.h and rdv_fused.h (one-launch step kernels), rdv_cold.h (reset, state access, evaluation summary),
+// rdv_policy.h (the shipped actor / critic), rdv_rollout.h and rdv_step_many.h (persistent kernels); three small ones (parameter upload,
+// device error word, snapshot header) are defined here.  rdv_tiles.hip, rdv_general.hip, rdv_groups.hip (which instantiates the step
+// kernels of rdv_step.h and rdv_fused.h once more, with a tile table) and rdv_policy_mlp.hip are translation units of their own, entered
+// through the launch functions of their headers.
 // The data layout in HBM is described in rdv_kernels.h.
 #include "rdv_device.h"
 #include "rdv_policy.h"
@@ -31,6 +33,7 @@
 #include "rdv_tiles.h"
 #include "rdv_general.h"
 #include "rdv_groups.h"
+#include "rdv_launch.h"
 
 namespace rdv {
 
@@ -191,6 +194,27 @@ struct DeviceGuard {
   }
   ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
 };
+// `device` exists: checked by every call that creates a handle (`who`, for the message)
+static int check_device(const char* who, int device) {
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RDV_ERR_NO_DEVICE, "no HIP device available: this library has no CPU path");
+  if (device < 0 || device >= count) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: device %d out of range [0,%d)", who, device, count);
+  return RDV_OK;
+}
+
+// The derived parameter block travels as a kernel argument and is written by the device: ordered on the caller's stream like
+// every other launch (a hipMemcpy from host memory is ordered against the legacy stream only, not against PyTorch's non-blocking
+// side streams) and legal inside a stream capture (the values are baked into the graph node).
+__global__ __launch_bounds__(kWave) void params_kernel(const DevParams src, DevParams* dst) {
+  const uint32_t* from = reinterpret_cast<const uint32_t*>(&src);
+  uint32_t* to = reinterpret_cast<uint32_t*>(dst);
+  for (int k = threadIdx.x; k < (int)(sizeof(DevParams) / 4); k += kWave) to[k] = from[k];
+}
+// rdv_debug_set_device_error: what a kernel that detects a fault does to the handle's error word
+__global__ __launch_bounds__(kWave) void device_error_kernel(uint32_t* word, uint32_t bits) {
+  if (threadIdx.x == 0) __hip_atomic_fetch_or(word, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+static_assert(sizeof(DevParams) % 4 == 0 && sizeof(DevParams) <= 3072, "DevParams is passed by value to params_kernel");
 
 }  // namespace rdv
 
@@ -246,7 +270,7 @@ struct RdvEnvBatch {
   GroupTable group_table = {nullptr, nullptr};
 };
 static constexpr uint32_t kMagic = 0x52445631u;   // "RDV1"
-static void apply_rigid_body(RdvEnvBatch* h);
+static void derive_block(const RdvEnvBatch* h, const RdvParams& p, DevParams& dev);
 
 #define RDV_CHECK_HANDLE(h) \
   if (!(h) || (h)->magic != kMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_handle")
@@ -295,6 +319,14 @@ static int ensure_prepared(RdvEnvBatch* h, hipStream_t s) {
   with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(prepare_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev_params, A); });
   RDV_HIP(hipGetLastError());
   h->prepared_ok = true;
+  return RDV_OK;
+}
+// The loops of rdv_step that rdv_step_many and rdv_rollout are defined by write row t of the caller's [T][N][17] observations from a kernel
+// that stores 16-byte vectors: the row is aligned if and only if N % 4 == 0.  Otherwise the kernel writes h->obs_tmp and the row is a copy.
+static inline bool obs_rows_aligned(const RdvEnvBatch* h) { return (h->n & 3) == 0; }
+static inline float* obs_row_target(const RdvEnvBatch* h, float* obs, int64_t t) { return obs_rows_aligned(h) ? obs + t * h->n * RDV_OBS_DIM : h->obs_tmp; }
+static int obs_row_flush(const RdvEnvBatch* h, float* obs, int64_t t, hipStream_t s) {
+  if (!obs_rows_aligned(h)) RDV_HIP(hipMemcpyAsync(obs + t * h->n * RDV_OBS_DIM, h->obs_tmp, (size_t)h->n * RDV_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
   return RDV_OK;
 }
 // the derived parameter block -> device, ordered on `s` (params_kernel)
@@ -388,31 +420,38 @@ struct RdvPolicyNet {
 static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
 static constexpr uint32_t kPolicyMagic = 0x52445650u;   // "RDVP"
 
+static bool all_finite(const float* w, int count) {
+  for (int i = 0; i < count; ++i) if (!std::isfinite(w[i])) return false;
+  return true;
+}
+// A packed parameter block -> a policy handle on `device` (the caller's DeviceGuard holds it): the allocation, the upload and the dynamic-LDS
+// limit of the kernels that will read the block, which is above the 64 KiB default (72 KiB for the shipped architecture, up to 90,752 B for 4 x 64)
+static int finish_policy(const char* who, const std::vector<float>& packed, const RdvMlpSpec& spec, bool shipped_arch, int out_dim, int device, rdv_policy* out) {
+  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
+  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
+  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim;
+  p->spec = spec; p->shipped_arch = shipped_arch; p->block_floats = shipped_arch ? kPolFloats : (int)packed.size();
+  hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
+  if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (err == hipSuccess && !shipped_arch) err = mlp_raise_lds_limit();
+  if (err == hipSuccess && shipped_arch) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
+  if (err == hipSuccess && shipped_arch) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_value_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
+  if (err != hipSuccess) { (void)hipGetLastError(); if (p->weights) (void)hipFree(p->weights); delete p; return fail(RDV_ERR_HIP, "%s: %s", who, hipGetErrorString(err)); }
+  *out = p;
+  return RDV_OK;
+}
+
 // A 17-64-64-out_dim tanh MLP of the checkpoint (out_dim <= 6) as a parameter block on the device
 static int create_mlp(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
                       const float* log_std, int out_dim, int device, rdv_policy* out) {
   if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create / rdv_critic_create: null argument");
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RDV_ERR_NO_DEVICE, "no HIP device available: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create: device %d out of range [0,%d)", device, count);
+  if (int rc = check_device("rdv_policy_create", device)) return rc;
   DeviceGuard guard(device);
-  for (int i = 0; i < kPolHid * kPolIn; ++i) if (!std::isfinite(w1[i])) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create: non-finite weight");
-  for (int i = 0; i < kPolHid * kPolHid; ++i) if (!std::isfinite(w2[i])) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create: non-finite weight");
-  for (int i = 0; i < out_dim * kPolHid; ++i) if (!std::isfinite(w3[i])) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create: non-finite weight");
+  if (!all_finite(w1, kPolHid * kPolIn) || !all_finite(w2, kPolHid * kPolHid) || !all_finite(w3, out_dim * kPolHid))
+    return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create: non-finite weight");
   std::vector<float> packed;
   pack_policy_weights(w1, b1, w2, b2, w3, b3, log_std, out_dim, packed);
-  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
-  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "rdv_policy_create: host allocation failed");
-  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim;
-  p->spec = kDefaultMlpSpec; p->shipped_arch = true; p->block_floats = kPolFloats;
-  hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
-  if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-  // the kernels keep the parameter block and the staged rows in 72 KiB of dynamic LDS (above the 64 KiB default limit)
-  if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
-  if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_value_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
-  if (err != hipSuccess) { (void)hipGetLastError(); if (p->weights) (void)hipFree(p->weights); delete p; return fail(RDV_ERR_HIP, "rdv_policy_create: %s", hipGetErrorString(err)); }
-  *out = p;
-  return RDV_OK;
+  return finish_policy("rdv_policy_create", packed, kDefaultMlpSpec, true, out_dim, device, out);
 }
 
 int rdv_policy_create(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
@@ -459,26 +498,15 @@ static int create_mlp_spec(const RdvMlpSpec* spec, const float* const* weights, 
   if (std::memcmp(spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0)
     return create_mlp(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, out_dim, device, out);
 #endif
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RDV_ERR_NO_DEVICE, "no HIP device available: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp: device %d out of range [0,%d)", device, count);
+  if (int rc = check_device("rdv_policy_create_mlp", device)) return rc;
   DeviceGuard guard(device);
   for (int l = 0; l <= L; ++l) {
     const int in_w = l == 0 ? kPolIn : spec->hidden[l - 1], out_w = l < L ? spec->hidden[l] : out_dim;
-    for (int i = 0; i < out_w * in_w; ++i) if (!std::isfinite(weights[l][i])) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create_mlp: non-finite weight in layer %d", l);
+    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create_mlp: non-finite weight in layer %d", l);
   }
   std::vector<float> packed;
   pack_mlp_weights(*spec, out_dim, weights, biases, log_std, packed);
-  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
-  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "rdv_policy_create_mlp: host allocation failed");
-  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim;
-  p->spec = *spec; p->shipped_arch = false; p->block_floats = (int)packed.size();
-  hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
-  if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = mlp_raise_lds_limit();   // up to 90,752 B of dynamic LDS (4 x 64), above the 64 KiB default limit
-  if (err != hipSuccess) { (void)hipGetLastError(); if (p->weights) (void)hipFree(p->weights); delete p; return fail(RDV_ERR_HIP, "rdv_policy_create_mlp: %s", hipGetErrorString(err)); }
-  *out = p;
-  return RDV_OK;
+  return finish_policy("rdv_policy_create_mlp", packed, *spec, false, out_dim, device, out);
 }
 
 int rdv_policy_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
@@ -569,16 +597,15 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
     // its implementation.  The per-lane RK45 inside the 168-register budget of the persistent kernel's 12-wave workgroup spilled 120
     // dwords per lane and ran SLOWER than this loop (72 against 58 us per step at 65,536 envs, round 2): not offered any more.
     const int64_t n = h->n;
-    const bool rows_aligned = (n & 3) == 0;      // row t of [T][N][17] starts 16-byte aligned
-    float* obs_t = rows_aligned ? out->obs : h->obs_tmp;
+    float* obs_t = obs_row_target(h, out->obs, 0);
     if (int rc = rdv_observe(h, obs_t, stream)) return rc;
     for (int32_t t = 0; t < n_steps; ++t) {
-      if (!rows_aligned) RDV_HIP(hipMemcpyAsync(out->obs + (int64_t)t * n * RDV_OBS_DIM, obs_t, (size_t)n * RDV_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
+      if (int rc = obs_row_flush(h, out->obs, t, s)) return rc;
       if (int rc = launch_policy_act(p, obs_t, h->act_tmp, n, deterministic ? 1 : 0, noise_seed, noise_counter0 + (uint64_t)t, h->env_id_offset,
                                      out->actions + (int64_t)t * n * RDV_ACT_DIM, out->log_prob ? out->log_prob + (int64_t)t * n : nullptr, s)) return rc;
       RdvStepOut so;
       std::memset(&so, 0, sizeof so);
-      float* obs_next = (t + 1 < n_steps) ? (rows_aligned ? out->obs + (int64_t)(t + 1) * n * RDV_OBS_DIM : h->obs_tmp) : out->last_obs;
+      float* obs_next = (t + 1 < n_steps) ? obs_row_target(h, out->obs, t + 1) : out->last_obs;
       so.obs = obs_next; so.reward = out->reward + (int64_t)t * n; so.done = out->done + (int64_t)t * n;
       if (int rc = rdv_step(h, h->act_tmp, &so, stream)) return rc;
       obs_t = obs_next;
@@ -612,16 +639,13 @@ int rdv_create(const RdvParams* params, int64_t n_envs, int device, int storage,
   if (storage != RDV_STORAGE_F32 && storage != RDV_STORAGE_F64) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_create: bad storage %d", storage);
   if (on_done != RDV_ON_DONE_RESET && on_done != RDV_ON_DONE_HALT && on_done != RDV_ON_DONE_CONTINUE) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_create: bad on_done %d", on_done);
   if (int rc = rdv_params_validate(params)) return rc;
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return fail(RDV_ERR_NO_DEVICE, "no HIP device available: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_create: device %d out of range [0,%d)", device, count);
+  if (int rc = check_device("rdv_create", device)) return rc;
   if (workspace && misaligned(workspace, 256)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_create: workspace must be 256-byte aligned");
   DeviceGuard guard(device);
   RdvEnvBatch* h = new (std::nothrow) RdvEnvBatch();
   if (!h) return fail(RDV_ERR_OUT_OF_MEMORY, "rdv_create: host allocation failed");
-  h->magic = kMagic; h->params = *params; derive_params(*params, h->dev);
-  (void)rdv_rigid_body_default(&h->body); h->general = false; apply_rigid_body(h);
+  h->magic = kMagic; h->params = *params;
+  (void)rdv_rigid_body_default(&h->body); h->general = false;
   h->raw_state = false;
   h->last_kernel = "";
 
@@ -651,7 +675,7 @@ int rdv_create(const RdvParams* params, int64_t n_envs, int device, int storage,
   h->act_tmp = reinterpret_cast<float*>(base + L.act_tmp);
   h->obs_tmp = reinterpret_cast<float*>(base + L.obs_tmp);
   h->prepared_ok = false;
-  h->dev.acos_table = h->acos_table;
+  derive_block(h, *params, h->dev);
   // every step of the set-up reports itself: which call failed, and why
   const char* what = "hipMemset of the workspace";
   hipError_t err = hipMemset(h->ws, 0, (size_t)bytes);
@@ -762,7 +786,12 @@ static void apply_body(const RdvRigidBody& b, DevParams& dev) {   // a validated
   for (int k = 0; k < 2; ++k) dev.body_general[k] = (b.integrator == RDV_INTEGRATOR_RK45 || !closed_form_applies(tensors[k], torques[k])) ? 1 : 0;
   if (b.integrator == RDV_INTEGRATOR_EXACT) dev.body_general[0] = dev.body_general[1] = 0;
 }
-static void apply_rigid_body(RdvEnvBatch* h) { apply_body(h->body, h->dev); }
+// a handle's derived block for the parameters `p`: the thresholds, the handle's acos table, its rigid body
+static void derive_block(const RdvEnvBatch* h, const RdvParams& p, DevParams& dev) {
+  derive_params(p, dev);
+  dev.acos_table = h->acos_table;
+  apply_body(h->body, dev);
+}
 // one group's derived block -> its place in the device table, ordered on `s` (params_kernel, as upload_params)
 static int upload_group(RdvEnvBatch* h, int32_t g, hipStream_t s) {
   hipLaunchKernelGGL(params_kernel, dim3(1), dim3(kWave), 0, s, h->group_dev[(size_t)g], const_cast<DevParams*>(h->group_table.params) + g);
@@ -778,7 +807,7 @@ int rdv_set_rigid_body(rdv_handle h, const RdvRigidBody* b, void* stream) {
                                     "(rdv_set_param_groups with n_groups = 0 returns it to one block)", h->n_groups);
   DeviceGuard guard(h->device);
   h->body = *b; h->general = general;
-  apply_rigid_body(h);
+  apply_body(h->body, h->dev);
   for (int32_t g = 0; g < h->n_groups; ++g) {
     apply_body(h->body, h->group_dev[(size_t)g]);
     if (int rc = upload_group(h, g, static_cast<hipStream_t>(stream))) return rc;
@@ -797,9 +826,7 @@ int rdv_set_params(rdv_handle h, const RdvParams* p, void* stream) {
   if (h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_set_params: this handle has %d parameter groups: use rdv_set_group_params (or rdv_set_param_groups)", h->n_groups);
   if (int rc = rdv_params_validate(p)) return rc;
   DeviceGuard guard(h->device);
-  h->params = *p; derive_params(*p, h->dev);
-  h->dev.acos_table = h->acos_table;
-  apply_rigid_body(h);
+  h->params = *p; derive_block(h, *p, h->dev);
   h->prepared_ok = false;   // nominal state / ranges may have changed: what a reset returns is no longer what the slots hold
   return upload_params(h, static_cast<hipStream_t>(stream));
 }
@@ -882,13 +909,6 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
   h->raw_state = false;
   const bool split = !A.diag && !A.eval && !h->general && !raw && !h->n_groups && (h->variant == RDV_VARIANT_SPLIT || (h->variant == RDV_VARIANT_AUTO && h->n <= kSplitAutoMaxEnvs));
   // every launch records the kernel's name, as spelled here, on the handle (host only: rdv_debug_last_kernel)
-#define RDV_LAUNCH(GRID, BLOCK, ...) do { hipLaunchKernelGGL((__VA_ARGS__), GRID, BLOCK, 0, s, A.ws, A.actions, h->dev_params, A.n, A.stats, A.obs, A.reward, A); \
-                                           h->last_kernel = #__VA_ARGS__; } while (0)
-#define RDV_LAUNCH_X(GRID, BLOCK, ...) RDV_LAUNCH(GRID, BLOCK, __VA_ARGS__)   // (K(ST, B) below is expanded before RDV_LAUNCH spells it)
-  // one of the four instantiations K(float | double, true | false) of a kernel, by the storage type and FLAG
-#define RDV_LAUNCH_BY(GRID, BLOCK, FLAG, K) do {                                                                                   \
-    if (f32) { if (FLAG) RDV_LAUNCH_X(GRID, BLOCK, K(float, true)); else RDV_LAUNCH_X(GRID, BLOCK, K(float, false)); }             \
-    else { if (FLAG) RDV_LAUNCH_X(GRID, BLOCK, K(double, true)); else RDV_LAUNCH_X(GRID, BLOCK, K(double, false)); } } while (0)
 #define RDV_K_SPLIT(ST, B) step_kernel_split<ST, B>
 #define RDV_K_PARTS(ST, B) step_kernel_parts<ST, B>
 #define RDV_K_FUSED(ST, B) step_kernel<ST, B>
@@ -898,7 +918,7 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
     const dim3 grid((unsigned)((h->n + kSplitEnvs - 1) / kSplitEnvs));
     const dim3 block(kSplitBlock);
     const bool all = h->on_done != RDV_ON_DONE_HALT;   // no halted envs: every lane runs the transition, the inputs travel together (advance_all)
-    RDV_LAUNCH_BY(grid, block, all, RDV_K_SPLIT);
+    RDV_LAUNCH_BY(h->last_kernel, f32, all, RDV_K_SPLIT, grid, block, s, RDV_HOT_ARGS(A, h->dev_params), A);
   } else {
     dim3 grid = grid_for(h->n), block(kBlock);
     { static const int forced = [] { const char* x = getenv("RDV_STREAM_ROWS"); return x ? atoi(x) : -1; }();   // diagnostics
@@ -919,7 +939,7 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
       // the evaluator build, and a general chaser beside the reference's target, run the fused per-lane form
       h->last_kernel = launch_step_general(f32, dg, h->dev.body_general[1] != 0 && h->split_general != 0, h->n, grid, s, h->dev_params, A);
     } else if (raw) {
-      RDV_LAUNCH_BY(grid, block, dg, RDV_K_RAW);
+      RDV_LAUNCH_BY(h->last_kernel, f32, dg, RDV_K_RAW, grid, block, s, RDV_HOT_ARGS(A, h->dev_params), A);
     } else if (!dg && h->variant != RDV_VARIANT_FUSED_INLANE) {
       const bool tiles = h->variant == RDV_VARIANT_FUSED_TILES && h->on_done != RDV_ON_DONE_HALT && h->tape_depth == 0;   // (halted envs skip the transition, a reset tape is a test device: step_kernel_parts)
       if (tiles) {
@@ -931,19 +951,16 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
         h->last_kernel = launch_step_tiles(f32, grid, s, h->dev_params, A);
       } else {
         const bool all = h->on_done != RDV_ON_DONE_HALT;   // (see the split branch)
-        RDV_LAUNCH_BY(grid, block, all, RDV_K_PARTS);
+        RDV_LAUNCH_BY(h->last_kernel, f32, all, RDV_K_PARTS, grid, block, s, RDV_HOT_ARGS(A, h->dev_params), A);
       }
     } else {
-      RDV_LAUNCH_BY(grid, block, dg, RDV_K_FUSED);
+      RDV_LAUNCH_BY(h->last_kernel, f32, dg, RDV_K_FUSED, grid, block, s, RDV_HOT_ARGS(A, h->dev_params), A);
     }
   }
 #undef RDV_K_RAW
 #undef RDV_K_FUSED
 #undef RDV_K_PARTS
 #undef RDV_K_SPLIT
-#undef RDV_LAUNCH_BY
-#undef RDV_LAUNCH_X
-#undef RDV_LAUNCH
   RDV_HIP(hipGetLastError());
   if (h->on_done == RDV_ON_DONE_RESET) h->prepared_ok = false;   // the step kernels reset in registers: the slots of the persistent kernels lag behind now
   return RDV_OK;
@@ -967,16 +984,14 @@ int rdv_step_many(rdv_handle h, const float* actions, int32_t n_steps, const Rdv
     // implementation): the per-lane RK45 does not fit the persistent kernel's register budget without scratch (round 2: 60 spilled
     // dwords per lane), and a step is bound by the integrator, not by the launch boundary this call exists to remove.
     const int64_t n = h->n;
-    const bool rows_aligned = (n & 3) == 0;
     for (int32_t k = 0; k < n_steps; ++k) {
       RdvStepOut so;
       std::memset(&so, 0, sizeof so);
-      float* row = out->obs + (int64_t)k * n * RDV_OBS_DIM;
-      so.obs = rows_aligned ? row : h->obs_tmp;
+      so.obs = obs_row_target(h, out->obs, k);
       so.reward = out->reward + (int64_t)k * n; so.done = out->done + (int64_t)k * n;
       so.done_reason = out->done_reason ? out->done_reason + (int64_t)k * n : nullptr;
       if (int rc = rdv_step(h, actions + (int64_t)k * n * RDV_ACT_DIM, &so, stream)) return rc;
-      if (!rows_aligned) RDV_HIP(hipMemcpyAsync(row, h->obs_tmp, (size_t)n * RDV_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
+      if (int rc = obs_row_flush(h, out->obs, k, s)) return rc;
     }
     return RDV_OK;
   }
@@ -1233,9 +1248,7 @@ int rdv_set_param_groups(rdv_handle h, const RdvParams* params, const int64_t* s
   h->group_start.assign((size_t)n_groups + 1, 0);
   std::vector<int32_t> table((size_t)entries);
   for (int32_t g = 0; g < n_groups; ++g) {
-    derive_params(params[g], h->group_dev[(size_t)g]);
-    h->group_dev[(size_t)g].acos_table = h->acos_table;
-    apply_body(h->body, h->group_dev[(size_t)g]);
+    derive_block(h, params[g], h->group_dev[(size_t)g]);
     h->group_start[(size_t)g + 1] = h->group_start[(size_t)g] + sizes[g];
     for (int64_t t = h->group_start[(size_t)g] / kGroupTile; t < (h->group_start[(size_t)g + 1] + kGroupTile - 1) / kGroupTile; ++t) table[(size_t)t] = g;
   }
@@ -1256,10 +1269,9 @@ int rdv_set_group_params(rdv_handle h, int32_t group, const RdvParams* p, void* 
   if (group < 0 || group >= h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_set_group_params: group %d of %d", group, h->n_groups);
   if (int rc = rdv_params_validate(p)) return rc;
   DeviceGuard guard(h->device);
-  DevParams& dev = h->group_dev[(size_t)group];
-  h->group_params[(size_t)group] = *p; derive_params(*p, dev);
-  dev.acos_table = h->acos_table;
-  apply_body(h->body, dev);
+  h->group_params[(size_t)group] = *p; derive_block(h, *p, h->group_dev[(size_t)group]);
+  // (prepared_ok stays as it is, unlike in rdv_set_params: only the persistent kernels read the slots, a grouped handle never launches one —
+  // rdv_step_many and rdv_rollout run the rdv_step loop — and every way out of the grouped state, rdv_set_param_groups, clears the flag)
   return upload_group(h, group, static_cast<hipStream_t>(stream));
 }
 int rdv_get_group_params(rdv_handle h, int32_t group, RdvParams* out) {

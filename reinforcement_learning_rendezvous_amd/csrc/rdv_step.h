@@ -31,9 +31,14 @@ __global__ __launch_bounds__(kBlock) void prepare_kernel(const DevParams* __rest
 // whole resets to the workgroup's last wave (profiles/r02_n_sweep_compacted_reset.csv), which held a wave slot and the LDS for a
 // lone serial chain.  Same expressions on the same inputs: bit-identical results.  (Forced to 128 VGPRs for four waves per SIMD it
 // spills 16 dwords and loses: 342 against 315 us at 4.2 M envs.)
-template <typename ST, bool kAll>   // kAll: on_done != HALT — every lane runs the transition (advance_all)
+// Parameter groups (rdv_groups.hip) instantiate this kernel with G = the pointer to the tile table, `const int32_t* __restrict__`, named
+// explicitly: the table is then one more top-level argument and the workgroup runs with the block of its tile's group (group_block, there)
+// instead of the handle's one block.  That is the only difference, so a grouped env's results are those of a stand-alone handle by
+// construction.  Without G the argument does not exist and the kernel is what it was before there were groups.
+template <typename ST, bool kAll, typename... G>   // kAll: on_done != HALT — every lane runs the transition (advance_all)
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(ST) == 4 ? RDV_PARTS_WAVES : 3))) void step_kernel_parts(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
-                                                             uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+                                                             uint64_t* stats_hot, float* obs_hot, float* reward_hot, G... tile_group, const StepArgs A_rest) {
+  static_assert(sizeof...(G) <= 1, "G is empty or the type of the tile table");
   const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
   using V = typename Vec4<ST>::type;
   __shared__ __attribute__((aligned(16))) float lds[kBlock * RDV_OBS_DIM];   // observation rows [256][17]; before that, per wave, the action rows
@@ -41,7 +46,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(S
   __shared__ uint32_t job_counter[kBlock];
   __shared__ uint16_t lists[kGroupWaves * kBlock];
   static_assert(kBlock == kGroupEnvs, "refill_pass_lds is written for 256-env workgroups");
-  const DevParams& P = *Pp;
+  const DevParams* Pb = Pp;   // the handle's one block
   const int lane = threadIdx.x & (kWave - 1);
   // Everything that is the same for the 64 lanes of a wave is computed on the scalar unit (readfirstlane tells the compiler that the wave
   // index is uniform): the wave's first env, its row count, the bases of its slices of every array.  A lane then addresses memory as
@@ -50,6 +55,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(S
   // XCD-aware block order: workgroups are dealt to the 8 XCDs round-robin (blockIdx % 8); with A.xcd_per != 0 XCD x walks its own
   // contiguous eighth of the envs in ascending order instead of every 8th workgroup of the whole batch (see kXcdOrderMaxEnvs)
   const int64_t lblock = A.xcd_per ? (int64_t)(blockIdx.x & 7) * A.xcd_per + (blockIdx.x >> 3) : (int64_t)blockIdx.x;
+  if constexpr (sizeof...(G) != 0) Pb = &group_block(Pp, tile_group..., lblock);   // the LOGICAL block: the table is in env order
+  const DevParams& P = *Pb;   // (the four waves of the reset by part share it: a group begins on a tile boundary)
   const int64_t block_base = lblock * kBlock;
   const int64_t wave_base = block_base + wave_in_block * kWave;
   const int64_t n = A.n;

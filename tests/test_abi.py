@@ -185,7 +185,7 @@ def test_no_kernel_uses_scratch_and_the_fused_step_fits_four_waves_per_simd():
     """Every kernel the library can launch keeps everything in registers: `make resource` (hipcc's kernel-resource remarks for all three
     translation units, gfx950 cross-compile, no GPU needed) must report ScratchSize 0 for ALL of them — the one-launch step kernels (general rigid bodies
     included), the actor / critic, the persistent kernels — and step_kernel_parts<float>, the kernel of batches beyond one workgroup
-    per CU, must fit 128 vector registers (four waves per SIMD).  (The general rigid-body forms of rdv_step_many / rdv_rollout, which
+    per CU, must fit 128 vector registers (four waves per SIMD), with and without the tile table of parameter groups.  (The general rigid-body forms of rdv_step_many / rdv_rollout, which
     spilled in round 2, are no longer instantiated: those calls run the rdv_step loop, include/rdv.h.)"""
     csrc = os.path.join(os.path.dirname(N.__file__), "csrc")
     r = subprocess.run(["make", "-C", csrc, "resource"], capture_output=True, text=True, timeout=600)
@@ -215,6 +215,10 @@ def test_no_kernel_uses_scratch_and_the_fused_step_fits_four_waves_per_simd():
     assert not any("rollout_kernelIfLb1" in k or "step_many_kernelIfLb1" in k for k in scratch)      # not instantiated any more
     parts = [v for k, v in vgprs.items() if "step_kernel_partsIf" in k]
     assert parts and max(parts) <= 128, parts
+    # ... and so must its instantiations for parameter groups (rdv_groups.hip: the tile table's type, `const int32_t* __restrict__`, is their
+    # last template argument): both of them are in the report, each within the same bound
+    grouped = {w: [v for k, v in vgprs.items() if w in k] for w in ("step_kernel_partsIfLb1EJrPKiE", "step_kernel_partsIfLb0EJrPKiE")}
+    assert all(len(v) == 1 and v[0] <= 128 for v in grouped.values()), grouped
     # the RK45 kernels fit two waves per SIMD (<= 256 registers, nothing parked in AGPRs or scratch) and the tile loop three (<= 168)
     assert max(v for k, v in vgprs.items() if "step_kernel_general" in k or "step_kernelIfLb0ELb1" in k or "step_kernelIdLb0ELb1" in k) <= 256
     assert max(v for k, v in vgprs.items() if "step_kernel_tilesIf" in k) <= 168

@@ -68,17 +68,41 @@ def _assert_outputs_equal(env, parts, what):
 
 
 # ---------------------------------------------------------------------------------------------------------------- 1
-@pytest.mark.parametrize("storage,on_done", [("f32", "reset"), ("f32", "halt"), ("f64", "reset"), ("f64", "halt")])
-def test_grouped_batch_equals_separate_handles_bit_for_bit(storage, on_done):
-    params = _sets()
-    env = _grouped(params, storage=storage, on_done=on_done, seed=11)
-    parts = _separate(params, SIZES, storage=storage, on_done=on_done, seed=11)
-    assert env.num_groups == 3 and [e.num_groups for e in parts] == [0, 0, 0]
-    assert [(s.start, s.stop) for s in env.group_slices] == [(0, 256), (256, 768), (768, 968)]
+RAGGED = [256, 293]    # 549 envs: three tiles, the last group partial, its last wave 37 live lanes; the XCD order pads the grid to 8 workgroups
+
+
+@pytest.mark.parametrize("storage,on_done,sizes,xcd_and_tape", [
+    pytest.param("f32", "reset", SIZES, False, id="f32-reset"), pytest.param("f32", "halt", SIZES, False, id="f32-halt"),
+    pytest.param("f64", "reset", SIZES, False, id="f64-reset"), pytest.param("f64", "halt", SIZES, False, id="f64-halt"),
+    # the XCD-contiguous block order forced on (five padding workgroups, which read the table's padding entries) and a reset tape
+    pytest.param("f32", "reset", RAGGED, True, id="f32-reset-ragged-xcd-tape"), pytest.param("f64", "reset", RAGGED, True, id="f64-reset-ragged-xcd-tape"),
+    pytest.param("f32", "halt", RAGGED, True, id="f32-halt-ragged-xcd-tape")])
+def test_grouped_batch_equals_separate_handles_bit_for_bit(storage, on_done, sizes, xcd_and_tape, monkeypatch):
+    params, n_envs = _sets()[:len(sizes)], sum(sizes)
+    if xcd_and_tape:
+        monkeypatch.setenv("RDV_XCD_ORDER", "1")     # read by rdv_create
+    env = _grouped(params, sizes, storage=storage, on_done=on_done, seed=11)
+    parts = _separate(params, sizes, storage=storage, on_done=on_done, seed=11)
+    monkeypatch.delenv("RDV_XCD_ORDER", raising=False)
+    assert env.num_groups == len(sizes) and [e.num_groups for e in parts] == [0] * len(sizes)
+    assert [(s.start, s.stop) for s in env.group_slices] == [(int(a), int(a + m)) for a, m in zip(np.cumsum([0] + sizes[:-1]), sizes)]
+    if xcd_and_tape:                                 # a tape of depth 2: the states two seeded resets of the grouped batch draw
+        rows = []
+        for seed in (21, 22):
+            env.seed(seed)
+            env.reset()
+            rows.append(to_numpy(env.get_state()))
+        tape = np.stack(rows)
+        env.seed(11)
+        env.set_reset_tape(torch.from_numpy(tape))
+        for e, s in zip(parts, env.group_slices):
+            e.set_reset_tape(torch.from_numpy(np.ascontiguousarray(tape[:, s])))
     np.testing.assert_array_equal(to_numpy(env.reset()), np.concatenate([to_numpy(e.reset()) for e in parts]))
+    if xcd_and_tape:
+        np.testing.assert_array_equal(to_numpy(env.get_state()), tape[0])
     a1 = to_numpy(parts[1].get_aux())
     assert a1[:, 2].sum() > 10                       # group 1 really starts inside the keep-out zone (the reset-time flag computation)
-    actions = _actions(5, STEPS, N_ENVS)
+    actions = _actions(5, STEPS, n_envs)
     for t in range(STEPS):
         if t == 24:                                  # tune_reward.py: reward coefficients changed mid-run, for one group
             kw = dict(collision_coef=3.0, bonus_coef=1.0, fuel_coef=0.0, att_coef=0.5)
@@ -96,7 +120,7 @@ def test_grouped_batch_equals_separate_handles_bit_for_bit(storage, on_done):
     for g, e in enumerate(parts):
         assert gs[g] == e.get_stats(), g             # counters exact, fp64 sums bit-equal: the same slots in the same order
         if on_done == "reset":
-            assert gs[g]["episodes"] >= 2 * SIZES[g]
+            assert gs[g]["episodes"] >= 2 * sizes[g]
     assert env.get_stats()["env_steps"] == sum(s["env_steps"] for s in gs)
     assert env.get_group_params(1).collision_coef == 3.0 and env.get_group_params(0).collision_coef == 0.7
     env.close(); [e.close() for e in parts]

@@ -96,13 +96,15 @@ def test_resource_report_lists_the_grouped_kernels():
         m = re.search(r"ScratchSize \[bytes/lane\]: (\d+)", line)
         if m and name:
             scratch[name] = int(m.group(1))
-    want = ["step_kernel_groupsIfLb1", "step_kernel_groupsIfLb0", "step_kernel_groupsIdLb1", "step_kernel_groupsIdLb0",
-            "step_kernel_groups_laneIfLb1ELb0", "step_kernel_groups_laneIfLb0ELb1", "step_kernel_groups_laneIfLb1ELb1",
-            "step_kernel_groups_laneIdLb1ELb0", "step_kernel_groups_laneIdLb0ELb1", "step_kernel_groups_laneIdLb1ELb1",
+    # the grouped step kernels are step_kernel_parts / step_kernel with the tile table's type (`const int32_t* __restrict__`: rPKi) as their
+    # last template argument
+    want = ["step_kernel_partsIfLb1EJrPKiE", "step_kernel_partsIfLb0EJrPKiE", "step_kernel_partsIdLb1EJrPKiE", "step_kernel_partsIdLb0EJrPKiE",
+            "step_kernelIfLb1ELb0ELb0EJrPKiE", "step_kernelIfLb0ELb0ELb1EJrPKiE", "step_kernelIfLb1ELb0ELb1EJrPKiE",
+            "step_kernelIdLb1ELb0ELb0EJrPKiE", "step_kernelIdLb0ELb0ELb1EJrPKiE", "step_kernelIdLb1ELb0ELb1EJrPKiE",
             "reset_kernel_groupsIf", "reset_kernel_groupsId", "access_kernel_groupsIf", "access_kernel_groupsId",
             "eval_summary_kernel_groupsIf", "eval_summary_kernel_groupsId"]
     for w in want:
         hits = [k for k in vgprs if w in k]
         assert hits, f"no kernel matching {w} in the resource report"
         assert all(scratch[k] == 0 for k in hits), (w, [scratch[k] for k in hits])
-    assert max(v for k, v in vgprs.items() if "step_kernel_groupsIf" in k) <= 128
+    assert max(v for k, v in vgprs.items() if "step_kernel_partsIf" in k and "EJrPKiE" in k) <= 128
