@@ -54,14 +54,24 @@ class OrcConfig(C.Structure):
 
 class OrcRigidBody(C.Structure):
     """self.inertia / self.inv_inertia (rendezvous_env.py:75-80), the target's (:96-101) and the torque arguments of
-    integrate_*_attitude (:552, :579); rtol/atol of the env's solve_ivp calls (:567-568)."""
+    integrate_*_attitude (:552, :579); rtol/atol of the env's solve_ivp calls (:567-568); closed_form[chaser, target]: that body takes
+    the exact solution instead of RK45 (the product's per-body choice; the reference itself integrates both with RK45)."""
     _fields_ = [("inertia_chaser", C.c_double * 9), ("inv_inertia_chaser", C.c_double * 9), ("torque_chaser", C.c_double * 3),
                 ("inertia_target", C.c_double * 9), ("inv_inertia_target", C.c_double * 9), ("torque_target", C.c_double * 3),
-                ("rtol", C.c_double), ("atol", C.c_double)]
+                ("rtol", C.c_double), ("atol", C.c_double), ("closed_form", C.c_int32 * 2)]
+
+    @staticmethod
+    def closed_form_applies(inertia, torque):
+        """c * Identity and zero torque: w x (I w) = 0, the rate is constant and the attitude ODE has the exact solution."""
+        m = np.asarray(inertia, np.float64).reshape(3, 3)
+        return bool((m == m[0, 0] * np.eye(3)).all() and (np.asarray(torque, np.float64) == 0.0).all())
 
     @classmethod
     def make(cls, inertia_chaser, inertia_target, torque_chaser=(0, 0, 0), torque_target=(0, 0, 0), rtol=1e-7, atol=1e-6,
-             inv_inertia_chaser=None, inv_inertia_target=None):
+             inv_inertia_chaser=None, inv_inertia_target=None, integrator="rk45"):
+        """integrator "rk45": both bodies on RK45, as the reference does.  "auto": a body to which the closed form applies takes it."""
+        if integrator not in ("rk45", "auto"):
+            raise ValueError(f"integrator {integrator!r}: 'rk45' or 'auto'")
         b = cls()
         ic = np.asarray(inertia_chaser, np.float64).reshape(3, 3); it = np.asarray(inertia_target, np.float64).reshape(3, 3)
         iic = np.linalg.inv(ic) if inv_inertia_chaser is None else np.asarray(inv_inertia_chaser, np.float64)   # :80
@@ -70,6 +80,8 @@ class OrcRigidBody(C.Structure):
         b.inertia_target[:] = it.ravel(); b.inv_inertia_target[:] = iit.ravel()
         b.torque_chaser[:] = np.asarray(torque_chaser, np.float64); b.torque_target[:] = np.asarray(torque_target, np.float64)
         b.rtol, b.atol = rtol, atol
+        if integrator == "auto":
+            b.closed_form[:] = [int(cls.closed_form_applies(ic, torque_chaser)), int(cls.closed_form_applies(it, torque_target))]
         return b
 
 
@@ -115,8 +127,10 @@ def lib():
         L = C.CDLL(_LIB_PATH)
         L.orc_sizeof_env.restype = C.c_int64
         L.orc_sizeof_params.restype = C.c_int64
+        L.orc_sizeof_rigid_body.restype = C.c_int64
         assert L.orc_sizeof_env() == ENV_DTYPE.itemsize, (L.orc_sizeof_env(), ENV_DTYPE.itemsize)
         assert L.orc_sizeof_params() == C.sizeof(OrcParams)
+        assert L.orc_sizeof_rigid_body() == C.sizeof(OrcRigidBody)
         L.orc_angle_between.restype = C.c_double
         L.orc_dist_from_koz.restype = C.c_double
         _lib = L

@@ -31,6 +31,7 @@
 int orc_version(void) { return 1; }
 int64_t orc_sizeof_env(void) { return (int64_t)sizeof(OrcEnv); }
 int64_t orc_sizeof_params(void) { return (int64_t)sizeof(OrcParams); }
+int64_t orc_sizeof_rigid_body(void) { return (int64_t)sizeof(OrcRigidBody); }
 
 static const double ORC_PI = 3.14159265358979323846;
 
@@ -550,8 +551,10 @@ static void step_one(const OrcParams* p, const OrcConfig* c, OrcEnv* e, int64_t 
     e->wc[j] = e->wc[j] + (c->numpy_legacy ? (double)dwb32[j] : (double)a32[3 + j] * p->max_delta_w);
   if (c->integrator == ORC_INTEGRATOR_GENERAL && c->rigid) {
     const OrcRigidBody* b = c->rigid;
-    orc_integrate_attitude_general(e->qc, e->wc, p->dt, b->inertia_chaser, b->inv_inertia_chaser, b->torque_chaser, b->rtol, b->atol); /* :181 */
-    orc_integrate_attitude_general(e->qt, e->wt, p->dt, b->inertia_target, b->inv_inertia_target, b->torque_target, b->rtol, b->atol); /* :184 */
+    if (b->closed_form[0]) orc_integrate_attitude(e->qc, e->wc, p->dt, ORC_INTEGRATOR_EXACT);
+    else orc_integrate_attitude_general(e->qc, e->wc, p->dt, b->inertia_chaser, b->inv_inertia_chaser, b->torque_chaser, b->rtol, b->atol); /* :181 */
+    if (b->closed_form[1]) orc_integrate_attitude(e->qt, e->wt, p->dt, ORC_INTEGRATOR_EXACT);
+    else orc_integrate_attitude_general(e->qt, e->wt, p->dt, b->inertia_target, b->inv_inertia_target, b->torque_target, b->rtol, b->atol); /* :184 */
   } else {
     orc_integrate_attitude(e->qc, e->wc, p->dt, c->integrator);                             /* :181 */
     orc_integrate_attitude(e->qt, e->wt, p->dt, c->integrator);                             /* :184 */

@@ -67,11 +67,15 @@ enum { ORC_INTEGRATOR_EXACT = 0, ORC_INTEGRATOR_RK45 = 1, ORC_INTEGRATOR_GENERAL
 
 /* The rigid-body attributes of the env (self.inertia / self.inv_inertia :75-80, self.inertia_target / self.inv_inertia_target
  * :96-101; row-major 3x3) and the torque arguments of integrate_chaser_attitude / integrate_target_attitude (:552, :579).
- * Used with ORC_INTEGRATOR_GENERAL: scipy's RK45 on the full right-hand side (dynamics.py:93-175). */
+ * Used with ORC_INTEGRATOR_GENERAL: scipy's RK45 on the full right-hand side (dynamics.py:93-175).
+ * closed_form[0 | 1] (chaser, target; 0 = what the reference does): that body is integrated with the exact solution
+ * (ORC_INTEGRATOR_EXACT) while the other stays on RK45 — the two attitude ODEs of a step are independent (:181, :184).  The caller
+ * sets it only for a body whose tensor is c * Identity with zero torque; orc_step does not check. */
 typedef struct OrcRigidBody {
   double inertia_chaser[9], inv_inertia_chaser[9], torque_chaser[3];
   double inertia_target[9], inv_inertia_target[9], torque_target[3];
   double rtol, atol;      /* :567-568: 1e-7, 1e-6 */
+  int32_t closed_form[2];
 } OrcRigidBody;
 
 typedef struct OrcConfig {
@@ -141,6 +145,7 @@ void orc_observe(const OrcParams* p, int64_t n, const OrcEnv* envs, float* obs);
 void orc_diagnose_batch(const OrcParams* p, int64_t n, const OrcEnv* envs, double* diag);
 int64_t orc_sizeof_env(void);
 int64_t orc_sizeof_params(void);
+int64_t orc_sizeof_rigid_body(void);
 
 #ifdef __cplusplus
 }

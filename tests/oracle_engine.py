@@ -11,14 +11,14 @@ from helpers import oracle_batch, to_numpy, to_oracle_params
 
 class OracleEngine:
     def __init__(self, num_envs, params, storage="f64", on_done="reset", seed=0, env_id_offset=0, n_threads=1,
-                 numpy_legacy=False, tape=None):
+                 numpy_legacy=False, tape=None, rigid=None):
         self.num_envs = int(num_envs)
         self.params = params.copy()
         self.device = torch.device("cpu")
         self._ctor = dict(storage=storage, on_done=on_done)          # as RendezvousBatch records them (helpers.batch_modes)
         self._orc = oracle_batch(
             self.num_envs, params, storage, on_done,
-            seed=seed, env_id_offset=env_id_offset, n_threads=n_threads, numpy_legacy=numpy_legacy,
+            seed=seed, env_id_offset=env_id_offset, n_threads=n_threads, numpy_legacy=numpy_legacy, rigid=rigid,
             **({} if tape is None else {"tape": np.asarray(tape, dtype=np.float64)}))      # reset tape [depth, N, 20]: recorded initial states
         self._orc_halts = on_done == "halt"
         self.obs = self.reward = self.done = None

@@ -2,11 +2,26 @@
 GPU tests (run with `-m gpu`) of the general rigid-body path: anisotropic inertia tensors and constant
 body torques, integrated inside the step kernel with the reference's scheme (scipy RK45 restated per lane).
 
-  - against the reference directly: tests/golden/steps_F_rigid.npz, recorded from the unmodified reference env with
-    anisotropic tensors assigned to its inertia attributes (tests/golden/make_golden_rigid.py);
-  - against the CPU oracle (itself pinned to scipy's solve_ivp in tests/test_oracle_golden.py: same results to 2e-14, same
-    number of right-hand-side evaluations) on random tensors, torques and parameters, both storage precisions;
-  - integrator selection and validation of rdv_set_rigid_body.
+References: the reference's own transitions (tests/golden/steps_F_rigid.npz, recorded from the unmodified reference env with
+anisotropic tensors assigned to its inertia attributes, tests/golden/make_golden_rigid.py) and the CPU oracle (pinned to scipy's
+solve_ivp in tests/test_oracle_golden.py: same results to 2e-14, same number of right-hand-side evaluations; its per-body choice
+between the closed form and RK45, OrcRigidBody.make(integrator="auto"), pinned there bit for bit to the two modes the reference pins).
+
+Which step kernel each test runs (names as rdv_debug_last_kernel spells them; ST = float | double):
+  test_transitions_match_the_reference_with_anisotropic_bodies     step_kernel<double, true, true>, the evaluator build (not asserted)
+  test_reference_transitions_on_the_training_kernels               step_kernel_general<double>, step_kernel<double, false, true>: asserted
+                                                                   on every step, golden F
+  test_training_kernels_against_the_oracle                         step_kernel_general<ST> (general target, both bodies, forced RK45) and
+                                                                   step_kernel<ST, false, true> (general chaser; both with
+                                                                   RDV_GENERAL_SPLIT=0): asserted on every step; tests/rigid_cases.py
+  test_the_three_general_body_forms_agree_bit_for_bit              step_kernel_general<ST>, step_kernel<ST, false, true> and
+                                                                   step_kernel<ST, true, true> beside each other: asserted on every step
+  test_random_bodies_against_the_oracle                            the evaluator build step_kernel<ST, true, true> (not asserted)
+  test_persistent_kernels_step_general_bodies_like_the_step_loop   rdv_step_many / rdv_rollout run the loop of training steps:
+                                                                   step_kernel_general<ST> (not asserted), compared with rdv_step itself
+  test_rk45_on_the_default_bodies_agrees_with_the_closed_form      step_kernel_general<double>, forced RK45 (not asserted), 512 envs
+  test_nan_actions_poison_only_their_env                           step_kernel_general<double> (not asserted), against a second handle
+  the rest                                                         validation and the attribute surface: one or two steps, finite state
 
 Tolerances: the kernel runs the same operations as the oracle in fp64 (no fused multiply-adds in the integrator); libm's
 pow in the step-size controller differs in the last bit, which moves an accepted step size by 1e-16 relative.  The comparisons
@@ -17,6 +32,7 @@ import pytest
 
 import oracle
 import parity
+import rigid_cases
 from helpers import counter_actions, gpu_batch, load_golden, oracle_batch, params_from_note, shipped_policy, to_numpy
 from reinforcement_learning_rendezvous_amd.params import make_params
 
@@ -37,13 +53,111 @@ def test_transitions_match_the_reference_with_anisotropic_bodies():
     env.close()
 
 
-def _random_body(rng):
-    def tensor():
-        qm, _ = np.linalg.qr(rng.normal(size=(3, 3)))
-        m = qm @ np.diag(rng.uniform(5.0, 40.0, 3)) @ qm.T
-        return 0.5 * (m + m.T)
-    return dict(inertia=tensor(), inertia_target=np.diag(rng.uniform(5.0, 40.0, 3)),
-                torque=rng.normal(scale=0.01, size=3), torque_target=rng.normal(scale=0.02, size=3))
+def _every_step_runs(env, kernel):
+    """env.step, with the name of the kernel it launched asserted after every call."""
+    step = env.step
+
+    def checked(*a, **kw):
+        out = step(*a, **kw)
+        assert env.last_kernel == kernel, f"ran {env.last_kernel!r}, expected {kernel!r}"
+        checked.calls += 1
+        return out
+    checked.calls = 0
+    env.step = checked
+    return checked
+
+
+@pytest.mark.parametrize("split", [True, False], ids=["step_kernel_general", "RDV_GENERAL_SPLIT=0"])
+def test_reference_transitions_on_the_training_kernels(split, monkeypatch):
+    """Golden F once more without diag: the training path, whose two kernels for general bodies (the target's RK45 on partner waves;
+    both integrations in one lane) are the ones PPO training runs.  The error norms and flags come from rdv_diagnose of the rows that
+    were not reset; same numbers as the evaluator replay above."""
+    g = load_golden("steps_F_rigid.npz")
+    p, _ = params_from_note(g["env_kwargs_json"])
+    if not split:
+        monkeypatch.setenv("RDV_GENERAL_SPLIT", "0")                    # read in rdv_create
+    env = gpu_batch(g["actions"].shape[1], params=p, storage="f64", on_done="reset", seed=0)
+    env.set_rigid_body(inertia=g["inertia_chaser"], inertia_target=g["inertia_target"])
+    steps = _every_step_runs(env, "step_kernel_general<double>" if split else "step_kernel<double, false, true>")
+    parity.replay_golden(env, g, halt=False, diag=False, obs_tol=6e-8, reward_kw=dict(rtol=0, atol=2e-6), reward_dtype=np.float64,
+                         bookkeeping=False)
+    assert steps.calls > 0
+    env.close()
+
+
+_random_body = rigid_cases.random_body
+
+# the training path against the oracle: parity.py's constants, except the reward to 3e-6 (as test_random_bodies_against_the_oracle) and
+# the counters without the sums; the state, the aux rows and rdv_diagnose's flags and error norms (live rows) on every step
+RIGID_KW = dict(reward_tol=3e-6, stats_sums=False)
+
+
+@pytest.mark.parametrize("case", rigid_cases.CASES, ids=rigid_cases.CASE_IDS)
+def test_training_kernels_against_the_oracle(case, monkeypatch):
+    """Every general-body kernel of the training path (no diag), by name on every step, against the oracle with the same per-body
+    integrator choice, at the sizes where the layout of step_kernel_general can go wrong (tests/rigid_cases.py: one lane, a second wave
+    with one row, a second workgroup with one env, a ragged wave in it), both storages, reset and halt, 40 steps.  That the oracle's
+    run ends episodes, steps a partly halted first workgroup (its handoff rows are stale) and moves the general body's rate is
+    asserted here and, for the oracle alone, in tests/test_parity_helpers.py."""
+    c = rigid_cases.RigidCase(*case)
+    for k, v in c.env_vars.items():
+        monkeypatch.setenv(k, v)                                        # read in rdv_create
+    env = gpu_batch(c.n, params=c.params, storage=c.storage, on_done=c.on_done, seed=c.seed)
+    env.set_rigid_body(**c.body)
+    orc = c.oracle()
+    parity.check_reset_obs(env.reset(), orc.reset())
+    cond = rigid_cases.Conditions(c, orc)
+
+    def on_step(orc_, ref, t):
+        assert env.last_kernel == c.kernel, f"step {t}: ran {env.last_kernel!r}, expected {c.kernel!r}"
+        cond(orc_, ref, t)
+    parity.run_against_oracle(env, orc, c.actions, c.storage, None, on_step=on_step, **RIGID_KW)
+    cond.check()
+    env.close()
+
+
+@pytest.mark.parametrize("on_done", ["reset", "halt"])
+@pytest.mark.parametrize("storage", ["f32", "f64"])
+def test_the_three_general_body_forms_agree_bit_for_bit(storage, on_done, monkeypatch):
+    """csrc/rdv_general.hip: "same functions on the same inputs as the fused general kernel: bit-identical results".  One body set
+    (both general), one seed, one action tape, 333 envs: step_kernel_general, step_kernel<ST, false, true> (RDV_GENERAL_SPLIT=0) and
+    the evaluator build step_kernel<ST, true, true> (diag) beside each other, every output and the whole state equal on every step."""
+    c = rigid_cases.RigidCase("both", 333, storage, on_done, seed=777)
+    st = "float" if storage == "f32" else "double"
+    names = [f"step_kernel_general<{st}>", f"step_kernel<{st}, false, true>", f"step_kernel<{st}, true, true>"]
+    envs = []
+    for k in range(3):
+        if k == 1:
+            monkeypatch.setenv("RDV_GENERAL_SPLIT", "0")                # read in rdv_create
+        else:
+            monkeypatch.delenv("RDV_GENERAL_SPLIT", raising=False)
+        envs.append(gpu_batch(c.n, params=c.params, storage=storage, on_done=on_done, seed=c.seed))
+        envs[-1].set_rigid_body(**c.body)
+    first = envs[0].reset().clone()
+    assert all(torch.equal(e.reset(), first) for e in envs[1:])
+
+    def same(what, t, tensors):
+        for name, x in zip(names[1:], tensors[1:]):
+            if not torch.equal(x, tensors[0]):      # (NaN never occurs: the oracle comparison above covers these bodies)
+                d = (x.double() - tensors[0].double()).abs()
+                raise AssertionError(f"{what}, step {t}: {name} differs from {names[0]} in {int((d > 0).sum())} entries, by {float(d.max()):.3e} at most")
+    n_done = 0
+    for t, a in enumerate(c.actions):
+        ta = torch.from_numpy(a).cuda()
+        outs = [e.step(ta, diag=(k == 2)) for k, e in enumerate(envs)]
+        for e, name in zip(envs, names):
+            assert e.last_kernel == name, f"step {t}: ran {e.last_kernel!r}, expected {name!r}"
+        for j, what in enumerate(("obs", "reward", "done")):
+            same(what, t, [o[j] for o in outs])
+        same("done_reason", t, [e.done_reason for e in envs])
+        same("state", t, [e.get_state() for e in envs])
+        same("aux", t, [e.get_aux() for e in envs])
+        stats = [e.get_stats() for e in envs]
+        assert stats[1] == stats[0] and stats[2] == stats[0], f"stats, step {t}"
+        n_done += int(outs[0][2].sum())
+    assert n_done > 0
+    for e in envs:
+        e.close()
 
 
 @pytest.mark.parametrize("case", range(4))
@@ -74,8 +188,9 @@ def test_random_bodies_against_the_oracle(case):
 
 @pytest.mark.parametrize("n,storage,on_done", [(1000, "f32", "reset"), (260, "f64", "reset"), (512, "f32", "halt"), (1001, "f32", "reset")])
 def test_persistent_kernels_step_general_bodies_like_the_step_loop(n, storage, on_done):
-    """rdv_step_many and rdv_rollout with general rigid bodies against rdv_step / rdv_policy_act + rdv_step, which
-    test_random_bodies_against_the_oracle ties to the oracle: bit for bit.  (Since round 3 the two calls RUN that loop for general
+    """rdv_step_many and rdv_rollout with general rigid bodies against rdv_step / rdv_policy_act + rdv_step — the training path's
+    step_kernel_general, which test_training_kernels_against_the_oracle ties to the oracle and
+    test_reference_transitions_on_the_training_kernels to the reference: bit for bit.  (Since round 3 the two calls RUN that loop for general
     bodies — include/rdv.h — instead of a persistent kernel with the per-lane RK45 inside, which spilled; what this checks is the
     plumbing of the rows: [K,N,...] outputs, unclipped actions, log-probabilities, the last observation, also for N not a multiple
     of 4, where a row of [K,N,17] is not 16-byte aligned.)"""
