@@ -480,6 +480,65 @@ typedef struct RdvRolloutOut {
 int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut* out_host, int deterministic,
                 uint64_t noise_seed, uint64_t noise_counter0, void* stream);
 
+/*
+ * Learner-ready rollouts (added within ABI 5): the columns of SB3's RolloutBuffer that rdv_rollout does not write — values, advantages,
+ * returns (RolloutBuffer.compute_returns_and_advantage, called by collect_rollouts; reference main.py:114) — and the refresh of a policy
+ * handle's weights after an optimiser step.  The reference never sets TimeLimit.truncated (vec_env.py:6-7), so SB3's time-limit
+ * bootstrap does not apply and is not built.  Out of scope: the PPO update itself and advantage normalisation (SB3 normalises per
+ * minibatch in train()).
+ *
+ * rdv_gae: generalised advantage estimation over [T,N] rows, ONE kernel for all T steps (csrc/rdv_advantages.h).  reward, done, values,
+ *   advantages and returns are [n_steps, n] contiguous device arrays, time-major, as rdv_rollout writes them; last_value is [n].  done[t]
+ *   is the row of step t, SB3's episode_starts[t+1].  The contract: the outputs are BIT-IDENTICAL to SB3's loop evaluated in NumPy
+ *   float32.  With g = (float)gamma and c = (float)(gamma * gae_lambda) — the product taken in double, then rounded once — for
+ *   t = n_steps-1 .. 0 and each env i:
+ *       nnt   = 1.0f - (float)done[t][i]
+ *       nv    = (t == n_steps-1) ? last_value[i] : values[t+1][i]
+ *       delta = ((reward[t][i] + (g * nv) * nnt) - values[t][i])
+ *       A     = delta + ((c * nnt) * A)                     A = 0 before the first step
+ *       advantages[t][i] = A;   returns[t][i] = A + values[t][i]
+ *   Every operation is rounded to fp32 on its own, in exactly this association: no fused multiply-add (a * b + c contracted into an
+ *   FMA rounds once where NumPy rounds twice, and changes the last bit); the kernel is compiled with contraction off.  A NaN or an
+ *   infinity in a row reaches only that env's outputs.  The recurrence is not split over T (segments plus a carry fix-up re-associate
+ *   the products: not bit-exact), so each env is one sequential chain: at small n the call is bound by latency, not bandwidth.
+ *   RDV_ERR_INVALID_ARGUMENT, the message naming the argument, for a null pointer, n_steps <= 0, n <= 0, and a gamma or gae_lambda that
+ *   is not finite or lies outside [0, 1]; these checks come before the device check and need no GPU.  The outputs must not alias the
+ *   inputs (not checked).  Enqueued on `stream`, legal inside a stream capture, no allocation, no synchronisation.
+ *
+ * rdv_rollout_advantages: values and advantages of a rollout in one call.  On `stream`, in this order: the critic over the
+ *   [n_steps * n, 17] rows of rows->obs into out->values, the critic over rows->last_obs into out->last_value — both by the launch of
+ *   rdv_policy_value (shipped or general architecture: values are bit-identical to what rdv_policy_value gives for the same rows; there
+ *   is no second critic kernel) — then the kernel of rdv_gae.  It reads rows->obs, rows->reward, rows->done and rows->last_obs; the
+ *   other members of `rows` may be NULL.  All four members of `out` are required.  The values are the critic's AT CALL TIME for the
+ *   observations the actor saw; for an env that was reset at the last step, last_obs is the reset observation, whose value is multiplied
+ *   by nnt = 0, as in SB3.  Argument checks as rdv_gae's (before the handle is looked at); then RDV_ERR_BAD_HANDLE for an invalid handle,
+ *   RDV_ERR_INVALID_ARGUMENT for an actor handle; alignment as rdv_policy_value (rows->obs, rows->last_obs: 16 bytes).
+ *
+ * rdv_policy_set_weights: new weights for an existing actor or critic handle, in the layout of rdv_policy_create_mlp: n_hidden + 1 HOST
+ *   pointers each, hidden layers first, the head last; the count and the shapes are those of the handle's own spec (three layers for a
+ *   handle of rdv_policy_create / rdv_critic_create).  log_std_host is required for an actor and must be NULL for a critic.  The block is
+ *   packed as at creation (same size) and written into the handle's existing device allocation.  A non-finite weight is
+ *   RDV_ERR_BAD_PARAMS and leaves the handle's block untouched.  ORDERING: the write is a copy enqueued on `stream` — launches already
+ *   queued on that stream read the old block, launches enqueued there after this call returns read the new one, and there is no other
+ *   synchronisation of the device (work on OTHER streams that uses the handle is not ordered against it: order it with events, as for any
+ *   buffer).  The host arrays may be reused as soon as the call returns: they are packed into a pinned staging buffer that the handle
+ *   owns (allocated by the first call), and an event recorded behind the copy makes the NEXT call on the handle wait on the host until
+ *   the previous copy has left that buffer.  Because of the reused buffer it is not legal inside a stream capture
+ *   (RDV_ERR_INVALID_ARGUMENT when hipStreamIsCapturing says so).
+ */
+typedef struct RdvAdvantageOut {
+  float* values;      /* [T,N] required: critic(obs[t])      (buffer.values)     */
+  float* last_value;  /* [N]   required: critic(last_obs)                        */
+  float* advantages;  /* [T,N] required                      (buffer.advantages) */
+  float* returns;     /* [T,N] required                      (buffer.returns)    */
+} RdvAdvantageOut;
+int rdv_gae(const float* reward, const uint8_t* done, const float* values, const float* last_value, int32_t n_steps, int64_t n,
+            double gamma, double gae_lambda, float* advantages, float* returns, int device, void* stream);
+int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,
+                           const RdvAdvantageOut* out, void* stream);
+int rdv_policy_set_weights(rdv_policy p, const float* const* weights_host, const float* const* biases_host, const float* log_std_host,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            "rdv_param_groups_check", "rdv_param_groups_validate", "rdv_set_param_groups", "rdv_set_group_params", "rdv_get_group_params",
            "rdv_num_groups", "rdv_get_group_stats", "rdv_eval_group_summary",
            # other MLP architectures (added within ABI 5)
-           "rdv_mlp_spec_default", "rdv_mlp_spec_check", "rdv_policy_create_mlp", "rdv_critic_create_mlp", "rdv_policy_get_spec"]
+           "rdv_mlp_spec_default", "rdv_mlp_spec_check", "rdv_policy_create_mlp", "rdv_critic_create_mlp", "rdv_policy_get_spec",
+           # learner-ready rollouts (added within ABI 5)
+           "rdv_gae", "rdv_rollout_advantages", "rdv_policy_set_weights"]
 
 
 class RdvError(RuntimeError):
@@ -74,6 +76,11 @@ class RolloutOut(C.Structure):
                 ("log_prob", C.c_void_p), ("last_obs", C.c_void_p)]
 
 
+class AdvantageOut(C.Structure):
+    """RdvAdvantageOut: device pointers of the rollout-buffer columns rdv_rollout_advantages writes"""
+    _fields_ = [("values", C.c_void_p), ("last_value", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p)]
+
+
 ACT_TANH, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 MLP_MAX_HIDDEN = 4
 
@@ -104,7 +111,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the five translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip) for gfx950 and link librdv_hip.so
+    """Compile the six translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_advantages.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -180,6 +187,9 @@ def lib():
         "rdv_policy_create_mlp": (C.c_int, [C.POINTER(MlpSpec), vp, vp, vp, C.c_int, C.POINTER(vp)]),
         "rdv_critic_create_mlp": (C.c_int, [C.POINTER(MlpSpec), vp, vp, C.c_int, C.POINTER(vp)]),
         "rdv_policy_get_spec": (C.c_int, [vp, C.POINTER(MlpSpec)]),
+        "rdv_gae": (C.c_int, [vp, vp, vp, vp, i32, i64, C.c_double, C.c_double, vp, vp, C.c_int, vp]),
+        "rdv_rollout_advantages": (C.c_int, [vp, C.POINTER(RolloutOut), i32, i64, C.c_double, C.c_double, C.POINTER(AdvantageOut), vp]),
+        "rdv_policy_set_weights": (C.c_int, [vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

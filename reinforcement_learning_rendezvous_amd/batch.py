@@ -277,6 +277,14 @@ class RendezvousBatch:
         self._defer(obs=out["last_obs"], reward=out["reward"][T - 1], done=out["done"][T - 1])
         return out
 
+    def collect(self, policy, n_steps, gamma=0.99, gae_lambda=0.95, deterministic=False, out=None):
+        """``rollout`` followed by ``policy.advantages`` on the current stream: every column of SB3's RolloutBuffer for ``n_steps``
+        steps — the rows of ``rollout`` plus ``values``, ``last_value``, ``advantages``, ``returns`` (what ``collect_rollouts`` leaves
+        behind after ``compute_returns_and_advantage``, main.py:114).  The rows are those of the two separate calls; pass the dict
+        back as ``out`` to reuse every buffer."""
+        ro = self.rollout(policy, n_steps, deterministic=deterministic, out=out)
+        return policy.advantages(ro, gamma=gamma, gae_lambda=gae_lambda, out=out)
+
     # ------------------------------------------------------------------------------------------------ evaluator helpers
     def set_state(self, states):
         """Overwrite rc, vc, qc, wc, qt, wt ([N,20] float64, CSV column order) as monte_carlo.py:107-112 does."""

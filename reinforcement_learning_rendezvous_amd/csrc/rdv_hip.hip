@@ -10,6 +10,7 @@
 #include "rdv_device.h"
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
+#include "rdv_advantages.h"
 
 #include <hip/hip_runtime.h>
 
@@ -416,6 +417,8 @@ struct RdvPolicyNet {
   RdvMlpSpec spec;
   bool shipped_arch;   // 17-64-64-out tanh: policy_act_kernel / policy_value_kernel, and the persistent rollout_kernel
   int block_floats;
+  float* staging;      // rdv_policy_set_weights: pinned host copy of the block in flight (made by the first call, nullptr before)
+  hipEvent_t staged;   // ... recorded behind the copy out of it: the next call waits for it before it overwrites `staging`
 };
 static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
 static constexpr uint32_t kPolicyMagic = 0x52445650u;   // "RDVP"
@@ -429,7 +432,7 @@ static bool all_finite(const float* w, int count) {
 static int finish_policy(const char* who, const std::vector<float>& packed, const RdvMlpSpec& spec, bool shipped_arch, int out_dim, int device, rdv_policy* out) {
   RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
   if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
-  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim;
+  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr; p->staged = nullptr;
   p->spec = spec; p->shipped_arch = shipped_arch; p->block_floats = shipped_arch ? kPolFloats : (int)packed.size();
   hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
   if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -526,11 +529,50 @@ int rdv_policy_get_spec(rdv_policy p, RdvMlpSpec* out_host) {
   return RDV_OK;
 }
 
+// ---- refreshing a handle's weights (a learner's optimiser step): the block is packed on the host as at creation and copied into the
+// handle's device allocation from a pinned buffer of the handle's own, on the caller's stream
+int rdv_policy_set_weights(rdv_policy p, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (!weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: null weights_host or biases_host");
+  const bool actor = p->out_dim == kPolOut;
+  if (actor && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: log_std_host is required for an actor");
+  if (!actor && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: log_std_host must be null for a critic (rdv_critic_create)");
+  const int L = p->spec.n_hidden;
+  for (int l = 0; l <= L; ++l)
+    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: null weights or biases of layer %d", l);
+  for (int l = 0; l <= L; ++l) {
+    const int in_w = l == 0 ? kPolIn : p->spec.hidden[l - 1], out_w = l < L ? p->spec.hidden[l] : p->out_dim;
+    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_set_weights: non-finite weight in layer %d", l);
+  }
+  std::vector<float> packed;
+  if (p->shipped_arch) pack_policy_weights(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, p->out_dim, packed);
+  else pack_mlp_weights(p->spec, p->out_dim, weights, biases, log_std, packed);
+  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "rdv_policy_set_weights: the packed block has %d floats, the handle's %d", (int)packed.size(), p->block_floats);
+  DeviceGuard guard(p->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  RDV_HIP(hipStreamIsCapturing(s, &capturing));
+  if (capturing != hipStreamCaptureStatusNone) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: not legal inside a stream capture (the staging buffer is reused by the next call)");
+  const size_t bytes = packed.size() * sizeof(float);
+  if (!p->staging) {
+    RDV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->staging), bytes, hipHostMallocDefault));
+    RDV_HIP(hipEventCreateWithFlags(&p->staged, hipEventDisableTiming));
+  } else {
+    RDV_HIP(hipEventSynchronize(p->staged));   // the previous refresh has left the buffer (usually long ago)
+  }
+  std::memcpy(p->staging, packed.data(), bytes);
+  RDV_HIP(hipMemcpyAsync(p->weights, p->staging, bytes, hipMemcpyHostToDevice, s));
+  RDV_HIP(hipEventRecord(p->staged, s));
+  return RDV_OK;
+}
+
 int rdv_policy_destroy(rdv_policy p) {
   if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
   DeviceGuard guard(p->device);
   (void)hipDeviceSynchronize();
   (void)hipFree(p->weights);
+  if (p->staging) (void)hipHostFree(p->staging);
+  if (p->staged) (void)hipEventDestroy(p->staged);
   p->magic = 0;
   delete p;
   return RDV_OK;
@@ -572,6 +614,57 @@ int rdv_policy_value(rdv_policy p, const float* obs, float* values, int64_t n, v
     return RDV_OK;
   }
   hipLaunchKernelGGL(policy_value_kernel, policy_grid(n), dim3(kPolBlock), kPolLdsBytes, static_cast<hipStream_t>(stream), p->weights, obs, values, n);
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- GAE (csrc/rdv_advantages.h)
+// gamma, gae_lambda and the sizes: what rdv_gae and rdv_rollout_advantages check alike, before any device is looked at
+static int check_gae_scalars(const char* who, int32_t n_steps, int64_t n, double gamma, double gae_lambda) {
+  if (n_steps <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_steps must be positive (got %d)", who, n_steps);
+  if (n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
+  if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
+  if (!std::isfinite(gae_lambda) || gae_lambda < 0.0 || gae_lambda > 1.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: gae_lambda must be in [0, 1] (got %g)", who, gae_lambda);
+  return RDV_OK;
+}
+// (diagnostics only: RDV_GAE_DEPTH = 2 | 4 | 8 | 16 picks the kernel's prefetch depth, for tools/gae_time.py; results do not depend on it)
+static int gae_depth() {
+  const char* x = getenv("RDV_GAE_DEPTH");
+  const int d = x ? atoi(x) : 0;
+  return (d == 2 || d == 4 || d == 8 || d == 16) ? d : 0;
+}
+
+int rdv_gae(const float* reward, const uint8_t* done, const float* values, const float* last_value, int32_t n_steps, int64_t n,
+            double gamma, double gae_lambda, float* advantages, float* returns, int device, void* stream) {
+  const struct { const void* p; const char* name; } ptrs[] = {{reward, "reward"}, {done, "done"}, {values, "values"}, {last_value, "last_value"},
+                                                              {advantages, "advantages"}, {returns, "returns"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_gae: %s is null", a.name);
+  if (int rc = check_gae_scalars("rdv_gae", n_steps, n, gamma, gae_lambda)) return rc;
+  if (int rc = check_device("rdv_gae", device)) return rc;
+  DeviceGuard guard(device);
+  gae_launch(reward, done, values, last_value, n_steps, n, (float)gamma, (float)(gamma * gae_lambda), advantages, returns, gae_depth(), static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,
+                           const RdvAdvantageOut* out, void* stream) {
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows is null");
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: out is null");
+  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->reward, "rows->reward"}, {rows->done, "rows->done"},
+                                                              {rows->last_obs, "rows->last_obs"}, {out->values, "out->values"}, {out->last_value, "out->last_value"},
+                                                              {out->advantages, "out->advantages"}, {out->returns, "out->returns"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: %s is null", a.name);
+  if (int rc = check_gae_scalars("rdv_rollout_advantages", n_steps, n, gamma, gae_lambda)) return rc;
+  if (!critic || critic->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: this handle is an actor (rdv_policy_create)");
+  if (misaligned(rows->obs, 16) || misaligned(rows->last_obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows->obs and rows->last_obs must be 16-byte aligned");
+  // the critic at call time over the rows the actor saw, then over the observation after the last step: rdv_policy_value's own launches
+  if (int rc = rdv_policy_value(critic, rows->obs, out->values, (int64_t)n_steps * n, stream)) return rc;
+  if (int rc = rdv_policy_value(critic, rows->last_obs, out->last_value, n, stream)) return rc;
+  DeviceGuard guard(critic->device);
+  gae_launch(rows->reward, rows->done, out->values, out->last_value, n_steps, n, (float)gamma, (float)(gamma * gae_lambda), out->advantages, out->returns,
+             gae_depth(), static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }

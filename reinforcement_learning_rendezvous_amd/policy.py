@@ -121,21 +121,34 @@ class MlpPolicy(torch.nn.Module):
                 torch.nn.init.orthogonal_(lin.weight, gain=gain, generator=g)
                 torch.nn.init.zeros_(lin.bias)
         else:
-            def load(layers, keys):
-                for lin, (kw, kb) in zip(layers, keys):
-                    w, b = (torch.as_tensor(np.asarray(weights[k]), dtype=torch.float32) for k in (kw, kb))
-                    if w.shape != lin.weight.shape or b.shape != lin.bias.shape:
-                        raise ValueError(f"{kw}: shape {tuple(w.shape)} does not fit net_arch (expected {tuple(lin.weight.shape)})")
-                    lin.weight.copy_(w); lin.bias.copy_(b)
-            with torch.no_grad():
-                load(self._layers("l"), _trunk_keys("policy_net", len(self.pi_arch)))
-                self.log_std.copy_(torch.as_tensor(np.asarray(weights["log_std"]), dtype=torch.float32))
-                vkeys = _trunk_keys("value_net", len(self.vf_arch))
-                if all(k in weights for pair in vkeys for k in pair):
-                    load(self._layers("v"), vkeys)
-                    self.has_critic = True
+            self._load_weights(weights)
         for p in self.parameters():
             p.requires_grad_(False)
+
+    def _load_weights(self, weights):
+        """The actor's layers and log_std, and the critic's when the weights hold every key of its trunk, into the modules (SB3's
+        state-dict keys); a shape that does not fit the architecture raises ValueError."""
+        todo = []           # every shape is checked before anything is copied: a refused dict leaves the modules as they were
+
+        def load(layers, keys):
+            for lin, (kw, kb) in zip(layers, keys):
+                w, b = (torch.as_tensor(np.asarray(weights[k]), dtype=torch.float32) for k in (kw, kb))
+                if w.shape != lin.weight.shape or b.shape != lin.bias.shape:
+                    raise ValueError(f"{kw}: shape {tuple(w.shape)} does not fit net_arch (expected {tuple(lin.weight.shape)})")
+                todo.extend([(lin.weight, w), (lin.bias, b)])
+        load(self._layers("l"), _trunk_keys("policy_net", len(self.pi_arch)))
+        log_std = torch.as_tensor(np.asarray(weights["log_std"]), dtype=torch.float32)
+        if log_std.shape != self.log_std.shape:
+            raise ValueError(f"log_std: shape {tuple(log_std.shape)} (expected {tuple(self.log_std.shape)})")
+        todo.append((self.log_std, log_std))
+        vkeys = _trunk_keys("value_net", len(self.vf_arch))
+        critic = all(k in weights for pair in vkeys for k in pair)
+        if critic:
+            load(self._layers("v"), vkeys)
+        with torch.no_grad():
+            for dst, src in todo:
+                dst.copy_(src)
+        self.has_critic = self.has_critic or critic
 
     def _layers(self, prefix):
         return [getattr(self, f"{prefix}{i + 1}") for i in range(len(self.pi_arch if prefix == "l" else self.vf_arch) + 1)]
@@ -185,13 +198,16 @@ class MlpPolicy(torch.nn.Module):
             self._hip[idx] = self._create_handle("l", self.pi_arch, idx)
         return self._hip[idx]
 
+    def _host_layers(self, prefix):
+        """(weights, biases, [log_std] or []) of a trunk as contiguous float32 CPU tensors, hidden layers first, the head last."""
+        host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
+        layers = self._layers(prefix)
+        return [host(l.weight) for l in layers], [host(l.bias) for l in layers], [host(self.log_std)] if prefix == "l" else []
+
     def _create_handle(self, prefix, arch, idx):
         """rdv_policy_create / rdv_critic_create for the shipped architecture, their _mlp forms (RdvMlpSpec) for every other."""
         from . import _native as N
-        host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
-        layers = self._layers(prefix)
-        ws, bs = [host(l.weight) for l in layers], [host(l.bias) for l in layers]
-        log_std = [host(self.log_std)] if prefix == "l" else []
+        ws, bs, log_std = self._host_layers(prefix)
         h = C.c_void_p()
         if arch == [64, 64] and self.activation == "tanh":
             flat = [t for pair in zip(ws, bs) for t in pair] + log_std
@@ -231,16 +247,82 @@ class MlpPolicy(torch.nn.Module):
         if self.backend != "torch" and flat.is_cuda and flat.dtype == torch.float32:
             from . import _native as N
             flat = flat.contiguous()
-            idx = flat.device.index if flat.device.index is not None else torch.cuda.current_device()
-            if idx not in self._hip_critic:
-                self._hip_critic[idx] = self._create_handle("v", self.vf_arch, idx)
             if out is None:
                 out = torch.empty((flat.shape[0],), dtype=torch.float32, device=flat.device)
             stream = C.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream)
-            N.check(N.lib().rdv_policy_value(self._hip_critic[idx], C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
+            N.check(N.lib().rdv_policy_value(self._critic_handle(flat.device), C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
                                              flat.shape[0], stream))
             return out.reshape(shape)
         return self._forward("v", flat).reshape(shape)
+
+    def _critic_handle(self, device):
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if idx not in self._hip_critic:
+            self._hip_critic[idx] = self._create_handle("v", self.vf_arch, idx)
+        return self._hip_critic[idx]
+
+    @torch.no_grad()
+    def advantages(self, ro, gamma=0.99, gae_lambda=0.95, out=None):
+        """The columns of SB3's RolloutBuffer that a rollout does not hold, for the rows ``ro`` of ``RendezvousBatch.rollout``:
+        ``values`` [T,N] (the critic on ``ro["obs"]``), ``last_value`` [N] (on ``ro["last_obs"]``), ``advantages`` and ``returns``
+        [T,N] (GAE: ``RolloutBuffer.compute_returns_and_advantage``; the defaults are SB3's).  Returns ``ro`` with the four added.
+        They are allocated once: taken from ``out`` (e.g. the dict an earlier call returned), or from ``ro`` itself when it has them.
+        CUDA rows: rdv_rollout_advantages on the current stream (two critic launches and the GAE kernel; the values are the critic's
+        at call time, bit-identical to ``value()``); ``backend="torch"`` or CPU rows: the modules plus ``advantages.gae``."""
+        from . import advantages as A
+        if not self.has_critic:
+            raise ValueError("advantages: this policy has no critic (its weights hold no value_net trunk)")
+        obs = ro["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
+            raise ValueError(f"obs: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
+        T, n, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+        A.check_tensor(obs, "obs", (T, n, 17), torch.float32, dev)
+        A.check_tensor(ro["reward"], "reward", (T, n), torch.float32, dev)
+        A.check_tensor(ro["done"], "done", (T, n), torch.uint8, dev)
+        A.check_tensor(ro["last_obs"], "last_obs", (n, 17), torch.float32, dev)
+        A.check_discounts(gamma, gae_lambda)
+        cols = dict(values=(T, n), last_value=(n,), advantages=(T, n), returns=(T, n))
+        src = out if out is not None else ro
+        for name, shape in cols.items():
+            t = src.get(name)
+            if t is None or tuple(t.shape) != shape or t.device != dev:
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            A.check_tensor(t, name, shape, torch.float32, dev)
+            ro[name] = t
+        if self.backend != "torch" and obs.is_cuda:
+            from . import _native as N
+            rows = N.RolloutOut(obs.data_ptr(), None, ro["reward"].data_ptr(), ro["done"].data_ptr(), None, ro["last_obs"].data_ptr())
+            ao = N.AdvantageOut(*[ro[f].data_ptr() for f, _ in N.AdvantageOut._fields_])
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            N.check(N.lib().rdv_rollout_advantages(self._critic_handle(dev), C.byref(rows), T, n, float(gamma), float(gae_lambda),
+                                                   C.byref(ao), stream))
+            return ro
+        ro["values"].copy_(self._forward("v", obs.reshape(-1, 17)).reshape(T, n))
+        ro["last_value"].copy_(self._forward("v", ro["last_obs"]).reshape(n))
+        A.gae(ro["reward"], ro["done"], ro["values"], ro["last_value"], gamma, gae_lambda, out=(ro["advantages"], ro["returns"]))
+        return ro
+
+    def update_weights(self, weights=None):
+        """New weights for the policy and for every live HIP handle of it — what a learner calls after ``optimizer.step()``.
+        ``weights``: a dict with the constructor's keys, loaded into the modules first (shapes are checked as in ``__init__``; the
+        critic is loaded when the dict holds its trunk); ``None``: the modules' current parameters are pushed.  Each actor / critic
+        handle is refreshed through rdv_policy_set_weights on the current stream of its device: launches already queued there use the
+        old weights, later ones the new.  A non-finite weight raises RdvError (BAD_PARAMS) and leaves that handle as it was.  The
+        call counter and the noise key are unchanged."""
+        if weights is not None:
+            self._load_weights(weights)
+        if not (self._hip or self._hip_critic):
+            return
+        from . import _native as N
+        for prefix, handles in (("l", self._hip), ("v", self._hip_critic)):
+            if not handles:
+                continue
+            ws, bs, log_std = self._host_layers(prefix)
+            wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+            bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
+            for idx, h in handles.items():
+                stream = C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)
+                N.check(N.lib().rdv_policy_set_weights(h, wp, bp, C.c_void_p(log_std[0].data_ptr()) if log_std else None, stream))
 
     def close(self):
         if self._hip or self._hip_critic:
