@@ -19,6 +19,34 @@
  *   - a handle is not thread-safe; different handles (device shards) may be used from different threads.
  *   - rdv_step performs no allocation.
  *   - quaternions are scalar-first (reference utils/quaternions.py:2).
+ *
+ * Stream capture (HIP graphs; tests/test_gpu_graphs.py)
+ *   Every call that only enqueues work on `stream` may be recorded into a graph (hipStreamBeginCapture ... EndCapture, torch.cuda.graph) and
+ *   replayed; the tests pin rdv_step (every variant, the evaluator build, groups, general bodies), rdv_step_many, rdv_rollout (the
+ *   persistent kernel and the loop forms), rdv_get_state, rdv_snapshot, rdv_policy_act, rdv_policy_value, rdv_gae,
+ *   rdv_rollout_advantages, and the setters rdv_set_params, rdv_set_group_params and rdv_set_rigid_body.  A replay computes bit for bit
+ *   what the same calls compute eagerly.  Make the calls once eagerly before recording them (lazily created handles and module loading
+ *   stay out of the capture), and record on one stream.
+ *   WHAT A GRAPH FREEZES.  The library decides on the host, at call time, what a launch will be; a graph keeps those decisions:
+ *     - the kernel chosen (variant, storage, on_done, diag / eval outputs, general bodies, groups, the first step after rdv_set_state);
+ *     - whether a prepare launch goes in front of rdv_step_many / rdv_rollout (it does when something since the last one — rdv_step, a
+ *       parameter change — left the prepared next-episode states behind);
+ *     - seed, the reset tape, noise_seed and noise_counter0, and every pointer.  A replayed rdv_rollout / rdv_policy_act therefore
+ *       REPEATS the noise counter of the recording: every replay draws the same noise for the same (env, step).  Eager calls that are to
+ *       reproduce a replay pass that same counter; a learner that wants fresh noise per replay records rollouts with different counters.
+ *   Calls that therefore INVALIDATE graphs recorded earlier on the handle (record again after them): rdv_seed, rdv_set_reset_tape,
+ *   rdv_set_kernel_variant, rdv_set_state / rdv_restore, rdv_set_param_groups, and rdv_set_rigid_body when it switches the handle
+ *   between general and non-general bodies.
+ *   Calls that REFUSE inside a capture (RDV_ERR_INVALID_ARGUMENT, the message says "stream capture"; asked before anything touches the
+ *   stream, so the capture stays valid): rdv_get_stats, rdv_get_group_stats, rdv_eval_summary, rdv_eval_group_summary, rdv_restore,
+ *   rdv_set_param_groups (they synchronise or allocate) and rdv_policy_set_weights (its staging buffer is reused).  rdv_create,
+ *   rdv_destroy and the policy create / destroy calls allocate and are not to be made while a capture is open either.
+ *   SUPPORTED between replays, eagerly, on the stream that replays: rdv_step (the persistent kernels of a graph find the prepared states
+ *   of the envs whose episodes it ended out of date by their tags and refill them before their first use) and rdv_set_params (it
+ *   clears those tags on the device, so the next persistent launch, replayed or not, refills every one from the new parameters).
+ *   The first step after rdv_set_state / rdv_restore: recorded there, a graph keeps the kRaw instantiation.  For normalised quaternions
+ *   its results are bit-equal to the regular kernels', so the graph stays correct for its later replays, but it runs the in-lane layout for
+ *   good: take one eager step after rdv_set_state / rdv_restore and record then.
  */
 #ifndef RDV_H_
 #define RDV_H_
@@ -203,7 +231,9 @@ int rdv_destroy(rdv_handle h);
 
 /* Replace parameters (reward coefficients, ranges, limits ...) between steps.  n/dt changes re-derive the CW matrix.
  * The new block is written by a kernel enqueued on `stream`: ordered like a step (launches already on that stream see the old
- * values, later ones the new), legal inside a stream capture, no host synchronisation. */
+ * values, later ones the new), legal inside a stream capture, no host synchronisation.  Behind it, on `stream` too, a clear of the
+ * tags of the prepared next-episode states (n_envs x 4 bytes): the persistent kernels, also those of graphs recorded earlier, then
+ * refill every env's prepared state from the new block before its first use. */
 int rdv_set_params(rdv_handle h, const RdvParams* params_host, void* stream);
 int rdv_get_params(rdv_handle h, RdvParams* out_host);
 /* Re-key the reset RNG (VecEnv.seed()).  Episode counters restart at 0. */

@@ -299,6 +299,16 @@ static inline auto with_storage(int storage, F&& f) {
   if (storage == RDV_STORAGE_F32) return f(float());
   return f(double());
 }
+// The calls that synchronise `s` or allocate (rdv_get_stats, rdv_get_group_stats, rdv_eval_summary, rdv_eval_group_summary, rdv_restore,
+// rdv_set_param_groups) are not legal while `s` records a graph: the runtime would fail the call and invalidate the capture.  They ask
+// here before they touch the stream, and refuse with the capture intact (include/rdv.h, "Stream capture").
+static int refuse_in_capture(const char* who, hipStream_t s) {
+  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
+  RDV_HIP(hipStreamIsCapturing(s, &capturing));
+  if (capturing != hipStreamCaptureStatusNone)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: not legal inside a stream capture (it synchronises the stream or allocates): call it outside the capture", who);
+  return RDV_OK;
+}
 // The handle's device error word, read back on `s` behind whatever the caller has enqueued there: this synchronises the stream and
 // leaves the bits in h->device_error (sticky).  `clear_stats_bytes`: rdv_get_stats zeroes that much of the statistics between the copy
 // and the wait.
@@ -921,6 +931,10 @@ int rdv_set_params(rdv_handle h, const RdvParams* p, void* stream) {
   DeviceGuard guard(h->device);
   h->params = *p; derive_block(h, *p, h->dev);
   h->prepared_ok = false;   // nominal state / ranges may have changed: what a reset returns is no longer what the slots hold
+  // ... and the same on the device, ordered on `stream`: a graph recorded earlier holds a persistent kernel without the prepare launch that
+  // prepared_ok asks for, and a tag says only which episode a slot belongs to, not which parameters drew it.  A tag of 0 never equals
+  // episode + 1, so the kernels' own guard refills every slot from the new block before its first use (capturable: a memset node).
+  RDV_HIP(hipMemsetAsync(h->prep_tag, 0, (size_t)h->n * sizeof(uint32_t), static_cast<hipStream_t>(stream)));
   return upload_params(h, static_cast<hipStream_t>(stream));
 }
 int rdv_get_params(rdv_handle h, RdvParams* out) {
@@ -1165,6 +1179,7 @@ int rdv_restore(rdv_handle h, const void* src, int64_t src_bytes, void* stream) 
   if (src_bytes < (int64_t)sizeof(SnapshotHeader)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_restore: %lld bytes cannot hold a snapshot header", (long long)src_bytes);
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = refuse_in_capture("rdv_restore", s)) return rc;
   SnapshotHeader hd;   // the header is validated on the host: this call synchronises `stream`
   RDV_HIP(hipMemcpyAsync(&hd, src, sizeof hd, hipMemcpyDeviceToHost, s));
   if (int rc = read_fault_word(h, s)) return rc;   // (it synchronises anyway)
@@ -1213,9 +1228,10 @@ int rdv_eval_begin(rdv_handle h, double* eval, void* stream) {
   return access(h, ACC_EVAL_BEGIN, nullptr, eval, nullptr, stream);
 }
 // the evaluation summary of envs [first, last) (whole waves, or up to the batch's end): rdv_eval_summary, rdv_eval_group_summary
-static int eval_summary_of(rdv_handle h, const double* eval, RdvEvalSummary* out, int64_t first, int64_t last, void* stream) {
+static int eval_summary_of(const char* who, rdv_handle h, const double* eval, RdvEvalSummary* out, int64_t first, int64_t last, void* stream) {
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = refuse_in_capture(who, s)) return rc;
   if (h->n_groups) launch_eval_summary_groups(h->storage == RDV_STORAGE_F32, grid_for(h->n), s, h->group_table, h->ws, h->n, h->cs, eval, h->eval_partial);
   else with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(eval_summary_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev, h->ws, h->n, h->cs, eval, h->eval_partial); });
   RDV_HIP(hipGetLastError());
@@ -1241,13 +1257,13 @@ static int eval_summary_of(rdv_handle h, const double* eval, RdvEvalSummary* out
 int rdv_eval_summary(rdv_handle h, const double* eval, RdvEvalSummary* out, void* stream) {
   RDV_CHECK_HANDLE(h);
   if (!eval || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_summary: null accumulators / output");
-  return eval_summary_of(h, eval, out, 0, h->n, stream);
+  return eval_summary_of("rdv_eval_summary", h, eval, out, 0, h->n, stream);
 }
 int rdv_eval_group_summary(rdv_handle h, int32_t group, const double* eval, RdvEvalSummary* out, void* stream) {
   RDV_CHECK_HANDLE(h);
   if (!eval || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_group_summary: null accumulators / output");
   if (group < 0 || group >= h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_eval_group_summary: group %d of %d", group, h->n_groups);
-  return eval_summary_of(h, eval, out, h->group_start[(size_t)group], h->group_start[(size_t)group + 1], stream);
+  return eval_summary_of("rdv_eval_group_summary", h, eval, out, h->group_start[(size_t)group], h->group_start[(size_t)group + 1], stream);
 }
 
 // the statistics slots -> the host (synchronises `stream`, reads the device error word; reset: zeroes them behind the copy)
@@ -1271,6 +1287,7 @@ int rdv_get_stats(rdv_handle h, RdvStats* out, int reset, void* stream) {
   RDV_CHECK_HANDLE(h);
   if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_stats: null output");
   DeviceGuard guard(h->device);
+  if (int rc = refuse_in_capture("rdv_get_stats", static_cast<hipStream_t>(stream))) return rc;
   if (int rc = fetch_slots(h, reset, static_cast<hipStream_t>(stream))) return rc;
   sum_slots(h, 0, h->host_slots.size() / kStatWords, out);
   return rdv_device_error_code(h->device_error);   // RDV_OK unless a kernel of this handle reported a fault (the statistics are filled either way)
@@ -1280,6 +1297,7 @@ int rdv_get_group_stats(rdv_handle h, RdvStats* out, int reset, void* stream) {
   if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_group_stats: null output");
   if (!h->n_groups) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_get_group_stats: this handle has no parameter groups (rdv_get_stats)");
   DeviceGuard guard(h->device);
+  if (int rc = refuse_in_capture("rdv_get_group_stats", static_cast<hipStream_t>(stream))) return rc;
   if (int rc = fetch_slots(h, reset, static_cast<hipStream_t>(stream))) return rc;
   // a group begins on a 256-env boundary, so its waves are a range of slots: the range a stand-alone handle of that group would sum
   for (int32_t g = 0; g < h->n_groups; ++g)
@@ -1317,6 +1335,10 @@ int rdv_param_groups_validate(const RdvParams* params, int32_t n_groups) {
 }
 int rdv_set_param_groups(rdv_handle h, const RdvParams* params, const int64_t* sizes, int32_t n_groups, void* stream) {
   RDV_CHECK_HANDLE(h);
+  {
+    DeviceGuard guard(h->device);
+    if (int rc = refuse_in_capture("rdv_set_param_groups", static_cast<hipStream_t>(stream))) return rc;
+  }
   if (n_groups == 0) {   // back to the handle's single block (the side allocation stays until rdv_destroy or the next grouping)
     if (h->n_groups) h->prepared_ok = false;
     h->n_groups = 0;

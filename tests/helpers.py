@@ -57,6 +57,29 @@ def shipped_policy(device=None, noise_seed=None):
     return p
 
 
+def capture(fn, before_record=None):
+    """``fn`` recorded into a HIP graph (tests/test_gpu_graphs.py); returns the ``torch.cuda.CUDAGraph``, ready for ``replay()``.
+    ``fn`` first runs ONCE EAGERLY on the side stream the capture will use — the lazy creation of policy handles, module loading and the
+    LDS-limit calls happen there, outside the capture — so a handle that ``fn`` drives has made its calls once before the first replay.
+    ``before_record`` (optional) then runs eagerly on the same stream: the calls that put a handle into the host state the recording is
+    to freeze (an eager rdv_step in front of a recorded rdv_step_many, an rdv_set_state in front of a recorded rdv_step).  The stream is
+    synchronised, then ``fn`` is recorded on it: one stream, a linear sequence, no parallel branches, no setting that changes how the
+    runtime replays."""
+    import torch
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        fn()
+        if before_record is not None:
+            before_record()
+    side.synchronize()
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=side):
+        fn()
+    return graph
+
+
 def counter_actions(seed, step, n, lo=0):
     """U(-1,1) float32 actions keyed by (seed, step, env id): reproducible on any host, any shard."""
     ids = np.arange(lo, lo + n, dtype=np.uint64)

@@ -1,0 +1,570 @@
+"""
+GPU tests (run with `-m gpu`) of HIP-graph replay: include/rdv.h, "Stream capture".  Almost every call of the ABI may be recorded into a
+graph, and the library decides on the HOST, at call time, what a launch will be (which kernel, whether a prepare launch goes in front,
+seed, tape, noise counter, every pointer): a graph freezes those decisions.  The specification is one sentence — a replayed graph
+computes what the same calls compute eagerly — so every comparison is `torch.equal`, on the bits of floating-point tensors (`==` on the
+statistics): the replayed kernels ARE the eager kernels, there is no tolerance.
+
+Every case drives two handles of the same seed and parameters.  `graphed` makes its calls once eagerly (the warm-up of
+helpers.capture), records them once and replays the graph REPLAYS times; `eager` makes the same calls 1 + REPLAYS times.  After each
+replay every output buffer is compared, at the end get_state, get_aux, get_stats (which also reads the device error word: a device
+fault raises) and rdv_debug_last_kernel.  With t_max = 6 s and dt = 1 s no episode is longer than 6 steps, so over the 4 x 5 steps of a
+case every env resets at least three times.
+
+  A  replay equals eager, per launch path            B  decisions a graph freezes (eager calls between replays, the raw first step)
+  C  calls that refuse inside a capture              D  two streams / two threads, one handle pair each
+"""
+import ctypes as C
+import threading
+
+import numpy as np
+import pytest
+
+from helpers import capture, counter_actions, expected_kernel, gpu_batch, persistent_kernel, shipped_policy
+from reinforcement_learning_rendezvous_amd import _native as N
+from reinforcement_learning_rendezvous_amd import advantages
+from reinforcement_learning_rendezvous_amd.params import make_params
+from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
+from rigid_cases import RigidCase
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+N_ENVS, K_STEPS, REPLAYS, T_MAX = 1000, 5, 3, 6.0
+STEP_OUTPUTS = ("obs", "reward", "done", "terminal_obs", "episode_return", "episode_length", "done_reason")
+GROUP_SIZES = [256, 512, 232]
+
+
+def _params(**kw):
+    return make_params(t_max=T_MAX, **kw)
+
+
+def _group_sets():
+    """three parameter sets that differ in what a step and a reset read; no episode of any longer than 6 steps"""
+    return [_params(), make_params(t_max=5.0, rc0_range=2.0, reward_kwargs=dict(bonus_coef=3.0, att_coef=0.25, fuel_coef=0.7, collision_coef=2.0)),
+            make_params(t_max=4.0, qt0_range=float(np.radians(60.0)), koz_radius=4.0)]
+
+
+def _tape(seed, steps, n):
+    return torch.from_numpy(np.stack([counter_actions(seed, t, n) for t in range(steps)])).to(DEV)
+
+
+def _flat(x, prefix=""):
+    """(name, tensor) of every tensor in a nested dict / list / tuple"""
+    if isinstance(x, torch.Tensor):
+        return [(prefix, x)]
+    items = x.items() if isinstance(x, dict) else enumerate(x)
+    return [p for k, v in items for p in _flat(v, f"{prefix}/{k}")]
+
+
+def _equal(a, b):
+    """torch.equal on the BITS of floating-point tensors: the evaluation accumulators hold NaN for "none so far" (include/rdv.h), which
+    compares unequal to itself; bit for bit is also the stricter statement (-0.0 is not 0.0)"""
+    if a.shape != b.shape or a.dtype != b.dtype:
+        return False
+    if a.is_floating_point():
+        as_int = {torch.float32: torch.int32, torch.float64: torch.int64}[a.dtype]
+        a, b = a.contiguous().view(as_int), b.contiguous().view(as_int)
+    return torch.equal(a, b)
+
+
+def _assert_same(got, want, what):
+    got, want = _flat(got), _flat(want)
+    assert [k for k, _ in got] == [k for k, _ in want] and got, what
+    for (name, a), (_, b) in zip(got, want):
+        assert _equal(a, b), f"{what}: {name} differs from the eager calls"
+
+
+def _assert_final(a, b, kernel=None):
+    """state, bookkeeping, statistics (get_stats raises RdvError on a device fault) and the kernel the host recorded"""
+    assert _equal(a.get_state(), b.get_state()), "final state"
+    assert _equal(a.get_aux(), b.get_aux()), "final bookkeeping"
+    sa, sb = a.get_stats(), b.get_stats()
+    assert sa == sb and sa["env_steps"] > 0, (sa, sb)
+    assert a.last_kernel == b.last_kernel if kernel is None else (a.last_kernel, b.last_kernel) == kernel, (a.last_kernel, b.last_kernel, kernel)
+    return sa
+
+
+class Twin:
+    """one of the two handles of a case with whatever its calls need (policy, buffers), and the count of calls made so far"""
+
+    def __init__(self, env, **kw):
+        self.env, self.calls, self.out = env, 0, None
+        self.__dict__.update(kw)
+
+    def noise_counter(self, steps):
+        """A replay repeats the noise counter of the recording (include/rdv.h): the warm-up draws with counter 0, the recording — and
+        so every replay — with `steps`; the eager twin therefore calls with `steps` every time after its first."""
+        self.pol._calls = min(self.calls, 1) * steps
+        self.calls += 1
+
+
+def _replay_equals_eager(make, fn, before_record=None, between=None, replays=REPLAYS, kernel=None):
+    """The frame of every case in A and B.  `make()` -> a Twin; `fn(twin)` makes the calls and returns its output tensors (nested);
+    `before_record(twin)`: eager calls between warm-up and recording; `between(twin, r)`: eager calls in front of replay r >= 1."""
+    graphed, eager = make(), make()
+    rec = {}
+    g = capture(lambda: rec.update(out=fn(graphed)), (lambda: before_record(graphed)) if before_record else None)
+    fn(eager)
+    if before_record:
+        before_record(eager)
+    for r in range(replays):
+        if between and r:
+            between(graphed, r)
+            between(eager, r)
+        g.replay()
+        want = fn(eager)
+        torch.cuda.synchronize()
+        _assert_same(rec["out"], want, f"replay {r}")
+    stats = _assert_final(graphed.env, eager.env, kernel)
+    for t in (graphed, eager):
+        t.env.close()
+        if getattr(t, "pol", None) is not None:
+            t.pol.close()
+    return stats
+
+
+def _step_rows(t):
+    """rdv_step x K over the rows of the twin's fixed action tape; every output buffer of every step"""
+    rows = []
+    for k in range(t.tape.shape[0]):
+        t.env.step(t.tape[k], **getattr(t, "step_kw", {}))
+        row = {name: getattr(t.env, name).clone() for name in STEP_OUTPUTS}
+        if getattr(t, "step_kw", None):
+            row.update(diag=t.env.diag.clone(), eval=t.env.eval.clone())
+        rows.append(row)
+    return rows
+
+
+# ---------------------------------------------------------------------------------------------------------------- A: rdv_step
+@pytest.mark.parametrize("variant,storage,on_done",
+                         [(v, "f32", o) for v in ("fused", "split", "fused_inlane", "fused_tiles") for o in ("reset", "halt", "continue")] + [("split", "f64", "reset")])
+def test_step_replay_equals_eager(variant, storage, on_done):
+    def make():
+        env = gpu_batch(N_ENVS, params=_params(), storage=storage, on_done=on_done, variant=variant, seed=21)
+        env.reset()
+        return Twin(env, tape=_tape(3, K_STEPS, N_ENVS))
+    stats = _replay_equals_eager(make, _step_rows, kernel=(expected_kernel(variant, N_ENVS, storage, on_done),) * 2)
+    assert stats["episodes"] >= (N_ENVS if on_done == "halt" else 3 * N_ENVS)
+
+
+def test_evaluator_build_replay_equals_eager():
+    """diag + eval outputs (step_kernel<ST, true>), halt mode; rdv_eval_begin outside the graph"""
+    def make():
+        env = gpu_batch(N_ENVS, params=_params(), on_done="halt", seed=22)
+        env.reset()
+        env.eval_begin()
+        return Twin(env, tape=_tape(4, K_STEPS, N_ENVS), step_kw=dict(diag=True, accumulate=True))
+    _replay_equals_eager(make, _step_rows, kernel=(expected_kernel("auto", N_ENVS, "f32", "halt", diag=True),) * 2)
+
+
+def _grouped(seed, **kw):
+    env = gpu_batch(sum(GROUP_SIZES), params=_group_sets(), group_sizes=GROUP_SIZES, seed=seed, **kw)
+    env.reset()
+    return env
+
+
+def test_grouped_step_replay_equals_eager():
+    stats = _replay_equals_eager(lambda: Twin(_grouped(23), tape=_tape(5, K_STEPS, N_ENVS)), _step_rows, kernel=("step_kernel_groups<float, true>",) * 2)
+    assert stats["episodes"] >= 3 * N_ENVS
+
+
+def _general(n=300, seed=24):
+    """a tri-axial torqued target (tests/rigid_cases.py) beside the reference's chaser: step_kernel_general"""
+    case = RigidCase("target", n, "f32", "reset", seed=seed)
+    p = case.params.copy()
+    p.update(t_max=T_MAX * p.dt)
+    env = gpu_batch(n, params=p, seed=seed)
+    env.set_rigid_body(**case.body)
+    env.reset()
+    return env, case
+
+
+def test_general_body_step_replay_equals_eager():
+    def make():
+        env, case = _general()
+        return Twin(env, tape=torch.from_numpy(np.stack(case.actions[:K_STEPS])).to(DEV))
+    stats = _replay_equals_eager(make, _step_rows, kernel=("step_kernel_general<float>",) * 2)
+    assert stats["episodes"] >= 3 * 300
+
+
+# ---------------------------------------------------------------------------------------------------------------- A: persistent kernels
+def _step_many(t):
+    t.out = t.env.step_many(t.tape, out=t.out)
+    return t.out
+
+
+def _many_twin(n, seed=25, steps=12):
+    env = gpu_batch(n, params=_params(), seed=seed)
+    env.reset()
+    return Twin(env, tape=_tape(6, steps, n), one=_tape(7, 3, n))
+
+
+@pytest.mark.parametrize("n", [N_ENVS, 777])
+@pytest.mark.parametrize("prepare_in_graph", [False, True], ids=["prepared", "after-step"])
+def test_step_many_replay_equals_eager(n, prepare_in_graph):
+    """Recorded behind an eager rdv_step_many (slots current: no prepare launch in the graph) and directly behind an eager rdv_step (the
+    prepare_kernel is a node of the graph and runs on every replay, where the eager calls run it once)."""
+    eager_step = (lambda t: t.env.step(t.one[0])) if prepare_in_graph else None
+    _replay_equals_eager(lambda: _many_twin(n), _step_many, before_record=eager_step, kernel=(persistent_kernel("step_many", "f32"),) * 2)
+
+
+def _rollout(t, steps=12, deterministic=False):
+    t.noise_counter(steps)
+    t.out = t.env.rollout(t.pol, steps, deterministic=deterministic, out=t.out)
+    return t.out
+
+
+def _relu_policy():
+    return MlpPolicy(net_arch=[32, 32], activation_fn="relu", seed=5)
+
+
+@pytest.mark.parametrize("which,deterministic", [
+    pytest.param("persistent", True, id="persistent-deterministic"), pytest.param("persistent", False, id="persistent-stochastic"),
+    pytest.param("relu", False, id="loop-relu-32x32"), pytest.param("grouped", True, id="loop-grouped"),
+    pytest.param("relu33", False, id="loop-relu-n33-row-copies")])
+def test_rollout_replay_equals_eager(which, deterministic):
+    """The persistent kernel (shipped policy) and the act + step loop forms: a [32, 32] ReLU policy, a grouped handle, and n = 33, where
+    the observation rows of [T, 33, 17] are not 16-byte aligned and each is a copy node behind the step (obs_tmp)."""
+    n = 33 if which == "relu33" else N_ENVS
+
+    def make():
+        env = _grouped(26) if which == "grouped" else gpu_batch(n, params=_params(), seed=26)
+        env.reset()
+        pol = _relu_policy() if which.startswith("relu") else shipped_policy(noise_seed=9)
+        if which.startswith("relu"):
+            pol.noise_seed = 9
+        return Twin(env, pol=pol)
+    kernel = {"persistent": persistent_kernel("rollout", "f32"), "grouped": "step_kernel_groups<float, true>"}.get(which, expected_kernel("auto", n, "f32", "reset"))
+    stats = _replay_equals_eager(make, lambda t: _rollout(t, deterministic=deterministic), kernel=(kernel,) * 2)
+    assert stats["episodes"] >= 3 * n
+
+
+# ---------------------------------------------------------------------------------------------------------------- A: the learner path
+def test_learner_calls_replay_equal_eager():
+    """policy.act, policy.value, advantages.gae and policy.advantages on the rows of a rollout: the four launches a learner adds"""
+    src = gpu_batch(N_ENVS, params=_params(), seed=27)
+    src.reset()
+    rows = {k: v.clone() for k, v in src.rollout(shipped_policy(noise_seed=2), 12).items()}
+    torch.cuda.synchronize()
+    src.close()
+
+    def make():
+        return Twin(None, pol=shipped_policy(noise_seed=4), bufs=None)
+
+    def fn(t):
+        t.noise_counter(1)
+        if t.bufs is None:
+            t.bufs = dict(act=torch.empty((N_ENVS, 6), device=DEV), val=torch.empty((12 * N_ENVS,), device=DEV), last=torch.empty((N_ENVS,), device=DEV),
+                          adv=torch.empty((12, N_ENVS), device=DEV), ret=torch.empty((12, N_ENVS), device=DEV), ro=dict(rows))
+        b = t.bufs
+        t.pol.act(rows["last_obs"], deterministic=False, out=b["act"])
+        t.pol.value(rows["obs"], out=b["val"])
+        t.pol.value(rows["last_obs"], out=b["last"])
+        advantages.gae(rows["reward"], rows["done"], b["val"].reshape(12, N_ENVS), b["last"], 0.97, 0.9, out=(b["adv"], b["ret"]))
+        b["ro"] = t.pol.advantages(b["ro"], gamma=0.97, gae_lambda=0.9)
+        return {k: v for k, v in b.items() if k != "ro"}, {k: b["ro"][k] for k in ("values", "last_value", "advantages", "returns")}
+
+    graphed, eager = make(), make()
+    rec = {}
+    g = capture(lambda: rec.update(out=fn(graphed)))
+    fn(eager)
+    for r in range(REPLAYS):
+        for _, x in _flat(rec["out"]):
+            x.fill_(float("nan"))                      # the replay, not the warm-up, wrote what is compared
+        g.replay()
+        want = fn(eager)
+        torch.cuda.synchronize()
+        _assert_same(rec["out"], want, f"replay {r}")
+    one, two = rec["out"]
+    assert _equal(one["adv"], two["advantages"]) and _equal(one["ret"], two["returns"]) and _equal(one["val"].reshape(12, N_ENVS), two["values"])
+    assert not torch.isnan(one["act"]).any()
+    graphed.pol.close(); eager.pol.close()
+
+
+def test_collect_as_one_graph_equals_eager():
+    """batch.collect (rollout, two critic launches, the GAE kernel) as one graph, n = 777, T = 16, `out` reused: values, advantages and
+    returns are those of the eager collect"""
+    def make():
+        env = gpu_batch(777, params=_params(), seed=28)
+        env.reset()
+        return Twin(env, pol=shipped_policy(noise_seed=6))
+
+    def fn(t):
+        t.noise_counter(16)
+        t.out = t.env.collect(t.pol, 16, gamma=0.97, gae_lambda=0.9, out=t.out)
+        return t.out
+    stats = _replay_equals_eager(make, fn, kernel=(persistent_kernel("rollout", "f32"),) * 2)
+    assert stats["episodes"] >= 3 * 777
+
+
+# ---------------------------------------------------------------------------------------------------------------- A: setters inside
+def test_set_group_params_inside_the_capture():
+    """[step, rdv_set_group_params(g = 1, p'), step]: the second step of every replay — and, the block being the handle's, the first of the next — uses p'"""
+    other = make_params(t_max=3.0, rc0_range=0.5, reward_kwargs=dict(bonus_coef=1.0, att_coef=2.0, fuel_coef=0.1, collision_coef=0.2))
+
+    def fn(t):
+        rows = _step_rows(Twin(t.env, tape=t.tape[:1]))
+        t.env.set_group_params(1, other)
+        return rows + _step_rows(Twin(t.env, tape=t.tape[1:2]))
+    _replay_equals_eager(lambda: Twin(_grouped(29), tape=_tape(8, 2, N_ENVS)), fn)
+
+
+def test_set_rigid_body_inside_the_capture():
+    """[step, rdv_set_rigid_body(another target torque), step] on a general handle (it stays general: no other kernel is chosen)"""
+    def make():
+        env, case = _general(seed=30)
+        return Twin(env, tape=torch.from_numpy(np.stack(case.actions[:2])).to(DEV), torque=case.body["torque_target"] * -1.5)
+
+    def fn(t):
+        rows = _step_rows(Twin(t.env, tape=t.tape[:1]))
+        t.env.set_rigid_body(torque_target=t.torque)
+        return rows + _step_rows(Twin(t.env, tape=t.tape[1:2]))
+    _replay_equals_eager(make, fn, kernel=("step_kernel_general<float>",) * 2)
+
+
+def test_snapshot_and_get_state_inside_the_capture():
+    def make():
+        env = gpu_batch(N_ENVS, params=_params(), seed=31)
+        env.reset()
+        return Twin(env, tape=_tape(9, 1, N_ENVS))
+
+    def fn(t):
+        rows = _step_rows(t)
+        return rows, t.env.snapshot(), t.env.get_state()
+    _replay_equals_eager(make, fn)
+
+
+# ---------------------------------------------------------------------------------------------------------------- B: frozen decisions
+def _persistent_case(which, n=N_ENVS, seed=32, steps=8):
+    def make():
+        env = gpu_batch(n, params=_params(), seed=seed)
+        env.reset()
+        return Twin(env, pol=shipped_policy(noise_seed=1), tape=_tape(10, steps, n), one=_tape(11, 3, n), ended=0)
+    fn = (lambda t: _rollout(t, steps=steps, deterministic=True)) if which == "rollout" else _step_many
+    return make, fn, (persistent_kernel(which, "f32"),) * 2
+
+
+@pytest.mark.parametrize("which", ["rollout", "step_many"])
+def test_eager_steps_between_replays(which):
+    """B1.  A graph of a persistent kernel recorded with current slots holds no prepare launch.  Three eager rdv_steps between two replays
+    end episodes: those envs' slots then lag behind (tag != episode + 1), and the replayed kernel's own guard refills them before their
+    first use — device code that no eager call sequence reaches (ensure_prepared runs the prepare_kernel there instead).  The eager twin
+    makes the same calls in the same order.  No device fault: get_stats (in _assert_final) would raise."""
+    make, fn, kernel = _persistent_case(which)
+
+    def eager_steps(t, r):
+        if r == 1:
+            for k in range(3):
+                t.env.step(t.one[k])
+                t.ended += int(t.env.done.sum())
+            assert 0 < t.ended, "no episode ended during the eager steps: the guard would not run"
+    # rdv_debug_last_kernel is a host record: the graphed handle's last HOST call is an eager step (replays make none), the eager twin's a persistent launch
+    _replay_equals_eager(make, fn, between=eager_steps, replays=4, kernel=(expected_kernel("auto", N_ENVS, "f32", "reset"), kernel[1]))
+
+
+@pytest.mark.parametrize("which", ["rollout", "step_many"])
+def test_eager_set_params_between_replays(which):
+    """B2.  An eager rdv_set_params between two replays changes the reset distribution (rc0_range, qt0_range) and t_max.  The slots then
+    hold states drawn from the old parameters under tags that still match (a tag encodes the episode index only), and the graph has no
+    prepare launch: rdv_set_params therefore clears the tags on the device, on the caller's stream, and the kernel's guard refills every
+    slot from the new block.  Without that clear every env's next reset returns a state of the old distribution.  Observed on an MI355X
+    with the clear taken out, this case, first replay after the change: rollout — all 1000 envs, 4000 of 8000 (step, env) rows of obs,
+    actions and reward differ (steps 1-4, one whole episode under the new t_max); step_many — all 1000 envs, 4000 rows of obs (steps
+    0-3); done is unaffected, the replays after it are equal again, the final statistics differ."""
+    make, fn, kernel = _persistent_case(which, seed=33)
+    p1 = make_params(t_max=4.0, rc0_range=3.0, qt0_range=float(np.radians(10.0)))
+    _replay_equals_eager(make, fn, between=lambda t, r: t.env.set_params(p1) if r == 1 else None, replays=4, kernel=kernel)
+
+
+def test_raw_first_step_recorded():
+    """B3.  [step] recorded directly behind an eager rdv_set_state freezes the kRaw instantiation (it tests each quaternion's norm and
+    rescales the rate where it is off by more than 1e-6).  For NORMALISED states that test never fires and the arithmetic is the regular
+    kernels': the replays, all kRaw, are bit-equal to the eager calls, which run kRaw once and the regular kernel afterwards.  (A graph
+    recorded that way keeps running the slower in-lane layout; include/rdv.h says so.)"""
+    src = gpu_batch(N_ENVS, params=_params(), seed=99)
+    src.reset()
+    for k in range(2):
+        src.step(_tape(12, 2, N_ENVS)[k])
+    states = src.get_state().clone()
+    torch.cuda.synchronize()
+    src.close()
+    for q in (states[:, 6:10], states[:, 13:17]):            # qc, qt: |q|^2 within 1e-6 of 1 (fp32 storage: ~1e-7), the kernel's own test
+        assert float(((q * q).sum(1) - 1).abs().max()) < 5e-7
+
+    def make():
+        env = gpu_batch(N_ENVS, params=_params(), seed=34)
+        env.reset()
+        return Twin(env, tape=_tape(13, 1, N_ENVS))
+    raw, regular = expected_kernel("auto", N_ENVS, "f32", "reset", after_set_state=True), expected_kernel("auto", N_ENVS, "f32", "reset")
+    assert raw != regular
+    _replay_equals_eager(make, _step_rows, before_record=lambda t: t.env.set_state(states), kernel=(raw, regular))
+
+
+# ---------------------------------------------------------------------------------------------------------------- C: refusals
+REFUSED = ("rdv_get_stats", "rdv_get_group_stats", "rdv_eval_summary", "rdv_eval_group_summary", "rdv_restore", "rdv_set_param_groups",
+           "rdv_policy_set_weights")
+
+
+@pytest.mark.parametrize("call", REFUSED)
+def test_synchronising_calls_refuse_inside_a_capture(call):
+    """[step, <call>, step] recorded: the call returns RDV_ERR_INVALID_ARGUMENT with a message that says "stream capture" BEFORE it touches
+    the stream, so the capture ends normally and its replay is the two steps.  (The call is made through ctypes during the recording
+    only: in the eager warm-up it would simply run.)"""
+    lib = N.lib()
+    grouped = "group" in call and call != "rdv_set_param_groups"
+
+    def make():
+        env = _grouped(35) if grouped else gpu_batch(N_ENVS, params=_params(), seed=35)
+        env.reset()
+        return Twin(env, tape=_tape(14, 2, N_ENVS), refusal=None)
+    graphed, eager = make(), make()
+    h, n = graphed.env._h, graphed.env.num_envs
+    ev = torch.zeros((n, N.EVAL_DIM), dtype=torch.float64, device=DEV)
+    snap = graphed.env.snapshot()
+    pol = shipped_policy()
+    ph = pol._hip_handle(torch.device(DEV))
+    ws, bs, log_std = pol._host_layers("l")
+    wp, bp = (C.c_void_p * 3)(*[t.data_ptr() for t in ws]), (C.c_void_p * 3)(*[t.data_ptr() for t in bs])
+    sets, sizes = (type(graphed.env.params) * 3)(*_group_sets()), (C.c_int64 * 3)(*GROUP_SIZES)
+    stats, group_stats, summary = N.Stats(), (N.Stats * 3)(), N.EvalSummary()
+    calls = {
+        "rdv_get_stats": lambda s: lib.rdv_get_stats(h, C.byref(stats), 0, s),
+        "rdv_get_group_stats": lambda s: lib.rdv_get_group_stats(h, group_stats, 0, s),
+        "rdv_eval_summary": lambda s: lib.rdv_eval_summary(h, ev.data_ptr(), C.byref(summary), s),
+        "rdv_eval_group_summary": lambda s: lib.rdv_eval_group_summary(h, 1, ev.data_ptr(), C.byref(summary), s),
+        "rdv_restore": lambda s: lib.rdv_restore(h, snap.data_ptr(), snap.numel(), s),
+        "rdv_set_param_groups": lambda s: lib.rdv_set_param_groups(h, sets, sizes, 3, s),
+        "rdv_policy_set_weights": lambda s: lib.rdv_policy_set_weights(ph, wp, bp, C.c_void_p(log_std[0].data_ptr()), s),
+    }
+
+    def fn(t):
+        rows = _step_rows(Twin(t.env, tape=t.tape[:1]))
+        if t is graphed and torch.cuda.is_current_stream_capturing():
+            rc = calls[call](t.env._stream())
+            t.refusal = (rc, lib.rdv_last_error().decode())
+        return rows + _step_rows(Twin(t.env, tape=t.tape[1:2]))
+    rec = {}
+    g = capture(lambda: rec.update(out=fn(graphed)))          # ends normally: torch raises if the capture was invalidated
+    rc, message = graphed.refusal
+    assert rc == -1 and "stream capture" in message and message.startswith(call + ":"), (rc, message)
+    fn(eager)
+    for r in range(2):
+        g.replay()
+        want = fn(eager)
+        torch.cuda.synchronize()
+        _assert_same(rec["out"], want, f"replay {r}")
+    assert graphed.env.num_groups == (3 if grouped else 0)
+    _assert_final(graphed.env, eager.env)
+    pol.close(); graphed.env.close(); eager.env.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- D: streams, threads
+PAIR_ENVS, PAIR_ROUNDS, PAIR_T = 4096, 4, 8
+PAIR_COLUMNS = ("obs", "actions", "reward", "done", "log_prob", "last_obs", "values", "last_value", "advantages", "returns")
+
+
+class Pair:
+    """an env batch and a policy of its own; `turns()` yields after every call of `PAIR_ROUNDS` x collect(T = 8) (collect is rollout +
+    policy.advantages: made here as the two calls it consists of, so that two pairs can be interleaved call by call)"""
+
+    def __init__(self, seed):
+        self.env = gpu_batch(PAIR_ENVS, params=_params(), seed=seed)
+        self.pol = shipped_policy(noise_seed=seed + 100)
+        self.env.reset()
+        dev = torch.device(DEV)
+        self.pol._hip_handle(dev), self.pol._critic_handle(dev)
+        self.rounds, self.out = [], None
+
+    def turns(self):
+        for _ in range(PAIR_ROUNDS):
+            self.out = self.env.rollout(self.pol, PAIR_T, out=self.out)
+            yield
+            self.pol.advantages(self.out, gamma=0.97, gae_lambda=0.9)
+            self.rounds.append({k: self.out[k].clone() for k in PAIR_COLUMNS})
+            yield
+
+    def result(self):
+        return self.rounds, self.env.get_state(), self.env.get_aux(), self.env.get_stats()
+
+    def close(self):
+        self.env.close(); self.pol.close()
+
+
+@pytest.fixture(scope="module")
+def solo_pairs():
+    """each pair run alone on the default stream: the reference of both D tests (computed once, left unchanged)"""
+    want = []
+    for seed in (41, 42):
+        p = Pair(seed)
+        for _ in p.turns():
+            pass
+        torch.cuda.synchronize()
+        want.append(p.result())
+        p.close()
+    assert not torch.equal(want[0][1], want[1][1])
+    return want
+
+
+def _assert_pair(got, want, what):
+    _assert_same(got[0], want[0], what)
+    assert _equal(got[1], want[1]) and _equal(got[2], want[2]) and got[3] == want[3], what
+
+
+def test_two_pairs_on_two_streams_interleaved(solo_pairs):
+    """one thread, two side streams, the two pairs' calls alternating one by one with no synchronisation in between"""
+    pairs, streams = [Pair(41), Pair(42)], [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    turns = [p.turns() for p in pairs]
+    for _ in range(2 * PAIR_ROUNDS):
+        for s, it in zip(streams, turns):
+            with torch.cuda.stream(s):
+                next(it)
+    got = []
+    for s, p in zip(streams, pairs):
+        with torch.cuda.stream(s):
+            got.append(p.result())
+    torch.cuda.synchronize()
+    for k in range(2):
+        _assert_pair(got[k], solo_pairs[k], f"pair {k}")
+        pairs[k].close()
+
+
+def test_two_pairs_from_two_threads(solo_pairs):
+    """Different handles may be used from different threads (include/rdv.h): ctypes releases the GIL around every call, so the two
+    pairs' launches run concurrently.  Thread 0 also provokes a refusal (n_steps = 0) and reads it back; rdv_last_error is per thread,
+    thread 1's stays empty."""
+    lib = N.lib()
+    pairs, streams = [Pair(41), Pair(42)], [torch.cuda.Stream(), torch.cuda.Stream()]
+    torch.cuda.synchronize()
+    got, errors, failures = [None, None], [None, None], []
+    start = threading.Barrier(2)
+
+    def work(k):
+        try:
+            start.wait(timeout=60)
+            with torch.cuda.stream(streams[k]):
+                for turn, _ in enumerate(pairs[k].turns()):
+                    if k == 0 and turn == 3:
+                        assert lib.rdv_step_many(pairs[0].env._h, None, 0, None, None) == -1
+                        errors[0] = lib.rdv_last_error()
+                got[k] = pairs[k].result()
+            streams[k].synchronize()
+            if k == 1:
+                errors[1] = lib.rdv_last_error()
+        except BaseException as exc:        # reported by the main thread
+            failures.append((k, exc))
+            start.abort()
+    threads = [threading.Thread(target=work, args=(k,)) for k in range(2)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=120)
+    assert not failures, failures
+    assert not any(t.is_alive() for t in threads)
+    torch.cuda.synchronize()
+    assert errors[0] is not None and b"n_steps must be positive" in errors[0] and errors[1] == b"", errors
+    for k in range(2):
+        _assert_pair(got[k], solo_pairs[k], f"pair {k}")
+        pairs[k].close()
