@@ -101,12 +101,20 @@ __device__ __forceinline__ float mul_f32_rn(float a, float b) {
   return a * b;
 }
 
-// 1/sqrt(x): v_rsq_f64 seed + two Newton steps (<= 2 ulp); replaces the sqrt-then-divide of every normalisation
+// 1/sqrt(x): v_rsq_f64 seed + two Newton steps (<= 2 ulp for every normal x, measured: 1.56); replaces the sqrt-then-divide of every normalisation.
+// The last step's three roundings are all of the error that is left: (x/2) y to half an ulp, the fma's result next to 1 and the product
+// — at most 0.5 + 1 + 0.5 ulp of a result just below a power of two, 1.25 ulp just above one.
+// 0 -> +inf, +inf -> 0, x < 0 and NaN -> NaN: the seed's own answers.  There a Newton factor is 0 * inf = NaN, which fmax replaces by 0.5
+// (inf and 0 keep their value under it); for every other x the factor is within 1e-7 of 1 and fmax returns it unchanged.
+// Subnormal x = k 2^-1074: x/2 is rounded when k is odd, and the steps converge towards 1/sqrt(2 RN(x/2)), a relative 1/(2k)
+// from 1/sqrt(x), without arriving: the result is within a relative 1/k of 1/sqrt(x), no better.
+// Only a sum of squares of values below 1.5e-154 is subnormal (a quaternion injected with such a norm: quat2mat, integrate_attitude<true>);
+// what is promised there is a finite positive factor that keeps the direction, not the 2 ulp.
 __device__ __forceinline__ double rsqrt64(double x) {
   double y = __builtin_amdgcn_rsq(x);
   const double hx = 0.5 * x;
-  y = y * fma(-hx * y, y, 1.5);
-  y = y * fma(-hx * y, y, 1.5);
+  y = y * fmax(fma(-hx * y, y, 1.5), 0.5);
+  y = y * fmax(fma(-hx * y, y, 1.5), 0.5);
   return y;
 }
 
@@ -115,7 +123,8 @@ __device__ __forceinline__ double dot3(const double* a, const double* b) { retur
 // same ascending chain of fused multiply-adds (oracle/rdv_oracle.c, norm3; pinned by tests/golden/boundary_diag.npz)
 __device__ __forceinline__ double sumsq3(const double* v) { return dot3(v, v); }
 
-// cos(t) and sin(t)/t from u = t*t, for u <= kSmallU (t <= ~pi/4): Taylor to u^9, truncation < 2e-18
+// cos(t) and sin(t)/t from u = t*t, for u <= kSmallU (t <= ~pi/4): Taylor to u^9, truncation < 2e-18 (the first dropped terms are
+// u^10/20! < 4e-21 and u^10/21!).  With the roundings of the last Horner steps both results are within 0.75 ulp (measured: 0.63, 0.60).
 constexpr double kSmallU = 0.62;
 __device__ __forceinline__ void cos_sinc_small(double u, double& c, double& sc) {
   double p = -1.0 / 6402373705728000.0;            // -1/18!
@@ -140,7 +149,8 @@ __device__ __forceinline__ void cos_sinc_small(double u, double& c, double& sc) 
   sc = fma(q, u, 1.0);
 }
 // The same two series cut after u^4, for u <= kTinyU = 2^-7 (t <= 0.088 rad = 5 deg): the first dropped terms are u^5/10! < 8e-18 and
-// u^5/11! < 8e-19, a twentieth of an ulp of results near 1.  Every attitude step inside the observation Box is in this range
+// u^5/11! < 8e-19 — of the spacing 1.1e-16 of results just below 1, a fourteenth for cos and a hundred-and-fortieth for sin(t)/t; with
+// the final rounding both are within 0.6 ulp (measured: 0.57, 0.50).  Every attitude step inside the observation Box is in this range
 // (|w| dt/2 <= 10 deg/s * dt/2), as is a reset's chaser attitude: 8 Horner steps instead of 18 (and as many 64-bit literals less).
 constexpr double kTinyU = 0.0078125;
 // (The eight coefficients as SGPR operands read from the parameter block — one s_load instead of sixteen v_mov — were measured in round 4:
@@ -159,7 +169,10 @@ __device__ __forceinline__ void cos_sinc_tiny(double u, double& c, double& sc) {
   sc = fma(q, u, 1.0);
 }
 // Larger angles (never reached inside the observation Box: |w| <= 10 deg/s): halve the angle until it is small,
-// then apply cos 2x = 2cos^2 x - 1, sinc 2x = sinc x cos x once per halving (error doubles per halving).
+// then apply cos 2x = 2cos^2 x - 1, sinc 2x = sinc x cos x once per halving.  c = 2c^2 - 1 scales an error in c by 4c (2.8 to 3.7 in the
+// first doubling, where x lies in (0.39, 0.79]; up to 4 later) and adds a rounding: after h halvings the absolute errors of both results
+// are at most (4 2/3)^h * 0.75 * 2^-53.  Measured maxima of cos, in units of 2^-53: 2.2, 5.3, 9.9, 22, 45 for h = 1..5 and 1.4e4 at
+// h = 10 (u ~ 5e5); sin(t)/t stays below 8.2 up to h = 11 (tests/test_gpu_device_math.py, profiles/device_math_ulp.txt).
 __device__ __forceinline__ void cos_sinc_large(double u, double& c, double& sc) {
   int halvings = 0;
 #pragma clang loop unroll(disable)
@@ -269,7 +282,8 @@ __device__ __forceinline__ double rms7(const double* x) {
 // libm's pow is ~230 instructions a call, and a wave whose lanes split over "accepted" and "rejected" runs both calls of an attempt:
 // the controller cost a third of an attempted step.  Here: x = m 2^e with e = 5k + j, so x^(-1/5) = 2^(-k) (m 2^j)^(-1/5) with
 // t = m 2^j in [0.5, 16); a float32 estimate of t^(-1/5) from the hardware's log2 / exp2 (relative error ~1e-6) and two Newton steps
-// y <- y (6 - t y^5) / 5 in fp64 (error e -> 3 e^2: 1e-6 -> 3e-12 -> below an ulp).  Within a few ulp of pow; ~35 instructions.
+// y <- y (6 - t y^5) / 5 in fp64 (error e -> 3 e^2: 1e-6 -> 3e-12 -> below an ulp).  What is left is the last step's roundings: within
+// 4 ulp of x^(-1/5) (measured: 2.4); ~35 instructions.
 __device__ __forceinline__ double pow_minus_fifth(double x) {
   if (!(x < 1e300)) return 0.0;                      // huge / inf / NaN: the callers clamp the factor from below (0.2) anyway
   int e;
@@ -519,7 +533,12 @@ __device__ __forceinline__ float normalized(double val, double lo, double span, 
 #pragma clang fp contract(off)
   const double y = 2.0 * (val - lo);
   double q = y * inv_span;
-  q = fma(fma(-q, span, y), inv_span, q);
+  // (the residual is finite — below an ulp of y — unless the quotient overflows: there it is -+inf or NaN and would turn +-inf into NaN.
+  //  Held to the finite doubles, which changes no finite residual, the quotient stays +-inf like the division's.  As two min / max, not
+  //  as a select on q: that form ran the split kernel at 18 us for 6.4)
+  constexpr double kFinite = 1.7976931348623157e308;
+  const double r = fmin(fmax(fma(-q, span, y), -kFinite), kFinite);
+  q = fma(r, inv_span, q);
   return (float)(q + -1.0);
 }
 // get_observation (:294-311).  The 17 floats are handed to `sink(j, value)` one by one as they are formed — a kernel whose sink writes

@@ -785,7 +785,7 @@ int rdv_create(const RdvParams* params, int64_t n_envs, int device, int storage,
   if (err == hipSuccess) {
     what = "hipMemcpy of the acos table";
     std::vector<double> table((size_t)kAcosEntries);
-    for (int k = 0; k < kAcosEntries; ++k) table[(size_t)k] = std::acos((double)(k - 100000) / 1e5);   // the oracle's expression
+    for (int k = 0; k < kAcosEntries; ++k) table[(size_t)k] = std::acos((double)(k - 100000) / 1e5);   // the oracle's expression (rdv_probe.hip: rdvprobe_fill_acos_table is its twin, for the tests: keep them in step)
     err = hipMemcpy(h->acos_table, table.data(), table.size() * sizeof(double), hipMemcpyHostToDevice);
   }
   if (err == hipSuccess) { what = "hipMemcpy of the parameter block"; err = hipMemcpy(h->dev_params, &h->dev, sizeof(DevParams), hipMemcpyHostToDevice); }
