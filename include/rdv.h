@@ -39,7 +39,8 @@
  *   between general and non-general bodies.
  *   Calls that REFUSE inside a capture (RDV_ERR_INVALID_ARGUMENT, the message says "stream capture"; asked before anything touches the
  *   stream, so the capture stays valid): rdv_get_stats, rdv_get_group_stats, rdv_eval_summary, rdv_eval_group_summary, rdv_restore,
- *   rdv_set_param_groups (they synchronise or allocate) and rdv_policy_set_weights (its staging buffer is reused).  rdv_create,
+ *   rdv_set_param_groups (they synchronise or allocate), rdv_policy_set_weights and rdv_policy_set_member_weights (their staging
+ *   buffer is reused).  rdv_create,
  *   rdv_destroy and the policy create / destroy calls allocate and are not to be made while a capture is open either.
  *   SUPPORTED between replays, eagerly, on the stream that replays: rdv_step (the persistent kernels of a graph find the prepared states
  *   of the envs whose episodes it ended out of date by their tags and refill them before their first use) and rdv_set_params (it
@@ -568,6 +569,58 @@ int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t
                            const RdvAdvantageOut* out, void* stream);
 int rdv_policy_set_weights(rdv_policy p, const float* const* weights_host, const float* const* biases_host, const float* log_std_host,
                            void* stream);
+
+/*
+ * Policy sets (added within ABI 5): one batch, several actors and critics, one launch — the network half of the reference's sweeps
+ * (tune_reward.py, tune_algorithm.py, tune_policy.py per architecture, the seed axis of sensitivity_analysis.py: one policy per
+ * configuration), as parameter groups are the environment half.  A set is n_members networks of ONE RdvMlpSpec; member g owns
+ * sizes[g] consecutive rows, member 0 from row 0 on.  The specification:
+ *
+ *     Row i of member g gets bit for bit what a stand-alone handle of member g's weights computes for that row, with the same
+ *     seed, the same counter and env_id_offset + start_g              (start_g = sizes[0] + .. + sizes[g-1]).
+ *
+ * This covers the clipped action, the unclipped sample, log_prob and the value; the noise contract above keys by global env id
+ * (env_id_offset + flat row of the set), so it holds as it stands.
+ *
+ * The 256-row rule: every size is positive and every size but the last is a multiple of 256 rows — the rule of parameter groups,
+ * checked by rdv_param_groups_check (host-only), whose message names the offending member as "group".  A workgroup of the actor
+ * kernels owns 256 rows and stages one parameter block; the set kernels (csrc/rdv_policy_sets.h) stage the block of their tile's
+ * member and are otherwise the kernels of stand-alone handles.  The same-spec rule: all members have the spec given at creation
+ * (the default spec: the shipped 17-64-64 tanh block and its kernels); members of different architectures are not offered.
+ *
+ * rdv_policy_set_create / rdv_critic_set_create: weights_host[g] and biases_host[g] are member g's arrays of n_hidden + 1 HOST
+ *   pointers in the layout of rdv_policy_create_mlp, log_std_host[g] its [6] (actors).  Checked per member as there (null pointers:
+ *   RDV_ERR_INVALID_ARGUMENT, a non-finite weight: RDV_ERR_BAD_PARAMS, the message naming layer and member), all before the device is
+ *   touched.  One device allocation holds the member blocks — exactly the bytes of stand-alone handles — and the tile table.  The result
+ *   is an rdv_policy: rdv_policy_destroy, rdv_policy_get_spec work on it.  n_members = 1 is legal and equals the plain handle (the plain
+ *   kernels, the persistent rollout kernel), with the row checks below.
+ * rdv_policy_num_members / rdv_policy_num_rows: 1 / 0 for a plain handle (-1 for an invalid one), as rdv_num_groups reports.
+ * Which calls accept a set:
+ *   rdv_policy_act          n must equal the set's rows (RDV_ERR_INVALID_ARGUMENT naming both numbers otherwise).
+ *   rdv_policy_value        n must be a positive multiple of the set's rows: obs is [k, rows, 17], flat row r belongs to env r mod rows
+ *                           (the [T, N, 17] rows of a rollout).  Row blocks whose first row is not 16-byte aligned (rows % 4 != 0) are
+ *                           read element-wise: obs itself must be 16-byte aligned, as for a plain handle.
+ *   rdv_rollout_advantages  passes n_steps and n through to rdv_policy_value: n must equal the set's rows.
+ *   rdv_rollout             the set's rows must equal the handle's envs.  A set of more than one member takes the loop the call is
+ *                           defined by (rdv_policy_act + rdv_step, n_steps times), whatever the env handle: there is no persistent
+ *                           kernel for sets.  A set's ranges and the env handle's parameter groups are independent: the handle may be
+ *                           ungrouped, or grouped with the same or other sizes.
+ *   rdv_policy_set_weights  RDV_ERR_INVALID_ARGUMENT for a set of more than one member: use rdv_policy_set_member_weights.
+ * rdv_policy_set_member_weights: rdv_policy_set_weights for ONE member (arguments, checks, ordering on `stream` and the refusal inside a
+ *   stream capture as there; member 0 of a plain handle is the handle).  Launches already queued on the stream read the old block of
+ *   that member, later ones the new; the other members' blocks are not written.  The pinned staging has one slot and one event per
+ *   member: refreshing all members back to back does not wait on the host for another member's copy, only a second refresh of the
+ *   SAME member waits for its first copy.
+ */
+int rdv_policy_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host,
+                          const float* const* const* weights_host, const float* const* const* biases_host,
+                          const float* const* log_std_host, int device, rdv_policy* out);
+int rdv_critic_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host,
+                          const float* const* const* weights_host, const float* const* const* biases_host, int device, rdv_policy* out);
+int rdv_policy_set_member_weights(rdv_policy p, int32_t member, const float* const* weights_host, const float* const* biases_host,
+                                  const float* log_std_host, void* stream);
+int32_t rdv_policy_num_members(rdv_policy p);
+int64_t rdv_policy_num_rows(rdv_policy p);
 
 #ifdef __cplusplus
 }

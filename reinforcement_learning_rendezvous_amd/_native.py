@@ -34,7 +34,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # other MLP architectures (added within ABI 5)
            "rdv_mlp_spec_default", "rdv_mlp_spec_check", "rdv_policy_create_mlp", "rdv_critic_create_mlp", "rdv_policy_get_spec",
            # learner-ready rollouts (added within ABI 5)
-           "rdv_gae", "rdv_rollout_advantages", "rdv_policy_set_weights"]
+           "rdv_gae", "rdv_rollout_advantages", "rdv_policy_set_weights",
+           # policy sets (added within ABI 5)
+           "rdv_policy_set_create", "rdv_critic_set_create", "rdv_policy_set_member_weights", "rdv_policy_num_members", "rdv_policy_num_rows"]
 
 
 class RdvError(RuntimeError):
@@ -111,7 +113,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the six translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_advantages.hip) for gfx950 and link librdv_hip.so
+    """Compile the seven translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_sets.hip, rdv_advantages.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -190,6 +192,11 @@ def lib():
         "rdv_gae": (C.c_int, [vp, vp, vp, vp, i32, i64, C.c_double, C.c_double, vp, vp, C.c_int, vp]),
         "rdv_rollout_advantages": (C.c_int, [vp, C.POINTER(RolloutOut), i32, i64, C.c_double, C.c_double, C.POINTER(AdvantageOut), vp]),
         "rdv_policy_set_weights": (C.c_int, [vp, vp, vp, vp, vp]),
+        "rdv_policy_set_create": (C.c_int, [C.POINTER(MlpSpec), i32, C.POINTER(i64), vp, vp, vp, C.c_int, C.POINTER(vp)]),
+        "rdv_critic_set_create": (C.c_int, [C.POINTER(MlpSpec), i32, C.POINTER(i64), vp, vp, C.c_int, C.POINTER(vp)]),
+        "rdv_policy_set_member_weights": (C.c_int, [vp, i32, vp, vp, vp, vp]),
+        "rdv_policy_num_members": (i32, [vp]),
+        "rdv_policy_num_rows": (i64, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

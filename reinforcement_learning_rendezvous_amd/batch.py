@@ -260,7 +260,10 @@ class RendezvousBatch:
         [T,N,6] (before clipping), ``reward`` [T,N], ``done`` [T,N] (uint8), ``log_prob`` [T,N], ``last_obs`` [N,17]; pass
         the dict back as ``out`` to reuse the buffers.  ``policy`` is an MlpPolicy (its HIP handle and noise key are used).
         A policy of another architecture than the shipped 17-64-64-6 tanh (``net_arch`` / ``activation_fn``) takes the loop
-        this call is defined by inside the library: rdv_policy_act + rdv_step, two launches per step, the same rows."""
+        this call is defined by inside the library: rdv_policy_act + rdv_step, two launches per step, the same rows.
+        ``policy`` may be a ``PolicySet`` whose rows are the batch's envs: member g acts for the envs of its range (env i as in a
+        batch of its own with ``env_id_offset + start_g``); a set of more than one member takes that loop too, its actor ONE launch
+        per step for all members.  The set's ranges and the batch's parameter groups are independent."""
         T, n, dev = int(n_steps), self.num_envs, self.device
         if out is None or out["obs"].shape[0] != T:
             out = dict(obs=torch.empty((T, n, N.OBS_DIM), dtype=torch.float32, device=dev),
@@ -281,7 +284,8 @@ class RendezvousBatch:
         """``rollout`` followed by ``policy.advantages`` on the current stream: every column of SB3's RolloutBuffer for ``n_steps``
         steps — the rows of ``rollout`` plus ``values``, ``last_value``, ``advantages``, ``returns`` (what ``collect_rollouts`` leaves
         behind after ``compute_returns_and_advantage``, main.py:114).  The rows are those of the two separate calls; pass the dict
-        back as ``out`` to reuse every buffer."""
+        back as ``out`` to reuse every buffer.  With a ``PolicySet`` this is the training entry point of a sweep: every env's columns
+        are those of its member's actor and critic, in one actor launch per step and two critic launches per call."""
         ro = self.rollout(policy, n_steps, deterministic=deterministic, out=out)
         return policy.advantages(ro, gamma=gamma, gae_lambda=gae_lambda, out=out)
 

@@ -4,12 +4,13 @@
 // included below: rdv_step.h and rdv_fused.h (one-launch step kernels), rdv_cold.h (reset, state access, evaluation summary),
 // rdv_policy.h (the shipped actor / critic), rdv_rollout.h and rdv_step_many.h (persistent kernels); three small ones (parameter upload,
 // device error word, snapshot header) are defined here.  rdv_tiles.hip, rdv_general.hip, rdv_groups.hip (which instantiates the step
-// kernels of rdv_step.h and rdv_fused.h once more, with a tile table) and rdv_policy_mlp.hip are translation units of their own, entered
-// through the launch functions of their headers.
+// kernels of rdv_step.h and rdv_fused.h once more, with a tile table), rdv_policy_mlp.hip and rdv_policy_sets.hip (the actor / critic kernels of policy sets) are translation units of
+// their own, entered through the launch functions of their headers.
 // The data layout in HBM is described in rdv_kernels.h.
 #include "rdv_device.h"
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
+#include "rdv_policy_sets.h"
 #include "rdv_advantages.h"
 
 #include <hip/hip_runtime.h>
@@ -427,8 +428,13 @@ struct RdvPolicyNet {
   RdvMlpSpec spec;
   bool shipped_arch;   // 17-64-64-out tanh: policy_act_kernel / policy_value_kernel, and the persistent rollout_kernel
   int block_floats;
-  float* staging;      // rdv_policy_set_weights: pinned host copy of the block in flight (made by the first call, nullptr before)
-  hipEvent_t staged;   // ... recorded behind the copy out of it: the next call waits for it before it overwrites `staging`
+  float* staging;      // rdv_policy_set_weights / rdv_policy_set_member_weights: pinned host copies of the blocks in flight, one slot per
+                       // member (made by the first call, nullptr before)
+  std::vector<hipEvent_t> staged;   // ... per member, recorded behind the copy out of its slot: the next refresh of THAT member waits for it
+  // policy sets (csrc/rdv_policy_sets.h): `weights` holds n_members blocks of block_floats floats, then the tile table
+  int32_t n_members;   // 1: a plain handle, or a set of one member (the plain kernels read its one block)
+  int64_t rows;        // 0: a plain handle (any n); a set: the rows its members own together
+  const int32_t* tile_member;   // device: member index per 256-row tile (inside the allocation of `weights`); nullptr for a plain handle
 };
 static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
 static constexpr uint32_t kPolicyMagic = 0x52445650u;   // "RDVP"
@@ -442,7 +448,8 @@ static bool all_finite(const float* w, int count) {
 static int finish_policy(const char* who, const std::vector<float>& packed, const RdvMlpSpec& spec, bool shipped_arch, int out_dim, int device, rdv_policy* out) {
   RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
   if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
-  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr; p->staged = nullptr;
+  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
+  p->n_members = 1; p->rows = 0; p->tile_member = nullptr;
   p->spec = spec; p->shipped_arch = shipped_arch; p->block_floats = shipped_arch ? kPolFloats : (int)packed.size();
   hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
   if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -541,40 +548,139 @@ int rdv_policy_get_spec(rdv_policy p, RdvMlpSpec* out_host) {
 
 // ---- refreshing a handle's weights (a learner's optimiser step): the block is packed on the host as at creation and copied into the
 // handle's device allocation from a pinned buffer of the handle's own, on the caller's stream
-int rdv_policy_set_weights(rdv_policy p, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  if (!weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: null weights_host or biases_host");
+// the checks of one network's host arrays against the handle's spec, and its packed block
+static int pack_for_handle(rdv_policy p, const char* who, const float* const* weights, const float* const* biases, const float* log_std, std::vector<float>& packed) {
+  if (!weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights_host or biases_host", who);
   const bool actor = p->out_dim == kPolOut;
-  if (actor && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: log_std_host is required for an actor");
-  if (!actor && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: log_std_host must be null for a critic (rdv_critic_create)");
+  if (actor && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host is required for an actor", who);
+  if (!actor && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host must be null for a critic (rdv_critic_create)", who);
   const int L = p->spec.n_hidden;
   for (int l = 0; l <= L; ++l)
-    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: null weights or biases of layer %d", l);
+    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights or biases of layer %d", who, l);
   for (int l = 0; l <= L; ++l) {
     const int in_w = l == 0 ? kPolIn : p->spec.hidden[l - 1], out_w = l < L ? p->spec.hidden[l] : p->out_dim;
-    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_set_weights: non-finite weight in layer %d", l);
+    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite weight in layer %d", who, l);
   }
-  std::vector<float> packed;
   if (p->shipped_arch) pack_policy_weights(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, p->out_dim, packed);
   else pack_mlp_weights(p->spec, p->out_dim, weights, biases, log_std, packed);
-  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "rdv_policy_set_weights: the packed block has %d floats, the handle's %d", (int)packed.size(), p->block_floats);
+  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "%s: the packed block has %d floats, the handle's %d", who, (int)packed.size(), p->block_floats);
+  return RDV_OK;
+}
+// block `member` of the handle <- packed, ordered on `stream`.  The pinned staging has one slot and one event per member, so refreshing
+// all members back to back never waits on the host for another member's copy, only for the previous refresh of the same member.
+static int upload_block(rdv_policy p, const char* who, int32_t member, const std::vector<float>& packed, void* stream) {
   DeviceGuard guard(p->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
   RDV_HIP(hipStreamIsCapturing(s, &capturing));
-  if (capturing != hipStreamCaptureStatusNone) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: not legal inside a stream capture (the staging buffer is reused by the next call)");
-  const size_t bytes = packed.size() * sizeof(float);
+  if (capturing != hipStreamCaptureStatusNone) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: not legal inside a stream capture (the staging buffer is reused by the next call)", who);
+  const size_t floats = (size_t)p->block_floats, bytes = floats * sizeof(float);
   if (!p->staging) {
-    RDV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->staging), bytes, hipHostMallocDefault));
-    RDV_HIP(hipEventCreateWithFlags(&p->staged, hipEventDisableTiming));
-  } else {
-    RDV_HIP(hipEventSynchronize(p->staged));   // the previous refresh has left the buffer (usually long ago)
+    RDV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->staging), bytes * (size_t)p->n_members, hipHostMallocDefault));
+    p->staged.assign((size_t)p->n_members, nullptr);
   }
-  std::memcpy(p->staging, packed.data(), bytes);
-  RDV_HIP(hipMemcpyAsync(p->weights, p->staging, bytes, hipMemcpyHostToDevice, s));
-  RDV_HIP(hipEventRecord(p->staged, s));
+  hipEvent_t& ev = p->staged[(size_t)member];
+  if (!ev) RDV_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  else RDV_HIP(hipEventSynchronize(ev));   // the previous refresh of this member has left its slot (usually long ago)
+  float* slot = p->staging + floats * (size_t)member;
+  std::memcpy(slot, packed.data(), bytes);
+  RDV_HIP(hipMemcpyAsync(p->weights + floats * (size_t)member, slot, bytes, hipMemcpyHostToDevice, s));
+  RDV_HIP(hipEventRecord(ev, s));
   return RDV_OK;
 }
+
+int rdv_policy_set_weights(rdv_policy p, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (p->n_members > 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: this handle is a policy set of %d members: refresh one member with rdv_policy_set_member_weights", p->n_members);
+  std::vector<float> packed;
+  if (int rc = pack_for_handle(p, "rdv_policy_set_weights", weights, biases, log_std, packed)) return rc;
+  return upload_block(p, "rdv_policy_set_weights", 0, packed, stream);
+}
+
+int rdv_policy_set_member_weights(rdv_policy p, int32_t member, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (member < 0 || member >= p->n_members) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_member_weights: member %d of %d", member, p->n_members);
+  std::vector<float> packed;
+  if (int rc = pack_for_handle(p, "rdv_policy_set_member_weights", weights, biases, log_std, packed)) return rc;
+  return upload_block(p, "rdv_policy_set_member_weights", member, packed, stream);
+}
+
+// ---- policy sets (csrc/rdv_policy_sets.h): n_members networks of one spec, member g owning sizes[g] consecutive rows
+static int create_set(const char* who, const RdvMlpSpec* spec, int32_t n_members, const int64_t* sizes, const float* const* const* weights,
+                      const float* const* const* biases, const float* const* log_std, int out_dim, int device, rdv_policy* out) {
+  if (!spec || !sizes || !weights || !biases || !out || (out_dim == kPolOut && !log_std)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (int rc = rdv_mlp_spec_check(spec)) return rc;
+  if (n_members < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_members = %d: a set has at least member 0", who, n_members);
+  // the set's rows are the sum of the sizes; the rule of parameter groups judges them: positive, every one but the last a multiple of 256
+  // (a size that is not positive, or would overflow the sum, ends the sum: the check then names it against a count nothing exceeds)
+  constexpr int64_t kMostRows = INT64_MAX / 2;
+  int64_t rows = 0;
+  for (int32_t g = 0; g < n_members && rows >= 0; ++g) rows = (sizes[g] > 0 && sizes[g] <= kMostRows - rows) ? rows + sizes[g] : -1;
+  if (int rc = rdv_param_groups_check(rows < 0 ? kMostRows : rows, n_members, sizes)) return rc;
+  const int L = spec->n_hidden;
+  for (int32_t g = 0; g < n_members; ++g) {
+    if (!weights[g] || !biases[g] || (out_dim == kPolOut && !log_std[g])) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights, biases or log_std of member %d", who, g);
+    for (int l = 0; l <= L; ++l) {
+      if (!weights[g][l] || !biases[g][l]) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights or biases of layer %d of member %d", who, l, g);
+      const int in_w = l == 0 ? kPolIn : spec->hidden[l - 1], out_w = l < L ? spec->hidden[l] : out_dim;
+      if (!all_finite(weights[g][l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite weight in layer %d of member %d", who, l, g);
+    }
+  }
+  if (int rc = check_device(who, device)) return rc;
+  DeviceGuard guard(device);
+#ifndef RDV_MLP_GENERAL_DEFAULT
+  const bool shipped = std::memcmp(spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0;
+#else
+  const bool shipped = false;
+#endif
+  // member blocks: exactly the bytes of stand-alone handles; then (256-byte aligned) the tile table
+  std::vector<float> all, packed;
+  for (int32_t g = 0; g < n_members; ++g) {
+    const float* ls = out_dim == kPolOut ? log_std[g] : nullptr;
+    if (shipped) pack_policy_weights(weights[g][0], biases[g][0], weights[g][1], biases[g][1], weights[g][2], biases[g][2], ls, out_dim, packed);
+    else pack_mlp_weights(*spec, out_dim, weights[g], biases[g], ls, packed);
+    if (g && packed.size() * (size_t)g != all.size()) return fail(RDV_ERR_HIP, "%s: member %d packs to %zu floats, member 0 to %zu", who, g, packed.size(), all.size() / (size_t)g);
+    all.insert(all.end(), packed.begin(), packed.end());
+  }
+  const size_t block_floats = packed.size();
+  const int64_t tiles = (rows + kSetTile - 1) / kSetTile;
+  std::vector<int32_t> table((size_t)tiles);
+  int64_t at = 0;
+  for (int32_t g = 0; g < n_members; ++g) {
+    for (int64_t t = at / kSetTile; t < (at + sizes[g] + kSetTile - 1) / kSetTile; ++t) table[(size_t)t] = g;
+    at += sizes[g];
+  }
+  const size_t table_at = (size_t)align_up((int64_t)(all.size() * sizeof(float)), 256);
+  // (finish_policy allocates and uploads ONE block; here the allocation also holds the other blocks and the table)
+  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
+  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
+  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
+  p->spec = *spec; p->shipped_arch = shipped; p->block_floats = (int)block_floats;
+  p->n_members = n_members; p->rows = rows; p->tile_member = nullptr;
+  hipError_t err = hipMalloc(&p->weights, table_at + table.size() * sizeof(int32_t));
+  if (err == hipSuccess) err = hipMemcpy(p->weights, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMemcpy(reinterpret_cast<char*>(p->weights) + table_at, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  // a set of one member runs the plain kernels on its one block; larger sets the set kernels
+  if (err == hipSuccess && !shipped) err = mlp_raise_lds_limit();
+  if (err == hipSuccess && shipped) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
+  if (err == hipSuccess && shipped) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_value_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
+  if (err == hipSuccess) err = sets_raise_lds_limit(shipped);
+  if (err != hipSuccess) { (void)hipGetLastError(); if (p->weights) (void)hipFree(p->weights); delete p; return fail(RDV_ERR_HIP, "%s: %s", who, hipGetErrorString(err)); }
+  p->tile_member = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p->weights) + table_at);
+  *out = p;
+  return RDV_OK;
+}
+
+int rdv_policy_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* const* weights_host,
+                          const float* const* const* biases_host, const float* const* log_std_host, int device, rdv_policy* out) {
+  return create_set("rdv_policy_set_create", spec_host, n_members, sizes_host, weights_host, biases_host, log_std_host, kPolOut, device, out);
+}
+int rdv_critic_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* const* weights_host,
+                          const float* const* const* biases_host, int device, rdv_policy* out) {
+  return create_set("rdv_critic_set_create", spec_host, n_members, sizes_host, weights_host, biases_host, nullptr, 1, device, out);
+}
+int32_t rdv_policy_num_members(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->n_members : -1; }
+int64_t rdv_policy_num_rows(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->rows : -1; }
 
 int rdv_policy_destroy(rdv_policy p) {
   if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
@@ -582,7 +688,7 @@ int rdv_policy_destroy(rdv_policy p) {
   (void)hipDeviceSynchronize();
   (void)hipFree(p->weights);
   if (p->staging) (void)hipHostFree(p->staging);
-  if (p->staged) (void)hipEventDestroy(p->staged);
+  for (hipEvent_t ev : p->staged) if (ev) (void)hipEventDestroy(ev);
   p->magic = 0;
   delete p;
   return RDV_OK;
@@ -591,6 +697,12 @@ int rdv_policy_destroy(rdv_policy p) {
 // the actor on n observation rows: clipped actions for the env and, optionally, the unclipped sample and its log-probability
 static int launch_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
                              uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s) {
+  if (p->n_members > 1) {   // a policy set: each 256-row tile reads its member's block (csrc/rdv_policy_sets.h); n == p->rows, checked by the callers
+    sets_launch_act(p->shipped_arch, p->spec.activation, p->weights, p->block_floats, p->tile_member, obs, actions, n, deterministic, seed, counter,
+                    env_id_offset, raw_actions, log_prob, s);
+    RDV_HIP(hipGetLastError());
+    return RDV_OK;
+  }
   if (!p->shipped_arch) {
     mlp_launch_act(p->spec.activation, p->weights, p->block_floats, obs, actions, n, deterministic, seed, counter, env_id_offset, raw_actions, log_prob, s);
     RDV_HIP(hipGetLastError());
@@ -608,6 +720,7 @@ int rdv_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, in
   if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: this handle is a critic (rdv_critic_create)");
   if (!obs || !actions || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs, actions and a positive n are required");
   if (misaligned(obs, 16) || misaligned(actions, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs and actions must be 16-byte aligned");
+  if (p->rows && n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: n = %lld, the policy set owns %lld rows", (long long)n, (long long)p->rows);
   DeviceGuard guard(p->device);
   return launch_policy_act(p, obs, actions, n, deterministic, seed, counter, env_id_offset, nullptr, nullptr, static_cast<hipStream_t>(stream));
 }
@@ -617,7 +730,13 @@ int rdv_policy_value(rdv_policy p, const float* obs, float* values, int64_t n, v
   if (p->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: this handle is an actor (rdv_policy_create)");
   if (!obs || !values || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs, values and a positive n are required");
   if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs must be 16-byte aligned");
+  if (p->rows && n % p->rows != 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: n = %lld is not a multiple of the %lld rows the critic set owns", (long long)n, (long long)p->rows);
   DeviceGuard guard(p->device);
+  if (p->n_members > 1) {   // flat row r belongs to env r mod rows: row blocks of the set's rows, the tile table serving each
+    sets_launch_value(p->shipped_arch, p->spec.activation, p->weights, p->block_floats, p->tile_member, obs, values, p->rows, n / p->rows, static_cast<hipStream_t>(stream));
+    RDV_HIP(hipGetLastError());
+    return RDV_OK;
+  }
   if (!p->shipped_arch) {
     mlp_launch_value(p->spec.activation, p->weights, p->block_floats, obs, values, n, static_cast<hipStream_t>(stream));
     RDV_HIP(hipGetLastError());
@@ -668,6 +787,7 @@ int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t
   if (int rc = check_gae_scalars("rdv_rollout_advantages", n_steps, n, gamma, gae_lambda)) return rc;
   if (!critic || critic->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
   if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: this handle is an actor (rdv_policy_create)");
+  if (critic->rows && n != critic->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: n = %lld, the critic set owns %lld rows", (long long)n, (long long)critic->rows);
   if (misaligned(rows->obs, 16) || misaligned(rows->last_obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows->obs and rows->last_obs must be 16-byte aligned");
   // the critic at call time over the rows the actor saw, then over the observation after the last step: rdv_policy_value's own launches
   if (int rc = rdv_policy_value(critic, rows->obs, out->values, (int64_t)n_steps * n, stream)) return rc;
@@ -686,6 +806,7 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: this handle is a critic (rdv_critic_create)");
   if (p->device != h->device) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: the policy lives on device %d, the envs on device %d", p->device, h->device);
   if (n_steps <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: n_steps must be positive (got %d)", n_steps);
+  if (p->rows && p->rows != h->n) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: the policy set owns %lld rows, the batch has %lld envs", (long long)p->rows, (long long)h->n);
   if (!out || !out->obs || !out->actions || !out->reward || !out->done || !out->last_obs)
     return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: obs, actions, reward, done and last_obs are required");
   if (misaligned(out->obs, 16) || misaligned(out->actions, 16) || misaligned(out->last_obs, 16))
@@ -694,8 +815,9 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   RDV_CHECK_FAULT(h);
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (h->general || h->n_groups || !p->shipped_arch) {
-    // General rigid bodies, parameter groups (no grouped persistent kernel) and policies of another architecture than the shipped one (the
+  if (h->general || h->n_groups || !p->shipped_arch || p->n_members > 1) {
+    // General rigid bodies, parameter groups (no grouped persistent kernel), policy sets of more than one member (no persistent kernel for
+    // sets) and policies of another architecture than the shipped one (the
     // persistent kernel's registers and LDS are laid out for 17-64-64-6 tanh): rdv_policy_act + rdv_step, n_steps times, on `stream` — the definition of this call's results, used as
     // its implementation.  The per-lane RK45 inside the 168-register budget of the persistent kernel's 12-wave workgroup spilled 120
     // dwords per lane and ran SLOWER than this loop (72 against 58 us per step at 65,536 envs, round 2): not offered any more.

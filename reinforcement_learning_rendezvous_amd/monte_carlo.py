@@ -147,7 +147,12 @@ def sweep(policy, initial_states, configs, device="cuda:0", storage="f32", deter
     config (include/rdv.h, parameter groups): one step launch per timestep for the whole grid.  Each group is padded to a multiple
     of 256 rows by repeating its last row (groups begin on 256-env boundaries); the padding is dropped from the results.  Returns
     one table per config, in the format ``run`` returns, equal to ``run(policy, initial_states, config=c)``.  Deterministic actor only
-    (the reference's sweep scripts use ``predict(deterministic=True)``)."""
+    (the reference's sweep scripts use ``predict(deterministic=True)``).
+
+    ``policy`` may also be a LIST of ``len(configs)`` policies of one architecture: config c is then evaluated by policy c — what the
+    reference's evaluation callback does in a reward or seed sweep, one trained policy per configuration — through a ``PolicySet``
+    over the same groups: one actor launch per timestep for all of them, the batch, the padding and the result format unchanged,
+    each table equal to ``run(policies[c], initial_states, config=configs[c])``."""
     from .batch import RendezvousBatch
     from .evaluation import episode_steps_bound
     from .params import GROUP_TILE
@@ -158,6 +163,12 @@ def sweep(policy, initial_states, configs, device="cuda:0", storage="f32", deter
     m = len(unit)
     padded = -(-m // GROUP_TILE) * GROUP_TILE
     rows = np.concatenate([unit, np.repeat(unit[-1:], padded - m, axis=0)])
+    own_set = isinstance(policy, (list, tuple))
+    if own_set:
+        from .policy import PolicySet
+        if len(policy) != len(params):
+            raise ValueError(f"sweep: {len(policy)} policies for {len(params)} configs (a list of policies has one per config)")
+        policy = PolicySet(policy, [padded] * len(params))
     env = RendezvousBatch(padded * len(params), params=params, group_sizes=[padded] * len(params), device=device, storage=storage,
                           on_done="halt", seed=seed)
     policy = policy.to(env.device)
@@ -172,6 +183,8 @@ def sweep(policy, initial_states, configs, device="cuda:0", storage="f32", deter
     aux = env.get_aux()
     out = [columns_from_accumulators(env.eval[s][:m], aux[s][:m], p) for s, p in zip(env.group_slices, params)]
     env.close()
+    if own_set:                               # the set made above: its handles go with it (the member policies are the caller's)
+        policy.close()
     return out
 
 

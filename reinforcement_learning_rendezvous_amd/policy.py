@@ -81,6 +81,44 @@ def infer_arch(weights, net):
     return arch or None
 
 
+@torch.no_grad()
+def _advantages(policy, ro, gamma, gae_lambda, out):
+    """``MlpPolicy.advantages`` / ``PolicySet.advantages``: ``policy`` gives has_critic, backend, _critic_handle(device) and
+    _value_torch(obs)."""
+    from . import advantages as A
+    if not policy.has_critic:
+        raise ValueError("advantages: this policy has no critic (its weights hold no value_net trunk)")
+    obs = ro["obs"]
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
+        raise ValueError(f"obs: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
+    T, n, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+    A.check_tensor(obs, "obs", (T, n, 17), torch.float32, dev)
+    A.check_tensor(ro["reward"], "reward", (T, n), torch.float32, dev)
+    A.check_tensor(ro["done"], "done", (T, n), torch.uint8, dev)
+    A.check_tensor(ro["last_obs"], "last_obs", (n, 17), torch.float32, dev)
+    A.check_discounts(gamma, gae_lambda)
+    cols = dict(values=(T, n), last_value=(n,), advantages=(T, n), returns=(T, n))
+    src = out if out is not None else ro
+    for name, shape in cols.items():
+        t = src.get(name)
+        if t is None or tuple(t.shape) != shape or t.device != dev:
+            t = torch.empty(shape, dtype=torch.float32, device=dev)
+        A.check_tensor(t, name, shape, torch.float32, dev)
+        ro[name] = t
+    if policy.backend != "torch" and obs.is_cuda:
+        from . import _native as N
+        rows = N.RolloutOut(obs.data_ptr(), None, ro["reward"].data_ptr(), ro["done"].data_ptr(), None, ro["last_obs"].data_ptr())
+        ao = N.AdvantageOut(*[ro[f].data_ptr() for f, _ in N.AdvantageOut._fields_])
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        N.check(N.lib().rdv_rollout_advantages(policy._critic_handle(dev), C.byref(rows), T, n, float(gamma), float(gae_lambda),
+                                               C.byref(ao), stream))
+        return ro
+    ro["values"].copy_(policy._value_torch(obs))
+    ro["last_value"].copy_(policy._value_torch(ro["last_obs"]))
+    A.gae(ro["reward"], ro["done"], ro["values"], ro["last_value"], gamma, gae_lambda, out=(ro["advantages"], ro["returns"]))
+    return ro
+
+
 class MlpPolicy(torch.nn.Module):
     def __init__(self, weights=None, net_arch=None, activation_fn="tanh", obs_dim=17, hidden=64, act_dim=6, seed=0, backend="auto"):
         super().__init__()
@@ -269,38 +307,11 @@ class MlpPolicy(torch.nn.Module):
         They are allocated once: taken from ``out`` (e.g. the dict an earlier call returned), or from ``ro`` itself when it has them.
         CUDA rows: rdv_rollout_advantages on the current stream (two critic launches and the GAE kernel; the values are the critic's
         at call time, bit-identical to ``value()``); ``backend="torch"`` or CPU rows: the modules plus ``advantages.gae``."""
-        from . import advantages as A
-        if not self.has_critic:
-            raise ValueError("advantages: this policy has no critic (its weights hold no value_net trunk)")
-        obs = ro["obs"]
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
-            raise ValueError(f"obs: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
-        T, n, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
-        A.check_tensor(obs, "obs", (T, n, 17), torch.float32, dev)
-        A.check_tensor(ro["reward"], "reward", (T, n), torch.float32, dev)
-        A.check_tensor(ro["done"], "done", (T, n), torch.uint8, dev)
-        A.check_tensor(ro["last_obs"], "last_obs", (n, 17), torch.float32, dev)
-        A.check_discounts(gamma, gae_lambda)
-        cols = dict(values=(T, n), last_value=(n,), advantages=(T, n), returns=(T, n))
-        src = out if out is not None else ro
-        for name, shape in cols.items():
-            t = src.get(name)
-            if t is None or tuple(t.shape) != shape or t.device != dev:
-                t = torch.empty(shape, dtype=torch.float32, device=dev)
-            A.check_tensor(t, name, shape, torch.float32, dev)
-            ro[name] = t
-        if self.backend != "torch" and obs.is_cuda:
-            from . import _native as N
-            rows = N.RolloutOut(obs.data_ptr(), None, ro["reward"].data_ptr(), ro["done"].data_ptr(), None, ro["last_obs"].data_ptr())
-            ao = N.AdvantageOut(*[ro[f].data_ptr() for f, _ in N.AdvantageOut._fields_])
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            N.check(N.lib().rdv_rollout_advantages(self._critic_handle(dev), C.byref(rows), T, n, float(gamma), float(gae_lambda),
-                                                   C.byref(ao), stream))
-            return ro
-        ro["values"].copy_(self._forward("v", obs.reshape(-1, 17)).reshape(T, n))
-        ro["last_value"].copy_(self._forward("v", ro["last_obs"]).reshape(n))
-        A.gae(ro["reward"], ro["done"], ro["values"], ro["last_value"], gamma, gae_lambda, out=(ro["advantages"], ro["returns"]))
-        return ro
+        return _advantages(self, ro, gamma, gae_lambda, out)
+
+    def _value_torch(self, obs):
+        """The critic's PyTorch modules on observations [..., 17]."""
+        return self._forward("v", obs.reshape(-1, 17)).reshape(obs.shape[:-1])
 
     def update_weights(self, weights=None):
         """New weights for the policy and for every live HIP handle of it — what a learner calls after ``optimizer.step()``.
@@ -352,3 +363,216 @@ class MlpPolicy(torch.nn.Module):
         dev = self.l1.weight.device
         obs = torch.as_tensor(np.asarray(observation), dtype=torch.float32, device=dev)
         return self.act(obs, deterministic=deterministic).cpu().numpy(), state
+
+
+class PolicySet:
+    """P member policies of ONE architecture over one batch: member g owns the next ``group_sizes[g]`` rows, and one launch evaluates all
+    members (include/rdv.h, "Policy sets"; csrc/rdv_policy_sets.h) — the network half of a sweep of P learners on one GPU, as a grouped
+    ``RendezvousBatch`` is the environment half.  Row i of member g gets bit for bit what ``policies[g]`` alone computes for that row with
+    the same noise seed, the same call counter and ``env_id_offset + start_g``.
+
+    ``policies``: MlpPolicy objects with the same ``pi_arch``, ``vf_arch`` and ``activation`` (ValueError naming the first member that
+    differs); they stay the source of truth for the weights (``set[g]``).  ``group_sizes``: positive, every one but the last a multiple
+    of 256 rows, summing to ``num_rows`` when that is given — the rule and the messages of rdv_param_groups_check, checked on the host
+    before any device is touched.  ``RendezvousBatch.act`` / ``rollout`` / ``collect`` take a set where they take an MlpPolicy; a set's
+    ranges and the batch's parameter groups are independent.  One noise key for the whole set: ``noise_seed`` (default: member 0's) and
+    the call counter ``_calls``.  CUDA float32 input goes to the set kernels; CPU input or ``backend="torch"`` loops the members'
+    PyTorch modules over their slices."""
+
+    def __init__(self, policies, group_sizes, num_rows=None, noise_seed=None, backend="auto"):
+        from .params import group_tile_table
+        policies = list(policies)
+        if not policies:
+            raise ValueError("PolicySet: at least one member policy")
+        sizes = [int(x) for x in group_sizes]
+        if len(sizes) != len(policies):
+            raise ValueError(f"PolicySet: {len(policies)} policies but {len(sizes)} group sizes")
+        first = policies[0]
+        for g, p in enumerate(policies):
+            if not isinstance(p, MlpPolicy):
+                raise TypeError(f"PolicySet: member {g} is a {type(p).__name__}, not an MlpPolicy")
+            for what in ("pi_arch", "vf_arch", "activation"):
+                if getattr(p, what) != getattr(first, what):
+                    raise ValueError(f"PolicySet: member {g} has {what} = {getattr(p, what)!r}, member 0 has {getattr(first, what)!r}: "
+                                     "the members of a set share one architecture")
+        rows = sum(sizes) if num_rows is None else int(num_rows)
+        group_tile_table(rows, sizes)
+        self.policies, self.group_sizes, self.num_rows = policies, sizes, rows
+        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self.group_slices = [slice(int(starts[g]), int(starts[g + 1])) for g in range(len(sizes))]
+        self.backend = backend
+        self.noise_seed = int(first.noise_seed if noise_seed is None else noise_seed)
+        self.noise_env_offset = 0
+        self._calls = 0
+        self._hip, self._hip_critic = {}, {}
+        self.pi_arch, self.vf_arch, self.activation = list(first.pi_arch), list(first.vf_arch), first.activation
+
+    def __len__(self):
+        return len(self.policies)
+
+    def __getitem__(self, g):
+        return self.policies[g]
+
+    def __iter__(self):
+        return iter(self.policies)
+
+    @property
+    def has_critic(self):
+        return all(p.has_critic for p in self.policies)
+
+    @property
+    def shipped_arch(self):
+        return self.policies[0].shipped_arch
+
+    def to(self, *args, **kwargs):
+        """The member modules moved as ``torch.nn.Module.to`` moves them (the HIP handles live on the device of the rows they are given)."""
+        self.policies = [p.to(*args, **kwargs) for p in self.policies]
+        return self
+
+    # ------------------------------------------------------------------------------------------------ handles
+    def _create_handle(self, prefix, arch, idx):
+        """rdv_policy_set_create / rdv_critic_set_create from the members' modules."""
+        from . import _native as N
+        host = [p._host_layers(prefix) for p in self.policies]        # kept alive until the call returns
+        n_layers = len(arch) + 1
+        wps = [(C.c_void_p * n_layers)(*[t.data_ptr() for t in ws]) for ws, _, _ in host]
+        bps = [(C.c_void_p * n_layers)(*[t.data_ptr() for t in bs]) for _, bs, _ in host]
+        P = len(host)
+        wpp = (C.c_void_p * P)(*[C.addressof(a) for a in wps])
+        bpp = (C.c_void_p * P)(*[C.addressof(a) for a in bps])
+        spec = N.MlpSpec.make(arch, ACTIVATIONS[self.activation][0])
+        N.check(N.lib().rdv_mlp_spec_check(C.byref(spec)))
+        sizes = (C.c_int64 * P)(*self.group_sizes)
+        h = C.c_void_p()
+        if prefix == "l":
+            lsp = (C.c_void_p * P)(*[ls[0].data_ptr() for _, _, ls in host])
+            N.check(N.lib().rdv_policy_set_create(C.byref(spec), P, sizes, wpp, bpp, lsp, idx, C.byref(h)))
+        else:
+            N.check(N.lib().rdv_critic_set_create(C.byref(spec), P, sizes, wpp, bpp, idx, C.byref(h)))
+        return h
+
+    def _hip_handle(self, device):
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if idx not in self._hip:
+            self._hip[idx] = self._create_handle("l", self.pi_arch, idx)
+        return self._hip[idx]
+
+    def _critic_handle(self, device):
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        if idx not in self._hip_critic:
+            self._hip_critic[idx] = self._create_handle("v", self.vf_arch, idx)
+        return self._hip_critic[idx]
+
+    def _check_rows(self, n, what):
+        if n != self.num_rows:
+            raise ValueError(f"{what}: {n} rows, the policy set owns {self.num_rows}")
+
+    # ------------------------------------------------------------------------------------------------ evaluation
+    @torch.no_grad()
+    def act(self, obs, deterministic=True, generator=None, out=None, env_id_offset=None):
+        """``MlpPolicy.act`` for the set: rows ``group_slices[g]`` of ``obs`` [n,17] through member g.  HIP: ONE launch
+        (rdv_policy_act on the set handle), the noise of row i keyed by (noise_seed, env_id_offset + i, call counter).  CPU rows or
+        ``backend="torch"``: the members' modules on their slices."""
+        hip = self.backend == "hip" or (self.backend == "auto" and obs.is_cuda and obs.dtype == torch.float32
+                                        and obs.dim() == 2 and obs.shape[1] == 17)
+        self._check_rows(int(obs.shape[0]), "act")
+        if hip:
+            from . import _native as N
+            if generator is not None:
+                self.noise_seed = int(generator.initial_seed())
+            offset = self.noise_env_offset if env_id_offset is None else int(env_id_offset)
+            obs = obs.contiguous()
+            n = obs.shape[0]
+            if out is None:
+                out = torch.empty((n, 6), dtype=torch.float32, device=obs.device)
+            stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
+            N.check(N.lib().rdv_policy_act(self._hip_handle(obs.device), C.c_void_p(obs.data_ptr()), C.c_void_p(out.data_ptr()), n,
+                                           int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls),
+                                           C.c_uint64(offset), stream))
+            self._calls += 1
+            return out
+        parts = [p.act(obs[s], deterministic=deterministic, generator=generator) for p, s in zip(self.policies, self.group_slices)]
+        res = torch.cat(parts, dim=0)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+
+    def _value_torch(self, obs):
+        """The members' critics (PyTorch modules) on observations [..., n, 17], each on its columns."""
+        return torch.cat([p._value_torch(obs[..., s, :]) for p, s in zip(self.policies, self.group_slices)], dim=-1)
+
+    @torch.no_grad()
+    def value(self, obs, out=None):
+        """The critics' values for observations [..., n, 17], n the set's rows: column i of every leading index through the member that
+        owns row i.  HIP: one launch over all row blocks (rdv_policy_value on the critic set handle)."""
+        if obs.dim() < 2 or obs.shape[-1] != 17:
+            raise ValueError(f"value: expected [..., n, 17] observations, got {tuple(obs.shape)}")
+        self._check_rows(int(obs.shape[-2]), "value")
+        shape = obs.shape[:-1]
+        if self.backend != "torch" and obs.is_cuda and obs.dtype == torch.float32:
+            from . import _native as N
+            flat = obs.reshape(-1, 17).contiguous()
+            if out is None:
+                out = torch.empty((flat.shape[0],), dtype=torch.float32, device=flat.device)
+            stream = C.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream)
+            N.check(N.lib().rdv_policy_value(self._critic_handle(flat.device), C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
+                                             flat.shape[0], stream))
+            return out.reshape(shape)
+        return self._value_torch(obs)
+
+    @torch.no_grad()
+    def advantages(self, ro, gamma=0.99, gae_lambda=0.95, out=None):
+        """``MlpPolicy.advantages`` for the set: ``values``, ``last_value``, ``advantages`` and ``returns`` of the rows ``ro``, env i
+        through the critic of the member that owns it; the same buffer reuse.  CUDA rows: rdv_rollout_advantages on the critic set
+        handle (two critic launches over all members and the GAE kernel)."""
+        if isinstance(ro.get("obs"), torch.Tensor) and ro["obs"].dim() == 3 and self.has_critic:
+            self._check_rows(int(ro["obs"].shape[1]), "advantages")
+        return _advantages(self, ro, gamma, gae_lambda, out)
+
+    # ------------------------------------------------------------------------------------------------ weights
+    def update_weights(self, member=None, weights=None):
+        """New weights for one member (``member`` = its index; ``weights``: a dict as ``MlpPolicy.update_weights`` takes, or None to
+        push the member module's current parameters) or for all members (``member`` None; ``weights``: None or a list of one dict or
+        None per member).  Dicts are loaded into the member modules first; then every live set handle is refreshed member by member
+        through rdv_policy_set_member_weights on the current stream of its device: launches already queued there use the old weights,
+        later ones the new, and the other members' blocks are not touched.  Not legal while the current stream is being captured
+        (RdvError, nothing touched).  The noise key and the call counter are unchanged."""
+        P = len(self.policies)
+        if (self._hip or self._hip_critic) and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            # refused before a module or a host copy is touched (either would invalidate the capture); the library refuses the same way
+            from . import _native as N
+            raise N.RdvError(-1, "rdv_policy_set_member_weights: not legal inside a stream capture (the staging buffer is reused by the next call)")
+        if member is None:
+            todo = list(range(P))
+            per = weights if weights is not None else [None] * P
+            if isinstance(per, dict) or len(per) != P:
+                raise ValueError(f"update_weights: weights for all members is a list of {P} dicts (or None); pass member= for one")
+        else:
+            member = int(member)
+            if not 0 <= member < P:
+                raise IndexError(f"update_weights: member {member} of {P}")
+            todo, per = [member], {member: weights}
+        for g in todo:
+            if per[g] is not None:
+                self.policies[g]._load_weights(per[g])
+        if not (self._hip or self._hip_critic):
+            return
+        from . import _native as N
+        for prefix, handles in (("l", self._hip), ("v", self._hip_critic)):
+            if not handles:
+                continue
+            for g in todo:
+                ws, bs, log_std = self.policies[g]._host_layers(prefix)
+                wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+                bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
+                for idx, h in handles.items():
+                    stream = C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)
+                    N.check(N.lib().rdv_policy_set_member_weights(h, g, wp, bp, C.c_void_p(log_std[0].data_ptr()) if log_std else None, stream))
+
+    def close(self):
+        if self._hip or self._hip_critic:
+            from . import _native as N
+            for h in list(self._hip.values()) + list(self._hip_critic.values()):
+                N.lib().rdv_policy_destroy(h)
+            self._hip, self._hip_critic = {}, {}
