@@ -63,6 +63,8 @@ extern "C" {
 #define RDV_ACT_DIM 6     /* rendezvous_env.py:140-144 */
 #define RDV_STATE_DIM 20  /* rc3 vc3 qc4 wc3 qt4 wt3, the column order of results/data_monte_carlo_initial_conditions.csv */
 #define RDV_DIAG_DIM 8    /* pos_err, vel_err, att_err, rot_err, in_koz(now), success(now), dist_from_koz, collided(latched) */
+/* (the three norms are evaluated in the order get_errors() :451-468 evaluates them under NumPy, so they are its numbers to 2 ulp also beside a
+ * turned target; the flags come from the kernels' own sums of squares against the host-derived limits) */
 #define RDV_EVAL_DIM 32   /* per-env evaluation accumulators, see rdv_eval_begin */
 
 typedef enum RdvError {
@@ -72,7 +74,7 @@ typedef enum RdvError {
   RDV_ERR_HIP = -3,            /* a HIP runtime call failed; see rdv_last_error() */
   RDV_ERR_OUT_OF_MEMORY = -4,
   RDV_ERR_BAD_HANDLE = -5,
-  RDV_ERR_BAD_PARAMS = -6,     /* violates an assert of the reference ctor (rendezvous_env.py:148-156) */
+  RDV_ERR_BAD_PARAMS = -6,     /* violates an assert of the reference ctor (rendezvous_env.py:148-156), or dt is not a multiple of 1 ms */
   RDV_ERR_DEVICE_FAULT = -7    /* a kernel of this handle reported a fault in its device error word (RdvDeviceError); the handle's
                                   results since then are not to be trusted.  Sticky: once a synchronising call (below) has read the
                                   word, every call that launches work on the handle or reads its state returns this code — rdv_reset,
@@ -137,7 +139,7 @@ typedef struct RdvParams {
   double wc0_range;             /* :63 [rad/s] */
   double qt0_range;             /* :64 [rad]   */
   double wt0_range;             /* :65 [rad/s] */
-  double dt;                    /* :69 */
+  double dt;                    /* :69; a multiple of 0.001 s (dt == rint(dt*1e3)/1e3): the reference's round(t + dt, 3) (:193) follows k*dt only then, any other is refused */
   double t_max;                 /* :70 */
   double max_delta_v;           /* :81 */
   double max_delta_w;           /* :82 */

@@ -221,6 +221,9 @@ class OracleBatch:
         self.L = lib()
         self.n = int(n)
         self.params = params if params is not None else default_params()
+        msg = C.create_string_buffer(512)
+        if self.L.orc_params_validate(C.byref(self.params), msg, C.c_int(len(msg))):
+            raise ValueError(msg.value.decode())
         self.envs = np.zeros(self.n, ENV_DTYPE)
         self.rigid = rigid      # OrcRigidBody: general inertia / torque, integrated with RK45 (INTEGRATOR_GENERAL)
         if rigid is not None:

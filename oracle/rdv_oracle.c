@@ -23,6 +23,7 @@
 #include "rdv_oracle.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 #ifdef _OPENMP
 #include <omp.h>
@@ -94,6 +95,14 @@ void orc_params_default(OrcParams* p) {
   const double ro = Re + h;                  /* :125 */
   p->n = sqrt(mu / (ro * ro * ro));          /* :126 */
   p->collision_coef = 0.5; p->bonus_coef = 8.0; p->fuel_coef = 0.2; p->att_coef = 1.0; /* :313 */
+}
+
+int orc_params_validate(const OrcParams* p, char* msg, int cap) {
+  if (p->dt == rint(p->dt * 1e3) / 1e3) return 0;
+  if (msg && cap > 0)
+    snprintf(msg, (size_t)cap, "dt = %.17g s is not a multiple of 0.001 s: the reference's round(t + dt, 3) drifts for such a dt "
+                               "(its running sum leaves round(k*dt, 3)), so episode times and the time limit would differ", p->dt);
+  return -6;
 }
 
 /* ---------------------------------------------------------------- Philox4x32-10 (Salmon et al. 2011, public algorithm) */
@@ -467,7 +476,8 @@ void orc_diagnose(const OrcParams* p, const OrcEnv* e, double diag[8]) {
 }
 
 static double env_time(const OrcParams* p, const OrcEnv* e) {
-  /* :193 t = round(t + dt, 3) every step == the decimal k*dt rounded to 3 places */
+  /* :193 t = round(t + dt, 3) every step == the decimal k*dt rounded to 3 places, for a dt that is a multiple of 1 ms
+   * (orc_params_validate refuses any other: there the reference's running sum drifts; tests/golden/thresholds_reference.npz) */
   return rint((double)e->k * p->dt * 1e3) / 1e3;
 }
 

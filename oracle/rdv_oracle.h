@@ -106,6 +106,11 @@ typedef struct OrcStepOut {
 
 int  orc_version(void);
 void orc_params_default(OrcParams* p);
+/* The one refusal the oracle shares with rdv_params_validate: a dt that is not a multiple of 0.001 s (as a double: dt == rint(dt*1e3)/1e3).
+ * The reference's t = round(t + dt, 3) (:193) follows the decimal k*dt only for such a dt; for any other its running sum drifts, and
+ * neither env_time() below nor the kernels' step count would be the reference's clock.  0: accepted; -6 (the value of
+ * RDV_ERR_BAD_PARAMS) with the reason in msg[0..cap). */
+int orc_params_validate(const OrcParams* p, char* msg, int cap);
 
 /* 24 uniforms in (0,1) for (seed, global env id, episode): Philox4x32-10, 4 blocks, 21 bits per uniform. */
 void orc_philox_uniforms(uint64_t seed, uint64_t env_id, uint32_t episode, double u[24]);

@@ -914,9 +914,48 @@ __device__ __forceinline__ void step_env(const DevParams& P, Env& e, const float
   step_env_finish<ST, kLazy, kGeneral>(P, e, r, d, c, sink);
 }
 
+// get_errors (:451-468) evaluated in the reference's own order — evaluator-only.  The DECISIONS compare d.pos2 / vel2 / rot2, which
+// derive_* form with a reciprocal square root and fused multiply-adds: each entry of R(q) is within an ulp of NumPy's, but
+// |rc - R(qt) rd| cancels (3 - 2 cos(phi) ~ 1 beside a turned target), so the norm lands 3-4 ulp from the one get_errors() returns.
+// What the evaluator REPORTS is the drop-in for get_errors(), so it takes NumPy's route: q / |q| by division (quaternions.py:57), the
+// matrix entries and the 3x3 products as rounded products and sums, and np.linalg.norm's chain of fused multiply-adds (the oracle's
+// norm3) — bit for bit what oracle/rdv_oracle.c computes from the same state (tests/golden/thresholds_reference.npz, angle rows).
+__device__ __forceinline__ void quat2mat_reported(const double* q, double* m) {
+#pragma clang fp contract(off)
+  const double mag = sqrt(fma(q[3], q[3], fma(q[2], q[2], fma(q[1], q[1], q[0] * q[0]))));
+  const double qw = q[0] / mag, qx = q[1] / mag, qy = q[2] / mag, qz = q[3] / mag;
+  m[0] = 2 * (qw * qw + qx * qx) - 1; m[1] = 2 * (qx * qy - qw * qz);     m[2] = 2 * (qx * qz + qw * qy);
+  m[3] = 2 * (qx * qy + qw * qz);     m[4] = 2 * (qw * qw + qy * qy) - 1; m[5] = 2 * (qy * qz - qw * qx);
+  m[6] = 2 * (qx * qz - qw * qy);     m[7] = 2 * (qy * qz + qw * qx);     m[8] = 2 * (qw * qw + qz * qz) - 1;
+}
+__device__ __forceinline__ void matvec_reported(const double* m, const double* v, double* o) {
+#pragma clang fp contract(off)
+  o[0] = m[0] * v[0] + m[1] * v[1] + m[2] * v[2];
+  o[1] = m[3] * v[0] + m[4] * v[1] + m[5] * v[2];
+  o[2] = m[6] * v[0] + m[7] * v[1] + m[8] * v[2];
+}
+__device__ __forceinline__ void reported_errors(const DevParams& P, const Env& e, double& pos, double& vel, double& rot) {
+#pragma clang fp contract(off)
+  double R[9], wc_l[3], wt_l[3], rd_l[3];
+  quat2mat_reported(e.qc, R);
+  matvec_reported(R, e.wc, wc_l);                       // :458
+  quat2mat_reported(e.qt, R);
+  matvec_reported(R, e.wt, wt_l);                       // :459
+  matvec_reported(R, P.rd, rd_l);                       // :460
+  const double vd_l[3] = {wt_l[1] * rd_l[2] - wt_l[2] * rd_l[1], wt_l[2] * rd_l[0] - wt_l[0] * rd_l[2],
+                          wt_l[0] * rd_l[1] - wt_l[1] * rd_l[0]};                                       // :461
+  const double dp[3] = {e.rc[0] - rd_l[0], e.rc[1] - rd_l[1], e.rc[2] - rd_l[2]};
+  const double dv[3] = {e.vc[0] - vd_l[0], e.vc[1] - vd_l[1], e.vc[2] - vd_l[2]};
+  const double dw[3] = {wc_l[0] - wt_l[0], wc_l[1] - wt_l[1], wc_l[2] - wt_l[2]};
+  pos = sqrt(fma(dp[2], dp[2], fma(dp[1], dp[1], dp[0] * dp[0])));                                      // :463
+  vel = sqrt(fma(dv[2], dv[2], fma(dv[1], dv[1], dv[0] * dv[0])));                                      // :464
+  rot = sqrt(fma(dw[2], dw[2], fma(dw[1], dw[1], dw[0] * dw[0])));                                      // :466
+}
+
 // diagnostics row (RDV_DIAG_DIM = 8) — evaluator-only
 __device__ __forceinline__ void diagnostics(const DevParams& P, const Env& e, const Derived& d, double* out) {
-  out[0] = sqrt(d.pos2); out[1] = sqrt(d.vel2); out[2] = angle_of(d.k_att); out[3] = sqrt(d.rot2);
+  reported_errors(P, e, out[0], out[1], out[3]);
+  out[2] = angle_of(d.k_att);
   out[4] = in_koz(P, d) ? 1.0 : 0.0;
   out[5] = (!(e.flags & FLAG_COLLIDED) && errors_ok(P, d)) ? 1.0 : 0.0;    // check_success (:406-422)
   out[6] = dist_from_koz(P, d);

@@ -150,7 +150,8 @@ static void derive_params(const RdvParams& p, DevParams& d) {
   d.max_delta_v_f32 = (float)p.max_delta_v;
   d.fuel_scale_f32 = (float)(p.dt * p.fuel_coef);
   d.fuel_div_f32 = (float)(3 * p.max_delta_v);
-  {  // :193 t = round(t + dt, 3), :368 t >= t_max  ->  first step count whose rounded time reaches t_max
+  {  // :193 t = round(t + dt, 3), :368 t >= t_max  ->  first step count whose rounded time reaches t_max (dt is a multiple of 1 ms:
+     // rdv_params_validate; then the running sum IS rint(k*dt*1e3)/1e3, tests/golden/thresholds_reference.npz)
     long long k = (long long)std::floor(p.t_max / p.dt) - 3;
     if (k < 0) k = 0;
     while (k < 2147483647LL && std::rint((double)k * p.dt * 1e3) / 1e3 < p.t_max) ++k;
@@ -408,6 +409,12 @@ int rdv_params_validate(const RdvParams* p) {
   if (!(p->dt > 0) || !(p->n > 0) || !(p->max_axial_distance > 0) || !(p->max_axial_speed > 0) || !(p->max_wc > 0) ||
       !(p->max_attitude_error > 0) || !(p->max_rd_error > 0) || !(p->max_qd_error > 0) || !(p->max_delta_v > 0))
     return fail(RDV_ERR_BAD_PARAMS, "dt, n, the observation scales and the error limits must be positive");
+  // :193 t = round(t + dt, 3).  For dt = j/1000 (as a double) every running sum rounds to the decimal k*j/1000, which is what k_time and
+  // the reported t assume (derive_params); for any other dt the reference's sum drifts away from round(k*dt, 3) — 1/3 s reaches
+  // t_max = 60 on step 181, 0.0125 s reaches 5 on step 398 — so such a dt is refused, not stepped on another clock than the reference's.
+  if (!(p->dt == std::rint(p->dt * 1e3) / 1e3))
+    return fail(RDV_ERR_BAD_PARAMS, "dt = %.17g s is not a multiple of 0.001 s: the reference's round(t + dt, 3) drifts for such a dt "
+                                    "(its running sum leaves round(k*dt, 3)), so episode times and the time limit would differ", p->dt);
   return RDV_OK;
 }
 

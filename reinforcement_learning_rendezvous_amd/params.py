@@ -87,6 +87,10 @@ def make_params(rc0=None, vc0=None, qc0=None, wc0=None, qt0=None, wt0=None,
     )
     p.dt = 1 if dt is None else dt                                          # :69
     p.t_max = 120 if t_max is None else t_max                               # :70
+    if math.isfinite(p.dt) and p.dt != round(p.dt * 1e3) / 1e3:
+        # :193 t = round(t + dt, 3) follows the decimal k*dt only for such a dt (rdv_params_validate gives the same refusal)
+        raise ValueError(f"dt = {p.dt!r} s is not a multiple of 0.001 s: the reference's round(t + dt, 3) drifts for such a dt "
+                         "(its running sum leaves round(k*dt, 3)), so episode times and the time limit would differ")
     p.max_delta_v = 10 / MASS * 0.5                                         # :81
     p.max_delta_w = 0.2 / INERTIA * 0.5                                     # :82 (0.5 s is hard-coded, independent of dt)
     p.max_axial_distance = float(np.linalg.norm(rc0)) + 10                  # :85
