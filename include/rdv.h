@@ -236,7 +236,8 @@ int rdv_destroy(rdv_handle h);
  * The new block is written by a kernel enqueued on `stream`: ordered like a step (launches already on that stream see the old
  * values, later ones the new), legal inside a stream capture, no host synchronisation.  Behind it, on `stream` too, a clear of the
  * tags of the prepared next-episode states (n_envs x 4 bytes): the persistent kernels, also those of graphs recorded earlier, then
- * refill every env's prepared state from the new block before its first use. */
+ * refill every env's prepared state from the new block before its first use.  A change of dt inside an episode is not defined (the
+ * reference keeps t across it, the library the step count): follow a set with another dt by a full rdv_reset. */
 int rdv_set_params(rdv_handle h, const RdvParams* params_host, void* stream);
 int rdv_get_params(rdv_handle h, RdvParams* out_host);
 /* Re-key the reset RNG (VecEnv.seed()).  Episode counters restart at 0. */

@@ -338,8 +338,10 @@ class RendezvousBatch:
         """An independent batch in the same state — what ``copy.deepcopy(env)`` gives the reference (utils/environment_utils.py:66-73;
         main.py:83 makes its ``eval_env`` that way): same parameters, rigid bodies, seed, reset tape and kernel variant; state,
         bookkeeping, episode counters and statistics through ``snapshot`` / ``restore``.  The two share nothing afterwards."""
-        other = RendezvousBatch(self.num_envs, params=self.group_params or self.params, group_sizes=self.group_sizes, device=self.device,
-                                seed=self._seed, env_id_offset=self.env_id_offset, **self._ctor)
+        other = RendezvousBatch(self.num_envs, params=self.params, device=self.device, seed=self._seed, env_id_offset=self.env_id_offset,
+                                **self._ctor)
+        if self.group_params is not None:     # the single block stays the original's: it is what ungrouping returns to
+            other.set_param_groups(self.group_params, self.group_sizes)
         body = self.get_rigid_body()
         other.set_rigid_body(inertia=body["inertia"], inertia_target=body["inertia_target"], torque=body["torque"],
                              torque_target=body["torque_target"], integrator=body["integrator"], rtol=body["rtol"], atol=body["atol"])

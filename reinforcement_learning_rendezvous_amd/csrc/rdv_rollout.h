@@ -130,7 +130,9 @@ __global__ __launch_bounds__(kRollBlock) void rollout_kernel(const DevParams* __
   const SlotStore<ST> H = hbm_slot_store<ST>(A.prep);   // the slots in HBM
   uint64_t* my_stats = stat_lds + (wv & (kRollEnvWaves - 1)) * kStatWords;
   if (env_role) {
-    if (lane < kStatWords) my_stats[lane] = 0ull;
+    // the rollout's statistics continue the wave's slot in HBM (read here, written back at the end): every step's sums are added to the
+    // running sums one by one, in the order of the rdv_step loop (rdv_step_many.h); words 12..15 start at zero (refills_done is word 15)
+    if (lane < kStatWords) my_stats[lane] = (i - lane < n && lane < 12) ? A.stats[(uint64_t)((i - lane) / kWave) * kStatWords + lane] : 0ull;
     __builtin_amdgcn_s_setprio(2);   // the env wave is the one fp64 dependency chain of its SIMD
     float o[RDV_OBS_DIM];
 #pragma unroll
@@ -398,13 +400,8 @@ __global__ __launch_bounds__(kRollBlock) void rollout_kernel(const DevParams* __
       slot_copy<ST>(H, i_e, L, sl_e);
       A.prep_tag[i_e] = e.episode + 1u;
     }
-    if (rows_e > 0 && ln_e < 12) {   // this wave's statistics slot in HBM += the rollout's (counters as integers, sums as fp64)
-      uint64_t* slot_stats = A.stats + (uint64_t)(wb_e / kWave) * kStatWords;
-      const uint64_t pre = slot_stats[ln_e], add = my_stats[ln_e];
-      const uint64_t as_int = pre + add;
-      const uint64_t as_real = (uint64_t)__double_as_longlong(__longlong_as_double((long long)pre) + __longlong_as_double((long long)add));
-      slot_stats[ln_e] = ln_e <= ST_SUM_LEN ? as_int : as_real;
-    }
+    if (rows_e > 0 && ln_e < 12)     // this wave's statistics slot in HBM: what it held at entry plus the rollout's steps, one by one
+      A.stats[(uint64_t)(wb_e / kWave) * kStatWords + ln_e] = my_stats[ln_e];
   }
 }
 

@@ -85,7 +85,9 @@ __global__ __launch_bounds__(kManyBlock) void step_many_kernel(const DevParams* 
     __builtin_amdgcn_s_setprio(2);
     float* my_obs = obs_rows + (slot - lane) * RDV_OBS_DIM;
     uint64_t* my_stats = stat_lds + wv * kStatWords;
-    if (lane < kStatWords) my_stats[lane] = 0ull;
+    // the launch's statistics continue the wave's slot in HBM (read here, written back at the end), so that every step's sums are added
+    // to the running sums one by one, in the order of the rdv_step loop: slot + (s1 + s2) differs from (slot + s1) + s2 in the last bit
+    if (lane < kStatWords) my_stats[lane] = (rows > 0 && lane < 12) ? A.stats[(uint64_t)(wave_base / kWave) * kStatWords + lane] : 0ull;
     const SlotStore<ST> H = hbm_slot_store<ST>(A.prep);   // the slots in HBM
     Env e;
     e.episode = 0u;
@@ -165,13 +167,8 @@ __global__ __launch_bounds__(kManyBlock) void step_many_kernel(const DevParams* 
         A.prep_tag[i] = e.episode + 1u;
       }
     }
-    if (rows > 0 && lane < 12) {   // this wave's statistics slot in HBM += the launch's (counters as integers, sums as fp64)
-      uint64_t* slot_stats = A.stats + (uint64_t)(wave_base / kWave) * kStatWords;
-      const uint64_t pre_s = slot_stats[lane], add = my_stats[lane];
-      const uint64_t as_int = pre_s + add;
-      const uint64_t as_real = (uint64_t)__double_as_longlong(__longlong_as_double((long long)pre_s) + __longlong_as_double((long long)add));
-      slot_stats[lane] = lane <= ST_SUM_LEN ? as_int : as_real;
-    }
+    if (rows > 0 && lane < 12)     // this wave's statistics slot in HBM: what it held at entry plus the launch's steps, one by one
+      A.stats[(uint64_t)(wave_base / kWave) * kStatWords + lane] = my_stats[lane];
   } else if (resets) {
     // ------------------------------------------------------------------ service waves
     const int role = wv - kManyEnvWaves;

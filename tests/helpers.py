@@ -99,7 +99,7 @@ def counter_actions(seed, step, n, lo=0):
 SPLIT_AUTO_MAX_ENVS = 65536      # include/rdv.h: AUTO runs SPLIT up to one 256-env workgroup per CU, FUSED above
 
 
-def expected_kernel(variant, n, storage, on_done, diag=False, tape=False, after_set_state=False):
+def expected_kernel(variant, n, storage, on_done, diag=False, tape=False, after_set_state=False, groups=False, general=None):
     """The step kernel rdv_step launches, from the dispatch rules as include/rdv.h documents them (not from the C++):
       - the first step after rdv_set_state / rdv_restore: the kRaw instantiation of step_kernel (it renormalises the quaternions);
       - diag or eval outputs: the evaluator build step_kernel<ST, true>, whatever the variant;
@@ -107,8 +107,22 @@ def expected_kernel(variant, n, storage, on_done, diag=False, tape=False, after_
       - SPLIT: step_kernel_split, FUSED: step_kernel_parts, both <ST, true> unless halt mode (<ST, false>: halted envs skip the step);
       - FUSED_INLANE: step_kernel<ST, false>;
       - FUSED_TILES: step_kernel_tiles<ST>, except with a reset tape or in halt mode, where it runs FUSED.
+    In front of all of these:
+      - ``groups`` (a grouped handle, rdv.h "Which kernel runs"): step_kernel_groups<ST, all> whichever variant was asked for (all: not
+        halt mode), step_kernel_groups_lane<ST, diag, raw> for the evaluator build and the first step after rdv_set_state / rdv_restore;
+      - ``general`` (a general rigid body; rdv.h: such a handle runs the in-lane layout; the names are the table of tests/rigid_cases.py):
+        "target" — the target is integrated with RK45 (its own tensor or torque, or RK45 forced) — runs step_kernel_general<ST>, "chaser"
+        (the chaser only) and every evaluator build step_kernel<ST, diag, true>; there is no raw build (the RK45 kernels integrate
+        the quaternion as given).
     ``rdv_debug_last_kernel`` spells the names as the instantiations are written."""
     st = "float" if storage in ("f32", 0) else "double"
+    b = lambda x: "true" if x else "false"
+    if groups:
+        if diag or after_set_state:
+            return f"step_kernel_groups_lane<{st}, {b(diag)}, {b(after_set_state)}>"
+        return f"step_kernel_groups<{st}, {b(on_done != 'halt')}>"
+    if general:
+        return f"step_kernel_general<{st}>" if general == "target" and not diag else f"step_kernel<{st}, {b(diag)}, true>"
     if after_set_state:
         return f"step_kernel<{st}, {'true' if diag else 'false'}, false, true>"
     if diag:
@@ -139,7 +153,12 @@ def expect_kernel(env, variant, diag=False, tape=False, after_set_state=False, w
     assert env.last_kernel == want, f"{what}: ran {env.last_kernel!r}, the dispatch rules say {want!r}"
 
 
-def persistent_kernel(which, storage):
-    """rdv_step_many / rdv_rollout (reference rigid bodies): one persistent kernel each."""
+def persistent_kernel(which, storage, n_steps=None, **step):
+    """rdv_step_many / rdv_rollout (reference rigid bodies, no groups): one persistent kernel each.  With ``groups`` or ``general`` in
+    ``step`` (the keywords of expected_kernel, with variant, n and on_done) the call runs the loop it is defined by, and the name is that
+    of the last rdv_step of ``n_steps``: the raw build only where the first step is the last."""
     st = "float" if storage in ("f32", 0) else "double"
+    if step.get("groups") or step.get("general"):
+        step["after_set_state"] = bool(step.get("after_set_state")) and n_steps == 1
+        return expected_kernel(storage=storage, **step)
     return f"{'step_many_kernel' if which == 'step_many' else 'rollout_kernel'}<{st}, false>"

@@ -1,36 +1,167 @@
-"""Test-only adapter: the CPU oracle behind the engine interface of RendezvousBatch (torch CPU tensors in/out).
+"""Test-only adapters of the CPU oracle.
 
-It lets the product's host logic (Monte Carlo driver, VecEnv, sharding) be exercised without a GPU.  It lives under
-tests/ on purpose: the product never imports the oracle.
+OracleModel: the stateless-engine model of a handle (NumPy in/out).  It is always a list of OracleBatch parts, one per 256-env tile,
+each with its own parameters and env_id_offset, so that parameter groups (whose boundaries are tile boundaries, include/rdv.h) are an
+assignment of parameters to parts and nothing else.  It draws every reset when it happens and keeps no prepared states, flags or
+tags: what tests/call_sequences.py compares a handle's call sequences with.
+
+OracleEngine: the model behind the engine interface of RendezvousBatch (torch CPU tensors in/out).  It lets the product's host logic
+(Monte Carlo driver, VecEnv, sharding) be exercised without a GPU.
+
+GroupedOracle: one OracleBatch per group, what tests/test_gpu_param_groups.py steps.
+
+All live under tests/ on purpose: the product never imports the oracle.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
+import oracle
 from helpers import oracle_batch, to_numpy, to_oracle_params
+from reinforcement_learning_rendezvous_amd.params import GROUP_TILE, group_tile_table
 
 
-class OracleEngine:
-    def __init__(self, num_envs, params, storage="f64", on_done="reset", seed=0, env_id_offset=0, n_threads=1,
-                 numpy_legacy=False, tape=None, rigid=None):
-        self.num_envs = int(num_envs)
-        self.params = params.copy()
-        self.device = torch.device("cpu")
-        self._ctor = dict(storage=storage, on_done=on_done)          # as RendezvousBatch records them (helpers.batch_modes)
-        self._orc = oracle_batch(
-            self.num_envs, params, storage, on_done,
-            seed=seed, env_id_offset=env_id_offset, n_threads=n_threads, numpy_legacy=numpy_legacy, rigid=rigid,
-            **({} if tape is None else {"tape": np.asarray(tape, dtype=np.float64)}))      # reset tape [depth, N, 20]: recorded initial states
-        self._orc_halts = on_done == "halt"
-        self.obs = self.reward = self.done = None
-        self.terminal_obs = self.episode_return = self.episode_length = self.done_reason = self.diag = None
-        self.eval = None
-        self._halted = np.zeros(self.num_envs, dtype=bool)
+def rigid_from_kwargs(kw):
+    """The OrcRigidBody of RendezvousBatch.set_rigid_body's keyword arguments (all four of inertia, inertia_target, torque,
+    torque_target given), None where the handle would not be general: the constructor's bodies without a forced RK45."""
+    forced = kw.get("integrator", "auto") == "rk45"
+    closed = [oracle.OrcRigidBody.closed_form_applies(kw["inertia"], kw["torque"]),
+              oracle.OrcRigidBody.closed_form_applies(kw["inertia_target"], kw["torque_target"])]
+    if all(closed) and not forced:
+        return None
+    return oracle.OrcRigidBody.make(kw["inertia"], kw["inertia_target"], kw["torque"], kw["torque_target"],
+                                    integrator="rk45" if forced else "auto")
 
+
+def cpu_act(policy, obs, deterministic):
+    """policy.act on CPU observations with the noise keyed by (noise_seed, call counter), the counter advanced as the HIP actor does."""
+    g = torch.Generator().manual_seed(int(policy.noise_seed) * 1000003 + int(policy._calls))
+    policy._calls += 1
+    return policy.act(obs, deterministic=deterministic, generator=g)
+
+
+class OracleModel:
+    def __init__(self, n, params, storage="f64", on_done="reset", seed=0, env_id_offset=0, n_threads=1, numpy_legacy=False, tape=None,
+                 rigid=None):
+        self.n, self.storage, self.on_done = int(n), storage, on_done
+        self.env_id_offset, self._seed = int(env_id_offset), seed
+        self._kw = dict(n_threads=n_threads, numpy_legacy=numpy_legacy)
+        self.slices = [slice(s, min(s + GROUP_TILE, self.n)) for s in range(0, self.n, GROUP_TILE)]
+        self.params = params.copy()          # the single set: what rdv_create / rdv_set_params gave the handle last
+        self.groups = None                   # ([EnvParams per group], sizes) while grouped
+        self._tape, self._rigid = None, rigid
+        self.parts = [oracle_batch(s.stop - s.start, params, storage, on_done, seed=seed, env_id_offset=self.env_id_offset + s.start,
+                                   rigid=rigid, **self._kw) for s in self.slices]
+        self._acc = None
+        if tape is not None:
+            self.set_reset_tape(tape)
+
+    def _cat(self, f):
+        return np.concatenate([f(o) for o in self.parts])
+
+    # ---- episodes
     def reset(self, mask=None):
-        m = None if mask is None else np.asarray(mask.cpu().numpy(), dtype=np.uint8)
-        self.obs = torch.from_numpy(self._orc.reset(m))
-        self._halted[:] = False
-        return self.obs
+        m = None if mask is None else np.asarray(mask, dtype=np.uint8)
+        return np.concatenate([o.reset(None if m is None else np.ascontiguousarray(m[s])) for o, s in zip(self.parts, self.slices)])
+
+    def step(self, actions, want_diag=False, accumulate=False):
+        a = np.asarray(actions, dtype=np.float32)
+        want_diag = want_diag or accumulate
+        stepped = ~self.halted()
+        out = [o.step(np.ascontiguousarray(a[s]), want_diag=want_diag) for o, s in zip(self.parts, self.slices)]
+        r = {k: (np.concatenate([x[k] for x in out]) if out[0][k] is not None else None) for k in out[0]}
+        if accumulate:
+            self._eval_accumulate(r["diag"], np.asarray(r["reward"], dtype=np.float64), stepped, self.get_aux()[:, 0])
+        return r
+
+    def halted(self):
+        return self._cat(lambda o: o.envs["halted"] != 0)
+
+    # ---- state access
+    def set_state(self, states):
+        s = np.asarray(states, dtype=np.float64)
+        for o, sl in zip(self.parts, self.slices):
+            o.set_state(np.ascontiguousarray(s[sl]))
+
+    def get_state(self):
+        return self._cat(lambda o: o.get_state())
+
+    def get_aux(self):
+        return self._cat(lambda o: o.get_aux())
+
+    def observe(self):
+        return self._cat(lambda o: o.observe())
+
+    def diagnose(self):
+        return self._cat(lambda o: o.diagnose())
+
+    def get_stats(self, reset=False):
+        st = [o.get_stats(reset) for o in self.parts]
+        return {k: ([sum(x) for x in zip(*[s[k] for s in st])] if k == "reasons" else sum(s[k] for s in st)) for k in st[0]}
+
+    # ---- what changes a reset
+    def seed(self, seed):
+        self._seed = seed
+        for o in self.parts:
+            o.seed(seed)
+
+    def set_reset_tape(self, tape):
+        self._tape = None if tape is None else np.ascontiguousarray(tape, dtype=np.float64)
+        for o, s in zip(self.parts, self.slices):                       # indexed with the batch's env index: sliced per part
+            o.set_reset_tape(None if tape is None else np.ascontiguousarray(self._tape[:, s]))
+
+    def _assign(self, per_part):
+        for o, p in zip(self.parts, per_part):
+            o.params = to_oracle_params(p)
+
+    def set_params(self, params):
+        assert self.groups is None, "rdv_set_params is refused on a grouped handle"
+        self.params = params.copy()
+        self._assign([params] * len(self.parts))
+
+    def group_on(self, params, sizes):
+        assert self._rigid is None, "groups and a general body exclude each other"
+        table = group_tile_table(self.n, sizes)
+        self.groups = ([p.copy() for p in params], [int(x) for x in sizes])
+        self._assign([self.groups[0][g] for g in table])
+
+    def set_group_params(self, group, params):
+        self.groups[0][int(group)] = params.copy()
+        self._assign([self.groups[0][g] for g in group_tile_table(self.n, self.groups[1])])
+
+    def group_off(self):
+        self.groups = None
+        self._assign([self.params] * len(self.parts))
+
+    def set_rigid_body(self, rigid):
+        """rigid: an OrcRigidBody, or None for the constructor's bodies on the closed form."""
+        assert rigid is None or self.groups is None, "groups and a general body exclude each other"
+        self._rigid = rigid
+        for o in self.parts:
+            o.rigid = rigid
+            o.cfg.integrator = oracle.INTEGRATOR_EXACT if rigid is None else oracle.INTEGRATOR_GENERAL
+            o.cfg.rigid = None if rigid is None else C.addressof(rigid)
+
+    # ---- snapshot / restore / clone: the env records (they hold k, episode and halted) and the statistics
+    def snapshot(self):
+        return [o.envs.copy() for o in self.parts], [oracle.OrcStats.from_buffer_copy(bytes(o.stats)) for o in self.parts]
+
+    def restore(self, snap, stats=True):
+        for o, e, st in zip(self.parts, *snap):
+            o.envs[:] = e
+            if self.on_done != "halt":                                    # include/rdv.h: the halted flags mean something to HALT handles only
+                o.envs["halted"] = 0
+            if stats:
+                o.stats = oracle.OrcStats.from_buffer_copy(bytes(st))
+
+    def clone(self):
+        other = OracleModel(self.n, self.params, self.storage, self.on_done, seed=self._seed, env_id_offset=self.env_id_offset,
+                            tape=self._tape, rigid=self._rigid, **self._kw)
+        if self.groups is not None:
+            other.group_on(*self.groups)
+        other.restore(self.snapshot())
+        return other
 
     # ---- the per-env evaluation accumulators of the product (include/rdv.h, rdv_eval_begin), restated in NumPy from the oracle's
     # diagnostics: an independent statement of the same bookkeeping (custom_callbacks.py:211-267, monte_carlo.py:117-189)
@@ -40,9 +171,8 @@ class OracleEngine:
         return [pm & vm & am & rm, (pm & vm & am) | (pm & vm & rm), pm & vm, pm]
 
     def eval_begin(self):
-        d = self._orc.diagnose()
-        n = self.num_envs
-        acc = np.zeros((n, 32))
+        d = self.diagnose()
+        acc = np.zeros((self.n, 32))
         koz = d[:, 4] != 0
         acc[:, 2] = d[:, 2]; acc[:, 3] = koz
         acc[:, 4] = np.where(koz, 0.0, np.nan); acc[:, 5] = np.where(koz, np.nan, d[:, 0])
@@ -51,8 +181,7 @@ class OracleEngine:
             acc[hit, 12 + 5 * L] = 1.0
             acc[hit, 13 + 5 * L: 17 + 5 * L] = d[hit, 0:4]
         self._acc = acc
-        self.eval = torch.from_numpy(acc)
-        return self.eval
+        return acc
 
     def _eval_accumulate(self, d, reward, stepped, t_now):
         acc = self._acc
@@ -76,9 +205,9 @@ class OracleEngine:
 
     def eval_summary(self):
         acc, p = self._acc, self.params
-        aux, st = self._orc.get_aux(), self._orc.get_state()
+        aux, st = self.get_aux(), self.get_state()
         steps = aux[:, 0] / p.dt
-        m = self.num_envs
+        m = self.n
         nanmean = lambda x: -1.0 if np.all(np.isnan(x)) else float(np.nanmean(x))
         return {"ep_rew": acc[:, 0].mean(), "ep_len": aux[:, 0].mean(), "ep_dist": np.linalg.norm(st[:, 0:3], axis=1).mean(),
                 "ep_delta_v": aux[:, 4].mean(), "ep_delta_w": aux[:, 5].mean(), "ep_success": aux[:, 3].mean(),
@@ -86,14 +215,37 @@ class OracleEngine:
                 "ep_min_pos_error": nanmean(acc[:, 5]), "ep_avg_att_error": (acc[:, 2] / (steps + 1)).mean(),
                 "%_collided_episodes": float((acc[:, 3] > 0).sum()) / m * 100, "%_successfull_episodes": float((aux[:, 3] > 0).sum()) / m * 100}
 
+
+class OracleEngine:
+    def __init__(self, num_envs, params, storage="f64", on_done="reset", seed=0, env_id_offset=0, n_threads=1,
+                 numpy_legacy=False, tape=None, rigid=None, variant="auto"):
+        self.num_envs = int(num_envs)
+        self.params = params.copy()
+        self.device = torch.device("cpu")
+        self.env_id_offset = int(env_id_offset)
+        self._ctor = dict(storage=storage, on_done=on_done, variant=variant)   # as RendezvousBatch records them (helpers.batch_modes)
+        self._orc = OracleModel(self.num_envs, params, storage, on_done, seed=seed, env_id_offset=env_id_offset, n_threads=n_threads,
+                                numpy_legacy=numpy_legacy, rigid=rigid,
+                                tape=None if tape is None else np.asarray(tape, dtype=np.float64))   # reset tape [depth, N, 20]: recorded initial states
+        self.obs = self.reward = self.done = None
+        self.terminal_obs = self.episode_return = self.episode_length = self.done_reason = self.diag = None
+        self.eval = None
+
+    def reset(self, mask=None):
+        m = None if mask is None else np.asarray(mask.cpu().numpy(), dtype=np.uint8)
+        self.obs = torch.from_numpy(self._orc.reset(m))
+        return self.obs
+
+    def eval_begin(self):
+        self.eval = torch.from_numpy(self._orc.eval_begin())
+        return self.eval
+
+    def eval_summary(self):
+        return self._orc.eval_summary()
+
     def step(self, actions, diag=False, accumulate=False):
-        stepped = ~self._halted
         diag = diag or accumulate
-        r = self._orc.step(to_numpy(actions).astype(np.float32), want_diag=diag)
-        if self._orc_halts:
-            self._halted |= r["done"].astype(bool)
-        if accumulate:
-            self._eval_accumulate(r["diag"], np.asarray(r["reward"], dtype=np.float64), stepped, self._orc.get_aux()[:, 0])
+        r = self._orc.step(to_numpy(actions).astype(np.float32), want_diag=diag, accumulate=accumulate)
         self.obs = torch.from_numpy(r["obs"])
         self.reward = torch.from_numpy(r["reward"].astype(np.float32))
         self.done = torch.from_numpy(r["done"])
@@ -103,6 +255,31 @@ class OracleEngine:
         self.done_reason = torch.from_numpy(r["done_reason"])
         self.diag = torch.from_numpy(r["diag"]) if diag else None
         return self.obs, self.reward, self.done
+
+    def step_many(self, actions, out=None):
+        """RendezvousBatch.step_many as the loop it is defined by."""
+        rows = {k: [] for k in ("obs", "reward", "done", "done_reason")}
+        for a in actions:
+            self.step(a)
+            for k in rows:
+                rows[k].append(getattr(self, k))
+        return {k: torch.stack(v) for k, v in rows.items()}
+
+    def act(self, policy, deterministic=False, out=None):
+        return cpu_act(policy, self.obs, deterministic)
+
+    def rollout(self, policy, n_steps, deterministic=False, out=None):
+        """RendezvousBatch.rollout as the loop it is defined by (the actor sees the observation of the state as it stands)."""
+        rows = {k: [] for k in ("obs", "actions", "reward", "done")}
+        obs = self.observe()
+        for _ in range(int(n_steps)):
+            a = cpu_act(policy, obs, deterministic)
+            rows["obs"].append(obs); rows["actions"].append(a)
+            obs, r, d = self.step(a)
+            rows["reward"].append(r); rows["done"].append(d)
+        out = {k: torch.stack(v) for k, v in rows.items()}
+        out["last_obs"] = obs
+        return out
 
     def set_state(self, states):
         self._orc.set_state(to_numpy(states))
@@ -131,12 +308,81 @@ class OracleEngine:
 
     def set_params(self, params):
         self.params = params.copy()
-        self._orc.params = to_oracle_params(params)
+        self._orc.set_params(params)
 
     def set_reward_kwargs(self, **kw):
         p = self.params.copy()
         p.update(**kw)
         self.set_params(p)
 
+    def set_param_groups(self, params, group_sizes):
+        if len(params):
+            self._orc.group_on(params, group_sizes)
+        else:
+            self._orc.group_off()
+
+    def set_group_params(self, group, params):
+        self._orc.set_group_params(group, params)
+
+    def set_rigid_body(self, **kw):
+        """All four of inertia, inertia_target, torque, torque_target (and optionally integrator), as tests/call_sequences.py passes them."""
+        self._orc.set_rigid_body(rigid_from_kwargs(kw))
+
+    def set_kernel_variant(self, variant):
+        self._ctor["variant"] = variant
+
+    def snapshot(self):
+        return self._orc.snapshot()
+
+    def restore(self, snap):
+        self._orc.restore(snap)
+        self.obs = self.observe()
+
+    def clone(self):
+        other = object.__new__(type(self))
+        other.__dict__.update(self.__dict__)
+        other._ctor, other.params, other._orc = dict(self._ctor), self.params.copy(), self._orc.clone()
+        other.eval = None
+        return other
+
     def close(self):
         pass
+
+
+class GroupedOracle:
+    """One OracleBatch per group (its parameters, its env_id_offset) behind the surface of one: what tests/parity.py steps and reads."""
+
+    def __init__(self, params, sizes, storage, on_done, seed):
+        starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+        self.parts = [oracle_batch(int(m), p, storage, on_done, seed=seed, env_id_offset=int(s)) for p, s, m in zip(params, starts, sizes)]
+        self.slices = [slice(int(s), int(s + m)) for s, m in zip(starts, sizes)]
+
+    def _cat(self, f):
+        return np.concatenate([f(o) for o in self.parts])
+
+    def reset(self):
+        return self._cat(lambda o: o.reset())
+
+    def step(self, a, want_diag=False):
+        out = [o.step(np.ascontiguousarray(a[s]), want_diag=want_diag) for o, s in zip(self.parts, self.slices)]
+        return {k: np.concatenate([r[k] for r in out]) for k in out[0] if out[0][k] is not None}
+
+    def set_state(self, states):
+        for o, s in zip(self.parts, self.slices):
+            o.set_state(np.ascontiguousarray(states[s]))
+
+    def get_state(self):
+        return self._cat(lambda o: o.get_state())
+
+    def get_aux(self):
+        return self._cat(lambda o: o.get_aux())
+
+    def observe(self):
+        return self._cat(lambda o: o.observe())
+
+    def diagnose(self):
+        return self._cat(lambda o: o.diagnose())
+
+    def get_stats(self):
+        st = [o.get_stats() for o in self.parts]
+        return {k: ([sum(x) for x in zip(*[s[k] for s in st])] if k == "reasons" else sum(s[k] for s in st)) for k in st[0]}

@@ -12,7 +12,8 @@ import numpy as np
 import pytest
 
 import parity
-from helpers import gpu_batch, load_golden, oracle_batch, shipped_policy, to_numpy
+from helpers import gpu_batch, load_golden, shipped_policy, to_numpy
+from oracle_engine import GroupedOracle
 from reinforcement_learning_rendezvous_amd import monte_carlo
 from reinforcement_learning_rendezvous_amd._native import RdvError
 from reinforcement_learning_rendezvous_amd.params import make_params
@@ -127,45 +128,6 @@ def test_grouped_batch_equals_separate_handles_bit_for_bit(storage, on_done, siz
 
 
 # ---------------------------------------------------------------------------------------------------------------- 2, 3
-class GroupedOracle:
-    """One OracleBatch per group (its parameters, its env_id_offset) behind the surface of one: what tests/parity.py steps and reads."""
-
-    def __init__(self, params, sizes, storage, on_done, seed):
-        starts = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-        self.parts = [oracle_batch(int(m), p, storage, on_done, seed=seed, env_id_offset=int(s)) for p, s, m in zip(params, starts, sizes)]
-        self.slices = [slice(int(s), int(s + m)) for s, m in zip(starts, sizes)]
-
-    def _cat(self, f):
-        return np.concatenate([f(o) for o in self.parts])
-
-    def reset(self):
-        return self._cat(lambda o: o.reset())
-
-    def step(self, a, want_diag=False):
-        out = [o.step(np.ascontiguousarray(a[s]), want_diag=want_diag) for o, s in zip(self.parts, self.slices)]
-        return {k: np.concatenate([r[k] for r in out]) for k in out[0] if out[0][k] is not None}
-
-    def set_state(self, states):
-        for o, s in zip(self.parts, self.slices):
-            o.set_state(np.ascontiguousarray(states[s]))
-
-    def get_state(self):
-        return self._cat(lambda o: o.get_state())
-
-    def get_aux(self):
-        return self._cat(lambda o: o.get_aux())
-
-    def observe(self):
-        return self._cat(lambda o: o.observe())
-
-    def diagnose(self):
-        return self._cat(lambda o: o.diagnose())
-
-    def get_stats(self):
-        st = [o.get_stats() for o in self.parts]
-        return {k: ([sum(x) for x in zip(*[s[k] for s in st])] if k == "reasons" else sum(s[k] for s in st)) for k in st[0]}
-
-
 @pytest.mark.parametrize("storage", ["f32", "f64"])
 @pytest.mark.parametrize("evaluator", [False, True])
 def test_grouped_batch_against_one_oracle_per_group(storage, evaluator):

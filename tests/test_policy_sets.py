@@ -182,11 +182,14 @@ def test_resource_report_of_the_new_translation_unit():
 def test_existing_actor_critic_and_rollout_kernels_are_what_they_were():
     """profiles/policy_sets_isa_diff.md records, for policy_act_kernel, policy_value_kernel, the six mlp_kernels and both
     rollout_kernels, that the parent's and this tree's gfx950 instruction streams are identical, with a digest of each stream.  This
-    tree's rdv_hip.hip and rdv_policy_mlp.hip, compiled again, still give those digests: a header that perturbs them is moved."""
+    tree's rdv_hip.hip and rdv_policy_mlp.hip, compiled again, still give those digests: a header that perturbs them is moved.  Rows
+    marked `changed` there hold the digest of a kernel as a later change left it."""
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_isa_diff as K
     rows = re.findall(r"^\| (\w+): `([^`]+)` \| (\d+) \| (\d+) \| `(\w+)` \| (\w+) \|$", open(os.path.join(ROOT, "profiles", "policy_sets_isa_diff.md")).read(), re.M)
-    assert len(rows) == 10 and all(r[5] == "yes" and r[2] == r[3] for r in rows), rows
+    # (the two rollout kernels were changed on purpose later — the order of their statistics sums — and are recorded as they are now)
+    assert len(rows) == 10 and all((r[5] == "yes" and r[2] == r[3]) or (r[5] == "changed" and "rollout_kernel" in r[1]) for r in rows), rows
+    assert sum(r[5] == "changed" for r in rows) == 2
     assert sorted(r[1].split("::")[1].split("<")[0] for r in rows) == ["mlp_kernel"] * 6 + ["policy_act_kernel", "policy_value_kernel"] + ["rollout_kernel"] * 2
     for unit in ("rdv_hip", "rdv_policy_mlp"):
         got = K.streams(unit)
