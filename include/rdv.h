@@ -625,6 +625,83 @@ int rdv_policy_set_member_weights(rdv_policy p, int32_t member, const float* con
 int32_t rdv_policy_num_members(rdv_policy p);
 int64_t rdv_policy_num_rows(rdv_policy p);
 
+/*
+ * The recurrent policy (added within ABI 5: additive exports): what the reference's main_rnn.py trains and tune_policy.py:80, :140-148
+ * and tune_algorithm.py:68 build — sb3-contrib RecurrentPPO("MlpLstmPolicy"), i.e. RecurrentActorCriticPolicy with ONE LSTM layer of
+ * lstm_hidden_size H in front of the mlp_extractor trunk, and separate LSTMs for actor and critic (shared_lstm = False,
+ * enable_critic_lstm = True, the defaults).  Per env row, with obs x [17], state (h, c) [H] each and episode_start s in {0, 1}:
+ *
+ *     h, c   <- (1 - s) h, (1 - s) c
+ *     a      =  W_ih x + b_ih + W_hh h + b_hh            W_ih [4H, 17], W_hh [4H, H], gate rows in torch.nn.LSTM's order i, f, g, o
+ *     c'     =  sigmoid(a_f) c + sigmoid(a_i) tanh(a_g)
+ *     h'     =  sigmoid(a_o) tanh(c')
+ *     latent =  h'  ->  trunk (an RdvMlpSpec: 1..4 hidden layers of 16 / 32 / 64, one activation; its first layer is [hidden[0], H])
+ *     actor:  mean = action_net(latent) [6]; sample, clip and log_prob exactly as rdv_policy_act (the noise contract above, unchanged)
+ *     critic: value = value_net(latent) [1], from ITS OWN LSTM and trunk
+ *
+ * What is served: H in {32, 64, 128, 256} (tune_policy.py's axis), n_layers = 1, shared = 0.  Refused by name with RDV_ERR_BAD_PARAMS
+ * (rdv_lstm_spec_check, host-only, needs no GPU, the message names the field): any other hidden_size, n_layers != 1 (more LSTM layers),
+ * shared != 0 (a shared LSTM; a critic without an LSTM of its own is the same refusal: every critic handle here has one), reserved != 0;
+ * the trunk is judged by rdv_mlp_spec_check.  The +-63 input clamp, the NaN rule (a NaN in a row reaches that row's outputs and that
+ * row's state, no other row) and the weight scaling of the MLP kernels hold: W_ih and W_hh share one power-of-two scale; a non-finite
+ * weight is RDV_ERR_BAD_PARAMS.  The state enters the matrix cores as the inputs do (times 2^10, two fp16 terms, clamped to +-63: no
+ * effect on a state the cell produced, |h| < 1).  Kernels: csrc/rdv_policy_lstm.h — two launches per call, the cell and the trunk.
+ *
+ * rdv_lstm_policy_create / rdv_lstm_critic_create: arrays are HOST pointers in torch's layout — w_ih [4H, 17], w_hh [4H, H], b_ih, b_hh
+ *   [4H]; trunk weights / biases: n_hidden + 1 pointers, hidden layers first, the head ([6 or 1, hidden[n_hidden-1]]) last; log_std [6].
+ *   n_rows > 0: the rows (envs) whose state the handle owns — fp32 (h, c) [n_rows, H] each in device memory.  The result is an rdv_policy:
+ *   rdv_policy_destroy frees it, rdv_policy_get_spec returns the TRUNK's spec, rdv_policy_num_rows n_rows.  The state is zero and every
+ *   row's PENDING episode-start flag is 1.  The pending flags are what rdv_rollout and rdv_rollout_advantages use for their first step; a
+ *   committing rdv_lstm_act / rdv_lstm_value and rdv_lstm_set_state clear them (the state then IS the caller's), rdv_rollout and
+ *   rdv_rollout_advantages leave done[T-1] there.
+ * rdv_lstm_act: one step of the actor for all rows.  n must equal the handle's rows.  episode_start: u8 [n] on the device, NULL = no row
+ *   starts an episode.  actions [n, 6] clipped; raw_actions [n, 6] (nullable) the sample before clipping, log_prob [n] (nullable) its
+ *   log-density.  Advances the state.  obs and actions 16-byte aligned.  Only enqueues on `stream`: no allocation, no synchronisation.
+ * rdv_lstm_value: one step of the critic; commit = 0 evaluates without writing the state (sb3-contrib's predict_values for the value of
+ *   the last observation), commit != 0 advances it.
+ * rdv_lstm_get_state / rdv_lstm_set_state: h and c as [rows, H] fp32 DEVICE arrays in plain row-major order (copies on `stream`).
+ * rdv_lstm_reset_state: zero state for the rows whose mask byte (u8 [rows], device) is not 0; NULL = every row.  Pending flags untouched.
+ * rdv_lstm_set_weights: new weights in the layout of the create calls (log_std required for an actor, NULL for a critic); the state is
+ *   kept.  Ordering on `stream`, the pinned staging buffer and the refusal inside a stream capture are rdv_policy_set_weights'.
+ * rdv_lstm_hidden_size: H (-1 for an invalid handle, 0 for a handle that is not recurrent).
+ *
+ * Which other calls take a recurrent handle:
+ *   rdv_rollout             an LSTM actor whose rows equal the handle's envs: the loop the call is defined by — rdv_lstm_act, then rdv_step,
+ *                           n_steps times on `stream`.  Step 0 uses the pending flags, step t out->done[t-1]; behind the last step
+ *                           out->done[T-1] is copied into the pending flags (device to device on `stream`), so the next rollout goes on
+ *                           where this one stopped.  rdv_debug_last_kernel names the step kernel, as for the other loop forms.
+ *   rdv_rollout_advantages  an LSTM critic whose rows equal n: n_steps COMMITTING rdv_lstm_value calls in time order over rows->obs[t] with
+ *                           the same flags (pending, then rows->done[t-1]), one non-committing call on rows->last_obs with done[T-1] for
+ *                           out->last_value, done[T-1] into the critic's pending flags, then the kernel of rdv_gae, unchanged.  When n % 4
+ *                           != 0, row t of rows->obs is not 16-byte aligned and is read through a copy in the handle's scratch rows.
+ *   rdv_policy_act, rdv_policy_value, rdv_policy_set_weights, rdv_policy_set_member_weights: RDV_ERR_INVALID_ARGUMENT (they would ignore
+ *                           the state); policy sets are built from weights of ONE RdvMlpSpec and have no recurrent members.
+ * Not offered: a persistent one-launch recurrent rollout, 2 or 3 LSTM layers, a shared LSTM, LSTM members in policy sets.
+ */
+typedef struct RdvLstmSpec {
+  int32_t hidden_size;   /* 32, 64, 128 or 256 */
+  int32_t n_layers;      /* 1 */
+  int32_t shared;        /* 0: separate actor and critic LSTMs */
+  int32_t reserved;      /* 0 */
+  RdvMlpSpec trunk;
+} RdvLstmSpec;
+int rdv_lstm_spec_check(const RdvLstmSpec* spec_host);
+int rdv_lstm_policy_create(const RdvLstmSpec* spec_host, const float* w_ih_host, const float* w_hh_host, const float* b_ih_host,
+                           const float* b_hh_host, const float* const* weights_host, const float* const* biases_host,
+                           const float* log_std_host, int64_t n_rows, int device, rdv_policy* out);
+int rdv_lstm_critic_create(const RdvLstmSpec* spec_host, const float* w_ih_host, const float* w_hh_host, const float* b_ih_host,
+                           const float* b_hh_host, const float* const* weights_host, const float* const* biases_host, int64_t n_rows,
+                           int device, rdv_policy* out);
+int rdv_lstm_act(rdv_policy p, const float* obs, const uint8_t* episode_start, float* actions, float* raw_actions, float* log_prob,
+                 int64_t n, int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, void* stream);
+int rdv_lstm_value(rdv_policy critic, const float* obs, const uint8_t* episode_start, float* values, int64_t n, int commit, void* stream);
+int rdv_lstm_get_state(rdv_policy p, float* h_out, float* c_out, void* stream);
+int rdv_lstm_set_state(rdv_policy p, const float* h, const float* c, void* stream);
+int rdv_lstm_reset_state(rdv_policy p, const uint8_t* mask, void* stream);
+int rdv_lstm_set_weights(rdv_policy p, const float* w_ih_host, const float* w_hh_host, const float* b_ih_host, const float* b_hh_host,
+                         const float* const* weights_host, const float* const* biases_host, const float* log_std_host, void* stream);
+int32_t rdv_lstm_hidden_size(rdv_policy p);
+
 #ifdef __cplusplus
 }
 #endif

@@ -36,7 +36,10 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # learner-ready rollouts (added within ABI 5)
            "rdv_gae", "rdv_rollout_advantages", "rdv_policy_set_weights",
            # policy sets (added within ABI 5)
-           "rdv_policy_set_create", "rdv_critic_set_create", "rdv_policy_set_member_weights", "rdv_policy_num_members", "rdv_policy_num_rows"]
+           "rdv_policy_set_create", "rdv_critic_set_create", "rdv_policy_set_member_weights", "rdv_policy_num_members", "rdv_policy_num_rows",
+           # the recurrent policy (added within ABI 5)
+           "rdv_lstm_spec_check", "rdv_lstm_policy_create", "rdv_lstm_critic_create", "rdv_lstm_act", "rdv_lstm_value", "rdv_lstm_get_state",
+           "rdv_lstm_set_state", "rdv_lstm_reset_state", "rdv_lstm_set_weights", "rdv_lstm_hidden_size"]
 
 
 class RdvError(RuntimeError):
@@ -101,6 +104,15 @@ class MlpSpec(C.Structure):
         return self.n_hidden, list(self.hidden), self.activation
 
 
+class LstmSpec(C.Structure):
+    """RdvLstmSpec: one LSTM layer of 32 / 64 / 128 / 256 units in front of an RdvMlpSpec trunk, separate actor and critic LSTMs"""
+    _fields_ = [("hidden_size", C.c_int32), ("n_layers", C.c_int32), ("shared", C.c_int32), ("reserved", C.c_int32), ("trunk", MlpSpec)]
+
+    @classmethod
+    def make(cls, hidden_size, trunk, activation=ACT_TANH, n_layers=1, shared=0):
+        return cls(int(hidden_size), int(n_layers), int(shared), 0, MlpSpec.make(trunk, activation))
+
+
 INTEGRATORS = {"auto": 0, "exact": 1, "rk45": 2}
 
 
@@ -113,7 +125,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the seven translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_sets.hip, rdv_advantages.hip) for gfx950 and link librdv_hip.so
+    """Compile the eight translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -197,6 +209,16 @@ def lib():
         "rdv_policy_set_member_weights": (C.c_int, [vp, i32, vp, vp, vp, vp]),
         "rdv_policy_num_members": (i32, [vp]),
         "rdv_policy_num_rows": (i64, [vp]),
+        "rdv_lstm_spec_check": (C.c_int, [C.POINTER(LstmSpec)]),
+        "rdv_lstm_policy_create": (C.c_int, [C.POINTER(LstmSpec), vp, vp, vp, vp, vp, vp, vp, i64, C.c_int, C.POINTER(vp)]),
+        "rdv_lstm_critic_create": (C.c_int, [C.POINTER(LstmSpec), vp, vp, vp, vp, vp, vp, i64, C.c_int, C.POINTER(vp)]),
+        "rdv_lstm_act": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.c_int, u64, u64, u64, vp]),
+        "rdv_lstm_value": (C.c_int, [vp, vp, vp, vp, i64, C.c_int, vp]),
+        "rdv_lstm_get_state": (C.c_int, [vp, vp, vp, vp]),
+        "rdv_lstm_set_state": (C.c_int, [vp, vp, vp, vp]),
+        "rdv_lstm_reset_state": (C.c_int, [vp, vp, vp]),
+        "rdv_lstm_set_weights": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rdv_lstm_hidden_size": (i32, [vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

@@ -263,7 +263,11 @@ class RendezvousBatch:
         this call is defined by inside the library: rdv_policy_act + rdv_step, two launches per step, the same rows.
         ``policy`` may be a ``PolicySet`` whose rows are the batch's envs: member g acts for the envs of its range (env i as in a
         batch of its own with ``env_id_offset + start_g``); a set of more than one member takes that loop too, its actor ONE launch
-        per step for all members.  The set's ranges and the batch's parameter groups are independent."""
+        per step for all members.  The set's ranges and the batch's parameter groups are independent.
+        ``policy`` may be an ``LstmPolicy`` whose rows are the batch's envs: rdv_lstm_act + rdv_step per step inside the library, episode
+        starts from the previous step's ``done`` (step 0: what the previous rollout left pending; every row at first).  The dict then
+        also holds ``lstm_state0``, the actor's ``(h, c)`` as step 0 sees it (what RecurrentPPO's buffer keeps for sequence starts),
+        and the next rollout goes on where this one stopped."""
         T, n, dev = int(n_steps), self.num_envs, self.device
         if out is None or out["obs"].shape[0] != T:
             out = dict(obs=torch.empty((T, n, N.OBS_DIM), dtype=torch.float32, device=dev),
@@ -272,10 +276,17 @@ class RendezvousBatch:
                        done=torch.empty((T, n), dtype=torch.uint8, device=dev),
                        log_prob=torch.empty((T, n), dtype=torch.float32, device=dev),
                        last_obs=torch.empty((n, N.OBS_DIM), dtype=torch.float32, device=dev))
+        recurrent = getattr(policy, "lstm_hidden_size", None) is not None
+        if recurrent:       # an LstmPolicy: the handle owns the state of this batch's envs
+            policy._rows(n)
+            policy._hip_handle(dev)
+            out["lstm_state0"] = policy.state_at_start("l", dev)
         ro = N.RolloutOut(*[out[f].data_ptr() for f, _ in N.RolloutOut._fields_])
         N.check(self._lib.rdv_rollout(self._h, policy._hip_handle(dev), T, C.byref(ro), int(bool(deterministic)),
                                       C.c_uint64(policy.noise_seed), C.c_uint64(policy._calls), self._stream()))
         policy._calls += T
+        if recurrent:
+            policy._pending["l"] = out["done"][T - 1].clone()
         # the batch's current observation / last rewards / dones, as after step(): copied on first access
         self._defer(obs=out["last_obs"], reward=out["reward"][T - 1], done=out["done"][T - 1])
         return out

@@ -10,6 +10,7 @@
 #include "rdv_device.h"
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
+#include "rdv_policy_lstm.h"
 #include "rdv_policy_sets.h"
 #include "rdv_advantages.h"
 
@@ -442,6 +443,11 @@ struct RdvPolicyNet {
   int32_t n_members;   // 1: a plain handle, or a set of one member (the plain kernels read its one block)
   int64_t rows;        // 0: a plain handle (any n); a set: the rows its members own together
   const int32_t* tile_member;   // device: member index per 256-row tile (inside the allocation of `weights`); nullptr for a plain handle
+  // the recurrent policy (csrc/rdv_policy_lstm.h): lstm_hidden != 0, `weights` = [trunk block | cell block], `rows` = the rows whose state
+  // the handle owns; one device allocation `lstm_state` holds h, c, h_next, c_tmp ([rows, H] fp32 each), obs_tmp [rows, 17], pending [rows]
+  int32_t lstm_hidden;
+  float *lstm_state, *lstm_h, *lstm_c, *lstm_h_next, *lstm_c_tmp, *lstm_obs_tmp;
+  uint8_t* lstm_pending;
 };
 static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
 static constexpr uint32_t kPolicyMagic = 0x52445650u;   // "RDVP"
@@ -456,7 +462,7 @@ static int finish_policy(const char* who, const std::vector<float>& packed, cons
   RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
   if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
   p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
-  p->n_members = 1; p->rows = 0; p->tile_member = nullptr;
+  p->n_members = 1; p->rows = 0; p->tile_member = nullptr; p->lstm_hidden = 0; p->lstm_state = nullptr;
   p->spec = spec; p->shipped_arch = shipped_arch; p->block_floats = shipped_arch ? kPolFloats : (int)packed.size();
   hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
   if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -598,6 +604,7 @@ static int upload_block(rdv_policy p, const char* who, int32_t member, const std
 
 int rdv_policy_set_weights(rdv_policy p, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
   if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_set_weights");
   if (p->n_members > 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: this handle is a policy set of %d members: refresh one member with rdv_policy_set_member_weights", p->n_members);
   std::vector<float> packed;
   if (int rc = pack_for_handle(p, "rdv_policy_set_weights", weights, biases, log_std, packed)) return rc;
@@ -606,6 +613,7 @@ int rdv_policy_set_weights(rdv_policy p, const float* const* weights, const floa
 
 int rdv_policy_set_member_weights(rdv_policy p, int32_t member, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
   if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_member_weights: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_set_weights");
   if (member < 0 || member >= p->n_members) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_member_weights: member %d of %d", member, p->n_members);
   std::vector<float> packed;
   if (int rc = pack_for_handle(p, "rdv_policy_set_member_weights", weights, biases, log_std, packed)) return rc;
@@ -663,7 +671,7 @@ static int create_set(const char* who, const RdvMlpSpec* spec, int32_t n_members
   if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
   p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
   p->spec = *spec; p->shipped_arch = shipped; p->block_floats = (int)block_floats;
-  p->n_members = n_members; p->rows = rows; p->tile_member = nullptr;
+  p->n_members = n_members; p->rows = rows; p->tile_member = nullptr; p->lstm_hidden = 0; p->lstm_state = nullptr;
   hipError_t err = hipMalloc(&p->weights, table_at + table.size() * sizeof(int32_t));
   if (err == hipSuccess) err = hipMemcpy(p->weights, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
   if (err == hipSuccess) err = hipMemcpy(reinterpret_cast<char*>(p->weights) + table_at, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
@@ -694,6 +702,7 @@ int rdv_policy_destroy(rdv_policy p) {
   DeviceGuard guard(p->device);
   (void)hipDeviceSynchronize();
   (void)hipFree(p->weights);
+  if (p->lstm_state) (void)hipFree(p->lstm_state);
   if (p->staging) (void)hipHostFree(p->staging);
   for (hipEvent_t ev : p->staged) if (ev) (void)hipEventDestroy(ev);
   p->magic = 0;
@@ -724,6 +733,7 @@ static int launch_policy_act(rdv_policy p, const float* obs, float* actions, int
 int rdv_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
                    uint64_t env_id_offset, void* stream) {
   if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_act, which carries the state");
   if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: this handle is a critic (rdv_critic_create)");
   if (!obs || !actions || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs, actions and a positive n are required");
   if (misaligned(obs, 16) || misaligned(actions, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs and actions must be 16-byte aligned");
@@ -734,6 +744,7 @@ int rdv_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, in
 
 int rdv_policy_value(rdv_policy p, const float* obs, float* values, int64_t n, void* stream) {
   if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: this handle is a recurrent policy (rdv_lstm_critic_create): use rdv_lstm_value, which carries the state");
   if (p->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: this handle is an actor (rdv_policy_create)");
   if (!obs || !values || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs, values and a positive n are required");
   if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs must be 16-byte aligned");
@@ -783,6 +794,217 @@ int rdv_gae(const float* reward, const uint8_t* done, const float* values, const
   return RDV_OK;
 }
 
+// ---- the recurrent policy (csrc/rdv_policy_lstm.h): one LSTM layer in front of an RdvMlpSpec trunk, the state owned by the handle
+int rdv_lstm_spec_check(const RdvLstmSpec* spec) {
+  if (!spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_spec_check: null spec");
+  if (!lstm_hidden_ok(spec->hidden_size))
+    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: hidden_size = %d is not 32, 64, 128 or 256 (lstm_hidden_size)", spec->hidden_size);
+  if (spec->n_layers != 1)
+    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: n_layers = %d: one LSTM layer is served (n_lstm_layers = 1)", spec->n_layers);
+  if (spec->shared != 0)
+    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: shared = %d: separate actor and critic LSTMs are served (shared_lstm = False, enable_critic_lstm = True)", spec->shared);
+  if (spec->reserved != 0) return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: reserved = %d must be 0", spec->reserved);
+  return rdv_mlp_spec_check(&spec->trunk);
+}
+
+// null pointers and finiteness of a recurrent network's host arrays (the spec has been checked)
+static int check_lstm_arrays(const char* who, int H, const RdvMlpSpec& trunk, int out_dim, const float* w_ih, const float* w_hh, const float* b_ih,
+                             const float* b_hh, const float* const* weights, const float* const* biases, const float* log_std) {
+  if (!w_ih || !w_hh || !b_ih || !b_hh || !weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (out_dim == kPolOut && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host is required for an actor", who);
+  if (out_dim != kPolOut && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host must be null for a critic", who);
+  const int L = trunk.n_hidden;
+  for (int l = 0; l <= L; ++l)
+    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights or biases of trunk layer %d", who, l);
+  if (!all_finite(w_ih, 4 * H * kPolIn) || !all_finite(w_hh, 4 * H * H) || !all_finite(b_ih, 4 * H) || !all_finite(b_hh, 4 * H))
+    return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite LSTM weight", who);
+  for (int l = 0; l <= L; ++l) {
+    const int in_w = l == 0 ? H : trunk.hidden[l - 1], out_w = l < L ? trunk.hidden[l] : out_dim;
+    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite weight in trunk layer %d", who, l);
+  }
+  return RDV_OK;
+}
+
+static int create_lstm(const char* who, const RdvLstmSpec* spec, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                       const float* const* weights, const float* const* biases, const float* log_std, int out_dim, int64_t n_rows, int device,
+                       rdv_policy* out) {
+  if (!spec || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (int rc = rdv_lstm_spec_check(spec)) return rc;
+  const int H = spec->hidden_size;
+  if (n_rows <= 0 || n_rows > (int64_t)1 << 31) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_rows = %lld must be in 1..2^31", who, (long long)n_rows);
+  if (int rc = check_lstm_arrays(who, H, spec->trunk, out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
+  if (int rc = check_device(who, device)) return rc;
+  DeviceGuard guard(device);
+  std::vector<float> packed;
+  pack_lstm_weights(H, spec->trunk, out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
+  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
+  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
+  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
+  p->n_members = 1; p->rows = n_rows; p->tile_member = nullptr; p->lstm_hidden = H; p->lstm_state = nullptr;
+  p->spec = spec->trunk; p->shipped_arch = false; p->block_floats = (int)packed.size();
+  const size_t state_floats = (size_t)n_rows * (size_t)H, obs_floats = ((size_t)n_rows * kPolIn + 3) & ~(size_t)3;
+  const size_t bytes = (4 * state_floats + obs_floats) * sizeof(float) + (size_t)n_rows;
+  hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
+  if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
+  if (err == hipSuccess) err = hipMalloc(&p->lstm_state, bytes);
+  if (err == hipSuccess) err = hipMemset(p->lstm_state, 0, bytes);
+  if (err == hipSuccess) {
+    p->lstm_h = p->lstm_state; p->lstm_c = p->lstm_h + state_floats; p->lstm_h_next = p->lstm_c + state_floats;
+    p->lstm_c_tmp = p->lstm_h_next + state_floats; p->lstm_obs_tmp = p->lstm_c_tmp + state_floats;
+    p->lstm_pending = reinterpret_cast<uint8_t*>(p->lstm_obs_tmp + obs_floats);
+    err = hipMemset(p->lstm_pending, 1, (size_t)n_rows);
+  }
+  if (err != hipSuccess) {
+    (void)hipGetLastError();
+    if (p->weights) (void)hipFree(p->weights);
+    if (p->lstm_state) (void)hipFree(p->lstm_state);
+    delete p;
+    return fail(err == hipErrorOutOfMemory ? RDV_ERR_OUT_OF_MEMORY : RDV_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
+  }
+  *out = p;
+  return RDV_OK;
+}
+
+int rdv_lstm_policy_create(const RdvLstmSpec* spec_host, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                           const float* const* weights_host, const float* const* biases_host, const float* log_std_host, int64_t n_rows,
+                           int device, rdv_policy* out) {
+  return create_lstm("rdv_lstm_policy_create", spec_host, w_ih, w_hh, b_ih, b_hh, weights_host, biases_host, log_std_host, kPolOut, n_rows, device, out);
+}
+int rdv_lstm_critic_create(const RdvLstmSpec* spec_host, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                           const float* const* weights_host, const float* const* biases_host, int64_t n_rows, int device, rdv_policy* out) {
+  return create_lstm("rdv_lstm_critic_create", spec_host, w_ih, w_hh, b_ih, b_hh, weights_host, biases_host, nullptr, 1, n_rows, device, out);
+}
+int32_t rdv_lstm_hidden_size(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->lstm_hidden : -1; }
+
+#define RDV_CHECK_LSTM(p, who)                                                                        \
+  if (!(p) || (p)->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");      \
+  if (!(p)->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, who ": this handle is not a recurrent policy (rdv_lstm_policy_create / rdv_lstm_critic_create)")
+
+// one step of a recurrent handle on `s`: the cell (flags: u8 [rows] or nullptr), then the trunk; commit: the state advances (the
+// pending flags are the caller's business).  The caller's DeviceGuard holds the device; the arguments have been checked.
+static int launch_lstm(rdv_policy p, const float* obs, const uint8_t* flags, float* out, float* raw_actions, float* log_prob, bool commit,
+                       int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, hipStream_t s) {
+  lstm_launch_cell(p->lstm_hidden, p->weights, obs, flags, p->lstm_h, p->lstm_c, p->lstm_h_next, commit ? p->lstm_c : p->lstm_c_tmp, p->rows, s);
+  RDV_HIP(hipGetLastError());
+  lstm_launch_trunk(p->spec.activation, p->out_dim == 1, p->weights, p->lstm_h_next, commit ? p->lstm_h : nullptr, out, p->rows, deterministic, seed,
+                    counter, env_id_offset, raw_actions, log_prob, s);
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+int rdv_lstm_act(rdv_policy p, const float* obs, const uint8_t* episode_start, float* actions, float* raw_actions, float* log_prob, int64_t n,
+                 int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_act");
+  if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: this handle is a critic (rdv_lstm_critic_create)");
+  if (!obs || !actions) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: obs and actions are required");
+  if (n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: n = %lld, the handle owns the state of %lld rows", (long long)n, (long long)p->rows);
+  if (misaligned(obs, 16) || misaligned(actions, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: obs and actions must be 16-byte aligned");
+  DeviceGuard guard(p->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = launch_lstm(p, obs, episode_start, actions, raw_actions, log_prob, true, deterministic ? 1 : 0, seed, counter, env_id_offset, s)) return rc;
+  RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, s));   // the state has moved past whatever start was pending
+  return RDV_OK;
+}
+
+int rdv_lstm_value(rdv_policy p, const float* obs, const uint8_t* episode_start, float* values, int64_t n, int commit, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_value");
+  if (p->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: this handle is an actor (rdv_lstm_policy_create)");
+  if (!obs || !values) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: obs and values are required");
+  if (n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: n = %lld, the handle owns the state of %lld rows", (long long)n, (long long)p->rows);
+  if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: obs must be 16-byte aligned");
+  DeviceGuard guard(p->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = launch_lstm(p, obs, episode_start, values, nullptr, nullptr, commit != 0, 1, 0, 0, 0, s)) return rc;
+  if (commit) RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, s));
+  return RDV_OK;
+}
+
+int rdv_lstm_get_state(rdv_policy p, float* h_out, float* c_out, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_get_state");
+  if (!h_out || !c_out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_get_state: h_out and c_out are required");
+  DeviceGuard guard(p->device);
+  const size_t bytes = (size_t)p->rows * (size_t)p->lstm_hidden * sizeof(float);
+  RDV_HIP(hipMemcpyAsync(h_out, p->lstm_h, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  RDV_HIP(hipMemcpyAsync(c_out, p->lstm_c, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  return RDV_OK;
+}
+
+int rdv_lstm_set_state(rdv_policy p, const float* h, const float* c, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_set_state");
+  if (!h || !c) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_set_state: h and c are required");
+  DeviceGuard guard(p->device);
+  const size_t bytes = (size_t)p->rows * (size_t)p->lstm_hidden * sizeof(float);
+  RDV_HIP(hipMemcpyAsync(p->lstm_h, h, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  RDV_HIP(hipMemcpyAsync(p->lstm_c, c, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, static_cast<hipStream_t>(stream)));
+  return RDV_OK;
+}
+
+int rdv_lstm_reset_state(rdv_policy p, const uint8_t* mask, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_reset_state");
+  DeviceGuard guard(p->device);
+  lstm_launch_reset(p->lstm_h, p->lstm_c, mask, p->rows, p->lstm_hidden, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+int rdv_lstm_set_weights(rdv_policy p, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* const* weights,
+                         const float* const* biases, const float* log_std, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_set_weights");
+  if (int rc = check_lstm_arrays("rdv_lstm_set_weights", p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
+  std::vector<float> packed;
+  pack_lstm_weights(p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
+  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "rdv_lstm_set_weights: the packed block has %d floats, the handle's %d", (int)packed.size(), p->block_floats);
+  return upload_block(p, "rdv_lstm_set_weights", 0, packed, stream);
+}
+
+// rdv_rollout with a recurrent actor: rdv_lstm_act + rdv_step, n_steps times on `stream` (the caller has checked the arguments)
+static int rollout_lstm(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut* out, int deterministic, uint64_t noise_seed,
+                        uint64_t noise_counter0, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int64_t n = h->n;
+  float* obs_t = obs_row_target(h, out->obs, 0);
+  if (int rc = rdv_observe(h, obs_t, stream)) return rc;
+  for (int32_t t = 0; t < n_steps; ++t) {
+    if (int rc = obs_row_flush(h, out->obs, t, s)) return rc;
+    const uint8_t* flags = t == 0 ? p->lstm_pending : out->done + (int64_t)(t - 1) * n;
+    if (int rc = launch_lstm(p, obs_t, flags, h->act_tmp, out->actions + (int64_t)t * n * RDV_ACT_DIM, out->log_prob ? out->log_prob + (int64_t)t * n : nullptr,
+                             true, deterministic ? 1 : 0, noise_seed, noise_counter0 + (uint64_t)t, h->env_id_offset, s)) return rc;
+    RdvStepOut so;
+    std::memset(&so, 0, sizeof so);
+    float* obs_next = (t + 1 < n_steps) ? obs_row_target(h, out->obs, t + 1) : out->last_obs;
+    so.obs = obs_next; so.reward = out->reward + (int64_t)t * n; so.done = out->done + (int64_t)t * n;
+    if (int rc = rdv_step(h, h->act_tmp, &so, stream)) return rc;
+    obs_t = obs_next;
+  }
+  RDV_HIP(hipMemcpyAsync(p->lstm_pending, out->done + (int64_t)(n_steps - 1) * n, (size_t)n, hipMemcpyDeviceToDevice, s));
+  return RDV_OK;
+}
+
+// rdv_rollout_advantages with a recurrent critic: n_steps committing steps in time order, one non-committing step on last_obs, GAE
+static int advantages_lstm(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,
+                           const RdvAdvantageOut* out, void* stream) {
+  DeviceGuard guard(critic->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const bool aligned = (n & 3) == 0;                                   // row t of rows->obs is 16-byte aligned if and only if n % 4 == 0
+  for (int32_t t = 0; t < n_steps; ++t) {
+    const float* obs_t = rows->obs + (int64_t)t * n * RDV_OBS_DIM;
+    if (!aligned) {
+      RDV_HIP(hipMemcpyAsync(critic->lstm_obs_tmp, obs_t, (size_t)n * RDV_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
+      obs_t = critic->lstm_obs_tmp;
+    }
+    const uint8_t* flags = t == 0 ? critic->lstm_pending : rows->done + (int64_t)(t - 1) * n;
+    if (int rc = launch_lstm(critic, obs_t, flags, out->values + (int64_t)t * n, nullptr, nullptr, true, 1, 0, 0, 0, s)) return rc;
+  }
+  const uint8_t* last_done = rows->done + (int64_t)(n_steps - 1) * n;
+  if (int rc = launch_lstm(critic, rows->last_obs, last_done, out->last_value, nullptr, nullptr, false, 1, 0, 0, 0, s)) return rc;
+  RDV_HIP(hipMemcpyAsync(critic->lstm_pending, last_done, (size_t)n, hipMemcpyDeviceToDevice, s));
+  gae_launch(rows->reward, rows->done, out->values, out->last_value, n_steps, n, (float)gamma, (float)(gamma * gae_lambda), out->advantages, out->returns,
+             gae_depth(), s);
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
 int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,
                            const RdvAdvantageOut* out, void* stream) {
   if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows is null");
@@ -794,6 +1016,11 @@ int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t
   if (int rc = check_gae_scalars("rdv_rollout_advantages", n_steps, n, gamma, gae_lambda)) return rc;
   if (!critic || critic->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
   if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: this handle is an actor (rdv_policy_create)");
+  if (critic->lstm_hidden) {
+    if (n != critic->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: n = %lld, the recurrent critic owns the state of %lld rows", (long long)n, (long long)critic->rows);
+    if (misaligned(rows->obs, 16) || misaligned(rows->last_obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows->obs and rows->last_obs must be 16-byte aligned");
+    return advantages_lstm(critic, rows, n_steps, n, gamma, gae_lambda, out, stream);
+  }
   if (critic->rows && n != critic->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: n = %lld, the critic set owns %lld rows", (long long)n, (long long)critic->rows);
   if (misaligned(rows->obs, 16) || misaligned(rows->last_obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows->obs and rows->last_obs must be 16-byte aligned");
   // the critic at call time over the rows the actor saw, then over the observation after the last step: rdv_policy_value's own launches
@@ -813,7 +1040,7 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: this handle is a critic (rdv_critic_create)");
   if (p->device != h->device) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: the policy lives on device %d, the envs on device %d", p->device, h->device);
   if (n_steps <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: n_steps must be positive (got %d)", n_steps);
-  if (p->rows && p->rows != h->n) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: the policy set owns %lld rows, the batch has %lld envs", (long long)p->rows, (long long)h->n);
+  if (p->rows && p->rows != h->n) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: the policy (a set, or a recurrent policy) owns %lld rows, the batch has %lld envs", (long long)p->rows, (long long)h->n);
   if (!out || !out->obs || !out->actions || !out->reward || !out->done || !out->last_obs)
     return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: obs, actions, reward, done and last_obs are required");
   if (misaligned(out->obs, 16) || misaligned(out->actions, 16) || misaligned(out->last_obs, 16))
@@ -822,6 +1049,7 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   RDV_CHECK_FAULT(h);
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
+  if (p->lstm_hidden) return rollout_lstm(h, p, n_steps, out, deterministic, noise_seed, noise_counter0, stream);
   if (h->general || h->n_groups || !p->shipped_arch || p->n_members > 1) {
     // General rigid bodies, parameter groups (no grouped persistent kernel), policy sets of more than one member (no persistent kernel for
     // sets) and policies of another architecture than the shipped one (the

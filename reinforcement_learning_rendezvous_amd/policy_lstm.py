@@ -1,0 +1,460 @@
+"""
+The recurrent policy of the reference's main_rnn.py (sb3-contrib ``RecurrentPPO("MlpLstmPolicy")``, also tune_policy.py:80,
+tune_algorithm.py:68): ``RecurrentActorCriticPolicy`` with ONE LSTM layer of ``lstm_hidden_size`` units in front of the
+``mlp_extractor`` trunk, and separate LSTMs for actor and critic (``shared_lstm=False``, ``enable_critic_lstm=True``, the defaults).
+Per env row::
+
+    h, c   <- (1 - episode_start) * (h, c)
+    h', c' =  LSTMCell(obs, (h, c))                     torch.nn.LSTM(17, H), gate order i, f, g, o
+    actor:  mean = action_net(policy_net(h'));   critic: value = value_net(value_net_trunk(h')) from its OWN LSTM
+
+On the GPU a step is two hand-written HIP kernels per network (csrc/rdv_policy_lstm.h, through the C ABI: rdv_lstm_act /
+rdv_lstm_value); the state lives in device memory, owned by the handle.  ``backend="torch"`` (and CPU observations) run the plain
+``torch.nn.LSTM`` and ``Linear`` modules with the same semantics, which the tests use as the kernels' reference.  Served: H in
+{32, 64, 128, 256}, trunks of 1..4 hidden layers of 16 / 32 / 64 with tanh / ReLU / sigmoid.  More LSTM layers, a shared LSTM, a critic
+without an LSTM and any other H raise ValueError.
+"""
+import ctypes as C
+import io
+import json
+import zipfile
+
+import numpy as np
+import torch
+
+from .policy import ACTIVATIONS, _trunk_keys, infer_arch, parse_activation, parse_net_arch
+
+LSTM_HIDDEN_SIZES = (32, 64, 128, 256)
+_LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
+
+
+def check_lstm_config(lstm_hidden_size, n_lstm_layers=1, shared_lstm=False, enable_critic_lstm=True):
+    """The refusals of include/rdv.h ("The recurrent policy"), by name, on the host."""
+    if int(n_lstm_layers) != 1:
+        raise ValueError(f"n_lstm_layers = {n_lstm_layers}: one LSTM layer is served")
+    if shared_lstm:
+        raise ValueError("shared_lstm = True: separate actor and critic LSTMs are served (the main_rnn.py defaults)")
+    if not enable_critic_lstm:
+        raise ValueError("enable_critic_lstm = False: a critic without an LSTM of its own is not served")
+    if int(lstm_hidden_size) not in LSTM_HIDDEN_SIZES:
+        raise ValueError(f"lstm_hidden_size = {lstm_hidden_size} is not one of {LSTM_HIDDEN_SIZES}")
+
+
+class LstmPolicy(torch.nn.Module):
+    def __init__(self, weights=None, lstm_hidden_size=256, net_arch=None, activation_fn="tanh", n_rows=None, seed=0, backend="auto",
+                 n_lstm_layers=1, shared_lstm=False, enable_critic_lstm=True):
+        super().__init__()
+        self.backend = backend          # "auto": HIP kernels for CUDA float32 observations, PyTorch otherwise; "torch"; "hip"
+        self.noise_seed = int(seed)
+        self.noise_env_offset = 0
+        self._calls = 0
+        self._hip, self._hip_critic = {}, {}        # device index -> rdv_policy handle (each owns the state of n_rows rows)
+        self.activation = parse_activation(activation_fn)
+        self._fn = ACTIVATIONS[self.activation][1]
+        if weights is not None:
+            if any(k.startswith("lstm_actor.") and not k.endswith("_l0") for k in weights):
+                raise ValueError("the weights hold more than one LSTM layer (lstm_actor.*_l1): n_lstm_layers = 1 is served")
+            if "lstm_actor.weight_hh_l0" not in weights:
+                raise KeyError("lstm_actor.weight_hh_l0: the weights hold no actor LSTM")
+            if "lstm_critic.weight_hh_l0" not in weights:
+                raise ValueError("the weights hold no lstm_critic.*: a shared LSTM (shared_lstm = True) or a critic without an LSTM "
+                                 "(enable_critic_lstm = False) is not served")
+            lstm_hidden_size = int(np.asarray(weights["lstm_actor.weight_hh_l0"]).shape[1])
+        check_lstm_config(lstm_hidden_size, n_lstm_layers, shared_lstm, enable_critic_lstm)
+        self.lstm_hidden_size = H = int(lstm_hidden_size)
+        if net_arch is not None:
+            pi, vf = parse_net_arch(net_arch)
+        elif weights is not None:
+            pi = infer_arch(weights, "policy_net")
+            if pi is None:
+                raise KeyError("mlp_extractor.policy_net.0.weight: the weights hold no actor trunk")
+            vf = infer_arch(weights, "value_net") or pi
+            parse_net_arch(dict(pi=pi, vf=vf))
+        else:
+            pi = vf = [64, 64]
+        self.pi_arch, self.vf_arch = list(pi), list(vf)
+        self.lstm_actor = torch.nn.LSTM(17, H, num_layers=1)
+        self.lstm_critic = torch.nn.LSTM(17, H, num_layers=1)
+        for prefix, arch, out in (("l", self.pi_arch, 6), ("v", self.vf_arch, 1)):
+            dims = [H] + arch + [out]
+            for i in range(len(dims) - 1):
+                setattr(self, f"{prefix}{i + 1}", torch.nn.Linear(dims[i], dims[i + 1]))
+        self.log_std = torch.nn.Parameter(torch.zeros(6))
+        self.has_critic = True
+        if weights is not None:
+            self._load_weights(weights)
+        for p in self.parameters():
+            p.requires_grad_(False)
+        self.n_rows = None if n_rows is None else int(n_rows)
+        self._state = {}                # torch backend: "l" / "v" -> [h, c] once the rows are known
+        # the handles' pending episode-start flags, mirrored: True (every row, as created), False (none) or the uint8 [rows] tensor a
+        # rollout left (done[T-1]); the torch backend's own flags
+        self._pending = {"l": True, "v": True}
+
+    # ------------------------------------------------------------------------------------------------ weights
+    def _layers(self, prefix):
+        return [getattr(self, f"{prefix}{i + 1}") for i in range(len(self.pi_arch if prefix == "l" else self.vf_arch) + 1)]
+
+    def _lstm(self, prefix):
+        return self.lstm_actor if prefix == "l" else self.lstm_critic
+
+    def _load_weights(self, weights):
+        """sb3-contrib's state-dict keys into the modules; every shape is checked before anything is copied."""
+        todo = []
+
+        def take(dst, key):
+            src = torch.as_tensor(np.asarray(weights[key]), dtype=torch.float32)
+            if src.shape != dst.shape:
+                raise ValueError(f"{key}: shape {tuple(src.shape)} does not fit the architecture (expected {tuple(dst.shape)})")
+            todo.append((dst, src))
+        for name, prefix, trunk in (("lstm_actor", "l", "policy_net"), ("lstm_critic", "v", "value_net")):
+            for k in _LSTM_KEYS:
+                take(getattr(self._lstm(prefix), k), f"{name}.{k}")
+            for lin, (kw, kb) in zip(self._layers(prefix), _trunk_keys(trunk, len(self.pi_arch if prefix == "l" else self.vf_arch))):
+                take(lin.weight, kw)
+                take(lin.bias, kb)
+        take(self.log_std, "log_std")
+        with torch.no_grad():
+            for dst, src in todo:
+                dst.copy_(src)
+
+    def state_dict_sb3(self):
+        """The parameters under sb3-contrib's keys, as NumPy arrays (what ``__init__`` takes)."""
+        out = {"log_std": self.log_std.detach().cpu().numpy()}
+        for name, prefix, trunk in (("lstm_actor", "l", "policy_net"), ("lstm_critic", "v", "value_net")):
+            for k in _LSTM_KEYS:
+                out[f"{name}.{k}"] = getattr(self._lstm(prefix), k).detach().cpu().numpy()
+            arch = self.pi_arch if prefix == "l" else self.vf_arch
+            for lin, (kw, kb) in zip(self._layers(prefix), _trunk_keys(trunk, len(arch))):
+                out[kw], out[kb] = lin.weight.detach().cpu().numpy(), lin.bias.detach().cpu().numpy()
+        return out
+
+    @classmethod
+    def from_npz(cls, path, **kwargs):
+        w = dict(np.load(path, allow_pickle=False))
+        if "activation_fn" in w:
+            kwargs.setdefault("activation_fn", str(w.pop("activation_fn")))
+        return cls(w, **kwargs)
+
+    @classmethod
+    def from_sb3_zip(cls, path, **kwargs):
+        """An sb3-contrib checkpoint zip as ``model.save()`` writes it; policy.pth is read with weights_only=True (nothing is
+        unpickled); H and the trunk come from the shapes, the activation from the zip's ``data`` JSON (absent: tanh)."""
+        with zipfile.ZipFile(path) as z:
+            sd = torch.load(io.BytesIO(z.read("policy.pth")), weights_only=True, map_location="cpu")
+            if "activation_fn" not in kwargs and "data" in z.namelist():
+                pk = json.loads(z.read("data").decode("utf-8")).get("policy_kwargs") or {}
+                fn = pk.get("activation_fn") if isinstance(pk, dict) else None
+                if fn is not None:
+                    kwargs["activation_fn"] = parse_activation(fn)
+        return cls({k: v.numpy() for k, v in sd.items()}, **kwargs)
+
+    # ------------------------------------------------------------------------------------------------ rows and state
+    def _rows(self, n):
+        if self.n_rows is None:
+            self.n_rows = int(n)
+        if int(n) != self.n_rows:
+            raise ValueError(f"{n} rows, the policy owns the state of {self.n_rows}")
+        return self.n_rows
+
+    def _torch_state(self, prefix, device):
+        if self.n_rows is None:
+            raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
+        st = self._state.get(prefix)
+        if st is None:
+            st = [torch.zeros((self.n_rows, self.lstm_hidden_size), dtype=torch.float32, device=device) for _ in range(2)]
+        elif st[0].device != device:
+            st = [t.to(device) for t in st]
+        self._state[prefix] = st
+        return st
+
+    def _pending_flags(self, prefix, device):
+        """The pending episode-start flags as a uint8 [rows] tensor."""
+        p = self._pending[prefix]
+        if isinstance(p, torch.Tensor):
+            return p.to(device)
+        return torch.full((self.n_rows,), 1 if p else 0, dtype=torch.uint8, device=device)
+
+    def state_at_start(self, prefix="l", device=None):
+        """``(h, c)`` as the next rollout's first step will see it: the state, zero where an episode start is pending — what
+        RecurrentPPO's buffer keeps for a sequence start (``RendezvousBatch.rollout`` returns it as ``lstm_state0``)."""
+        h, c = self._get_state(prefix, device)
+        keep = (self._pending_flags(prefix, h.device) == 0).to(h.dtype)[:, None]
+        return h * keep, c * keep
+
+    def _use_hip(self, obs):
+        return self.backend == "hip" or (self.backend == "auto" and obs.is_cuda and obs.dtype == torch.float32)
+
+    def _host_arrays(self, prefix):
+        host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
+        lstm = self._lstm(prefix)
+        layers = self._layers(prefix)
+        return ([host(getattr(lstm, k)) for k in _LSTM_KEYS], [host(l.weight) for l in layers], [host(l.bias) for l in layers],
+                [host(self.log_std)] if prefix == "l" else [])
+
+    def _create_handle(self, prefix, idx):
+        from . import _native as N
+        arch = self.pi_arch if prefix == "l" else self.vf_arch
+        spec = N.LstmSpec.make(self.lstm_hidden_size, arch, ACTIVATIONS[self.activation][0])
+        N.check(N.lib().rdv_lstm_spec_check(C.byref(spec)))
+        lstm, ws, bs, log_std = self._host_arrays(prefix)
+        wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+        bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
+        h = C.c_void_p()
+        lp = [C.c_void_p(t.data_ptr()) for t in lstm]
+        if prefix == "l":
+            N.check(N.lib().rdv_lstm_policy_create(C.byref(spec), *lp, wp, bp, C.c_void_p(log_std[0].data_ptr()), self.n_rows, idx, C.byref(h)))
+        else:
+            N.check(N.lib().rdv_lstm_critic_create(C.byref(spec), *lp, wp, bp, self.n_rows, idx, C.byref(h)))
+        return h
+
+    def _handle(self, prefix, device):
+        if self.n_rows is None:
+            raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        table = self._hip if prefix == "l" else self._hip_critic
+        if idx not in table:
+            table[idx] = self._create_handle(prefix, idx)
+        return table[idx]
+
+    def _hip_handle(self, device):
+        return self._handle("l", torch.device(device))
+
+    def _critic_handle(self, device):
+        return self._handle("v", torch.device(device))
+
+    @staticmethod
+    def _stream(device):
+        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+    def _get_state(self, prefix, device=None):
+        table = self._hip if prefix == "l" else self._hip_critic
+        if self.backend != "torch" and table:
+            from . import _native as N
+            idx = next(iter(table)) if device is None or torch.device(device).index is None else torch.device(device).index
+            dev = torch.device("cuda", idx)
+            h = torch.empty((self.n_rows, self.lstm_hidden_size), dtype=torch.float32, device=dev)
+            c = torch.empty_like(h)
+            N.check(N.lib().rdv_lstm_get_state(table[idx], C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), self._stream(dev)))
+            return h, c
+        st = self._torch_state(prefix, torch.device(device) if device is not None else self.log_std.device)
+        return st[0].clone(), st[1].clone()
+
+    def _set_state(self, prefix, hc, device=None):
+        h, c = hc
+        if self.backend != "torch" and isinstance(h, torch.Tensor) and h.is_cuda:
+            from . import _native as N
+            self._rows(h.shape[0])
+            h, c = h.to(torch.float32).contiguous(), c.to(torch.float32).contiguous()
+            N.check(N.lib().rdv_lstm_set_state(self._handle(prefix, h.device), C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), self._stream(h.device)))
+            self._pending[prefix] = False
+            return
+        h = torch.as_tensor(h, dtype=torch.float32)
+        c = torch.as_tensor(c, dtype=torch.float32)
+        self._rows(h.shape[0])
+        st = self._torch_state(prefix, h.device)
+        st[0].copy_(h); st[1].copy_(c)
+        self._pending[prefix] = False
+
+    @property
+    def state(self):
+        """The actor's ``(h, c)``, [rows, H] float32 each, plain row-major (a copy)."""
+        return self._get_state("l")
+
+    @state.setter
+    def state(self, hc):
+        self._set_state("l", hc)
+
+    @property
+    def critic_state(self):
+        return self._get_state("v")
+
+    @critic_state.setter
+    def critic_state(self, hc):
+        self._set_state("v", hc)
+
+    @torch.no_grad()
+    def reset_state(self, mask=None):
+        """Zero state for the rows of ``mask`` (None: every row), actor and critic alike."""
+        from . import _native as N
+        for prefix, table in (("l", self._hip), ("v", self._hip_critic)):
+            for idx, hnd in table.items():
+                dev = torch.device("cuda", idx)
+                m = None if mask is None else torch.as_tensor(mask).to(dev, torch.uint8).contiguous()
+                N.check(N.lib().rdv_lstm_reset_state(hnd, None if m is None else C.c_void_p(m.data_ptr()), self._stream(dev)))
+            st = self._state.get(prefix)
+            if st is not None:
+                keep = torch.zeros(self.n_rows, dtype=torch.bool, device=st[0].device) if mask is None else \
+                    ~torch.as_tensor(mask).to(st[0].device).bool()
+                st[0].mul_(keep[:, None]); st[1].mul_(keep[:, None])
+
+    # ------------------------------------------------------------------------------------------------ evaluation
+    def _cell_torch(self, prefix, obs, start, commit=True):
+        """One step of the PyTorch modules on [n, 17] observations: the latent h' (the state advances when ``commit``)."""
+        st = self._torch_state(prefix, obs.device)
+        keep = 1.0 - (torch.zeros(obs.shape[0], device=obs.device) if start is None else start.to(obs.device, torch.float32))
+        h0, c0 = st[0] * keep[:, None], st[1] * keep[:, None]
+        _, (h1, c1) = self._lstm(prefix)(obs[None].to(torch.float32), (h0[None], c0[None]))
+        if commit:
+            st[0].copy_(h1[0]); st[1].copy_(c1[0])
+            self._pending[prefix] = False
+        return h1[0]
+
+    def _trunk_torch(self, prefix, x):
+        layers = self._layers(prefix)
+        for lin in layers[:-1]:
+            x = self._fn(lin(x))
+        return layers[-1](x)
+
+    @staticmethod
+    def _aligned(obs):
+        """Contiguous rows at a 16-byte aligned address, as the kernels read them (row t of a [T, N, 17] tensor is not when N % 4 != 0)."""
+        obs = obs.contiguous()
+        return obs.clone() if obs.data_ptr() % 16 else obs
+
+    @staticmethod
+    def _flags(episode_start, n, device):
+        if episode_start is None:
+            return None
+        f = torch.as_tensor(np.asarray(episode_start) if not isinstance(episode_start, torch.Tensor) else episode_start)
+        if f.shape != (n,):
+            raise ValueError(f"episode_start: expected {n} flags, got {tuple(f.shape)}")
+        return (f != 0).to(device, torch.uint8).contiguous()
+
+    @torch.no_grad()
+    def act(self, obs, episode_start=None, deterministic=True, generator=None, out=None, env_id_offset=None, raw_out=None, log_prob_out=None):
+        """One step of the actor on observations [n, 17], n the policy's rows: the clipped action; the state advances.
+        ``episode_start``: [n] flags (None: no row starts an episode).  HIP backend: noise keyed by (noise_seed, env_id_offset + i,
+        call counter), as ``MlpPolicy.act``; ``raw_out`` [n, 6] / ``log_prob_out`` [n] receive the unclipped sample and its log-density."""
+        n = self._rows(obs.shape[0])
+        if self._use_hip(obs):
+            from . import _native as N
+            if generator is not None:
+                self.noise_seed = int(generator.initial_seed())
+            offset = self.noise_env_offset if env_id_offset is None else int(env_id_offset)
+            obs = self._aligned(obs)
+            flags = self._flags(episode_start, n, obs.device)
+            if out is None:
+                out = torch.empty((n, 6), dtype=torch.float32, device=obs.device)
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            N.check(N.lib().rdv_lstm_act(self._handle("l", obs.device), ptr(obs), ptr(flags), ptr(out), ptr(raw_out), ptr(log_prob_out), n,
+                                         int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls), C.c_uint64(offset),
+                                         self._stream(obs.device)))
+            self._calls += 1
+            self._pending["l"] = False
+            return out
+        mean = self._trunk_torch("l", self._cell_torch("l", obs, self._flags(episode_start, n, obs.device)))
+        a = mean
+        if not deterministic:
+            noise = torch.randn(a.shape, dtype=a.dtype, device=a.device, generator=generator)
+            a = a + torch.exp(self.log_std) * noise
+            if log_prob_out is not None:
+                log_prob_out.copy_((-0.5 * noise * noise - self.log_std).sum(dim=1) - 3.0 * float(np.log(2.0 * np.pi)))
+        elif log_prob_out is not None:
+            log_prob_out.fill_(-float(self.log_std.sum()) - 3.0 * float(np.log(2.0 * np.pi)))
+        if raw_out is not None:
+            raw_out.copy_(a)
+        res = torch.clamp(a, -1.0, 1.0)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+
+    @torch.no_grad()
+    def value(self, obs, episode_start=None, commit=True, out=None):
+        """One step of the critic on observations [n, 17]: values [n].  ``commit=False`` evaluates without writing the critic's state
+        (sb3-contrib's ``predict_values`` for the value of the last observation)."""
+        n = self._rows(obs.shape[0])
+        if self._use_hip(obs):
+            from . import _native as N
+            obs = self._aligned(obs)
+            flags = self._flags(episode_start, n, obs.device)
+            if out is None:
+                out = torch.empty((n,), dtype=torch.float32, device=obs.device)
+            N.check(N.lib().rdv_lstm_value(self._handle("v", obs.device), C.c_void_p(obs.data_ptr()), None if flags is None else C.c_void_p(flags.data_ptr()),
+                                           C.c_void_p(out.data_ptr()), n, int(bool(commit)), self._stream(obs.device)))
+            if commit:
+                self._pending["v"] = False
+            return out
+        v = self._trunk_torch("v", self._cell_torch("v", obs, self._flags(episode_start, n, obs.device), commit=commit))[:, 0]
+        if out is not None:
+            out.copy_(v)
+            return out
+        return v
+
+    def predict(self, observation, state=None, episode_start=None, deterministic=True):
+        """SB3's calling convention (save_new_trajectory.py:106): NumPy observations [n, 17] (or [17]); ``state`` = the ``(h, c)`` a
+        previous call returned (None: the policy's own, zero at first) -> ``(action, state)``."""
+        dev = self.log_std.device
+        obs = torch.as_tensor(np.asarray(observation), dtype=torch.float32, device=dev)
+        single = obs.dim() == 1
+        obs = obs.reshape(-1, 17)
+        self._rows(obs.shape[0])
+        if state is not None:
+            self._set_state("l", tuple(torch.as_tensor(np.asarray(s), dtype=torch.float32, device=dev).reshape(obs.shape[0], -1) for s in state))
+        a = self.act(obs, episode_start=episode_start, deterministic=deterministic).cpu().numpy()
+        h, c = self._get_state("l", dev)
+        return (a[0] if single else a), (h.cpu().numpy(), c.cpu().numpy())
+
+    # ------------------------------------------------------------------------------------------------ rollouts
+    @torch.no_grad()
+    def advantages(self, ro, gamma=0.99, gae_lambda=0.95, out=None):
+        """``MlpPolicy.advantages`` for the recurrent critic: T committing critic steps in time order over ``ro["obs"]`` (episode starts:
+        the critic's pending flags, then ``ro["done"][t-1]``), one non-committing step on ``ro["last_obs"]`` with ``done[T-1]``, GAE."""
+        from . import advantages as A
+        obs = ro["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
+            raise ValueError(f"obs: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
+        T, n, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+        self._rows(n)
+        A.check_tensor(obs, "obs", (T, n, 17), torch.float32, dev)
+        A.check_tensor(ro["reward"], "reward", (T, n), torch.float32, dev)
+        A.check_tensor(ro["done"], "done", (T, n), torch.uint8, dev)
+        A.check_tensor(ro["last_obs"], "last_obs", (n, 17), torch.float32, dev)
+        A.check_discounts(gamma, gae_lambda)
+        src = out if out is not None else ro
+        for name, shape in dict(values=(T, n), last_value=(n,), advantages=(T, n), returns=(T, n)).items():
+            t = src.get(name)
+            if t is None or tuple(t.shape) != shape or t.device != dev:
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            ro[name] = t
+        if self.backend != "torch" and obs.is_cuda:
+            from . import _native as N
+            rows = N.RolloutOut(obs.data_ptr(), None, ro["reward"].data_ptr(), ro["done"].data_ptr(), None, ro["last_obs"].data_ptr())
+            ao = N.AdvantageOut(*[ro[f].data_ptr() for f, _ in N.AdvantageOut._fields_])
+            N.check(N.lib().rdv_rollout_advantages(self._handle("v", dev), C.byref(rows), T, n, float(gamma), float(gae_lambda), C.byref(ao),
+                                                   self._stream(dev)))
+            self._pending["v"] = ro["done"][T - 1].clone()
+            return ro
+        for t in range(T):
+            flags = self._pending_flags("v", dev) if t == 0 else ro["done"][t - 1]
+            self.value(obs[t], episode_start=flags, out=ro["values"][t])
+        self.value(ro["last_obs"], episode_start=ro["done"][T - 1], commit=False, out=ro["last_value"])
+        self._pending["v"] = ro["done"][T - 1].clone()
+        A.gae(ro["reward"], ro["done"], ro["values"], ro["last_value"], gamma, gae_lambda, out=(ro["advantages"], ro["returns"]))
+        return ro
+
+    def update_weights(self, weights=None):
+        """New weights for the modules (a dict with the constructor's keys; None: push the modules' current parameters) and for every
+        live HIP handle, through rdv_lstm_set_weights on the current stream of its device; the recurrent state is kept."""
+        if weights is not None:
+            self._load_weights(weights)
+        if not (self._hip or self._hip_critic):
+            return
+        from . import _native as N
+        for prefix, table in (("l", self._hip), ("v", self._hip_critic)):
+            if not table:
+                continue
+            lstm, ws, bs, log_std = self._host_arrays(prefix)
+            wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
+            bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
+            for idx, h in table.items():
+                N.check(N.lib().rdv_lstm_set_weights(h, *[C.c_void_p(t.data_ptr()) for t in lstm], wp, bp,
+                                                     C.c_void_p(log_std[0].data_ptr()) if log_std else None, self._stream(torch.device("cuda", idx))))
+
+    def close(self):
+        if self._hip or self._hip_critic:
+            from . import _native as N
+            for h in list(self._hip.values()) + list(self._hip_critic.values()):
+                N.lib().rdv_policy_destroy(h)
+            self._hip, self._hip_critic = {}, {}
