@@ -259,6 +259,11 @@ struct RdvEnvBatch {
   uint32_t host_error_word;
   std::vector<double> host_eval;
   bool prepared_ok;  // every slot holds what the env's next reset returns (false: prepare_kernel runs before the next slot-using launch)
+  // step_kernel_split's slot form asks less of the slots and keeps them so itself: a tag that equals episode + 1 tells the truth (rdv_step.h).
+  // False after whatever clears prepared_ok from outside and after every rdv_step launch of another kernel (they advance episodes in
+  // registers); prepare_kernel then runs in front of the next slot-form launch.
+  bool step_slots_ok;
+  int split_form;    // step_kernel_split, fp32 storage, RESET: 1 the slot form, 0 the speculative reset (RDV_SPLIT_FORM=slots|speculative in the environment of rdv_create; default: split_slots_by_size)
 #ifdef RDV_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -333,7 +338,18 @@ static int ensure_prepared(RdvEnvBatch* h, hipStream_t s) {
   with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(prepare_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev_params, A); });
   RDV_HIP(hipGetLastError());
   h->prepared_ok = true;
+  h->step_slots_ok = true;
   return RDV_OK;
+}
+// ... and the slot form of step_kernel_split on the slots' tags telling the truth (step_slots_ok).  prepare_kernel is idempotent, so a
+// capture that begins with the flag down simply records it in front of its first step.
+static int ensure_step_slots(RdvEnvBatch* h, hipStream_t s) {
+  if (h->step_slots_ok) return RDV_OK;
+  const bool was = h->prepared_ok;
+  h->prepared_ok = false;
+  const int rc = ensure_prepared(h, s);
+  if (rc) h->prepared_ok = was;
+  return rc;
 }
 // The loops of rdv_step that rdv_step_many and rdv_rollout are defined by write row t of the caller's [T][N][17] observations from a kernel
 // that stores 16-byte vectors: the row is aligned if and only if N % 4 == 0.  Otherwise the kernel writes h->obs_tmp and the row is a copy.
@@ -1134,7 +1150,8 @@ int rdv_create(const RdvParams* params, int64_t n_envs, int device, int storage,
   h->device_error = 0u; h->host_error_word = 0u;
   h->act_tmp = reinterpret_cast<float*>(base + L.act_tmp);
   h->obs_tmp = reinterpret_cast<float*>(base + L.obs_tmp);
-  h->prepared_ok = false;
+  h->prepared_ok = false; h->step_slots_ok = false;
+  { const char* x = getenv("RDV_SPLIT_FORM"); h->split_form = (x && !strcmp(x, "slots")) ? 1 : (x && !strcmp(x, "speculative")) ? 0 : -1; }
   derive_block(h, *params, h->dev);
   // every step of the set-up reports itself: which call failed, and why
   const char* what = "hipMemset of the workspace";
@@ -1287,7 +1304,7 @@ int rdv_set_params(rdv_handle h, const RdvParams* p, void* stream) {
   if (int rc = rdv_params_validate(p)) return rc;
   DeviceGuard guard(h->device);
   h->params = *p; derive_block(h, *p, h->dev);
-  h->prepared_ok = false;   // nominal state / ranges may have changed: what a reset returns is no longer what the slots hold
+  h->prepared_ok = false; h->step_slots_ok = false;   // nominal state / ranges may have changed: what a reset returns is no longer what the slots hold
   // ... and the same on the device, ordered on `stream`: a graph recorded earlier holds a persistent kernel without the prepare launch that
   // prepared_ok asks for, and a tag says only which episode a slot belongs to, not which parameters drew it.  A tag of 0 never equals
   // episode + 1, so the kernels' own guard refills every slot from the new block before its first use (capturable: a memset node).
@@ -1303,7 +1320,7 @@ int rdv_get_params(rdv_handle h, RdvParams* out) {
 }
 int rdv_seed(rdv_handle h, uint64_t seed) {
   RDV_CHECK_HANDLE(h);
-  h->seed = seed; h->fresh = true; h->prepared_ok = false;
+  h->seed = seed; h->fresh = true; h->prepared_ok = false; h->step_slots_ok = false;
   return RDV_OK;
 }
 #ifdef RDV_STAMPS
@@ -1325,7 +1342,7 @@ int rdv_set_reset_tape(rdv_handle h, const double* tape, int32_t depth) {
   RDV_CHECK_HANDLE(h);
   if ((tape == nullptr) != (depth <= 0)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_set_reset_tape: tape and depth must both be set or both be empty");
   h->tape = tape; h->tape_depth = tape ? depth : 0;
-  h->prepared_ok = false;   // the slots hold states of the previous reset source
+  h->prepared_ok = false; h->step_slots_ok = false;   // the slots hold states of the previous reset source
   return RDV_OK;
 }
 
@@ -1341,7 +1358,7 @@ int rdv_reset(rdv_handle h, const uint8_t* mask, float* obs_out, void* stream) {
   if (h->n_groups) launch_reset_groups(h->storage == RDV_STORAGE_F32, grid_for(h->n), s, h->group_table, A, mask, obs_out, fresh);
   else with_storage(h->storage, [&](auto st) { hipLaunchKernelGGL(reset_kernel<decltype(st)>, grid_for(h->n), dim3(kBlock), 0, s, h->dev_params, A, mask, obs_out, fresh); });
   RDV_HIP(hipGetLastError());
-  if (fresh) h->prepared_ok = true;   // reset_kernel refills the slot of every env it resets: after a full reset all are current
+  if (fresh) h->prepared_ok = h->step_slots_ok = true;   // reset_kernel refills the slot of every env it resets: after a full reset all are current
   h->fresh = false;
   return RDV_OK;
 }
@@ -1378,7 +1395,15 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
 #define RDV_K_FUSED(ST, B) step_kernel<ST, B>
 #define RDV_K_RAW(ST, B) step_kernel<ST, B, false, true>
   const bool f32 = h->storage == RDV_STORAGE_F32, dg = A.diag != nullptr || A.eval != nullptr;   // either one: the evaluator build
-  if (split) {
+  const bool slots = split && f32 && h->on_done == RDV_ON_DONE_RESET && (h->split_form < 0 ? split_slots_by_size(h->n) : h->split_form != 0);
+  if (slots) {
+    // the slot form (rdv_step.h): the same instantiation by name — the third template argument has a default — with one refill workgroup
+    // appended per step workgroup
+    if (int rc = ensure_step_slots(h, s)) return rc;
+    const unsigned step_wgs = (unsigned)((h->n + kSplitEnvs - 1) / kSplitEnvs);
+    hipLaunchKernelGGL((step_kernel_split<float, true, true>), dim3(2u * step_wgs), dim3(kSplitBlock), 0, s, RDV_HOT_ARGS(A, h->dev_params), A);
+    h->last_kernel = "step_kernel_split<float, true>";
+  } else if (split) {
     const dim3 grid((unsigned)((h->n + kSplitEnvs - 1) / kSplitEnvs));
     const dim3 block(kSplitBlock);
     const bool all = h->on_done != RDV_ON_DONE_HALT;   // no halted envs: every lane runs the transition, the inputs travel together (advance_all)
@@ -1427,6 +1452,7 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
 #undef RDV_K_SPLIT
   RDV_HIP(hipGetLastError());
   if (h->on_done == RDV_ON_DONE_RESET) h->prepared_ok = false;   // the step kernels reset in registers: the slots of the persistent kernels lag behind now
+  h->step_slots_ok = slots;   // (the slot form leaves the slots of the episodes that ended to the next launch's refill: enough for itself, not for the persistent kernels)
   return RDV_OK;
 }
 
@@ -1554,7 +1580,7 @@ int rdv_restore(rdv_handle h, const void* src, int64_t src_bytes, void* stream) 
     if (int rc = access(h, ACC_CLEAR_HALTED, nullptr, nullptr, nullptr, stream)) return rc;
   h->fresh = false;
   h->raw_state = true;      // the snapshot may have been taken right after rdv_set_state
-  h->prepared_ok = false;   // the episode counters changed: the slots are re-derived before the next launch that uses them
+  h->prepared_ok = false; h->step_slots_ok = false;   // the episode counters changed: the slots are re-derived before the next launch that uses them
   return RDV_OK;
 }
 
@@ -1697,7 +1723,7 @@ int rdv_set_param_groups(rdv_handle h, const RdvParams* params, const int64_t* s
     if (int rc = refuse_in_capture("rdv_set_param_groups", static_cast<hipStream_t>(stream))) return rc;
   }
   if (n_groups == 0) {   // back to the handle's single block (the side allocation stays until rdv_destroy or the next grouping)
-    if (h->n_groups) h->prepared_ok = false;
+    if (h->n_groups) h->prepared_ok = h->step_slots_ok = false;
     h->n_groups = 0;
     return RDV_OK;
   }
@@ -1733,7 +1759,7 @@ int rdv_set_param_groups(rdv_handle h, const RdvParams* params, const int64_t* s
   h->group_table.params = reinterpret_cast<const DevParams*>(base);
   h->group_table.tile_group = reinterpret_cast<const int32_t*>(base + block_bytes);
   h->n_groups = n_groups;
-  h->prepared_ok = false;
+  h->prepared_ok = false; h->step_slots_ok = false;
   return RDV_OK;
 }
 int rdv_set_group_params(rdv_handle h, int32_t group, const RdvParams* p, void* stream) {

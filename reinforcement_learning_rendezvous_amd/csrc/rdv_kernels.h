@@ -58,6 +58,9 @@ constexpr int kTilesPerCU = 3;                  // RDV_VARIANT_FUSED_TILES: work
 // 1.5 M and 2 M: within the spread of the allocations — the upper end moved from 655,360 to 1,310,720 envs.
 static inline int stagger_by_size(int64_t n) { return (n < 229376 || n >= 1310720) ? 0 : n < 393216 ? 6 : 8; }
 constexpr int64_t kSplitAutoMaxEnvs = 65536;    // measured crossover (tools/n_sweep.py, profiles/r02_n_sweep_parts.csv): split wins up to one 256-env workgroup per CU
+// step_kernel_split's form for fp32 storage and on_done == RESET: prepared slots prefetched by the service waves and refilled by appended
+// workgroups (true), or the speculative reset on the service waves (false).  Measured: profiles/split_slots_prefetch.txt.
+static inline bool split_slots_by_size(int64_t n) { (void)n; return true; }
 enum { ST_STEPS = 0, ST_EPISODES, ST_SUCCESS, ST_COLLIDED, ST_REASON0, ST_REASON1, ST_REASON2, ST_REASON3,
        ST_SUM_LEN, ST_SUM_RET, ST_SUM_DV, ST_SUM_DW };
 

@@ -13,7 +13,9 @@
 // tag[i] == e.episode + 1 says that env i's slot in HBM holds reset(seed, id, counter = e.episode) (whose own episode field is
 // e.episode + 1); anything else is refilled before its first use.
 // Results are bit-identical to the in-lane reset (same expressions on the same inputs).
-// (The one-launch step kernels do NOT use slots: measured, round 2 — see step_kernel_split in rdv_step.h.)
+// Of the one-launch step kernels only step_kernel_split's slot form uses the slots (fp32 storage, on_done == RESET: the service waves
+// prefetch the records from HBM, appended workgroups refill them by part — rdv_step.h); it needs less than the persistent kernels: a
+// tag that equals episode + 1 must tell the truth, a slot may lag behind.  The other layouts reset in registers (measured, round 2).
 #pragma once
 
 namespace rdv {

@@ -169,6 +169,48 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(sizeof(S
 constexpr int kSplitEnvs = 256;      // envs per workgroup
 constexpr int kSplitBlock = 512;     // 8 waves
 
+// The refill workgroup of step_kernel_split's slot form, waves 0-3: the envs [base, base + 256) whose episode has just begun (k == 0) and
+// whose slot does not hold the reset that ends it (tag != episode + 1) get that reset into their slot.  Wave w reads k, episode and tag
+// of envs 64 w + lane and posts them in LDS; behind the workgroup's own barrier all four compact the SAME list — one decision per env,
+// whatever the step workgroup stores meanwhile — and wave w writes part w of every listed slot (rc+vc+bookkeeping | qc+wc | qt | wt,
+// as the persistent kernels' refill does: ~150-350 instructions where the whole reset has ~900), wave 0 the tags behind its part.
+// Nobody reads a record in the launch that writes it (see the kernel), so parts and tag need no order among themselves.
+template <typename ST>
+__device__ __forceinline__ void refill_stale_slots(const StepArgs& A, const DevParams& P, int64_t base, int wv, int lane, uint32_t* job_kind,
+                                                   uint32_t* job_counter, uint16_t* lists) {
+  constexpr int Q = kSplitEnvs / kWave;
+  constexpr int kWords = sizeof(typename Vec4<ST>::type) / 4, kWordK = kWords / 4, kWordEpisode = 3 * kWords / 4;   // .y and .w of chunk 5
+  if (wv < Q) {
+    const uint32_t* c5 = reinterpret_cast<const uint32_t*>(reinterpret_cast<const typename Vec4<ST>::type*>(A.ws) + 5 * A.cs);
+    const int s = wv * kWave + lane;
+    const int64_t ii = base + s;
+    const bool ok = ii < A.n;
+    const int64_t il = ok ? ii : A.n - 1;
+    const uint32_t k = c5[il * kWords + kWordK], episode = c5[il * kWords + kWordEpisode], tag = A.prep_tag[il];
+    job_kind[s] = (ok && k == 0u && tag != episode + 1u) ? JOB_REFILL : JOB_NONE;
+    job_counter[s] = episode;
+  }
+  __syncthreads();
+  if (wv >= Q) return;
+  uint16_t* list = lists + wv * kSplitEnvs;
+  bool flag[Q];
+#pragma unroll
+  for (int q = 0; q < Q; ++q) flag[q] = job_kind[q * kWave + lane] != JOB_NONE;
+  const int total = compact_flags<Q>(flag, lane, list);
+  const SlotStore<ST> S = hbm_slot_store<ST>(A.prep);
+#pragma clang loop unroll(disable)
+  for (int j0 = 0; j0 < total; j0 += kWave) {
+    const int j = j0 + lane;
+    if (j < total) {
+      const int s = (int)list[j];
+      const uint32_t counter = job_counter[s];
+      const int64_t ii = base + s;
+      slot_refill_role<ST>(wv, P, S, ii, A.seed, A.env_id_offset + (uint64_t)ii, counter, tape_row_of(A.tape, A.tape_depth, A.n, ii, counter));
+      if (wv == 0) A.prep_tag[ii] = counter + 1u;
+    }
+  }
+}
+
 // Round 3 measured three ways of shortening what stands in front of the barrier (all bit-identical, all SLOWER; code in commits
 // 794a540, 8ad2438 and 93382df, evidence under profiles/):
 //  - the speculative reset split over TWO service waves per step wave (12-wave workgroup, chaser half | target half in LDS): the
@@ -187,7 +229,33 @@ constexpr int kSplitBlock = 512;     // 8 waves
 //    The step waves' transition is no faster beside nearly idle service waves (it is a dependency chain through the chaser side, not
 //    an issue count: removing the whole target side from it gains 0.17 us), and the slot copy is work they did not have before
 //    (profiles/r03_split_slots_hint.txt).
-template <typename ST, bool kAll>   // kAll: on_done != HALT — every lane of the step waves runs the transition (advance_all)
+//
+// The slot form (kSlots; fp32 storage, kAll, on_done == RESET only) is the fourth attempt at taking the speculative reset off the path to
+// the barrier, and keeps everything that made this kernel win: the single barrier right behind the transition, the step waves as they
+// are, the reset writes beside the step waves' statistics and outputs.  It changes the two things the slot attempts lost by:
+//  - the SERVICE waves fetch the prepared slots, not the step waves: at entry every service lane requests its env's 192-byte record
+//    (rdv_slots.h: hbm_slot_store), the env's chunk 5 (k, episode) and its tag — dense, coalesced, thousands of cycles before the data
+//    is used — and goes to the barrier without any arithmetic.  Behind it a lane whose env finished copies the record (state chunks to
+//    HBM, observation to its LDS row) when tag == episode + 1 and k >= 1, both as read at entry; otherwise (an env that ends on the
+//    first step of its episode, or a slot that is stale for whatever reason) it runs today's in-lane reset: slow, rare, correct;
+//  - the refill leaves the workgroup: the grid has one more workgroup per step workgroup (blockIdx.x >= the number of step workgroups;
+//    for the flagship's 256 both indices are equal mod 8: same XCD, same L2), whose waves 0-3 list — ballots, no atomics — the envs of
+//    step workgroup j with k == 0 and tag != episode + 1 (~13 of 256 with random actions, all 256 after a synchronous episode end)
+//    and write their slots BY PART, one part per wave (refill_stale_slots, above).  No LDS hand-off to the step workgroup, no barrier
+//    shared with it, no statistics; priority 0, in the issue gaps of a step wave as the speculative reset is.  (A grid has one block
+//    size: waves 4-7 of a refill workgroup end at its barrier.)  The first version ran the WHOLE reset for the listed envs on one
+//    wave, in-lane: that wave began behind the dispatch of all step workgroups, waited for its loads and then had the ~900
+//    instructions of a reset in front of it — it outlived the step waves and the launch took 7.27 us against 6.46; by part the refill
+//    waves leave 3,970 ns after the launch's first wave (median) where the step waves leave at 4,110, and the launch takes 6.07 us.
+// Why no torn record can be consumed: a record is WRITTEN only in a launch where its env has k == 0 on entry, and CONSUMED only in a
+// launch where it has k >= 1 on entry — never both in one launch, and launches on a stream are ordered.  The one exception is a refill
+// wave that runs late and already sees the new episode (k == 0) of an env that finished in this very launch: that write comes after
+// the consumer has loaded the record and stored the state, and the next launch rewrites it identically or finds the tag current.  A
+// slot that is stale while k >= 1 is deliberately NOT refilled in-kernel: its env falls back when it ends and is refilled one launch
+// later.  Launches that advance episodes without maintaining the slots (every other rdv_step kernel) and calls that change what a
+// reset returns clear the handle's step_slots_ok; prepare_kernel then runs in front of the next slot-form launch (rdv_hip.hip).
+// Measured: profiles/split_slots_prefetch.txt.
+template <typename ST, bool kAll, bool kSlots = false>   // kAll: on_done != HALT — every lane of the step waves runs the transition (advance_all)
 __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
                                                        uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
   const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
@@ -199,9 +267,9 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
   const int wv = threadIdx.x >> 6;
   const bool step_role = wv < kSplitEnvs / kWave;
   const int slot_in_block = threadIdx.x & (kSplitEnvs - 1);          // both roles: the env this lane is responsible for
+  const int64_t n = A.n;
   const int64_t i = (int64_t)blockIdx.x * kSplitEnvs + slot_in_block;
   const int64_t wave_base = i - lane;
-  const int64_t n = A.n;
   const bool active = i < n;
   const int64_t rows = (n - wave_base) < kWave ? (n - wave_base) : kWave;
   V* ws = reinterpret_cast<V*>(A.ws);
@@ -209,6 +277,22 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
   RDV_STAMP_DECL
   RDV_STAMP(0);
 
+  if constexpr (kSlots) {
+    static_assert(sizeof(ST) == 4 && kAll, "the slot form is built for fp32 storage without halted envs");
+    // ------------------------------------------------------------------ refill workgroups
+    const unsigned n_step_wgs = (unsigned)((n + kSplitEnvs - 1) / kSplitEnvs);
+    const bool refill_role = blockIdx.x >= n_step_wgs;
+    const unsigned refill_wg = blockIdx.x - n_step_wgs;
+    if (refill_role) {
+      uint32_t* words = reinterpret_cast<uint32_t*>(stage);
+      refill_stale_slots<ST>(A, P, (int64_t)refill_wg * kSplitEnvs, wv, lane, words, words + kSplitEnvs, reinterpret_cast<uint16_t*>(words + 2 * kSplitEnvs));
+      if (wv == 0) {
+        RDV_STAMP(7);
+        RDV_STAMP_FLUSH(((uint64_t)refill_wg + n_step_wgs) * 8)
+      }
+      return;
+    }
+  }
   if (step_role) {
     // ------------------------------------------------------------------ step waves
     __builtin_amdgcn_s_setprio(2);   // (the longer of the SIMD's two instruction streams first: 6.43 -> 6.41 us per launch; the service waves first: 7.03)
@@ -271,6 +355,68 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
     store_step_outputs<true>(A, i, active, fin, r, e, obs_r);
     if (m_reset == 0ull) store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
     RDV_STAMP(5);
+    RDV_STAMP(6);
+  } else if constexpr (kSlots) {
+    // ------------------------------------------------------------------ service waves, slot form
+    // Every lane issues every request (the index is clamped into the batch, as in tile_fetch): nothing sits under a branch, all 14 are
+    // in flight together.  Native vectors, and every lane of them is used behind the barrier (profiles/r03_split_slots_hint.txt).
+    constexpr int kRecVecs = kChunks + kSlotObsVecs;
+    static_assert(slot_record_bytes<ST>() == kRecVecs * 16, "the fp32 slot record is 12 vectors");
+    const int64_t il = active ? i : n - 1;
+    const pin_f4* recp = reinterpret_cast<const pin_f4*>(A.prep) + il * kRecVecs;
+    pin_f4 rec[kRecVecs];
+#pragma unroll
+    for (int v = 0; v < kRecVecs; ++v) rec[v] = recp[v];
+    pin_f4 c5 = reinterpret_cast<const pin_f4*>(ws)[5 * A.cs + il];
+    uint32_t tag = A.prep_tag[il];
+    RDV_STAMP(1);
+    RDV_STAMP(2);
+    RDV_STAMP(3);
+    __syncthreads();
+    RDV_STAMP(4);
+#pragma unroll
+    for (int v = 0; v < kRecVecs; ++v) asm volatile("" : "+v"(rec[v]));
+    asm volatile("" : "+v"(c5), "+v"(tag));
+    const unsigned long long m_reset = fin_mask[wv - kSplitEnvs / kWave];
+    if (m_reset != 0ull) {   // wave-uniform: some env of the step wave we serve finished its episode
+      float* wl = stage + (wv - kSplitEnvs / kWave) * (kWave * RDV_OBS_DIM);
+      if (active && ((m_reset >> lane) & 1ull)) {
+        const uint32_t k_in = __float_as_uint(c5.y), episode_in = __float_as_uint(c5.w);
+        if (tag == episode_in + 1u && k_in >= 1u) {
+          // copy path: the record is reset(seed, id, episode_in), state chunks in storage layout + observation
+          if (__float_as_uint(rec[5].z) == kFlagsPending) {   // refilled by part (persistent kernels): the flags need the whole state
+            float4 c[kChunks];
+#pragma unroll
+            for (int j = 0; j < kChunks; ++j) c[j] = make_float4(rec[j].x, rec[j].y, rec[j].z, rec[j].w);
+            Env se;
+            unpack_env<float>(c, se);
+            rec[5].z = __uint_as_float(reset_flags(P, se));
+          }
+          pin_f4* dst = reinterpret_cast<pin_f4*>(ws) + i;
+#pragma unroll
+          for (int j = 0; j < kChunks; ++j) __builtin_nontemporal_store(rec[j], dst + j * A.cs);
+#pragma unroll
+          for (int j = 0; j < RDV_OBS_DIM; ++j) wl[lane * RDV_OBS_DIM + j] = rec[kChunks + (j >> 2)][j & 3];
+        } else {
+          // fallback path: today's reset, in-lane
+          Env ne;
+          float robs[RDV_OBS_DIM];
+          ne.episode = episode_in;
+          const double* row = nullptr;
+          if (A.tape_depth > 0) row = A.tape + ((int64_t)(ne.episode % (uint32_t)A.tape_depth) * n + i) * RDV_STATE_DIM;
+          reset_state<ST, false>(P, ne, A.seed, A.env_id_offset + (uint64_t)i, row);
+          reset_aux<ST>(P, ne);
+          canon_rest<ST>(ne);
+          observation(P, ne, robs);
+          store_env<ST, true>(ws, A.cs, i, ne, true);
+#pragma unroll
+          for (int j = 0; j < RDV_OBS_DIM; ++j) wl[lane * RDV_OBS_DIM + j] = robs[j];
+        }
+      }
+      wave_lds_fence();
+      RDV_STAMP(5);
+      store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
+    }
     RDV_STAMP(6);
   } else {
     // ------------------------------------------------------------------ service waves

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: A/B of two builds of the library (the product .so against an experimental one) on the one-launch step at 65,536 envs
-and 524,288 envs: each build in its own child process, alternated, 256-launch graphs under sustained load.
+and 524,288 envs: each build in its own child process, alternated, 256-launch graphs under sustained load.  AB_SIZES=65536,32768,16384 picks the sizes; the children inherit the
+environment (RDV_SPLIT_FORM=speculative|slots: the form of step_kernel_split in the builds that have both).
     python tools/lib_ab.py tools/_nt.so"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,7 +35,7 @@ for n in [int(x) for x in os.environ.get("AB_SIZES", "65536,32768").split(",")]:
     print(f"{n}: {e0.elapsed_time(e1) * 1e3 / (R * 256):.3f}", end="  ")
     if n == 65536:      # the closed loop as two launches per step: the observation rows are read by the actor kernel next
         from reinforcement_learning_rendezvous_amd.policy import MlpPolicy
-        pol = MlpPolicy.from_npz(os.path.join('/root/repo', "tests", "golden", "mlp_policy.npz")).to("cuda:0")
+        pol = MlpPolicy.from_npz(os.path.join(%r, "tests", "golden", "mlp_policy.npz")).to("cuda:0")
         buf = torch.empty((n, 6), dtype=torch.float32, device="cuda:0")
         for t in range(16): env.step(pol.act(env.obs, deterministic=False, out=buf))
         g2 = torch.cuda.CUDAGraph()
@@ -51,7 +52,7 @@ for n in [int(x) for x in os.environ.get("AB_SIZES", "65536,32768").split(",")]:
         pol.close()
     env.close()
 print()
-''' % ROOT
+''' % (ROOT, ROOT)
 others = sys.argv[1:]
 for rep in range(2):
     for label, lib in [("product", "-")] + [(os.path.basename(o), o) for o in others]:

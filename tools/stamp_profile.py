@@ -6,6 +6,8 @@ Builds a -DRDV_STAMPS copy of the library into tools/_stamps.so, runs a few hund
   0 entry | 1 inputs staged | 2 step / next-state computed | 3 at the barrier | 4 past it | 5 | 6 | 7 end
 plus, from s_memrealtime (100 MHz, one counter for the whole chip): the shader clock, when waves enter and leave
 relative to the first wave of the launch, and the span of the launch as the waves see it.
+RDV_SPLIT_FORM=speculative|slots picks the form (csrc/rdv_step.h); in the slot form the second half of the grid is the refill workgroups;
+the lifetime of their wave 0 (it writes the largest part and the tags) is printed beside the two roles.  RDV_STAMPS_PREBUILT=1 uses tools/_stamps.so as it stands.
 Never quote this build's run time: the stamps fence the scheduler."""
 import ctypes as C
 import os
@@ -24,7 +26,8 @@ def main():
     wpg = 4 * (1 + svc)
     lib = os.path.join(ROOT, "tools", "_stamps.so")
     from _build import build_variant
-    build_variant(lib, ["-DRDV_STAMPS"] + os.environ.get("RDV_EXTRA_FLAGS", "").split())
+    if not os.environ.get("RDV_STAMPS_PREBUILT"):
+        build_variant(lib, ["-DRDV_STAMPS"] + os.environ.get("RDV_EXTRA_FLAGS", "").split())
     import torch
     from reinforcement_learning_rendezvous_amd import _native
     _native.LIB_PATH = lib
@@ -33,7 +36,7 @@ def main():
     L = _native.lib()
     L.rdv_debug_set_stamps.argtypes = [C.c_void_p, C.c_void_p]
     waves = (n + 255) // 256 * wpg
-    stamps = torch.zeros((waves, 10), dtype=torch.int64, device="cuda:0")
+    stamps = torch.zeros((2 * waves, 10), dtype=torch.int64, device="cuda:0")      # (the slot form's refill workgroups: the second half)
     gen = torch.Generator(device="cuda:0").manual_seed(1)
     acts = [(torch.rand((n, 6), device="cuda:0", generator=gen) * 2 - 1).contiguous() for _ in range(8)]
     env.reset()
@@ -46,7 +49,8 @@ def main():
             env.step(acts[t % 8])
         torch.cuda.synchronize()
         rows.append(stamps.cpu().numpy().copy())
-    s = np.stack(rows).astype(np.float64)            # [iter, wave, 10]
+    s_all = np.stack(rows).astype(np.float64)        # [iter, wave, 10]
+    s = s_all[:, :waves]
     role = (np.arange(waves) % wpg) // 4          # 0 step, 1 service (chaser half if svc = 2), 2 service (target half)
     cyc = s[:, :, 7] - s[:, :, 0]
     real = (s[:, :, 9] - s[:, :, 8]) * 10.0          # ns
@@ -63,6 +67,14 @@ def main():
               f"{np.median(ext):.0f} ns (p95 {np.percentile(ext, 95):.0f}, max {np.median(ext.max(axis=1)):.0f}) after the first wave")
     at_barrier = s[:, :, 3] - s[:, :, 0]
     print("cycles from entry to the barrier, median by role: " + ", ".join(f"{names[k]} {np.median(at_barrier[:, role == k]):.0f}" for k in range(1 + svc)))
+    refill = s_all[:, waves::wpg]                    # wave 0 of every refill workgroup (all zero in the speculative form)
+    if refill[:, :, 9].max() > 0:
+        ent, ext = (refill[:, :, 8] - t0) * 10.0, (refill[:, :, 9] - t0) * 10.0
+        step_ext = (s[:, role == 0, 9] - t0) * 10.0
+        print(f"refill waves: lifetime {np.median(ext - ent):.0f} ns (p95 {np.percentile(ext - ent, 95):.0f}) | enter {np.median(ent):.0f} ns (p95 {np.percentile(ent, 95):.0f}) and leave "
+              f"{np.median(ext):.0f} ns (p95 {np.percentile(ext, 95):.0f}, max {np.median(ext.max(axis=1)):.0f}) after the first wave | the last step wave leaves at "
+              f"{np.median(step_ext.max(axis=1)):.0f} ns, the last refill wave {np.median(ext.max(axis=1) - step_ext.max(axis=1)):+.0f} ns from it")
+        print(f"launch span with the refill waves: {np.median((s_all[:, :, 9].max(axis=1) - s[:, :, 8].min(axis=1)) * 10):.0f} ns")
     print(f"launch span seen by the waves (first entry -> last exit): {np.median((s[:, :, 9].max(axis=1) - s[:, :, 8].min(axis=1)) * 10):.0f} ns")
 
 
