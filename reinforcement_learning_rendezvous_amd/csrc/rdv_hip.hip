@@ -1,18 +1,16 @@
-// rdv_hip.hip — the host side of the MI355X-native batched rendezvous environment: the C ABI of include/rdv.h (env handles, policy
-// handles, parameter groups, argument checks, launches, snapshot / restore, statistics), the derivation of the thresholds the kernels
-// compare against (derive_params), rigid-body validation and the workspace layout.  Its kernels are instantiated from the headers
+// rdv_hip.hip — the host side of the MI355X-native batched rendezvous environment: the C ABI of include/rdv.h for env handles
+// (parameter groups, argument checks, launches, snapshot / restore, statistics) and rdv_rollout, the derivation of the thresholds the
+// kernels compare against (derive_params), rigid-body validation and the workspace layout.  Its kernels are instantiated from the headers
 // included below: rdv_step.h and rdv_fused.h (one-launch step kernels), rdv_cold.h (reset, state access, evaluation summary),
-// rdv_policy.h (the shipped actor / critic), rdv_rollout.h and rdv_step_many.h (persistent kernels); three small ones (parameter upload,
-// device error word, snapshot header) are defined here.  rdv_tiles.hip, rdv_general.hip, rdv_groups.hip (which instantiates the step
-// kernels of rdv_step.h and rdv_fused.h once more, with a tile table), rdv_policy_mlp.hip and rdv_policy_sets.hip (the actor / critic kernels of policy sets) are translation units of
-// their own, entered through the launch functions of their headers.
-// The data layout in HBM is described in rdv_kernels.h.
+// rdv_policy.h (the shipped actor / critic, launched through shipped_launch_*), rdv_rollout.h and rdv_step_many.h (persistent kernels);
+// three small ones (parameter upload, device error word, snapshot header) are defined here.  rdv_tiles.hip, rdv_general.hip,
+// rdv_groups.hip (which instantiates the step kernels of rdv_step.h and rdv_fused.h once more, with a tile table), rdv_policy_mlp.hip,
+// rdv_policy_lstm.hip, rdv_policy_sets.hip (the actor / critic kernels of policy sets) and rdv_advantages.hip are translation units of
+// their own, entered through the launch functions of their headers; rdv_policy_host.hip is the host side of the policy handles and has
+// no kernel (rdv_host.h: what it shares with this file).  The data layout in HBM is described in rdv_kernels.h.
 #include "rdv_device.h"
 #include "rdv_policy.h"
-#include "rdv_policy_mlp.h"
-#include "rdv_policy_lstm.h"
-#include "rdv_policy_sets.h"
-#include "rdv_advantages.h"
+#include "rdv_host.h"
 
 #include <hip/hip_runtime.h>
 
@@ -43,27 +41,13 @@ namespace rdv {
 // ---------------------------------------------------------------------------------------------------------------
 // host side
 static thread_local char g_err[512] = "";
-static int fail(int code, const char* fmt, ...) {
+int fail(int code, const char* fmt, ...) {   // (rdv_host.h: rdv_policy_host.hip reports through it too)
   va_list ap;
   va_start(ap, fmt);
   vsnprintf(g_err, sizeof g_err, fmt, ap);
   va_end(ap);
   return code;
 }
-// A failed HIP call also leaves its code in the runtime's per-thread "last error", which the NEXT caller of hipGetLastError() would
-// be handed — e.g. PyTorch's launch check after its next kernel, which would then raise for a failure that was ours and has been
-// reported through this ABI.  Reading it here clears it.
-#define RDV_HIP(call)                                                                                       \
-  do {                                                                                                      \
-    hipError_t err__ = (call);                                                                              \
-    if (err__ != hipSuccess) {                                                                              \
-      (void)hipGetLastError();                                                                              \
-      return fail(err__ == hipErrorOutOfMemory ? RDV_ERR_OUT_OF_MEMORY : RDV_ERR_HIP,                       \
-                  "%s failed: %s", #call, hipGetErrorString(err__));                                        \
-    }                                                                                                       \
-  } while (0)
-
-static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 static inline int64_t n_waves(int64_t n) { return (n + kBlock - 1) / kBlock * (kBlock / kWave); }
 // Chunk stride (in envs): chunk c of env i is vector c * stride + i of the workspace.  The seven chunk arrays are walked in
 // lockstep, and every BASELINE size puts them a power of two apart; padding each array to 64 KiB / 2 MiB and offsetting neighbours by
@@ -191,21 +175,6 @@ static void derive_params(const RdvParams& p, DevParams& d) {
   d.qt0_tiny = (0.25 * p.qt0_range * p.qt0_range <= kTinyU) ? 1 : 0;
 }
 
-struct DeviceGuard {
-  int prev = -1; bool switched = false;
-  explicit DeviceGuard(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
-};
-// `device` exists: checked by every call that creates a handle (`who`, for the message)
-static int check_device(const char* who, int device) {
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return fail(RDV_ERR_NO_DEVICE, "no HIP device available: this library has no CPU path");
-  if (device < 0 || device >= count) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: device %d out of range [0,%d)", who, device, count);
-  return RDV_OK;
-}
-
 // The derived parameter block travels as a kernel argument and is written by the device: ordered on the caller's stream like
 // every other launch (a hipMemcpy from host memory is ordered against the legacy stream only, not against PyTorch's non-blocking
 // side streams) and legal inside a stream capture (the values are baked into the graph node).
@@ -299,23 +268,12 @@ static void base_args(const RdvEnvBatch* h, StepArgs& A) {
 }
 static inline dim3 grid_for(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 static inline dim3 policy_grid(int64_t n) { return dim3((unsigned)((n + kPolBlockEnvs - 1) / kPolBlockEnvs)); }
-static inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 // f(ST()) with ST the storage type of a batch: the env kernels are templates over it.  (The deduced return type has the call
 // instantiated where it stands, so the kernels are emitted in the order of the launch sites in this file.)
 template <class F>
 static inline auto with_storage(int storage, F&& f) {
   if (storage == RDV_STORAGE_F32) return f(float());
   return f(double());
-}
-// The calls that synchronise `s` or allocate (rdv_get_stats, rdv_get_group_stats, rdv_eval_summary, rdv_eval_group_summary, rdv_restore,
-// rdv_set_param_groups) are not legal while `s` records a graph: the runtime would fail the call and invalidate the capture.  They ask
-// here before they touch the stream, and refuse with the capture intact (include/rdv.h, "Stream capture").
-static int refuse_in_capture(const char* who, hipStream_t s) {
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  RDV_HIP(hipStreamIsCapturing(s, &capturing));
-  if (capturing != hipStreamCaptureStatusNone)
-    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: not legal inside a stream capture (it synchronises the stream or allocates): call it outside the capture", who);
-  return RDV_OK;
 }
 // The handle's device error word, read back on `s` behind whatever the caller has enqueued there: this synchronises the stream and
 // leaves the bits in h->device_error (sticky).  `clear_stats_bytes`: rdv_get_stats zeroes that much of the statistics between the copy
@@ -364,6 +322,22 @@ static int upload_params(RdvEnvBatch* h, hipStream_t s) {
   hipLaunchKernelGGL(params_kernel, dim3(1), dim3(kWave), 0, s, h->dev, h->dev_params);
   RDV_HIP(hipGetLastError());
   return RDV_OK;
+}
+
+// The shipped actor / critic (rdv_policy.h: policy_act_kernel, policy_value_kernel) for rdv_policy_host.hip, in the shape of
+// rdv_policy_mlp.h's trio; the limit is raised when a handle that will run them is created.
+hipError_t rdv::shipped_raise_lds_limit() {
+  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
+  if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_value_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
+  return err;
+}
+void rdv::shipped_launch_act(int, const float* W, int, const float* obs, float* actions, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
+                             uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s) {
+  hipLaunchKernelGGL(policy_act_kernel, policy_grid(n), dim3(kPolBlock), kPolLdsBytes, s, W, obs, actions, n, deterministic, seed,
+                     counter, env_id_offset, raw_actions, log_prob);
+}
+void rdv::shipped_launch_value(int, const float* W, int, const float* obs, float* values, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(policy_value_kernel, policy_grid(n), dim3(kPolBlock), kPolLdsBytes, s, W, obs, values, n);
 }
 
 extern "C" {
@@ -442,617 +416,10 @@ int64_t rdv_workspace_bytes(int64_t n_envs, int storage) {
 
 int64_t rdv_num_envs(rdv_handle h) { return (h && h->magic == kMagic) ? h->n : -1; }
 
-// ---------------------------------------------------------------------------------------------------------------
-// The shipped actor (SB3 MlpPolicy 17-64-64-6 tanh) as one kernel: see csrc/rdv_policy.h
-struct RdvPolicyNet {
-  uint32_t magic;
-  int device;
-  float* weights;   // device, kPolFloats floats: the parameter block of csrc/rdv_policy.h (shipped_arch) or block_floats of csrc/rdv_policy_mlp.h
-  int out_dim;      // 6: the actor (rdv_policy_create), 1: the critic (rdv_critic_create)
-  RdvMlpSpec spec;
-  bool shipped_arch;   // 17-64-64-out tanh: policy_act_kernel / policy_value_kernel, and the persistent rollout_kernel
-  int block_floats;
-  float* staging;      // rdv_policy_set_weights / rdv_policy_set_member_weights: pinned host copies of the blocks in flight, one slot per
-                       // member (made by the first call, nullptr before)
-  std::vector<hipEvent_t> staged;   // ... per member, recorded behind the copy out of its slot: the next refresh of THAT member waits for it
-  // policy sets (csrc/rdv_policy_sets.h): `weights` holds n_members blocks of block_floats floats, then the tile table
-  int32_t n_members;   // 1: a plain handle, or a set of one member (the plain kernels read its one block)
-  int64_t rows;        // 0: a plain handle (any n); a set: the rows its members own together
-  const int32_t* tile_member;   // device: member index per 256-row tile (inside the allocation of `weights`); nullptr for a plain handle
-  // the recurrent policy (csrc/rdv_policy_lstm.h): lstm_hidden != 0, `weights` = [trunk block | cell block], `rows` = the rows whose state
-  // the handle owns; one device allocation `lstm_state` holds h, c, h_next, c_tmp ([rows, H] fp32 each), obs_tmp [rows, 17], pending [rows]
-  int32_t lstm_hidden;
-  float *lstm_state, *lstm_h, *lstm_c, *lstm_h_next, *lstm_c_tmp, *lstm_obs_tmp;
-  uint8_t* lstm_pending;
-};
-static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
-static constexpr uint32_t kPolicyMagic = 0x52445650u;   // "RDVP"
-
-static bool all_finite(const float* w, int count) {
-  for (int i = 0; i < count; ++i) if (!std::isfinite(w[i])) return false;
-  return true;
-}
-// A packed parameter block -> a policy handle on `device` (the caller's DeviceGuard holds it): the allocation, the upload and the dynamic-LDS
-// limit of the kernels that will read the block, which is above the 64 KiB default (72 KiB for the shipped architecture, up to 90,752 B for 4 x 64)
-static int finish_policy(const char* who, const std::vector<float>& packed, const RdvMlpSpec& spec, bool shipped_arch, int out_dim, int device, rdv_policy* out) {
-  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
-  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
-  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
-  p->n_members = 1; p->rows = 0; p->tile_member = nullptr; p->lstm_hidden = 0; p->lstm_state = nullptr;
-  p->spec = spec; p->shipped_arch = shipped_arch; p->block_floats = shipped_arch ? kPolFloats : (int)packed.size();
-  hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
-  if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (err == hipSuccess && !shipped_arch) err = mlp_raise_lds_limit();
-  if (err == hipSuccess && shipped_arch) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
-  if (err == hipSuccess && shipped_arch) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_value_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
-  if (err != hipSuccess) { (void)hipGetLastError(); if (p->weights) (void)hipFree(p->weights); delete p; return fail(RDV_ERR_HIP, "%s: %s", who, hipGetErrorString(err)); }
-  *out = p;
-  return RDV_OK;
-}
-
-// A 17-64-64-out_dim tanh MLP of the checkpoint (out_dim <= 6) as a parameter block on the device
-static int create_mlp(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
-                      const float* log_std, int out_dim, int device, rdv_policy* out) {
-  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create / rdv_critic_create: null argument");
-  if (int rc = check_device("rdv_policy_create", device)) return rc;
-  DeviceGuard guard(device);
-  if (!all_finite(w1, kPolHid * kPolIn) || !all_finite(w2, kPolHid * kPolHid) || !all_finite(w3, out_dim * kPolHid))
-    return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create: non-finite weight");
-  std::vector<float> packed;
-  pack_policy_weights(w1, b1, w2, b2, w3, b3, log_std, out_dim, packed);
-  return finish_policy("rdv_policy_create", packed, kDefaultMlpSpec, true, out_dim, device, out);
-}
-
-int rdv_policy_create(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
-                      const float* log_std, int device, rdv_policy* out) {
-  if (!log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create: null argument");
-  return create_mlp(w1, b1, w2, b2, w3, b3, log_std, kPolOut, device, out);
-}
-int rdv_critic_create(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
-                      int device, rdv_policy* out) {
-  return create_mlp(w1, b1, w2, b2, w3, b3, nullptr, 1, device, out);
-}
-
-// ---- other architectures (RdvMlpSpec): csrc/rdv_policy_mlp.h
-int rdv_mlp_spec_default(RdvMlpSpec* out_host) {
-  if (!out_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_mlp_spec_default: null argument");
-  *out_host = kDefaultMlpSpec;
-  return RDV_OK;
-}
-
-int rdv_mlp_spec_check(const RdvMlpSpec* spec) {
-  if (!spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_mlp_spec_check: null spec");
-  if (spec->n_hidden < 1 || spec->n_hidden > RDV_MLP_MAX_HIDDEN)
-    return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: n_hidden = %d is not in 1..%d", spec->n_hidden, RDV_MLP_MAX_HIDDEN);
-  for (int l = 0; l < RDV_MLP_MAX_HIDDEN; ++l) {
-    const int wd = spec->hidden[l];
-    if (l < spec->n_hidden ? (wd != 16 && wd != 32 && wd != 64) : wd != 0)
-      return fail(RDV_ERR_INVALID_ARGUMENT, l < spec->n_hidden ? "RdvMlpSpec: hidden[%d] = %d is not 16, 32 or 64" : "RdvMlpSpec: hidden[%d] = %d beyond n_hidden must be 0", l, wd);
-  }
-  if (spec->activation != RDV_ACT_TANH && spec->activation != RDV_ACT_RELU && spec->activation != RDV_ACT_SIGMOID)
-    return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: activation = %d is not an RdvActivation (0 tanh, 1 relu, 2 sigmoid)", spec->activation);
-  if (spec->reserved != 0) return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: reserved = %d must be 0", spec->reserved);
-  return RDV_OK;
-}
-
-static int create_mlp_spec(const RdvMlpSpec* spec, const float* const* weights, const float* const* biases, const float* log_std,
-                           int out_dim, int device, rdv_policy* out) {
-  if (!spec || !weights || !biases || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp / rdv_critic_create_mlp: null argument");
-  if (int rc = rdv_mlp_spec_check(spec)) return rc;
-  const int L = spec->n_hidden;
-  for (int l = 0; l <= L; ++l)
-    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp / rdv_critic_create_mlp: null weights or biases of layer %d", l);
-  // the shipped architecture IS rdv_policy_create / rdv_critic_create: same block, same kernels, the persistent rollout kernel
-#ifndef RDV_MLP_GENERAL_DEFAULT   // (diagnostic build, tools/mlp_arch_time.py: the shipped architecture through the general kernel, to time the two side by side)
-  if (std::memcmp(spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0)
-    return create_mlp(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, out_dim, device, out);
-#endif
-  if (int rc = check_device("rdv_policy_create_mlp", device)) return rc;
-  DeviceGuard guard(device);
-  for (int l = 0; l <= L; ++l) {
-    const int in_w = l == 0 ? kPolIn : spec->hidden[l - 1], out_w = l < L ? spec->hidden[l] : out_dim;
-    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create_mlp: non-finite weight in layer %d", l);
-  }
-  std::vector<float> packed;
-  pack_mlp_weights(*spec, out_dim, weights, biases, log_std, packed);
-  return finish_policy("rdv_policy_create_mlp", packed, *spec, false, out_dim, device, out);
-}
-
-int rdv_policy_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
-                          const float* log_std_host, int device, rdv_policy* out) {
-  if (!log_std_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp: null argument");
-  return create_mlp_spec(spec_host, weights_host, biases_host, log_std_host, kPolOut, device, out);
-}
-int rdv_critic_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
-                          int device, rdv_policy* out) {
-  return create_mlp_spec(spec_host, weights_host, biases_host, nullptr, 1, device, out);
-}
-
-int rdv_policy_get_spec(rdv_policy p, RdvMlpSpec* out_host) {
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  if (!out_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_get_spec: null argument");
-  *out_host = p->spec;
-  return RDV_OK;
-}
-
-// ---- refreshing a handle's weights (a learner's optimiser step): the block is packed on the host as at creation and copied into the
-// handle's device allocation from a pinned buffer of the handle's own, on the caller's stream
-// the checks of one network's host arrays against the handle's spec, and its packed block
-static int pack_for_handle(rdv_policy p, const char* who, const float* const* weights, const float* const* biases, const float* log_std, std::vector<float>& packed) {
-  if (!weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights_host or biases_host", who);
-  const bool actor = p->out_dim == kPolOut;
-  if (actor && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host is required for an actor", who);
-  if (!actor && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host must be null for a critic (rdv_critic_create)", who);
-  const int L = p->spec.n_hidden;
-  for (int l = 0; l <= L; ++l)
-    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights or biases of layer %d", who, l);
-  for (int l = 0; l <= L; ++l) {
-    const int in_w = l == 0 ? kPolIn : p->spec.hidden[l - 1], out_w = l < L ? p->spec.hidden[l] : p->out_dim;
-    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite weight in layer %d", who, l);
-  }
-  if (p->shipped_arch) pack_policy_weights(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, p->out_dim, packed);
-  else pack_mlp_weights(p->spec, p->out_dim, weights, biases, log_std, packed);
-  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "%s: the packed block has %d floats, the handle's %d", who, (int)packed.size(), p->block_floats);
-  return RDV_OK;
-}
-// block `member` of the handle <- packed, ordered on `stream`.  The pinned staging has one slot and one event per member, so refreshing
-// all members back to back never waits on the host for another member's copy, only for the previous refresh of the same member.
-static int upload_block(rdv_policy p, const char* who, int32_t member, const std::vector<float>& packed, void* stream) {
-  DeviceGuard guard(p->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  hipStreamCaptureStatus capturing = hipStreamCaptureStatusNone;
-  RDV_HIP(hipStreamIsCapturing(s, &capturing));
-  if (capturing != hipStreamCaptureStatusNone) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: not legal inside a stream capture (the staging buffer is reused by the next call)", who);
-  const size_t floats = (size_t)p->block_floats, bytes = floats * sizeof(float);
-  if (!p->staging) {
-    RDV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->staging), bytes * (size_t)p->n_members, hipHostMallocDefault));
-    p->staged.assign((size_t)p->n_members, nullptr);
-  }
-  hipEvent_t& ev = p->staged[(size_t)member];
-  if (!ev) RDV_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-  else RDV_HIP(hipEventSynchronize(ev));   // the previous refresh of this member has left its slot (usually long ago)
-  float* slot = p->staging + floats * (size_t)member;
-  std::memcpy(slot, packed.data(), bytes);
-  RDV_HIP(hipMemcpyAsync(p->weights + floats * (size_t)member, slot, bytes, hipMemcpyHostToDevice, s));
-  RDV_HIP(hipEventRecord(ev, s));
-  return RDV_OK;
-}
-
-int rdv_policy_set_weights(rdv_policy p, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_set_weights");
-  if (p->n_members > 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: this handle is a policy set of %d members: refresh one member with rdv_policy_set_member_weights", p->n_members);
-  std::vector<float> packed;
-  if (int rc = pack_for_handle(p, "rdv_policy_set_weights", weights, biases, log_std, packed)) return rc;
-  return upload_block(p, "rdv_policy_set_weights", 0, packed, stream);
-}
-
-int rdv_policy_set_member_weights(rdv_policy p, int32_t member, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_member_weights: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_set_weights");
-  if (member < 0 || member >= p->n_members) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_member_weights: member %d of %d", member, p->n_members);
-  std::vector<float> packed;
-  if (int rc = pack_for_handle(p, "rdv_policy_set_member_weights", weights, biases, log_std, packed)) return rc;
-  return upload_block(p, "rdv_policy_set_member_weights", member, packed, stream);
-}
-
-// ---- policy sets (csrc/rdv_policy_sets.h): n_members networks of one spec, member g owning sizes[g] consecutive rows
-static int create_set(const char* who, const RdvMlpSpec* spec, int32_t n_members, const int64_t* sizes, const float* const* const* weights,
-                      const float* const* const* biases, const float* const* log_std, int out_dim, int device, rdv_policy* out) {
-  if (!spec || !sizes || !weights || !biases || !out || (out_dim == kPolOut && !log_std)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  if (int rc = rdv_mlp_spec_check(spec)) return rc;
-  if (n_members < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_members = %d: a set has at least member 0", who, n_members);
-  // the set's rows are the sum of the sizes; the rule of parameter groups judges them: positive, every one but the last a multiple of 256
-  // (a size that is not positive, or would overflow the sum, ends the sum: the check then names it against a count nothing exceeds)
-  constexpr int64_t kMostRows = INT64_MAX / 2;
-  int64_t rows = 0;
-  for (int32_t g = 0; g < n_members && rows >= 0; ++g) rows = (sizes[g] > 0 && sizes[g] <= kMostRows - rows) ? rows + sizes[g] : -1;
-  if (int rc = rdv_param_groups_check(rows < 0 ? kMostRows : rows, n_members, sizes)) return rc;
-  const int L = spec->n_hidden;
-  for (int32_t g = 0; g < n_members; ++g) {
-    if (!weights[g] || !biases[g] || (out_dim == kPolOut && !log_std[g])) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights, biases or log_std of member %d", who, g);
-    for (int l = 0; l <= L; ++l) {
-      if (!weights[g][l] || !biases[g][l]) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights or biases of layer %d of member %d", who, l, g);
-      const int in_w = l == 0 ? kPolIn : spec->hidden[l - 1], out_w = l < L ? spec->hidden[l] : out_dim;
-      if (!all_finite(weights[g][l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite weight in layer %d of member %d", who, l, g);
-    }
-  }
-  if (int rc = check_device(who, device)) return rc;
-  DeviceGuard guard(device);
-#ifndef RDV_MLP_GENERAL_DEFAULT
-  const bool shipped = std::memcmp(spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0;
-#else
-  const bool shipped = false;
-#endif
-  // member blocks: exactly the bytes of stand-alone handles; then (256-byte aligned) the tile table
-  std::vector<float> all, packed;
-  for (int32_t g = 0; g < n_members; ++g) {
-    const float* ls = out_dim == kPolOut ? log_std[g] : nullptr;
-    if (shipped) pack_policy_weights(weights[g][0], biases[g][0], weights[g][1], biases[g][1], weights[g][2], biases[g][2], ls, out_dim, packed);
-    else pack_mlp_weights(*spec, out_dim, weights[g], biases[g], ls, packed);
-    if (g && packed.size() * (size_t)g != all.size()) return fail(RDV_ERR_HIP, "%s: member %d packs to %zu floats, member 0 to %zu", who, g, packed.size(), all.size() / (size_t)g);
-    all.insert(all.end(), packed.begin(), packed.end());
-  }
-  const size_t block_floats = packed.size();
-  const int64_t tiles = (rows + kSetTile - 1) / kSetTile;
-  std::vector<int32_t> table((size_t)tiles);
-  int64_t at = 0;
-  for (int32_t g = 0; g < n_members; ++g) {
-    for (int64_t t = at / kSetTile; t < (at + sizes[g] + kSetTile - 1) / kSetTile; ++t) table[(size_t)t] = g;
-    at += sizes[g];
-  }
-  const size_t table_at = (size_t)align_up((int64_t)(all.size() * sizeof(float)), 256);
-  // (finish_policy allocates and uploads ONE block; here the allocation also holds the other blocks and the table)
-  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
-  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
-  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
-  p->spec = *spec; p->shipped_arch = shipped; p->block_floats = (int)block_floats;
-  p->n_members = n_members; p->rows = rows; p->tile_member = nullptr; p->lstm_hidden = 0; p->lstm_state = nullptr;
-  hipError_t err = hipMalloc(&p->weights, table_at + table.size() * sizeof(int32_t));
-  if (err == hipSuccess) err = hipMemcpy(p->weights, all.data(), all.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMemcpy(reinterpret_cast<char*>(p->weights) + table_at, table.data(), table.size() * sizeof(int32_t), hipMemcpyHostToDevice);
-  // a set of one member runs the plain kernels on its one block; larger sets the set kernels
-  if (err == hipSuccess && !shipped) err = mlp_raise_lds_limit();
-  if (err == hipSuccess && shipped) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_act_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
-  if (err == hipSuccess && shipped) err = hipFuncSetAttribute(reinterpret_cast<const void*>(policy_value_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, kPolLdsBytes);
-  if (err == hipSuccess) err = sets_raise_lds_limit(shipped);
-  if (err != hipSuccess) { (void)hipGetLastError(); if (p->weights) (void)hipFree(p->weights); delete p; return fail(RDV_ERR_HIP, "%s: %s", who, hipGetErrorString(err)); }
-  p->tile_member = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p->weights) + table_at);
-  *out = p;
-  return RDV_OK;
-}
-
-int rdv_policy_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* const* weights_host,
-                          const float* const* const* biases_host, const float* const* log_std_host, int device, rdv_policy* out) {
-  return create_set("rdv_policy_set_create", spec_host, n_members, sizes_host, weights_host, biases_host, log_std_host, kPolOut, device, out);
-}
-int rdv_critic_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* const* weights_host,
-                          const float* const* const* biases_host, int device, rdv_policy* out) {
-  return create_set("rdv_critic_set_create", spec_host, n_members, sizes_host, weights_host, biases_host, nullptr, 1, device, out);
-}
-int32_t rdv_policy_num_members(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->n_members : -1; }
-int64_t rdv_policy_num_rows(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->rows : -1; }
-
-int rdv_policy_destroy(rdv_policy p) {
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  DeviceGuard guard(p->device);
-  (void)hipDeviceSynchronize();
-  (void)hipFree(p->weights);
-  if (p->lstm_state) (void)hipFree(p->lstm_state);
-  if (p->staging) (void)hipHostFree(p->staging);
-  for (hipEvent_t ev : p->staged) if (ev) (void)hipEventDestroy(ev);
-  p->magic = 0;
-  delete p;
-  return RDV_OK;
-}
-
-// the actor on n observation rows: clipped actions for the env and, optionally, the unclipped sample and its log-probability
-static int launch_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
-                             uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s) {
-  if (p->n_members > 1) {   // a policy set: each 256-row tile reads its member's block (csrc/rdv_policy_sets.h); n == p->rows, checked by the callers
-    sets_launch_act(p->shipped_arch, p->spec.activation, p->weights, p->block_floats, p->tile_member, obs, actions, n, deterministic, seed, counter,
-                    env_id_offset, raw_actions, log_prob, s);
-    RDV_HIP(hipGetLastError());
-    return RDV_OK;
-  }
-  if (!p->shipped_arch) {
-    mlp_launch_act(p->spec.activation, p->weights, p->block_floats, obs, actions, n, deterministic, seed, counter, env_id_offset, raw_actions, log_prob, s);
-    RDV_HIP(hipGetLastError());
-    return RDV_OK;
-  }
-  hipLaunchKernelGGL(policy_act_kernel, policy_grid(n), dim3(kPolBlock), kPolLdsBytes, s, p->weights, obs, actions, n, deterministic, seed,
-                     counter, env_id_offset, raw_actions, log_prob);
-  RDV_HIP(hipGetLastError());
-  return RDV_OK;
-}
-
-int rdv_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
-                   uint64_t env_id_offset, void* stream) {
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_act, which carries the state");
-  if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: this handle is a critic (rdv_critic_create)");
-  if (!obs || !actions || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs, actions and a positive n are required");
-  if (misaligned(obs, 16) || misaligned(actions, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs and actions must be 16-byte aligned");
-  if (p->rows && n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: n = %lld, the policy set owns %lld rows", (long long)n, (long long)p->rows);
-  DeviceGuard guard(p->device);
-  return launch_policy_act(p, obs, actions, n, deterministic, seed, counter, env_id_offset, nullptr, nullptr, static_cast<hipStream_t>(stream));
-}
-
-int rdv_policy_value(rdv_policy p, const float* obs, float* values, int64_t n, void* stream) {
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: this handle is a recurrent policy (rdv_lstm_critic_create): use rdv_lstm_value, which carries the state");
-  if (p->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: this handle is an actor (rdv_policy_create)");
-  if (!obs || !values || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs, values and a positive n are required");
-  if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs must be 16-byte aligned");
-  if (p->rows && n % p->rows != 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: n = %lld is not a multiple of the %lld rows the critic set owns", (long long)n, (long long)p->rows);
-  DeviceGuard guard(p->device);
-  if (p->n_members > 1) {   // flat row r belongs to env r mod rows: row blocks of the set's rows, the tile table serving each
-    sets_launch_value(p->shipped_arch, p->spec.activation, p->weights, p->block_floats, p->tile_member, obs, values, p->rows, n / p->rows, static_cast<hipStream_t>(stream));
-    RDV_HIP(hipGetLastError());
-    return RDV_OK;
-  }
-  if (!p->shipped_arch) {
-    mlp_launch_value(p->spec.activation, p->weights, p->block_floats, obs, values, n, static_cast<hipStream_t>(stream));
-    RDV_HIP(hipGetLastError());
-    return RDV_OK;
-  }
-  hipLaunchKernelGGL(policy_value_kernel, policy_grid(n), dim3(kPolBlock), kPolLdsBytes, static_cast<hipStream_t>(stream), p->weights, obs, values, n);
-  RDV_HIP(hipGetLastError());
-  return RDV_OK;
-}
-
-// ---- GAE (csrc/rdv_advantages.h)
-// gamma, gae_lambda and the sizes: what rdv_gae and rdv_rollout_advantages check alike, before any device is looked at
-static int check_gae_scalars(const char* who, int32_t n_steps, int64_t n, double gamma, double gae_lambda) {
-  if (n_steps <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_steps must be positive (got %d)", who, n_steps);
-  if (n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
-  if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
-  if (!std::isfinite(gae_lambda) || gae_lambda < 0.0 || gae_lambda > 1.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: gae_lambda must be in [0, 1] (got %g)", who, gae_lambda);
-  return RDV_OK;
-}
-// (diagnostics only: RDV_GAE_DEPTH = 2 | 4 | 8 | 16 picks the kernel's prefetch depth, for tools/gae_time.py; results do not depend on it)
-static int gae_depth() {
-  const char* x = getenv("RDV_GAE_DEPTH");
-  const int d = x ? atoi(x) : 0;
-  return (d == 2 || d == 4 || d == 8 || d == 16) ? d : 0;
-}
-
-int rdv_gae(const float* reward, const uint8_t* done, const float* values, const float* last_value, int32_t n_steps, int64_t n,
-            double gamma, double gae_lambda, float* advantages, float* returns, int device, void* stream) {
-  const struct { const void* p; const char* name; } ptrs[] = {{reward, "reward"}, {done, "done"}, {values, "values"}, {last_value, "last_value"},
-                                                              {advantages, "advantages"}, {returns, "returns"}};
-  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_gae: %s is null", a.name);
-  if (int rc = check_gae_scalars("rdv_gae", n_steps, n, gamma, gae_lambda)) return rc;
-  if (int rc = check_device("rdv_gae", device)) return rc;
-  DeviceGuard guard(device);
-  gae_launch(reward, done, values, last_value, n_steps, n, (float)gamma, (float)(gamma * gae_lambda), advantages, returns, gae_depth(), static_cast<hipStream_t>(stream));
-  RDV_HIP(hipGetLastError());
-  return RDV_OK;
-}
-
-// ---- the recurrent policy (csrc/rdv_policy_lstm.h): one LSTM layer in front of an RdvMlpSpec trunk, the state owned by the handle
-int rdv_lstm_spec_check(const RdvLstmSpec* spec) {
-  if (!spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_spec_check: null spec");
-  if (!lstm_hidden_ok(spec->hidden_size))
-    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: hidden_size = %d is not 32, 64, 128 or 256 (lstm_hidden_size)", spec->hidden_size);
-  if (spec->n_layers != 1)
-    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: n_layers = %d: one LSTM layer is served (n_lstm_layers = 1)", spec->n_layers);
-  if (spec->shared != 0)
-    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: shared = %d: separate actor and critic LSTMs are served (shared_lstm = False, enable_critic_lstm = True)", spec->shared);
-  if (spec->reserved != 0) return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: reserved = %d must be 0", spec->reserved);
-  return rdv_mlp_spec_check(&spec->trunk);
-}
-
-// null pointers and finiteness of a recurrent network's host arrays (the spec has been checked)
-static int check_lstm_arrays(const char* who, int H, const RdvMlpSpec& trunk, int out_dim, const float* w_ih, const float* w_hh, const float* b_ih,
-                             const float* b_hh, const float* const* weights, const float* const* biases, const float* log_std) {
-  if (!w_ih || !w_hh || !b_ih || !b_hh || !weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  if (out_dim == kPolOut && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host is required for an actor", who);
-  if (out_dim != kPolOut && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host must be null for a critic", who);
-  const int L = trunk.n_hidden;
-  for (int l = 0; l <= L; ++l)
-    if (!weights[l] || !biases[l]) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights or biases of trunk layer %d", who, l);
-  if (!all_finite(w_ih, 4 * H * kPolIn) || !all_finite(w_hh, 4 * H * H) || !all_finite(b_ih, 4 * H) || !all_finite(b_hh, 4 * H))
-    return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite LSTM weight", who);
-  for (int l = 0; l <= L; ++l) {
-    const int in_w = l == 0 ? H : trunk.hidden[l - 1], out_w = l < L ? trunk.hidden[l] : out_dim;
-    if (!all_finite(weights[l], out_w * in_w)) return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite weight in trunk layer %d", who, l);
-  }
-  return RDV_OK;
-}
-
-static int create_lstm(const char* who, const RdvLstmSpec* spec, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
-                       const float* const* weights, const float* const* biases, const float* log_std, int out_dim, int64_t n_rows, int device,
-                       rdv_policy* out) {
-  if (!spec || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
-  if (int rc = rdv_lstm_spec_check(spec)) return rc;
-  const int H = spec->hidden_size;
-  if (n_rows <= 0 || n_rows > (int64_t)1 << 31) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_rows = %lld must be in 1..2^31", who, (long long)n_rows);
-  if (int rc = check_lstm_arrays(who, H, spec->trunk, out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
-  if (int rc = check_device(who, device)) return rc;
-  DeviceGuard guard(device);
-  std::vector<float> packed;
-  pack_lstm_weights(H, spec->trunk, out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
-  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
-  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
-  p->magic = kPolicyMagic; p->device = device; p->weights = nullptr; p->out_dim = out_dim; p->staging = nullptr;
-  p->n_members = 1; p->rows = n_rows; p->tile_member = nullptr; p->lstm_hidden = H; p->lstm_state = nullptr;
-  p->spec = spec->trunk; p->shipped_arch = false; p->block_floats = (int)packed.size();
-  const size_t state_floats = (size_t)n_rows * (size_t)H, obs_floats = ((size_t)n_rows * kPolIn + 3) & ~(size_t)3;
-  const size_t bytes = (4 * state_floats + obs_floats) * sizeof(float) + (size_t)n_rows;
-  hipError_t err = hipMalloc(&p->weights, packed.size() * sizeof(float));
-  if (err == hipSuccess) err = hipMemcpy(p->weights, packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice);
-  if (err == hipSuccess) err = hipMalloc(&p->lstm_state, bytes);
-  if (err == hipSuccess) err = hipMemset(p->lstm_state, 0, bytes);
-  if (err == hipSuccess) {
-    p->lstm_h = p->lstm_state; p->lstm_c = p->lstm_h + state_floats; p->lstm_h_next = p->lstm_c + state_floats;
-    p->lstm_c_tmp = p->lstm_h_next + state_floats; p->lstm_obs_tmp = p->lstm_c_tmp + state_floats;
-    p->lstm_pending = reinterpret_cast<uint8_t*>(p->lstm_obs_tmp + obs_floats);
-    err = hipMemset(p->lstm_pending, 1, (size_t)n_rows);
-  }
-  if (err != hipSuccess) {
-    (void)hipGetLastError();
-    if (p->weights) (void)hipFree(p->weights);
-    if (p->lstm_state) (void)hipFree(p->lstm_state);
-    delete p;
-    return fail(err == hipErrorOutOfMemory ? RDV_ERR_OUT_OF_MEMORY : RDV_ERR_HIP, "%s: %s", who, hipGetErrorString(err));
-  }
-  *out = p;
-  return RDV_OK;
-}
-
-int rdv_lstm_policy_create(const RdvLstmSpec* spec_host, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
-                           const float* const* weights_host, const float* const* biases_host, const float* log_std_host, int64_t n_rows,
-                           int device, rdv_policy* out) {
-  return create_lstm("rdv_lstm_policy_create", spec_host, w_ih, w_hh, b_ih, b_hh, weights_host, biases_host, log_std_host, kPolOut, n_rows, device, out);
-}
-int rdv_lstm_critic_create(const RdvLstmSpec* spec_host, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
-                           const float* const* weights_host, const float* const* biases_host, int64_t n_rows, int device, rdv_policy* out) {
-  return create_lstm("rdv_lstm_critic_create", spec_host, w_ih, w_hh, b_ih, b_hh, weights_host, biases_host, nullptr, 1, n_rows, device, out);
-}
-int32_t rdv_lstm_hidden_size(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->lstm_hidden : -1; }
-
-#define RDV_CHECK_LSTM(p, who)                                                                        \
-  if (!(p) || (p)->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");      \
-  if (!(p)->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, who ": this handle is not a recurrent policy (rdv_lstm_policy_create / rdv_lstm_critic_create)")
-
-// one step of a recurrent handle on `s`: the cell (flags: u8 [rows] or nullptr), then the trunk; commit: the state advances (the
-// pending flags are the caller's business).  The caller's DeviceGuard holds the device; the arguments have been checked.
-static int launch_lstm(rdv_policy p, const float* obs, const uint8_t* flags, float* out, float* raw_actions, float* log_prob, bool commit,
-                       int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, hipStream_t s) {
-  lstm_launch_cell(p->lstm_hidden, p->weights, obs, flags, p->lstm_h, p->lstm_c, p->lstm_h_next, commit ? p->lstm_c : p->lstm_c_tmp, p->rows, s);
-  RDV_HIP(hipGetLastError());
-  lstm_launch_trunk(p->spec.activation, p->out_dim == 1, p->weights, p->lstm_h_next, commit ? p->lstm_h : nullptr, out, p->rows, deterministic, seed,
-                    counter, env_id_offset, raw_actions, log_prob, s);
-  RDV_HIP(hipGetLastError());
-  return RDV_OK;
-}
-
-int rdv_lstm_act(rdv_policy p, const float* obs, const uint8_t* episode_start, float* actions, float* raw_actions, float* log_prob, int64_t n,
-                 int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, void* stream) {
-  RDV_CHECK_LSTM(p, "rdv_lstm_act");
-  if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: this handle is a critic (rdv_lstm_critic_create)");
-  if (!obs || !actions) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: obs and actions are required");
-  if (n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: n = %lld, the handle owns the state of %lld rows", (long long)n, (long long)p->rows);
-  if (misaligned(obs, 16) || misaligned(actions, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: obs and actions must be 16-byte aligned");
-  DeviceGuard guard(p->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = launch_lstm(p, obs, episode_start, actions, raw_actions, log_prob, true, deterministic ? 1 : 0, seed, counter, env_id_offset, s)) return rc;
-  RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, s));   // the state has moved past whatever start was pending
-  return RDV_OK;
-}
-
-int rdv_lstm_value(rdv_policy p, const float* obs, const uint8_t* episode_start, float* values, int64_t n, int commit, void* stream) {
-  RDV_CHECK_LSTM(p, "rdv_lstm_value");
-  if (p->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: this handle is an actor (rdv_lstm_policy_create)");
-  if (!obs || !values) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: obs and values are required");
-  if (n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: n = %lld, the handle owns the state of %lld rows", (long long)n, (long long)p->rows);
-  if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: obs must be 16-byte aligned");
-  DeviceGuard guard(p->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (int rc = launch_lstm(p, obs, episode_start, values, nullptr, nullptr, commit != 0, 1, 0, 0, 0, s)) return rc;
-  if (commit) RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, s));
-  return RDV_OK;
-}
-
-int rdv_lstm_get_state(rdv_policy p, float* h_out, float* c_out, void* stream) {
-  RDV_CHECK_LSTM(p, "rdv_lstm_get_state");
-  if (!h_out || !c_out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_get_state: h_out and c_out are required");
-  DeviceGuard guard(p->device);
-  const size_t bytes = (size_t)p->rows * (size_t)p->lstm_hidden * sizeof(float);
-  RDV_HIP(hipMemcpyAsync(h_out, p->lstm_h, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  RDV_HIP(hipMemcpyAsync(c_out, p->lstm_c, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  return RDV_OK;
-}
-
-int rdv_lstm_set_state(rdv_policy p, const float* h, const float* c, void* stream) {
-  RDV_CHECK_LSTM(p, "rdv_lstm_set_state");
-  if (!h || !c) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_set_state: h and c are required");
-  DeviceGuard guard(p->device);
-  const size_t bytes = (size_t)p->rows * (size_t)p->lstm_hidden * sizeof(float);
-  RDV_HIP(hipMemcpyAsync(p->lstm_h, h, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  RDV_HIP(hipMemcpyAsync(p->lstm_c, c, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
-  RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, static_cast<hipStream_t>(stream)));
-  return RDV_OK;
-}
-
-int rdv_lstm_reset_state(rdv_policy p, const uint8_t* mask, void* stream) {
-  RDV_CHECK_LSTM(p, "rdv_lstm_reset_state");
-  DeviceGuard guard(p->device);
-  lstm_launch_reset(p->lstm_h, p->lstm_c, mask, p->rows, p->lstm_hidden, static_cast<hipStream_t>(stream));
-  RDV_HIP(hipGetLastError());
-  return RDV_OK;
-}
-
-int rdv_lstm_set_weights(rdv_policy p, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* const* weights,
-                         const float* const* biases, const float* log_std, void* stream) {
-  RDV_CHECK_LSTM(p, "rdv_lstm_set_weights");
-  if (int rc = check_lstm_arrays("rdv_lstm_set_weights", p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
-  std::vector<float> packed;
-  pack_lstm_weights(p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
-  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "rdv_lstm_set_weights: the packed block has %d floats, the handle's %d", (int)packed.size(), p->block_floats);
-  return upload_block(p, "rdv_lstm_set_weights", 0, packed, stream);
-}
-
-// rdv_rollout with a recurrent actor: rdv_lstm_act + rdv_step, n_steps times on `stream` (the caller has checked the arguments)
-static int rollout_lstm(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut* out, int deterministic, uint64_t noise_seed,
-                        uint64_t noise_counter0, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int64_t n = h->n;
-  float* obs_t = obs_row_target(h, out->obs, 0);
-  if (int rc = rdv_observe(h, obs_t, stream)) return rc;
-  for (int32_t t = 0; t < n_steps; ++t) {
-    if (int rc = obs_row_flush(h, out->obs, t, s)) return rc;
-    const uint8_t* flags = t == 0 ? p->lstm_pending : out->done + (int64_t)(t - 1) * n;
-    if (int rc = launch_lstm(p, obs_t, flags, h->act_tmp, out->actions + (int64_t)t * n * RDV_ACT_DIM, out->log_prob ? out->log_prob + (int64_t)t * n : nullptr,
-                             true, deterministic ? 1 : 0, noise_seed, noise_counter0 + (uint64_t)t, h->env_id_offset, s)) return rc;
-    RdvStepOut so;
-    std::memset(&so, 0, sizeof so);
-    float* obs_next = (t + 1 < n_steps) ? obs_row_target(h, out->obs, t + 1) : out->last_obs;
-    so.obs = obs_next; so.reward = out->reward + (int64_t)t * n; so.done = out->done + (int64_t)t * n;
-    if (int rc = rdv_step(h, h->act_tmp, &so, stream)) return rc;
-    obs_t = obs_next;
-  }
-  RDV_HIP(hipMemcpyAsync(p->lstm_pending, out->done + (int64_t)(n_steps - 1) * n, (size_t)n, hipMemcpyDeviceToDevice, s));
-  return RDV_OK;
-}
-
-// rdv_rollout_advantages with a recurrent critic: n_steps committing steps in time order, one non-committing step on last_obs, GAE
-static int advantages_lstm(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,
-                           const RdvAdvantageOut* out, void* stream) {
-  DeviceGuard guard(critic->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool aligned = (n & 3) == 0;                                   // row t of rows->obs is 16-byte aligned if and only if n % 4 == 0
-  for (int32_t t = 0; t < n_steps; ++t) {
-    const float* obs_t = rows->obs + (int64_t)t * n * RDV_OBS_DIM;
-    if (!aligned) {
-      RDV_HIP(hipMemcpyAsync(critic->lstm_obs_tmp, obs_t, (size_t)n * RDV_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
-      obs_t = critic->lstm_obs_tmp;
-    }
-    const uint8_t* flags = t == 0 ? critic->lstm_pending : rows->done + (int64_t)(t - 1) * n;
-    if (int rc = launch_lstm(critic, obs_t, flags, out->values + (int64_t)t * n, nullptr, nullptr, true, 1, 0, 0, 0, s)) return rc;
-  }
-  const uint8_t* last_done = rows->done + (int64_t)(n_steps - 1) * n;
-  if (int rc = launch_lstm(critic, rows->last_obs, last_done, out->last_value, nullptr, nullptr, false, 1, 0, 0, 0, s)) return rc;
-  RDV_HIP(hipMemcpyAsync(critic->lstm_pending, last_done, (size_t)n, hipMemcpyDeviceToDevice, s));
-  gae_launch(rows->reward, rows->done, out->values, out->last_value, n_steps, n, (float)gamma, (float)(gamma * gae_lambda), out->advantages, out->returns,
-             gae_depth(), s);
-  RDV_HIP(hipGetLastError());
-  return RDV_OK;
-}
-
-int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,
-                           const RdvAdvantageOut* out, void* stream) {
-  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows is null");
-  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: out is null");
-  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->reward, "rows->reward"}, {rows->done, "rows->done"},
-                                                              {rows->last_obs, "rows->last_obs"}, {out->values, "out->values"}, {out->last_value, "out->last_value"},
-                                                              {out->advantages, "out->advantages"}, {out->returns, "out->returns"}};
-  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: %s is null", a.name);
-  if (int rc = check_gae_scalars("rdv_rollout_advantages", n_steps, n, gamma, gae_lambda)) return rc;
-  if (!critic || critic->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
-  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: this handle is an actor (rdv_policy_create)");
-  if (critic->lstm_hidden) {
-    if (n != critic->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: n = %lld, the recurrent critic owns the state of %lld rows", (long long)n, (long long)critic->rows);
-    if (misaligned(rows->obs, 16) || misaligned(rows->last_obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows->obs and rows->last_obs must be 16-byte aligned");
-    return advantages_lstm(critic, rows, n_steps, n, gamma, gae_lambda, out, stream);
-  }
-  if (critic->rows && n != critic->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: n = %lld, the critic set owns %lld rows", (long long)n, (long long)critic->rows);
-  if (misaligned(rows->obs, 16) || misaligned(rows->last_obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows->obs and rows->last_obs must be 16-byte aligned");
-  // the critic at call time over the rows the actor saw, then over the observation after the last step: rdv_policy_value's own launches
-  if (int rc = rdv_policy_value(critic, rows->obs, out->values, (int64_t)n_steps * n, stream)) return rc;
-  if (int rc = rdv_policy_value(critic, rows->last_obs, out->last_value, n, stream)) return rc;
-  DeviceGuard guard(critic->device);
-  gae_launch(rows->reward, rows->done, out->values, out->last_value, n_steps, n, (float)gamma, (float)(gamma * gae_lambda), out->advantages, out->returns,
-             gae_depth(), static_cast<hipStream_t>(stream));
-  RDV_HIP(hipGetLastError());
-  return RDV_OK;
-}
-
 int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut* out, int deterministic, uint64_t noise_seed,
                 uint64_t noise_counter0, void* stream) {
   RDV_CHECK_HANDLE(h);
-  if (!p || p->magic != kPolicyMagic) return fail(RDV_ERR_BAD_HANDLE, "invalid rdv_policy");
+  RDV_CHECK_POLICY(p);
   if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: this handle is a critic (rdv_critic_create)");
   if (p->device != h->device) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: the policy lives on device %d, the envs on device %d", p->device, h->device);
   if (n_steps <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout: n_steps must be positive (got %d)", n_steps);
@@ -1065,20 +432,20 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
   RDV_CHECK_FAULT(h);
   DeviceGuard guard(h->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (p->lstm_hidden) return rollout_lstm(h, p, n_steps, out, deterministic, noise_seed, noise_counter0, stream);
-  if (h->general || h->n_groups || !p->shipped_arch || p->n_members > 1) {
+  if (h->general || h->n_groups || !p->shipped_arch || p->n_members > 1 || p->lstm_hidden) {
     // General rigid bodies, parameter groups (no grouped persistent kernel), policy sets of more than one member (no persistent kernel for
-    // sets) and policies of another architecture than the shipped one (the
-    // persistent kernel's registers and LDS are laid out for 17-64-64-6 tanh): rdv_policy_act + rdv_step, n_steps times, on `stream` — the definition of this call's results, used as
-    // its implementation.  The per-lane RK45 inside the 168-register budget of the persistent kernel's 12-wave workgroup spilled 120
-    // dwords per lane and ran SLOWER than this loop (72 against 58 us per step at 65,536 envs, round 2): not offered any more.
+    // sets), recurrent policies and policies of another architecture than the shipped one (the persistent kernel's registers and LDS are
+    // laid out for 17-64-64-6 tanh): rdv_policy_act (rdv_lstm_act for a recurrent actor) + rdv_step, n_steps times, on `stream` — the
+    // definition of this call's results, used as its implementation.  The per-lane RK45 inside the 168-register budget of the persistent
+    // kernel's 12-wave workgroup spilled 120 dwords per lane and ran SLOWER than this loop (72 against 58 us per step at 65,536 envs,
+    // round 2): not offered any more.
     const int64_t n = h->n;
     float* obs_t = obs_row_target(h, out->obs, 0);
     if (int rc = rdv_observe(h, obs_t, stream)) return rc;
     for (int32_t t = 0; t < n_steps; ++t) {
       if (int rc = obs_row_flush(h, out->obs, t, s)) return rc;
-      if (int rc = launch_policy_act(p, obs_t, h->act_tmp, n, deterministic ? 1 : 0, noise_seed, noise_counter0 + (uint64_t)t, h->env_id_offset,
-                                     out->actions + (int64_t)t * n * RDV_ACT_DIM, out->log_prob ? out->log_prob + (int64_t)t * n : nullptr, s)) return rc;
+      if (int rc = policy_act_step(p, t, obs_t, out->done, h->act_tmp, n, deterministic ? 1 : 0, noise_seed, noise_counter0 + (uint64_t)t, h->env_id_offset,
+                                   out->actions + (int64_t)t * n * RDV_ACT_DIM, out->log_prob ? out->log_prob + (int64_t)t * n : nullptr, s)) return rc;
       RdvStepOut so;
       std::memset(&so, 0, sizeof so);
       float* obs_next = (t + 1 < n_steps) ? obs_row_target(h, out->obs, t + 1) : out->last_obs;
@@ -1086,6 +453,8 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
       if (int rc = rdv_step(h, h->act_tmp, &so, stream)) return rc;
       obs_t = obs_next;
     }
+    // a recurrent actor's state has moved past the last step: what was done there is the start its next call finds pending
+    if (p->lstm_hidden) RDV_HIP(hipMemcpyAsync(p->lstm_pending, out->done + (int64_t)(n_steps - 1) * n, (size_t)n, hipMemcpyDeviceToDevice, s));
     return RDV_OK;
   }
   h->raw_state = false;   // the rollout kernel integrates injected (unnormalised) quaternions itself

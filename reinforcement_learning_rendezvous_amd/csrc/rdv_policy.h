@@ -413,6 +413,13 @@ __device__ __forceinline__ void actor_outputs(const float* sd, int lane, int64_t
   }
 }
 
+// The launches of the two kernels below and their dynamic-LDS limit (rdv_hip.hip, where the kernels are instantiated), in the shape of
+// rdv_policy_mlp.h's trio; `activation` (tanh) and `block_floats` (kPolFloats) are not read.  Internal to the library: hidden.
+__attribute__((visibility("hidden"))) hipError_t shipped_raise_lds_limit();
+__attribute__((visibility("hidden"))) void shipped_launch_act(int activation, const float* W, int block_floats, const float* obs, float* actions, int64_t n, int deterministic,
+                                                              uint64_t seed, uint64_t counter, uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s);
+__attribute__((visibility("hidden"))) void shipped_launch_value(int activation, const float* W, int block_floats, const float* obs, float* values, int64_t n, hipStream_t s);
+
 #ifndef RDV_POLICY_FUNCTIONS_ONLY   // (rdv_policy_mlp.hip takes the functions above; the two kernels belong to rdv_hip.hip)
 // raw_actions [n,6] / log_prob [n] (both nullable): the sample BEFORE clipping and its log-density, the rows SB3's RolloutBuffer keeps
 // (rdv_rollout's act + step form for general rigid bodies asks for them; rdv_policy_act does not).

@@ -1,0 +1,535 @@
+// rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
+// value / set-weights entry points, policy sets, the recurrent policy (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
+// rdv_rollout_advantages, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
+// rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
+// mlp_*, sets_*, lstm_*, gae_launch), so an edit to an argument check recompiles no kernel.
+#define RDV_POLICY_FUNCTIONS_ONLY
+#include "rdv_policy.h"
+#include "rdv_policy_mlp.h"
+#include "rdv_policy_lstm.h"
+#include "rdv_policy_sets.h"
+#include "rdv_advantages.h"
+#include "rdv_host.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <new>
+
+using namespace rdv;
+
+// the shipped architecture, which IS rdv_policy_create / rdv_critic_create: same block, same kernels, the persistent rollout kernel
+static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
+static bool is_shipped(const RdvMlpSpec* spec) {
+#ifndef RDV_MLP_GENERAL_DEFAULT   // (diagnostic build, tools/mlp_arch_time.py: the shipped architecture through the general kernel, to time the two side by side)
+  return std::memcmp(spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0;
+#else
+  return false;
+#endif
+}
+static bool all_finite(const float* w, int count) {
+  for (int i = 0; i < count; ++i) if (!std::isfinite(w[i])) return false;
+  return true;
+}
+// The layers of a trunk (first input width in0, then `spec`, then out_dim), l = 0 .. n_hidden: null pointers (kNull), non-finite weights
+// (kFinite), or both layer by layer.  `where`: how the message names layer l — "layer %d", "trunk layer %d", "layer %d of member %d" (g).
+enum { kNull = 1, kFinite = 2 };
+static int check_layers(int what, const char* who, const char* where, int g, int in0, const RdvMlpSpec& spec, int out_dim,
+                        const float* const* weights, const float* const* biases) {
+  const int L = spec.n_hidden;
+  char layer[48];
+  for (int l = 0; l <= L; ++l) {
+    const int in_w = l == 0 ? in0 : spec.hidden[l - 1], out_w = l < L ? spec.hidden[l] : out_dim;
+    const bool null = (what & kNull) && (!weights[l] || !biases[l]);
+    if (!null && (!(what & kFinite) || all_finite(weights[l], out_w * in_w))) continue;
+    std::snprintf(layer, sizeof layer, where, l, g);
+    return null ? fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights or biases of %s", who, layer)
+                : fail(RDV_ERR_BAD_PARAMS, "%s: non-finite weight in %s", who, layer);
+  }
+  return RDV_OK;
+}
+// one network's parameter block, as the kernels of its architecture read it
+static void pack_block(bool shipped, const RdvMlpSpec& spec, int out_dim, const float* const* weights, const float* const* biases, const float* log_std,
+                       std::vector<float>& packed) {
+  if (shipped) pack_policy_weights(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, out_dim, packed);
+  else pack_mlp_weights(spec, out_dim, weights, biases, log_std, packed);
+}
+
+// what rdv_policy_destroy frees, and a constructor that fails half-way
+static void free_policy(RdvPolicyNet* p) {
+  (void)hipFree(p->weights);
+  if (p->lstm_state) (void)hipFree(p->lstm_state);
+  if (p->staging) (void)hipHostFree(p->staging);
+  for (hipEvent_t ev : p->staged) if (ev) (void)hipEventDestroy(ev);
+  p->magic = 0; delete p;
+}
+// THE constructor of a policy handle on `device` (the caller's DeviceGuard holds it).  `blocks`: the n_members packed blocks back to back,
+// uploaded to the `weights` allocation; `table` (a set: non-null): the tile table, placed behind them at the next multiple of 256 bytes.
+// lstm_hidden != 0: the state allocation for `rows` rows, zeroed, every row's start pending.  Otherwise the dynamic-LDS limits of exactly
+// the kernels the handle will run are raised above the 64 KiB default (72 KiB for the shipped architecture, up to 90,752 B for 4 x 64).
+static int make_policy(const char* who, int device, int out_dim, const RdvMlpSpec& spec, bool shipped, int32_t n_members, int64_t rows,
+                       int32_t lstm_hidden, const std::vector<float>& blocks, const std::vector<int32_t>* table, rdv_policy* out) {
+  RdvPolicyNet* p = new (std::nothrow) RdvPolicyNet();
+  if (!p) return fail(RDV_ERR_OUT_OF_MEMORY, "%s: host allocation failed", who);
+  p->device = device; p->out_dim = out_dim; p->spec = spec; p->shipped_arch = shipped; p->block_floats = (int)(blocks.size() / (size_t)n_members);
+  p->n_members = n_members; p->rows = rows; p->lstm_hidden = lstm_hidden;
+  const size_t block_bytes = blocks.size() * sizeof(float), table_at = (size_t)align_up((int64_t)block_bytes, 256);
+  hipError_t err = hipMalloc(&p->weights, table ? table_at + table->size() * sizeof(int32_t) : block_bytes);
+  if (err == hipSuccess) err = hipMemcpy(p->weights, blocks.data(), block_bytes, hipMemcpyHostToDevice);
+  if (err == hipSuccess && table) {
+    p->tile_member = reinterpret_cast<const int32_t*>(reinterpret_cast<const char*>(p->weights) + table_at);
+    err = hipMemcpy(const_cast<int32_t*>(p->tile_member), table->data(), table->size() * sizeof(int32_t), hipMemcpyHostToDevice);
+  }
+  if (lstm_hidden) {
+    const size_t state_floats = (size_t)rows * (size_t)lstm_hidden, obs_floats = ((size_t)rows * kPolIn + 3) & ~(size_t)3;
+    const size_t bytes = (4 * state_floats + obs_floats) * sizeof(float) + (size_t)rows;
+    if (err == hipSuccess) err = hipMalloc(&p->lstm_state, bytes);
+    if (err == hipSuccess) err = hipMemset(p->lstm_state, 0, bytes);
+    if (err == hipSuccess) {
+      p->lstm_h = p->lstm_state; p->lstm_c = p->lstm_h + state_floats; p->lstm_h_next = p->lstm_c + state_floats;
+      p->lstm_c_tmp = p->lstm_h_next + state_floats; p->lstm_obs_tmp = p->lstm_c_tmp + state_floats;
+      p->lstm_pending = reinterpret_cast<uint8_t*>(p->lstm_obs_tmp + obs_floats);
+      err = hipMemset(p->lstm_pending, 1, (size_t)rows);
+    }
+  } else {   // a set of one member runs the plain kernels on its one block; larger sets the set kernels
+    if (err == hipSuccess) err = shipped ? shipped_raise_lds_limit() : mlp_raise_lds_limit();
+    if (err == hipSuccess && table) err = sets_raise_lds_limit(shipped);
+  }
+  if (err != hipSuccess) { (void)hipGetLastError(); free_policy(p); return fail(err == hipErrorOutOfMemory ? RDV_ERR_OUT_OF_MEMORY : RDV_ERR_HIP, "%s: %s", who, hipGetErrorString(err)); }
+  *out = p;
+  return RDV_OK;
+}
+
+// A 17-64-64-out_dim tanh MLP of the checkpoint (out_dim <= 6) as a parameter block on the device
+static int create_mlp(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                      const float* log_std, int out_dim, int device, rdv_policy* out) {
+  if (!w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create / rdv_critic_create: null argument");
+  if (int rc = check_device("rdv_policy_create", device)) return rc;
+  DeviceGuard guard(device);
+  if (!all_finite(w1, kPolHid * kPolIn) || !all_finite(w2, kPolHid * kPolHid) || !all_finite(w3, out_dim * kPolHid))
+    return fail(RDV_ERR_BAD_PARAMS, "rdv_policy_create: non-finite weight");
+  const float *const w[3] = {w1, w2, w3}, *const b[3] = {b1, b2, b3};
+  std::vector<float> packed;
+  pack_block(true, kDefaultMlpSpec, out_dim, w, b, log_std, packed);
+  return make_policy("rdv_policy_create", device, out_dim, kDefaultMlpSpec, true, 1, 0, 0, packed, nullptr, out);
+}
+static int create_mlp_spec(const RdvMlpSpec* spec, const float* const* weights, const float* const* biases, const float* log_std,
+                           int out_dim, int device, rdv_policy* out) {
+  if (!spec || !weights || !biases || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp / rdv_critic_create_mlp: null argument");
+  if (int rc = rdv_mlp_spec_check(spec)) return rc;
+  if (int rc = check_layers(kNull, "rdv_policy_create_mlp / rdv_critic_create_mlp", "layer %d", 0, kPolIn, *spec, out_dim, weights, biases)) return rc;
+  if (is_shipped(spec)) return create_mlp(weights[0], biases[0], weights[1], biases[1], weights[2], biases[2], log_std, out_dim, device, out);
+  if (int rc = check_device("rdv_policy_create_mlp", device)) return rc;
+  DeviceGuard guard(device);
+  if (int rc = check_layers(kFinite, "rdv_policy_create_mlp", "layer %d", 0, kPolIn, *spec, out_dim, weights, biases)) return rc;
+  std::vector<float> packed;
+  pack_block(false, *spec, out_dim, weights, biases, log_std, packed);
+  return make_policy("rdv_policy_create_mlp", device, out_dim, *spec, false, 1, 0, 0, packed, nullptr, out);
+}
+
+// ---- refreshing a handle's weights (a learner's optimiser step): the block is packed on the host as at creation and copied into the
+// handle's device allocation from a pinned buffer of the handle's own, on the caller's stream
+// block `member` of the handle <- packed, ordered on `stream`.  The pinned staging has one slot and one event per member, so refreshing
+// all members back to back never waits on the host for another member's copy, only for the previous refresh of the same member.
+static int upload_block(rdv_policy p, const char* who, int32_t member, const std::vector<float>& packed, void* stream) {
+  DeviceGuard guard(p->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = refuse_in_capture(who, s, "(the staging buffer is reused by the next call)")) return rc;
+  const size_t floats = (size_t)p->block_floats, bytes = floats * sizeof(float);
+  if (!p->staging) {
+    RDV_HIP(hipHostMalloc(reinterpret_cast<void**>(&p->staging), bytes * (size_t)p->n_members, hipHostMallocDefault));
+    p->staged.assign((size_t)p->n_members, nullptr);
+  }
+  hipEvent_t& ev = p->staged[(size_t)member];
+  if (!ev) RDV_HIP(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+  else RDV_HIP(hipEventSynchronize(ev));   // the previous refresh of this member has left its slot (usually long ago)
+  float* slot = p->staging + floats * (size_t)member;
+  std::memcpy(slot, packed.data(), bytes);
+  RDV_HIP(hipMemcpyAsync(p->weights + floats * (size_t)member, slot, bytes, hipMemcpyHostToDevice, s));
+  RDV_HIP(hipEventRecord(ev, s));
+  return RDV_OK;
+}
+// one network's host arrays checked against the handle's spec, packed, and uploaded as block `member`
+static int refresh_member(rdv_policy p, const char* who, int32_t member, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  if (!weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights_host or biases_host", who);
+  const bool actor = p->out_dim == kPolOut;
+  if (actor && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host is required for an actor", who);
+  if (!actor && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host must be null for a critic (rdv_critic_create)", who);
+  if (int rc = check_layers(kNull, who, "layer %d", 0, kPolIn, p->spec, p->out_dim, weights, biases)) return rc;
+  if (int rc = check_layers(kFinite, who, "layer %d", 0, kPolIn, p->spec, p->out_dim, weights, biases)) return rc;
+  std::vector<float> packed;
+  pack_block(p->shipped_arch, p->spec, p->out_dim, weights, biases, log_std, packed);
+  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "%s: the packed block has %d floats, the handle's %d", who, (int)packed.size(), p->block_floats);
+  return upload_block(p, who, member, packed, stream);
+}
+
+// ---- policy sets (csrc/rdv_policy_sets.h): n_members networks of one spec, member g owning sizes[g] consecutive rows
+static int create_set(const char* who, const RdvMlpSpec* spec, int32_t n_members, const int64_t* sizes, const float* const* const* weights,
+                      const float* const* const* biases, const float* const* log_std, int out_dim, int device, rdv_policy* out) {
+  if (!spec || !sizes || !weights || !biases || !out || (out_dim == kPolOut && !log_std)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (int rc = rdv_mlp_spec_check(spec)) return rc;
+  if (n_members < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_members = %d: a set has at least member 0", who, n_members);
+  // the set's rows are the sum of the sizes; the rule of parameter groups judges them: positive, every one but the last a multiple of 256
+  // (a size that is not positive, or would overflow the sum, ends the sum: the check then names it against a count nothing exceeds)
+  constexpr int64_t kMostRows = INT64_MAX / 2;
+  int64_t rows = 0;
+  for (int32_t g = 0; g < n_members && rows >= 0; ++g) rows = (sizes[g] > 0 && sizes[g] <= kMostRows - rows) ? rows + sizes[g] : -1;
+  if (int rc = rdv_param_groups_check(rows < 0 ? kMostRows : rows, n_members, sizes)) return rc;
+  for (int32_t g = 0; g < n_members; ++g) {
+    if (!weights[g] || !biases[g] || (out_dim == kPolOut && !log_std[g])) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights, biases or log_std of member %d", who, g);
+    if (int rc = check_layers(kNull | kFinite, who, "layer %d of member %d", g, kPolIn, *spec, out_dim, weights[g], biases[g])) return rc;
+  }
+  if (int rc = check_device(who, device)) return rc;
+  DeviceGuard guard(device);
+  const bool shipped = is_shipped(spec);
+  // member blocks: exactly the bytes of stand-alone handles; then (256-byte aligned) the tile table
+  std::vector<float> all, packed;
+  for (int32_t g = 0; g < n_members; ++g) {
+    pack_block(shipped, *spec, out_dim, weights[g], biases[g], out_dim == kPolOut ? log_std[g] : nullptr, packed);
+    if (g && packed.size() * (size_t)g != all.size()) return fail(RDV_ERR_HIP, "%s: member %d packs to %zu floats, member 0 to %zu", who, g, packed.size(), all.size() / (size_t)g);
+    all.insert(all.end(), packed.begin(), packed.end());
+  }
+  std::vector<int32_t> table((size_t)((rows + kSetTile - 1) / kSetTile));
+  int64_t at = 0;
+  for (int32_t g = 0; g < n_members; ++g) {
+    for (int64_t t = at / kSetTile; t < (at + sizes[g] + kSetTile - 1) / kSetTile; ++t) table[(size_t)t] = g;
+    at += sizes[g];
+  }
+  return make_policy(who, device, out_dim, *spec, shipped, n_members, rows, 0, all, &table, out);
+}
+
+// The forward kernels of a feed-forward handle on n rows (checked against p->rows by the callers), the one place that chooses them: the set
+// forms for more than one member (each 256-row tile reads its member's block; a critic's flat row r belongs to env r mod rows: n / rows row
+// blocks), else the general MLP kernels, else the shipped pair; by out_dim the actor (out = clipped actions) or the critic (out = values).
+static int launch_forward(rdv_policy p, const float* obs, float* out, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
+                          uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s) {
+  const bool critic = p->out_dim == 1, set = p->n_members > 1;
+  const int act = p->spec.activation, bf = p->block_floats;
+  const float* W = p->weights;
+  if (set && critic) sets_launch_value(p->shipped_arch, act, W, bf, p->tile_member, obs, out, p->rows, n / p->rows, s);
+  else if (set) sets_launch_act(p->shipped_arch, act, W, bf, p->tile_member, obs, out, n, deterministic, seed, counter, env_id_offset, raw_actions, log_prob, s);
+  else if (critic) (p->shipped_arch ? shipped_launch_value : mlp_launch_value)(act, W, bf, obs, out, n, s);
+  else (p->shipped_arch ? shipped_launch_act : mlp_launch_act)(act, W, bf, obs, out, n, deterministic, seed, counter, env_id_offset, raw_actions, log_prob, s);
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- GAE (csrc/rdv_advantages.h)
+// gamma, gae_lambda and the sizes: what rdv_gae and rdv_rollout_advantages check alike, before any device is looked at
+static int check_gae_scalars(const char* who, int32_t n_steps, int64_t n, double gamma, double gae_lambda) {
+  if (n_steps <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_steps must be positive (got %d)", who, n_steps);
+  if (n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
+  if (!std::isfinite(gamma) || gamma < 0.0 || gamma > 1.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: gamma must be in [0, 1] (got %g)", who, gamma);
+  if (!std::isfinite(gae_lambda) || gae_lambda < 0.0 || gae_lambda > 1.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: gae_lambda must be in [0, 1] (got %g)", who, gae_lambda);
+  return RDV_OK;
+}
+static int launch_gae(const float* reward, const uint8_t* done, const float* values, const float* last_value, int32_t n_steps, int64_t n,
+                      double gamma, double gae_lambda, float* advantages, float* returns, hipStream_t s) {
+  // (diagnostics only: RDV_GAE_DEPTH = 2 | 4 | 8 | 16 picks the kernel's prefetch depth, for tools/gae_time.py; results do not depend on it)
+  const char* x = getenv("RDV_GAE_DEPTH");
+  const int d = x ? atoi(x) : 0;
+  gae_launch(reward, done, values, last_value, n_steps, n, (float)gamma, (float)(gamma * gae_lambda), advantages, returns,
+             (d == 2 || d == 4 || d == 8 || d == 16) ? d : 0, s);
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- the recurrent policy (csrc/rdv_policy_lstm.h): one LSTM layer in front of an RdvMlpSpec trunk, the state owned by the handle
+// null pointers and finiteness of a recurrent network's host arrays (the spec has been checked)
+static int check_lstm_arrays(const char* who, int H, const RdvMlpSpec& trunk, int out_dim, const float* w_ih, const float* w_hh, const float* b_ih,
+                             const float* b_hh, const float* const* weights, const float* const* biases, const float* log_std) {
+  if (!w_ih || !w_hh || !b_ih || !b_hh || !weights || !biases) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (out_dim == kPolOut && !log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host is required for an actor", who);
+  if (out_dim != kPolOut && log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: log_std_host must be null for a critic", who);
+  if (int rc = check_layers(kNull, who, "trunk layer %d", 0, H, trunk, out_dim, weights, biases)) return rc;
+  if (!all_finite(w_ih, 4 * H * kPolIn) || !all_finite(w_hh, 4 * H * H) || !all_finite(b_ih, 4 * H) || !all_finite(b_hh, 4 * H))
+    return fail(RDV_ERR_BAD_PARAMS, "%s: non-finite LSTM weight", who);
+  return check_layers(kFinite, who, "trunk layer %d", 0, H, trunk, out_dim, weights, biases);
+}
+static int create_lstm(const char* who, const RdvLstmSpec* spec, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                       const float* const* weights, const float* const* biases, const float* log_std, int out_dim, int64_t n_rows, int device,
+                       rdv_policy* out) {
+  if (!spec || !out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (int rc = rdv_lstm_spec_check(spec)) return rc;
+  const int H = spec->hidden_size;
+  if (n_rows <= 0 || n_rows > (int64_t)1 << 31) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_rows = %lld must be in 1..2^31", who, (long long)n_rows);
+  if (int rc = check_lstm_arrays(who, H, spec->trunk, out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
+  if (int rc = check_device(who, device)) return rc;
+  DeviceGuard guard(device);
+  std::vector<float> packed;
+  pack_lstm_weights(H, spec->trunk, out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
+  return make_policy(who, device, out_dim, spec->trunk, false, 1, n_rows, H, packed, nullptr, out);
+}
+#define RDV_CHECK_LSTM(p, who) \
+  RDV_CHECK_POLICY(p);         \
+  if (!(p)->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, who ": this handle is not a recurrent policy (rdv_lstm_policy_create / rdv_lstm_critic_create)")
+
+// one step of a recurrent handle on `s`: the cell (flags: u8 [rows] or nullptr), then the trunk; commit: the state advances (the
+// pending flags are the caller's business).  The caller's DeviceGuard holds the device; the arguments have been checked.
+static int launch_lstm(rdv_policy p, const float* obs, const uint8_t* flags, float* out, float* raw_actions, float* log_prob, bool commit,
+                       int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, hipStream_t s) {
+  lstm_launch_cell(p->lstm_hidden, p->weights, obs, flags, p->lstm_h, p->lstm_c, p->lstm_h_next, commit ? p->lstm_c : p->lstm_c_tmp, p->rows, s);
+  RDV_HIP(hipGetLastError());
+  lstm_launch_trunk(p->spec.activation, p->out_dim == 1, p->weights, p->lstm_h_next, commit ? p->lstm_h : nullptr, out, p->rows, deterministic, seed,
+                    counter, env_id_offset, raw_actions, log_prob, s);
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+int rdv::policy_act_step(rdv_policy p, int32_t t, const float* obs, const uint8_t* done, float* actions, int64_t n, int deterministic, uint64_t seed,
+                         uint64_t counter, uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s) {
+  if (!p->lstm_hidden) return launch_forward(p, obs, actions, n, deterministic, seed, counter, env_id_offset, raw_actions, log_prob, s);
+  return launch_lstm(p, obs, t == 0 ? p->lstm_pending : done + (int64_t)(t - 1) * n, actions, raw_actions, log_prob, true, deterministic, seed, counter,
+                     env_id_offset, s);
+}
+
+// rdv_rollout_advantages with a recurrent critic: n_steps committing steps in time order, one non-committing step on last_obs (GAE follows)
+static int values_lstm(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, const RdvAdvantageOut* out, hipStream_t s) {
+  const bool aligned = (n & 3) == 0;                                   // row t of rows->obs is 16-byte aligned if and only if n % 4 == 0
+  for (int32_t t = 0; t < n_steps; ++t) {
+    const float* obs_t = rows->obs + (int64_t)t * n * RDV_OBS_DIM;
+    if (!aligned) {
+      RDV_HIP(hipMemcpyAsync(critic->lstm_obs_tmp, obs_t, (size_t)n * RDV_OBS_DIM * sizeof(float), hipMemcpyDeviceToDevice, s));
+      obs_t = critic->lstm_obs_tmp;
+    }
+    if (int rc = launch_lstm(critic, obs_t, t == 0 ? critic->lstm_pending : rows->done + (int64_t)(t - 1) * n, out->values + (int64_t)t * n, nullptr, nullptr, true, 1, 0, 0, 0, s)) return rc;
+  }
+  const uint8_t* last_done = rows->done + (int64_t)(n_steps - 1) * n;
+  if (int rc = launch_lstm(critic, rows->last_obs, last_done, out->last_value, nullptr, nullptr, false, 1, 0, 0, 0, s)) return rc;
+  RDV_HIP(hipMemcpyAsync(critic->lstm_pending, last_done, (size_t)n, hipMemcpyDeviceToDevice, s));
+  return RDV_OK;
+}
+
+extern "C" {
+
+int rdv_policy_create(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                      const float* log_std, int device, rdv_policy* out) {
+  if (!log_std) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create: null argument");
+  return create_mlp(w1, b1, w2, b2, w3, b3, log_std, kPolOut, device, out);
+}
+int rdv_critic_create(const float* w1, const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                      int device, rdv_policy* out) {
+  return create_mlp(w1, b1, w2, b2, w3, b3, nullptr, 1, device, out);
+}
+
+// ---- other architectures (RdvMlpSpec): csrc/rdv_policy_mlp.h
+int rdv_mlp_spec_default(RdvMlpSpec* out_host) {
+  if (!out_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_mlp_spec_default: null argument");
+  *out_host = kDefaultMlpSpec;
+  return RDV_OK;
+}
+
+int rdv_mlp_spec_check(const RdvMlpSpec* spec) {
+  if (!spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_mlp_spec_check: null spec");
+  if (spec->n_hidden < 1 || spec->n_hidden > RDV_MLP_MAX_HIDDEN)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: n_hidden = %d is not in 1..%d", spec->n_hidden, RDV_MLP_MAX_HIDDEN);
+  for (int l = 0; l < RDV_MLP_MAX_HIDDEN; ++l) {
+    const int wd = spec->hidden[l];
+    if (l < spec->n_hidden ? (wd != 16 && wd != 32 && wd != 64) : wd != 0)
+      return fail(RDV_ERR_INVALID_ARGUMENT, l < spec->n_hidden ? "RdvMlpSpec: hidden[%d] = %d is not 16, 32 or 64" : "RdvMlpSpec: hidden[%d] = %d beyond n_hidden must be 0", l, wd);
+  }
+  if (spec->activation != RDV_ACT_TANH && spec->activation != RDV_ACT_RELU && spec->activation != RDV_ACT_SIGMOID)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: activation = %d is not an RdvActivation (0 tanh, 1 relu, 2 sigmoid)", spec->activation);
+  if (spec->reserved != 0) return fail(RDV_ERR_INVALID_ARGUMENT, "RdvMlpSpec: reserved = %d must be 0", spec->reserved);
+  return RDV_OK;
+}
+
+int rdv_policy_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
+                          const float* log_std_host, int device, rdv_policy* out) {
+  if (!log_std_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_create_mlp: null argument");
+  return create_mlp_spec(spec_host, weights_host, biases_host, log_std_host, kPolOut, device, out);
+}
+int rdv_critic_create_mlp(const RdvMlpSpec* spec_host, const float* const* weights_host, const float* const* biases_host,
+                          int device, rdv_policy* out) {
+  return create_mlp_spec(spec_host, weights_host, biases_host, nullptr, 1, device, out);
+}
+
+int rdv_policy_get_spec(rdv_policy p, RdvMlpSpec* out_host) {
+  RDV_CHECK_POLICY(p);
+  if (!out_host) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_get_spec: null argument");
+  *out_host = p->spec;
+  return RDV_OK;
+}
+
+int rdv_policy_set_weights(rdv_policy p, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  RDV_CHECK_POLICY(p);
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_set_weights");
+  if (p->n_members > 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_weights: this handle is a policy set of %d members: refresh one member with rdv_policy_set_member_weights", p->n_members);
+  return refresh_member(p, "rdv_policy_set_weights", 0, weights, biases, log_std, stream);
+}
+
+int rdv_policy_set_member_weights(rdv_policy p, int32_t member, const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  RDV_CHECK_POLICY(p);
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_member_weights: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_set_weights");
+  if (member < 0 || member >= p->n_members) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_set_member_weights: member %d of %d", member, p->n_members);
+  return refresh_member(p, "rdv_policy_set_member_weights", member, weights, biases, log_std, stream);
+}
+
+int rdv_policy_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* const* weights_host,
+                          const float* const* const* biases_host, const float* const* log_std_host, int device, rdv_policy* out) {
+  return create_set("rdv_policy_set_create", spec_host, n_members, sizes_host, weights_host, biases_host, log_std_host, kPolOut, device, out);
+}
+int rdv_critic_set_create(const RdvMlpSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* const* weights_host,
+                          const float* const* const* biases_host, int device, rdv_policy* out) {
+  return create_set("rdv_critic_set_create", spec_host, n_members, sizes_host, weights_host, biases_host, nullptr, 1, device, out);
+}
+int32_t rdv_policy_num_members(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->n_members : -1; }
+int64_t rdv_policy_num_rows(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->rows : -1; }
+
+int rdv_policy_destroy(rdv_policy p) {
+  RDV_CHECK_POLICY(p);
+  DeviceGuard guard(p->device);
+  (void)hipDeviceSynchronize();
+  free_policy(p);
+  return RDV_OK;
+}
+
+int rdv_policy_act(rdv_policy p, const float* obs, float* actions, int64_t n, int deterministic, uint64_t seed, uint64_t counter,
+                   uint64_t env_id_offset, void* stream) {
+  RDV_CHECK_POLICY(p);
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: this handle is a recurrent policy (rdv_lstm_policy_create): use rdv_lstm_act, which carries the state");
+  if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: this handle is a critic (rdv_critic_create)");
+  if (!obs || !actions || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs, actions and a positive n are required");
+  if (misaligned(obs, 16) || misaligned(actions, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: obs and actions must be 16-byte aligned");
+  if (p->rows && n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_act: n = %lld, the policy set owns %lld rows", (long long)n, (long long)p->rows);
+  DeviceGuard guard(p->device);
+  return launch_forward(p, obs, actions, n, deterministic, seed, counter, env_id_offset, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int rdv_policy_value(rdv_policy p, const float* obs, float* values, int64_t n, void* stream) {
+  RDV_CHECK_POLICY(p);
+  if (p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: this handle is a recurrent policy (rdv_lstm_critic_create): use rdv_lstm_value, which carries the state");
+  if (p->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: this handle is an actor (rdv_policy_create)");
+  if (!obs || !values || n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs, values and a positive n are required");
+  if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: obs must be 16-byte aligned");
+  if (p->rows && n % p->rows != 0) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_policy_value: n = %lld is not a multiple of the %lld rows the critic set owns", (long long)n, (long long)p->rows);
+  DeviceGuard guard(p->device);
+  return launch_forward(p, obs, values, n, 1, 0, 0, 0, nullptr, nullptr, static_cast<hipStream_t>(stream));
+}
+
+int rdv_gae(const float* reward, const uint8_t* done, const float* values, const float* last_value, int32_t n_steps, int64_t n,
+            double gamma, double gae_lambda, float* advantages, float* returns, int device, void* stream) {
+  const struct { const void* p; const char* name; } ptrs[] = {{reward, "reward"}, {done, "done"}, {values, "values"}, {last_value, "last_value"},
+                                                              {advantages, "advantages"}, {returns, "returns"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_gae: %s is null", a.name);
+  if (int rc = check_gae_scalars("rdv_gae", n_steps, n, gamma, gae_lambda)) return rc;
+  if (int rc = check_device("rdv_gae", device)) return rc;
+  DeviceGuard guard(device);
+  return launch_gae(reward, done, values, last_value, n_steps, n, gamma, gae_lambda, advantages, returns, static_cast<hipStream_t>(stream));
+}
+
+int rdv_lstm_spec_check(const RdvLstmSpec* spec) {
+  if (!spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_spec_check: null spec");
+  if (!lstm_hidden_ok(spec->hidden_size))
+    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: hidden_size = %d is not 32, 64, 128 or 256 (lstm_hidden_size)", spec->hidden_size);
+  if (spec->n_layers != 1)
+    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: n_layers = %d: one LSTM layer is served (n_lstm_layers = 1)", spec->n_layers);
+  if (spec->shared != 0)
+    return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: shared = %d: separate actor and critic LSTMs are served (shared_lstm = False, enable_critic_lstm = True)", spec->shared);
+  if (spec->reserved != 0) return fail(RDV_ERR_BAD_PARAMS, "RdvLstmSpec: reserved = %d must be 0", spec->reserved);
+  return rdv_mlp_spec_check(&spec->trunk);
+}
+
+int rdv_lstm_policy_create(const RdvLstmSpec* spec_host, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                           const float* const* weights_host, const float* const* biases_host, const float* log_std_host, int64_t n_rows,
+                           int device, rdv_policy* out) {
+  return create_lstm("rdv_lstm_policy_create", spec_host, w_ih, w_hh, b_ih, b_hh, weights_host, biases_host, log_std_host, kPolOut, n_rows, device, out);
+}
+int rdv_lstm_critic_create(const RdvLstmSpec* spec_host, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                           const float* const* weights_host, const float* const* biases_host, int64_t n_rows, int device, rdv_policy* out) {
+  return create_lstm("rdv_lstm_critic_create", spec_host, w_ih, w_hh, b_ih, b_hh, weights_host, biases_host, nullptr, 1, n_rows, device, out);
+}
+int32_t rdv_lstm_hidden_size(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->lstm_hidden : -1; }
+
+int rdv_lstm_act(rdv_policy p, const float* obs, const uint8_t* episode_start, float* actions, float* raw_actions, float* log_prob, int64_t n,
+                 int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_act");
+  if (p->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: this handle is a critic (rdv_lstm_critic_create)");
+  if (!obs || !actions) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: obs and actions are required");
+  if (n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: n = %lld, the handle owns the state of %lld rows", (long long)n, (long long)p->rows);
+  if (misaligned(obs, 16) || misaligned(actions, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_act: obs and actions must be 16-byte aligned");
+  DeviceGuard guard(p->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = launch_lstm(p, obs, episode_start, actions, raw_actions, log_prob, true, deterministic ? 1 : 0, seed, counter, env_id_offset, s)) return rc;
+  RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, s));   // the state has moved past whatever start was pending
+  return RDV_OK;
+}
+
+int rdv_lstm_value(rdv_policy p, const float* obs, const uint8_t* episode_start, float* values, int64_t n, int commit, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_value");
+  if (p->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: this handle is an actor (rdv_lstm_policy_create)");
+  if (!obs || !values) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: obs and values are required");
+  if (n != p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: n = %lld, the handle owns the state of %lld rows", (long long)n, (long long)p->rows);
+  if (misaligned(obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_value: obs must be 16-byte aligned");
+  DeviceGuard guard(p->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = launch_lstm(p, obs, episode_start, values, nullptr, nullptr, commit != 0, 1, 0, 0, 0, s)) return rc;
+  if (commit) RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, s));
+  return RDV_OK;
+}
+
+int rdv_lstm_get_state(rdv_policy p, float* h_out, float* c_out, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_get_state");
+  if (!h_out || !c_out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_get_state: h_out and c_out are required");
+  DeviceGuard guard(p->device);
+  const size_t bytes = (size_t)p->rows * (size_t)p->lstm_hidden * sizeof(float);
+  RDV_HIP(hipMemcpyAsync(h_out, p->lstm_h, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  RDV_HIP(hipMemcpyAsync(c_out, p->lstm_c, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  return RDV_OK;
+}
+
+int rdv_lstm_set_state(rdv_policy p, const float* h, const float* c, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_set_state");
+  if (!h || !c) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_set_state: h and c are required");
+  DeviceGuard guard(p->device);
+  const size_t bytes = (size_t)p->rows * (size_t)p->lstm_hidden * sizeof(float);
+  RDV_HIP(hipMemcpyAsync(p->lstm_h, h, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  RDV_HIP(hipMemcpyAsync(p->lstm_c, c, bytes, hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+  RDV_HIP(hipMemsetAsync(p->lstm_pending, 0, (size_t)p->rows, static_cast<hipStream_t>(stream)));
+  return RDV_OK;
+}
+
+int rdv_lstm_reset_state(rdv_policy p, const uint8_t* mask, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_reset_state");
+  DeviceGuard guard(p->device);
+  lstm_launch_reset(p->lstm_h, p->lstm_c, mask, p->rows, p->lstm_hidden, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+int rdv_lstm_set_weights(rdv_policy p, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* const* weights,
+                         const float* const* biases, const float* log_std, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_set_weights");
+  if (int rc = check_lstm_arrays("rdv_lstm_set_weights", p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
+  std::vector<float> packed;
+  pack_lstm_weights(p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
+  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "rdv_lstm_set_weights: the packed block has %d floats, the handle's %d", (int)packed.size(), p->block_floats);
+  return upload_block(p, "rdv_lstm_set_weights", 0, packed, stream);
+}
+
+int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,
+                           const RdvAdvantageOut* out, void* stream) {
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows is null");
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: out is null");
+  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->reward, "rows->reward"}, {rows->done, "rows->done"},
+                                                              {rows->last_obs, "rows->last_obs"}, {out->values, "out->values"}, {out->last_value, "out->last_value"},
+                                                              {out->advantages, "out->advantages"}, {out->returns, "out->returns"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: %s is null", a.name);
+  if (int rc = check_gae_scalars("rdv_rollout_advantages", n_steps, n, gamma, gae_lambda)) return rc;
+  RDV_CHECK_POLICY(critic);
+  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: this handle is an actor (rdv_policy_create)");
+  if (critic->lstm_hidden && n != critic->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: n = %lld, the recurrent critic owns the state of %lld rows", (long long)n, (long long)critic->rows);
+  if (!critic->lstm_hidden && critic->rows && n != critic->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: n = %lld, the critic set owns %lld rows", (long long)n, (long long)critic->rows);
+  if (misaligned(rows->obs, 16) || misaligned(rows->last_obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_rollout_advantages: rows->obs and rows->last_obs must be 16-byte aligned");
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  DeviceGuard guard(critic->device);
+  if (critic->lstm_hidden) {
+    if (int rc = values_lstm(critic, rows, n_steps, n, out, s)) return rc;
+  } else {
+    // the critic at call time over the rows the actor saw, then over the observation after the last step: rdv_policy_value's own launches
+    if (int rc = rdv_policy_value(critic, rows->obs, out->values, (int64_t)n_steps * n, stream)) return rc;
+    if (int rc = rdv_policy_value(critic, rows->last_obs, out->last_value, n, stream)) return rc;
+  }
+  return launch_gae(rows->reward, rows->done, out->values, out->last_value, n_steps, n, gamma, gae_lambda, out->advantages, out->returns, s);
+}
+
+}  // extern "C"

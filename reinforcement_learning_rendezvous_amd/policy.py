@@ -119,7 +119,67 @@ def _advantages(policy, ro, gamma, gae_lambda, out):
     return ro
 
 
-class MlpPolicy(torch.nn.Module):
+def _ptrs(tensors):
+    """A C array of the tensors' addresses, as the ABI's ``const float* const*`` arguments take them (the tensors outlive the call)."""
+    return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
+
+
+class _HipHandles:
+    """The HIP side that MlpPolicy, PolicySet and LstmPolicy share: the per-device handle caches ``_hip`` (actor) and ``_hip_critic``
+    (device index -> rdv_policy, made on first use by the class's ``_create_handle(prefix, idx)``; prefix "l": actor, "v": critic),
+    ``close``, and the rdv_policy_act / rdv_policy_value calls of the feed-forward handles."""
+
+    @staticmethod
+    def _stream(device):
+        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+    def _handle(self, prefix, device):
+        device = torch.device(device)
+        idx = device.index if device.index is not None else torch.cuda.current_device()
+        table = self._hip if prefix == "l" else self._hip_critic
+        if idx not in table:
+            table[idx] = self._create_handle(prefix, idx)
+        return table[idx]
+
+    def _hip_handle(self, device):
+        return self._handle("l", device)
+
+    def _critic_handle(self, device):
+        return self._handle("v", device)
+
+    def close(self):
+        if self._hip or self._hip_critic:
+            from . import _native as N
+            for h in list(self._hip.values()) + list(self._hip_critic.values()):
+                N.lib().rdv_policy_destroy(h)
+            self._hip, self._hip_critic = {}, {}
+
+    def _act_hip(self, obs, deterministic, out=None, env_id_offset=None):
+        """rdv_policy_act on the actor handle of the rows' device, current stream; the call counter advances."""
+        from . import _native as N
+        offset = self.noise_env_offset if env_id_offset is None else int(env_id_offset)
+        obs = obs.contiguous()
+        n = obs.shape[0]
+        if out is None:
+            out = torch.empty((n, 6), dtype=torch.float32, device=obs.device)
+        N.check(N.lib().rdv_policy_act(self._hip_handle(obs.device), C.c_void_p(obs.data_ptr()), C.c_void_p(out.data_ptr()), n,
+                                       int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls),
+                                       C.c_uint64(offset), self._stream(obs.device)))
+        self._calls += 1
+        return out
+
+    def _value_hip(self, obs, out=None):
+        """rdv_policy_value on the critic handle: float32 CUDA observations [..., 17] -> values [...], current stream."""
+        from . import _native as N
+        flat = obs.reshape(-1, 17).contiguous()
+        if out is None:
+            out = torch.empty((flat.shape[0],), dtype=torch.float32, device=flat.device)
+        N.check(N.lib().rdv_policy_value(self._critic_handle(flat.device), C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
+                                         flat.shape[0], self._stream(flat.device)))
+        return out.reshape(obs.shape[:-1])
+
+
+class MlpPolicy(_HipHandles, torch.nn.Module):
     def __init__(self, weights=None, net_arch=None, activation_fn="tanh", obs_dim=17, hidden=64, act_dim=6, seed=0, backend="auto"):
         super().__init__()
         self.backend = backend          # "auto": HIP kernel for CUDA observations, PyTorch otherwise; "torch"; "hip"
@@ -229,22 +289,16 @@ class MlpPolicy(torch.nn.Module):
     def mean(self, obs):
         return self._forward("l", obs)
 
-    def _hip_handle(self, device):
-        from . import _native as N
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if idx not in self._hip:
-            self._hip[idx] = self._create_handle("l", self.pi_arch, idx)
-        return self._hip[idx]
-
     def _host_layers(self, prefix):
         """(weights, biases, [log_std] or []) of a trunk as contiguous float32 CPU tensors, hidden layers first, the head last."""
         host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
         layers = self._layers(prefix)
         return [host(l.weight) for l in layers], [host(l.bias) for l in layers], [host(self.log_std)] if prefix == "l" else []
 
-    def _create_handle(self, prefix, arch, idx):
+    def _create_handle(self, prefix, idx):
         """rdv_policy_create / rdv_critic_create for the shipped architecture, their _mlp forms (RdvMlpSpec) for every other."""
         from . import _native as N
+        arch = self.pi_arch if prefix == "l" else self.vf_arch
         ws, bs, log_std = self._host_layers(prefix)
         h = C.c_void_p()
         if arch == [64, 64] and self.activation == "tanh":
@@ -254,50 +308,19 @@ class MlpPolicy(torch.nn.Module):
             return h
         spec = N.MlpSpec.make(arch, ACTIVATIONS[self.activation][0])
         N.check(N.lib().rdv_mlp_spec_check(C.byref(spec)))        # a message naming the field, before any pointer is read
-        wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-        bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
         if prefix == "l":
-            N.check(N.lib().rdv_policy_create_mlp(C.byref(spec), wp, bp, C.c_void_p(log_std[0].data_ptr()), idx, C.byref(h)))
+            N.check(N.lib().rdv_policy_create_mlp(C.byref(spec), _ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()), idx, C.byref(h)))
         else:
-            N.check(N.lib().rdv_critic_create_mlp(C.byref(spec), wp, bp, idx, C.byref(h)))
+            N.check(N.lib().rdv_critic_create_mlp(C.byref(spec), _ptrs(ws), _ptrs(bs), idx, C.byref(h)))
         return h
-
-    def _act_hip(self, obs, deterministic, out=None, env_id_offset=None):
-        from . import _native as N
-        offset = self.noise_env_offset if env_id_offset is None else int(env_id_offset)
-        obs = obs.contiguous()
-        n = obs.shape[0]
-        if out is None:
-            out = torch.empty((n, 6), dtype=torch.float32, device=obs.device)
-        stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-        N.check(N.lib().rdv_policy_act(self._hip_handle(obs.device), C.c_void_p(obs.data_ptr()), C.c_void_p(out.data_ptr()), n,
-                                       int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls),
-                                       C.c_uint64(offset), stream))
-        self._calls += 1
-        return out
 
     @torch.no_grad()
     def value(self, obs, out=None):
         """The critic's value estimate for observations [..., 17] (SB3 ``policy.predict_values``): one HIP kernel for CUDA
         float32 observations (rdv_policy_value), the PyTorch modules otherwise / with ``backend="torch"``."""
-        shape = obs.shape[:-1]
-        flat = obs.reshape(-1, 17)
-        if self.backend != "torch" and flat.is_cuda and flat.dtype == torch.float32:
-            from . import _native as N
-            flat = flat.contiguous()
-            if out is None:
-                out = torch.empty((flat.shape[0],), dtype=torch.float32, device=flat.device)
-            stream = C.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream)
-            N.check(N.lib().rdv_policy_value(self._critic_handle(flat.device), C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
-                                             flat.shape[0], stream))
-            return out.reshape(shape)
-        return self._forward("v", flat).reshape(shape)
-
-    def _critic_handle(self, device):
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if idx not in self._hip_critic:
-            self._hip_critic[idx] = self._create_handle("v", self.vf_arch, idx)
-        return self._hip_critic[idx]
+        if self.backend != "torch" and obs.is_cuda and obs.dtype == torch.float32:
+            return self._value_hip(obs, out)
+        return self._value_torch(obs)
 
     @torch.no_grad()
     def advantages(self, ro, gamma=0.99, gae_lambda=0.95, out=None):
@@ -329,18 +352,9 @@ class MlpPolicy(torch.nn.Module):
             if not handles:
                 continue
             ws, bs, log_std = self._host_layers(prefix)
-            wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-            bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
             for idx, h in handles.items():
-                stream = C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)
-                N.check(N.lib().rdv_policy_set_weights(h, wp, bp, C.c_void_p(log_std[0].data_ptr()) if log_std else None, stream))
-
-    def close(self):
-        if self._hip or self._hip_critic:
-            from . import _native as N
-            for h in list(self._hip.values()) + list(self._hip_critic.values()):
-                N.lib().rdv_policy_destroy(h)
-            self._hip, self._hip_critic = {}, {}
+                N.check(N.lib().rdv_policy_set_weights(h, _ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()) if log_std else None,
+                                                       self._stream(idx)))
 
     @torch.no_grad()
     def act(self, obs, deterministic=True, generator=None, out=None, env_id_offset=None):
@@ -365,7 +379,7 @@ class MlpPolicy(torch.nn.Module):
         return self.act(obs, deterministic=deterministic).cpu().numpy(), state
 
 
-class PolicySet:
+class PolicySet(_HipHandles):
     """P member policies of ONE architecture over one batch: member g owns the next ``group_sizes[g]`` rows, and one launch evaluates all
     members (include/rdv.h, "Policy sets"; csrc/rdv_policy_sets.h) — the network half of a sweep of P learners on one GPU, as a grouped
     ``RendezvousBatch`` is the environment half.  Row i of member g gets bit for bit what ``policies[g]`` alone computes for that row with
@@ -430,13 +444,13 @@ class PolicySet:
         return self
 
     # ------------------------------------------------------------------------------------------------ handles
-    def _create_handle(self, prefix, arch, idx):
+    def _create_handle(self, prefix, idx):
         """rdv_policy_set_create / rdv_critic_set_create from the members' modules."""
         from . import _native as N
+        arch = self.pi_arch if prefix == "l" else self.vf_arch
         host = [p._host_layers(prefix) for p in self.policies]        # kept alive until the call returns
-        n_layers = len(arch) + 1
-        wps = [(C.c_void_p * n_layers)(*[t.data_ptr() for t in ws]) for ws, _, _ in host]
-        bps = [(C.c_void_p * n_layers)(*[t.data_ptr() for t in bs]) for _, bs, _ in host]
+        wps = [_ptrs(ws) for ws, _, _ in host]
+        bps = [_ptrs(bs) for _, bs, _ in host]
         P = len(host)
         wpp = (C.c_void_p * P)(*[C.addressof(a) for a in wps])
         bpp = (C.c_void_p * P)(*[C.addressof(a) for a in bps])
@@ -445,23 +459,11 @@ class PolicySet:
         sizes = (C.c_int64 * P)(*self.group_sizes)
         h = C.c_void_p()
         if prefix == "l":
-            lsp = (C.c_void_p * P)(*[ls[0].data_ptr() for _, _, ls in host])
+            lsp = _ptrs([ls[0] for _, _, ls in host])
             N.check(N.lib().rdv_policy_set_create(C.byref(spec), P, sizes, wpp, bpp, lsp, idx, C.byref(h)))
         else:
             N.check(N.lib().rdv_critic_set_create(C.byref(spec), P, sizes, wpp, bpp, idx, C.byref(h)))
         return h
-
-    def _hip_handle(self, device):
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if idx not in self._hip:
-            self._hip[idx] = self._create_handle("l", self.pi_arch, idx)
-        return self._hip[idx]
-
-    def _critic_handle(self, device):
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        if idx not in self._hip_critic:
-            self._hip_critic[idx] = self._create_handle("v", self.vf_arch, idx)
-        return self._hip_critic[idx]
 
     def _check_rows(self, n, what):
         if n != self.num_rows:
@@ -477,20 +479,9 @@ class PolicySet:
                                         and obs.dim() == 2 and obs.shape[1] == 17)
         self._check_rows(int(obs.shape[0]), "act")
         if hip:
-            from . import _native as N
             if generator is not None:
                 self.noise_seed = int(generator.initial_seed())
-            offset = self.noise_env_offset if env_id_offset is None else int(env_id_offset)
-            obs = obs.contiguous()
-            n = obs.shape[0]
-            if out is None:
-                out = torch.empty((n, 6), dtype=torch.float32, device=obs.device)
-            stream = C.c_void_p(torch.cuda.current_stream(obs.device).cuda_stream)
-            N.check(N.lib().rdv_policy_act(self._hip_handle(obs.device), C.c_void_p(obs.data_ptr()), C.c_void_p(out.data_ptr()), n,
-                                           int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls),
-                                           C.c_uint64(offset), stream))
-            self._calls += 1
-            return out
+            return self._act_hip(obs, deterministic, out, env_id_offset)
         parts = [p.act(obs[s], deterministic=deterministic, generator=generator) for p, s in zip(self.policies, self.group_slices)]
         res = torch.cat(parts, dim=0)
         if out is not None:
@@ -509,16 +500,8 @@ class PolicySet:
         if obs.dim() < 2 or obs.shape[-1] != 17:
             raise ValueError(f"value: expected [..., n, 17] observations, got {tuple(obs.shape)}")
         self._check_rows(int(obs.shape[-2]), "value")
-        shape = obs.shape[:-1]
         if self.backend != "torch" and obs.is_cuda and obs.dtype == torch.float32:
-            from . import _native as N
-            flat = obs.reshape(-1, 17).contiguous()
-            if out is None:
-                out = torch.empty((flat.shape[0],), dtype=torch.float32, device=flat.device)
-            stream = C.c_void_p(torch.cuda.current_stream(flat.device).cuda_stream)
-            N.check(N.lib().rdv_policy_value(self._critic_handle(flat.device), C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
-                                             flat.shape[0], stream))
-            return out.reshape(shape)
+            return self._value_hip(obs, out)
         return self._value_torch(obs)
 
     @torch.no_grad()
@@ -564,15 +547,6 @@ class PolicySet:
                 continue
             for g in todo:
                 ws, bs, log_std = self.policies[g]._host_layers(prefix)
-                wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-                bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
                 for idx, h in handles.items():
-                    stream = C.c_void_p(torch.cuda.current_stream(idx).cuda_stream)
-                    N.check(N.lib().rdv_policy_set_member_weights(h, g, wp, bp, C.c_void_p(log_std[0].data_ptr()) if log_std else None, stream))
-
-    def close(self):
-        if self._hip or self._hip_critic:
-            from . import _native as N
-            for h in list(self._hip.values()) + list(self._hip_critic.values()):
-                N.lib().rdv_policy_destroy(h)
-            self._hip, self._hip_critic = {}, {}
+                    N.check(N.lib().rdv_policy_set_member_weights(h, g, _ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()) if log_std else None,
+                                                                  self._stream(idx)))

@@ -22,7 +22,7 @@ import zipfile
 import numpy as np
 import torch
 
-from .policy import ACTIVATIONS, _trunk_keys, infer_arch, parse_activation, parse_net_arch
+from .policy import ACTIVATIONS, _HipHandles, _ptrs, _trunk_keys, infer_arch, parse_activation, parse_net_arch
 
 LSTM_HIDDEN_SIZES = (32, 64, 128, 256)
 _LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
@@ -40,7 +40,7 @@ def check_lstm_config(lstm_hidden_size, n_lstm_layers=1, shared_lstm=False, enab
         raise ValueError(f"lstm_hidden_size = {lstm_hidden_size} is not one of {LSTM_HIDDEN_SIZES}")
 
 
-class LstmPolicy(torch.nn.Module):
+class LstmPolicy(_HipHandles, torch.nn.Module):
     def __init__(self, weights=None, lstm_hidden_size=256, net_arch=None, activation_fn="tanh", n_rows=None, seed=0, backend="auto",
                  n_lstm_layers=1, shared_lstm=False, enable_critic_lstm=True):
         super().__init__()
@@ -198,8 +198,7 @@ class LstmPolicy(torch.nn.Module):
         spec = N.LstmSpec.make(self.lstm_hidden_size, arch, ACTIVATIONS[self.activation][0])
         N.check(N.lib().rdv_lstm_spec_check(C.byref(spec)))
         lstm, ws, bs, log_std = self._host_arrays(prefix)
-        wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-        bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
+        wp, bp = _ptrs(ws), _ptrs(bs)
         h = C.c_void_p()
         lp = [C.c_void_p(t.data_ptr()) for t in lstm]
         if prefix == "l":
@@ -211,21 +210,7 @@ class LstmPolicy(torch.nn.Module):
     def _handle(self, prefix, device):
         if self.n_rows is None:
             raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
-        idx = device.index if device.index is not None else torch.cuda.current_device()
-        table = self._hip if prefix == "l" else self._hip_critic
-        if idx not in table:
-            table[idx] = self._create_handle(prefix, idx)
-        return table[idx]
-
-    def _hip_handle(self, device):
-        return self._handle("l", torch.device(device))
-
-    def _critic_handle(self, device):
-        return self._handle("v", torch.device(device))
-
-    @staticmethod
-    def _stream(device):
-        return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        return super()._handle(prefix, device)
 
     def _get_state(self, prefix, device=None):
         table = self._hip if prefix == "l" else self._hip_critic
@@ -446,15 +431,6 @@ class LstmPolicy(torch.nn.Module):
             if not table:
                 continue
             lstm, ws, bs, log_std = self._host_arrays(prefix)
-            wp = (C.c_void_p * len(ws))(*[t.data_ptr() for t in ws])
-            bp = (C.c_void_p * len(bs))(*[t.data_ptr() for t in bs])
             for idx, h in table.items():
-                N.check(N.lib().rdv_lstm_set_weights(h, *[C.c_void_p(t.data_ptr()) for t in lstm], wp, bp,
+                N.check(N.lib().rdv_lstm_set_weights(h, *[C.c_void_p(t.data_ptr()) for t in lstm], _ptrs(ws), _ptrs(bs),
                                                      C.c_void_p(log_std[0].data_ptr()) if log_std else None, self._stream(torch.device("cuda", idx))))
-
-    def close(self):
-        if self._hip or self._hip_critic:
-            from . import _native as N
-            for h in list(self._hip.values()) + list(self._hip_critic.values()):
-                N.lib().rdv_policy_destroy(h)
-            self._hip, self._hip_critic = {}, {}

@@ -47,6 +47,21 @@ def test_every_declared_symbol_is_exported():
     assert "orc_" not in nm                  # the oracle is not linked into the product
 
 
+def test_the_policy_handles_have_a_host_only_unit_of_their_own():
+    """csrc/rdv_policy_host.hip ("The host unit of the policy handles") emits no kernel — it reaches them through the launch
+    functions of the headers — and rdv_hip.hip keeps no policy entry point but rdv_rollout, which owns the env handle."""
+    import sys
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    try:
+        import kernel_isa_diff
+    finally:
+        sys.path.pop(0)
+    assert kernel_isa_diff.streams("rdv_policy_host") == {}
+    src = open(os.path.join(ROOT, "reinforcement_learning_rendezvous_amd", "csrc", "rdv_hip.hip")).read()
+    assert re.findall(r"^int rdv_(?:policy|critic|lstm|mlp|gae)\w*", src, re.M) == []
+    assert len(re.findall(r"RDV_CHECK_POLICY\(", src)) == 1 and "int rdv_rollout(" in src
+
+
 def test_device_error_word_is_never_absorbed():
     """The host check behind rdv_get_stats / rdv_eval_summary (include/rdv.h, RdvDeviceError): a kernel that gives up a bounded
     wait (rdv_rollout.h: the env waves' poll of the slot-refill counter, 2^22 polls = ~0.35 s) sets a bit of the handle's device
