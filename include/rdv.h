@@ -677,8 +677,41 @@ int64_t rdv_policy_num_rows(rdv_policy p);
  *                           out->last_value, done[T-1] into the critic's pending flags, then the kernel of rdv_gae, unchanged.  When n % 4
  *                           != 0, row t of rows->obs is not 16-byte aligned and is read through a copy in the handle's scratch rows.
  *   rdv_policy_act, rdv_policy_value, rdv_policy_set_weights, rdv_policy_set_member_weights: RDV_ERR_INVALID_ARGUMENT (they would ignore
- *                           the state); policy sets are built from weights of ONE RdvMlpSpec and have no recurrent members.
- * Not offered: a persistent one-launch recurrent rollout, 2 or 3 LSTM layers, a shared LSTM, LSTM members in policy sets.
+ *                           the state); rdv_policy_set_create builds from weights of ONE RdvMlpSpec and has no recurrent members:
+ *                           recurrent networks go into a recurrent set of their own (below).
+ *
+ * Recurrent policy sets (added within ABI 5: additive exports) — the network half of a sweep of P recurrent learners, as policy sets
+ * are for MLP learners: n_members recurrent networks of ONE RdvLstmSpec (the same H, the same trunk spec), member g owning sizes[g]
+ * consecutive rows, member 0 from row 0 on.  The set handle owns the state (h, c) [rows, H] and the pending flags of all rows,
+ * rows = sum(sizes).  The contract:
+ *
+ *     Row i of member g gets bit for bit what a stand-alone rdv_lstm_policy_create / rdv_lstm_critic_create handle of member g's arrays
+ *     with n_rows = sizes[g] computes for that row, fed the same observations and episode-start flags, the same seed, the same counter
+ *     and env_id_offset + start_g (start_g = sizes[0] + .. + sizes[g-1]), over any number of steps.
+ *
+ * This covers the clipped action, the unclipped sample, log_prob, the value, and h and c after every call (the set's state rows
+ * start_g .. start_g + sizes[g] - 1 equal the stand-alone handle's state).  The 256-row rule of policy sets holds (every size positive,
+ * every size but the last a multiple of 256; rdv_param_groups_check, whose message names the member as "group"): a workgroup of the
+ * cell and trunk kernels owns 256 consecutive rows, so it never spans two members; the set forms of the kernels read the block of
+ * their tile's member and are otherwise the kernels of stand-alone handles (csrc/rdv_policy_lstm.h).
+ *
+ * rdv_lstm_policy_set_create / rdv_lstm_critic_set_create: w_ih_host[g] .. b_hh_host[g], weights_host[g], biases_host[g] and (actors)
+ *   log_std_host[g] are member g's arrays in the layout of rdv_lstm_policy_create.  Checked in this order, all before the device is
+ *   touched: the spec (rdv_lstm_spec_check), the sizes (rdv_param_groups_check; at most 2^31 rows), every member's arrays as
+ *   rdv_lstm_policy_create checks them, the message naming the member.  One device allocation holds the member blocks — exactly the
+ *   bytes of stand-alone handles — and the tile table; one state allocation serves all rows.  The state is zero and every row's pending
+ *   flag is 1.  n_members = 1 is legal: it runs the plain kernels and equals the plain handle.
+ * Calls that take a recurrent set as they take a recurrent handle, n being the set's rows, their semantics (the pending-flag rules
+ *   included) unchanged: rdv_lstm_act, rdv_lstm_value (commit 0 / 1), rdv_lstm_get_state, rdv_lstm_set_state, rdv_lstm_reset_state,
+ *   rdv_lstm_hidden_size, rdv_policy_num_members, rdv_policy_num_rows, rdv_policy_get_spec, rdv_policy_destroy, rdv_rollout (the
+ *   rdv_lstm_act + rdv_step loop, whatever the env handle's grouping: the set's ranges and the handle's parameter groups are independent)
+ *   and rdv_rollout_advantages (as for a recurrent critic, the copy through the scratch rows when n % 4 != 0 included).
+ * rdv_lstm_set_weights: RDV_ERR_INVALID_ARGUMENT for a set of more than one member: use rdv_lstm_set_member_weights.
+ * rdv_lstm_set_member_weights: rdv_lstm_set_weights for ONE member (arguments, checks, ordering on `stream`, the per-member staging slot
+ *   and event, and the refusal inside a stream capture as there and as rdv_policy_set_member_weights; member 0 of a plain recurrent handle
+ *   is the handle).  The state and the other members' blocks are not written.
+ * Not offered: a persistent one-launch recurrent rollout, 2 or 3 LSTM layers, a shared LSTM, members of different H or trunks in one
+ * recurrent set, recurrent and MLP members in one set.
  */
 typedef struct RdvLstmSpec {
   int32_t hidden_size;   /* 32, 64, 128 or 256 */
@@ -703,6 +736,17 @@ int rdv_lstm_reset_state(rdv_policy p, const uint8_t* mask, void* stream);
 int rdv_lstm_set_weights(rdv_policy p, const float* w_ih_host, const float* w_hh_host, const float* b_ih_host, const float* b_hh_host,
                          const float* const* weights_host, const float* const* biases_host, const float* log_std_host, void* stream);
 int32_t rdv_lstm_hidden_size(rdv_policy p);
+int rdv_lstm_policy_set_create(const RdvLstmSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* w_ih_host,
+                               const float* const* w_hh_host, const float* const* b_ih_host, const float* const* b_hh_host,
+                               const float* const* const* weights_host, const float* const* const* biases_host,
+                               const float* const* log_std_host, int device, rdv_policy* out);
+int rdv_lstm_critic_set_create(const RdvLstmSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* w_ih_host,
+                               const float* const* w_hh_host, const float* const* b_ih_host, const float* const* b_hh_host,
+                               const float* const* const* weights_host, const float* const* const* biases_host, int device,
+                               rdv_policy* out);
+int rdv_lstm_set_member_weights(rdv_policy p, int32_t member, const float* w_ih_host, const float* w_hh_host, const float* b_ih_host,
+                                const float* b_hh_host, const float* const* weights_host, const float* const* biases_host,
+                                const float* log_std_host, void* stream);
 
 #ifdef __cplusplus
 }

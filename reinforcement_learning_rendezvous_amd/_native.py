@@ -39,7 +39,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            "rdv_policy_set_create", "rdv_critic_set_create", "rdv_policy_set_member_weights", "rdv_policy_num_members", "rdv_policy_num_rows",
            # the recurrent policy (added within ABI 5)
            "rdv_lstm_spec_check", "rdv_lstm_policy_create", "rdv_lstm_critic_create", "rdv_lstm_act", "rdv_lstm_value", "rdv_lstm_get_state",
-           "rdv_lstm_set_state", "rdv_lstm_reset_state", "rdv_lstm_set_weights", "rdv_lstm_hidden_size"]
+           "rdv_lstm_set_state", "rdv_lstm_reset_state", "rdv_lstm_set_weights", "rdv_lstm_hidden_size",
+           # recurrent policy sets (added within ABI 5)
+           "rdv_lstm_policy_set_create", "rdv_lstm_critic_set_create", "rdv_lstm_set_member_weights"]
 
 
 class RdvError(RuntimeError):
@@ -219,6 +221,9 @@ def lib():
         "rdv_lstm_reset_state": (C.c_int, [vp, vp, vp]),
         "rdv_lstm_set_weights": (C.c_int, [vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "rdv_lstm_hidden_size": (i32, [vp]),
+        "rdv_lstm_policy_set_create": (C.c_int, [C.POINTER(LstmSpec), i32, C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]),
+        "rdv_lstm_critic_set_create": (C.c_int, [C.POINTER(LstmSpec), i32, C.POINTER(i64), vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]),
+        "rdv_lstm_set_member_weights": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

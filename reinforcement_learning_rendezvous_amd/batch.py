@@ -267,7 +267,8 @@ class RendezvousBatch:
         ``policy`` may be an ``LstmPolicy`` whose rows are the batch's envs: rdv_lstm_act + rdv_step per step inside the library, episode
         starts from the previous step's ``done`` (step 0: what the previous rollout left pending; every row at first).  The dict then
         also holds ``lstm_state0``, the actor's ``(h, c)`` as step 0 sees it (what RecurrentPPO's buffer keeps for sequence starts),
-        and the next rollout goes on where this one stopped."""
+        and the next rollout goes on where this one stopped.  An ``LstmPolicySet`` whose rows are the batch's envs is taken the same way:
+        member g acts for the envs of its range, ONE cell and ONE trunk launch per step for all members; ``lstm_state0`` is the set's."""
         T, n, dev = int(n_steps), self.num_envs, self.device
         if out is None or out["obs"].shape[0] != T:
             out = dict(obs=torch.empty((T, n, N.OBS_DIM), dtype=torch.float32, device=dev),
@@ -296,7 +297,9 @@ class RendezvousBatch:
         steps — the rows of ``rollout`` plus ``values``, ``last_value``, ``advantages``, ``returns`` (what ``collect_rollouts`` leaves
         behind after ``compute_returns_and_advantage``, main.py:114).  The rows are those of the two separate calls; pass the dict
         back as ``out`` to reuse every buffer.  With a ``PolicySet`` this is the training entry point of a sweep: every env's columns
-        are those of its member's actor and critic, in one actor launch per step and two critic launches per call."""
+        are those of its member's actor and critic, in one actor launch per step and two critic launches per call.  With an
+        ``LstmPolicySet`` it is the same for a sweep of recurrent learners: the critics' ``n_steps`` + 1 steps are one cell and one trunk
+        launch each for all members."""
         ro = self.rollout(policy, n_steps, deterministic=deterministic, out=out)
         return policy.advantages(ro, gamma=gamma, gae_lambda=gae_lambda, out=out)
 

@@ -78,8 +78,9 @@ struct RdvPolicyNet {
   int32_t n_members = 1;      // 1: a plain handle, or a set of one member (the plain kernels read its one block)
   int64_t rows = 0;           // 0: a plain handle (any n); a set: the rows its members own together
   const int32_t* tile_member = nullptr;   // device: member index per 256-row tile (inside the allocation of `weights`); nullptr for a plain handle
-  // the recurrent policy (csrc/rdv_policy_lstm.h): lstm_hidden != 0, `weights` = [trunk block | cell block], `rows` = the rows whose state
-  // the handle owns; one device allocation `lstm_state` holds h, c, h_next, c_tmp ([rows, H] fp32 each), obs_tmp [rows, 17], pending [rows]
+  // the recurrent policy (csrc/rdv_policy_lstm.h): lstm_hidden != 0, `weights` = [trunk block | cell block] (a recurrent set: n_members
+  // such blocks, then the tile table, as a policy set), `rows` = the rows whose state the handle owns; one device allocation
+  // `lstm_state` holds h, c, h_next, c_tmp ([rows, H] fp32 each), obs_tmp [rows, 17], pending [rows]
   int32_t lstm_hidden = 0;
   float *lstm_state = nullptr, *lstm_h = nullptr, *lstm_c = nullptr, *lstm_h_next = nullptr, *lstm_c_tmp = nullptr, *lstm_obs_tmp = nullptr;
   uint8_t* lstm_pending = nullptr;

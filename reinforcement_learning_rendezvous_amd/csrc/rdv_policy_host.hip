@@ -1,5 +1,5 @@
 // rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
-// value / set-weights entry points, policy sets, the recurrent policy (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
+// value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
 // rdv_rollout_advantages, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
 // mlp_*, sets_*, lstm_*, gae_launch), so an edit to an argument check recompiles no kernel.
@@ -259,6 +259,54 @@ static int create_lstm(const char* who, const RdvLstmSpec* spec, const float* w_
   pack_lstm_weights(H, spec->trunk, out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
   return make_policy(who, device, out_dim, spec->trunk, false, 1, n_rows, H, packed, nullptr, out);
 }
+// ---- recurrent policy sets: n_members recurrent networks of one RdvLstmSpec, member g owning sizes[g] consecutive rows; the handle owns
+// the state and the pending flags of all rows.  The order of work: the spec, the sizes, every member's arrays, then the device.
+static int create_lstm_set(const char* who, const RdvLstmSpec* spec, int32_t n_members, const int64_t* sizes, const float* const* w_ih,
+                           const float* const* w_hh, const float* const* b_ih, const float* const* b_hh, const float* const* const* weights,
+                           const float* const* const* biases, const float* const* log_std, int out_dim, int device, rdv_policy* out) {
+  if (!spec || !sizes || !w_ih || !w_hh || !b_ih || !b_hh || !weights || !biases || !out || (out_dim == kPolOut && !log_std))
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
+  if (int rc = rdv_lstm_spec_check(spec)) return rc;
+  if (n_members < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_members = %d: a set has at least member 0", who, n_members);
+  // the rule of parameter groups judges the sizes, as create_set's (a size that ends the sum is named against a count nothing exceeds)
+  constexpr int64_t kMostRows = INT64_MAX / 2;
+  int64_t rows = 0;
+  for (int32_t g = 0; g < n_members && rows >= 0; ++g) rows = (sizes[g] > 0 && sizes[g] <= kMostRows - rows) ? rows + sizes[g] : -1;
+  if (int rc = rdv_param_groups_check(rows < 0 ? kMostRows : rows, n_members, sizes)) return rc;
+  if (rows > (int64_t)1 << 31) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the sizes sum to %lld rows, which must be in 1..2^31", who, (long long)rows);
+  const int H = spec->hidden_size;
+  char member[96];
+  for (int32_t g = 0; g < n_members; ++g) {
+    std::snprintf(member, sizeof member, "%s: member %d", who, g);
+    if (int rc = check_lstm_arrays(member, H, spec->trunk, out_dim, w_ih[g], w_hh[g], b_ih[g], b_hh[g], weights[g], biases[g],
+                                   out_dim == kPolOut ? log_std[g] : nullptr)) return rc;
+  }
+  if (int rc = check_device(who, device)) return rc;
+  DeviceGuard guard(device);
+  // member blocks: exactly the bytes pack_lstm_weights gives stand-alone handles; then (256-byte aligned) the tile table
+  std::vector<float> all, packed;
+  for (int32_t g = 0; g < n_members; ++g) {
+    pack_lstm_weights(H, spec->trunk, out_dim, w_ih[g], w_hh[g], b_ih[g], b_hh[g], weights[g], biases[g], out_dim == kPolOut ? log_std[g] : nullptr, packed);
+    if (g && packed.size() * (size_t)g != all.size()) return fail(RDV_ERR_HIP, "%s: member %d packs to %zu floats, member 0 to %zu", who, g, packed.size(), all.size() / (size_t)g);
+    all.insert(all.end(), packed.begin(), packed.end());
+  }
+  std::vector<int32_t> table((size_t)((rows + kSetTile - 1) / kSetTile));
+  int64_t at = 0;
+  for (int32_t g = 0; g < n_members; ++g) {
+    for (int64_t t = at / kSetTile; t < (at + sizes[g] + kSetTile - 1) / kSetTile; ++t) table[(size_t)t] = g;
+    at += sizes[g];
+  }
+  return make_policy(who, device, out_dim, spec->trunk, false, n_members, rows, H, all, &table, out);
+}
+// one recurrent network's host arrays checked against the handle's spec, packed, and uploaded as block `member`
+static int refresh_lstm_member(rdv_policy p, const char* who, int32_t member, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                               const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  if (int rc = check_lstm_arrays(who, p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
+  std::vector<float> packed;
+  pack_lstm_weights(p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
+  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "%s: the packed block has %d floats, the handle's %d", who, (int)packed.size(), p->block_floats);
+  return upload_block(p, who, member, packed, stream);
+}
 #define RDV_CHECK_LSTM(p, who) \
   RDV_CHECK_POLICY(p);         \
   if (!(p)->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, who ": this handle is not a recurrent policy (rdv_lstm_policy_create / rdv_lstm_critic_create)")
@@ -267,10 +315,12 @@ static int create_lstm(const char* who, const RdvLstmSpec* spec, const float* w_
 // pending flags are the caller's business).  The caller's DeviceGuard holds the device; the arguments have been checked.
 static int launch_lstm(rdv_policy p, const float* obs, const uint8_t* flags, float* out, float* raw_actions, float* log_prob, bool commit,
                        int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, hipStream_t s) {
-  lstm_launch_cell(p->lstm_hidden, p->weights, obs, flags, p->lstm_h, p->lstm_c, p->lstm_h_next, commit ? p->lstm_c : p->lstm_c_tmp, p->rows, s);
+  const int32_t* table = p->n_members > 1 ? p->tile_member : nullptr;   // a set of one member runs the plain kernels on its one block
+  lstm_launch_cell(p->lstm_hidden, p->weights, p->block_floats, table, obs, flags, p->lstm_h, p->lstm_c, p->lstm_h_next,
+                   commit ? p->lstm_c : p->lstm_c_tmp, p->rows, s);
   RDV_HIP(hipGetLastError());
-  lstm_launch_trunk(p->spec.activation, p->out_dim == 1, p->weights, p->lstm_h_next, commit ? p->lstm_h : nullptr, out, p->rows, deterministic, seed,
-                    counter, env_id_offset, raw_actions, log_prob, s);
+  lstm_launch_trunk(p->spec.activation, p->out_dim == 1, p->weights, p->block_floats, table, p->lstm_h_next, commit ? p->lstm_h : nullptr, out,
+                    p->rows, deterministic, seed, counter, env_id_offset, raw_actions, log_prob, s);
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }
@@ -499,11 +549,29 @@ int rdv_lstm_reset_state(rdv_policy p, const uint8_t* mask, void* stream) {
 int rdv_lstm_set_weights(rdv_policy p, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh, const float* const* weights,
                          const float* const* biases, const float* log_std, void* stream) {
   RDV_CHECK_LSTM(p, "rdv_lstm_set_weights");
-  if (int rc = check_lstm_arrays("rdv_lstm_set_weights", p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
-  std::vector<float> packed;
-  pack_lstm_weights(p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
-  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "rdv_lstm_set_weights: the packed block has %d floats, the handle's %d", (int)packed.size(), p->block_floats);
-  return upload_block(p, "rdv_lstm_set_weights", 0, packed, stream);
+  if (p->n_members > 1) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_set_weights: this handle is a recurrent policy set of %d members: refresh one member with rdv_lstm_set_member_weights", p->n_members);
+  return refresh_lstm_member(p, "rdv_lstm_set_weights", 0, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, stream);
+}
+
+int rdv_lstm_set_member_weights(rdv_policy p, int32_t member, const float* w_ih, const float* w_hh, const float* b_ih, const float* b_hh,
+                                const float* const* weights, const float* const* biases, const float* log_std, void* stream) {
+  RDV_CHECK_LSTM(p, "rdv_lstm_set_member_weights");
+  if (member < 0 || member >= p->n_members) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_lstm_set_member_weights: member %d of %d", member, p->n_members);
+  return refresh_lstm_member(p, "rdv_lstm_set_member_weights", member, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, stream);
+}
+
+int rdv_lstm_policy_set_create(const RdvLstmSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* w_ih_host,
+                               const float* const* w_hh_host, const float* const* b_ih_host, const float* const* b_hh_host,
+                               const float* const* const* weights_host, const float* const* const* biases_host, const float* const* log_std_host,
+                               int device, rdv_policy* out) {
+  return create_lstm_set("rdv_lstm_policy_set_create", spec_host, n_members, sizes_host, w_ih_host, w_hh_host, b_ih_host, b_hh_host, weights_host,
+                         biases_host, log_std_host, kPolOut, device, out);
+}
+int rdv_lstm_critic_set_create(const RdvLstmSpec* spec_host, int32_t n_members, const int64_t* sizes_host, const float* const* w_ih_host,
+                               const float* const* w_hh_host, const float* const* b_ih_host, const float* const* b_hh_host,
+                               const float* const* const* weights_host, const float* const* const* biases_host, int device, rdv_policy* out) {
+  return create_lstm_set("rdv_lstm_critic_set_create", spec_host, n_members, sizes_host, w_ih_host, w_hh_host, b_ih_host, b_hh_host, weights_host,
+                         biases_host, nullptr, 1, device, out);
 }
 
 int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t n_steps, int64_t n, double gamma, double gae_lambda,

@@ -14,6 +14,7 @@
 //                           mlp_head) -> actions / value; when the call commits, the rows of h_next it has just read become h.
 // A call that does not commit (rdv_lstm_value with commit = 0) has the cell kernel write c' into a scratch buffer and the trunk kernel
 // leave h alone: h and c are then never written.  The state is fp32, row-major [rows, H], owned by the handle.
+// Recurrent sets (several networks, each owning a range of rows): the same two kernels with one more argument, see LstmSetBlocks below.
 //
 // The B operand of the h k-steps is read from the state as it lies: lane (r, hh) of k-step ks takes the 8 floats h[r][16 ks + 8 hh ..]
 // (two 16-byte loads), times 2^10, clamped to +-63 as an input is (|h| < 1 unless rdv_lstm_set_state put something else there; a NaN
@@ -131,11 +132,21 @@ inline void pack_lstm_weights(int H, const RdvMlpSpec& trunk, int out_dim, const
 
 // The launches (rdv_policy_lstm.hip).  `W`: the handle's block on the device.  start: u8 [n] or nullptr (no episode starts).
 // h, c: the state; h_next: where the cell kernel leaves h'; c_out: c (a committing call) or a scratch buffer.
-void lstm_launch_cell(int H, const float* W, const float* obs, const uint8_t* start, const float* h, const float* c, float* h_next, float* c_out,
-                      int64_t n, hipStream_t s);
+// tile_member: nullptr for one network (the block at W), or a recurrent set's tile table (device, one member index per 256 rows): the
+// set forms of the kernels, each workgroup reading the block at W + member * block_floats.
+void lstm_launch_cell(int H, const float* W, int block_floats, const int32_t* tile_member, const float* obs, const uint8_t* start, const float* h,
+                      const float* c, float* h_next, float* c_out, int64_t n, hipStream_t s);
 // h_commit: the state's h when the call commits (the rows of h_next are copied there), nullptr otherwise
-void lstm_launch_trunk(int activation, bool critic, const float* W, const float* h_next, float* h_commit, float* out, int64_t n, int deterministic,
-                       uint64_t seed, uint64_t counter, uint64_t env_id_offset, float* raw_actions, float* log_prob, hipStream_t s);
+void lstm_launch_trunk(int activation, bool critic, const float* W, int block_floats, const int32_t* tile_member, const float* h_next, float* h_commit,
+                       float* out, int64_t n, int deterministic, uint64_t seed, uint64_t counter, uint64_t env_id_offset, float* raw_actions,
+                       float* log_prob, hipStream_t s);
+// A recurrent set's last kernel argument (include/rdv.h, "Recurrent policy sets"): P blocks of block_floats floats back to back at W, and
+// the member that owns each 256-row tile.  A block is self-describing (header words 4 and 5 are relative to it) and block_floats is a
+// multiple of 4, so every 16-byte fragment read stays aligned.
+struct LstmSetBlocks {
+  const int32_t* tile_member;
+  int block_floats;
+};
 // rows of h and c whose mask byte is not 0 (mask nullptr: every row) <- 0
 void lstm_launch_reset(float* h, float* c, const uint8_t* mask, int64_t n, int H, hipStream_t s);
 
@@ -157,12 +168,22 @@ __device__ __forceinline__ void lstm_h_frag(const float* row8, f16x8 (&b)[2], po
   split2(x, b);
 }
 
+// The set forms of the two kernels are the same templates with ONE more argument, a LstmSetBlocks: lstm_cell_kernel<H, LstmSetBlocks> and
+// lstm_trunk_kernel<ACT, CRITIC, LstmSetBlocks>.  A workgroup owns 256 consecutive rows, which never span two members (every size but the
+// last is a multiple of 256), and reads its member's block at W + tile_member[blockIdx.x] * block_floats: one wave-uniform load more, no
+// barrier, no LDS hand-off, everything behind it the same device code — so row i of member g gets bit for bit what the plain kernel gives
+// a stand-alone handle of that member.  The plain forms (an empty pack) take no such argument and compile to what they were.
+__device__ __forceinline__ const float* lstm_member_block(const float* W, const LstmSetBlocks& set) {
+  return W + (size_t)set.tile_member[blockIdx.x] * (size_t)set.block_floats;
+}
+
 // One call of the cell for the wave's 32 envs.  512 threads = 8 waves = 256 envs per workgroup, as the actor kernels.
-template <int H>
+template <int H, class... SET>
 __global__ __launch_bounds__(kPolBlock) void lstm_cell_kernel(const float* __restrict__ W, const float* __restrict__ obs,
                                                               const uint8_t* __restrict__ start, const float* __restrict__ h_in,
                                                               const float* c_in, float* __restrict__ h_next,
-                                                              float* c_out /* = c_in when the call commits */, int64_t n) {
+                                                              float* c_out /* = c_in when the call commits */, int64_t n, SET... set) {
+  if constexpr (sizeof...(SET) != 0) W = lstm_member_block(W, set...);
   __shared__ __attribute__((aligned(16))) float stage[(kPolBlock / 64) * kPolObsStage];
   constexpr int NB = H / 32, TILES = 4 * NB, KS = 2 + H / 16;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -277,11 +298,13 @@ __device__ __forceinline__ void lstm_trunk_first(const float* wf, int frag0, int
 }
 
 // The trunk and the head for the wave's 32 envs; CRITIC: out = values [n], otherwise actions [n, 6] (and raw_actions / log_prob).
-template <int ACT, bool CRITIC>
+// (the noise of row i is keyed by env_id_offset + i, i counted over all rows: in a set, a stand-alone member's env_id_offset + start_g + its row)
+template <int ACT, bool CRITIC, class... SET>
 __global__ __launch_bounds__(kPolBlock) void lstm_trunk_kernel(const float* __restrict__ W, const float* __restrict__ h_next, float* __restrict__ h_commit,
                                                                float* __restrict__ out, int64_t n, int deterministic, uint64_t seed,
                                                                uint64_t counter, uint64_t env_id_offset, float* __restrict__ raw_actions,
-                                                               float* __restrict__ log_prob) {
+                                                               float* __restrict__ log_prob, SET... set) {
+  if constexpr (sizeof...(SET) != 0) W = lstm_member_block(W, set...);
   __shared__ __attribute__((aligned(16))) float astage[(kPolBlock / 64) * kPolActStage];
   const int32_t* Hd = reinterpret_cast<const int32_t*>(W);
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;

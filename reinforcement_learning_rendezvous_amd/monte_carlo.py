@@ -152,7 +152,9 @@ def sweep(policy, initial_states, configs, device="cuda:0", storage="f32", deter
     ``policy`` may also be a LIST of ``len(configs)`` policies of one architecture: config c is then evaluated by policy c — what the
     reference's evaluation callback does in a reward or seed sweep, one trained policy per configuration — through a ``PolicySet``
     over the same groups: one actor launch per timestep for all of them, the batch, the padding and the result format unchanged,
-    each table equal to ``run(policies[c], initial_states, config=configs[c])``."""
+    each table equal to ``run(policies[c], initial_states, config=configs[c])``.  A list of ``LstmPolicy`` goes through an
+    ``LstmPolicySet`` the same way (one cell and one trunk launch per timestep for all of them): the set's state is zero at the first
+    step, as a fresh policy's is in ``run``, and the members' own state is not touched."""
     from .batch import RendezvousBatch
     from .evaluation import episode_steps_bound
     from .params import GROUP_TILE
@@ -166,9 +168,11 @@ def sweep(policy, initial_states, configs, device="cuda:0", storage="f32", deter
     own_set = isinstance(policy, (list, tuple))
     if own_set:
         from .policy import PolicySet
+        from .policy_lstm import LstmPolicy, LstmPolicySet
         if len(policy) != len(params):
             raise ValueError(f"sweep: {len(policy)} policies for {len(params)} configs (a list of policies has one per config)")
-        policy = PolicySet(policy, [padded] * len(params))
+        recurrent = len(policy) > 0 and isinstance(policy[0], LstmPolicy)
+        policy = (LstmPolicySet if recurrent else PolicySet)(policy, [padded] * len(params))
     env = RendezvousBatch(padded * len(params), params=params, group_sizes=[padded] * len(params), device=device, storage=storage,
                           on_done="halt", seed=seed)
     policy = policy.to(env.device)

@@ -13,6 +13,9 @@ rdv_lstm_value); the state lives in device memory, owned by the handle.  ``backe
 ``torch.nn.LSTM`` and ``Linear`` modules with the same semantics, which the tests use as the kernels' reference.  Served: H in
 {32, 64, 128, 256}, trunks of 1..4 hidden layers of 16 / 32 / 64 with tanh / ReLU / sigmoid.  More LSTM layers, a shared LSTM, a critic
 without an LSTM and any other H raise ValueError.
+
+``LstmPolicySet`` holds P such policies of one architecture over one batch, member g owning a range of rows: one cell launch and one
+trunk launch per call for all members (include/rdv.h, "Recurrent policy sets"), the state of all rows owned by the set.
 """
 import ctypes as C
 import io
@@ -40,7 +43,222 @@ def check_lstm_config(lstm_hidden_size, n_lstm_layers=1, shared_lstm=False, enab
         raise ValueError(f"lstm_hidden_size = {lstm_hidden_size} is not one of {LSTM_HIDDEN_SIZES}")
 
 
-class LstmPolicy(_HipHandles, torch.nn.Module):
+class _LstmRows(_HipHandles):
+    """What LstmPolicy and LstmPolicySet share: the rows whose state (h, c) a recurrent handle owns, the pending episode-start flags and their
+    mirror, and the act / value / advantages calls on the handles of ``_create_handle``.  The class gives ``lstm_hidden_size``, ``n_rows``,
+    ``backend``, ``noise_seed``, ``noise_env_offset``, ``_calls``, ``_state``, ``_pending``, and for the PyTorch path ``_module_device``,
+    ``_forward_torch(prefix, obs, start, commit)`` (one step of the modules: means [n, 6] or values [n, 1]) and
+    ``_sample_torch(mean, deterministic, generator, log_prob_out)`` (the unclipped action; ``log_prob_out`` [n] or None is filled)."""
+
+    def _rows(self, n):
+        if self.n_rows is None:
+            self.n_rows = int(n)
+        if int(n) != self.n_rows:
+            raise ValueError(f"{n} rows, the policy owns the state of {self.n_rows}")
+        return self.n_rows
+
+    def _torch_state(self, prefix, device):
+        if self.n_rows is None:
+            raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
+        st = self._state.get(prefix)
+        if st is None:
+            st = [torch.zeros((self.n_rows, self.lstm_hidden_size), dtype=torch.float32, device=device) for _ in range(2)]
+        elif st[0].device != device:
+            st = [t.to(device) for t in st]
+        self._state[prefix] = st
+        return st
+
+    def _pending_flags(self, prefix, device):
+        """The pending episode-start flags as a uint8 [rows] tensor."""
+        p = self._pending[prefix]
+        if isinstance(p, torch.Tensor):
+            return p.to(device)
+        return torch.full((self.n_rows,), 1 if p else 0, dtype=torch.uint8, device=device)
+
+    def state_at_start(self, prefix="l", device=None):
+        """``(h, c)`` as the next rollout's first step will see it: the state, zero where an episode start is pending — what
+        RecurrentPPO's buffer keeps for a sequence start (``RendezvousBatch.rollout`` returns it as ``lstm_state0``)."""
+        h, c = self._get_state(prefix, device)
+        keep = (self._pending_flags(prefix, h.device) == 0).to(h.dtype)[:, None]
+        return h * keep, c * keep
+
+    def _use_hip(self, obs):
+        return self.backend == "hip" or (self.backend == "auto" and obs.is_cuda and obs.dtype == torch.float32)
+
+    def _handle(self, prefix, device):
+        if self.n_rows is None:
+            raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
+        return super()._handle(prefix, device)
+
+    def _get_state(self, prefix, device=None):
+        table = self._hip if prefix == "l" else self._hip_critic
+        if self.backend != "torch" and table:
+            from . import _native as N
+            idx = next(iter(table)) if device is None or torch.device(device).index is None else torch.device(device).index
+            dev = torch.device("cuda", idx)
+            h = torch.empty((self.n_rows, self.lstm_hidden_size), dtype=torch.float32, device=dev)
+            c = torch.empty_like(h)
+            N.check(N.lib().rdv_lstm_get_state(table[idx], C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), self._stream(dev)))
+            return h, c
+        st = self._torch_state(prefix, torch.device(device) if device is not None else self._module_device)
+        return st[0].clone(), st[1].clone()
+
+    def _set_state(self, prefix, hc, device=None):
+        h, c = hc
+        if self.backend != "torch" and isinstance(h, torch.Tensor) and h.is_cuda:
+            from . import _native as N
+            self._rows(h.shape[0])
+            h, c = h.to(torch.float32).contiguous(), c.to(torch.float32).contiguous()
+            N.check(N.lib().rdv_lstm_set_state(self._handle(prefix, h.device), C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), self._stream(h.device)))
+            self._pending[prefix] = False
+            return
+        h = torch.as_tensor(h, dtype=torch.float32)
+        c = torch.as_tensor(c, dtype=torch.float32)
+        self._rows(h.shape[0])
+        st = self._torch_state(prefix, h.device)
+        st[0].copy_(h); st[1].copy_(c)
+        self._pending[prefix] = False
+
+    @property
+    def state(self):
+        """The actor's ``(h, c)``, [rows, H] float32 each, plain row-major (a copy)."""
+        return self._get_state("l")
+
+    @state.setter
+    def state(self, hc):
+        self._set_state("l", hc)
+
+    @property
+    def critic_state(self):
+        return self._get_state("v")
+
+    @critic_state.setter
+    def critic_state(self, hc):
+        self._set_state("v", hc)
+
+    @torch.no_grad()
+    def reset_state(self, mask=None):
+        """Zero state for the rows of ``mask`` (None: every row), actor and critic alike."""
+        from . import _native as N
+        for prefix, table in (("l", self._hip), ("v", self._hip_critic)):
+            for idx, hnd in table.items():
+                dev = torch.device("cuda", idx)
+                m = None if mask is None else torch.as_tensor(mask).to(dev, torch.uint8).contiguous()
+                N.check(N.lib().rdv_lstm_reset_state(hnd, None if m is None else C.c_void_p(m.data_ptr()), self._stream(dev)))
+            st = self._state.get(prefix)
+            if st is not None:
+                keep = torch.zeros(self.n_rows, dtype=torch.bool, device=st[0].device) if mask is None else \
+                    ~torch.as_tensor(mask).to(st[0].device).bool()
+                st[0].mul_(keep[:, None]); st[1].mul_(keep[:, None])
+
+    @staticmethod
+    def _aligned(obs):
+        """Contiguous rows at a 16-byte aligned address, as the kernels read them (row t of a [T, N, 17] tensor is not when N % 4 != 0)."""
+        obs = obs.contiguous()
+        return obs.clone() if obs.data_ptr() % 16 else obs
+
+    @staticmethod
+    def _flags(episode_start, n, device):
+        if episode_start is None:
+            return None
+        f = torch.as_tensor(np.asarray(episode_start) if not isinstance(episode_start, torch.Tensor) else episode_start)
+        if f.shape != (n,):
+            raise ValueError(f"episode_start: expected {n} flags, got {tuple(f.shape)}")
+        return (f != 0).to(device, torch.uint8).contiguous()
+
+    @torch.no_grad()
+    def act(self, obs, episode_start=None, deterministic=True, generator=None, out=None, env_id_offset=None, raw_out=None, log_prob_out=None):
+        """One step of the actor on observations [n, 17], n the policy's rows: the clipped action; the state advances.
+        ``episode_start``: [n] flags (None: no row starts an episode).  HIP backend: noise keyed by (noise_seed, env_id_offset + i,
+        call counter), as ``MlpPolicy.act``; ``raw_out`` [n, 6] / ``log_prob_out`` [n] receive the unclipped sample and its log-density."""
+        n = self._rows(obs.shape[0])
+        if self._use_hip(obs):
+            from . import _native as N
+            if generator is not None:
+                self.noise_seed = int(generator.initial_seed())
+            offset = self.noise_env_offset if env_id_offset is None else int(env_id_offset)
+            obs = self._aligned(obs)
+            flags = self._flags(episode_start, n, obs.device)
+            if out is None:
+                out = torch.empty((n, 6), dtype=torch.float32, device=obs.device)
+            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+            N.check(N.lib().rdv_lstm_act(self._handle("l", obs.device), ptr(obs), ptr(flags), ptr(out), ptr(raw_out), ptr(log_prob_out), n,
+                                         int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls), C.c_uint64(offset),
+                                         self._stream(obs.device)))
+            self._calls += 1
+            self._pending["l"] = False
+            return out
+        mean = self._forward_torch("l", obs, self._flags(episode_start, n, obs.device))
+        a = self._sample_torch(mean, deterministic, generator, log_prob_out)
+        if raw_out is not None:
+            raw_out.copy_(a)
+        res = torch.clamp(a, -1.0, 1.0)
+        if out is not None:
+            out.copy_(res)
+            return out
+        return res
+
+    @torch.no_grad()
+    def value(self, obs, episode_start=None, commit=True, out=None):
+        """One step of the critic on observations [n, 17]: values [n].  ``commit=False`` evaluates without writing the critic's state
+        (sb3-contrib's ``predict_values`` for the value of the last observation)."""
+        n = self._rows(obs.shape[0])
+        if self._use_hip(obs):
+            from . import _native as N
+            obs = self._aligned(obs)
+            flags = self._flags(episode_start, n, obs.device)
+            if out is None:
+                out = torch.empty((n,), dtype=torch.float32, device=obs.device)
+            N.check(N.lib().rdv_lstm_value(self._handle("v", obs.device), C.c_void_p(obs.data_ptr()), None if flags is None else C.c_void_p(flags.data_ptr()),
+                                           C.c_void_p(out.data_ptr()), n, int(bool(commit)), self._stream(obs.device)))
+            if commit:
+                self._pending["v"] = False
+            return out
+        v = self._forward_torch("v", obs, self._flags(episode_start, n, obs.device), commit=commit)[:, 0]
+        if out is not None:
+            out.copy_(v)
+            return out
+        return v
+
+    @torch.no_grad()
+    def advantages(self, ro, gamma=0.99, gae_lambda=0.95, out=None):
+        """``MlpPolicy.advantages`` for the recurrent critic: T committing critic steps in time order over ``ro["obs"]`` (episode starts:
+        the critic's pending flags, then ``ro["done"][t-1]``), one non-committing step on ``ro["last_obs"]`` with ``done[T-1]``, GAE."""
+        from . import advantages as A
+        obs = ro["obs"]
+        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
+            raise ValueError(f"obs: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
+        T, n, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+        self._rows(n)
+        A.check_tensor(obs, "obs", (T, n, 17), torch.float32, dev)
+        A.check_tensor(ro["reward"], "reward", (T, n), torch.float32, dev)
+        A.check_tensor(ro["done"], "done", (T, n), torch.uint8, dev)
+        A.check_tensor(ro["last_obs"], "last_obs", (n, 17), torch.float32, dev)
+        A.check_discounts(gamma, gae_lambda)
+        src = out if out is not None else ro
+        for name, shape in dict(values=(T, n), last_value=(n,), advantages=(T, n), returns=(T, n)).items():
+            t = src.get(name)
+            if t is None or tuple(t.shape) != shape or t.device != dev:
+                t = torch.empty(shape, dtype=torch.float32, device=dev)
+            ro[name] = t
+        if self.backend != "torch" and obs.is_cuda:
+            from . import _native as N
+            rows = N.RolloutOut(obs.data_ptr(), None, ro["reward"].data_ptr(), ro["done"].data_ptr(), None, ro["last_obs"].data_ptr())
+            ao = N.AdvantageOut(*[ro[f].data_ptr() for f, _ in N.AdvantageOut._fields_])
+            N.check(N.lib().rdv_rollout_advantages(self._handle("v", dev), C.byref(rows), T, n, float(gamma), float(gae_lambda), C.byref(ao),
+                                                   self._stream(dev)))
+            self._pending["v"] = ro["done"][T - 1].clone()
+            return ro
+        for t in range(T):
+            flags = self._pending_flags("v", dev) if t == 0 else ro["done"][t - 1]
+            self.value(obs[t], episode_start=flags, out=ro["values"][t])
+        self.value(ro["last_obs"], episode_start=ro["done"][T - 1], commit=False, out=ro["last_value"])
+        self._pending["v"] = ro["done"][T - 1].clone()
+        A.gae(ro["reward"], ro["done"], ro["values"], ro["last_value"], gamma, gae_lambda, out=(ro["advantages"], ro["returns"]))
+        return ro
+
+
+class LstmPolicy(_LstmRows, torch.nn.Module):
     def __init__(self, weights=None, lstm_hidden_size=256, net_arch=None, activation_fn="tanh", n_rows=None, seed=0, backend="auto",
                  n_lstm_layers=1, shared_lstm=False, enable_critic_lstm=True):
         super().__init__()
@@ -149,42 +367,7 @@ class LstmPolicy(_HipHandles, torch.nn.Module):
                     kwargs["activation_fn"] = parse_activation(fn)
         return cls({k: v.numpy() for k, v in sd.items()}, **kwargs)
 
-    # ------------------------------------------------------------------------------------------------ rows and state
-    def _rows(self, n):
-        if self.n_rows is None:
-            self.n_rows = int(n)
-        if int(n) != self.n_rows:
-            raise ValueError(f"{n} rows, the policy owns the state of {self.n_rows}")
-        return self.n_rows
-
-    def _torch_state(self, prefix, device):
-        if self.n_rows is None:
-            raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
-        st = self._state.get(prefix)
-        if st is None:
-            st = [torch.zeros((self.n_rows, self.lstm_hidden_size), dtype=torch.float32, device=device) for _ in range(2)]
-        elif st[0].device != device:
-            st = [t.to(device) for t in st]
-        self._state[prefix] = st
-        return st
-
-    def _pending_flags(self, prefix, device):
-        """The pending episode-start flags as a uint8 [rows] tensor."""
-        p = self._pending[prefix]
-        if isinstance(p, torch.Tensor):
-            return p.to(device)
-        return torch.full((self.n_rows,), 1 if p else 0, dtype=torch.uint8, device=device)
-
-    def state_at_start(self, prefix="l", device=None):
-        """``(h, c)`` as the next rollout's first step will see it: the state, zero where an episode start is pending — what
-        RecurrentPPO's buffer keeps for a sequence start (``RendezvousBatch.rollout`` returns it as ``lstm_state0``)."""
-        h, c = self._get_state(prefix, device)
-        keep = (self._pending_flags(prefix, h.device) == 0).to(h.dtype)[:, None]
-        return h * keep, c * keep
-
-    def _use_hip(self, obs):
-        return self.backend == "hip" or (self.backend == "auto" and obs.is_cuda and obs.dtype == torch.float32)
-
+    # ------------------------------------------------------------------------------------------------ handles
     def _host_arrays(self, prefix):
         host = lambda t: t.detach().to("cpu", torch.float32).contiguous()
         lstm = self._lstm(prefix)
@@ -207,72 +390,6 @@ class LstmPolicy(_HipHandles, torch.nn.Module):
             N.check(N.lib().rdv_lstm_critic_create(C.byref(spec), *lp, wp, bp, self.n_rows, idx, C.byref(h)))
         return h
 
-    def _handle(self, prefix, device):
-        if self.n_rows is None:
-            raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
-        return super()._handle(prefix, device)
-
-    def _get_state(self, prefix, device=None):
-        table = self._hip if prefix == "l" else self._hip_critic
-        if self.backend != "torch" and table:
-            from . import _native as N
-            idx = next(iter(table)) if device is None or torch.device(device).index is None else torch.device(device).index
-            dev = torch.device("cuda", idx)
-            h = torch.empty((self.n_rows, self.lstm_hidden_size), dtype=torch.float32, device=dev)
-            c = torch.empty_like(h)
-            N.check(N.lib().rdv_lstm_get_state(table[idx], C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), self._stream(dev)))
-            return h, c
-        st = self._torch_state(prefix, torch.device(device) if device is not None else self.log_std.device)
-        return st[0].clone(), st[1].clone()
-
-    def _set_state(self, prefix, hc, device=None):
-        h, c = hc
-        if self.backend != "torch" and isinstance(h, torch.Tensor) and h.is_cuda:
-            from . import _native as N
-            self._rows(h.shape[0])
-            h, c = h.to(torch.float32).contiguous(), c.to(torch.float32).contiguous()
-            N.check(N.lib().rdv_lstm_set_state(self._handle(prefix, h.device), C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), self._stream(h.device)))
-            self._pending[prefix] = False
-            return
-        h = torch.as_tensor(h, dtype=torch.float32)
-        c = torch.as_tensor(c, dtype=torch.float32)
-        self._rows(h.shape[0])
-        st = self._torch_state(prefix, h.device)
-        st[0].copy_(h); st[1].copy_(c)
-        self._pending[prefix] = False
-
-    @property
-    def state(self):
-        """The actor's ``(h, c)``, [rows, H] float32 each, plain row-major (a copy)."""
-        return self._get_state("l")
-
-    @state.setter
-    def state(self, hc):
-        self._set_state("l", hc)
-
-    @property
-    def critic_state(self):
-        return self._get_state("v")
-
-    @critic_state.setter
-    def critic_state(self, hc):
-        self._set_state("v", hc)
-
-    @torch.no_grad()
-    def reset_state(self, mask=None):
-        """Zero state for the rows of ``mask`` (None: every row), actor and critic alike."""
-        from . import _native as N
-        for prefix, table in (("l", self._hip), ("v", self._hip_critic)):
-            for idx, hnd in table.items():
-                dev = torch.device("cuda", idx)
-                m = None if mask is None else torch.as_tensor(mask).to(dev, torch.uint8).contiguous()
-                N.check(N.lib().rdv_lstm_reset_state(hnd, None if m is None else C.c_void_p(m.data_ptr()), self._stream(dev)))
-            st = self._state.get(prefix)
-            if st is not None:
-                keep = torch.zeros(self.n_rows, dtype=torch.bool, device=st[0].device) if mask is None else \
-                    ~torch.as_tensor(mask).to(st[0].device).bool()
-                st[0].mul_(keep[:, None]); st[1].mul_(keep[:, None])
-
     # ------------------------------------------------------------------------------------------------ evaluation
     def _cell_torch(self, prefix, obs, start, commit=True):
         """One step of the PyTorch modules on [n, 17] observations: the latent h' (the state advances when ``commit``)."""
@@ -291,44 +408,14 @@ class LstmPolicy(_HipHandles, torch.nn.Module):
             x = self._fn(lin(x))
         return layers[-1](x)
 
-    @staticmethod
-    def _aligned(obs):
-        """Contiguous rows at a 16-byte aligned address, as the kernels read them (row t of a [T, N, 17] tensor is not when N % 4 != 0)."""
-        obs = obs.contiguous()
-        return obs.clone() if obs.data_ptr() % 16 else obs
+    @property
+    def _module_device(self):
+        return self.log_std.device
 
-    @staticmethod
-    def _flags(episode_start, n, device):
-        if episode_start is None:
-            return None
-        f = torch.as_tensor(np.asarray(episode_start) if not isinstance(episode_start, torch.Tensor) else episode_start)
-        if f.shape != (n,):
-            raise ValueError(f"episode_start: expected {n} flags, got {tuple(f.shape)}")
-        return (f != 0).to(device, torch.uint8).contiguous()
+    def _forward_torch(self, prefix, obs, start, commit=True):
+        return self._trunk_torch(prefix, self._cell_torch(prefix, obs, start, commit=commit))
 
-    @torch.no_grad()
-    def act(self, obs, episode_start=None, deterministic=True, generator=None, out=None, env_id_offset=None, raw_out=None, log_prob_out=None):
-        """One step of the actor on observations [n, 17], n the policy's rows: the clipped action; the state advances.
-        ``episode_start``: [n] flags (None: no row starts an episode).  HIP backend: noise keyed by (noise_seed, env_id_offset + i,
-        call counter), as ``MlpPolicy.act``; ``raw_out`` [n, 6] / ``log_prob_out`` [n] receive the unclipped sample and its log-density."""
-        n = self._rows(obs.shape[0])
-        if self._use_hip(obs):
-            from . import _native as N
-            if generator is not None:
-                self.noise_seed = int(generator.initial_seed())
-            offset = self.noise_env_offset if env_id_offset is None else int(env_id_offset)
-            obs = self._aligned(obs)
-            flags = self._flags(episode_start, n, obs.device)
-            if out is None:
-                out = torch.empty((n, 6), dtype=torch.float32, device=obs.device)
-            ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
-            N.check(N.lib().rdv_lstm_act(self._handle("l", obs.device), ptr(obs), ptr(flags), ptr(out), ptr(raw_out), ptr(log_prob_out), n,
-                                         int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls), C.c_uint64(offset),
-                                         self._stream(obs.device)))
-            self._calls += 1
-            self._pending["l"] = False
-            return out
-        mean = self._trunk_torch("l", self._cell_torch("l", obs, self._flags(episode_start, n, obs.device)))
+    def _sample_torch(self, mean, deterministic, generator, log_prob_out):
         a = mean
         if not deterministic:
             noise = torch.randn(a.shape, dtype=a.dtype, device=a.device, generator=generator)
@@ -337,35 +424,7 @@ class LstmPolicy(_HipHandles, torch.nn.Module):
                 log_prob_out.copy_((-0.5 * noise * noise - self.log_std).sum(dim=1) - 3.0 * float(np.log(2.0 * np.pi)))
         elif log_prob_out is not None:
             log_prob_out.fill_(-float(self.log_std.sum()) - 3.0 * float(np.log(2.0 * np.pi)))
-        if raw_out is not None:
-            raw_out.copy_(a)
-        res = torch.clamp(a, -1.0, 1.0)
-        if out is not None:
-            out.copy_(res)
-            return out
-        return res
-
-    @torch.no_grad()
-    def value(self, obs, episode_start=None, commit=True, out=None):
-        """One step of the critic on observations [n, 17]: values [n].  ``commit=False`` evaluates without writing the critic's state
-        (sb3-contrib's ``predict_values`` for the value of the last observation)."""
-        n = self._rows(obs.shape[0])
-        if self._use_hip(obs):
-            from . import _native as N
-            obs = self._aligned(obs)
-            flags = self._flags(episode_start, n, obs.device)
-            if out is None:
-                out = torch.empty((n,), dtype=torch.float32, device=obs.device)
-            N.check(N.lib().rdv_lstm_value(self._handle("v", obs.device), C.c_void_p(obs.data_ptr()), None if flags is None else C.c_void_p(flags.data_ptr()),
-                                           C.c_void_p(out.data_ptr()), n, int(bool(commit)), self._stream(obs.device)))
-            if commit:
-                self._pending["v"] = False
-            return out
-        v = self._trunk_torch("v", self._cell_torch("v", obs, self._flags(episode_start, n, obs.device), commit=commit))[:, 0]
-        if out is not None:
-            out.copy_(v)
-            return out
-        return v
+        return a
 
     def predict(self, observation, state=None, episode_start=None, deterministic=True):
         """SB3's calling convention (save_new_trajectory.py:106): NumPy observations [n, 17] (or [17]); ``state`` = the ``(h, c)`` a
@@ -380,44 +439,6 @@ class LstmPolicy(_HipHandles, torch.nn.Module):
         a = self.act(obs, episode_start=episode_start, deterministic=deterministic).cpu().numpy()
         h, c = self._get_state("l", dev)
         return (a[0] if single else a), (h.cpu().numpy(), c.cpu().numpy())
-
-    # ------------------------------------------------------------------------------------------------ rollouts
-    @torch.no_grad()
-    def advantages(self, ro, gamma=0.99, gae_lambda=0.95, out=None):
-        """``MlpPolicy.advantages`` for the recurrent critic: T committing critic steps in time order over ``ro["obs"]`` (episode starts:
-        the critic's pending flags, then ``ro["done"][t-1]``), one non-committing step on ``ro["last_obs"]`` with ``done[T-1]``, GAE."""
-        from . import advantages as A
-        obs = ro["obs"]
-        if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
-            raise ValueError(f"obs: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
-        T, n, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
-        self._rows(n)
-        A.check_tensor(obs, "obs", (T, n, 17), torch.float32, dev)
-        A.check_tensor(ro["reward"], "reward", (T, n), torch.float32, dev)
-        A.check_tensor(ro["done"], "done", (T, n), torch.uint8, dev)
-        A.check_tensor(ro["last_obs"], "last_obs", (n, 17), torch.float32, dev)
-        A.check_discounts(gamma, gae_lambda)
-        src = out if out is not None else ro
-        for name, shape in dict(values=(T, n), last_value=(n,), advantages=(T, n), returns=(T, n)).items():
-            t = src.get(name)
-            if t is None or tuple(t.shape) != shape or t.device != dev:
-                t = torch.empty(shape, dtype=torch.float32, device=dev)
-            ro[name] = t
-        if self.backend != "torch" and obs.is_cuda:
-            from . import _native as N
-            rows = N.RolloutOut(obs.data_ptr(), None, ro["reward"].data_ptr(), ro["done"].data_ptr(), None, ro["last_obs"].data_ptr())
-            ao = N.AdvantageOut(*[ro[f].data_ptr() for f, _ in N.AdvantageOut._fields_])
-            N.check(N.lib().rdv_rollout_advantages(self._handle("v", dev), C.byref(rows), T, n, float(gamma), float(gae_lambda), C.byref(ao),
-                                                   self._stream(dev)))
-            self._pending["v"] = ro["done"][T - 1].clone()
-            return ro
-        for t in range(T):
-            flags = self._pending_flags("v", dev) if t == 0 else ro["done"][t - 1]
-            self.value(obs[t], episode_start=flags, out=ro["values"][t])
-        self.value(ro["last_obs"], episode_start=ro["done"][T - 1], commit=False, out=ro["last_value"])
-        self._pending["v"] = ro["done"][T - 1].clone()
-        A.gae(ro["reward"], ro["done"], ro["values"], ro["last_value"], gamma, gae_lambda, out=(ro["advantages"], ro["returns"]))
-        return ro
 
     def update_weights(self, weights=None):
         """New weights for the modules (a dict with the constructor's keys; None: push the modules' current parameters) and for every
@@ -434,3 +455,147 @@ class LstmPolicy(_HipHandles, torch.nn.Module):
             for idx, h in table.items():
                 N.check(N.lib().rdv_lstm_set_weights(h, *[C.c_void_p(t.data_ptr()) for t in lstm], _ptrs(ws), _ptrs(bs),
                                                      C.c_void_p(log_std[0].data_ptr()) if log_std else None, self._stream(torch.device("cuda", idx))))
+
+
+class LstmPolicySet(_LstmRows):
+    """P recurrent member policies of ONE architecture over one batch: member g owns the next ``group_sizes[g]`` rows, and one cell launch
+    and one trunk launch per call evaluate all members (include/rdv.h, "Recurrent policy sets"; csrc/rdv_policy_lstm.h) — what
+    ``PolicySet`` is for MLP learners.  Row i of member g gets bit for bit what a stand-alone ``LstmPolicy`` of member g's weights with
+    ``n_rows = group_sizes[g]`` computes for that row, fed the same observations and episode starts, with the same noise seed, the same
+    call counter and ``env_id_offset + start_g`` — actions, samples, log-densities, values, and the state after every call.
+
+    ``policies``: ``LstmPolicy`` modules with the same ``lstm_hidden_size``, ``pi_arch``, ``vf_arch`` and ``activation`` (ValueError naming
+    the member and the field).  They stay the source of truth for the weights (``set[g]``); their own ``n_rows`` and state are not used:
+    the SET owns the state of all rows (``state``, ``critic_state``, ``reset_state``, ``state_at_start``) and the pending episode-start
+    flags.  ``group_sizes``: positive, every one but the last a multiple of 256 rows — the rule and the messages of
+    rdv_param_groups_check, checked on the host.  ``RendezvousBatch.rollout`` / ``collect`` take a set where they take an ``LstmPolicy``;
+    the set's ranges and the batch's parameter groups are independent.  One noise key for the whole set (``seed``) and one call counter.
+    CUDA float32 input goes to the set kernels; CPU input or ``backend="torch"`` loops the members' modules over their slices."""
+
+    def __init__(self, policies, group_sizes, seed=0, backend="auto"):
+        from .params import group_tile_table
+        policies = list(policies)
+        if not policies:
+            raise ValueError("LstmPolicySet: at least one member policy")
+        sizes = [int(x) for x in group_sizes]
+        if len(sizes) != len(policies):
+            raise ValueError(f"LstmPolicySet: {len(policies)} policies but {len(sizes)} group sizes")
+        for g, p in enumerate(policies):
+            if not isinstance(p, LstmPolicy):
+                raise TypeError(f"LstmPolicySet: member {g} is a {type(p).__name__}, not an LstmPolicy")
+            for what in ("lstm_hidden_size", "pi_arch", "vf_arch", "activation"):
+                if getattr(p, what) != getattr(policies[0], what):
+                    raise ValueError(f"LstmPolicySet: member {g} has {what} = {getattr(p, what)!r}, member 0 has "
+                                     f"{getattr(policies[0], what)!r}: the members of a set share one architecture")
+        group_tile_table(sum(sizes), sizes)
+        first = policies[0]
+        self.policies, self.group_sizes = policies, sizes
+        self.n_rows = self.num_rows = sum(sizes)
+        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self.group_slices = [slice(int(starts[g]), int(starts[g + 1])) for g in range(len(sizes))]
+        self.backend = backend
+        self.noise_seed = int(seed)
+        self.noise_env_offset = 0
+        self._calls = 0
+        self._hip, self._hip_critic = {}, {}        # device index -> rdv_policy handle of the set (each owns the state of all rows)
+        self.lstm_hidden_size = first.lstm_hidden_size
+        self.pi_arch, self.vf_arch, self.activation = list(first.pi_arch), list(first.vf_arch), first.activation
+        self.has_critic = True
+        self._state = {}
+        self._pending = {"l": True, "v": True}
+
+    def __len__(self):
+        return len(self.policies)
+
+    def __getitem__(self, g):
+        return self.policies[g]
+
+    def __iter__(self):
+        return iter(self.policies)
+
+    def to(self, *args, **kwargs):
+        """The member modules moved as ``torch.nn.Module.to`` moves them (the HIP handles live on the device of the rows they are given)."""
+        self.policies = [p.to(*args, **kwargs) for p in self.policies]
+        return self
+
+    # ------------------------------------------------------------------------------------------------ handles
+    def _create_handle(self, prefix, idx):
+        """rdv_lstm_policy_set_create / rdv_lstm_critic_set_create from the members' modules."""
+        from . import _native as N
+        arch = self.pi_arch if prefix == "l" else self.vf_arch
+        spec = N.LstmSpec.make(self.lstm_hidden_size, arch, ACTIVATIONS[self.activation][0])
+        N.check(N.lib().rdv_lstm_spec_check(C.byref(spec)))
+        host = [p._host_arrays(prefix) for p in self.policies]        # kept alive until the call returns
+        P = len(host)
+        lstm = [_ptrs([m[0][k] for m in host]) for k in range(len(_LSTM_KEYS))]
+        wps, bps = [_ptrs(m[1]) for m in host], [_ptrs(m[2]) for m in host]
+        wpp = (C.c_void_p * P)(*[C.addressof(a) for a in wps])
+        bpp = (C.c_void_p * P)(*[C.addressof(a) for a in bps])
+        sizes = (C.c_int64 * P)(*self.group_sizes)
+        h = C.c_void_p()
+        if prefix == "l":
+            lsp = _ptrs([m[3][0] for m in host])
+            N.check(N.lib().rdv_lstm_policy_set_create(C.byref(spec), P, sizes, *lstm, wpp, bpp, lsp, idx, C.byref(h)))
+        else:
+            N.check(N.lib().rdv_lstm_critic_set_create(C.byref(spec), P, sizes, *lstm, wpp, bpp, idx, C.byref(h)))
+        return h
+
+    # ------------------------------------------------------------------------------------------------ the PyTorch path
+    @property
+    def _module_device(self):
+        return self.policies[0].log_std.device
+
+    def _forward_torch(self, prefix, obs, start, commit=True):
+        """One step of the members' modules, each on its slice of the set's state."""
+        st = self._torch_state(prefix, obs.device)
+        keep = 1.0 - (torch.zeros(obs.shape[0], device=obs.device) if start is None else start.to(obs.device, torch.float32))
+        outs = []
+        for p, s in zip(self.policies, self.group_slices):
+            h0, c0 = st[0][s] * keep[s, None], st[1][s] * keep[s, None]
+            _, (h1, c1) = p._lstm(prefix)(obs[s][None].to(torch.float32), (h0[None], c0[None]))
+            if commit:
+                st[0][s].copy_(h1[0]); st[1][s].copy_(c1[0])
+            outs.append(p._trunk_torch(prefix, h1[0]))
+        if commit:
+            self._pending[prefix] = False
+        return torch.cat(outs, dim=0)
+
+    def _sample_torch(self, mean, deterministic, generator, log_prob_out):
+        return torch.cat([p._sample_torch(mean[s], deterministic, generator, None if log_prob_out is None else log_prob_out[s])
+                          for p, s in zip(self.policies, self.group_slices)], dim=0)
+
+    # ------------------------------------------------------------------------------------------------ weights
+    def update_weights(self, member=None, weights=None):
+        """New weights for one member (``member`` = its index; ``weights``: a dict as ``LstmPolicy.update_weights`` takes, or None to
+        push the member module's current parameters) or for all members (``member`` None; ``weights``: None or a list of one dict or
+        None per member).  Dicts are loaded into the member modules first; then every live set handle is refreshed member by member
+        through rdv_lstm_set_member_weights on the current stream of its device: launches already queued there use the old weights,
+        later ones the new; the state and the other members' blocks are not touched.  Not legal while the current stream is being
+        captured (RdvError, nothing touched).  The noise key and the call counter are unchanged."""
+        P = len(self.policies)
+        if (self._hip or self._hip_critic) and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            from . import _native as N
+            raise N.RdvError(-1, "rdv_lstm_set_member_weights: not legal inside a stream capture (the staging buffer is reused by the next call)")
+        if member is None:
+            todo = list(range(P))
+            per = weights if weights is not None else [None] * P
+            if isinstance(per, dict) or len(per) != P:
+                raise ValueError(f"update_weights: weights for all members is a list of {P} dicts (or None); pass member= for one")
+        else:
+            member = int(member)
+            if not 0 <= member < P:
+                raise IndexError(f"update_weights: member {member} of {P}")
+            todo, per = [member], {member: weights}
+        for g in todo:
+            if per[g] is not None:
+                self.policies[g]._load_weights(per[g])
+        if not (self._hip or self._hip_critic):
+            return
+        from . import _native as N
+        for prefix, table in (("l", self._hip), ("v", self._hip_critic)):
+            for g in todo if table else []:
+                lstm, ws, bs, log_std = self.policies[g]._host_arrays(prefix)
+                for idx, h in table.items():
+                    N.check(N.lib().rdv_lstm_set_member_weights(h, g, *[C.c_void_p(t.data_ptr()) for t in lstm], _ptrs(ws), _ptrs(bs),
+                                                                C.c_void_p(log_std[0].data_ptr()) if log_std else None,
+                                                                self._stream(torch.device("cuda", idx))))
