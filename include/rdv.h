@@ -520,8 +520,9 @@ int rdv_rollout(rdv_handle h, rdv_policy p, int32_t n_steps, const RdvRolloutOut
  * Learner-ready rollouts (added within ABI 5): the columns of SB3's RolloutBuffer that rdv_rollout does not write — values, advantages,
  * returns (RolloutBuffer.compute_returns_and_advantage, called by collect_rollouts; reference main.py:114) — and the refresh of a policy
  * handle's weights after an optimiser step.  The reference never sets TimeLimit.truncated (vec_env.py:6-7), so SB3's time-limit
- * bootstrap does not apply and is not built.  Out of scope: the PPO update itself and advantage normalisation (SB3 normalises per
- * minibatch in train()).
+ * bootstrap does not apply and is not built.  The loss and the gradients of one PPO minibatch are rdv_ppo_loss_grad ("PPO minibatch
+ * gradients", below); out of scope: advantage normalisation (SB3 normalises per minibatch in train(); the Python layer does it in
+ * torch), gradient clipping, the optimiser and its schedules, which stay PyTorch's.
  *
  * rdv_gae: generalised advantage estimation over [T,N] rows, ONE kernel for all T steps (csrc/rdv_advantages.h).  reward, done, values,
  *   advantages and returns are [n_steps, n] contiguous device arrays, time-major, as rdv_rollout writes them; last_value is [n].  done[t]
@@ -574,6 +575,85 @@ int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t
                            const RdvAdvantageOut* out, void* stream);
 int rdv_policy_set_weights(rdv_policy p, const float* const* weights_host, const float* const* biases_host, const float* log_std_host,
                            void* stream);
+
+/*
+ * PPO minibatch gradients (added within ABI 5): the loss of SB3's PPO.train() for ONE minibatch of n samples and its gradients with respect
+ * to every parameter of the shipped actor and critic, in one call on the device (csrc/rdv_ppo.h).  Gradient clipping, the optimiser (Adam)
+ * and the learning-rate / clip-range schedules stay PyTorch's: they run on the gradients this call writes, and rdv_policy_set_weights then
+ * pushes the new weights as before.
+ *
+ * The mathematics (ActorCriticPolicy.evaluate_actions with a DiagGaussianDistribution, clip_range_vf = None; eps = clip_range), for the
+ * sampled rows i = 0 .. n-1, mean mu_i and value v_i of the handles' networks, sigma = exp(log_std):
+ *     log_prob_i   = sum_c ( -(a_c - mu_c)^2 / (2 sigma_c^2) - log_std_c ) - 3 ln(2 pi)
+ *     entropy_i    = sum_c ( 0.5 + 0.5 ln(2 pi) + log_std_c )
+ *     ratio_i      = exp(log_prob_i - old_log_prob_i)
+ *     policy_loss  = -mean( min(A_i ratio_i, A_i clamp(ratio_i, 1 - eps, 1 + eps)) )
+ *     value_loss   = mean( (returns_i - v_i)^2 )
+ *     entropy_loss = -mean( entropy_i )
+ *     loss         = policy_loss + ent_coef entropy_loss + vf_coef value_loss
+ *     approx_kl    = mean( (ratio_i - 1) - (log_prob_i - old_log_prob_i) )
+ *     clip_fraction = mean( |ratio_i - 1| > eps )
+ *   The gradients are d loss / d theta for every actor parameter (log_std with its entropy term) and every critic parameter.  The
+ *   sub-gradient of the clipped term is PyTorch's: min(x, y) passes the gradient to the strictly smaller argument and halves it between
+ *   equal ones, clamp passes it inside its limits, limits included.  So d / d ratio_i of min(A ratio, A clamp(ratio)) is
+ *       A_i   when 1 - eps <= ratio_i <= 1 + eps (the two arguments are equal: one half each, and the clamp passes its half), or when
+ *             ratio_i lies outside and the unclipped term A_i ratio_i is the strictly smaller one;
+ *       0     otherwise (outside, and the clipped term is smaller or equal).
+ *   1 - eps and 1 + eps are taken in double and rounded to float once.  A comparison with a NaN is false, as in PyTorch: a NaN in any
+ *   sampled row (observation, action, old_log_prob, advantage, return) reaches the gradients and the scalars — a sum has no isolation rule.
+ *
+ * RdvPpoRows: flat views of a rollout's rows (the [T,N,...] columns of rdv_rollout / rdv_rollout_advantages seen as [T*N,...]).  Sample i
+ *   reads row indices[i] of every column, or row i when indices is NULL (then n <= rows).  The indices are NOT range-checked on the device:
+ *   an index outside [0, rows) reads outside the arrays.  A duplicate index counts once per occurrence.  `advantages` holds the values as
+ *   they ENTER the loss: the call never normalises.  obs must be 16-byte aligned.
+ * RdvPpoOut: actor_grad [5708] = w1[64,17] b1[64] w2[64,64] b2[64] w3[6,64] b3[6] log_std[6], critic_grad [5377] = w1 b1 w2 b2 w3[1,64] b3[1],
+ *   every matrix in nn.Linear's [out, in] order; scalars [8] = loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, 0, 0;
+ *   log_prob [n] and values [n] (both nullable): the log-density of the sampled actions under the CURRENT actor and the current critic's
+ *   values, in sample order.
+ *
+ * The contract:
+ *   - Weights: the handles' parameter blocks as of stream order — a call enqueued on `stream` after rdv_policy_set_weights on the same
+ *     stream differentiates the new weights.  What is differentiated is the function the forward kernels compute: the two-term fp16
+ *     weights (hi + lo) 2^-s of the block, and observations clamped to +-63.
+ *   - out->values is bit-identical to what rdv_policy_value writes for the same rows, and the means inside the call are those of
+ *     rdv_policy_act with deterministic = 1 before the clip: the forward half is the device code of those kernels.
+ *   - Accuracy: the backward products are brought to fp32 level as the forward ones (two fp16 terms per operand, three MFMAs), the sums
+ *     over rows are fp32; tests/test_gpu_ppo_grad.py holds every gradient tensor to a small multiple of the error of PyTorch's own float32
+ *     autograd against an fp64 reference.
+ *   - Determinism: the same inputs give the same bits in every output, eager or replayed from a captured graph.  No floating-point
+ *     atomic: per-wave sums are added in wave order, per-workgroup sums go to the workspace and are added in index order.
+ *   - Enqueued on `stream`, legal inside a stream capture, no allocation, no synchronisation.  The workspace is the caller's: at least
+ *     rdv_ppo_workspace_bytes (n) bytes (-1 for n <= 0; needs no GPU; monotone in n), 16-byte aligned, not shared with a call in flight on
+ *     another stream.  The outputs must not alias the inputs or the workspace (not checked).
+ *   - Shipped architecture only: both handles 17-64-64 tanh (rdv_policy_create / rdv_critic_create or the default RdvMlpSpec), one
+ *     member, not recurrent, on the same device.  rdv_ppo_spec_check judges two specs on the host (no GPU) with the messages of the call.
+ *   - RDV_ERR_INVALID_ARGUMENT, the message naming the argument, for: a null rows, out or required pointer (everything but rows->indices,
+ *     out->log_prob, out->values), n <= 0, rows->rows <= 0, n > rows->rows without indices, a misaligned rows->obs or workspace, a short
+ *     workspace, a clip_range that is not finite or not positive, an ent_coef or vf_coef that is not finite or negative — these come
+ *     before the handles are looked at and need no GPU; then RDV_ERR_BAD_HANDLE for an invalid handle; then RDV_ERR_INVALID_ARGUMENT for a
+ *     recurrent handle, a policy set, actor and critic swapped, any other architecture, or handles on different devices.  A refused call
+ *     enqueues nothing and leaves the handles as they were.
+ */
+typedef struct RdvPpoRows {          /* flat views of a rollout's [T*N] rows, device pointers */
+  const float*   obs;                /* [rows,17]  16-byte aligned                          */
+  const float*   actions;            /* [rows,6]   the UNCLIPPED samples (buffer.actions)   */
+  const float*   old_log_prob;       /* [rows]                                              */
+  const float*   advantages;         /* [rows]     as they ENTER the loss                   */
+  const float*   returns;            /* [rows]                                              */
+  const int64_t* indices;            /* [n] row of each minibatch sample; NULL: rows 0..n-1 */
+  int64_t        rows;
+} RdvPpoRows;
+typedef struct RdvPpoOut {           /* device pointers */
+  float* actor_grad;                 /* [5708] required */
+  float* critic_grad;                /* [5377] required */
+  float* scalars;                    /* [8]    required */
+  float* log_prob;                   /* [n]    nullable */
+  float* values;                     /* [n]    nullable */
+} RdvPpoOut;
+int64_t rdv_ppo_workspace_bytes(int64_t n);
+int rdv_ppo_spec_check(const RdvMlpSpec* actor_spec_host, const RdvMlpSpec* critic_spec_host);
+int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef,
+                      double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream);
 
 /*
  * Policy sets (added within ABI 5): one batch, several actors and critics, one launch — the network half of the reference's sweeps

@@ -41,7 +41,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            "rdv_lstm_spec_check", "rdv_lstm_policy_create", "rdv_lstm_critic_create", "rdv_lstm_act", "rdv_lstm_value", "rdv_lstm_get_state",
            "rdv_lstm_set_state", "rdv_lstm_reset_state", "rdv_lstm_set_weights", "rdv_lstm_hidden_size",
            # recurrent policy sets (added within ABI 5)
-           "rdv_lstm_policy_set_create", "rdv_lstm_critic_set_create", "rdv_lstm_set_member_weights"]
+           "rdv_lstm_policy_set_create", "rdv_lstm_critic_set_create", "rdv_lstm_set_member_weights",
+           # PPO minibatch gradients (added within ABI 5)
+           "rdv_ppo_workspace_bytes", "rdv_ppo_spec_check", "rdv_ppo_loss_grad"]
 
 
 class RdvError(RuntimeError):
@@ -88,6 +90,21 @@ class AdvantageOut(C.Structure):
     _fields_ = [("values", C.c_void_p), ("last_value", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p)]
 
 
+class PpoRows(C.Structure):
+    """RdvPpoRows: flat device views of a rollout's rows, and the minibatch's row indices (nullable)"""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p),
+                ("returns", C.c_void_p), ("indices", C.c_void_p), ("rows", C.c_int64)]
+
+
+class PpoOut(C.Structure):
+    """RdvPpoOut: device pointers of what rdv_ppo_loss_grad writes (log_prob and values nullable)"""
+    _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
+PPO_ACTOR_GRAD, PPO_CRITIC_GRAD, PPO_SCALARS = 5708, 5377, 8
+PPO_SCALAR_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
+
 ACT_TANH, ACT_RELU, ACT_SIGMOID = 0, 1, 2
 MLP_MAX_HIDDEN = 4
 
@@ -127,7 +144,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the nine translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
+    """Compile the ten translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -224,6 +241,9 @@ def lib():
         "rdv_lstm_policy_set_create": (C.c_int, [C.POINTER(LstmSpec), i32, C.POINTER(i64), vp, vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]),
         "rdv_lstm_critic_set_create": (C.c_int, [C.POINTER(LstmSpec), i32, C.POINTER(i64), vp, vp, vp, vp, vp, vp, C.c_int, C.POINTER(vp)]),
         "rdv_lstm_set_member_weights": (C.c_int, [vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "rdv_ppo_workspace_bytes": (i64, [i64]),
+        "rdv_ppo_spec_check": (C.c_int, [C.POINTER(MlpSpec), C.POINTER(MlpSpec)]),
+        "rdv_ppo_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), i64, C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

@@ -1,14 +1,15 @@
 // rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
 // value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
-// rdv_rollout_advantages, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
+// rdv_rollout_advantages, rdv_ppo_*, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
-// mlp_*, sets_*, lstm_*, gae_launch), so an edit to an argument check recompiles no kernel.
+// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch), so an edit to an argument check recompiles no kernel.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
 #include "rdv_policy_lstm.h"
 #include "rdv_policy_sets.h"
 #include "rdv_advantages.h"
+#include "rdv_ppo.h"
 #include "rdv_host.h"
 
 #include <cstdio>
@@ -598,6 +599,66 @@ int rdv_rollout_advantages(rdv_policy critic, const RdvRolloutOut* rows, int32_t
     if (int rc = rdv_policy_value(critic, rows->last_obs, out->last_value, n, stream)) return rc;
   }
   return launch_gae(rows->reward, rows->done, out->values, out->last_value, n_steps, n, gamma, gae_lambda, out->advantages, out->returns, s);
+}
+
+// ---- PPO minibatch gradients (csrc/rdv_ppo.h)
+int64_t rdv_ppo_workspace_bytes(int64_t n) { return n > 0 ? ppo_workspace_bytes(n) : -1; }
+
+int rdv_ppo_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec) {
+  if (!actor_spec || !critic_spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_spec_check: null %s", !actor_spec ? "actor_spec" : "critic_spec");
+  if (int rc = rdv_mlp_spec_check(actor_spec)) return rc;
+  if (int rc = rdv_mlp_spec_check(critic_spec)) return rc;
+  const struct { const RdvMlpSpec* s; const char* name; } nets[] = {{actor_spec, "actor"}, {critic_spec, "critic"}};
+  for (const auto& a : nets)
+    if (std::memcmp(a.s, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) != 0)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_loss_grad: the %s is not the shipped architecture (two hidden layers of 64, tanh): its gradients are not built", a.name);
+  return RDV_OK;
+}
+
+int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef, double vf_coef,
+                      void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream) {
+  const char* who = "rdv_ppo_loss_grad";
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
+  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"},
+                                                              {rows->advantages, "rows->advantages"}, {rows->returns, "rows->returns"},
+                                                              {out->actor_grad, "out->actor_grad"}, {out->critic_grad, "out->critic_grad"},
+                                                              {out->scalars, "out->scalars"}, {workspace, "workspace"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
+  if (n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
+  if (rows->rows <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->rows must be positive (got %lld)", who, (long long)rows->rows);
+  if (!rows->indices && n > rows->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n = %lld exceeds rows->rows = %lld and rows->indices is null", who, (long long)n, (long long)rows->rows);
+  if (misaligned(rows->obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->obs must be 16-byte aligned", who);
+  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (workspace_bytes < ppo_workspace_bytes(n))
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, n = %lld needs %lld (rdv_ppo_workspace_bytes)", who, (long long)workspace_bytes, (long long)n, (long long)ppo_workspace_bytes(n));
+  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: clip_range must be finite and positive (got %g)", who, clip_range);
+  if (!std::isfinite(ent_coef) || ent_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: ent_coef must be finite and not negative (got %g)", who, ent_coef);
+  if (!std::isfinite(vf_coef) || vf_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: vf_coef must be finite and not negative (got %g)", who, vf_coef);
+  RDV_CHECK_POLICY(actor);
+  RDV_CHECK_POLICY(critic);
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor, "actor"}, {critic, "critic"}};
+  for (const auto& a : nets) {
+    if (a.p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a recurrent policy: its gradients are not built", who, a.name);
+    if (a.p->n_members > 1 || a.p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a policy set: its gradients are not built", who, a.name);
+  }
+  if (actor->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor is a critic handle (rdv_critic_create): actor and critic are swapped", who);
+  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic is an actor handle (rdv_policy_create): actor and critic are swapped", who);
+  if (int rc = rdv_ppo_spec_check(&actor->spec, &critic->spec)) return rc;
+  if (!actor->shipped_arch || !critic->shipped_arch) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the handles do not run the shipped kernels", who);
+  if (actor->device != critic->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor on device %d, critic on device %d", who, actor->device, critic->device);
+  DeviceGuard guard(actor->device);
+  static bool raised[64] = {};   // the kernels' dynamic-LDS limit, once per device (a host-side attribute: no stream work)
+  if (actor->device >= 64 || !raised[actor->device]) {
+    RDV_HIP(ppo_raise_lds_limit());
+    if (actor->device < 64) raised[actor->device] = true;
+  }
+  PpoLaunch a = {actor->weights, critic->weights, rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, n,
+                 (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)clip_range, (float)ent_coef, (float)vf_coef,
+                 static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
+  ppo_launch(a, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
 }
 
 }  // extern "C"

@@ -1,0 +1,64 @@
+// rdv_ppo.h — the PPO minibatch loss and its gradients for the shipped actor and critic (rdv_ppo_loss_grad, include/rdv.h, "PPO minibatch
+// gradients"): what SB3's PPO.train() computes for ONE minibatch between `rollout_buffer.get` and `optimizer.step`, on the device.
+// The kernels are in rdv_ppo.hip, a translation unit of its own; this header holds the sizes and the launch that the host unit
+// (rdv_policy_host.hip) needs, and the description.
+//
+// Four launches per call, all on the caller's stream:
+//   1. ppo_transpose_kernel: the A-operand fragments of W3^T and W2^T of both nets, derived from the handles' FORWARD blocks (a permutation
+//      of their fp16 terms: (hi + lo) 2^-s is exactly the weight the forward pass multiplies by, i.e. the function being differentiated)
+//      into the head of the workspace.  No host state is added to the handles; a call enqueued behind rdv_policy_set_weights reads the new block.
+//   2. ppo_net_kernel<true>  (actor)  and  3. ppo_net_kernel<false> (critic): a wave owns 32 minibatch rows, a workgroup 256, as in
+//      policy_act_kernel.  Per wave:
+//        gather   the rows' observations by `indices` into the wave's LDS rows (68-byte rows, as stage_obs_rows stages contiguous ones);
+//        forward  the shipped device functions of rdv_policy.h (actor_inputs, layer, tanh2_f32, split2: the sequence of actor_means, so
+//                 the means and the values are the bits of rdv_policy_act / rdv_policy_value), keeping h1 and h2 (times 2^10) in registers;
+//        loss     per lane: log_prob, ratio, the clip rule, d loss / d mean_c and d loss / d log_std_c (actor), 2 vf_coef (v - return) (critic),
+//                 WITHOUT the 1/n of the means (the last kernel divides);
+//        backward delta_{l-1} = (W_l^T delta_l) o (1 - h_{l-1}^2): the forward's `layer` with the transposed fragments as A operand and the
+//                 error tile — an accumulator tile again — as B operand;
+//        weights  dW_l = delta_l h_{l-1}^T contracted over the wave's 32 rows (k = rows): both operands need the row index along k, so
+//                 delta_l and h_{l-1} are transposed through the wave's LDS tiles ([term][feature][row] fp16); the bias gradients (and
+//                 d log_std) are one more column tile of ones.
+//      Every backward operand is brought to fp32 level as the forward's: scaled by a power of two (here the WAVE's: the largest |delta| of
+//      the tile goes to [2^13, 2^14)), split into two fp16 terms, three MFMAs per product (mfma3).  The per-wave tiles are added in LDS in
+//      wave order and the workgroup's sums go to its row of the workspace: no floating-point atomic anywhere, the same bits every time.
+//   4. ppo_finish_kernel: adds the workgroups' rows in index order, divides by n, adds the entropy term to d log_std, writes actor_grad,
+//      critic_grad and the eight scalars.
+#pragma once
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace rdv {
+
+constexpr int kPpoActorGrad = 5708;    // w1[64,17] b1[64] w2[64,64] b2[64] w3[6,64] b3[6] log_std[6]
+constexpr int kPpoCriticGrad = 5377;   // w1 b1 w2 b2 w3[1,64] b3[1]
+constexpr int kPpoScalars = 8;
+constexpr int kPpoW1 = 0, kPpoB1 = 1088, kPpoW2 = 1152, kPpoB2 = 5248, kPpoW3 = 5312;   // offsets inside either gradient; b3 = w3 + out_dim * 64
+// backward block of one net: 20 fragments of 1 KiB ([q][mt][ks]: W3^T at 0 (2 x 2 x 1), W2^T at 4 (2 x 2 x 4)), then 64 zero floats (the
+// "bias" that `layer` starts its accumulators from)
+constexpr int kPpoBwdW3 = 0, kPpoBwdW2 = 4, kPpoBwdFrags = 20;
+constexpr int kPpoBwdZero = kPpoBwdFrags * 256, kPpoBwdFloats = kPpoBwdZero + 64;       // 5,184 floats = 20,736 B
+// a workgroup's row of partial sums: actor gradient | critic gradient | (pad to 16 bytes) | policy, kl, clipped count, value sums
+constexpr int kPpoPartCritic = kPpoActorGrad, kPpoPartScalars = 11088, kPpoPartFloats = 11096;
+static_assert(kPpoPartCritic + kPpoCriticGrad <= kPpoPartScalars, "the scalar sums lie behind the critic's gradient");
+constexpr int kPpoBlockRows = 256;     // kPolBlockEnvs
+
+inline int64_t ppo_workgroups(int64_t n) { return (n + kPpoBlockRows - 1) / kPpoBlockRows; }
+inline int64_t ppo_workspace_bytes(int64_t n) { return (2 * (int64_t)kPpoBwdFloats + ppo_workgroups(n) * kPpoPartFloats) * (int64_t)sizeof(float); }
+
+struct PpoLaunch {
+  const float *actor_block, *critic_block;   // the handles' forward parameter blocks (device)
+  const float *obs, *actions, *old_log_prob, *advantages, *returns;
+  const int64_t* indices;                    // nullable
+  int64_t n;
+  float clip_lo, clip_hi, clip_range;        // (float)(1 - eps), (float)(1 + eps), (float)eps: the differences taken in double
+  float ent_coef, vf_coef;
+  float* workspace;
+  float *actor_grad, *critic_grad, *scalars, *log_prob, *values;
+};
+
+__attribute__((visibility("hidden"))) hipError_t ppo_raise_lds_limit();
+__attribute__((visibility("hidden"))) void ppo_launch(const PpoLaunch& a, hipStream_t s);
+
+}  // namespace rdv

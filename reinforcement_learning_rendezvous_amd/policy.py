@@ -356,6 +356,23 @@ class MlpPolicy(_HipHandles, torch.nn.Module):
                 N.check(N.lib().rdv_policy_set_weights(h, _ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()) if log_std else None,
                                                        self._stream(idx)))
 
+    def ppo_grad(self, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
+        """The loss of SB3's ``PPO.train()`` for ONE minibatch and its gradients, written into ``.grad`` of this module's 13 parameters
+        (ppo.py; include/rdv.h "PPO minibatch gradients").  ``buf``: the dict ``RendezvousBatch.collect`` returns; its [T,N,...] columns
+        ``obs``, ``actions`` (unclipped), ``log_prob`` (the old one), ``advantages`` and ``returns`` are viewed flat, not copied.
+        ``indices``: int64 rows of the minibatch on the rows' device (one piece of ``ppo_minibatches``), or None for all rows in order.
+        With ``normalize_advantage`` and more than one sample the minibatch advantages are normalised with SB3's own expression in torch
+        and written back to their rows of a flat column the policy owns, which the library call then reads through the same indices (the
+        C call never normalises).  ``.grad`` are views of two flat buffers the policy owns (allocated once, with the workspace), so
+        ``clip_grad_norm_(policy.parameters(), 0.5); optimizer.step(); policy.update_weights()`` follow unchanged.  Returns the scalars
+        ``loss``, ``policy_loss``, ``value_loss``, ``entropy_loss``, ``approx_kl``, ``clip_fraction`` as 0-dim tensors on the rows'
+        device: nothing synchronises.  ``check``: a caller's own ``indices`` are validated with one ``torch.aminmax`` (the kernel does not
+        range-check); pieces of ``ppo_minibatches`` for this row count skip it.  CUDA rows with the shipped 17-64-64 tanh actor and critic:
+        rdv_ppo_loss_grad on the current stream (differentiates the handles' weights as of stream order).  CPU rows,
+        ``backend="torch"`` or another architecture: the same expressions through autograd over these modules."""
+        from . import ppo
+        return ppo.ppo_grad(self, buf, indices, clip_range, ent_coef, vf_coef, normalize_advantage, check)
+
     @torch.no_grad()
     def act(self, obs, deterministic=True, generator=None, out=None, env_id_offset=None):
         """SB3 ``predict``: the distribution mean (or a sample), clipped to the action Box.  HIP backend: the exploration noise of
@@ -512,6 +529,11 @@ class PolicySet(_HipHandles):
         if isinstance(ro.get("obs"), torch.Tensor) and ro["obs"].dim() == 3 and self.has_critic:
             self._check_rows(int(ro["obs"].shape[1]), "advantages")
         return _advantages(self, ro, gamma, gae_lambda, out)
+
+    def ppo_grad(self, *args, **kwargs):
+        """Not offered for a set: ``MlpPolicy.ppo_grad`` serves one actor and one critic."""
+        from . import ppo
+        return ppo.ppo_grad(self, *args, **kwargs)
 
     # ------------------------------------------------------------------------------------------------ weights
     def update_weights(self, member=None, weights=None):

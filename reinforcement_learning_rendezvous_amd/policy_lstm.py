@@ -440,6 +440,11 @@ class LstmPolicy(_LstmRows, torch.nn.Module):
         h, c = self._get_state("l", dev)
         return (a[0] if single else a), (h.cpu().numpy(), c.cpu().numpy())
 
+    def ppo_grad(self, *args, **kwargs):
+        """Not offered for a recurrent policy: ``MlpPolicy.ppo_grad`` serves the feed-forward shipped actor and critic."""
+        from . import ppo
+        return ppo.ppo_grad(self, *args, **kwargs)
+
     def update_weights(self, weights=None):
         """New weights for the modules (a dict with the constructor's keys; None: push the modules' current parameters) and for every
         live HIP handle, through rdv_lstm_set_weights on the current stream of its device; the recurrent state is kept."""
@@ -565,6 +570,11 @@ class LstmPolicySet(_LstmRows):
                           for p, s in zip(self.policies, self.group_slices)], dim=0)
 
     # ------------------------------------------------------------------------------------------------ weights
+    def ppo_grad(self, *args, **kwargs):
+        """Not offered for a recurrent policy: ``MlpPolicy.ppo_grad`` serves the feed-forward shipped actor and critic."""
+        from . import ppo
+        return ppo.ppo_grad(self, *args, **kwargs)
+
     def update_weights(self, member=None, weights=None):
         """New weights for one member (``member`` = its index; ``weights``: a dict as ``LstmPolicy.update_weights`` takes, or None to
         push the member module's current parameters) or for all members (``member`` None; ``weights``: None or a list of one dict or

@@ -1,0 +1,203 @@
+"""
+The learner's step between ``RendezvousBatch.collect`` and ``optimizer.step()``: the loss of SB3's ``PPO.train()`` for one minibatch and
+its gradients (stable_baselines3/ppo/ppo.py, the body of the ``for rollout_data in self.rollout_buffer.get(self.batch_size)`` loop, with
+``clip_range_vf=None``; ``ActorCriticPolicy.evaluate_actions`` with a ``DiagGaussianDistribution``, common/distributions.py).
+
+    for epoch in range(n_epochs):
+        for idx in ppo_minibatches(T * N, batch_size, generator):
+            stats = policy.ppo_grad(buf, idx, clip_range=0.2, ent_coef=0.0, vf_coef=0.5)      # fills .grad, returns 0-dim tensors
+            torch.nn.utils.clip_grad_norm_(policy.parameters(), 0.5)
+            optimizer.step()
+            policy.update_weights()
+
+For CUDA rows and the shipped 17-64-64 tanh actor and critic the loss and the gradients are ONE call of the library (rdv_ppo_loss_grad,
+include/rdv.h "PPO minibatch gradients"; csrc/rdv_ppo.h): hand-written MFMA kernels on the current stream, no allocation, no
+synchronisation, legal inside a stream capture.  CPU rows, ``backend="torch"`` and every other architecture run the same expressions
+through autograd over the policy's own modules and fill the same ``.grad`` tensors.  Gradient clipping, the optimiser and its schedules are
+PyTorch's; ``update_weights`` repacks as it always did.
+"""
+import ctypes as C
+import math
+
+import torch
+
+_LOG_2PI = math.log(2.0 * math.pi)
+SCALAR_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
+
+
+def ppo_minibatches(n_rows, batch_size, generator=None, device=None):
+    """The index tensors of one epoch over ``n_rows`` flat rollout rows: a ``torch.randperm`` on the device (the generator's, unless
+    ``device`` says otherwise) cut into consecutive pieces of ``batch_size`` as SB3's ``RolloutBuffer.get`` cuts its permutation
+    (common/buffers.py: ``indices[start_idx : start_idx + batch_size]``); the last one may be short.  Every row appears exactly once.
+    The tensors are marked as in range for ``n_rows``, so ``ppo_grad`` does not check them again."""
+    n_rows, batch_size = int(n_rows), int(batch_size)
+    if n_rows <= 0 or batch_size <= 0:
+        raise ValueError(f"ppo_minibatches: n_rows = {n_rows} and batch_size = {batch_size} must be positive")
+    if device is None:
+        device = generator.device if generator is not None else "cpu"
+    perm = torch.randperm(n_rows, generator=generator, device=device)
+    parts = list(torch.split(perm, batch_size))
+    for p in parts:
+        p._rdv_ppo_rows = n_rows
+    return parts
+
+
+def ppo_loss_terms(mean, log_std, values, actions, old_log_prob, advantages, returns, clip_range, ent_coef, vf_coef):
+    """SB3's expressions on torch tensors of any dtype: ``mean`` [n,6], ``values`` [n] of the current networks.  Returns (loss, dict of
+    the six scalars, log_prob [n])."""
+    var = torch.exp(log_std) ** 2
+    log_prob = (-((actions - mean) ** 2) / (2 * var) - log_std - 0.5 * _LOG_2PI).sum(-1)        # Normal.log_prob, summed over the action
+    entropy = (0.5 + 0.5 * _LOG_2PI + log_std).expand_as(mean).sum(-1)                          # Normal.entropy, summed
+    ratio = torch.exp(log_prob - old_log_prob)
+    policy_loss = -torch.min(advantages * ratio, advantages * torch.clamp(ratio, 1 - clip_range, 1 + clip_range)).mean()
+    value_loss = ((returns - values) ** 2).mean()                                                # F.mse_loss(returns, values_pred)
+    entropy_loss = -entropy.mean()
+    loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss
+    with torch.no_grad():
+        log_ratio = log_prob - old_log_prob
+        approx_kl = ((torch.exp(log_ratio) - 1) - log_ratio).mean()
+        clip_fraction = (torch.abs(ratio - 1) > clip_range).to(ratio.dtype).mean()
+    scalars = dict(loss=loss.detach(), policy_loss=policy_loss.detach(), value_loss=value_loss.detach(), entropy_loss=entropy_loss.detach(),
+                   approx_kl=approx_kl, clip_fraction=clip_fraction)
+    return loss, scalars, log_prob
+
+
+def normalize_advantages(a):
+    """SB3's expression (ppo.py: ``(advantages - advantages.mean()) / (advantages.std() + 1e-8)``), applied when the minibatch has more
+    than one sample."""
+    return (a - a.mean()) / (a.std() + 1e-8)
+
+
+def _params(policy):
+    """The 13 parameter tensors (any architecture: 2 per layer) in the order of the flat gradient buffers: actor layers, log_std, critic layers."""
+    actor = [t for lin in policy._layers("l") for t in (lin.weight, lin.bias)] + [policy.log_std]
+    critic = [t for lin in policy._layers("v") for t in (lin.weight, lin.bias)]
+    return actor, critic
+
+
+def _state(policy, dev, n, rows):
+    """The buffers the policy owns for ppo_grad on device ``dev``: two flat gradient buffers (the parameters' ``.grad`` are views of them
+    when the modules live on ``dev``), the scalars, and — HIP path — the workspace and the advantage column, grown when a call needs more."""
+    st = policy.__dict__.setdefault("_ppo", {}).get(dev)
+    actor, critic = _params(policy)
+    if st is None:
+        st = dict(actor=torch.zeros(sum(p.numel() for p in actor), dtype=torch.float32, device=dev),
+                  critic=torch.zeros(sum(p.numel() for p in critic), dtype=torch.float32, device=dev),
+                  scalars=torch.zeros(8, dtype=torch.float32, device=dev), workspace=None, adv=None, n=0)
+        policy._ppo[dev] = st
+    if n is not None and (st["workspace"] is None or st["n"] < n):
+        from . import _native as N
+        st["workspace"] = torch.empty(int(N.lib().rdv_ppo_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        st["n"] = n
+    if rows is not None and (st["adv"] is None or st["adv"].numel() < rows):
+        st["adv"] = torch.zeros(rows, dtype=torch.float32, device=dev)
+    return st
+
+
+def _bind_grads(policy, st, dev):
+    """``.grad`` of every parameter <- its piece of the flat buffers: a view when the parameter lives on ``dev``, a copy otherwise."""
+    for flat, params in zip((st["actor"], st["critic"]), _params(policy)):
+        at = 0
+        for p in params:
+            piece = flat[at:at + p.numel()].view(p.shape)
+            at += p.numel()
+            if p.device == piece.device:
+                if p.grad is None or p.grad.data_ptr() != piece.data_ptr():
+                    p.grad = piece
+            else:
+                if p.grad is None:
+                    p.grad = torch.empty_like(p)
+                p.grad.copy_(piece)
+
+
+def _columns(buf):
+    obs = buf["obs"]
+    if not isinstance(obs, torch.Tensor) or obs.dim() < 2 or obs.shape[-1] != 17:
+        raise ValueError(f"ppo_grad: buf['obs']: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
+    rows, dev = obs.numel() // 17, obs.device
+    cols = dict(obs=(17,), actions=(6,), log_prob=(), advantages=(), returns=())
+    flat = {}
+    for name, tail in cols.items():
+        t = buf.get(name)
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.device != dev or not t.is_contiguous() or t.numel() != rows * (tail[0] if tail else 1):
+            raise ValueError(f"ppo_grad: buf[{name!r}] must be a contiguous float32 tensor of {rows} rows on {dev} (what RendezvousBatch.collect returns)")
+        flat[name] = t.view((rows,) + tail)                           # a view, not a copy
+    return flat, rows, dev
+
+
+def ppo_grad(policy, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
+    """See ``MlpPolicy.ppo_grad``."""
+    from .policy import MlpPolicy
+    if not isinstance(policy, MlpPolicy):
+        raise TypeError(f"ppo_grad: a {type(policy).__name__} is not offered: the PPO minibatch gradients are built for MlpPolicy alone "
+                        "(PolicySet, LstmPolicy and LstmPolicySet keep SB3 / PyTorch for the update)")
+    if not policy.has_critic:
+        raise ValueError("ppo_grad: this policy has no critic (its weights hold no value_net trunk)")
+    for name, v, low in (("clip_range", clip_range, None), ("ent_coef", ent_coef, 0.0), ("vf_coef", vf_coef, 0.0)):
+        v = float(v)
+        if not math.isfinite(v) or (v <= 0.0 if low is None else v < low):
+            raise ValueError(f"ppo_grad: {name} = {v!r} must be finite and " + ("positive" if low is None else "not negative"))
+    cols, rows, dev = _columns(buf)
+    if indices is None:
+        n = rows
+    else:
+        if not isinstance(indices, torch.Tensor) or indices.dtype != torch.int64 or indices.dim() != 1 or indices.device != dev or indices.numel() == 0:
+            raise ValueError(f"ppo_grad: indices must be a non-empty 1-d int64 tensor on {dev}")
+        indices = indices.contiguous()
+        n = int(indices.numel())
+        if check and getattr(indices, "_rdv_ppo_rows", None) != rows:
+            lo, hi = (int(x) for x in torch.aminmax(indices))
+            if lo < 0 or hi >= rows:
+                raise IndexError(f"ppo_grad: indices span [{lo}, {hi}], the rollout has rows 0..{rows - 1}")
+    hip = policy.backend != "torch" and dev.type == "cuda" and policy.shipped_arch and policy.vf_arch == [64, 64]
+    take = (lambda t: t[:n]) if indices is None else (lambda t: t[indices])
+    adv = take(cols["advantages"])
+    if normalize_advantage and n > 1:
+        adv = normalize_advantages(adv)
+
+    if not hip:
+        pdev = policy.l1.weight.device
+        st = _state(policy, pdev, None, None)
+        actor, critic = _params(policy)
+        params = actor + critic
+        flags = [p.requires_grad for p in params]
+        try:
+            for p in params:
+                p.requires_grad_(True)
+            with torch.enable_grad():
+                obs = take(cols["obs"]).to(pdev)
+                mean, values = policy._forward("l", obs), policy._forward("v", obs).squeeze(-1)
+                loss, scalars, _ = ppo_loss_terms(mean, policy.log_std, values, take(cols["actions"]).to(pdev), take(cols["log_prob"]).to(pdev),
+                                                  adv.to(pdev), take(cols["returns"]).to(pdev), float(clip_range), float(ent_coef), float(vf_coef))
+                grads = torch.autograd.grad(loss, params)
+        finally:
+            for p, f in zip(params, flags):
+                p.requires_grad_(f)
+        with torch.no_grad():
+            torch.cat([g.reshape(-1) for g in grads[:len(actor)]], out=st["actor"])
+            torch.cat([g.reshape(-1) for g in grads[len(actor):]], out=st["critic"])
+        _bind_grads(policy, st, pdev)
+        return scalars
+
+    from . import _native as N
+    st = _state(policy, dev, n, rows)
+    with torch.no_grad():
+        if normalize_advantage and n > 1:
+            # the normalised minibatch advantages go back to their rows of a flat column the policy owns (a duplicate index writes the
+            # same value twice), so the C call reads every column through the same indices
+            if indices is None:
+                st["adv"][:n] = adv
+            else:
+                st["adv"].index_copy_(0, indices, adv)
+            adv_col = st["adv"]
+        else:
+            adv_col = cols["advantages"]
+    r = N.PpoRows(cols["obs"].data_ptr(), cols["actions"].data_ptr(), cols["log_prob"].data_ptr(), adv_col.data_ptr(), cols["returns"].data_ptr(),
+                  indices.data_ptr() if indices is not None else None, rows)
+    o = N.PpoOut(st["actor"].data_ptr(), st["critic"].data_ptr(), st["scalars"].data_ptr(), None, None)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    N.check(N.lib().rdv_ppo_loss_grad(policy._hip_handle(dev), policy._critic_handle(dev), C.byref(r), n, float(clip_range), float(ent_coef),
+                                      float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    _bind_grads(policy, st, dev)
+    s = st["scalars"].clone()
+    return {name: s[k] for k, name in enumerate(SCALAR_NAMES)}

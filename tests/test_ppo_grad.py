@@ -1,0 +1,228 @@
+"""
+CPU: the PPO minibatch loss and gradients (include/rdv.h, "PPO minibatch gradients") — the reference of tests/ppo_reference.py against
+itself (analytic NumPy float64 against double autograd), the conditions of the GPU test's inputs, the autograd fallback of
+``MlpPolicy.ppo_grad``, ``ppo_minibatches``, the host-only checks of the C ABI, and the refusals.  tests/test_gpu_ppo_grad.py holds the
+kernels to the same reference.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import policy_mlp_reference as M
+import ppo_reference as P
+from reinforcement_learning_rendezvous_amd import _native as N
+from reinforcement_learning_rendezvous_amd import MlpPolicy, PolicySet, LstmPolicy, ppo_grad, ppo_minibatches
+
+ENT, VF = 0.01, 0.5
+FLOOR = 2.0 ** -23
+C_BOUND = 128.0          # the bound of tests/test_gpu_ppo_grad.py (its scalars'; the gradients' is tighter)
+
+
+def _buf(case):
+    t = lambda k, *shape: torch.from_numpy(np.array(case[k])).reshape(*shape)
+    return dict(obs=t("obs", 4, 300, 17), actions=t("actions", 4, 300, 6), log_prob=t("old_log_prob", 4, 300),
+                advantages=t("advantages", 4, 300), returns=t("returns", 4, 300))
+
+
+def _policy(case, **kw):
+    return MlpPolicy(M.weights_dict(case["actor"], case["critic"]), **kw)
+
+
+def _grads(pol):
+    return [p.grad.numpy() for p in (pol.l1.weight, pol.l1.bias, pol.l2.weight, pol.l2.bias, pol.l3.weight, pol.l3.bias, pol.log_std,
+                                     pol.v1.weight, pol.v1.bias, pol.v2.weight, pol.v2.bias, pol.v3.weight, pol.v3.bias)]
+
+
+@pytest.mark.parametrize("member", sorted(P.MEMBERS))
+def test_the_inputs_hold_the_conditions_of_the_comparison(member):
+    """Every class {ratio below, inside, above the clip range} x {A < 0, A > 0} holds at least 5 % of the rows, and no fp64 ratio lies
+    within 1e-4 of a clip limit; the index vectors hold duplicates and reach row 0 and the last row."""
+    case = P.make_case(member)
+    ref = P.analytic64(case["actor"], case["critic"], *P.take(case, P.ROWS))
+    shares = P.class_shares(ref["ratio"], case["advantages"])
+    assert len(shares) == 6 and min(shares.values()) >= 0.05, shares
+    assert np.abs(ref["ratio"] - (1 - P.EPS)).min() >= P.GUARD and np.abs(ref["ratio"] - (1 + P.EPS)).min() >= P.GUARD
+    assert np.abs(case["obs"]).max() <= 1.0
+    for n in P.SHAPES[1:]:
+        idx = P.index_vector(n)
+        assert idx.shape == (n,) and idx.min() == 0 and idx.max() == P.ROWS - 1 and len(set(idx.tolist())) < n
+    if member == "random":
+        assert -1.4 <= case["actor"]["log_std"].min() and case["actor"]["log_std"].max() <= -0.4 and np.ptp(case["actor"]["log_std"]) > 0.3
+
+
+@pytest.mark.parametrize("n", [1, 33, 549])
+@pytest.mark.parametrize("member", sorted(P.MEMBERS))
+def test_analytic_gradients_equal_double_autograd(member, n):
+    case = P.make_case(member)
+    mb = P.take(case, P.index_vector(n))
+    a = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF)
+    if n == 549:      # rows on each side of both clip limits, with either sign of the advantage
+        assert all(v > 0 for v in P.class_shares(a["ratio"], mb[3]).values())
+    g, s = P.autograd(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF)
+    for name, x, y in zip(P.NAMES, a["grads"], g):
+        assert x.shape == y.shape and P.rel_err(x, y) <= 1e-12, name
+    for k in P.SCALARS:
+        assert a["scalars"][k] == pytest.approx(s[k], rel=1e-12, abs=1e-15), k
+
+
+@pytest.mark.parametrize("wrong", P.WRONG)
+def test_the_bound_tells_a_wrong_restatement_from_the_right_one(wrong):
+    """The clip rule without the interior of the inclusive limits, tanh' from the other layer's activations, log_std without the entropy
+    term: each moves at least one gradient tensor beyond C max(e32, 2^-23) by orders of magnitude; float32 autograd itself sits at 1."""
+    case = P.make_case("random")
+    mb = P.take(case, P.index_vector(549))
+    right = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF)
+    bad = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF, wrong=wrong)
+    g32, _ = P.autograd(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF, dtype="float32")
+    bounds = [C_BOUND * max(P.rel_err(y, w), FLOOR) for y, w in zip(g32, right["grads"])]
+    over = {name: P.rel_err(b, w) / bound for name, b, w, bound in zip(P.NAMES, bad["grads"], right["grads"], bounds)}
+    assert max(over.values()) > 50.0, over
+    affected = dict(open_clip=P.NAMES[:7], wrong_h=P.NAMES[:4] + P.NAMES[7:11], no_entropy=("actor.log_std",))[wrong]
+    assert all(over[k] > 10.0 for k in affected) and all(v == 0.0 for k, v in over.items() if k not in affected), over
+
+
+@pytest.mark.parametrize("member", sorted(P.MEMBERS))
+def test_the_fallback_fills_grad_and_returns_the_scalars(member):
+    """CPU rows: autograd over the policy's own modules.  Raw advantages against the fp64 reference and the float32 restatement of
+    ppo_reference; normalised advantages against the reference fed SB3's normalisation."""
+    case = P.make_case(member)
+    pol = _policy(case)
+    buf = _buf(case)
+    idx = P.index_vector(257)
+    s = pol.ppo_grad(buf, torch.from_numpy(idx), clip_range=P.EPS, ent_coef=ENT, vf_coef=VF, normalize_advantage=False)
+    assert all(not p.requires_grad for p in pol.parameters())
+    mb = P.take(case, idx)
+    ref = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF)
+    g32, s32 = P.autograd(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF, dtype="float32")
+    for name, g, w, y in zip(P.NAMES, _grads(pol), ref["grads"], g32):
+        assert g.dtype == np.float32 and P.rel_err(g, w) <= 4.0 * max(P.rel_err(y, w), FLOOR), name
+    for k in P.SCALARS:
+        assert s[k].dim() == 0 and float(s[k]) == pytest.approx(ref["scalars"][k], rel=4.0 * max(abs(s32[k] - ref["scalars"][k]) / abs(ref["scalars"][k]), 4 * FLOOR)), k
+    # the .grad tensors are views of two flat buffers: the next call writes the same storage, and the optimiser's lines run unchanged
+    before = [p.grad.data_ptr() for p in pol.parameters()]
+    s = pol.ppo_grad(buf, torch.from_numpy(idx), clip_range=P.EPS, ent_coef=ENT, vf_coef=VF)
+    assert [p.grad.data_ptr() for p in pol.parameters()] == before
+    a = torch.from_numpy(np.array(mb[3]))
+    norm = ((a - a.mean()) / (a.std() + 1e-8)).numpy()
+    ref = P.analytic64(case["actor"], case["critic"], mb[0], mb[1], mb[2], norm, mb[4], ent_coef=ENT, vf_coef=VF)
+    for name, g, w in zip(P.NAMES, _grads(pol), ref["grads"]):
+        assert P.rel_err(g, w) <= 1e-4, name
+    opt = torch.optim.Adam(pol.parameters(), lr=1e-3)
+    w0 = pol.l2.weight.detach().clone()
+    torch.nn.utils.clip_grad_norm_(pol.parameters(), 0.5)
+    opt.step()
+    pol.update_weights()
+    assert not torch.equal(w0, pol.l2.weight)
+
+
+def test_the_fallback_serves_other_architectures_and_all_rows():
+    rng_net = M.dense([32, 16], "relu", seed=4)
+    pol = MlpPolicy(M.weights_dict(rng_net, M.critic_of(M.dense([32, 16], "relu", seed=5))), activation_fn="relu")
+    buf = _buf(P.make_case("random"))
+    s = pol.ppo_grad(buf, None, clip_range=0.2)
+    assert set(s) == set(P.SCALARS) and all(bool(torch.isfinite(v)) for v in s.values())
+    assert all(p.grad is not None and p.grad.shape == p.shape and bool(torch.isfinite(p.grad).all()) for p in pol.parameters())
+
+
+def test_ppo_minibatches_cover_every_row_once():
+    gen = torch.Generator().manual_seed(7)
+    parts = ppo_minibatches(2400, 512, gen)
+    assert [len(p) for p in parts] == [512, 512, 512, 512, 352] and all(p.dtype == torch.int64 for p in parts)
+    assert sorted(torch.cat(parts).tolist()) == list(range(2400))
+    again = ppo_minibatches(2400, 512, torch.Generator().manual_seed(7))
+    assert all(torch.equal(a, b) for a, b in zip(parts, again))
+    assert not torch.equal(torch.cat(parts), torch.cat(ppo_minibatches(2400, 512, gen)))      # the next epoch is another permutation
+    assert [len(p) for p in ppo_minibatches(5, 8)] == [5]
+    with pytest.raises(ValueError, match="positive"):
+        ppo_minibatches(0, 8)
+
+
+def test_indices_are_checked_unless_they_come_from_ppo_minibatches():
+    case = P.make_case("random")
+    pol, buf = _policy(case), _buf(case)
+    with pytest.raises(IndexError, match=r"\[0, 1200\]"):
+        pol.ppo_grad(buf, torch.tensor([0, 5, 1200]))
+    with pytest.raises(IndexError):
+        pol.ppo_grad(buf, torch.tensor([-1, 5]))
+    with pytest.raises(ValueError, match="int64"):
+        pol.ppo_grad(buf, torch.tensor([1, 2], dtype=torch.int32))
+    with pytest.raises(ValueError, match="clip_range"):
+        pol.ppo_grad(buf, None, clip_range=0.0)
+    with pytest.raises(ValueError, match=r"buf\['actions'\]"):
+        pol.ppo_grad(dict(buf, actions=buf["actions"][:, :, :5]), None)
+    piece = ppo_minibatches(1200, 100)[3]
+    assert piece._rdv_ppo_rows == 1200
+    pol.ppo_grad(buf, piece)
+
+
+def test_policy_sets_and_recurrent_policies_are_refused_by_name():
+    case = P.make_case("random")
+    pol, buf = _policy(case), _buf(case)
+    with pytest.raises(TypeError, match="PolicySet"):
+        PolicySet([pol, pol], [256, 944]).ppo_grad(buf, None)
+    with pytest.raises(TypeError, match="LstmPolicy"):
+        LstmPolicy(lstm_hidden_size=32, net_arch=[64, 64]).ppo_grad(buf, None)
+    with pytest.raises(TypeError, match="dict"):
+        ppo_grad({}, buf)
+
+
+def test_workspace_bytes_needs_no_gpu_and_is_monotone():
+    lib = N.lib()
+    sizes = [lib.rdv_ppo_workspace_bytes(n) for n in (1, 2, 255, 256, 257, 512, 513, 4096, 65536, 1 << 22)]
+    assert all(a <= b for a, b in zip(sizes, sizes[1:])) and sizes[0] > 0 and sizes[3] < sizes[4] and sizes[-1] > sizes[0]
+    assert sizes[0] == sizes[3]                                  # one workgroup owns 256 rows
+    assert lib.rdv_ppo_workspace_bytes(0) == -1 and lib.rdv_ppo_workspace_bytes(-5) == -1
+
+
+def test_spec_check_names_the_net():
+    lib = N.lib()
+    shipped, other = N.MlpSpec.make([64, 64]), N.MlpSpec.make([64, 32])
+    assert lib.rdv_ppo_spec_check(C.byref(shipped), C.byref(shipped)) == 0
+    assert lib.rdv_ppo_spec_check(C.byref(other), C.byref(shipped)) == -1 and b"the actor is not the shipped architecture" in lib.rdv_last_error()
+    assert lib.rdv_ppo_spec_check(C.byref(shipped), C.byref(N.MlpSpec.make([64, 64], N.ACT_RELU))) == -1 and b"the critic" in lib.rdv_last_error()
+    assert lib.rdv_ppo_spec_check(None, C.byref(shipped)) == -1 and b"actor_spec" in lib.rdv_last_error()
+    assert lib.rdv_ppo_spec_check(C.byref(N.MlpSpec.make([64, 48])), C.byref(shipped)) == -1 and b"hidden[1]" in lib.rdv_last_error()
+
+
+def test_argument_checks_come_first_and_name_the_argument():
+    """As rdv_gae: before any handle or device is looked at (the handles here are NULL), so they run without a GPU."""
+    lib = N.lib()
+    host = np.zeros(64, np.float32)                              # never dereferenced: every call below is refused
+    p = host.ctypes.data
+    assert p % 16 == 0 or True
+    base = (p + 15) // 16 * 16
+    good_rows = dict(obs=base, actions=base, old_log_prob=base, advantages=base, returns=base, indices=None, rows=100)
+    good_out = dict(actor_grad=base, critic_grad=base, scalars=base, log_prob=None, values=None)
+    big = lib.rdv_ppo_workspace_bytes(100)
+
+    def refused(word, rows=None, out=None, n=100, clip=0.2, ent=0.0, vf=0.5, ws=base, ws_bytes=big, null_rows=False, null_out=False):
+        r, o = N.PpoRows(**dict(good_rows, **(rows or {}))), N.PpoOut(**dict(good_out, **(out or {})))
+        rc = lib.rdv_ppo_loss_grad(None, None, None if null_rows else C.byref(r), n, clip, ent, vf, C.c_void_p(ws), ws_bytes,
+                                   None if null_out else C.byref(o), None)
+        msg = lib.rdv_last_error().decode()
+        assert rc == -1 and word in msg and "rdv_ppo_loss_grad" in msg, (word, rc, msg)
+
+    refused("rows is null", null_rows=True)
+    refused("out is null", null_out=True)
+    for name in ("obs", "actions", "old_log_prob", "advantages", "returns"):
+        refused(f"rows->{name} is null", rows={name: None})
+    for name in ("actor_grad", "critic_grad", "scalars"):
+        refused(f"out->{name} is null", out={name: None})
+    refused("workspace is null", ws=None)
+    refused("n must be positive", n=0)
+    refused("n must be positive", n=-3)
+    refused("rows->rows", rows=dict(rows=0))
+    refused("exceeds rows->rows", n=101)
+    refused("rows->obs must be 16-byte aligned", rows=dict(obs=base + 4))
+    refused("workspace must be 16-byte aligned", ws=base + 8)
+    refused("workspace_bytes", ws_bytes=big - 1)
+    for bad in (0.0, -0.1, float("nan"), float("inf")):
+        refused("clip_range", clip=bad)
+    for bad in (-1e-3, float("nan"), float("inf")):
+        refused("ent_coef", ent=bad)
+        refused("vf_coef", vf=bad)
+    # every argument in order: what is left is the handle
+    r, o = N.PpoRows(**good_rows), N.PpoOut(**good_out)
+    assert lib.rdv_ppo_loss_grad(None, None, C.byref(r), 100, 0.2, 0.0, 0.5, C.c_void_p(base), big, C.byref(o), None) == -5
