@@ -708,6 +708,56 @@ int32_t rdv_policy_num_members(rdv_policy p);
 int64_t rdv_policy_num_rows(rdv_policy p);
 
 /*
+ * PPO minibatch gradients for policy sets (added within ABI 5: additive exports): the minibatches of all P members of an actor set and a
+ * critic set in ONE call of four launches — the update half of a sweep of P learners, as the set kernels are its rollout half.  A call
+ * of rdv_ppo_loss_grad is latency-bound (one workgroup per 256 samples on a 256-CU chip); P members' minibatches are P independent sets
+ * of workgroups, and here they share the launches.  The specification:
+ *
+ *     Every output of member g is bit for bit what rdv_ppo_loss_grad writes for stand-alone handles of member g's weights, given the
+ *     same `rows`, indices + off_g, n = counts_host[g] and the same coefficients       (off_g = counts_host[0] + .. + counts_host[g-1]).
+ *
+ * actor_set / critic_set: handles of rdv_policy_set_create / rdv_critic_set_create with the same number of members P
+ *   (rdv_policy_num_members), the default (shipped) spec, the same device.  A plain handle is a set of one member and is accepted.  The
+ *   set's rows and its 256-row ranges play no part: membership of a sample is given by the counts alone.
+ * counts_host [P], host: counts_host[g] >= 0 is member g's minibatch size; at least one is positive.  A member with count 0 takes no
+ *   part: nothing of its gradient, scalar, log_prob or value outputs is written.
+ * rows: as for rdv_ppo_loss_grad, but rows->indices is REQUIRED: a device array of off_P = sum of the counts entries, member g's samples
+ *   at indices[off_g .. off_g + counts_host[g]), each a flat row of the rollout's columns.  Not range-checked on the device; a duplicate
+ *   counts once per occurrence.  All members read the same columns (members of a set own different env columns of one rollout).
+ * RdvPpoSetOut: actor_grad [P,5708], critic_grad [P,5377], scalars [P,8] (row g: member g's, in the layout of RdvPpoOut); log_prob and
+ *   values [off_P] (both nullable), member g's at off_g.
+ * One clip_range / ent_coef / vf_coef serves all members.
+ *
+ * Everything else of the contract of rdv_ppo_loss_grad carries over: the weights are the members' blocks as of stream order (a call
+ * behind rdv_policy_set_member_weights on the same stream differentiates that member's new block, the other members are unaffected); no
+ * floating-point atomic; the same bits eager or replayed from a captured graph; enqueued on `stream` only — no allocation, no
+ * synchronisation, no copy, legal inside a stream capture.  The counts travel by value in the kernel arguments, which is why a call
+ * serves at most 64 members (kPpoSetMaxMembers of csrc/rdv_ppo.h: 64 x 3 x 8 bytes of the 4 KiB kernel-argument segment).  The workspace
+ * is the caller's: at least rdv_ppo_set_workspace_bytes (n_members, counts_host) bytes, 16-byte aligned, laid out member after member
+ * as [the two backward blocks | one row of partial sums per 256 samples].  rdv_ppo_set_workspace_bytes needs no GPU, returns -1 for
+ * n_members outside 1..64, null counts, a negative count or no positive one, and is monotone in every count.
+ *
+ * A refused call enqueues nothing and leaves both handles usable; the message names the argument.  RDV_ERR_INVALID_ARGUMENT, host-only
+ * and before the handles are judged, for: a null rows, out, counts_host or required pointer (rows->indices among them; out->log_prob and
+ * out->values are nullable), a negative count, no positive count, rows->rows <= 0, a misaligned rows->obs or workspace, a short
+ * workspace, a clip_range that is not finite or not positive, an ent_coef or vf_coef that is not finite or negative.  (The number of
+ * counts examined is actor_set's member count; with an invalid actor_set it is 1.)  Then RDV_ERR_BAD_HANDLE for an invalid handle.  Then
+ * RDV_ERR_INVALID_ARGUMENT for: a recurrent handle or recurrent set, actor and critic swapped, any other architecture, different member
+ * counts, more than 64 members, different devices.
+ */
+typedef struct RdvPpoSetOut {        /* device pointers */
+  float* actor_grad;                 /* [P,5708]        required */
+  float* critic_grad;                /* [P,5377]        required */
+  float* scalars;                    /* [P,8]           required */
+  float* log_prob;                   /* [sum of counts] nullable */
+  float* values;                     /* [sum of counts] nullable */
+} RdvPpoSetOut;
+int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_host);
+int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host,
+                          double clip_range, double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes,
+                          const RdvPpoSetOut* out, void* stream);
+
+/*
  * The recurrent policy (added within ABI 5: additive exports): what the reference's main_rnn.py trains and tune_policy.py:80, :140-148
  * and tune_algorithm.py:68 build — sb3-contrib RecurrentPPO("MlpLstmPolicy"), i.e. RecurrentActorCriticPolicy with ONE LSTM layer of
  * lstm_hidden_size H in front of the mlp_extractor trunk, and separate LSTMs for actor and critic (shared_lstm = False,

@@ -43,7 +43,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # recurrent policy sets (added within ABI 5)
            "rdv_lstm_policy_set_create", "rdv_lstm_critic_set_create", "rdv_lstm_set_member_weights",
            # PPO minibatch gradients (added within ABI 5)
-           "rdv_ppo_workspace_bytes", "rdv_ppo_spec_check", "rdv_ppo_loss_grad"]
+           "rdv_ppo_workspace_bytes", "rdv_ppo_spec_check", "rdv_ppo_loss_grad",
+           # PPO minibatch gradients for policy sets (added within ABI 5)
+           "rdv_ppo_set_workspace_bytes", "rdv_ppo_set_loss_grad"]
 
 
 class RdvError(RuntimeError):
@@ -98,6 +100,12 @@ class PpoRows(C.Structure):
 
 class PpoOut(C.Structure):
     """RdvPpoOut: device pointers of what rdv_ppo_loss_grad writes (log_prob and values nullable)"""
+    _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
+class PpoSetOut(C.Structure):
+    """RdvPpoSetOut: device pointers of what rdv_ppo_set_loss_grad writes: [P,5708], [P,5377], [P,8]; log_prob and values [sum of counts], nullable"""
     _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
                 ("values", C.c_void_p)]
 
@@ -244,6 +252,8 @@ def lib():
         "rdv_ppo_workspace_bytes": (i64, [i64]),
         "rdv_ppo_spec_check": (C.c_int, [C.POINTER(MlpSpec), C.POINTER(MlpSpec)]),
         "rdv_ppo_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), i64, C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoOut), vp]),
+        "rdv_ppo_set_workspace_bytes": (i64, [i32, C.POINTER(i64)]),
+        "rdv_ppo_set_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), C.POINTER(i64), C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoSetOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

@@ -2,7 +2,7 @@
 // value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
 // rdv_rollout_advantages, rdv_ppo_*, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
-// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch), so an edit to an argument check recompiles no kernel.
+// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch), so an edit to an argument check recompiles no kernel.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
@@ -615,6 +615,17 @@ int rdv_ppo_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_sp
   return RDV_OK;
 }
 
+// the dynamic-LDS limit of the PPO kernels, plain and set forms, once per device (a host-side attribute: no stream work); the caller's
+// DeviceGuard holds `device`
+static int raise_ppo_lds_limit(int device) {
+  static bool raised[64] = {};
+  if (device >= 64 || !raised[device]) {
+    RDV_HIP(ppo_raise_lds_limit());
+    if (device < 64) raised[device] = true;
+  }
+  return RDV_OK;
+}
+
 int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef, double vf_coef,
                       void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream) {
   const char* who = "rdv_ppo_loss_grad";
@@ -648,15 +659,79 @@ int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* row
   if (!actor->shipped_arch || !critic->shipped_arch) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the handles do not run the shipped kernels", who);
   if (actor->device != critic->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor on device %d, critic on device %d", who, actor->device, critic->device);
   DeviceGuard guard(actor->device);
-  static bool raised[64] = {};   // the kernels' dynamic-LDS limit, once per device (a host-side attribute: no stream work)
-  if (actor->device >= 64 || !raised[actor->device]) {
-    RDV_HIP(ppo_raise_lds_limit());
-    if (actor->device < 64) raised[actor->device] = true;
-  }
+  if (int rc = raise_ppo_lds_limit(actor->device)) return rc;
   PpoLaunch a = {actor->weights, critic->weights, rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, n,
                  (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)clip_range, (float)ent_coef, (float)vf_coef,
                  static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
   ppo_launch(a, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- PPO minibatch gradients for policy sets (csrc/rdv_ppo.h, "the set form")
+int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_host) {
+  if (n_members < 1 || n_members > kPpoSetMaxMembers || !counts_host) return -1;
+  bool any = false;
+  for (int32_t g = 0; g < n_members; ++g) {
+    if (counts_host[g] < 0) return -1;
+    any = any || counts_host[g] > 0;
+  }
+  return any ? ppo_set_table(n_members, counts_host, nullptr) : -1;
+}
+
+int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host, double clip_range,
+                          double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoSetOut* out, void* stream) {
+  const char* who = "rdv_ppo_set_loss_grad";
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
+  if (!counts_host) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host is null", who);
+  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"},
+                                                              {rows->advantages, "rows->advantages"}, {rows->returns, "rows->returns"},
+                                                              {rows->indices, "rows->indices"}, {out->actor_grad, "out->actor_grad"},
+                                                              {out->critic_grad, "out->critic_grad"}, {out->scalars, "out->scalars"}, {workspace, "workspace"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
+  // counts_host has one entry per member of the handles; with an invalid actor handle (refused below, behind the host-only checks) it is
+  // read as one member's.  A set larger than the cap is refused below, before anything past the cap is looked at.
+  const bool valid = actor_set && actor_set->magic == kPolicyMagic;
+  const int32_t P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
+  bool any = false;
+  for (int32_t g = 0; g < P; ++g) {
+    if (counts_host[g] < 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host[%d] = %lld is negative", who, g, (long long)counts_host[g]);
+    any = any || counts_host[g] > 0;
+  }
+  if (!any) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host holds no positive count (%d member%s)", who, P, P == 1 ? "" : "s");
+  if (rows->rows <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->rows must be positive (got %lld)", who, (long long)rows->rows);
+  if (misaligned(rows->obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->obs must be 16-byte aligned", who);
+  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  PpoSetLaunch L = {};
+  const int64_t need = ppo_set_table(P, counts_host, &L.table, nullptr, &L.max_workgroups);
+  if (workspace_bytes < need)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, these counts need %lld (rdv_ppo_set_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
+  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: clip_range must be finite and positive (got %g)", who, clip_range);
+  if (!std::isfinite(ent_coef) || ent_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: ent_coef must be finite and not negative (got %g)", who, ent_coef);
+  if (!std::isfinite(vf_coef) || vf_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: vf_coef must be finite and not negative (got %g)", who, vf_coef);
+  RDV_CHECK_POLICY(actor_set);
+  RDV_CHECK_POLICY(critic_set);
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};
+  for (const auto& a : nets)
+    if (a.p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is a recurrent policy or a recurrent set: its gradients are not built", who, a.name);
+  if (actor_set->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set is a critic handle (rdv_critic_set_create): actor and critic are swapped", who);
+  if (critic_set->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic_set is an actor handle (rdv_policy_set_create): actor and critic are swapped", who);
+  for (const auto& a : nets)
+    if (std::memcmp(&a.p->spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) != 0 || !a.p->shipped_arch)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not the shipped architecture (two hidden layers of 64, tanh): its gradients are not built", who, a.name);
+  if (actor_set->n_members != critic_set->n_members)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, critic_set has %d", who, actor_set->n_members, critic_set->n_members);
+  if (actor_set->n_members > kPpoSetMaxMembers)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, at most %d are served by one call (kPpoSetMaxMembers)", who, actor_set->n_members, kPpoSetMaxMembers);
+  if (actor_set->device != critic_set->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set on device %d, critic_set on device %d", who, actor_set->device, critic_set->device);
+  DeviceGuard guard(actor_set->device);
+  if (int rc = raise_ppo_lds_limit(actor_set->device)) return rc;
+  L.a = {actor_set->weights, critic_set->weights, rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, 0,
+         (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)clip_range, (float)ent_coef, (float)vf_coef,
+         static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
+  L.n_members = P;
+  ppo_set_launch(L, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }

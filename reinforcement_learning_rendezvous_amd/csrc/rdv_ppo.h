@@ -7,7 +7,7 @@
 //   1. ppo_transpose_kernel: the A-operand fragments of W3^T and W2^T of both nets, derived from the handles' FORWARD blocks (a permutation
 //      of their fp16 terms: (hi + lo) 2^-s is exactly the weight the forward pass multiplies by, i.e. the function being differentiated)
 //      into the head of the workspace.  No host state is added to the handles; a call enqueued behind rdv_policy_set_weights reads the new block.
-//   2. ppo_net_kernel<true>  (actor)  and  3. ppo_net_kernel<false> (critic): a wave owns 32 minibatch rows, a workgroup 256, as in
+//   2. ppo_net_kernel<true, false>  (actor)  and  3. ppo_net_kernel<false, false> (critic): a wave owns 32 minibatch rows, a workgroup 256, as in
 //      policy_act_kernel.  Per wave:
 //        gather   the rows' observations by `indices` into the wave's LDS rows (68-byte rows, as stage_obs_rows stages contiguous ones);
 //        forward  the shipped device functions of rdv_policy.h (actor_inputs, layer, tanh2_f32, split2: the sequence of actor_means, so
@@ -58,7 +58,53 @@ struct PpoLaunch {
   float *actor_grad, *critic_grad, *scalars, *log_prob, *values;
 };
 
-__attribute__((visibility("hidden"))) hipError_t ppo_raise_lds_limit();
+// ---- the set form (rdv_ppo_set_loss_grad, include/rdv.h "PPO minibatch gradients for policy sets"): P members' minibatches in the same
+// four launches, as rdv_policy_sets.h gives the forward kernels a set form — the same bodies, the member taken from the grid.
+//   ppo_set_transpose_kernel  grid (21, 2, P)                        member z, net y
+//   ppo_net_kernel<A, true>   grid (max_g workgroups(counts[g]), P)  workgroup (x, y) is workgroup x of member y's stand-alone launch; it
+//                             returns before its first barrier when x >= workgroups(counts[y]) (a workgroup-uniform test)
+//   ppo_set_finish_kernel     grid (44, P)                           member y
+// Everything a workgroup touches is the stand-alone kernel's, offset by member: the forward block is set base + y * kPolFloats (the set
+// allocation holds exactly the bytes of stand-alone handles), the backward blocks and `parts` are member y's piece of the workspace,
+// `indices`, log_prob and values are advanced by off[y], n is count[y].  wave_base, the LDS layout, the wave-order sums and the index-order
+// sum of the last kernel are per member exactly as alone, so every output of member y has the bits of the stand-alone call.
+// count, off and the workspace offsets travel BY VALUE in the kernel arguments (PpoSetTable): no device table, hence no host-to-device
+// copy that a capture would forbid.  That is the reason for the cap: 64 members x 3 x 8 bytes = 1,536 B of the 4 KiB argument segment, next
+// to the 104 B of the stand-alone kernel's own arguments.
+// The workspace, member after member, members with count 0 left out: [2 x kPpoBwdFloats | workgroups(count[g]) x kPpoPartFloats] floats;
+// both pieces are multiples of 16 bytes.
+constexpr int kPpoSetMaxMembers = 64;
+struct PpoSetTable {
+  int64_t count[kPpoSetMaxMembers];   // member g's minibatch size (0: the member takes no part)
+  int64_t off[kPpoSetMaxMembers];     // count[0] + .. + count[g-1]: where its indices, log_prob and values start
+  int64_t ws[kPpoSetMaxMembers];      // where its piece of the workspace starts, in floats
+};
+static_assert((2 * kPpoBwdFloats) % 4 == 0 && kPpoPartFloats % 4 == 0, "every piece of the workspace is 16-byte aligned");
+// fills `t` for counts[0 .. n_members) (all >= 0, n_members <= kPpoSetMaxMembers) -> the workspace's size in bytes
+inline int64_t ppo_set_table(int32_t n_members, const int64_t* counts, PpoSetTable* t, int64_t* total = nullptr, int64_t* max_workgroups = nullptr) {
+  int64_t off = 0, ws = 0, most = 0;
+  for (int g = 0; g < kPpoSetMaxMembers; ++g) {
+    const int64_t c = g < n_members ? counts[g] : 0;
+    if (t) { t->count[g] = c; t->off[g] = off; t->ws[g] = ws; }
+    off += c;
+    if (c > 0) ws += 2 * (int64_t)kPpoBwdFloats + ppo_workgroups(c) * kPpoPartFloats;
+    if (ppo_workgroups(c) > most) most = ppo_workgroups(c);
+  }
+  if (total) *total = off;
+  if (max_workgroups) *max_workgroups = most;
+  return ws * (int64_t)sizeof(float);
+}
+
+struct PpoSetLaunch {
+  PpoLaunch a;            // actor_block, critic_block: the sets' allocations (member g at g * kPolFloats); n unused; indices required;
+                          // actor_grad [P,5708], critic_grad [P,5377], scalars [P,8]; log_prob, values [sum of counts], nullable
+  int32_t n_members;
+  int64_t max_workgroups;
+  PpoSetTable table;
+};
+
+__attribute__((visibility("hidden"))) hipError_t ppo_raise_lds_limit();   // the plain and the set instantiations
 __attribute__((visibility("hidden"))) void ppo_launch(const PpoLaunch& a, hipStream_t s);
+__attribute__((visibility("hidden"))) void ppo_set_launch(const PpoSetLaunch& a, hipStream_t s);
 
 }  // namespace rdv

@@ -4,6 +4,8 @@
 #include "rdv_policy.h"
 #include "rdv_ppo.h"
 
+#include <type_traits>
+
 namespace rdv {
 
 // LDS of ppo_net_kernel (floats): parameters | per wave: observation rows [32][17] | per wave: three operand tiles | per wave: 4 scalar sums.
@@ -21,10 +23,7 @@ static_assert(kPpoBlockRows == kPolBlockEnvs, "a workgroup owns 256 rows");
 //   W2^T, b = 4 + (q*2 + mt)*4 + ks: W2_q[perm(ks, h, j)][32 mt + r]
 // read from where the forward block keeps W_q[o][i]: fragment base + (q*MT + (o >> 5))*4 + ks(i), lane (o & 31, h(i)), element j(i), the
 // inverse of perm.
-__global__ __launch_bounds__(512) void ppo_transpose_kernel(const float* __restrict__ actor_block, const float* __restrict__ critic_block,
-                                                            float* __restrict__ workspace) {
-  const uint16_t* src = reinterpret_cast<const uint16_t*>(blockIdx.y == 0 ? actor_block : critic_block);
-  float* dstf = workspace + (size_t)blockIdx.y * kPpoBwdFloats;
+__device__ __forceinline__ void ppo_transpose_body(const uint16_t* __restrict__ src, float* __restrict__ dstf) {
   const int b = blockIdx.x, t = threadIdx.x;
   if (b == kPpoBwdFrags) { if (t < 64) dstf[kPpoBwdZero + t] = 0.0f; return; }
   const int lane = t >> 3, j = t & 7, r = lane & 31, h = lane >> 5;
@@ -35,6 +34,18 @@ __global__ __launch_bounds__(512) void ppo_transpose_kernel(const float* __restr
   const int ks_i = (i >> 5) * 2 + ((i >> 4) & 1), h_i = (i >> 2) & 1, j_i = ((i >> 3) & 1) * 4 + (i & 3);
   const int frag = head ? kPolW3Frag + q * 4 + ks_i : kPolW2Frag + (q * 2 + (o >> 5)) * 4 + ks_i;
   reinterpret_cast<uint16_t*>(dstf)[(b * 64 + lane) * 8 + j] = src[(frag * 64 + (o & 31) + 32 * h_i) * 8 + j_i];
+}
+__global__ __launch_bounds__(512) void ppo_transpose_kernel(const float* __restrict__ actor_block, const float* __restrict__ critic_block,
+                                                            float* __restrict__ workspace) {
+  ppo_transpose_body(reinterpret_cast<const uint16_t*>(blockIdx.y == 0 ? actor_block : critic_block), workspace + (size_t)blockIdx.y * kPpoBwdFloats);
+}
+// the set form: member blockIdx.z of the sets' allocations -> the head of its piece of the workspace; a member without samples is skipped
+__global__ __launch_bounds__(512) void ppo_set_transpose_kernel(const float* __restrict__ actor_set, const float* __restrict__ critic_set,
+                                                                float* __restrict__ workspace, const PpoSetTable T) {
+  const int g = blockIdx.z;
+  if (T.count[g] == 0) return;
+  const float* block = (blockIdx.y == 0 ? actor_set : critic_set) + (size_t)g * kPolFloats;
+  ppo_transpose_body(reinterpret_cast<const uint16_t*>(block), workspace + T.ws[g] + (size_t)blockIdx.y * kPpoBwdFloats);
 }
 
 // ---- 2, 3. one net's loss terms and gradients
@@ -195,8 +206,41 @@ __device__ __forceinline__ void weight_grads(const float (&delta)[MT][16], float
   }
 }
 
-template <bool ACTOR>
-__global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const PpoNetArgs A) {
+// The set form's arguments: `net` holds the set-wide pointers (block: the set's allocation; parts: the workspace; indices and out: all
+// members'; bwd and n unused); ppo_member_args derives member blockIdx.y's own.  `idle`: workgroup x has no rows of that member (it has
+// fewer workgroups than the widest member, or no samples) — a workgroup-uniform test, taken before the first barrier.
+struct PpoSetNetArgs {
+  PpoNetArgs net;
+  PpoSetTable table;
+};
+template <bool ACTOR, bool SET>
+__device__ __forceinline__ PpoNetArgs ppo_member_args(const std::conditional_t<SET, PpoSetNetArgs, PpoNetArgs>& S, bool& idle) {
+  if constexpr (SET) {
+    const int g = blockIdx.y;
+    const int64_t n = S.table.count[g];
+    idle = (int64_t)blockIdx.x * kPpoBlockRows >= n;
+    const int64_t off = S.table.off[g];
+    float* ws = S.net.parts + S.table.ws[g];
+    PpoNetArgs M = S.net;
+    M.block = S.net.block + (size_t)g * kPolFloats;
+    M.bwd = ws + (ACTOR ? 0 : kPpoBwdFloats);
+    M.indices = S.net.indices + off;
+    M.n = n;
+    M.parts = ws + 2 * kPpoBwdFloats;
+    M.out = S.net.out ? S.net.out + off : nullptr;
+    return M;
+  } else {
+    idle = false;
+    return S;
+  }
+}
+// SET = false: the kernel of rdv_ppo_loss_grad, the instruction stream it had before there was a set form (profiles/ppo_set_isa_diff.md).
+// SET = true: workgroup (x, y) is workgroup x of member y's stand-alone launch: the same body on the member's arguments.
+template <bool ACTOR, bool SET>
+__global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const std::conditional_t<SET, PpoSetNetArgs, PpoNetArgs> S) {
+  bool idle;
+  const PpoNetArgs A = ppo_member_args<ACTOR, SET>(S, idle);
+  if (SET && idle) return;
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int OUT = ACTOR ? kPolOut : 1;
   float* w = lds;
@@ -381,9 +425,9 @@ __global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const PpoNetArgs A) 
 }
 
 // ---- 4. the workgroups' rows added in index order -> the gradients (divided by n; - ent_coef on d log_std) and the scalars
-__global__ __launch_bounds__(256) void ppo_finish_kernel(const float* __restrict__ parts, int64_t workgroups, int64_t n, const float* __restrict__ actor_block,
-                                                          float ent_coef, float vf_coef, float* __restrict__ actor_grad, float* __restrict__ critic_grad,
-                                                          float* __restrict__ scalars) {
+__device__ __forceinline__ void ppo_finish_body(const float* __restrict__ parts, int64_t workgroups, int64_t n, const float* __restrict__ actor_block,
+                                                float ent_coef, float vf_coef, float* __restrict__ actor_grad, float* __restrict__ critic_grad,
+                                                float* __restrict__ scalars) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const float fn = (float)n;
   if (i < kPpoActorGrad + kPpoCriticGrad) {
@@ -409,10 +453,27 @@ __global__ __launch_bounds__(256) void ppo_finish_kernel(const float* __restrict
     scalars[4] = (float)(s[1] / dn); scalars[5] = (float)(s[2] / dn); scalars[6] = 0.0f; scalars[7] = 0.0f;
   }
 }
+__global__ __launch_bounds__(256) void ppo_finish_kernel(const float* __restrict__ parts, int64_t workgroups, int64_t n, const float* __restrict__ actor_block,
+                                                          float ent_coef, float vf_coef, float* __restrict__ actor_grad, float* __restrict__ critic_grad,
+                                                          float* __restrict__ scalars) {
+  ppo_finish_body(parts, workgroups, n, actor_block, ent_coef, vf_coef, actor_grad, critic_grad, scalars);
+}
+// the set form: member blockIdx.y's rows of the workspace -> row blockIdx.y of the outputs; nothing of a member without samples is written
+__global__ __launch_bounds__(256) void ppo_set_finish_kernel(const float* __restrict__ workspace, const float* __restrict__ actor_set, float ent_coef,
+                                                              float vf_coef, float* __restrict__ actor_grad, float* __restrict__ critic_grad,
+                                                              float* __restrict__ scalars, const PpoSetTable T) {
+  const int g = blockIdx.y;
+  const int64_t n = T.count[g];
+  if (n == 0) return;
+  ppo_finish_body(workspace + T.ws[g] + 2 * kPpoBwdFloats, (n + kPpoBlockRows - 1) / kPpoBlockRows, n, actor_set + (size_t)g * kPolFloats, ent_coef, vf_coef,
+                  actor_grad + (size_t)g * kPpoActorGrad, critic_grad + (size_t)g * kPpoCriticGrad, scalars + (size_t)g * kPpoScalars);
+}
 
 hipError_t ppo_raise_lds_limit() {
-  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_net_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoLdsBytes);
-  if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_net_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoLdsBytes);
+  hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_net_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoLdsBytes);
+  if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_net_kernel<false, false>), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoLdsBytes);
+  if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_net_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoLdsBytes);
+  if (err == hipSuccess) err = hipFuncSetAttribute(reinterpret_cast<const void*>(ppo_net_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoLdsBytes);
   return err;
 }
 
@@ -422,12 +483,26 @@ void ppo_launch(const PpoLaunch& a, hipStream_t s) {
   hipLaunchKernelGGL(ppo_transpose_kernel, dim3(kPpoBwdFrags + 1, 2), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace);
   PpoNetArgs net = {a.actor_block, a.workspace, a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, a.indices, a.n,
                     a.clip_lo, a.clip_hi, a.clip_range, 2.0f * a.vf_coef, parts, a.log_prob};
-  hipLaunchKernelGGL(ppo_net_kernel<true>, dim3((unsigned)groups), dim3(kPolBlock), kPpoLdsBytes, s, net);
+  hipLaunchKernelGGL((ppo_net_kernel<true, false>), dim3((unsigned)groups), dim3(kPolBlock), kPpoLdsBytes, s, net);
   net.block = a.critic_block; net.bwd = a.workspace + kPpoBwdFloats; net.out = a.values;
-  hipLaunchKernelGGL(ppo_net_kernel<false>, dim3((unsigned)groups), dim3(kPolBlock), kPpoLdsBytes, s, net);
+  hipLaunchKernelGGL((ppo_net_kernel<false, false>), dim3((unsigned)groups), dim3(kPolBlock), kPpoLdsBytes, s, net);
   const int total = kPpoActorGrad + kPpoCriticGrad + 1;
   hipLaunchKernelGGL(ppo_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, parts, groups, a.n, a.actor_block, a.ent_coef, a.vf_coef,
                      a.actor_grad, a.critic_grad, a.scalars);
+}
+
+void ppo_set_launch(const PpoSetLaunch& L, hipStream_t s) {
+  const PpoLaunch& a = L.a;
+  const unsigned P = (unsigned)L.n_members;
+  hipLaunchKernelGGL(ppo_set_transpose_kernel, dim3(kPpoBwdFrags + 1, 2, P), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace, L.table);
+  PpoSetNetArgs S = {{a.actor_block, nullptr, a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, a.indices, 0,
+                      a.clip_lo, a.clip_hi, a.clip_range, 2.0f * a.vf_coef, a.workspace, a.log_prob}, L.table};
+  hipLaunchKernelGGL((ppo_net_kernel<true, true>), dim3((unsigned)L.max_workgroups, P), dim3(kPolBlock), kPpoLdsBytes, s, S);
+  S.net.block = a.critic_block; S.net.out = a.values;
+  hipLaunchKernelGGL((ppo_net_kernel<false, true>), dim3((unsigned)L.max_workgroups, P), dim3(kPolBlock), kPpoLdsBytes, s, S);
+  const int total = kPpoActorGrad + kPpoCriticGrad + 1;
+  hipLaunchKernelGGL(ppo_set_finish_kernel, dim3((total + 255) / 256, P), dim3(256), 0, s, a.workspace, a.actor_block, a.ent_coef, a.vf_coef,
+                     a.actor_grad, a.critic_grad, a.scalars, L.table);
 }
 
 }  // namespace rdv

@@ -531,9 +531,28 @@ class PolicySet(_HipHandles):
         return _advantages(self, ro, gamma, gae_lambda, out)
 
     def ppo_grad(self, *args, **kwargs):
-        """Not offered for a set: ``MlpPolicy.ppo_grad`` serves one actor and one critic."""
+        """Not offered for a set: ``MlpPolicy.ppo_grad`` serves one actor and one critic (``ppo_grads`` serves all members at once)."""
         from . import ppo
         return ppo.ppo_grad(self, *args, **kwargs)
+
+    def ppo_grads(self, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
+        """``MlpPolicy.ppo_grad`` for every member at once: the PPO loss of one minibatch per member and its gradients, written into
+        ``.grad`` of the member modules' parameters (ppo.py; include/rdv.h "PPO minibatch gradients for policy sets").  ``buf``: the dict
+        ``RendezvousBatch.collect(set, T)`` returns; ``buf["obs"]`` must be [T, N, 17] with N the set's rows.  ``indices``: a list of P
+        int64 tensors of flat rows on the rows' device (one step of ``ppo_set_minibatches``), ``None`` for a member that sits this step
+        out: its ``.grad`` is left as it was and its entry of the result is ``None``.  With ``check`` every member's indices that
+        ``ppo_set_minibatches`` did not make for this set and T must be in range and lie in that member's env columns
+        (``idx % N`` in its slice; IndexError), which also keeps the members' rows disjoint.  One clip_range / ent_coef / vf_coef for
+        all members.  CUDA rows, the shipped 17-64-64 tanh architecture, ``backend != "torch"``: the indices are concatenated into a
+        buffer the set owns (the counts are the tensors' sizes: nothing is read from the device), the advantages are normalised per
+        member with SB3's expression on its own minibatch — the expression of ``ppo_grad``, hence its bits — into one advantage column
+        the set owns, and ONE rdv_ppo_set_loss_grad runs on the current stream.  The gradients land in two buffers [P,5708] and
+        [P,5377] the set owns; member g's ``.grad`` tensors are views of row g, so per-member ``clip_grad_norm_``, one optimiser over
+        all members' parameters and ``update_weights()`` follow unchanged.  Every member's gradients and scalars are bit for bit those
+        of its own ``MlpPolicy.ppo_grad`` on the same buffer and indices.  CPU rows, ``backend="torch"`` or another architecture:
+        ``ppo.ppo_grad`` member by member.  Returns a list of P dicts of 0-dim tensors (the scalars of ``ppo_grad``)."""
+        from . import ppo
+        return ppo.ppo_set_grads(self, buf, indices, clip_range, ent_coef, vf_coef, normalize_advantage, check)
 
     # ------------------------------------------------------------------------------------------------ weights
     def update_weights(self, member=None, weights=None):

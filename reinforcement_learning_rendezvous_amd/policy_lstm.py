@@ -575,6 +575,11 @@ class LstmPolicySet(_LstmRows):
         from . import ppo
         return ppo.ppo_grad(self, *args, **kwargs)
 
+    def ppo_grads(self, *args, **kwargs):
+        """Not offered for a recurrent set: ``PolicySet.ppo_grads`` serves sets of the feed-forward shipped actor and critic."""
+        from . import ppo
+        return ppo.ppo_set_grads(self, *args, **kwargs)
+
     def update_weights(self, member=None, weights=None):
         """New weights for one member (``member`` = its index; ``weights``: a dict as ``LstmPolicy.update_weights`` takes, or None to
         push the member module's current parameters) or for all members (``member`` None; ``weights``: None or a list of one dict or

@@ -15,6 +15,19 @@ include/rdv.h "PPO minibatch gradients"; csrc/rdv_ppo.h): hand-written MFMA kern
 synchronisation, legal inside a stream capture.  CPU rows, ``backend="torch"`` and every other architecture run the same expressions
 through autograd over the policy's own modules and fill the same ``.grad`` tensors.  Gradient clipping, the optimiser and its schedules are
 PyTorch's; ``update_weights`` repacks as it always did.
+
+A sweep of P learners on one GPU (``PolicySet``, one grouped batch) takes the same step for all members at once:
+
+    for epoch in range(n_epochs):
+        for pieces in ppo_set_minibatches(learners, T, batch_size, generator):                # step k: one index tensor per member
+            stats = learners.ppo_grads(buf, pieces, clip_range=0.2, ent_coef=0.0, vf_coef=0.5)
+            for member in learners:
+                torch.nn.utils.clip_grad_norm_(member.parameters(), 0.5)
+            optimizer.step()                                                                  # one optimiser over all members' parameters
+            learners.update_weights()
+
+``PolicySet.ppo_grads`` is ONE call of rdv_ppo_set_loss_grad (include/rdv.h "PPO minibatch gradients for policy sets"): the members'
+minibatches share four launches, and every member gets the bits of its own ``MlpPolicy.ppo_grad``.
 """
 import ctypes as C
 import math
@@ -40,6 +53,32 @@ def ppo_minibatches(n_rows, batch_size, generator=None, device=None):
     for p in parts:
         p._rdv_ppo_rows = n_rows
     return parts
+
+
+def ppo_set_minibatches(pset, n_steps, batch_size, generator=None, device=None):
+    """One epoch for all members of a ``PolicySet`` over a ``[T, N]`` rollout (T = ``n_steps``, N the set's rows): member g gets a
+    ``torch.randperm(T * size_g)``, drawn in member order from the one generator and cut into pieces of ``batch_size`` as
+    ``ppo_minibatches`` cuts; local row j of member g is the flat row ``(j // size_g) * N + start_g + j % size_g`` of the buffer (step
+    j // size_g, the member's env column j % size_g).  Returns a list of steps; step k is a list of P int64 tensors of flat rows, ``None``
+    for a member whose pieces have run out (unequal group sizes give unequal piece counts).  Over the epoch every member sees each of its
+    T * size_g rows exactly once.  The tensors are marked as checked for this set and T, so ``PolicySet.ppo_grads`` does not check them
+    again."""
+    n_steps, batch_size = int(n_steps), int(batch_size)
+    if n_steps <= 0 or batch_size <= 0:
+        raise ValueError(f"ppo_set_minibatches: n_steps = {n_steps} and batch_size = {batch_size} must be positive")
+    if device is None:
+        device = generator.device if generator is not None else "cpu"
+    N = int(pset.num_rows)
+    per = []
+    for sl in pset.group_slices:
+        size = sl.stop - sl.start
+        perm = torch.randperm(n_steps * size, generator=generator, device=device)
+        flat = torch.div(perm, size, rounding_mode="floor") * N + (sl.start + perm % size)
+        pieces = list(torch.split(flat, batch_size))
+        for p in pieces:
+            p._rdv_ppo_set = (n_steps * N, N, sl.start, sl.stop)
+        per.append(pieces)
+    return [[pieces[k] if k < len(pieces) else None for pieces in per] for k in range(max(len(pieces) for pieces in per))]
 
 
 def ppo_loss_terms(mean, log_std, values, actions, old_log_prob, advantages, returns, clip_range, ent_coef, vf_coef):
@@ -125,18 +164,22 @@ def _columns(buf):
     return flat, rows, dev
 
 
+def _check_coefficients(who, clip_range, ent_coef, vf_coef):
+    for name, v, low in (("clip_range", clip_range, None), ("ent_coef", ent_coef, 0.0), ("vf_coef", vf_coef, 0.0)):
+        v = float(v)
+        if not math.isfinite(v) or (v <= 0.0 if low is None else v < low):
+            raise ValueError(f"{who}: {name} = {v!r} must be finite and " + ("positive" if low is None else "not negative"))
+
+
 def ppo_grad(policy, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
     """See ``MlpPolicy.ppo_grad``."""
     from .policy import MlpPolicy
     if not isinstance(policy, MlpPolicy):
-        raise TypeError(f"ppo_grad: a {type(policy).__name__} is not offered: the PPO minibatch gradients are built for MlpPolicy alone "
-                        "(PolicySet, LstmPolicy and LstmPolicySet keep SB3 / PyTorch for the update)")
+        raise TypeError(f"ppo_grad: a {type(policy).__name__} is not offered: it serves one MlpPolicy (a PolicySet has ppo_grads for all "
+                        "its members at once; LstmPolicy and LstmPolicySet keep SB3 / PyTorch for the update)")
     if not policy.has_critic:
         raise ValueError("ppo_grad: this policy has no critic (its weights hold no value_net trunk)")
-    for name, v, low in (("clip_range", clip_range, None), ("ent_coef", ent_coef, 0.0), ("vf_coef", vf_coef, 0.0)):
-        v = float(v)
-        if not math.isfinite(v) or (v <= 0.0 if low is None else v < low):
-            raise ValueError(f"ppo_grad: {name} = {v!r} must be finite and " + ("positive" if low is None else "not negative"))
+    _check_coefficients("ppo_grad", clip_range, ent_coef, vf_coef)
     cols, rows, dev = _columns(buf)
     if indices is None:
         n = rows
@@ -201,3 +244,103 @@ def ppo_grad(policy, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.
     _bind_grads(policy, st, dev)
     s = st["scalars"].clone()
     return {name: s[k] for k, name in enumerate(SCALAR_NAMES)}
+
+
+def _set_state(pset, dev, P, total, rows, counts):
+    """The buffers a PolicySet owns for ppo_grads on device ``dev``: the gradients [P,5708] and [P,5377] (row g: member g's flat buffers,
+    of which its parameters' ``.grad`` are views), the scalars [P,8], the concatenated indices, the advantage column and the workspace,
+    the last three grown when a call needs more."""
+    from . import _native as N
+    st = pset.__dict__.setdefault("_ppo", {}).get(dev)
+    if st is None:
+        st = dict(actor=torch.zeros((P, N.PPO_ACTOR_GRAD), dtype=torch.float32, device=dev),
+                  critic=torch.zeros((P, N.PPO_CRITIC_GRAD), dtype=torch.float32, device=dev),
+                  scalars=torch.zeros((P, N.PPO_SCALARS), dtype=torch.float32, device=dev), idx=None, adv=None, workspace=None)
+        pset._ppo[dev] = st
+    if st["idx"] is None or st["idx"].numel() < total:
+        st["idx"] = torch.zeros(total, dtype=torch.int64, device=dev)
+    if st["adv"] is None or st["adv"].numel() < rows:
+        st["adv"] = torch.zeros(rows, dtype=torch.float32, device=dev)
+    need = int(N.lib().rdv_ppo_set_workspace_bytes(P, counts))
+    if need < 0:
+        raise ValueError(f"ppo_grads: a set of {P} members is not served by one call (rdv_ppo_set_workspace_bytes)")
+    if st["workspace"] is None or st["workspace"].numel() < need:
+        st["workspace"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return st
+
+
+def ppo_set_grads(pset, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
+    """See ``PolicySet.ppo_grads``."""
+    from .policy import PolicySet
+    if not isinstance(pset, PolicySet):
+        raise TypeError(f"ppo_grads: a {type(pset).__name__} is not offered: the set form of the PPO minibatch gradients is built for "
+                        "PolicySet alone (LstmPolicySet keeps SB3 / PyTorch for the update)")
+    P = len(pset)
+    if not isinstance(indices, (list, tuple)) or len(indices) != P:
+        raise ValueError(f"ppo_grads: indices must be a list of {P} tensors (or None), one per member")
+    if not pset.has_critic:
+        raise ValueError("ppo_grads: a member has no critic (its weights hold no value_net trunk)")
+    _check_coefficients("ppo_grads", clip_range, ent_coef, vf_coef)
+    cols, rows, dev = _columns(buf)
+    obs = buf["obs"]
+    if obs.dim() != 3 or int(obs.shape[1]) != pset.num_rows:
+        raise ValueError(f"ppo_grads: buf['obs'] is {tuple(obs.shape)}, expected [T, {pset.num_rows}, 17]: N must be the set's rows")
+    n_envs = pset.num_rows
+    live = [g for g in range(P) if indices[g] is not None]
+    if not live:
+        raise ValueError("ppo_grads: every member's indices are None")
+    indices = list(indices)
+    for g in live:
+        idx, sl = indices[g], pset.group_slices[g]
+        if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int64 or idx.dim() != 1 or idx.device != dev or idx.numel() == 0:
+            raise ValueError(f"ppo_grads: indices[{g}] must be a non-empty 1-d int64 tensor on {dev} (or None)")
+        if check and getattr(idx, "_rdv_ppo_set", None) != (rows, n_envs, sl.start, sl.stop):
+            lo, hi = (int(x) for x in torch.aminmax(idx))
+            if lo < 0 or hi >= rows:
+                raise IndexError(f"ppo_grads: indices[{g}] span [{lo}, {hi}], the rollout has rows 0..{rows - 1}")
+            lo, hi = (int(x) for x in torch.aminmax(idx % n_envs))
+            if lo < sl.start or hi >= sl.stop:
+                raise IndexError(f"ppo_grads: indices[{g}] reach env columns [{lo}, {hi}], member {g} owns {sl.start}..{sl.stop - 1}")
+        indices[g] = idx.contiguous()
+
+    hip = pset.backend != "torch" and dev.type == "cuda" and pset.shipped_arch and pset.vf_arch == [64, 64]
+    if not hip:
+        out = [None] * P
+        for g in live:
+            member = pset[g]
+            backend = member.backend
+            if pset.backend == "torch":
+                member.backend = "torch"
+            try:
+                out[g] = ppo_grad(member, buf, indices[g], clip_range, ent_coef, vf_coef, normalize_advantage, check=False)
+            finally:
+                member.backend = backend
+        return out
+
+    from . import _native as N
+    counts = (C.c_int64 * P)(*[int(indices[g].numel()) if indices[g] is not None else 0 for g in range(P)])
+    total = sum(counts)
+    st = _set_state(pset, dev, P, total, rows, counts)
+    with torch.no_grad():
+        torch.cat([indices[g] for g in live], out=st["idx"][:total])
+        if normalize_advantage and max(counts) > 1:
+            # SB3's expression per member on its own 1-d minibatch (the expression of ppo_grad: the same bits), written back to the
+            # member's rows of the one advantage column the set owns; a lone sample keeps its raw advantage, as SB3 leaves it
+            for g in live:
+                adv = cols["advantages"][indices[g]]
+                st["adv"].index_copy_(0, indices[g], normalize_advantages(adv) if counts[g] > 1 else adv)
+            adv_col = st["adv"]
+        else:
+            adv_col = cols["advantages"]
+    r = N.PpoRows(cols["obs"].data_ptr(), cols["actions"].data_ptr(), cols["log_prob"].data_ptr(), adv_col.data_ptr(), cols["returns"].data_ptr(),
+                  st["idx"].data_ptr(), rows)
+    o = N.PpoSetOut(st["actor"].data_ptr(), st["critic"].data_ptr(), st["scalars"].data_ptr(), None, None)
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    N.check(N.lib().rdv_ppo_set_loss_grad(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(r), counts, float(clip_range), float(ent_coef),
+                                          float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    s = st["scalars"].clone()
+    out = [None] * P
+    for g in live:
+        _bind_grads(pset[g], dict(actor=st["actor"][g], critic=st["critic"][g]), dev)
+        out[g] = {name: s[g, k] for k, name in enumerate(SCALAR_NAMES)}
+    return out
