@@ -233,11 +233,15 @@ __device__ __forceinline__ void refill_stale_slots(const StepArgs& A, const DevP
 // The slot form (kSlots; fp32 storage, kAll, on_done == RESET only) is the fourth attempt at taking the speculative reset off the path to
 // the barrier, and keeps everything that made this kernel win: the single barrier right behind the transition, the step waves as they
 // are, the reset writes beside the step waves' statistics and outputs.  It changes the two things the slot attempts lost by:
-//  - the SERVICE waves fetch the prepared slots, not the step waves: at entry every service lane requests its env's 192-byte record
-//    (rdv_slots.h: hbm_slot_store), the env's chunk 5 (k, episode) and its tag — dense, coalesced, thousands of cycles before the data
-//    is used — and goes to the barrier without any arithmetic.  Behind it a lane whose env finished copies the record (state chunks to
-//    HBM, observation to its LDS row) when tag == episode + 1 and k >= 1, both as read at entry; otherwise (an env that ends on the
-//    first step of its episode, or a slot that is stale for whatever reason) it runs today's in-lane reset: slow, rare, correct;
+//  - the SERVICE waves fetch the prepared slots, not the step waves: at entry every service lane requests its env's chunk 5 (k, episode)
+//    and its tag, waits for them, and then — if tag == episode + 1 and k >= 1, i.e. if the slot can be consumed in this launch —
+//    its env's 192-byte record (rdv_slots.h: hbm_slot_store): dense, coalesced, ~4,000 cycles before the data is used; it goes to the
+//    barrier without any arithmetic.  Behind it a lane whose env finished copies the record (state chunks to HBM, observation to its
+//    LDS row) if it requested one; otherwise (an env that ends on the first step of its episode, or a slot that is stale for whatever
+//    reason) it runs today's in-lane reset: slow, rare, correct.  The records go out in a SECOND stage because they are the least
+//    urgent requests of the CU and were the most numerous: issued at entry with everything else (54 KB per CU beside the step waves'
+//    35 KB) they stood in the queues in front of the state the step waves begin with (profiles/split_prefetch_order.txt: 6.09 ->
+//    5.92 us per launch at 65,536 envs; a fixed s_sleep in front of the requests gains less at every length);
 //  - the refill leaves the workgroup: the grid has one more workgroup per step workgroup (blockIdx.x >= the number of step workgroups;
 //    for the flagship's 256 both indices are equal mod 8: same XCD, same L2), whose waves 0-3 list — ballots, no atomics — the envs of
 //    step workgroup j with k == 0 and tag != episode + 1 (~13 of 256 with random actions, all 256 after a synchronous episode end)
@@ -358,31 +362,67 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
     RDV_STAMP(6);
   } else if constexpr (kSlots) {
     // ------------------------------------------------------------------ service waves, slot form
-    // Every lane issues every request (the index is clamped into the batch, as in tile_fetch): nothing sits under a branch, all 14 are
-    // in flight together.  Native vectors, and every lane of them is used behind the barrier (profiles/r03_split_slots_hint.txt).
+    // The requests in the order of their urgency (profiles/split_prefetch_order.txt).  Every lane first requests its env's chunk 5 (k,
+    // episode) and its tag (the index is clamped into the batch, as in tile_fetch) and waits for them: one round trip to L2, in which
+    // the step waves' ten input requests of this CU — and of the workgroups dispatched a little earlier on the XCD — are served
+    // without 12 x 16 bytes per service lane queued in front of them.  The wait is the delay: no constant to tune.  Then the lanes whose
+    // slot CAN be consumed in this launch (tag == episode + 1 and k >= 1: `copy_ok`, the one value that also picks the copy path behind
+    // the barrier, so a lane that requested nothing cannot copy) request the twelve vectors of the record, all in flight together,
+    // ~4,000 cycles before the barrier.  The other lanes (k == 0: ~5 % with random actions, and their records are the ones the refill
+    // workgroup is writing in this launch) request nothing.  Loads and waits are inline assembly with the registers as operands, as
+    // PinnedInputs' are (rdv_kernels.h): written as C++ loads the compiler hoists the record requests back in front of the wait.  The
+    // record requests are ONE statement under an exec mask it saves and restores itself: no branch, and no place for the compiler to put
+    // a copy of a register whose data has not landed.
     constexpr int kRecVecs = kChunks + kSlotObsVecs;
-    static_assert(slot_record_bytes<ST>() == kRecVecs * 16, "the fp32 slot record is 12 vectors");
+    static_assert(slot_record_bytes<ST>() == kRecVecs * 16 && kRecVecs == 12, "the fp32 slot record is 12 vectors: the requests are written out below");
     const int64_t il = active ? i : n - 1;
     const pin_f4* recp = reinterpret_cast<const pin_f4*>(A.prep) + il * kRecVecs;
     pin_f4 rec[kRecVecs];
-#pragma unroll
-    for (int v = 0; v < kRecVecs; ++v) rec[v] = recp[v];
-    pin_f4 c5 = reinterpret_cast<const pin_f4*>(ws)[5 * A.cs + il];
-    uint32_t tag = A.prep_tag[il];
+    pin_f4 c5;
+    uint32_t tag;
+    asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dword %1, %3, off"
+                 : "=&v"(c5), "=&v"(tag) : "v"(reinterpret_cast<const pin_f4*>(ws) + 5 * A.cs + il), "v"(A.prep_tag + il));
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(c5), "+v"(tag));
     RDV_STAMP(1);
+    const uint32_t k_in = __float_as_uint(c5.y), episode_in = __float_as_uint(c5.w);
+    const bool copy_ok = tag == episode_in + 1u && k_in >= 1u;
+#pragma unroll
+    for (int v = 0; v < kRecVecs; ++v) asm volatile("" : "=v"(rec[v]));   // (defined registers for the lanes that request nothing)
+    unsigned long long saved_exec;
+    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
+                 "global_load_dwordx4 %[r0], %[p], off\n\t"
+                 "global_load_dwordx4 %[r1], %[p], off offset:16\n\t"
+                 "global_load_dwordx4 %[r2], %[p], off offset:32\n\t"
+                 "global_load_dwordx4 %[r3], %[p], off offset:48\n\t"
+                 "global_load_dwordx4 %[r4], %[p], off offset:64\n\t"
+                 "global_load_dwordx4 %[r5], %[p], off offset:80\n\t"
+                 "global_load_dwordx4 %[r6], %[p], off offset:96\n\t"
+                 "global_load_dwordx4 %[r7], %[p], off offset:112\n\t"
+                 "global_load_dwordx4 %[r8], %[p], off offset:128\n\t"
+                 "global_load_dwordx4 %[r9], %[p], off offset:144\n\t"
+                 "global_load_dwordx4 %[r10], %[p], off offset:160\n\t"
+                 "global_load_dwordx4 %[r11], %[p], off offset:176\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [r0] "+v"(rec[0]), [r1] "+v"(rec[1]), [r2] "+v"(rec[2]), [r3] "+v"(rec[3]), [r4] "+v"(rec[4]), [r5] "+v"(rec[5]), [r6] "+v"(rec[6]),
+                   [r7] "+v"(rec[7]), [r8] "+v"(rec[8]), [r9] "+v"(rec[9]), [r10] "+v"(rec[10]), [r11] "+v"(rec[11]), [sv] "=&s"(saved_exec)
+                 : [p] "v"(recp), [m] "s"(__ballot(copy_ok))
+                 : "scc");
+#ifdef RDV_STAMPS
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]),
+                 "+v"(rec[7]), "+v"(rec[8]), "+v"(rec[9]), "+v"(rec[10]), "+v"(rec[11]));   // stamps build only: stamp 2 is "the records have landed"
+#endif
     RDV_STAMP(2);
     RDV_STAMP(3);
     __syncthreads();
     RDV_STAMP(4);
-#pragma unroll
-    for (int v = 0; v < kRecVecs; ++v) asm volatile("" : "+v"(rec[v]));
-    asm volatile("" : "+v"(c5), "+v"(tag));
+    // the compiler does not track these loads: every use of a record register it sees is of the value behind this wait
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]),
+                 "+v"(rec[7]), "+v"(rec[8]), "+v"(rec[9]), "+v"(rec[10]), "+v"(rec[11]));
     const unsigned long long m_reset = fin_mask[wv - kSplitEnvs / kWave];
     if (m_reset != 0ull) {   // wave-uniform: some env of the step wave we serve finished its episode
       float* wl = stage + (wv - kSplitEnvs / kWave) * (kWave * RDV_OBS_DIM);
       if (active && ((m_reset >> lane) & 1ull)) {
-        const uint32_t k_in = __float_as_uint(c5.y), episode_in = __float_as_uint(c5.w);
-        if (tag == episode_in + 1u && k_in >= 1u) {
+        if (copy_ok) {
           // copy path: the record is reset(seed, id, episode_in), state chunks in storage layout + observation
           if (__float_as_uint(rec[5].z) == kFlagsPending) {   // refilled by part (persistent kernels): the flags need the whole state
             float4 c[kChunks];

@@ -58,3 +58,5 @@ for rep in range(2):
     for label, lib in [("product", "-")] + [(os.path.basename(o), o) for o in others]:
         r = subprocess.run([sys.executable, "-c", CHILD, lib], capture_output=True, text=True, timeout=300)
         print(f"{label:10s} us per launch  {r.stdout.strip()}" + ("" if r.returncode == 0 else " FAILED " + r.stderr[-300:]), flush=True)
+        if r.returncode != 0:      # nothing more is started on a device behind a child that failed
+            sys.exit(1)

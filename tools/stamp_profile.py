@@ -4,6 +4,7 @@
 Builds a -DRDV_STAMPS copy of the library into tools/_stamps.so, runs a few hundred steps at N envs and prints, per role
 (step waves / service waves), the median shader-cycle counts between the stamps
   0 entry | 1 inputs staged | 2 step / next-state computed | 3 at the barrier | 4 past it | 5 | 6 | 7 end
+(service waves of the slot form: 1 chunk 5 and tag landed, record requests go out | 2 the records have landed — this build waits for them there)
 plus, from s_memrealtime (100 MHz, one counter for the whole chip): the shader clock, when waves enter and leave
 relative to the first wave of the launch, and the span of the launch as the waves see it.
 RDV_SPLIT_FORM=speculative|slots picks the form (csrc/rdv_step.h); in the slot form the second half of the grid is the refill workgroups;
