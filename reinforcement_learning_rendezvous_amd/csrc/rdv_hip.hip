@@ -35,8 +35,10 @@
 #include "rdv_general.h"
 #include "rdv_groups.h"
 #include "rdv_launch.h"
+#include "rdv_policy_sets.h"
 
 namespace rdv {
+static_assert(kGroupTile == kSetTile, "one rule (rdv_param_groups_check) and one table (rdv_host.h: tile_table) serve parameter groups and policy sets");
 
 // ---------------------------------------------------------------------------------------------------------------
 // host side
@@ -1113,13 +1115,11 @@ int rdv_set_param_groups(rdv_handle h, const RdvParams* params, const int64_t* s
   h->group_params.assign(params, params + n_groups);
   h->group_dev.resize((size_t)n_groups);
   h->group_start.assign((size_t)n_groups + 1, 0);
-  std::vector<int32_t> table((size_t)entries);
   for (int32_t g = 0; g < n_groups; ++g) {
     derive_block(h, params[g], h->group_dev[(size_t)g]);
     h->group_start[(size_t)g + 1] = h->group_start[(size_t)g] + sizes[g];
-    for (int64_t t = h->group_start[(size_t)g] / kGroupTile; t < (h->group_start[(size_t)g + 1] + kGroupTile - 1) / kGroupTile; ++t) table[(size_t)t] = g;
   }
-  for (int64_t t = tiles; t < entries; ++t) table[(size_t)t] = n_groups - 1;
+  const std::vector<int32_t> table = tile_table(sizes, n_groups, kGroupTile, entries);
   char* const base = static_cast<char*>(h->group_mem);
   // the copies leave pageable host memory that this call owns: ordered on `stream`, and waited for before it returns
   RDV_HIP(hipMemcpyAsync(base, h->group_dev.data(), (size_t)n_groups * sizeof(DevParams), hipMemcpyHostToDevice, s));

@@ -32,6 +32,13 @@ RDV_INTERNAL int fail(int code, const char* fmt, ...);
 
 static inline int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
 static inline bool misaligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+// THE tile table of parameter groups and policy sets (group g of n owns the next sizes[g] rows): tile t -> the owner of row t * tile; past the last tile: n - 1
+static inline std::vector<int32_t> tile_table(const int64_t* sizes, int32_t n, int64_t tile, int64_t entries) {
+  std::vector<int32_t> table((size_t)entries, n - 1);
+  for (int64_t g = 0, at = 0; g < n; at += sizes[g++])
+    for (int64_t t = at / tile; t < (at + sizes[g] + tile - 1) / tile && t < entries; ++t) table[(size_t)t] = (int32_t)g;
+  return table;
+}
 
 struct DeviceGuard {
   int prev = -1; bool switched = false;

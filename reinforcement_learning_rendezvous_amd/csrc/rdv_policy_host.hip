@@ -129,9 +129,10 @@ static int create_mlp_spec(const RdvMlpSpec* spec, const float* const* weights, 
 
 // ---- refreshing a handle's weights (a learner's optimiser step): the block is packed on the host as at creation and copied into the
 // handle's device allocation from a pinned buffer of the handle's own, on the caller's stream
-// block `member` of the handle <- packed, ordered on `stream`.  The pinned staging has one slot and one event per member, so refreshing
+// block `member` of the handle <- packed (of the handle's block size, or refused), ordered on `stream`.  The pinned staging has one slot and one event per member, so refreshing
 // all members back to back never waits on the host for another member's copy, only for the previous refresh of the same member.
 static int upload_block(rdv_policy p, const char* who, int32_t member, const std::vector<float>& packed, void* stream) {
+  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "%s: the packed block has %d floats, the handle's %d", who, (int)packed.size(), p->block_floats);
   DeviceGuard guard(p->device);
   hipStream_t s = static_cast<hipStream_t>(stream);
   if (int rc = refuse_in_capture(who, s, "(the staging buffer is reused by the next call)")) return rc;
@@ -159,22 +160,34 @@ static int refresh_member(rdv_policy p, const char* who, int32_t member, const f
   if (int rc = check_layers(kFinite, who, "layer %d", 0, kPolIn, p->spec, p->out_dim, weights, biases)) return rc;
   std::vector<float> packed;
   pack_block(p->shipped_arch, p->spec, p->out_dim, weights, biases, log_std, packed);
-  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "%s: the packed block has %d floats, the handle's %d", who, (int)packed.size(), p->block_floats);
   return upload_block(p, who, member, packed, stream);
 }
 
 // ---- policy sets (csrc/rdv_policy_sets.h): n_members networks of one spec, member g owning sizes[g] consecutive rows
+// *rows <- the sum of a set's sizes, judged by the rule of parameter groups (a size that is not positive or would overflow ends the sum, and is named against a count nothing exceeds)
+static int set_rows(const char* who, int32_t n_members, const int64_t* sizes, int64_t* rows) {
+  if (n_members < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_members = %d: a set has at least member 0", who, n_members);
+  constexpr int64_t kMostRows = INT64_MAX / 2;
+  *rows = 0;
+  for (int32_t g = 0; g < n_members && *rows >= 0; ++g) *rows = (sizes[g] > 0 && sizes[g] <= kMostRows - *rows) ? *rows + sizes[g] : -1;
+  return rdv_param_groups_check(*rows < 0 ? kMostRows : *rows, n_members, sizes);
+}
+// all <- the members' blocks back to back, each exactly the bytes of a stand-alone handle (pack_one(g, packed): member g's), all of one size
+template <class PackOne> static int pack_members(const char* who, int32_t n_members, PackOne pack_one, std::vector<float>& all) {
+  std::vector<float> packed;
+  for (int32_t g = 0; g < n_members; ++g) {
+    pack_one(g, packed);
+    if (g && packed.size() * (size_t)g != all.size()) return fail(RDV_ERR_HIP, "%s: member %d packs to %zu floats, member 0 to %zu", who, g, packed.size(), all.size() / (size_t)g);
+    all.insert(all.end(), packed.begin(), packed.end());
+  }
+  return RDV_OK;
+}
 static int create_set(const char* who, const RdvMlpSpec* spec, int32_t n_members, const int64_t* sizes, const float* const* const* weights,
                       const float* const* const* biases, const float* const* log_std, int out_dim, int device, rdv_policy* out) {
   if (!spec || !sizes || !weights || !biases || !out || (out_dim == kPolOut && !log_std)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
   if (int rc = rdv_mlp_spec_check(spec)) return rc;
-  if (n_members < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_members = %d: a set has at least member 0", who, n_members);
-  // the set's rows are the sum of the sizes; the rule of parameter groups judges them: positive, every one but the last a multiple of 256
-  // (a size that is not positive, or would overflow the sum, ends the sum: the check then names it against a count nothing exceeds)
-  constexpr int64_t kMostRows = INT64_MAX / 2;
   int64_t rows = 0;
-  for (int32_t g = 0; g < n_members && rows >= 0; ++g) rows = (sizes[g] > 0 && sizes[g] <= kMostRows - rows) ? rows + sizes[g] : -1;
-  if (int rc = rdv_param_groups_check(rows < 0 ? kMostRows : rows, n_members, sizes)) return rc;
+  if (int rc = set_rows(who, n_members, sizes, &rows)) return rc;
   for (int32_t g = 0; g < n_members; ++g) {
     if (!weights[g] || !biases[g] || (out_dim == kPolOut && !log_std[g])) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null weights, biases or log_std of member %d", who, g);
     if (int rc = check_layers(kNull | kFinite, who, "layer %d of member %d", g, kPolIn, *spec, out_dim, weights[g], biases[g])) return rc;
@@ -182,19 +195,10 @@ static int create_set(const char* who, const RdvMlpSpec* spec, int32_t n_members
   if (int rc = check_device(who, device)) return rc;
   DeviceGuard guard(device);
   const bool shipped = is_shipped(spec);
-  // member blocks: exactly the bytes of stand-alone handles; then (256-byte aligned) the tile table
-  std::vector<float> all, packed;
-  for (int32_t g = 0; g < n_members; ++g) {
-    pack_block(shipped, *spec, out_dim, weights[g], biases[g], out_dim == kPolOut ? log_std[g] : nullptr, packed);
-    if (g && packed.size() * (size_t)g != all.size()) return fail(RDV_ERR_HIP, "%s: member %d packs to %zu floats, member 0 to %zu", who, g, packed.size(), all.size() / (size_t)g);
-    all.insert(all.end(), packed.begin(), packed.end());
-  }
-  std::vector<int32_t> table((size_t)((rows + kSetTile - 1) / kSetTile));
-  int64_t at = 0;
-  for (int32_t g = 0; g < n_members; ++g) {
-    for (int64_t t = at / kSetTile; t < (at + sizes[g] + kSetTile - 1) / kSetTile; ++t) table[(size_t)t] = g;
-    at += sizes[g];
-  }
+  std::vector<float> all;
+  const auto pack_one = [&](int32_t g, std::vector<float>& packed) { pack_block(shipped, *spec, out_dim, weights[g], biases[g], out_dim == kPolOut ? log_std[g] : nullptr, packed); };
+  if (int rc = pack_members(who, n_members, pack_one, all)) return rc;
+  const std::vector<int32_t> table = tile_table(sizes, n_members, kSetTile, (rows + kSetTile - 1) / kSetTile);
   return make_policy(who, device, out_dim, *spec, shipped, n_members, rows, 0, all, &table, out);
 }
 
@@ -268,12 +272,8 @@ static int create_lstm_set(const char* who, const RdvLstmSpec* spec, int32_t n_m
   if (!spec || !sizes || !w_ih || !w_hh || !b_ih || !b_hh || !weights || !biases || !out || (out_dim == kPolOut && !log_std))
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null argument", who);
   if (int rc = rdv_lstm_spec_check(spec)) return rc;
-  if (n_members < 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n_members = %d: a set has at least member 0", who, n_members);
-  // the rule of parameter groups judges the sizes, as create_set's (a size that ends the sum is named against a count nothing exceeds)
-  constexpr int64_t kMostRows = INT64_MAX / 2;
   int64_t rows = 0;
-  for (int32_t g = 0; g < n_members && rows >= 0; ++g) rows = (sizes[g] > 0 && sizes[g] <= kMostRows - rows) ? rows + sizes[g] : -1;
-  if (int rc = rdv_param_groups_check(rows < 0 ? kMostRows : rows, n_members, sizes)) return rc;
+  if (int rc = set_rows(who, n_members, sizes, &rows)) return rc;
   if (rows > (int64_t)1 << 31) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the sizes sum to %lld rows, which must be in 1..2^31", who, (long long)rows);
   const int H = spec->hidden_size;
   char member[96];
@@ -284,19 +284,10 @@ static int create_lstm_set(const char* who, const RdvLstmSpec* spec, int32_t n_m
   }
   if (int rc = check_device(who, device)) return rc;
   DeviceGuard guard(device);
-  // member blocks: exactly the bytes pack_lstm_weights gives stand-alone handles; then (256-byte aligned) the tile table
-  std::vector<float> all, packed;
-  for (int32_t g = 0; g < n_members; ++g) {
-    pack_lstm_weights(H, spec->trunk, out_dim, w_ih[g], w_hh[g], b_ih[g], b_hh[g], weights[g], biases[g], out_dim == kPolOut ? log_std[g] : nullptr, packed);
-    if (g && packed.size() * (size_t)g != all.size()) return fail(RDV_ERR_HIP, "%s: member %d packs to %zu floats, member 0 to %zu", who, g, packed.size(), all.size() / (size_t)g);
-    all.insert(all.end(), packed.begin(), packed.end());
-  }
-  std::vector<int32_t> table((size_t)((rows + kSetTile - 1) / kSetTile));
-  int64_t at = 0;
-  for (int32_t g = 0; g < n_members; ++g) {
-    for (int64_t t = at / kSetTile; t < (at + sizes[g] + kSetTile - 1) / kSetTile; ++t) table[(size_t)t] = g;
-    at += sizes[g];
-  }
+  std::vector<float> all;
+  const auto pack_one = [&](int32_t g, std::vector<float>& packed) { pack_lstm_weights(H, spec->trunk, out_dim, w_ih[g], w_hh[g], b_ih[g], b_hh[g], weights[g], biases[g], out_dim == kPolOut ? log_std[g] : nullptr, packed); };
+  if (int rc = pack_members(who, n_members, pack_one, all)) return rc;
+  const std::vector<int32_t> table = tile_table(sizes, n_members, kSetTile, (rows + kSetTile - 1) / kSetTile);
   return make_policy(who, device, out_dim, spec->trunk, false, n_members, rows, H, all, &table, out);
 }
 // one recurrent network's host arrays checked against the handle's spec, packed, and uploaded as block `member`
@@ -305,7 +296,6 @@ static int refresh_lstm_member(rdv_policy p, const char* who, int32_t member, co
   if (int rc = check_lstm_arrays(who, p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std)) return rc;
   std::vector<float> packed;
   pack_lstm_weights(p->lstm_hidden, p->spec, p->out_dim, w_ih, w_hh, b_ih, b_hh, weights, biases, log_std, packed);
-  if ((int)packed.size() != p->block_floats) return fail(RDV_ERR_HIP, "%s: the packed block has %d floats, the handle's %d", who, (int)packed.size(), p->block_floats);
   return upload_block(p, who, member, packed, stream);
 }
 #define RDV_CHECK_LSTM(p, who) \
@@ -615,6 +605,12 @@ int rdv_ppo_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_sp
   return RDV_OK;
 }
 
+static int check_ppo_coefficients(const char* who, double clip_range, double ent_coef, double vf_coef) {
+  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: clip_range must be finite and positive (got %g)", who, clip_range);
+  if (!std::isfinite(ent_coef) || ent_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: ent_coef must be finite and not negative (got %g)", who, ent_coef);
+  if (!std::isfinite(vf_coef) || vf_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: vf_coef must be finite and not negative (got %g)", who, vf_coef);
+  return RDV_OK;
+}
 // the dynamic-LDS limit of the PPO kernels, plain and set forms, once per device (a host-side attribute: no stream work); the caller's
 // DeviceGuard holds `device`
 static int raise_ppo_lds_limit(int device) {
@@ -643,9 +639,7 @@ int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* row
   if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
   if (workspace_bytes < ppo_workspace_bytes(n))
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, n = %lld needs %lld (rdv_ppo_workspace_bytes)", who, (long long)workspace_bytes, (long long)n, (long long)ppo_workspace_bytes(n));
-  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: clip_range must be finite and positive (got %g)", who, clip_range);
-  if (!std::isfinite(ent_coef) || ent_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: ent_coef must be finite and not negative (got %g)", who, ent_coef);
-  if (!std::isfinite(vf_coef) || vf_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: vf_coef must be finite and not negative (got %g)", who, vf_coef);
+  if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
   RDV_CHECK_POLICY(actor);
   RDV_CHECK_POLICY(critic);
   const struct { rdv_policy p; const char* name; } nets[] = {{actor, "actor"}, {critic, "critic"}};
@@ -707,9 +701,7 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
   const int64_t need = ppo_set_table(P, counts_host, &L.table, nullptr, &L.max_workgroups);
   if (workspace_bytes < need)
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, these counts need %lld (rdv_ppo_set_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
-  if (!std::isfinite(clip_range) || clip_range <= 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: clip_range must be finite and positive (got %g)", who, clip_range);
-  if (!std::isfinite(ent_coef) || ent_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: ent_coef must be finite and not negative (got %g)", who, ent_coef);
-  if (!std::isfinite(vf_coef) || vf_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: vf_coef must be finite and not negative (got %g)", who, vf_coef);
+  if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
   RDV_CHECK_POLICY(actor_set);
   RDV_CHECK_POLICY(critic_set);
   const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};

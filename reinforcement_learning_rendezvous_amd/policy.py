@@ -124,14 +124,31 @@ def _ptrs(tensors):
     return (C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
 
 
+def _pptrs(lists):
+    """``const float* const* const*``: a C array of the addresses of one ``_ptrs`` array per list of tensors (which it keeps alive)."""
+    rows = [_ptrs(ts) for ts in lists]
+    out = (C.c_void_p * len(rows))(*[C.addressof(a) for a in rows])
+    out._rows = rows
+    return out
+
+
 class _HipHandles:
     """The HIP side that MlpPolicy, PolicySet and LstmPolicy share: the per-device handle caches ``_hip`` (actor) and ``_hip_critic``
     (device index -> rdv_policy, made on first use by the class's ``_create_handle(prefix, idx)``; prefix "l": actor, "v": critic),
-    ``close``, and the rdv_policy_act / rdv_policy_value calls of the feed-forward handles."""
+    ``close``, the weight refresh of the live handles, and the rdv_policy_act / rdv_policy_value calls of the feed-forward handles."""
 
     @staticmethod
     def _stream(device):
         return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+    def _refresh_handles(self, members=(None,)):
+        """THE loop of every ``update_weights``: each live actor and critic handle, on the current stream of its device, through the
+        class's ``_refresh(h, prefix, member, stream)`` (handle h <- the modules' trunk ``prefix``; ``member``: the block of a set handle
+        and the member whose modules are read, None for a policy of its own)."""
+        for prefix, handles in (("l", self._hip), ("v", self._hip_critic)):
+            for g in members:
+                for idx, h in handles.items():
+                    self._refresh(h, prefix, g, self._stream(torch.device("cuda", idx)))
 
     def _handle(self, prefix, device):
         device = torch.device(device)
@@ -177,6 +194,92 @@ class _HipHandles:
         N.check(N.lib().rdv_policy_value(self._critic_handle(flat.device), C.c_void_p(flat.data_ptr()), C.c_void_p(out.data_ptr()),
                                          flat.shape[0], self._stream(flat.device)))
         return out.reshape(obs.shape[:-1])
+
+
+class _Members:
+    """Set membership, which PolicySet and LstmPolicySet share: P member policies of ONE architecture, member g owning rows
+    ``group_slices[g]`` (the next ``group_sizes[g]``) of ``num_rows``, held in ``policies``; the container protocol, the ctypes member
+    tables of the set-create calls, and ``update_weights``.  The class gives ``_refresh_call``, the ABI function that the members'
+    ``_refresh`` reaches for a block of a set handle."""
+
+    def _init_members(self, name, member_type, fields, policies, group_sizes, num_rows=None):
+        """The validation at construction: ``name`` is the class's in the messages, ``fields`` what the members must agree in (the set
+        takes them from member 0).  The sizes: the rule and the messages of rdv_param_groups_check (params.group_tile_table)."""
+        from .params import group_tile_table
+        policies = list(policies)
+        if not policies:
+            raise ValueError(f"{name}: at least one member policy")
+        sizes = [int(x) for x in group_sizes]
+        if len(sizes) != len(policies):
+            raise ValueError(f"{name}: {len(policies)} policies but {len(sizes)} group sizes")
+        first = policies[0]
+        for g, p in enumerate(policies):
+            if not isinstance(p, member_type):
+                raise TypeError(f"{name}: member {g} is a {type(p).__name__}, not an {member_type.__name__}")
+            for what in fields:
+                if getattr(p, what) != getattr(first, what):
+                    raise ValueError(f"{name}: member {g} has {what} = {getattr(p, what)!r}, member 0 has {getattr(first, what)!r}: "
+                                     "the members of a set share one architecture")
+        rows = sum(sizes) if num_rows is None else int(num_rows)
+        group_tile_table(rows, sizes)
+        self.policies, self.group_sizes, self.num_rows = policies, sizes, rows
+        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        self.group_slices = [slice(int(starts[g]), int(starts[g + 1])) for g in range(len(sizes))]
+        for what in fields:
+            v = getattr(first, what)
+            setattr(self, what, list(v) if isinstance(v, list) else v)
+
+    def __len__(self):
+        return len(self.policies)
+
+    def __getitem__(self, g):
+        return self.policies[g]
+
+    def __iter__(self):
+        return iter(self.policies)
+
+    def to(self, *args, **kwargs):
+        """The member modules moved as ``torch.nn.Module.to`` moves them (the HIP handles live on the device of the rows they are given)."""
+        self.policies = [p.to(*args, **kwargs) for p in self.policies]
+        return self
+
+    def _member_tables(self, host):
+        """(P, sizes, weights, biases, log_std) as the set-create calls take them; ``host[g][-3:]``: member g's (weights, biases,
+        [log_std] or []) on the host, which the caller keeps alive until the call returns."""
+        sizes = (C.c_int64 * len(host))(*self.group_sizes)
+        return (len(host), sizes, _pptrs([m[-3] for m in host]), _pptrs([m[-2] for m in host]),
+                _ptrs([m[-1][0] for m in host]) if host[0][-1] else None)
+
+    def _refresh(self, h, prefix, member, stream):
+        self.policies[member]._refresh(h, prefix, member, stream)
+
+    def update_weights(self, member=None, weights=None):
+        """New weights for one member (``member`` = its index; ``weights``: a dict as the member's own ``update_weights`` takes, or None
+        to push the member module's current parameters) or for all members (``member`` None; ``weights``: None or a list of one dict or
+        None per member).  Dicts are loaded into the member modules first; then every live set handle is refreshed member by member
+        through rdv_policy_set_member_weights (a recurrent set: rdv_lstm_set_member_weights) on the current stream of its device:
+        launches already queued there use the old weights, later ones the new; the other members' blocks, and a recurrent set's state,
+        are not touched.  Not legal while the current stream is being captured (RdvError, nothing touched).  The noise key and the call
+        counter are unchanged."""
+        P = len(self.policies)
+        if (self._hip or self._hip_critic) and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            # refused before a module or a host copy is touched (either would invalidate the capture); the library refuses the same way
+            from . import _native as N
+            raise N.RdvError(-1, f"{self._refresh_call}: not legal inside a stream capture (the staging buffer is reused by the next call)")
+        if member is None:
+            todo = list(range(P))
+            per = weights if weights is not None else [None] * P
+            if isinstance(per, dict) or len(per) != P:
+                raise ValueError(f"update_weights: weights for all members is a list of {P} dicts (or None); pass member= for one")
+        else:
+            member = int(member)
+            if not 0 <= member < P:
+                raise IndexError(f"update_weights: member {member} of {P}")
+            todo, per = [member], {member: weights}
+        for g in todo:
+            if per[g] is not None:
+                self.policies[g]._load_weights(per[g])
+        self._refresh_handles(todo)
 
 
 class MlpPolicy(_HipHandles, torch.nn.Module):
@@ -345,16 +448,14 @@ class MlpPolicy(_HipHandles, torch.nn.Module):
         call counter and the noise key are unchanged."""
         if weights is not None:
             self._load_weights(weights)
-        if not (self._hip or self._hip_critic):
-            return
+        self._refresh_handles()
+
+    def _refresh(self, h, prefix, member, stream):
+        """rdv_policy_set_weights, or rdv_policy_set_member_weights as block ``member`` of a set handle: h <- this policy's trunk."""
         from . import _native as N
-        for prefix, handles in (("l", self._hip), ("v", self._hip_critic)):
-            if not handles:
-                continue
-            ws, bs, log_std = self._host_layers(prefix)
-            for idx, h in handles.items():
-                N.check(N.lib().rdv_policy_set_weights(h, _ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()) if log_std else None,
-                                                       self._stream(idx)))
+        ws, bs, log_std = self._host_layers(prefix)
+        args = (_ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()) if log_std else None, stream)
+        N.check(N.lib().rdv_policy_set_weights(h, *args) if member is None else N.lib().rdv_policy_set_member_weights(h, member, *args))
 
     def ppo_grad(self, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
         """The loss of SB3's ``PPO.train()`` for ONE minibatch and its gradients, written into ``.grad`` of this module's 13 parameters
@@ -396,7 +497,7 @@ class MlpPolicy(_HipHandles, torch.nn.Module):
         return self.act(obs, deterministic=deterministic).cpu().numpy(), state
 
 
-class PolicySet(_HipHandles):
+class PolicySet(_Members, _HipHandles):
     """P member policies of ONE architecture over one batch: member g owns the next ``group_sizes[g]`` rows, and one launch evaluates all
     members (include/rdv.h, "Policy sets"; csrc/rdv_policy_sets.h) — the network half of a sweep of P learners on one GPU, as a grouped
     ``RendezvousBatch`` is the environment half.  Row i of member g gets bit for bit what ``policies[g]`` alone computes for that row with
@@ -410,42 +511,15 @@ class PolicySet(_HipHandles):
     the call counter ``_calls``.  CUDA float32 input goes to the set kernels; CPU input or ``backend="torch"`` loops the members'
     PyTorch modules over their slices."""
 
+    _refresh_call = "rdv_policy_set_member_weights"
+
     def __init__(self, policies, group_sizes, num_rows=None, noise_seed=None, backend="auto"):
-        from .params import group_tile_table
-        policies = list(policies)
-        if not policies:
-            raise ValueError("PolicySet: at least one member policy")
-        sizes = [int(x) for x in group_sizes]
-        if len(sizes) != len(policies):
-            raise ValueError(f"PolicySet: {len(policies)} policies but {len(sizes)} group sizes")
-        first = policies[0]
-        for g, p in enumerate(policies):
-            if not isinstance(p, MlpPolicy):
-                raise TypeError(f"PolicySet: member {g} is a {type(p).__name__}, not an MlpPolicy")
-            for what in ("pi_arch", "vf_arch", "activation"):
-                if getattr(p, what) != getattr(first, what):
-                    raise ValueError(f"PolicySet: member {g} has {what} = {getattr(p, what)!r}, member 0 has {getattr(first, what)!r}: "
-                                     "the members of a set share one architecture")
-        rows = sum(sizes) if num_rows is None else int(num_rows)
-        group_tile_table(rows, sizes)
-        self.policies, self.group_sizes, self.num_rows = policies, sizes, rows
-        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        self.group_slices = [slice(int(starts[g]), int(starts[g + 1])) for g in range(len(sizes))]
+        self._init_members("PolicySet", MlpPolicy, ("pi_arch", "vf_arch", "activation"), policies, group_sizes, num_rows)
         self.backend = backend
-        self.noise_seed = int(first.noise_seed if noise_seed is None else noise_seed)
+        self.noise_seed = int(self.policies[0].noise_seed if noise_seed is None else noise_seed)
         self.noise_env_offset = 0
         self._calls = 0
         self._hip, self._hip_critic = {}, {}
-        self.pi_arch, self.vf_arch, self.activation = list(first.pi_arch), list(first.vf_arch), first.activation
-
-    def __len__(self):
-        return len(self.policies)
-
-    def __getitem__(self, g):
-        return self.policies[g]
-
-    def __iter__(self):
-        return iter(self.policies)
 
     @property
     def has_critic(self):
@@ -455,28 +529,17 @@ class PolicySet(_HipHandles):
     def shipped_arch(self):
         return self.policies[0].shipped_arch
 
-    def to(self, *args, **kwargs):
-        """The member modules moved as ``torch.nn.Module.to`` moves them (the HIP handles live on the device of the rows they are given)."""
-        self.policies = [p.to(*args, **kwargs) for p in self.policies]
-        return self
-
     # ------------------------------------------------------------------------------------------------ handles
     def _create_handle(self, prefix, idx):
         """rdv_policy_set_create / rdv_critic_set_create from the members' modules."""
         from . import _native as N
         arch = self.pi_arch if prefix == "l" else self.vf_arch
         host = [p._host_layers(prefix) for p in self.policies]        # kept alive until the call returns
-        wps = [_ptrs(ws) for ws, _, _ in host]
-        bps = [_ptrs(bs) for _, bs, _ in host]
-        P = len(host)
-        wpp = (C.c_void_p * P)(*[C.addressof(a) for a in wps])
-        bpp = (C.c_void_p * P)(*[C.addressof(a) for a in bps])
+        P, sizes, wpp, bpp, lsp = self._member_tables(host)
         spec = N.MlpSpec.make(arch, ACTIVATIONS[self.activation][0])
         N.check(N.lib().rdv_mlp_spec_check(C.byref(spec)))
-        sizes = (C.c_int64 * P)(*self.group_sizes)
         h = C.c_void_p()
         if prefix == "l":
-            lsp = _ptrs([ls[0] for _, _, ls in host])
             N.check(N.lib().rdv_policy_set_create(C.byref(spec), P, sizes, wpp, bpp, lsp, idx, C.byref(h)))
         else:
             N.check(N.lib().rdv_critic_set_create(C.byref(spec), P, sizes, wpp, bpp, idx, C.byref(h)))
@@ -553,41 +616,3 @@ class PolicySet(_HipHandles):
         ``ppo.ppo_grad`` member by member.  Returns a list of P dicts of 0-dim tensors (the scalars of ``ppo_grad``)."""
         from . import ppo
         return ppo.ppo_set_grads(self, buf, indices, clip_range, ent_coef, vf_coef, normalize_advantage, check)
-
-    # ------------------------------------------------------------------------------------------------ weights
-    def update_weights(self, member=None, weights=None):
-        """New weights for one member (``member`` = its index; ``weights``: a dict as ``MlpPolicy.update_weights`` takes, or None to
-        push the member module's current parameters) or for all members (``member`` None; ``weights``: None or a list of one dict or
-        None per member).  Dicts are loaded into the member modules first; then every live set handle is refreshed member by member
-        through rdv_policy_set_member_weights on the current stream of its device: launches already queued there use the old weights,
-        later ones the new, and the other members' blocks are not touched.  Not legal while the current stream is being captured
-        (RdvError, nothing touched).  The noise key and the call counter are unchanged."""
-        P = len(self.policies)
-        if (self._hip or self._hip_critic) and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            # refused before a module or a host copy is touched (either would invalidate the capture); the library refuses the same way
-            from . import _native as N
-            raise N.RdvError(-1, "rdv_policy_set_member_weights: not legal inside a stream capture (the staging buffer is reused by the next call)")
-        if member is None:
-            todo = list(range(P))
-            per = weights if weights is not None else [None] * P
-            if isinstance(per, dict) or len(per) != P:
-                raise ValueError(f"update_weights: weights for all members is a list of {P} dicts (or None); pass member= for one")
-        else:
-            member = int(member)
-            if not 0 <= member < P:
-                raise IndexError(f"update_weights: member {member} of {P}")
-            todo, per = [member], {member: weights}
-        for g in todo:
-            if per[g] is not None:
-                self.policies[g]._load_weights(per[g])
-        if not (self._hip or self._hip_critic):
-            return
-        from . import _native as N
-        for prefix, handles in (("l", self._hip), ("v", self._hip_critic)):
-            if not handles:
-                continue
-            for g in todo:
-                ws, bs, log_std = self.policies[g]._host_layers(prefix)
-                for idx, h in handles.items():
-                    N.check(N.lib().rdv_policy_set_member_weights(h, g, _ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()) if log_std else None,
-                                                                  self._stream(idx)))

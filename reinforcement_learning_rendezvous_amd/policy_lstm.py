@@ -25,7 +25,7 @@ import zipfile
 import numpy as np
 import torch
 
-from .policy import ACTIVATIONS, _HipHandles, _ptrs, _trunk_keys, infer_arch, parse_activation, parse_net_arch
+from .policy import ACTIVATIONS, _HipHandles, _Members, _ptrs, _trunk_keys, infer_arch, parse_activation, parse_net_arch
 
 LSTM_HIDDEN_SIZES = (32, 64, 128, 256)
 _LSTM_KEYS = ("weight_ih_l0", "weight_hh_l0", "bias_ih_l0", "bias_hh_l0")
@@ -450,19 +450,17 @@ class LstmPolicy(_LstmRows, torch.nn.Module):
         live HIP handle, through rdv_lstm_set_weights on the current stream of its device; the recurrent state is kept."""
         if weights is not None:
             self._load_weights(weights)
-        if not (self._hip or self._hip_critic):
-            return
+        self._refresh_handles()
+
+    def _refresh(self, h, prefix, member, stream):
+        """rdv_lstm_set_weights, or rdv_lstm_set_member_weights as block ``member`` of a set handle: h <- this policy's LSTM and trunk."""
         from . import _native as N
-        for prefix, table in (("l", self._hip), ("v", self._hip_critic)):
-            if not table:
-                continue
-            lstm, ws, bs, log_std = self._host_arrays(prefix)
-            for idx, h in table.items():
-                N.check(N.lib().rdv_lstm_set_weights(h, *[C.c_void_p(t.data_ptr()) for t in lstm], _ptrs(ws), _ptrs(bs),
-                                                     C.c_void_p(log_std[0].data_ptr()) if log_std else None, self._stream(torch.device("cuda", idx))))
+        lstm, ws, bs, log_std = self._host_arrays(prefix)
+        args = (*[C.c_void_p(t.data_ptr()) for t in lstm], _ptrs(ws), _ptrs(bs), C.c_void_p(log_std[0].data_ptr()) if log_std else None, stream)
+        N.check(N.lib().rdv_lstm_set_weights(h, *args) if member is None else N.lib().rdv_lstm_set_member_weights(h, member, *args))
 
 
-class LstmPolicySet(_LstmRows):
+class LstmPolicySet(_Members, _LstmRows):
     """P recurrent member policies of ONE architecture over one batch: member g owns the next ``group_sizes[g]`` rows, and one cell launch
     and one trunk launch per call evaluate all members (include/rdv.h, "Recurrent policy sets"; csrc/rdv_policy_lstm.h) — what
     ``PolicySet`` is for MLP learners.  Row i of member g gets bit for bit what a stand-alone ``LstmPolicy`` of member g's weights with
@@ -477,51 +475,19 @@ class LstmPolicySet(_LstmRows):
     the set's ranges and the batch's parameter groups are independent.  One noise key for the whole set (``seed``) and one call counter.
     CUDA float32 input goes to the set kernels; CPU input or ``backend="torch"`` loops the members' modules over their slices."""
 
+    _refresh_call = "rdv_lstm_set_member_weights"
+
     def __init__(self, policies, group_sizes, seed=0, backend="auto"):
-        from .params import group_tile_table
-        policies = list(policies)
-        if not policies:
-            raise ValueError("LstmPolicySet: at least one member policy")
-        sizes = [int(x) for x in group_sizes]
-        if len(sizes) != len(policies):
-            raise ValueError(f"LstmPolicySet: {len(policies)} policies but {len(sizes)} group sizes")
-        for g, p in enumerate(policies):
-            if not isinstance(p, LstmPolicy):
-                raise TypeError(f"LstmPolicySet: member {g} is a {type(p).__name__}, not an LstmPolicy")
-            for what in ("lstm_hidden_size", "pi_arch", "vf_arch", "activation"):
-                if getattr(p, what) != getattr(policies[0], what):
-                    raise ValueError(f"LstmPolicySet: member {g} has {what} = {getattr(p, what)!r}, member 0 has "
-                                     f"{getattr(policies[0], what)!r}: the members of a set share one architecture")
-        group_tile_table(sum(sizes), sizes)
-        first = policies[0]
-        self.policies, self.group_sizes = policies, sizes
-        self.n_rows = self.num_rows = sum(sizes)
-        starts = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
-        self.group_slices = [slice(int(starts[g]), int(starts[g + 1])) for g in range(len(sizes))]
+        self._init_members("LstmPolicySet", LstmPolicy, ("lstm_hidden_size", "pi_arch", "vf_arch", "activation"), policies, group_sizes)
+        self.n_rows = self.num_rows
         self.backend = backend
         self.noise_seed = int(seed)
         self.noise_env_offset = 0
         self._calls = 0
         self._hip, self._hip_critic = {}, {}        # device index -> rdv_policy handle of the set (each owns the state of all rows)
-        self.lstm_hidden_size = first.lstm_hidden_size
-        self.pi_arch, self.vf_arch, self.activation = list(first.pi_arch), list(first.vf_arch), first.activation
         self.has_critic = True
         self._state = {}
         self._pending = {"l": True, "v": True}
-
-    def __len__(self):
-        return len(self.policies)
-
-    def __getitem__(self, g):
-        return self.policies[g]
-
-    def __iter__(self):
-        return iter(self.policies)
-
-    def to(self, *args, **kwargs):
-        """The member modules moved as ``torch.nn.Module.to`` moves them (the HIP handles live on the device of the rows they are given)."""
-        self.policies = [p.to(*args, **kwargs) for p in self.policies]
-        return self
 
     # ------------------------------------------------------------------------------------------------ handles
     def _create_handle(self, prefix, idx):
@@ -531,15 +497,10 @@ class LstmPolicySet(_LstmRows):
         spec = N.LstmSpec.make(self.lstm_hidden_size, arch, ACTIVATIONS[self.activation][0])
         N.check(N.lib().rdv_lstm_spec_check(C.byref(spec)))
         host = [p._host_arrays(prefix) for p in self.policies]        # kept alive until the call returns
-        P = len(host)
+        P, sizes, wpp, bpp, lsp = self._member_tables(host)
         lstm = [_ptrs([m[0][k] for m in host]) for k in range(len(_LSTM_KEYS))]
-        wps, bps = [_ptrs(m[1]) for m in host], [_ptrs(m[2]) for m in host]
-        wpp = (C.c_void_p * P)(*[C.addressof(a) for a in wps])
-        bpp = (C.c_void_p * P)(*[C.addressof(a) for a in bps])
-        sizes = (C.c_int64 * P)(*self.group_sizes)
         h = C.c_void_p()
         if prefix == "l":
-            lsp = _ptrs([m[3][0] for m in host])
             N.check(N.lib().rdv_lstm_policy_set_create(C.byref(spec), P, sizes, *lstm, wpp, bpp, lsp, idx, C.byref(h)))
         else:
             N.check(N.lib().rdv_lstm_critic_set_create(C.byref(spec), P, sizes, *lstm, wpp, bpp, idx, C.byref(h)))
@@ -579,38 +540,3 @@ class LstmPolicySet(_LstmRows):
         """Not offered for a recurrent set: ``PolicySet.ppo_grads`` serves sets of the feed-forward shipped actor and critic."""
         from . import ppo
         return ppo.ppo_set_grads(self, *args, **kwargs)
-
-    def update_weights(self, member=None, weights=None):
-        """New weights for one member (``member`` = its index; ``weights``: a dict as ``LstmPolicy.update_weights`` takes, or None to
-        push the member module's current parameters) or for all members (``member`` None; ``weights``: None or a list of one dict or
-        None per member).  Dicts are loaded into the member modules first; then every live set handle is refreshed member by member
-        through rdv_lstm_set_member_weights on the current stream of its device: launches already queued there use the old weights,
-        later ones the new; the state and the other members' blocks are not touched.  Not legal while the current stream is being
-        captured (RdvError, nothing touched).  The noise key and the call counter are unchanged."""
-        P = len(self.policies)
-        if (self._hip or self._hip_critic) and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
-            from . import _native as N
-            raise N.RdvError(-1, "rdv_lstm_set_member_weights: not legal inside a stream capture (the staging buffer is reused by the next call)")
-        if member is None:
-            todo = list(range(P))
-            per = weights if weights is not None else [None] * P
-            if isinstance(per, dict) or len(per) != P:
-                raise ValueError(f"update_weights: weights for all members is a list of {P} dicts (or None); pass member= for one")
-        else:
-            member = int(member)
-            if not 0 <= member < P:
-                raise IndexError(f"update_weights: member {member} of {P}")
-            todo, per = [member], {member: weights}
-        for g in todo:
-            if per[g] is not None:
-                self.policies[g]._load_weights(per[g])
-        if not (self._hip or self._hip_critic):
-            return
-        from . import _native as N
-        for prefix, table in (("l", self._hip), ("v", self._hip_critic)):
-            for g in todo if table else []:
-                lstm, ws, bs, log_std = self.policies[g]._host_arrays(prefix)
-                for idx, h in table.items():
-                    N.check(N.lib().rdv_lstm_set_member_weights(h, g, *[C.c_void_p(t.data_ptr()) for t in lstm], _ptrs(ws), _ptrs(bs),
-                                                                C.c_void_p(log_std[0].data_ptr()) if log_std else None,
-                                                                self._stream(torch.device("cuda", idx))))

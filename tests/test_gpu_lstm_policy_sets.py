@@ -17,18 +17,17 @@ import pytest
 
 import policy_lstm_reference as L
 from helpers import gpu_batch, load_golden, to_numpy
+from policy_set_cases import (DEV, assert_columns_equal, close as _close, dev as _dev, env_sets, lstm_loop, short_episodes as _short_episodes,
+                              stagger as _stagger, starts as _starts, stream as _stream)
 from reinforcement_learning_rendezvous_amd import _native as N
 from reinforcement_learning_rendezvous_amd import monte_carlo
 from reinforcement_learning_rendezvous_amd._native import RdvError
-from reinforcement_learning_rendezvous_amd.params import make_params
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 LAYOUTS = {"256+256": (256, 256), "256+37": (256, 37), "512+256+1": (512, 256, 1)}
 SEED = 0xABCDEF12345
-COLUMNS = ("obs", "actions", "reward", "done", "log_prob", "last_obs", "values", "last_value", "advantages", "returns")
 
 
 @functools.lru_cache(maxsize=None)
@@ -46,30 +45,12 @@ def _member(H, arch, act, g, n_rows=None, offset=0):
     return p
 
 
-def _starts(sizes):
-    return [int(x) for x in np.concatenate([[0], np.cumsum(sizes)[:-1]])]
-
-
 def _set(H, sizes, arch=(64, 64), act="tanh", shift=0):
     """(the set, stand-alone twins of its members: n_rows = sizes[g], noise_env_offset = start_g, the same seed)"""
     from reinforcement_learning_rendezvous_amd import LstmPolicySet
     pset = LstmPolicySet([_member(H, arch, act, g + shift) for g in range(len(sizes))], sizes, seed=SEED)
     twins = [_member(H, arch, act, g + shift, n_rows=m, offset=s) for g, (m, s) in enumerate(zip(sizes, _starts(sizes)))]
     return pset, twins
-
-
-def _dev(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(DEV)
-
-
-def _close(*things):
-    for t in things:
-        for x in (t if isinstance(t, (list, tuple)) else [t]):
-            x.close()
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
 
 
 def _cat(parts):
@@ -226,40 +207,6 @@ def test_refresh_of_one_member_and_the_refusal_of_the_whole_set_call():
 
 
 # ---------------------------------------------------------------------------------------------------------------- 3
-def _short_episodes():
-    return make_params(dt=1.0, t_max=4.0)
-
-
-def _stagger(env):
-    """Four steps with zero actions, rows r % 5 > s reset behind step s: five episode ages, so that with episodes of 4 steps some envs,
-    never all, finish at every step of the rollouts below."""
-    n = env.num_envs
-    zero = torch.zeros((n, 6), dtype=torch.float32, device=DEV)
-    r = torch.arange(n, device=DEV)
-    for s in range(4):
-        env.step(zero)
-        env.reset(mask=(r % 5 > s))
-
-
-def _loop(env, pol, T, ctr0):
-    """The loop rdv_rollout is defined by, through the Python calls: rdv_lstm_act(flags) on the set + rdv_step."""
-    n = env.num_envs
-    rows = dict(obs=[], actions=[], reward=[], done=[], log_prob=[])
-    obs = env.obs.clone()
-    flags = pol._pending_flags("l", torch.device(DEV))
-    for t in range(T):
-        raw = torch.empty((n, 6), dtype=torch.float32, device=DEV)
-        lp = torch.empty((n,), dtype=torch.float32, device=DEV)
-        pol._calls = ctr0 + t
-        act = pol.act(obs, episode_start=flags, deterministic=False, env_id_offset=env.env_id_offset, raw_out=raw, log_prob_out=lp)
-        o, r, d = env.step(act)
-        rows["obs"].append(obs); rows["actions"].append(raw); rows["reward"].append(r.clone()); rows["done"].append(d.clone().to(torch.uint8)); rows["log_prob"].append(lp)
-        obs, flags = o.clone(), d.clone().to(torch.uint8)
-    out = {k: torch.stack(v) for k, v in rows.items()}
-    out["last_obs"] = obs
-    return out
-
-
 def test_rollout_is_the_set_act_plus_step_loop_and_continues():
     """512 envs x 8 steps, episodes of 4 steps, a set of (256, 256): rdv_rollout with the set against the explicit loop on a clone —
     every column and last_obs by equality; two rollouts of 4 steps equal one of 8 (the second goes on from the pending flags)."""
@@ -274,7 +221,7 @@ def test_rollout_is_the_set_act_plus_step_loop_and_continues():
     ro = envs[0].rollout(sets[0], T)
     assert envs[0].last_kernel.startswith("step_kernel") and sets[0]._calls == ctr0 + T
     assert int(ro["done"].sum()) >= n and int(ro["done"][:-1].sum()) > 0                  # episodes end inside the rollout
-    loop = _loop(envs[1], sets[1], T, ctr0)
+    loop, _ = lstm_loop(envs[1], sets[1], T, ctr0)
     for k in ("obs", "actions", "reward", "done", "log_prob", "last_obs"):
         assert torch.equal(ro[k].to(loop[k].dtype), loop[k]), k
     assert float(ro["lstm_state0"][0].abs().max()) == 0.0                                # every row was pending: step 0 starts from zero
@@ -297,16 +244,6 @@ def test_rollout_is_the_set_act_plus_step_loop_and_continues():
     _close(envs, sets)
 
 
-def _env_sets():
-    """two parameter sets that differ in dt, KOZ radius, nominal state and t_max; 6 and 8 steps to the time limit"""
-    return [
-        make_params(dt=1.0, t_max=6.0, koz_radius=5.0, rc0=np.array([0.5, -11.0, -0.3]), rc0_range=1.0, vc0_range=0.1,
-                    wt0=np.radians([0.0, 0.0, 1.5]), wt0_range=np.radians(3.0)),
-        make_params(dt=0.5, t_max=4.0, koz_radius=4.0, rc0=np.array([0.0, -2.2, 0.0]), rc0_range=1.5, vc0_range=0.05,
-                    qt0_range=np.radians(60.0), wt0=np.radians([1.0, -2.0, 0.5]), wt0_range=np.radians(1.0)),
-    ]
-
-
 def _collect_equals_separate(env, parts, pset, twins, what, T=16):
     """two collects in a row (the second continues from the pending flags of actor and critic) against separate batches and policies"""
     env.reset()
@@ -315,11 +252,7 @@ def _collect_equals_separate(env, parts, pset, twins, what, T=16):
         got = env.collect(pset, T, gamma=0.99, gae_lambda=0.95)
         want = [e.collect(p, T, gamma=0.99, gae_lambda=0.95) for e, p in zip(parts, twins)]
         assert int(got["done"].sum(dim=0).min()) >= 1, "every env resets at least once"
-        for name in COLUMNS:
-            axis = 0 if name in ("last_obs", "last_value") else 1
-            np.testing.assert_array_equal(to_numpy(got[name]), np.concatenate([to_numpy(w[name]) for w in want], axis=axis), err_msg=f"{name}, {what}, call {call}")
-        for i in range(2):
-            assert torch.equal(got["lstm_state0"][i], _cat(w["lstm_state0"][i] for w in want)), f"lstm_state0, {what}, call {call}"
+        assert_columns_equal(got, want, f"{what}, call {call}", extra=("lstm_state0",))
         assert pset._calls == T * (call + 1) and all(p._calls == T * (call + 1) for p in twins)
     _assert_state_equal(pset, twins, what)
 
@@ -329,8 +262,8 @@ def test_collect_on_a_grouped_batch_equals_separate_batches_and_policies():
     pset, twins = _set(64, sizes)
     for p in twins:
         p.noise_env_offset = 0                                   # the separate batches pass their env_id_offset = start_g themselves
-    env = gpu_batch(sum(sizes), params=_env_sets(), group_sizes=list(sizes), seed=11)
-    parts = [gpu_batch(m, params=p, env_id_offset=s, seed=11) for p, s, m in zip(_env_sets(), _starts(sizes), sizes)]
+    env = gpu_batch(sum(sizes), params=env_sets()[:2], group_sizes=list(sizes), seed=11)
+    parts = [gpu_batch(m, params=p, env_id_offset=s, seed=11) for p, s, m in zip(env_sets()[:2], _starts(sizes), sizes)]
     assert env.num_groups == 2
     _collect_equals_separate(env, parts, pset, twins, "grouped")
     _close(env, parts, pset, twins)
@@ -341,7 +274,7 @@ def test_collect_on_an_ungrouped_batch_of_549_envs_with_two_members():
     member has 293 rows (a tile of 37: one full wave and 5 rows)"""
     sizes = (256, 293)
     pset, twins = _set(32, sizes)
-    params = _env_sets()[1]
+    params = env_sets()[1]
     env = gpu_batch(sum(sizes), params=params, seed=12)
     parts = [gpu_batch(m, params=params, env_id_offset=s, seed=12) for s, m in zip(_starts(sizes), sizes)]
     assert env.num_groups == 0

@@ -18,11 +18,11 @@ import advantages_reference as AR
 import policy_lstm_reference as L
 import policy_reference as R
 from helpers import gpu_batch
+from policy_set_cases import DEV, dev as _dev, lstm_loop, short_episodes as _short_episodes, stagger as _stagger, stream as _stream
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
 
-DEV = "cuda:0"
 N_MAX = max(L.BATCH_SIZES)
 
 
@@ -31,14 +31,6 @@ def _policy(net, critic, n_rows, seed=0):
     p = LstmPolicy(L.weights_dict(net, critic), activation_fn=net["act"], n_rows=n_rows).to(DEV)
     p.noise_seed = seed
     return p
-
-
-def _dev(a, dtype=np.float32):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype)).to(DEV)
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream(torch.device(DEV)).cuda_stream)
 
 
 def _check_steps(tag, pol, kind, net, bud, obs, starts, n, worst, failures):
@@ -217,41 +209,6 @@ def test_update_weights_equals_a_fresh_policy_and_keeps_the_state():
 
 
 # ------------------------------------------------------------------------------------------------------ rollout and collect
-def _short_episodes():
-    from reinforcement_learning_rendezvous_amd.params import make_params
-    return make_params(dt=1.0, t_max=4.0)
-
-
-def _stagger(env):
-    """Four steps with zero actions, rows r % 5 > s reset behind step s: five episode ages, so that with episodes of 4 steps some
-    envs, never all, finish at every step of the rollouts below (60 or 120 of 300; counted on the CPU oracle)."""
-    n = env.num_envs
-    zero = torch.zeros((n, 6), dtype=torch.float32, device=DEV)
-    r = torch.arange(n, device=DEV)
-    for s in range(4):
-        env.step(zero)
-        env.reset(mask=(r % 5 > s))
-
-
-def _loop(env, pol, T, seed, ctr0):
-    """The loop rdv_rollout is defined by, through the Python calls: rdv_lstm_act(flags) + rdv_step."""
-    n = env.num_envs
-    rows = dict(obs=[], actions=[], reward=[], done=[], log_prob=[])
-    obs = env.obs.clone()
-    flags = pol._pending_flags("l", torch.device(DEV))
-    for t in range(T):
-        raw = torch.empty((n, 6), dtype=torch.float32, device=DEV)
-        lp = torch.empty((n,), dtype=torch.float32, device=DEV)
-        pol._calls = ctr0 + t
-        act = pol.act(obs, episode_start=flags, deterministic=False, env_id_offset=env.env_id_offset, raw_out=raw, log_prob_out=lp)
-        o, r, d = env.step(act)
-        rows["obs"].append(obs); rows["actions"].append(raw); rows["reward"].append(r.clone()); rows["done"].append(d.clone().to(torch.uint8)); rows["log_prob"].append(lp)
-        obs, flags = o.clone(), d.clone().to(torch.uint8)
-    out = {k: torch.stack(v) for k, v in rows.items()}
-    out["last_obs"] = obs
-    return out, flags
-
-
 def test_rollout_is_the_lstm_act_plus_step_loop_and_continues():
     """300 envs x 12 steps, episodes of 4 steps: rdv_rollout with an LSTM actor against the explicit loop — every column, last_obs, the
     final state and the pending flags by equality; two rollouts of 6 steps equal one of 12."""
@@ -267,7 +224,7 @@ def test_rollout_is_the_lstm_act_plus_step_loop_and_continues():
     ro = envs[0].rollout(pols[0], T)
     assert envs[0].last_kernel.startswith("step_kernel") and pols[0]._calls == ctr0 + T
     assert int(ro["done"].sum()) >= 2 * n and int(ro["done"][:-1].sum()) > 0            # episodes end inside the rollout
-    loop, last_flags = _loop(envs[1], pols[1], T, seed, ctr0)
+    loop, last_flags = lstm_loop(envs[1], pols[1], T, ctr0)
     for k in ("obs", "actions", "reward", "done", "log_prob", "last_obs"):
         assert torch.equal(ro[k].to(loop[k].dtype), loop[k]), k
     assert float(ro["lstm_state0"][0].abs().max()) == 0.0                                # every row was pending: step 0 starts from zero

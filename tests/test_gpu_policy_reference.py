@@ -11,7 +11,6 @@ useless for shift_lt_10 (A ~ 10), whose large weights do not chain.
 The reference clamps observations to +-63 first: the kernel's documented deviation from PyTorch (rdv.h; nothing changes
 inside the observation Box [-1, 1]).
 """
-import ctypes as C
 import math
 import time
 
@@ -20,11 +19,10 @@ import pytest
 
 import policy_reference as R
 from helpers import gpu_batch
+from policy_set_cases import DEV, act_via_abi, dev as _dev
 
 torch = pytest.importorskip("torch")
 pytestmark = pytest.mark.gpu
-
-DEV = "cuda:0"
 
 
 def _mlp_policy(net, critic=None, seed=0):
@@ -39,19 +37,13 @@ def _mlp_policy(net, critic=None, seed=0):
     return p
 
 
-def _act(pol, obs, deterministic=True, seed=0, counter=0, offset=0):
+def _act(pol, obs, **kw):
     """rdv_policy_act through the C ABI with every noise argument given explicitly."""
-    from reinforcement_learning_rendezvous_amd import _native as N
-    o = torch.from_numpy(np.ascontiguousarray(obs, np.float32)).to(DEV)
-    out = torch.full((o.shape[0], 6), 7.0, dtype=torch.float32, device=DEV)
-    N.check(N.lib().rdv_policy_act(pol._hip_handle(o.device), C.c_void_p(o.data_ptr()), C.c_void_p(out.data_ptr()), o.shape[0],
-                                   int(deterministic), C.c_uint64(seed), C.c_uint64(counter), C.c_uint64(offset),
-                                   C.c_void_p(torch.cuda.current_stream(o.device).cuda_stream)))
-    return out.cpu().numpy()
+    return act_via_abi(pol._hip_handle(torch.device(DEV)), obs, **kw).cpu().numpy()
 
 
 def _value(pol, obs):
-    return pol.value(torch.from_numpy(np.ascontiguousarray(obs, np.float32)).to(DEV)).cpu().numpy()
+    return pol.value(_dev(obs)).cpu().numpy()
 
 
 def _bounds(net, x):
