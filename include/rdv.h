@@ -619,7 +619,10 @@ int rdv_policy_set_weights(rdv_policy p, const float* const* weights_host, const
  *     rdv_policy_act with deterministic = 1 before the clip: the forward half is the device code of those kernels.
  *   - Accuracy: the backward products are brought to fp32 level as the forward ones (two fp16 terms per operand, three MFMAs), the sums
  *     over rows are fp32; tests/test_gpu_ppo_grad.py holds every gradient tensor to a small multiple of the error of PyTorch's own float32
- *     autograd against an fp64 reference.
+ *     autograd against an fp64 reference: err = max|G - G64| / max|G64| <= 16 max(e32, 2^-23).  Measured up to n = 1,048,576
+ *     (profiles/ppo_grad_accuracy.csv): the largest err / max(e32, 2^-23) of a gradient tensor is 4.96 up to n = 549, 2.25 at n = 4,096,
+ *     4.72 at n = 65,536 and 13.3 at n = 1,048,576.  The sum over the n / 256 workgroups is a float32 sum in index order, and its share
+ *     grows with their number; beyond 1,048,576 samples in one call the rule has not been measured and is not claimed.
  *   - Determinism: the same inputs give the same bits in every output, eager or replayed from a captured graph.  No floating-point
  *     atomic: per-wave sums are added in wave order, per-workgroup sums go to the workspace and are added in index order.
  *   - Enqueued on `stream`, legal inside a stream capture, no allocation, no synchronisation.  The workspace is the caller's: at least

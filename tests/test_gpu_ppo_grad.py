@@ -20,8 +20,19 @@ of two at least twice the largest err / max(e32, 2^-23) of profiles/ppo_grad_acc
     3.8e-7 .. 8.1e-5 across the shapes).  DESIGN.md, "PPO minibatch gradients", has the reasoning; the gradients are held to C_GRAD.
 A wrong fragment index, a transposed operand or a dropped 1/n moves err to order 1, some 10^5 x e32 (tests/test_ppo_grad.py shows the rule
 separating three wrong restatements at C = 128).
+
+Beyond that box, under the same rule and constants (the table has their rows too: 612 in all):
+  * large minibatches of a 65,536-row case by the same recipe: n = 4,096 and 65,536 with rows in order, n = 1,048,576 as the first 4,096
+    rows 256 times each.  Largest ratio of a gradient tensor 2.25, 4.72 and 13.3 (critic.w2, random member); of a scalar 1.65, 2.57 and
+    1.65.  The float32 sum over the n / 256 workgroups is what grows; the rule is measured, and claimed, up to 1,048,576 samples;
+  * the corners of the wave scale on the random member: no policy gradient in a minibatch, in workgroups and waves beside live ones, one
+    live row in a wave, an exact critic, advantages over ten decades, exact homogeneity in 2^k;
+  * the "clamp" member: the +-63 clamp of the observations in the backward pass;
+  * the header's NaN rule, one column at a time;
+  * the first on-policy minibatch of a real rollout (test_one_epoch_end_to_end).
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -32,7 +43,7 @@ import ppo_reference as P
 from reinforcement_learning_rendezvous_amd import _native as N
 from reinforcement_learning_rendezvous_amd.policy import MlpPolicy, PolicySet
 from reinforcement_learning_rendezvous_amd.policy_lstm import LstmPolicy
-from reinforcement_learning_rendezvous_amd.ppo import ppo_minibatches
+from reinforcement_learning_rendezvous_amd.ppo import normalize_advantages, ppo_minibatches
 
 pytestmark = pytest.mark.gpu
 
@@ -53,8 +64,7 @@ def members():
     for m in P.MEMBERS:
         case = P.make_case(m)
         pol = make_policy(case["actor"], case["critic"])
-        cols = {k: torch.from_numpy(np.array(case[k])).to(DEV) for k in ("obs", "actions", "old_log_prob", "advantages", "returns")}
-        out[m] = (case, pol, cols)
+        out[m] = (case, pol, device_columns(case))
     yield out
     for _, pol, _ in out.values():
         pol.close()
@@ -90,6 +100,21 @@ def call(pol, cols, n, idx=None, eps=P.EPS, ent=ENT, vf=VF, actor=None, critic=N
                 raw=(ag, cg, sc, lp, val))
 
 
+def device_columns(case):
+    return {k: torch.from_numpy(np.array(case[k])).to(DEV) for k in P.COLUMNS}
+
+
+def compare(got, ref, g32, s32):
+    """rows (name, err, e32) of the accuracy rule: the 13 gradient tensors and five scalars of one call against the fp64 reference, beside
+    the float32 autograd yardstick."""
+    rows = [(name, P.rel_err(g, w), P.rel_err(y, w)) for name, g, w, y in zip(P.NAMES, got["grads"], ref["grads"], g32)]
+    for name in P.SCALARS:
+        if name != "clip_fraction":
+            w = ref["scalars"][name]
+            rows.append((name, abs(got["scalars"][name] - w) / abs(w), abs(s32[name] - w) / abs(w)))
+    return rows
+
+
 def measure(case, pol, cols, n, indexed):
     """One shape: the call, the fp64 reference, the float32 autograd yardstick -> rows (name, err, e32) and the pieces the test asserts on."""
     idx = P.index_vector(n) if indexed else None
@@ -97,18 +122,26 @@ def measure(case, pol, cols, n, indexed):
     got = call(pol, cols, n, idx)
     ref = P.analytic64(case["actor"], case["critic"], *mb, eps=P.EPS, ent_coef=ENT, vf_coef=VF)
     g32, s32 = P.autograd(case["actor"], case["critic"], *mb, eps=P.EPS, ent_coef=ENT, vf_coef=VF, dtype="float32")
-    rows = [(name, P.rel_err(g, w), P.rel_err(y, w)) for name, g, w, y in zip(P.NAMES, got["grads"], ref["grads"], g32)]
-    for name in P.SCALARS:
-        if name != "clip_fraction":
-            w = ref["scalars"][name]
-            rows.append((name, abs(got["scalars"][name] - w) / abs(w), abs(s32[name] - w) / abs(w)))
-    return rows, got, ref, mb
+    return compare(got, ref, g32, s32), got, ref, mb
 
 
-@pytest.mark.parametrize("indexed", [False, True], ids=["rows", "indexed"])
-@pytest.mark.parametrize("n", P.SHAPES)
-@pytest.mark.parametrize("member", sorted(P.MEMBERS))
-def test_loss_and_gradients_match_the_fp64_reference(members, member, n, indexed):
+def assert_rule(label, rows, skip=()):
+    """The accuracy rule on the rows of ``compare``: err <= C max(e32, 2^-23), C_GRAD for a gradient tensor, C_BOUND for a scalar."""
+    worst = []
+    for name, err, e32 in rows:
+        bound = max(e32, FLOOR)
+        print(f"{label} {name}: err {err:.3e} e32 {e32:.3e} ratio {err / bound:.3f}")
+        if name not in skip and not err <= (C_GRAD if "." in name else C_BOUND) * bound:
+            worst.append((name, err, e32))
+    assert not worst, worst
+
+
+def assert_clip_count(got, ref, n):
+    count = got["scalars"]["clip_fraction"] * n                     # (the scalar is count / n rounded to float32)
+    assert round(count) == round(ref["scalars"]["clip_fraction"] * n) and abs(count - round(count)) < 1e-3
+
+
+def check_shape(members, member, n, indexed):
     case, pol, cols = members[member]
     rows, got, ref, mb = measure(case, pol, cols, n, indexed)
     obs = torch.from_numpy(np.array(mb[0])).to(DEV)
@@ -118,15 +151,214 @@ def test_loss_and_gradients_match_the_fp64_reference(members, member, n, indexed
     print(f"{member} n={n} indexed={indexed}: log_prob err/budget max {float((lp_err / lp_tol).max()):.3f}")
     assert (lp_err <= lp_tol).all(), float((lp_err / lp_tol).max())
     # 2. the 13 gradients and 3. five scalars: err <= C max(e32, 2^-23); clip_fraction n: the reference's count exactly
-    worst = []
-    for name, err, e32 in rows:
-        bound = max(e32, FLOOR)
-        print(f"{member} n={n} indexed={indexed} {name}: err {err:.3e} e32 {e32:.3e} ratio {err / bound:.3f}")
-        if not err <= (C_GRAD if "." in name else C_BOUND) * bound:
-            worst.append((name, err, e32))
-    assert not worst, worst
-    count = got["scalars"]["clip_fraction"] * n                     # (the scalar is count / n rounded to float32)
-    assert round(count) == round(ref["scalars"]["clip_fraction"] * n) and abs(count - round(count)) < 1e-3
+    assert_rule(f"{member} n={n} indexed={indexed}", rows)
+    assert_clip_count(got, ref, n)
+
+
+@pytest.mark.parametrize("indexed", [False, True], ids=["rows", "indexed"])
+@pytest.mark.parametrize("n", P.SHAPES)
+@pytest.mark.parametrize("member", P.BASE_MEMBERS)
+def test_loss_and_gradients_match_the_fp64_reference(members, member, n, indexed):
+    check_shape(members, member, n, indexed)
+
+
+# ---------------------------------------------------------------------------------------------------------- large minibatches
+@pytest.fixture(scope="module")
+def big():
+    """member -> (the 65,536-row case, its columns on the device); made once, left unchanged."""
+    return {m: (P.big_case(m), device_columns(P.big_case(m))) for m in P.BASE_MEMBERS}
+
+
+@functools.lru_cache(maxsize=None)
+def big_reference(member, n):
+    """(fp64 reference, float32 autograd gradients and scalars) of the first n rows of the big case; computed once, shared, unchanged."""
+    case = P.big_case(member)
+    mb = P.take(case, n)
+    ref = P.analytic64(case["actor"], case["critic"], *mb, eps=P.EPS, ent_coef=ENT, vf_coef=VF)
+    return (ref,) + tuple(P.autograd(case["actor"], case["critic"], *mb, eps=P.EPS, ent_coef=ENT, vf_coef=VF, dtype="float32"))
+
+
+def measure_big(member, pol, cols, n):
+    """A large shape of a member -> (rows of ``compare``, the call's outputs, the reference, the index vector or None).  n = 4,096 or
+    65,536: rows in order.  n = 1,048,576: ``repeated_index_vector``, against the reference of the 4,096 rows it repeats."""
+    idx = P.repeated_index_vector() if n == P.REPEAT_BASE * P.REPEAT_TIMES else None
+    assert idx is not None or n in P.BIG_SHAPES
+    ref, g32, s32 = big_reference(member, P.REPEAT_BASE if idx is not None else n)
+    got = call(pol, cols, n, idx)
+    return compare(got, ref, g32, s32), got, ref, idx
+
+
+def check_big(members, big, member, n):
+    case, cols = big[member]
+    pol = members[member][1]
+    rows, got, ref, idx = measure_big(member, pol, cols, n)
+    sel = slice(0, n) if idx is None else idx
+    base = n if idx is None else P.REPEAT_BASE
+    assert np.array_equal(got["values"], pol.value(cols["obs"][:base]).cpu().numpy()[sel])
+    lp_tol = P.log_prob_budget(case["actor"], case["obs"][:base], case["actions"][:base])[sel]
+    lp_err = np.abs(got["log_prob"].astype(np.float64) - ref["log_prob"][sel])
+    print(f"{member} n={n}: log_prob err/budget max {float((lp_err / lp_tol).max()):.3f}")
+    assert (lp_err <= lp_tol).all(), float((lp_err / lp_tol).max())
+    assert_rule(f"{member} n={n} indexed={int(idx is not None)}", rows)
+    assert_clip_count(got, ref, n)
+
+
+@pytest.mark.parametrize("n", P.BIG_SHAPES)
+@pytest.mark.parametrize("member", P.BASE_MEMBERS)
+def test_large_minibatches_match_the_fp64_reference(members, big, member, n):
+    """n = 4,096 and 65,536 (16 and 256 workgroups), rows in order, of the 65,536-row case: the unchanged rule against the fp64 reference
+    and float32 autograd of the same rows.  The sum over workgroups is what grows with n here; PyTorch's own sums are blocked, so e32 does
+    not."""
+    check_big(members, big, member, n)
+
+
+@pytest.mark.parametrize("member", P.BASE_MEMBERS)
+def test_a_million_samples_match_the_minibatch_they_repeat(members, big, member):
+    """n = 1,048,576 (4,096 workgroups, a workspace of 182 MB): the index vector holds each of the big case's first 4,096 rows 256 times,
+    shuffled with a fixed seed so that the workgroups differ.  Every sample has the same multiplicity (asserted on the CPU in
+    tests/test_ppo_grad.py), so in exact arithmetic the loss, every gradient and every scalar equal those of the 4,096-row minibatch: its
+    fp64 reference is the reference here, and its float32 autograd is e32.  A million-row call is checked at the CPU cost of 4,096 rows."""
+    check_big(members, big, member, P.REPEAT_BASE * P.REPEAT_TIMES)
+
+
+# ---------------------------------------------------------------------------------------------------------- degenerate error tiles
+def reference_pair(case, mb):
+    ref = P.analytic64(case["actor"], case["critic"], *mb, eps=P.EPS, ent_coef=ENT, vf_coef=VF)
+    return (ref,) + tuple(P.autograd(case["actor"], case["critic"], *mb, eps=P.EPS, ent_coef=ENT, vf_coef=VF, dtype="float32"))
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.int32)
+
+
+@pytest.mark.parametrize("n", [1, 32, 549])
+def test_a_minibatch_without_policy_gradient(members, n):
+    """Every row on the zero-gradient side of the clip (``ppo_reference.zero_policy_gradient``), the state of late PPO epochs: the head's
+    error tile of every actor wave is all zeros (the wave scale's all-zero case).  The six weight and bias gradients of the actor are
+    zero and d log_std is -ent_coef, by equality; clip_fraction is 1; policy_loss and the critic's gradients are within the rule."""
+    base, pol, _ = members["random"]
+    case = P.zero_policy_gradient(base)
+    got = call(pol, device_columns(case), n)
+    ref, g32, s32 = reference_pair(case, P.take(case, n))
+    for name, g in zip(P.NAMES[:6], got["grads"]):
+        assert np.all(g == 0.0), name                                # (-0.0 counts)
+    assert np.array_equal(bits(got["grads"][6]), bits(np.full(6, -np.float32(ENT))))
+    assert got["scalars"]["clip_fraction"] * n == n
+    with np.errstate(invalid="ignore"):                              # (the reference's actor tensors are all zeros: no relative error)
+        rows = [r for r in compare(got, ref, g32, s32) if r[0] in P.NAMES[7:] + ("policy_loss",)]
+    assert_rule(f"zero policy gradient n={n}", rows)
+
+
+def test_dead_waves_beside_live_ones_and_a_lone_live_row(members):
+    """n = 549: waves 0, 2, 5 of workgroup 0 and all of workgroup 1 have no policy gradient, and the last, partial wave keeps one live
+    row, its last (``ppo_reference.dead_wave_mask``): all-zero error tiles are added to live ones within a workgroup and across
+    workgroups, and one wave's scale comes from a single lane."""
+    base, pol, _ = members["random"]
+    case = P.zero_policy_gradient(base, P.dead_wave_mask())
+    got = call(pol, device_columns(case), P.DEAD_N)
+    ref, g32, s32 = reference_pair(case, P.take(case, P.DEAD_N))
+    assert_rule("dead waves n=549", compare(got, ref, g32, s32))
+    assert_clip_count(got, ref, P.DEAD_N)
+
+
+def test_a_critic_that_fits_exactly(members):
+    """The ``values`` a first call writes are the ``returns`` of a second: every critic gradient and value_loss are exactly zero, loss is
+    float32(policy_loss + ent_coef entropy_loss) of the call's own scalars to one unit in the last place (the kernel adds them in
+    double before it rounds), and the actor's outputs are the first call's bits."""
+    _, pol, cols = members["random"]
+    n = 549
+    first = call(pol, cols, n)
+    returns = cols["returns"].clone()
+    returns[:n] = first["raw"][4]
+    second = call(pol, dict(cols, returns=returns), n)
+    assert all(np.all(g == 0.0) for g in second["grads"][7:]) and second["scalars"]["value_loss"] == 0.0
+    sc = second["raw"][2].cpu().numpy()
+    want = np.float32(np.float64(sc[1]) + np.float64(np.float32(ENT)) * np.float64(sc[3]))
+    assert abs(np.float64(sc[0]) - np.float64(want)) <= np.spacing(np.abs(want)), (sc[0], want)
+    assert torch.equal(first["raw"][0].view(torch.int32), second["raw"][0].view(torch.int32))
+    assert np.array_equal(bits(first["log_prob"]), bits(second["log_prob"])) and np.array_equal(bits(first["values"]), bits(second["values"]))
+    assert all(first["scalars"][k] == second["scalars"][k] for k in ("policy_loss", "entropy_loss", "approx_kl", "clip_fraction"))
+    assert any(np.abs(g).max() > 0.0 for g in first["grads"][7:])
+
+
+def test_advantages_over_ten_decades(members):
+    """Advantages sign 10^U(-6, 4) through the C ABI (the call never normalises), n = 549, under the unchanged rule.  The rule is relative
+    to max|G|, so rows below the floor do not matter; a wave scale taken from the wrong lane or a saturated fp16 term does."""
+    base, pol, _ = members["random"]
+    case = P.wide_advantages(base)
+    a = np.abs(case["advantages"][:549])
+    assert a.min() < 1e-5 and a.max() > 1e3
+    got = call(pol, device_columns(case), 549)
+    ref, g32, s32 = reference_pair(case, P.take(case, 549))
+    assert_rule("wide advantages n=549", compare(got, ref, g32, s32))
+    assert_clip_count(got, ref, 549)
+
+
+@pytest.mark.parametrize("k", [32, -32, -64])
+def test_the_call_is_exactly_homogeneous_in_the_advantages(members, k):
+    """A wave's scale comes from the exponent of its largest |delta| alone, so scaling every error by 2^k changes no rounding: with
+    advantages 2^k, vf_coef 2^k and ent_coef = 0 all 13 gradient tensors, policy_loss and loss are 2^k times the base call's BIT FOR BIT,
+    and value_loss, approx_kl, clip_fraction, entropy_loss, log_prob and values are unchanged.  An invariant of IEEE arithmetic for any
+    correct implementation of the scheme, not a comparison with a recording.  k = +-32 keep every scale far from the limits of the
+    exponent field; k = -64 brings the scales to 2^73 and beyond (errors near 2^-64), the upper part of the range the scale's exponent
+    is clamped to, [2, 253] — still exact.  Entries whose base magnitude is below 2^(|k| - 122) are exempt (scaled down they would
+    leave the normal range): fewer than 0.1 % of the entries; none are expected."""
+    _, pol, cols = members["random"]
+    n, f = 549, 2.0 ** k
+    base = call(pol, cols, n, ent=0.0, vf=VF)
+    scaled = call(pol, dict(cols, advantages=cols["advantages"] * f), n, ent=0.0, vf=VF * f)
+    tiny, total = 0, 0
+    for name, b, s in list(zip(P.NAMES, base["grads"], scaled["grads"])) + [(q, np.array([base["scalars"][q]]), np.array([scaled["scalars"][q]]))
+                                                                             for q in ("policy_loss", "loss")]:
+        live = np.abs(b) >= 2.0 ** (abs(k) - 122)
+        tiny, total = tiny + int((~live).sum()), total + b.size
+        assert np.array_equal(bits(s[live]), bits(b[live] * f)), name
+        assert np.all(s[b == 0.0] == 0.0), name
+    print(f"k={k}: {tiny} of {total} entries exempt")
+    assert tiny < 1e-3 * total
+    for q in ("value_loss", "approx_kl", "clip_fraction", "entropy_loss"):
+        assert bits(base["scalars"][q]) == bits(scaled["scalars"][q]), q
+    assert np.array_equal(bits(base["log_prob"]), bits(scaled["log_prob"])) and np.array_equal(bits(base["values"]), bits(scaled["values"]))
+
+
+# ---------------------------------------------------------------------------------------------------------- the clamp, the NaN rule
+@pytest.mark.parametrize("indexed", [False, True], ids=["rows", "indexed"])
+@pytest.mark.parametrize("n", [257, 549])
+def test_the_backward_pass_differentiates_the_clamped_observations(members, n, indexed):
+    """The "clamp" member: every eighth row has obs[3] in {62.9, 63, 64, 1e4, -64, -1e4} and the first layers read that feature through a
+    weight of 2^-7 its size, so those rows stay live and column 3 of dW1 — x = +-63 against |x| < 1 elsewhere — holds its largest
+    entries.  dW1 is the product with the CLAMPED rows (include/rdv.h: what is differentiated is the function the forward kernels
+    compute); tests/test_ppo_grad.py shows that the rule tells a product with the rows as given by more than 100 bounds."""
+    check_shape(members, "clamp", n, indexed)
+
+
+@pytest.mark.parametrize("column", P.COLUMNS)
+def test_a_nan_in_one_row_reaches_the_gradients_and_the_scalars(members, column):
+    """include/rdv.h: "a NaN in any sampled row (observation, action, old_log_prob, advantage, return) reaches the gradients and the
+    scalars".  n = 549, one NaN in row 540 (the last, partial wave of the last workgroup; component 3 of obs and actions).  Which
+    gradient tensors are NaN throughout and which scalars are NaN is the fp64 reference's pattern (``ppo_reference.NAN_RULE``, pinned on
+    the CPU); everything else is finite; a net whose inputs are clean keeps the bits of the clean call, and so do log_prob and values of
+    every other row."""
+    base, pol, cols = members["random"]
+    n, row = 549, P.NAN_ROW
+    case = P.with_nan(base, column, row)
+    clean = call(pol, cols, n)
+    got = call(pol, device_columns(case), n)
+    ref = P.analytic64(case["actor"], case["critic"], *P.take(case, n), eps=P.EPS, ent_coef=ENT, vf_coef=VF)
+    want = P.nan_pattern(ref["grads"], ref["scalars"])
+    assert want == (tuple(P.NAN_RULE[column][0]), tuple(P.NAN_RULE[column][1]))
+    assert P.nan_pattern(got["grads"], got["scalars"]) == want
+    for net, names in ((0, P.NAMES[:7]), (1, P.NAMES[7:])):
+        if not set(names) & set(want[0]):
+            assert torch.equal(got["raw"][net].view(torch.int32), clean["raw"][net].view(torch.int32)), names
+    others = np.arange(n) != row
+    for key in ("log_prob", "values"):
+        assert np.array_equal(bits(got[key][others]), bits(clean[key][others])), key
+        assert bool(np.isnan(got[key][row])) == bool(np.isnan(ref[key][row])), key
+    for q in ("entropy_loss", "clip_fraction"):
+        assert np.isfinite(got["scalars"][q])
+    finite = [q for q in P.SCALARS if q not in want[1]]
+    assert all(np.isfinite(got["scalars"][q]) for q in finite)
 
 
 def test_raw_advantage_of_a_lone_lane_through_ppo_grad(members):
@@ -211,9 +443,48 @@ def test_update_weights_then_ppo_grad_differentiates_the_new_weights(members):
         pol.close()
 
 
+def check_on_policy_minibatch(pol, buf, idx):
+    """Real rollout rows, before any optimiser step: real observations, the shipped actor's saturating samples, its sigma of 0.05 .. 0.1,
+    GAE advantages normalised in the Python layer.  The normalised advantages the call used are read back from the policy's flat column
+    and fed, with the rows' other columns, to the fp64 reference and to float32 autograd over the weights of mlp_policy.npz.
+    Gradients and value_loss: the unchanged rule.  On-policy every ratio is 1 +- the log_prob error and the normalised advantages have
+    zero mean, so policy_loss, approx_kl and loss are pure cancellations and a relative rule says nothing about them; they are held to
+    absolute bounds from the reference alone, with b_i = ppo_reference.log_prob_budget of row i (what log_prob may be off by) and 2^-22
+    for the float32 evaluation of exp, the product and the sums:
+        |policy_loss - policy_loss64| <= mean_i |A_i| (b_i + 2^-22),   |approx_kl| <= max_i b_i + 2^-22,
+        |loss - loss64| <= the policy_loss bound + vf_coef times the value_loss bound of the rule.
+    clip_fraction is 0 exactly."""
+    clip, ent, vf = 0.2, 0.0, 0.5
+    stats = pol.ppo_grad(buf, idx, clip_range=clip, ent_coef=ent, vf_coef=vf, normalize_advantage=True)
+    used = pol._ppo[buf["obs"].device]["adv"][idx]
+    assert torch.allclose(used, normalize_advantages(buf["advantages"].flatten()[idx]), rtol=1e-6, atol=0.0)
+    rows_of = lambda k, *tail: buf[k].reshape(-1, *tail)[idx].cpu().numpy()
+    mb = (rows_of("obs", 17), rows_of("actions", 6), rows_of("log_prob"), used.cpu().numpy(), rows_of("returns"))
+    actor, critic = P.golden_nets()
+    ref = P.analytic64(actor, critic, *mb, eps=clip, ent_coef=ent, vf_coef=vf)
+    g32, s32 = P.autograd(actor, critic, *mb, eps=clip, ent_coef=ent, vf_coef=vf, dtype="float32")
+    grads = [p.grad.cpu().numpy().astype(np.float64) for p in (pol.l1.weight, pol.l1.bias, pol.l2.weight, pol.l2.bias, pol.l3.weight, pol.l3.bias, pol.log_std,
+                                                                pol.v1.weight, pol.v1.bias, pol.v2.weight, pol.v2.bias, pol.v3.weight, pol.v3.bias)]
+    got = dict(grads=grads, scalars={k: float(stats[k]) for k in P.SCALARS})
+    rows = compare(got, ref, g32, s32)
+    assert_rule("on-policy n=512", rows, skip=("policy_loss", "approx_kl", "loss"))
+    b = P.log_prob_budget(actor, mb[0], mb[1])
+    pl_bound = float(np.mean(np.abs(mb[3].astype(np.float64)) * (b + 2.0 ** -22)))
+    vl = {name: max(e32, FLOOR) for name, _, e32 in rows}["value_loss"]
+    loss_bound = pl_bound + vf * C_BOUND * vl * abs(ref["scalars"]["value_loss"])
+    d = {k: got["scalars"][k] - ref["scalars"][k] for k in ("policy_loss", "loss")}
+    print(f"on-policy n=512: |d policy_loss| {abs(d['policy_loss']):.3e} bound {pl_bound:.3e}; |d loss| {abs(d['loss']):.3e} bound {loss_bound:.3e}; "
+          f"approx_kl {got['scalars']['approx_kl']:.3e} (fp64 {ref['scalars']['approx_kl']:.3e}) bound {float(b.max()) + 2.0 ** -22:.3e}")
+    assert abs(d["policy_loss"]) <= pl_bound
+    assert abs(got["scalars"]["approx_kl"]) <= float(b.max()) + 2.0 ** -22
+    assert abs(d["loss"]) <= loss_bound
+    assert got["scalars"]["clip_fraction"] == 0.0 and ref["scalars"]["clip_fraction"] == 0.0
+
+
 def test_one_epoch_end_to_end():
     """batch.collect (300 envs x 8 steps), one epoch of ppo_minibatches(..., 512), clip_grad_norm_, Adam, update_weights: afterwards the
-    handles act as a fresh policy built from the modules' parameters, and every .grad is finite and nonzero."""
+    handles act as a fresh policy built from the modules' parameters, and every .grad is finite and nonzero.  The first minibatch, before
+    any optimiser step, is held to the fp64 reference (``check_on_policy_minibatch``)."""
     from reinforcement_learning_rendezvous_amd.batch import RendezvousBatch
     import os
     from helpers import GOLDEN
@@ -226,6 +497,7 @@ def test_one_epoch_end_to_end():
     gen = torch.Generator(device=DEV).manual_seed(2)
     pieces = ppo_minibatches(300 * 8, 512, gen)
     assert [len(p) for p in pieces] == [512, 512, 512, 512, 352]
+    check_on_policy_minibatch(pol, buf, pieces[0])
     for idx in pieces:
         stats = pol.ppo_grad(buf, idx, clip_range=0.2, ent_coef=0.0, vf_coef=0.5)
         for name, p in pol.named_parameters():

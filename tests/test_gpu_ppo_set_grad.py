@@ -131,6 +131,19 @@ def test_every_member_gets_the_bits_of_the_stand_alone_call(world, counts):
     assert not bits_equal(outs[0][live[0]], outs[0][live[1]]) and not bits_equal(outs[1][live[0]], outs[1][live[1]])
 
 
+def test_a_member_of_256_workgroups_gets_the_bits_of_the_stand_alone_call(world):
+    """Counts (65536, 0, 300): a member whose rows fill 256 workgroups beside a skipped one and one of two workgroups — the sum over
+    workgroups of the shared finishing body at the size the stand-alone call is pinned at (tests/test_gpu_ppo_grad.py).  The index
+    vectors draw from the 1,200 rows with repetition."""
+    pset, alone, cols = world
+    counts = (65536, 0, 300)
+    rng = np.random.default_rng(21)
+    idx = [torch.as_tensor(rng.integers(0, P.ROWS, size=n), device=DEV) if n else None for n in counts]
+    outs = set_call(pset, cols, counts, idx)
+    assert_members_equal_alone(outs, alone, cols, counts, idx)
+    assert not bits_equal(outs[0][0], outs[0][2]) and not bits_equal(outs[1][0], outs[1][2])
+
+
 def test_two_eager_calls_and_a_graph_replay_give_the_same_bits(world):
     pset, _, cols = world
     counts = (1, 549, 32)

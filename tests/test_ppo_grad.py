@@ -5,6 +5,7 @@ itself (analytic NumPy float64 against double autograd), the conditions of the G
 kernels to the same reference.
 """
 import ctypes as C
+import zlib
 
 import numpy as np
 import pytest
@@ -18,6 +19,7 @@ from reinforcement_learning_rendezvous_amd import MlpPolicy, PolicySet, LstmPoli
 ENT, VF = 0.01, 0.5
 FLOOR = 2.0 ** -23
 C_BOUND = 128.0          # the bound of tests/test_gpu_ppo_grad.py (its scalars'; the gradients' is tighter)
+C_GRAD = 16.0            # the gradients'
 
 
 def _buf(case):
@@ -35,7 +37,7 @@ def _grads(pol):
                                      pol.v1.weight, pol.v1.bias, pol.v2.weight, pol.v2.bias, pol.v3.weight, pol.v3.bias)]
 
 
-@pytest.mark.parametrize("member", sorted(P.MEMBERS))
+@pytest.mark.parametrize("member", P.BASE_MEMBERS)
 def test_the_inputs_hold_the_conditions_of_the_comparison(member):
     """Every class {ratio below, inside, above the clip range} x {A < 0, A > 0} holds at least 5 % of the rows, and no fp64 ratio lies
     within 1e-4 of a clip limit; the index vectors hold duplicates and reach row 0 and the last row."""
@@ -50,6 +52,115 @@ def test_the_inputs_hold_the_conditions_of_the_comparison(member):
         assert idx.shape == (n,) and idx.min() == 0 and idx.max() == P.ROWS - 1 and len(set(idx.tolist())) < n
     if member == "random":
         assert -1.4 <= case["actor"]["log_std"].min() and case["actor"]["log_std"].max() <= -0.4 and np.ptp(case["actor"]["log_std"]) > 0.3
+
+
+def test_the_default_case_keeps_its_bits():
+    """``make_case`` with a ``rows`` argument and a third member: the 1,200-row cases of the two members are the arrays they were
+    (CRC-32 of the first column drawn and of the last one, which follows every re-draw of the guard loop)."""
+    crc = lambda a: zlib.crc32(a.tobytes())
+    for member, obs, adv in (("golden", 3030179336, 931998238), ("random", 1315193278, 345156336)):
+        case = P.make_case(member)
+        assert case["obs"].shape == (P.ROWS, 17) and (crc(case["obs"]), crc(case["advantages"])) == (obs, adv), member
+        assert P.make_case(member, rows=P.ROWS)["obs"].tobytes() == case["obs"].tobytes()
+
+
+@pytest.mark.parametrize("member", P.BASE_MEMBERS)
+def test_the_big_case_holds_the_conditions_of_the_comparison(member):
+    """65,536 rows by the recipe of the default case: no fp64 ratio within GUARD of a clip limit, every class at least 5 % of the rows —
+    of all rows and of the first 4,096, the two large minibatches of the GPU test and the base of the repeated one."""
+    case = P.big_case(member)
+    assert case["obs"].shape == (P.BIG_ROWS, 17) and np.abs(case["obs"]).max() <= 1.0
+    ref = P.analytic64(case["actor"], case["critic"], *P.take(case, P.BIG_ROWS))
+    assert np.abs(ref["ratio"] - (1 - P.EPS)).min() >= P.GUARD and np.abs(ref["ratio"] - (1 + P.EPS)).min() >= P.GUARD
+    for n in P.BIG_SHAPES + (P.REPEAT_BASE,):
+        shares = P.class_shares(ref["ratio"][:n], case["advantages"][:n])
+        assert len(shares) == 6 and min(shares.values()) >= 0.05, (n, shares)
+
+
+def test_the_repeated_index_vector_gives_every_row_the_same_multiplicity():
+    """1,048,576 samples = rows 0 .. 4,095 of the big case, 256 times each: a sum over the samples is 256 times the sum over the rows and
+    n is 256 times 4,096, so every mean — the loss, the gradients, the scalars — is that of the 4,096-row minibatch in exact arithmetic.
+    Shuffled: no two workgroups hold the same rows in the same places."""
+    idx = P.repeated_index_vector()
+    assert idx.dtype == np.int64 and idx.shape == (P.REPEAT_BASE * P.REPEAT_TIMES,) == (1 << 20,)
+    assert np.array_equal(np.bincount(idx, minlength=P.REPEAT_BASE), np.full(P.REPEAT_BASE, P.REPEAT_TIMES))
+    groups = idx.reshape(-1, 256)
+    assert len({g.tobytes() for g in groups}) == groups.shape[0] == 4096
+    assert np.array_equal(idx, P.repeated_index_vector())
+
+
+def test_the_clamp_member_tells_a_missing_backward_clamp():
+    """The "clamp" member: (a) its rows with |obs[3]| near and beyond 63 are live — on at least half of the first layer's units of either
+    net, 1 - h1^2 exceeds 0.1 on one of them — so they contribute to dW1; (b) the reference whose dW1 is contracted with the rows as
+    given, not clamped, leaves the rule's bound for ``actor.w1`` and ``critic.w1`` behind by more than a factor of 100, and changes
+    nothing else."""
+    case = P.make_case("clamp")
+    at = np.arange(0, P.ROWS, P.CLAMP_EVERY)
+    assert set(np.unique(case["obs"][at, P.CLAMP_COL]).tolist()) == set(np.asarray(P.CLAMP_VALUES, np.float32).tolist())
+    rest = np.delete(case["obs"], P.CLAMP_COL, axis=1)
+    assert np.abs(rest).max() <= 1.0 and np.abs(np.delete(case["obs"][:, P.CLAMP_COL], at)).max() <= 1.0
+    for n, idx in ((257, None), (549, None), (257, P.index_vector(257)), (549, P.index_vector(549))):
+        mb = P.take(case, n if idx is None else idx)
+        hot = np.abs(mb[0][:, P.CLAMP_COL]) > 60.0
+        assert hot.sum() >= 20
+        right = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF)
+        for key in ("h1", "c1"):
+            assert ((1.0 - right[key][hot] ** 2).max(0) > 0.1).mean() >= 0.5, (n, key)
+        assert min(P.class_shares(right["ratio"], mb[3]).values()) > 0.0
+        bad = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF, wrong="no_backward_clamp")
+        g32, _ = P.autograd(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF, dtype="float32")
+        over = {name: P.rel_err(b, w) / (C_GRAD * max(P.rel_err(y, w), FLOOR)) for name, b, w, y in zip(P.NAMES, bad["grads"], right["grads"], g32)}
+        assert over["actor.w1"] > 100.0 and over["critic.w1"] > 100.0, over
+        assert all(v == 0.0 for k, v in over.items() if k not in ("actor.w1", "critic.w1")), over
+        w1 = right["grads"][0]                                         # column 3 carries the largest entries of dW1: x is 63 there
+        assert np.abs(w1[:, P.CLAMP_COL]).max() == np.abs(w1).max()
+
+
+@pytest.mark.parametrize("n", [1, 32, 549])
+def test_rows_on_the_zero_gradient_side_of_the_clip_have_no_policy_gradient(n):
+    """``zero_policy_gradient``: both references give exactly 0.0 for the six weight and bias gradients of the actor, -ent_coef for
+    d log_std, a clip_fraction of 1 and a policy_loss that is not zero."""
+    case = P.zero_policy_gradient(P.make_case("random"))
+    mb = P.take(case, n)
+    ref = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF)
+    assert np.all((ref["ratio"] < 0.62) | (ref["ratio"] > 1.64))
+    g32, s32 = P.autograd(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF, dtype="float32")
+    for grads, scalars, exact in ((ref["grads"], ref["scalars"], True), (g32, s32, False)):
+        assert all(np.all(g == 0.0) for g in grads[:6])
+        # autograd adds ent_coef / n over the rows in float32 (the backward of a mean): -ent_coef to a few roundings, not to the bit
+        assert np.all(grads[6] == -ENT) if exact else np.abs(grads[6] + ENT).max() <= 4 * FLOOR * ENT
+        assert scalars["clip_fraction"] == 1.0 and abs(scalars["policy_loss"]) > 0.05
+        assert all(np.abs(g).max() > 0.0 for g in grads[7:])
+    if n == 549:
+        assert ref["scalars"]["policy_loss"] == pytest.approx(-0.256, abs=5e-4)
+
+
+def test_the_dead_wave_mask_leaves_one_live_row_in_the_last_wave():
+    mask = P.dead_wave_mask()
+    waves = mask[:544].reshape(17, 32)
+    assert [int(w.sum()) for w in waves] == [32, 0, 32, 0, 0, 32, 0, 0] + [32] * 9
+    assert mask[544:548].all() and not mask[548] and not mask[549:].any()
+    case = P.zero_policy_gradient(P.make_case("random"), mask)
+    ref = P.analytic64(case["actor"], case["critic"], *P.take(case, P.DEAD_N))
+    dead = (ref["ratio"] < 0.62) | (ref["ratio"] > 1.64)
+    assert np.array_equal(dead[mask[:P.DEAD_N]], np.ones(int(mask.sum()), bool)) and np.abs(ref["grads"][0]).max() > 0.0
+    base = P.make_case("random")
+    assert np.array_equal(case["advantages"][~mask], base["advantages"][~mask]) and np.array_equal(case["old_log_prob"][~mask], base["old_log_prob"][~mask])
+
+
+@pytest.mark.parametrize("column", P.COLUMNS)
+def test_a_nan_reaches_what_the_header_says(column):
+    """One NaN in row 540 of 549: the fp64 reference and float32 autograd agree on which gradient tensors are NaN throughout and which
+    scalars are NaN (``ppo_reference.NAN_RULE``); everything else is finite, entropy_loss and clip_fraction among it."""
+    case = P.with_nan(P.make_case("random"), column)
+    mb = P.take(case, 549)
+    assert sum(int(np.isnan(c).sum()) for c in mb) == 1
+    ref = P.analytic64(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF)
+    g32, s32 = P.autograd(case["actor"], case["critic"], *mb, ent_coef=ENT, vf_coef=VF, dtype="float32")
+    want = (tuple(P.NAN_RULE[column][0]), tuple(P.NAN_RULE[column][1]))
+    assert P.nan_pattern(ref["grads"], ref["scalars"]) == want
+    assert P.nan_pattern(g32, s32) == want
+    assert "entropy_loss" not in want[1] and "clip_fraction" not in want[1]
 
 
 @pytest.mark.parametrize("n", [1, 33, 549])
@@ -83,7 +194,7 @@ def test_the_bound_tells_a_wrong_restatement_from_the_right_one(wrong):
     assert all(over[k] > 10.0 for k in affected) and all(v == 0.0 for k, v in over.items() if k not in affected), over
 
 
-@pytest.mark.parametrize("member", sorted(P.MEMBERS))
+@pytest.mark.parametrize("member", P.BASE_MEMBERS)
 def test_the_fallback_fills_grad_and_returns_the_scalars(member):
     """CPU rows: autograd over the policy's own modules.  Raw advantages against the fp64 reference and the float32 restatement of
     ppo_reference; normalised advantages against the reference fed SB3's normalisation."""

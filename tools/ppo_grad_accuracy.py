@@ -2,6 +2,8 @@
 """The accuracy table behind the bound of tests/test_gpu_ppo_grad.py: for both members, every shape (with and without an index vector),
 every one of the 13 gradient tensors and five scalars of rdv_ppo_loss_grad, err = max|G_gpu - G64| / max|G64| against the fp64 reference of
 tests/ppo_reference.py, e32 = the same quantity for PyTorch's float32 autograd of the same loss (CPU), and err / max(e32, 2^-23).
+Behind the seven small shapes come the large ones of the 65,536-row case: n = 4,096 and 65,536 with rows in order (indexed = 0) and
+n = 1,048,576, the first 4,096 rows 256 times each, shuffled (indexed = 1), against the reference of the rows it repeats.
 
     python tools/ppo_grad_accuracy.py [--out profiles/ppo_grad_accuracy.csv]
 
@@ -26,17 +28,22 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("ppo_grad_accuracy.py: no GPU: nothing is measured")
     lines, worst = ["member,n,indexed,tensor,err,e32,err_over_max_e32_floor"], (0.0, "")
-    for member in sorted(P.MEMBERS):
+    for member in P.BASE_MEMBERS:
         case = P.make_case(member)
         pol = T.make_policy(case["actor"], case["critic"])
-        cols = {k: torch.from_numpy(case[k].copy()).to(T.DEV) for k in ("obs", "actions", "old_log_prob", "advantages", "returns")}
-        for n in P.SHAPES:
-            for indexed in (False, True):
-                rows, _, _, _ = T.measure(case, pol, cols, n, indexed)
-                for name, err, e32 in rows:
-                    ratio = err / max(e32, T.FLOOR)
-                    lines.append(f"{member},{n},{int(indexed)},{name},{err:.4e},{e32:.4e},{ratio:.4f}")
-                    worst = max(worst, (ratio, lines[-1]))
+        shapes = [(n, indexed, T.measure(case, pol, T.device_columns(case), n, indexed)[0]) for n in P.SHAPES for indexed in (False, True)]
+        big_cols = T.device_columns(P.big_case(member))
+        for n in P.BIG_SHAPES + (P.REPEAT_BASE * P.REPEAT_TIMES,):
+            rows, _, _, idx = T.measure_big(member, pol, big_cols, n)
+            shapes.append((n, idx is not None, rows))
+        for n, indexed, rows in shapes:
+            for name, err, e32 in rows:
+                ratio = err / max(e32, T.FLOOR)
+                lines.append(f"{member},{n},{int(indexed)},{name},{err:.4e},{e32:.4e},{ratio:.4f}")
+                worst = max(worst, (ratio, lines[-1]))
+            grad = max(err / max(e32, T.FLOOR) for name, err, e32 in rows if "." in name)
+            print(f"{member} n={n} indexed={int(indexed)}: largest ratio of a gradient tensor {grad:.3f}, of a scalar "
+                  f"{max(err / max(e32, T.FLOOR) for name, err, e32 in rows if '.' not in name):.3f}")
         pol.close()
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as fh:
