@@ -435,23 +435,39 @@ __device__ __forceinline__ void derive_chaser(const DevParams& P, const Env& e, 
 //  over from derive_chaser it occupied 18 registers across the target's attitude step and the whole of this function, which is where
 //  the fused kernels' register pressure peaked: tools/vgpr_pressure.py.  The quaternion is passed through an empty asm there so that
 //  the compiler does not recognise the expression as the one derive_chaser evaluated and keep that result alive instead.)
-template <bool kLazy>
-__device__ __forceinline__ void derive_target(const DevParams& P, const Env& e, Derived& d, double inv_dist) {
-  double Rt[9];
-  quat2mat(e.qt, Rt);
-  double rd_l[3];
+// The head of derive_target, which reads the canonical qt and nothing else of the env: R(qt) and the docking port R(qt) rd (:460).  A
+// partner wave can run it beside the chaser half and hand `rd_l` over (step_kernel_split_target, rdv_step.h).
+__device__ __forceinline__ void derive_target_head(const DevParams& P, const double* qt, double* Rt, double* rd_l) {
+  quat2mat(qt, Rt);
   matvec(Rt, P.rd, rd_l);               // :460
+}
+// R(qt) again inside a lazy branch of a caller that was handed `rd_l` and holds no matrix: from the same canonical quaternion, so the
+// same matrix bit for bit (the empty asm keeps the compiler from hoisting the rebuild out of the rare branch)
+__device__ __forceinline__ void rebuild_target_matrix(const Env& e, double* Rt) {
+  double qt_again[4] = {e.qt[0], e.qt[1], e.qt[2], e.qt[3]};
+  asm volatile("" : "+v"(qt_again[0]), "+v"(qt_again[1]), "+v"(qt_again[2]), "+v"(qt_again[3]));
+  quat2mat(qt_again, Rt);
+}
+// `rd_handed` (kHanded): R(qt) rd as derive_target_head formed it elsewhere from this e.qt; the lazy branches then rebuild R(qt).
+template <bool kLazy, bool kHanded = false>
+__device__ __forceinline__ void derive_target(const DevParams& P, const Env& e, Derived& d, double inv_dist, const double* rd_handed = nullptr) {
+  double Rt[9];
+  double rd_l[3];
+  if constexpr (kHanded) { rd_l[0] = rd_handed[0]; rd_l[1] = rd_handed[1]; rd_l[2] = rd_handed[2]; }
+  else derive_target_head(P, e.qt, Rt, rd_l);
   const double dp[3] = {e.rc[0] - rd_l[0], e.rc[1] - rd_l[1], e.rc[2] - rd_l[2]};
   d.pos2 = sumsq3(dp);                  // :463
   const double inf = __builtin_huge_val();
   d.vel2 = inf; d.rot2 = inf; d.k_corr = inf;
   // the corridor angle first: after it only the next branch needs R(qt), and that one is done with it before it builds R(qc)
   if (!kLazy || d.r2 <= P.lt2_koz) {
+    if constexpr (kHanded) rebuild_target_matrix(e, Rt);
     double corr_l[3];
     matvec(Rt, P.corridor_axis, corr_l);                                                // :400
     d.k_corr = rint(dot3(e.rc, corr_l) * (inv_dist * P.inv_corridor_norm) * 1e5);
   }
   if (!kLazy || d.pos2 <= P.le2_rd) {
+    if constexpr (kHanded) rebuild_target_matrix(e, Rt);
     double wt_l[3];
     matvec(Rt, e.wt, wt_l);             // :459
     const double vd_l[3] = {fma(wt_l[1], rd_l[2], -wt_l[2] * rd_l[1]), fma(wt_l[2], rd_l[0], -wt_l[0] * rd_l[2]),
@@ -484,10 +500,16 @@ __device__ __forceinline__ double angle_of(double k) { return acos(div_1e5(k)); 
 // The same value on the step path: a rounded cosine takes one of 200,001 values k*1e-5, so acos(k/1e5) is read from a
 // 1.6 MB table the host fills with its libm acos (the oracle's), instead of ~110 instructions of device acos.  Only the
 // ~14k entries of attitude errors below 30 deg are ever touched (episodes end beyond): ~110 KB, L2-resident.
+// kGlobal: the entry is requested with a global load instead of the flat load a pointer read from the parameter block compiles to.  A flat
+// load also counts as an LDS operation, so the first wait for LDS behind it — a workgroup barrier's — waits for the entry; a kernel
+// that has a barrier between the request and the reward (step_kernel_split_target) asks for the global form.  The same bytes.
+template <bool kGlobal = false>
 __device__ __forceinline__ double attitude_error_of(const DevParams& P, double k) {
   const bool valid = fabs(k) <= 100000.0;                    // false for NaN (rc = 0: the reference asserts there)
   const int idx = valid ? (int)k + 100000 : 100000;
-  const double a = P.acos_table[idx];
+  double a;
+  if constexpr (kGlobal) a = ((const __attribute__((address_space(1))) double*)P.acos_table)[idx];
+  else a = P.acos_table[idx];
   return valid ? a : __builtin_nan("");
 }
 
@@ -804,7 +826,8 @@ struct StepCtx {
 // tumbling tri-axial target beside the reference's chaser leaves the chaser on the closed form.
 // `pre()` is called once, behind the last thing that does not need the action (the chaser's rotation matrix) and in front of the first
 // use of `a`: a kernel whose action row is still in flight waits for it there (step_kernel_split / _parts: PinnedInputs).
-template <typename ST, bool kGeneral = false, bool kRaw = false, typename Pre = NoHook>
+// kGlobalTable: see attitude_error_of.
+template <typename ST, bool kGeneral = false, bool kRaw = false, bool kGlobalTable = false, typename Pre = NoHook>
 __device__ __forceinline__ void step_env_chaser(const DevParams& P, Env& e, const float* a, Derived& d, StepCtx& c, Pre&& pre = Pre()) {
   const ST tag = ST(0);
   // :172 delta_v = R(qc) * (a[0:3] * max_delta_v); the product is float32 (float32 array * Python float)
@@ -839,7 +862,7 @@ __device__ __forceinline__ void step_env_chaser(const DevParams& P, Env& e, cons
 #pragma unroll
   for (int i = 0; i < 4; ++i) e.qc[i] = canon(e.qc[i], tag);
   derive_chaser(P, e, d, c.inv_dist);
-  c.att = attitude_error_of(P, d.k_att);
+  c.att = attitude_error_of<kGlobalTable>(P, d.k_att);
 }
 
 // The target's attitude step (:184) on (qt, wt) alone: what a partner wave can run beside the chaser half (step_kernel_general).
@@ -852,16 +875,22 @@ __device__ __forceinline__ void step_target(const DevParams& P, double* qt, doub
 
 // Second half (:187-221): the target's state made canonical, its half of the derived quantities, the latches, bookkeeping, reward,
 // observation and termination.
-template <typename ST, bool kLazy, bool kGeneral = false, typename Sink>
-__device__ __forceinline__ void step_env_finish(const DevParams& P, Env& e, StepResult& r, Derived& d, const StepCtx& c, Sink&& sink) {
+// kHanded (step_kernel_split_target): a partner wave ran the target's step, the rounding of qt and derive_target_head — e.qt arrives
+// canonical, with `rd_handed` = R(qt) rd — and the table entry c.att has had less time to travel: the reward, the only thing that
+// reads it, is formed LAST, behind the observation and the termination tests.  The pieces are the same in either order.
+template <typename ST, bool kLazy, bool kGeneral = false, bool kHanded = false, typename Sink>
+__device__ __forceinline__ void step_env_finish(const DevParams& P, Env& e, StepResult& r, Derived& d, const StepCtx& c, Sink&& sink,
+                                                const double* rd_handed = nullptr) {
   const ST tag = ST(0);
   if (kGeneral) {
 #pragma unroll
     for (int i = 0; i < 3; ++i) e.wt[i] = canon(e.wt[i], tag);
   }
+  if constexpr (!kHanded) {
 #pragma unroll
-  for (int i = 0; i < 4; ++i) e.qt[i] = canon(e.qt[i], tag);
-  derive_target<kLazy>(P, e, d, c.inv_dist);
+    for (int i = 0; i < 4; ++i) e.qt[i] = canon(e.qt[i], tag);
+  }
+  derive_target<kLazy, kHanded>(P, e, d, c.inv_dist, rd_handed);
   const bool inst_coll = in_koz(P, d);
   // :187-190
   if (!(e.flags & FLAG_COLLIDED)) {
@@ -875,18 +904,21 @@ __device__ __forceinline__ void step_env_finish(const DevParams& P, Env& e, Step
   e.sum_dw = canon(fma((double)c.sum_w, P.max_delta_w, e.sum_dw), tag);
 
   // :313-353 (the reward does not depend on the observation or on done: computed first, the observation last, so that its 17 floats
-  // go straight to the sink)
-  const double att = c.att;
-  double rew = P.att_term * fma(-att, P.inv_max_attitude_error, 1.0);                  // :329
-  rew += (double)(mul_f32_rn(P.fuel_scale_f32, c.sum_v) / P.fuel_div_f32);             // :333
-  if (inst_coll) rew -= P.coll_term;                                                   // :336-337
-  if (d.r2 <= P.lt2_koz && !(e.flags & FLAG_COLLIDED) && d.pos2 <= P.lt2_rd) {             // :340, :348 (both strict: lt2_*)
-    rew += P.bonus_term * fma(-sqrt(d.pos2), P.inv_max_rd_error, 2.0);                 // :349
-    if (d.k_att >= P.ka_bonus_min) rew += P.bonus_term * fma(-att, P.inv_max_qd_error, 2.0);   // :350-351
-  }
-  e.ep_ret = canon(e.ep_ret + rew, tag);
-  r.reward = (float)rew;
-  r.reward64 = rew;
+  // go straight to the sink; kHanded: last, see above)
+  auto reward = [&]() {
+    const double att = c.att;
+    double rew = P.att_term * fma(-att, P.inv_max_attitude_error, 1.0);                  // :329
+    rew += (double)(mul_f32_rn(P.fuel_scale_f32, c.sum_v) / P.fuel_div_f32);             // :333
+    if (inst_coll) rew -= P.coll_term;                                                   // :336-337
+    if (d.r2 <= P.lt2_koz && !(e.flags & FLAG_COLLIDED) && d.pos2 <= P.lt2_rd) {             // :340, :348 (both strict: lt2_*)
+      rew += P.bonus_term * fma(-sqrt(d.pos2), P.inv_max_rd_error, 2.0);                 // :349
+      if (d.k_att >= P.ka_bonus_min) rew += P.bonus_term * fma(-att, P.inv_max_qd_error, 2.0);   // :350-351
+    }
+    e.ep_ret = canon(e.ep_ret + rew, tag);
+    r.reward = (float)rew;
+    r.reward64 = rew;
+  };
+  if constexpr (!kHanded) reward();
   // :205, :355-386
   bool outside = false;
   observation_to(P, e, [&](int j, float v) {
@@ -901,6 +933,7 @@ __device__ __forceinline__ void step_env_finish(const DevParams& P, Env& e, Step
   const bool c_time = e.k >= P.k_time, c_att = d.k_att <= P.ka_done_max;
   r.done = (outside | c_time | c_bubble | c_att) ? 1 : 0;
   r.reason = outside ? 1 : (c_time ? 2 : (c_bubble ? 3 : (c_att ? 4 : 0)));            // :381 first true
+  if constexpr (kHanded) reward();
 }
 
 // step (:160-221) on one env; `a` are the raw float32 actions (not clipped, as the reference :170).

@@ -61,6 +61,10 @@ constexpr int64_t kSplitAutoMaxEnvs = 65536;    // measured crossover (tools/n_s
 // step_kernel_split's form for fp32 storage and on_done == RESET: prepared slots prefetched by the service waves and refilled by appended
 // workgroups (true), or the speculative reset on the service waves (false).  Measured: profiles/split_slots_prefetch.txt.
 static inline bool split_slots_by_size(int64_t n) { (void)n; return true; }
+// ... and, where the slot form runs, whether its service waves also take the target's side of the transition off the step waves
+// (step_kernel_split_target, rdv_step.h).  Measured (profiles/split_target_on_service.txt, us per launch, slot form -> target form):
+// 65,536 envs 5.93 -> 5.71, 32,768 5.59 -> 5.27, 16,384 5.10 -> 4.79, against a parent-to-parent spread of 0.01-0.02: on at every size.
+static inline bool split_target_by_size(int64_t n) { (void)n; return true; }
 enum { ST_STEPS = 0, ST_EPISODES, ST_SUCCESS, ST_COLLIDED, ST_REASON0, ST_REASON1, ST_REASON2, ST_REASON3,
        ST_SUM_LEN, ST_SUM_RET, ST_SUM_DV, ST_SUM_DW };
 
@@ -401,21 +405,30 @@ struct PinnedInputs {
   pin_f2 a2;
   pin_f2 sp;
 };
+// kNoTarget (step_kernel_split_target, whose service waves own the target's chunks 4 and 6): eight requests, the five chunks of the chaser
+// and the bookkeeping and the same three behind them — the waits' literals count the requests BEHIND the state and stay as they are.
+// c[4] and c[6] are zero there: unpack_env reads them, the kernel overwrites qt and wt with what the service wave hands over.
+template <bool kNoTarget = false>
 __device__ __forceinline__ void pinned_fetch(const StepArgs& A, int64_t wave_base, int lane, PinnedInputs& in) {
   const int64_t wb = wave_base < A.n ? wave_base : ((A.n - 1) & ~(int64_t)(kWave - 1));   // as tile_fetch: every lane loads, from a valid env
   const int64_t rows = A.n - wb;
   const int l = lane < rows ? lane : 0;
   const pin_f4* wsw = reinterpret_cast<const pin_f4*>(A.ws) + wb + l;
 #pragma unroll
-  for (int c = 0; c < kChunks; ++c) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(in.c[c]) : "v"(wsw + c * A.cs));
+  for (int c = 0; c < kChunks; ++c) {
+    if (kNoTarget && (c == 4 || c == 6)) in.c[c] = pin_f4{0.0f, 0.0f, 0.0f, 0.0f};
+    else asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(in.c[c]) : "v"(wsw + c * A.cs));
+  }
   const float* row = A.actions + (wb + l) * RDV_ACT_DIM;
   asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dwordx2 %1, %2, off offset:16" : "=&v"(in.a4), "=&v"(in.a2) : "v"(row));
   const uint64_t* sp = A.stats + (uint64_t)(wb / kWave) * kStatWords + (lane & (kStatWords - 1));
   asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(in.sp) : "v"(sp));
 }
+template <bool kNoTarget = false>
 __device__ __forceinline__ void pinned_wait_state(PinnedInputs& in) {
   asm volatile("s_waitcnt vmcnt(3)" : "+v"(in.c[0]), "+v"(in.c[1]), "+v"(in.c[2]), "+v"(in.c[3]));
-  asm volatile("" : "+v"(in.c[4]), "+v"(in.c[5]), "+v"(in.c[6]));
+  if constexpr (kNoTarget) asm volatile("" : "+v"(in.c[5]));
+  else asm volatile("" : "+v"(in.c[4]), "+v"(in.c[5]), "+v"(in.c[6]));
 }
 __device__ __forceinline__ void pinned_wait_rest(PinnedInputs& in, double& after) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(in.a4), "+v"(in.a2), "+v"(in.sp), "+v"(after)); }
 __device__ __forceinline__ void pinned_unpack(const PinnedInputs& in, Env& e) {
@@ -430,9 +443,10 @@ __device__ __forceinline__ void pinned_unpack(const PinnedInputs& in, Env& e) {
 //     uses nothing);
 //   pinned_rest: the wait for the rest, action row -> `a`, statistics slot -> `slot_pre`.  The kernels hand it to advance_all as the
 //     hook that runs behind the chaser's rotation matrix.
+template <bool kNoTarget = false>
 __device__ __forceinline__ void pinned_state(const StepArgs& A, int64_t wave_base, int lane, PinnedInputs& pin, Env& e) {
-  pinned_fetch(A, wave_base, lane, pin);
-  pinned_wait_state(pin);
+  pinned_fetch<kNoTarget>(A, wave_base, lane, pin);
+  pinned_wait_state<kNoTarget>(pin);
   pinned_unpack(pin, e);
 }
 __device__ __forceinline__ void pinned_rest(PinnedInputs& pin, double& after, float* a, uint64_t& slot_pre) {

@@ -259,13 +259,40 @@ __device__ __forceinline__ void refill_stale_slots(const StepArgs& A, const DevP
 // later.  Launches that advance episodes without maintaining the slots (every other rdv_step kernel) and calls that change what a
 // reset returns clear the handle's step_slots_ok; prepare_kernel then runs in front of the next slot-form launch (rdv_hip.hip).
 // Measured: profiles/split_slots_prefetch.txt.
-template <typename ST, bool kAll, bool kSlots = false>   // kAll: on_done != HALT — every lane of the step waves runs the transition (advance_all)
-__global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
-                                                       uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+//
+// The target form (kTarget; the slot form's conditions, its refill workgroups and its reset paths unchanged) gives the service wave, which
+// in the slot form only waits in front of the barrier, the part of the transition that depends on nothing the step wave computes: the
+// target's attitude step (step_target), the rounding of qt, R(qt) and R(qt) rd (derive_target_head) — the same functions on the same
+// inputs, so the same bits.  The service wave loads chunks 4 and 6 with its first stage (the step wave no longer requests them: the
+// bytes requested at entry per CU are the same), posts qt as four floats, R(qt) rd as three doubles and wt as three floats in LDS
+// ([component][env], 52 bytes per env), and requests the slot records BEHIND the join, so that nothing but the second barrier stands
+// between the untracked record loads and their wait (no instruction there that could move a record register; the requests in front of
+// the arithmetic, with a dozen live record registers across it, were not built).  The step wave runs step_env_chaser, JOINS at a
+// workgroup barrier, and finishes from the posted values (step_env_finish<.., kHanded>: the lazy branches rebuild R(qt), the reward —
+// the one consumer of the table entry requested at the end of the chaser half — comes last; the entry is requested with a GLOBAL load
+// there, because a flat load counts as an LDS operation and the join's wait for LDS would wait for it).  Every wave of a step workgroup
+// executes exactly two barriers, on every path: the join, and the barrier behind the termination ballot; the refill workgroups are the
+// slot form's.  Measured (profiles/split_target_on_service.txt, tools/lib_ab.py, us per launch, slot form -> this form): 5.93 -> 5.71 at
+// 65,536 envs, 5.59 -> 5.27 at 32,768, 5.10 -> 4.79 at 16,384; the stamped build has the service wave post 2,160 cycles after entry and
+// wait 1,430 at the join, the step wave arrive at 3,520 and wait 56.  The default form wherever the slot form runs (split_target_by_size).
+// The two older forms now run through the same body function, which changed their instruction streams by operand order and a few
+// instructions (profiles/split_target_isa_diff.md): the slot form measures 5.97 us that way, 0.04 more than before.
+#ifndef RDV_TARGET_SERVICE_PRIO
+// s_setprio of the service wave's arithmetic segment; the step waves run at 2.  Above them it wins: the first stage lands while the step wave
+// still waits for its state, and what fits there is free — 5.74 us per launch at 0 and at 1, 5.71 at 3 (65,536 envs, four children each)
+#define RDV_TARGET_SERVICE_PRIO 3
+#endif
+// The body of both kernels below.  kAll: on_done != HALT — every lane of the step waves runs the transition (advance_all).
+// stage / fin_mask: the kernel's LDS (observation rows [256][17]; per step wave, the lanes to reset).  hand_f / hand_d: the target form's
+// hand-over in LDS ([7][256] floats: qt, wt; [3][256] doubles: R(qt) rd), null otherwise.
+template <typename ST, bool kAll, bool kSlots, bool kTarget>
+__device__ __forceinline__ void split_body(void* ws_hot, const float* actions_hot, const DevParams* Pp, int64_t n_hot, uint64_t* stats_hot, float* obs_hot,
+                                           float* reward_hot, const StepArgs& A_rest, float* stage, unsigned long long* fin_mask, float* hand_f, double* hand_d) {
+  static_assert(!kTarget || kSlots, "the target form is a form of the slot form");
+  constexpr int kS = kTarget ? 1 : 0;   // stamps (diagnostic build): the target form has 2 = at the join, 3 = past it, and the later ones one up
+  (void)kS; (void)hand_f; (void)hand_d;
   const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
   using V = typename Vec4<ST>::type;
-  __shared__ __attribute__((aligned(16))) float stage[kSplitEnvs * RDV_OBS_DIM];   // observation rows
-  __shared__ unsigned long long fin_mask[kSplitEnvs / kWave];                        // per step wave: lanes to reset
   const DevParams& P = *Pp;   // scalar loads: see step_kernel
   const int lane = threadIdx.x & (kWave - 1);
   const int wv = threadIdx.x >> 6;
@@ -310,8 +337,8 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
     PinnedInputs pin;
     if constexpr (kPinned) {
       // state chunks, action row and statistics slot requested together (rdv_kernels.h: PinnedInputs); the state is waited for here, the
-      // action row behind the chaser's rotation matrix (actions_ready)
-      pinned_state(A, wave_base, lane, pin, e);
+      // action row behind the chaser's rotation matrix (actions_ready).  kTarget: without chunks 4 and 6, which the service wave loads
+      pinned_state<kTarget>(A, wave_base, lane, pin, e);
     } else if constexpr (kAll) {
       TileInputs<ST> in;
       tile_fetch<ST>(A, wave_base, lane, in);
@@ -337,9 +364,28 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
     auto row_sink = [&](int j, float v) { obs_r[j] = v; my_row[j] = v; };
     bool stepped;
     auto actions_ready = [&](double& after) { if constexpr (kPinned) pinned_rest(pin, after, a, slot_pre); };
-    if constexpr (kAll) { advance_all<ST>(P, e, a, r, row_sink, kPack ? packed : nullptr, actions_ready); stepped = active; }
-    else stepped = advance<ST, false>(A, P, i, active, e, a, r, row_sink, NoHook(), kPack ? packed : nullptr);
-    RDV_STAMP(2);
+    if constexpr (kTarget) {
+      // advance_all in its halves: the chaser half, the join, the finish from what the service wave posted
+      r.done = 0; r.reason = 0; r.reward = 0.0f; r.reward64 = 0.0;
+      Derived d;
+      StepCtx c;
+      step_env_chaser<ST, false, false, true>(P, e, a, d, c, actions_ready);   // (the table entry by a global load: the join must not wait for it)
+      RDV_STAMP(2);
+      __syncthreads();   // the join: the service waves have posted the target side of this workgroup's envs
+      RDV_STAMP(3);
+      double rd_l[3];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) e.qt[k] = (double)hand_f[k * kSplitEnvs + slot_in_block];   // canonical: (double)(float) as canon() forms it
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { e.wt[k] = (double)hand_f[(4 + k) * kSplitEnvs + slot_in_block]; rd_l[k] = hand_d[k * kSplitEnvs + slot_in_block]; }
+      step_env_finish<ST, true, false, true>(P, e, r, d, c, row_sink, rd_l);
+      pack_env<ST>(e, packed);
+      stepped = active;
+    } else {
+      if constexpr (kAll) { advance_all<ST>(P, e, a, r, row_sink, kPack ? packed : nullptr, actions_ready); stepped = active; }
+      else stepped = advance<ST, false>(A, P, i, active, e, a, r, row_sink, NoHook(), kPack ? packed : nullptr);
+      RDV_STAMP(2);
+    }
     const bool fin = stepped && r.done;
     const bool to_reset = fin && resets;
     const unsigned long long m_reset = __ballot(to_reset);
@@ -352,14 +398,14 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
     // 65,536 envs, 5.35 -> 5.29 at 16,384; moving the reward / done / terminal-row stores there as well loses: 6.89).  Reset lanes: service wave.
     halt_if_done<ST>(A, fin, e, kPack ? packed : nullptr);
     if (stepped && !to_reset) { if (kPack) store_chunks<ST, true>(ws, A.cs, i, packed, false); else store_env<ST>(ws, A.cs, i, e, false); }
-    RDV_STAMP(3);
+    RDV_STAMP(3 + kS);
     __syncthreads();
-    RDV_STAMP(4);
+    RDV_STAMP(4 + kS);
     stats_update(slot, slot_pre, lane, stepped, fin, r.reason, e.flags, e.k, e.ep_ret, e.sum_dv, e.sum_dw);
     store_step_outputs<true>(A, i, active, fin, r, e, obs_r);
     if (m_reset == 0ull) store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
-    RDV_STAMP(5);
-    RDV_STAMP(6);
+    RDV_STAMP(5 + kS);
+    RDV_STAMP(6 + kS);
   } else if constexpr (kSlots) {
     // ------------------------------------------------------------------ service waves, slot form
     // The requests in the order of their urgency (profiles/split_prefetch_order.txt).  Every lane first requests its env's chunk 5 (k,
@@ -380,12 +426,42 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
     pin_f4 rec[kRecVecs];
     pin_f4 c5;
     uint32_t tag;
-    asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dword %1, %3, off"
-                 : "=&v"(c5), "=&v"(tag) : "v"(reinterpret_cast<const pin_f4*>(ws) + 5 * A.cs + il), "v"(A.prep_tag + il));
-    asm volatile("s_waitcnt vmcnt(0)" : "+v"(c5), "+v"(tag));
-    RDV_STAMP(1);
+    if constexpr (kTarget) {
+      // the first stage also brings the target's chunks 4 (qt) and 6 (wt), which the step wave no longer requests; behind the wait the
+      // target side of the transition runs here, beside the step wave's chaser half, and is posted for the join
+      pin_f4 c4, c6;
+      const pin_f4* wsl = reinterpret_cast<const pin_f4*>(ws) + il;
+      asm volatile("global_load_dwordx4 %0, %4, off\n\tglobal_load_dwordx4 %1, %5, off\n\tglobal_load_dwordx4 %2, %6, off\n\tglobal_load_dword %3, %7, off"
+                   : "=&v"(c4), "=&v"(c6), "=&v"(c5), "=&v"(tag) : "v"(wsl + 4 * A.cs), "v"(wsl + 6 * A.cs), "v"(wsl + 5 * A.cs), "v"(A.prep_tag + il));
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(c4), "+v"(c6), "+v"(c5), "+v"(tag));
+      RDV_STAMP(1);
+      if (RDV_TARGET_SERVICE_PRIO) __builtin_amdgcn_s_setprio(RDV_TARGET_SERVICE_PRIO);
+      double qt[4] = {c4.x, c4.y, c4.z, c4.w}, wt[3] = {c6.x, c6.y, c6.z};
+      step_target<false, false>(P, qt, wt);       // :184 (wt is constant under the reference's bodies: handed over as loaded)
+      double Rt[9], rd_l[3];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) qt[k] = canon(qt[k], ST(0));
+      derive_target_head(P, qt, Rt, rd_l);
+#pragma unroll
+      for (int k = 0; k < 4; ++k) hand_f[k * kSplitEnvs + slot_in_block] = (float)qt[k];
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { hand_f[(4 + k) * kSplitEnvs + slot_in_block] = c6[k]; hand_d[k * kSplitEnvs + slot_in_block] = rd_l[k]; }
+      if (RDV_TARGET_SERVICE_PRIO) __builtin_amdgcn_s_setprio(0);
+    } else {
+      asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dword %1, %3, off"
+                   : "=&v"(c5), "=&v"(tag) : "v"(reinterpret_cast<const pin_f4*>(ws) + 5 * A.cs + il), "v"(A.prep_tag + il));
+      asm volatile("s_waitcnt vmcnt(0)" : "+v"(c5), "+v"(tag));
+      RDV_STAMP(1);
+    }
     const uint32_t k_in = __float_as_uint(c5.y), episode_in = __float_as_uint(c5.w);
     const bool copy_ok = tag == episode_in + 1u && k_in >= 1u;
+    if constexpr (kTarget) {
+      // The join.  The record requests go out BEHIND it: nothing but the second barrier then stands between the untracked loads and
+      // their wait, as in the slot form, and they have the step waves' whole finish to land in.
+      RDV_STAMP(2);
+      __syncthreads();
+      RDV_STAMP(3);
+    }
 #pragma unroll
     for (int v = 0; v < kRecVecs; ++v) asm volatile("" : "=v"(rec[v]));   // (defined registers for the lanes that request nothing)
     unsigned long long saved_exec;
@@ -411,10 +487,10 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]),
                  "+v"(rec[7]), "+v"(rec[8]), "+v"(rec[9]), "+v"(rec[10]), "+v"(rec[11]));   // stamps build only: stamp 2 is "the records have landed"
 #endif
-    RDV_STAMP(2);
-    RDV_STAMP(3);
+    if constexpr (!kTarget) RDV_STAMP(2);
+    RDV_STAMP(3 + kS);
     __syncthreads();
-    RDV_STAMP(4);
+    RDV_STAMP(4 + kS);
     // the compiler does not track these loads: every use of a record register it sees is of the value behind this wait
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]),
                  "+v"(rec[7]), "+v"(rec[8]), "+v"(rec[9]), "+v"(rec[10]), "+v"(rec[11]));
@@ -454,10 +530,10 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
         }
       }
       wave_lds_fence();
-      RDV_STAMP(5);
+      RDV_STAMP(5 + kS);
       store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
     }
-    RDV_STAMP(6);
+    RDV_STAMP(6 + kS);
   } else {
     // ------------------------------------------------------------------ service waves
     // The observation and the storage packing of the next initial state are computed after the barrier, by the lanes that use them:
@@ -498,6 +574,27 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, c
   }
   RDV_STAMP(7);
   RDV_STAMP_FLUSH((uint64_t)blockIdx.x * 8 + wv)
+}
+
+template <typename ST, bool kAll, bool kSlots = false>
+__global__ __launch_bounds__(kSplitBlock) void step_kernel_split(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
+                                                       uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+  __shared__ __attribute__((aligned(16))) float stage[kSplitEnvs * RDV_OBS_DIM];   // observation rows
+  __shared__ unsigned long long fin_mask[kSplitEnvs / kWave];                        // per step wave: lanes to reset
+  split_body<ST, kAll, kSlots, false>(ws_hot, actions_hot, Pp, n_hot, stats_hot, obs_hot, reward_hot, A_rest, stage, fin_mask, nullptr, nullptr);
+}
+
+// The target form: a kernel of its own name (the launch still reports "step_kernel_split<float, true>": it is a form of that kernel, picked
+// like the slot form), with the 13 KB of the hand-over beside the observation rows — 30,752 bytes of LDS per workgroup, so a step and a
+// refill workgroup still share a CU.
+template <typename ST>
+__global__ __launch_bounds__(kSplitBlock) void step_kernel_split_target(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
+                                                              uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+  __shared__ __attribute__((aligned(16))) float stage[kSplitEnvs * RDV_OBS_DIM];   // observation rows
+  __shared__ unsigned long long fin_mask[kSplitEnvs / kWave];                        // per step wave: lanes to reset
+  __shared__ double hand_d[3 * kSplitEnvs];   // R(qt) rd, [component][env]
+  __shared__ float hand_f[7 * kSplitEnvs];    // canonical qt, then wt
+  split_body<ST, true, true, true>(ws_hot, actions_hot, Pp, n_hot, stats_hot, obs_hot, reward_hot, A_rest, stage, fin_mask, hand_f, hand_d);
 }
 
 }  // namespace rdv

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Diagnostic: A/B of two builds of the library (the product .so against an experimental one) on the one-launch step at 65,536 envs
 and 524,288 envs: each build in its own child process, alternated, 256-launch graphs under sustained load.  AB_SIZES=65536,32768,16384 picks the sizes; the children inherit the
-environment (RDV_SPLIT_FORM=speculative|slots: the form of step_kernel_split in the builds that have both).
+environment (RDV_SPLIT_FORM=speculative|slots|slots_target: the form of step_kernel_split in the builds that have them).
     python tools/lib_ab.py tools/_nt.so"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

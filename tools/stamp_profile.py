@@ -7,8 +7,14 @@ Builds a -DRDV_STAMPS copy of the library into tools/_stamps.so, runs a few hund
 (service waves of the slot form: 1 chunk 5 and tag landed, record requests go out | 2 the records have landed — this build waits for them there)
 plus, from s_memrealtime (100 MHz, one counter for the whole chip): the shader clock, when waves enter and leave
 relative to the first wave of the launch, and the span of the launch as the waves see it.
-RDV_SPLIT_FORM=speculative|slots picks the form (csrc/rdv_step.h); in the slot form the second half of the grid is the refill workgroups;
-the lifetime of their wave 0 (it writes the largest part and the tags) is printed beside the two roles.  RDV_STAMPS_PREBUILT=1 uses tools/_stamps.so as it stands.
+RDV_SPLIT_FORM=speculative|slots|slots_target picks the form (csrc/rdv_step.h); in the slot forms the second half of the grid is the refill workgroups;
+the lifetime of their wave 0 (it writes the largest part and the tags) is printed beside the two roles.  RDV_STAMPS_PREBUILT=1 uses tools/_stamps.so
+(or the library RDV_STAMPS_LIB names) as it stands.
+The target form (slots_target) has a join in front of the barrier, and its stamps are
+  0 entry | 1 inputs staged (service waves: first stage landed, chunks 4 and 6 with it) | 2 at the join (step waves: chaser half done; service
+  waves: target side posted) | 3 past the join | 4 at the barrier (service waves of this build: the records, requested behind the join, have
+  landed) | 5 past it | 6 | 7 end
+so phase 2>3 is what a role waits at the join; the join's line is printed beside the barrier's.
 Never quote this build's run time: the stamps fence the scheduler."""
 import ctypes as C
 import os
@@ -25,7 +31,9 @@ def main():
     n = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
     svc = 1          # service waves per step wave (round 3 also stamped a 12-wave workgroup with two: profiles/r03_split_service_waves_stamps.txt)
     wpg = 4 * (1 + svc)
-    lib = os.path.join(ROOT, "tools", "_stamps.so")
+    lib = os.environ.get("RDV_STAMPS_LIB") or os.path.join(ROOT, "tools", "_stamps.so")
+    target_form = os.environ.get("RDV_SPLIT_FORM", "slots_target") == "slots_target"      # the library's default form (a library from before it: RDV_SPLIT_FORM=slots)
+    k_barrier = 4 if target_form else 3          # the stamp "at the barrier"
     from _build import build_variant
     if not os.environ.get("RDV_STAMPS_PREBUILT"):
         build_variant(lib, ["-DRDV_STAMPS"] + os.environ.get("RDV_EXTRA_FLAGS", "").split())
@@ -66,8 +74,13 @@ def main():
         print(f"{name}: median cycles per phase 0>1>..>7 {np.median(d, axis=(0, 1)).astype(int).tolist()} | wave lifetime "
               f"{np.median(real[:, sel]):.0f} ns | enters {np.median(ent):.0f} ns (p95 {np.percentile(ent, 95):.0f}) and leaves "
               f"{np.median(ext):.0f} ns (p95 {np.percentile(ext, 95):.0f}, max {np.median(ext.max(axis=1)):.0f}) after the first wave")
-    at_barrier = s[:, :, 3] - s[:, :, 0]
-    print("cycles from entry to the barrier, median by role: " + ", ".join(f"{names[k]} {np.median(at_barrier[:, role == k]):.0f}" for k in range(1 + svc)))
+    if target_form:
+        at_join, wait_join = s[:, :, 2] - s[:, :, 0], s[:, :, 3] - s[:, :, 2]
+        print("cycles from entry to the join, median by role: " + ", ".join(f"{names[k]} {np.median(at_join[:, role == k]):.0f}" for k in range(1 + svc))
+              + " | waited at the join: " + ", ".join(f"{names[k]} {np.median(wait_join[:, role == k]):.0f}" for k in range(1 + svc)))
+    at_barrier = s[:, :, k_barrier] - s[:, :, 0]
+    print("cycles from entry to the barrier, median by role: " + ", ".join(f"{names[k]} {np.median(at_barrier[:, role == k]):.0f}" for k in range(1 + svc))
+          + " | waited at the barrier: " + ", ".join(f"{np.median((s[:, :, k_barrier + 1] - s[:, :, k_barrier])[:, role == k]):.0f}" for k in range(1 + svc)))
     refill = s_all[:, waves::wpg]                    # wave 0 of every refill workgroup (all zero in the speculative form)
     if refill[:, :, 9].max() > 0:
         ent, ext = (refill[:, :, 8] - t0) * 10.0, (refill[:, :, 9] - t0) * 10.0
