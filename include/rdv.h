@@ -345,6 +345,14 @@ int rdv_diagnose(rdv_handle h, double* diag_out, void* stream);
  * rdv_eval_begin writes the k = 0 entries from the current state (after rdv_reset / rdv_set_state, as the evaluators do);
  * rdv_eval_summary reduces the batch to the twelve means the callback logs (:285-298) with one wavefront reduction per 64 envs
  * (synchronises `stream`).
+ *
+ * On a RESET or CONTINUE handle rdv_step accepts `eval` too, and what it accumulates is this: every executed transition is added
+ * with the diagnostics of its post-step, PRE-reset state, so the sums, counts and minima run on across episode boundaries (RESET: over
+ * all the episodes an env plays; CONTINUE: over the steps past the end).  Entry 4 holds the time within the episode in which the first
+ * KOZ step fell; the start state of a later episode (its k = 0 sample) is never added; a level's block never restarts.  These are
+ * per-env totals over everything stepped since rdv_eval_begin, not the evaluators' per-episode records: rdv_eval_summary and
+ * rdv_eval_group_summary divide by the step count of the episode an env is in (end_time / dt, 0 right after a reset), so
+ * ep_collision_percentage and ep_avg_att_error are the reference's quantities in halt mode only.
  */
 typedef struct RdvEvalSummary {
   double ep_rew, ep_len, ep_dist, ep_delta_v, ep_delta_w, ep_success, ep_collision_percentage;

@@ -165,9 +165,25 @@ class OracleModel:
 
     # ---- the per-env evaluation accumulators of the product (include/rdv.h, rdv_eval_begin), restated in NumPy from the oracle's
     # diagnostics: an independent statement of the same bookkeeping (custom_callbacks.py:211-267, monte_carlo.py:117-189)
+    def row_params(self, field):
+        """[N] the scalar parameter `field` of every env's own set: its group's while grouped, the handle's otherwise."""
+        if self.groups is None:
+            return np.full(self.n, getattr(self.params, field))
+        sets, sizes = self.groups
+        return np.concatenate([np.full(s.stop - s.start, getattr(sets[g], field))
+                               for s, g in zip(self.slices, group_tile_table(self.n, sizes))])
+
+    def group_rows(self, group):
+        """The envs of parameter group `group` as a slice; refused as rdv_eval_group_summary refuses (include/rdv.h)."""
+        n_groups = 0 if self.groups is None else len(self.groups[1])
+        if not 0 <= int(group) < n_groups:
+            raise ValueError(f"rdv_eval_group_summary: group {int(group)} of {n_groups}")
+        starts = np.concatenate([[0], np.cumsum(self.groups[1])])
+        return slice(int(starts[int(group)]), int(starts[int(group) + 1]))
+
     def _levels(self, d):
-        p = self.params
-        pm, vm, am, rm = d[:, 0] < p.max_rd_error, d[:, 1] < p.max_vd_error, d[:, 2] < p.max_qd_error, d[:, 3] < p.max_wd_error
+        lim = [self.row_params(f) for f in ("max_rd_error", "max_vd_error", "max_qd_error", "max_wd_error")]
+        pm, vm, am, rm = d[:, 0] < lim[0], d[:, 1] < lim[1], d[:, 2] < lim[2], d[:, 3] < lim[3]      # monte_carlo.py:159-162, strict
         return [pm & vm & am & rm, (pm & vm & am) | (pm & vm & rm), pm & vm, pm]
 
     def eval_begin(self):
@@ -203,11 +219,13 @@ class OracleModel:
             acc[on, 12 + 5 * L] += 1
             acc[on, 13 + 5 * L: 17 + 5 * L] += d[on, 0:4]
 
-    def eval_summary(self):
-        acc, p = self._acc, self.params
-        aux, st = self.get_aux(), self.get_state()
-        steps = aux[:, 0] / p.dt
-        m = self.n
+    def eval_summary(self, rows=None):
+        """custom_callbacks.py:254-298 over the envs `rows` (a slice; None: the whole batch), every env's times in its own set's dt."""
+        rows = slice(None) if rows is None else rows
+        acc, dt = self._acc[rows], self.row_params("dt")[rows]
+        aux, st = self.get_aux()[rows], self.get_state()[rows]
+        steps = aux[:, 0] / dt                                                                       # :255
+        m = len(acc)
         nanmean = lambda x: -1.0 if np.all(np.isnan(x)) else float(np.nanmean(x))
         return {"ep_rew": acc[:, 0].mean(), "ep_len": aux[:, 0].mean(), "ep_dist": np.linalg.norm(st[:, 0:3], axis=1).mean(),
                 "ep_delta_v": aux[:, 4].mean(), "ep_delta_w": aux[:, 5].mean(), "ep_success": aux[:, 3].mean(),
@@ -240,8 +258,8 @@ class OracleEngine:
         self.eval = torch.from_numpy(self._orc.eval_begin())
         return self.eval
 
-    def eval_summary(self):
-        return self._orc.eval_summary()
+    def eval_summary(self, group=None):
+        return self._orc.eval_summary(None if group is None else self._orc.group_rows(group))
 
     def step(self, actions, diag=False, accumulate=False):
         diag = diag or accumulate
