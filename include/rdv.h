@@ -770,6 +770,54 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
                           const RdvPpoSetOut* out, void* stream);
 
 /*
+ * PPO minibatch gradients for every MLP architecture (added within ABI 5: additive exports): rdv_ppo_loss_grad for handles of ANY
+ * RdvMlpSpec — 1..4 hidden layers of 16 / 32 / 64, tanh, ReLU or sigmoid, everything rdv_policy_create_mlp and rdv_critic_create_mlp
+ * accept (csrc/rdv_ppo_mlp.h).  Actor and critic may differ in depth, widths and activation (SB3's net_arch = dict(pi=..., vf=...)).
+ * rdv_ppo_loss_grad, rdv_ppo_spec_check, rdv_ppo_workspace_bytes and the set form are unchanged, their refusals included.
+ *
+ * rdv_ppo_mlp_spec_check (host-only): RDV_OK for two specs that each pass rdv_mlp_spec_check; a null pointer is
+ *   RDV_ERR_INVALID_ARGUMENT naming the argument, anything else the message of rdv_mlp_spec_check behind "actor: " or "critic: ".
+ * rdv_ppo_mlp_grad_floats (host-only): the length of a net's flat gradient — per layer w[out, in] then b[out], hidden layers first, the
+ *   head last, every matrix in nn.Linear's [out, in] order; for an actor (is_actor != 0) log_std[6] follows.  The default spec: 5708 and
+ *   5377, the layout of RdvPpoOut above.  A 16-wide layer has 16 rows: the padded rows of its tile have no entry.  -1 for a bad spec.
+ * rdv_ppo_mlp_workspace_bytes (host-only): the workspace a call with handles of these specs and n samples needs; -1 for n <= 0 or a
+ *   bad spec; monotone in n, a multiple of 16; for the default pair at least rdv_ppo_workspace_bytes (n).
+ * rdv_ppo_mlp_loss_grad: rows, out (actor_grad and critic_grad of the lengths above), the scalars, log_prob and values as in
+ *   rdv_ppo_loss_grad.
+ *
+ * The contract is that of rdv_ppo_loss_grad, restated for any spec:
+ *   - The mathematics, PyTorch's min / clamp sub-gradient rule, the float-rounded clip limits and the NaN rule are the ones above.
+ *   - What is differentiated is the function the forward kernels compute: the two-term fp16 weights of the handle's block as of stream
+ *     order, observations clamped to +-63 (also in the contraction that gives the first layer's weight gradient), the bias added behind
+ *     the products.  The activation's derivative is taken from the forward's own activation h: tanh 1 - h^2; sigmoid h (1 - h); ReLU 1
+ *     where 0 < h < 63 and 0 elsewhere — PyTorch's 0 at the kink, and 0 where the kernel's [0, 63] cap acted.
+ *   - out->values is bit-identical to what rdv_policy_value writes for the same rows, and the means inside the call are those of
+ *     rdv_policy_act with deterministic = 1 before the clip: the forward half is the device code of those kernels (the hidden layers
+ *     are recomputed in front of each backward step: the same code, the same bits).
+ *   - Determinism: no floating-point atomic; per-wave sums in wave order, per-workgroup sums through the workspace in index order; the
+ *     same bits eager or replayed from a captured graph.  A workgroup owns 256 rows, or 128 where the net's parameter block leaves
+ *     the CU's LDS no room for eight waves — a function of that net's spec alone, so the bits depend on the specs and the inputs only.
+ *   - Enqueue only: no allocation, no synchronisation, no host-to-device copy; legal inside a stream capture.  The workspace is the
+ *     caller's, 16-byte aligned, not shared with a call in flight on another stream.
+ *   - Accuracy: tests/test_gpu_ppo_mlp_grad.py holds every gradient tensor to err = max|G - G64| / max|G64| <= C max(e32, 2^-23), e32
+ *     the same quantity for PyTorch's float32 autograd.  Measured (profiles/ppo_mlp_grad_accuracy.csv, n up to 549): the largest
+ *     err / max(e32, 2^-23) of a gradient tensor is 8.47, at n = 1, where the lone sample's log_prob error scales every actor gradient
+ *     (5.37 over n >= 33): C = 32; of a scalar 39.8: C = 128.  Larger n has not been measured under the rule for these kernels.
+ *   - Handles of the default spec (the shipped block and kernels): the call IS rdv_ppo_loss_grad, its bits and, past this call's own
+ *     checks, its refusals.  One default-spec handle paired with a general one is refused (RDV_ERR_INVALID_ARGUMENT).
+ *   - Order of checks: first the host-only ones, RDV_ERR_INVALID_ARGUMENT naming the argument — a null rows, out or required pointer,
+ *     n <= 0, rows->rows <= 0, n > rows->rows without indices, a misaligned rows->obs or workspace, the three coefficients; then
+ *     RDV_ERR_BAD_HANDLE for an invalid handle; then RDV_ERR_INVALID_ARGUMENT for a recurrent handle, a policy set of more than one
+ *     member, actor and critic swapped, handles on different devices, the mixed pair, and — the requirement depends on the handles'
+ *     specs — a short workspace.  A refused call enqueues nothing and leaves the handles as they were.
+ */
+int rdv_ppo_mlp_spec_check(const RdvMlpSpec* actor_spec_host, const RdvMlpSpec* critic_spec_host);
+int64_t rdv_ppo_mlp_grad_floats(const RdvMlpSpec* spec_host, int is_actor);
+int64_t rdv_ppo_mlp_workspace_bytes(const RdvMlpSpec* actor_spec_host, const RdvMlpSpec* critic_spec_host, int64_t n);
+int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef,
+                          double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream);
+
+/*
  * The recurrent policy (added within ABI 5: additive exports): what the reference's main_rnn.py trains and tune_policy.py:80, :140-148
  * and tune_algorithm.py:68 build — sb3-contrib RecurrentPPO("MlpLstmPolicy"), i.e. RecurrentActorCriticPolicy with ONE LSTM layer of
  * lstm_hidden_size H in front of the mlp_extractor trunk, and separate LSTMs for actor and critic (shared_lstm = False,

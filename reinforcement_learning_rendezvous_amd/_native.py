@@ -45,7 +45,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # PPO minibatch gradients (added within ABI 5)
            "rdv_ppo_workspace_bytes", "rdv_ppo_spec_check", "rdv_ppo_loss_grad",
            # PPO minibatch gradients for policy sets (added within ABI 5)
-           "rdv_ppo_set_workspace_bytes", "rdv_ppo_set_loss_grad"]
+           "rdv_ppo_set_workspace_bytes", "rdv_ppo_set_loss_grad",
+           # PPO minibatch gradients for every MLP architecture (added within ABI 5)
+           "rdv_ppo_mlp_spec_check", "rdv_ppo_mlp_grad_floats", "rdv_ppo_mlp_workspace_bytes", "rdv_ppo_mlp_loss_grad"]
 
 
 class RdvError(RuntimeError):
@@ -99,7 +101,7 @@ class PpoRows(C.Structure):
 
 
 class PpoOut(C.Structure):
-    """RdvPpoOut: device pointers of what rdv_ppo_loss_grad writes (log_prob and values nullable)"""
+    """RdvPpoOut: device pointers of what rdv_ppo_loss_grad / rdv_ppo_mlp_loss_grad write (log_prob and values nullable)"""
     _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
                 ("values", C.c_void_p)]
 
@@ -152,7 +154,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the ten translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
+    """Compile the eleven translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip, rdv_ppo_mlp.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -254,6 +256,10 @@ def lib():
         "rdv_ppo_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), i64, C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoOut), vp]),
         "rdv_ppo_set_workspace_bytes": (i64, [i32, C.POINTER(i64)]),
         "rdv_ppo_set_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), C.POINTER(i64), C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoSetOut), vp]),
+        "rdv_ppo_mlp_spec_check": (C.c_int, [C.POINTER(MlpSpec), C.POINTER(MlpSpec)]),
+        "rdv_ppo_mlp_grad_floats": (i64, [C.POINTER(MlpSpec), C.c_int]),
+        "rdv_ppo_mlp_workspace_bytes": (i64, [C.POINTER(MlpSpec), C.POINTER(MlpSpec), i64]),
+        "rdv_ppo_mlp_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), i64, C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

@@ -1,8 +1,8 @@
 // rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
 // value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
-// rdv_rollout_advantages, rdv_ppo_*, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
+// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_*, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
-// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch), so an edit to an argument check recompiles no kernel.
+// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch), so an edit to an argument check recompiles no kernel.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
@@ -10,11 +10,13 @@
 #include "rdv_policy_sets.h"
 #include "rdv_advantages.h"
 #include "rdv_ppo.h"
+#include "rdv_ppo_mlp.h"
 #include "rdv_host.h"
 
 #include <cstdio>
 #include <cstdlib>
 #include <new>
+#include <string>
 
 using namespace rdv;
 
@@ -658,6 +660,105 @@ int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* row
                  (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)clip_range, (float)ent_coef, (float)vf_coef,
                  static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
   ppo_launch(a, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- PPO minibatch gradients for every MLP architecture (csrc/rdv_ppo_mlp.h)
+int rdv_ppo_mlp_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec) {
+  if (!actor_spec || !critic_spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_mlp_spec_check: null %s", !actor_spec ? "actor_spec" : "critic_spec");
+  const struct { const RdvMlpSpec* s; const char* name; } nets[] = {{actor_spec, "actor"}, {critic_spec, "critic"}};
+  for (const auto& a : nets)
+    if (int rc = rdv_mlp_spec_check(a.s)) {
+      const std::string why = rdv_last_error();
+      return fail(rc, "rdv_ppo_mlp_spec_check: %s: %s", a.name, why.c_str());
+    }
+  return RDV_OK;
+}
+
+// (a bad spec: the two size queries answer -1; rdv_last_error holds rdv_mlp_spec_check's reason)
+static bool mlp_spec_ok(const RdvMlpSpec* spec) { return rdv_mlp_spec_check(spec) == RDV_OK; }
+static bool is_default_spec(const RdvMlpSpec& spec) { return std::memcmp(&spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0; }
+
+int64_t rdv_ppo_mlp_grad_floats(const RdvMlpSpec* spec, int is_actor) {
+  if (!mlp_spec_ok(spec)) return -1;
+  PpoMlpTable t;
+  ppo_mlp_table(*spec, is_actor != 0, t);
+  return t.grad_floats;
+}
+
+// the general layout's bytes; a default pair runs the shipped kernels, whose workspace (smaller: the same rows, shorter backward blocks) it covers
+static int64_t ppo_mlp_bytes(const RdvMlpSpec& actor_spec, const RdvMlpSpec& critic_spec, int64_t n) {
+  PpoMlpTable a, c;
+  ppo_mlp_table(actor_spec, true, a);
+  ppo_mlp_table(critic_spec, false, c);
+  int64_t bytes = ppo_mlp_workspace_floats(a, c, n) * (int64_t)sizeof(float);
+  if (is_default_spec(actor_spec) && is_default_spec(critic_spec) && bytes < ppo_workspace_bytes(n)) bytes = ppo_workspace_bytes(n);
+  return bytes;
+}
+int64_t rdv_ppo_mlp_workspace_bytes(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec, int64_t n) {
+  if (n <= 0 || !mlp_spec_ok(actor_spec) || !mlp_spec_ok(critic_spec)) return -1;
+  return ppo_mlp_bytes(*actor_spec, *critic_spec, n);
+}
+
+static int raise_ppo_mlp_lds_limit(int device) {
+  static bool raised[64] = {};
+  if (device >= 64 || !raised[device]) {
+    RDV_HIP(ppo_mlp_raise_lds_limit());
+    if (device < 64) raised[device] = true;
+  }
+  return RDV_OK;
+}
+
+int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef, double vf_coef,
+                          void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream) {
+  const char* who = "rdv_ppo_mlp_loss_grad";
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
+  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"},
+                                                              {rows->advantages, "rows->advantages"}, {rows->returns, "rows->returns"},
+                                                              {out->actor_grad, "out->actor_grad"}, {out->critic_grad, "out->critic_grad"},
+                                                              {out->scalars, "out->scalars"}, {workspace, "workspace"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
+  if (n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
+  if (rows->rows <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->rows must be positive (got %lld)", who, (long long)rows->rows);
+  if (!rows->indices && n > rows->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n = %lld exceeds rows->rows = %lld and rows->indices is null", who, (long long)n, (long long)rows->rows);
+  if (misaligned(rows->obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->obs must be 16-byte aligned", who);
+  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
+  RDV_CHECK_POLICY(actor);
+  RDV_CHECK_POLICY(critic);
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor, "actor"}, {critic, "critic"}};
+  for (const auto& a : nets) {
+    if (a.p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a recurrent policy: its gradients are not built", who, a.name);
+    if (a.p->n_members > 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a policy set of %d members: its gradients are not built (the shipped architecture: rdv_ppo_set_loss_grad)", who, a.name, a.p->n_members);
+  }
+  if (actor->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor is a critic handle (rdv_critic_create_mlp): actor and critic are swapped", who);
+  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic is an actor handle (rdv_policy_create_mlp): actor and critic are swapped", who);
+  if (actor->device != critic->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor on device %d, critic on device %d", who, actor->device, critic->device);
+  if (actor->shipped_arch != critic->shipped_arch)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle has the default spec (the shipped block and kernels), the %s handle another: the mixed pair is not built", who,
+                actor->shipped_arch ? "actor" : "critic", actor->shipped_arch ? "critic" : "actor");
+  const int64_t need = ppo_mlp_bytes(actor->spec, critic->spec, n);
+  if (workspace_bytes < need)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, n = %lld and these specs need %lld (rdv_ppo_mlp_workspace_bytes)", who, (long long)workspace_bytes, (long long)n, (long long)need);
+  // the default pair: the shipped blocks and the kernels of rdv_ppo_loss_grad, its bits
+  if (actor->shipped_arch) return rdv_ppo_loss_grad(actor, critic, rows, n, clip_range, ent_coef, vf_coef, workspace, workspace_bytes, out, stream);
+  PpoMlpLaunch a = {};
+  ppo_mlp_table(actor->spec, true, a.actor);
+  ppo_mlp_table(critic->spec, false, a.critic);
+  if (a.actor.block_floats != actor->block_floats || a.critic.block_floats != critic->block_floats)
+    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor->block_floats, critic->block_floats, a.actor.block_floats, a.critic.block_floats);
+  DeviceGuard guard(actor->device);
+  if (int rc = raise_ppo_mlp_lds_limit(actor->device)) return rc;
+  a.actor_block = actor->weights; a.critic_block = critic->weights; a.actor_act = actor->spec.activation; a.critic_act = critic->spec.activation;
+  a.obs = rows->obs; a.actions = rows->actions; a.old_log_prob = rows->old_log_prob; a.advantages = rows->advantages; a.returns = rows->returns;
+  a.indices = rows->indices; a.n = n;
+  a.clip_lo = (float)(1.0 - clip_range); a.clip_hi = (float)(1.0 + clip_range); a.clip_range = (float)clip_range;
+  a.ent_coef = (float)ent_coef; a.vf_coef = (float)vf_coef;
+  a.workspace = static_cast<float*>(workspace);
+  a.actor_grad = out->actor_grad; a.critic_grad = out->critic_grad; a.scalars = out->scalars; a.log_prob = out->log_prob; a.values = out->values;
+  ppo_mlp_launch(a, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }

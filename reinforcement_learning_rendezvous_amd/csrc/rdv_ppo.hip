@@ -3,6 +3,7 @@
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_ppo.h"
+#include "rdv_ppo_ops.h"
 
 #include <type_traits>
 
@@ -98,28 +99,6 @@ __device__ __forceinline__ void ppo_forward(const float* w, const float* rows, i
   mean[0] = d3[0][0] * s3; mean[1] = d3[0][1] * s3; mean[2] = d3[0][2] * s3; mean[3] = d3[0][3] * s3;
 }
 
-__device__ __forceinline__ float wave_sum(float v) {   // the same tree every time: deterministic
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
-  return v;
-}
-// The wave's power-of-two scale for a tensor whose largest |entry| in this lane is `m`: S with (wave max) * S in [2^13, 2^14), and 1 / S.
-// fmaxf drops NaNs, so a NaN entry does not decide the scale (it stays a NaN through the split and the products); all zeros: S = 2^126.
-__device__ __forceinline__ void wave_scale(float m, float& S, float& invS) {
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) m = fmaxf(m, __shfl_xor(m, off));
-  const int e = (int)((__float_as_uint(m) >> 23) & 0xffu);
-  int se = 127 + 13 - (e - 127);
-  se = se < 2 ? 2 : (se > 253 ? 253 : se);
-  S = __uint_as_float((uint32_t)se << 23);
-  invS = __uint_as_float((uint32_t)(254 - se) << 23);
-}
-__device__ __forceinline__ float tile_max(const float (&v)[16]) {
-  float m = 0.0f;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) m = fmaxf(m, fabsf(v[e]));
-  return m;
-}
 // an error tile (accumulator order, already scaled) as the B fragments of the next backward layer's k-steps 2 t, 2 t + 1
 __device__ __forceinline__ void error_frags(const float (&v)[16], f16x8 (&lo_step)[2], f16x8 (&hi_step)[2]) {
   float x[8];
@@ -135,27 +114,6 @@ __device__ __forceinline__ void error_tile(const f32x16& pre, const float (&hs)[
   constexpr float inv = 1.0f / (float)(1 << kPolXShift);
 #pragma unroll
   for (int e = 0; e < 16; ++e) { const float hv = hs[e] * inv; delta[e] = pre[e] * (1.0f - hv * hv) * unscale; }
-}
-
-// A tile in accumulator order (lane = row r, register e = feature (e & 3) + 8 (e >> 2) + 4 h) -> the LDS operand tile [term][feature][row]
-__device__ __forceinline__ void stage_tile(_Float16* tile, const float (&v)[16], int lane) {
-  const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int f = (e & 3) + 8 * (e >> 2) + 4 * h;
-    const _Float16 hi = (_Float16)v[e];
-    const _Float16 lo = (_Float16)(v[e] - (float)hi);
-    tile[f * 32 + r] = hi;
-    tile[32 * 32 + f * 32 + r] = lo;
-  }
-}
-// the fragments of both k-steps (rows 16 s + 8 h + j) of a staged tile: lane (feature r, h) reads 16 bytes per term and k-step
-__device__ __forceinline__ void load_frags(const _Float16* tile, int lane, f16x8 (&f)[2][2]) {
-  const int r = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int s = 0; s < 2; ++s)
-#pragma unroll
-    for (int q = 0; q < 2; ++q) f[s][q] = *reinterpret_cast<const f16x8*>(tile + q * 32 * 32 + r * 32 + 16 * s + 8 * h);
 }
 
 // dW = delta . B^T for one layer: MT row tiles of delta (accumulator order, scaled by the wave's S), NT staged B tiles (this wave's tiles 0

@@ -1,0 +1,489 @@
+// rdv_ppo_mlp.hip — the kernels of rdv_ppo_mlp.h and their launch, in a translation unit of its own (the objects of the other units do
+// not change when it does).  The exported rdv_ppo_mlp_* entry points are in rdv_policy_host.hip, with the other policy entry points.
+#define RDV_POLICY_FUNCTIONS_ONLY
+#include "rdv_ppo_mlp.h"
+#include "rdv_ppo_ops.h"
+
+namespace rdv {
+
+// LDS of ppo_mlp_net_kernel (floats), W = waves of the workgroup (8 or 4, ppo_mlp_waves):
+//   parameter block | per wave: observation rows [32][17] | per wave: three operand tiles | per wave: 4 scalar sums.
+// An operand tile is [term hi, lo][feature 32][row 32] fp16 = 4 KiB = 1,024 floats, as in rdv_ppo.hip: tiles 0, 1 of a wave hold the B
+// operand (h_l, up to 64 features), tile 2 the A operand (32 features of delta_l) and then, as [32][32] fp32, the wave's product.
+constexpr int kTile = 1024, kWaveTiles = 3 * kTile;
+static_assert(kPolObsStage + kWaveTiles + 4 == kPpoMlpWaveFloats, "a wave's share of the LDS");
+static_assert((kMlpMaxFloats + 4 * kPpoMlpWaveFloats) * 4 <= kPpoMlpLdsLimit, "the largest block with four waves fits the CU's LDS");
+
+// ---- 1. the transposed fragments of one net.  Backward fragment (q, mt, ks) of layer l, lane (r, h), element j:
+//   W_l,q[o][i],  o = perm(ks, h, j) (the k order of an accumulator tile used as B operand),  i = 32 mt + r,
+// read from where the forward block keeps it: fragment frag0_l + (q MT_l + (o >> 5)) KS_l + ks(i), lane (o & 31, h(i)), element j(i) — the
+// inverse of perm — or zero where the forward layer has no such tile row or k-step (a 16-wide neighbour).
+__global__ __launch_bounds__(512) void ppo_mlp_transpose_kernel(const float* __restrict__ actor_block, const float* __restrict__ critic_block,
+                                                                float* __restrict__ workspace) {
+  const float* block = blockIdx.y == 0 ? actor_block : critic_block;
+  float* dstf = workspace + (size_t)blockIdx.y * kPpoMlpBwdFloats;
+  const int b = blockIdx.x, t = threadIdx.x;
+  if (b == kPpoMlpBwdFrags) { if (t < 64) dstf[kPpoMlpBwdZero + t] = 0.0f; return; }
+  const int32_t* H = reinterpret_cast<const int32_t*>(block);
+  const int L = H[0];
+  int l = 0, base = 0, MTh = 1, KSd = 1;
+  for (int k = 1, at = 0; k <= L; ++k) {
+    const int mth = H[kMlpRec + kMlpRecStride * (k - 1) + 2], ksd = k < L ? H[kMlpRec + kMlpRecStride * (k + 1) + 3] : 1;
+    const int count = 2 * mth * ksd;
+    if (b >= at && b < at + count) { l = k; base = at; MTh = mth; KSd = ksd; }
+    at += count;
+  }
+  if (l == 0) return;                                     // a fragment slot this architecture does not use
+  const int32_t* rec = H + kMlpRec + kMlpRecStride * l;
+  const int frag0 = rec[0], MT = rec[2], KS = rec[3];
+  const int bb = b - base, q = bb / (MTh * KSd), mt = (bb / KSd) % MTh, ks = bb % KSd;
+  const int lane = t >> 3, j = t & 7, r = lane & 31, h = lane >> 5;
+  const int o = 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3), i = 32 * mt + r;
+  const int ks_i = (i >> 5) * 2 + ((i >> 4) & 1), h_i = (i >> 2) & 1, j_i = ((i >> 3) & 1) * 4 + (i & 3);
+  uint16_t v = 0;
+  if ((o >> 5) < MT && ks_i < KS) {
+    const uint16_t* src = reinterpret_cast<const uint16_t*>(block + kMlpHdr);
+    v = src[((size_t)(frag0 + (q * MT + (o >> 5)) * KS + ks_i) * 64 + (size_t)((o & 31) + 32 * h_i)) * 8 + j_i];
+  }
+  reinterpret_cast<uint16_t*>(dstf)[((size_t)b * 64 + lane) * 8 + j] = v;
+}
+
+// ---- 2, 3. one net's loss terms and gradients
+struct PpoMlpNetArgs {
+  const float *block, *bwd;      // forward parameter block, backward block (workspace)
+  const float *obs, *actions, *old_log_prob, *advantages, *returns;
+  const int64_t* indices;
+  int64_t n;
+  float clip_lo, clip_hi, clip_range, vf2;   // vf2 = 2 vf_coef
+  float* parts;                  // [workgroups][T.part_floats]
+  float* out;                    // nullable [n]: log_prob (actor) or values (critic)
+  PpoMlpTable T;
+};
+
+// mlp_activate of rdv_policy_mlp.h — the same operations in the same order — that also keeps the activations (times 2^10)
+template <int ACT>
+__device__ __forceinline__ void mlp_activate_keep(const f32x16& d, float k, f16x8 (&lo_step)[2], f16x8 (&hi_step)[2], float (&hs)[16]) {
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) mlp_act2<ACT>(d[j], d[j + 1], k, x[j], x[j + 1]);
+  split2(x, lo_step);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) hs[j] = x[j];
+#pragma unroll
+  for (int j = 0; j < 8; j += 2) mlp_act2<ACT>(d[8 + j], d[9 + j], k, x[j], x[j + 1]);
+  split2(x, hi_step);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) hs[8 + j] = x[j];
+}
+// mlp_hidden with the activations of its MT tiles kept
+template <int ACT, int MT, int KS>
+__device__ __forceinline__ void mlp_hidden_keep(const float* wf, const float* zerop, int frag0, const float* biasp, float k, int lane, f16x8 (&x)[4][2],
+                                                float (&hs)[2][16]) {
+  f16x8 xin[KS][2];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) { xin[ks][0] = x[ks][0]; xin[ks][1] = x[ks][1]; }
+  f32x16 d[MT];
+  layer<MT, KS>(wf, frag0, zerop, xin, lane, d);
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    mlp_add_bias(d[mt], biasp + (mt * 2 + (lane >> 5)) * 16);
+    mlp_activate_keep<ACT>(d[mt], k, x[2 * mt], x[2 * mt + 1], hs[mt]);
+  }
+}
+// mlp_means up to hidden layer `upto` (1 .. L): x <- the B fragments of h_upto, hs <- h_upto (times 2^10) in accumulator order
+template <int ACT>
+__device__ __forceinline__ void mlp_forward_keep(const float* w, const int32_t* __restrict__ H, const float* rows, int lane, int upto, f16x8 (&x)[4][2],
+                                                 float (&hs)[2][16]) {
+  const float* wf = w + kMlpHdr;
+  const float* zerop = w + kMlpZero;
+  {
+    f16x8 x0[2][2];
+    actor_inputs(rows, lane, x0);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) { x[0][q] = x0[0][q]; x[1][q] = x0[1][q]; x[2][q] = (f16x8)(0); x[3][q] = (f16x8)(0); }
+  }
+#pragma nounroll
+  for (int l = 0; l < upto; ++l) {
+    const int32_t* rec = H + kMlpRec + kMlpRecStride * l;
+    const int frag0 = rec[0];
+    const float* biasp = w + rec[1];
+    const float k = mlp_act_const<ACT>(__int_as_float(rec[4]));
+    switch (rec[2] * 8 + rec[3]) {
+      case 8 + 1: mlp_hidden_keep<ACT, 1, 1>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 8 + 2: mlp_hidden_keep<ACT, 1, 2>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 8 + 4: mlp_hidden_keep<ACT, 1, 4>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 16 + 1: mlp_hidden_keep<ACT, 2, 1>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 16 + 2: mlp_hidden_keep<ACT, 2, 2>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      default: mlp_hidden_keep<ACT, 2, 4>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+    }
+  }
+}
+
+// The derivative of the activation from the forward's own activation (hs = h 2^10): tanh 1 - h^2; sigmoid h (1 - h); ReLU 1 where
+// 0 < h < 63 — PyTorch's 0 at the kink, and 0 where the kernel's [0, 63] cap acted.  A NaN activation gives 0 for the ReLU; the error it
+// multiplies is a NaN already (the NaN reached the head), and NaN x 0 stays NaN.
+template <int ACT>
+__device__ __forceinline__ float mlp_act_derivative(float hs) {
+  constexpr float one = (float)(1 << kPolXShift), inv = 1.0f / one;
+  if (ACT == RDV_ACT_RELU) return (hs > 0.0f && hs < 63.0f * one) ? 1.0f : 0.0f;
+  const float hv = hs * inv;
+  if (ACT == RDV_ACT_TANH) return 1.0f - hv * hv;
+  return hv * (1.0f - hv);
+}
+
+// registers 8 s .. 8 s + 7 of an error tile (accumulator order, already scaled) as the B fragments of k-step s of the next backward layer
+__device__ __forceinline__ void error_frags(const float (&v)[16], int s, f16x8 (&step)[2]) {
+  float x[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x[j] = v[8 * s + j];
+  split2(x, step);
+}
+
+// dW = delta . B^T for one layer: MT row tiles of delta (accumulator order, scaled by the wave's S), NT staged B tiles (this wave's tiles 0
+// .. NT-1, features times 2^10) and one more column tile of ones (times 2^10), whose column 0 holds the row sums (bias gradients).
+// Per (mt, nt): the wave's product, unscaled, -> its tile 2 as [32][32] fp32; barrier; the workgroup's `nw` waves' tiles added in wave
+// order, element (row 32 mt + m, column 32 nt + c) handed to store(row, col, sum) (the ones tile: store(row, -1 - c, sum)); barrier.
+// Every wave of the workgroup takes part.
+template <int MT, int NT, class Store>
+__device__ __forceinline__ void weight_grads(const float (&delta)[2][16], float* wave_tiles, const float* tiles0, int nw, float unscale, int lane, Store store) {
+  _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
+  float* prod = wave_tiles + 2 * kTile;
+  const int c = lane & 31, h = lane >> 5;
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    stage_tile(tb + 2 * (2 * kTile), delta[mt], lane);
+    wave_fence();
+    f16x8 a[2][2];
+    load_frags(tb + 2 * (2 * kTile), lane, a);
+#pragma unroll
+    for (int nt = 0; nt <= NT; ++nt) {
+      f16x8 b[2][2];
+      if (nt < NT) {
+        load_frags(tb + nt * (2 * kTile), lane, b);
+      } else {
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+          for (int j = 0; j < 8; ++j) { b[s][0][j] = (_Float16)(float)(1 << kPolXShift); b[s][1][j] = (_Float16)0.0f; }
+      }
+      f32x16 acc;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
+      acc = mfma3(a[0], b[0], acc);
+      acc = mfma3(a[1], b[1], acc);
+      wave_fence();
+#pragma unroll
+      for (int e = 0; e < 16; ++e) prod[((e & 3) + 8 * (e >> 2) + 4 * h) * 32 + c] = acc[e] * unscale;
+      __syncthreads();
+      for (int el = (int)threadIdx.x; el < kTile; el += nw * 64) {
+        float sum = 0.0f;
+        for (int wv = 0; wv < nw; ++wv) sum += tiles0[wv * kWaveTiles + 2 * kTile + el];
+        store(32 * mt + (el >> 5), nt < NT ? 32 * nt + (el & 31) : -1 - (el & 31), sum);
+      }
+      __syncthreads();
+    }
+  }
+}
+
+// One backward step, layer l >= 1 (l == L: the head), MTh tiles of h_l, KSd k-steps and MTd tiles of delta_l (KSd = 4 <=> MTd = 2):
+//   dl (delta_l times n, in) is scaled by the wave's S;  pre = W_l^T dl (the forward's `layer` on the transposed fragments);
+//   delta_{l-1} = pre o act'(h_l) 2^-s_l / S;  dW_l, db_l (the head of an actor: d log_std from tile rows 8..13) -> the workgroup's row;
+//   dl <- delta_{l-1}.
+template <int ACT, bool ACTOR, int MTh, int KSd>
+__device__ __forceinline__ void backward_step(const PpoMlpTable& T, int l, const float* bwd, float inv_acc, float (&dl)[2][16], const float (&hs)[2][16],
+                                              float* wave_tiles, const float* tiles0, int nw, int lane, float* part) {
+  constexpr int MTd = KSd == 4 ? 2 : 1;
+  constexpr float xs = (float)(1 << kPolXShift), inv_xs = 1.0f / xs;
+  const bool head = l == T.L;
+  float S, invS;
+  wave_scale(MTd == 2 ? fmaxf(tile_max(dl[0]), tile_max(dl[1])) : tile_max(dl[0]), S, invS);
+#pragma unroll
+  for (int mt = 0; mt < MTd; ++mt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dl[mt][e] *= S;
+  float nd[MTh][16];
+  {
+    f16x8 b[KSd][2];
+    if constexpr (KSd == 1) {
+      float x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = (head && j >= 4) ? 0.0f : dl[0][j];   // the head's d log_std terms stay out of the product
+      split2(x, b[0]);
+    } else {
+#pragma unroll
+      for (int s = 0; s < KSd; ++s) error_frags(dl[s >> 1], s & 1, b[s]);
+    }
+    f32x16 pre[MTh];
+    layer<MTh, KSd>(bwd, T.bfrag[l], bwd + kPpoMlpBwdZero, b, lane, pre);
+    const float un = inv_acc * xs * invS;                                      // 2^-s_l / S
+#pragma unroll
+    for (int mt = 0; mt < MTh; ++mt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) nd[mt][e] = pre[mt][e] * mlp_act_derivative<ACT>(hs[mt][e]) * un;
+  }
+  {
+    _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
+#pragma unroll
+    for (int mt = 0; mt < MTh; ++mt) stage_tile(tb + mt * (2 * kTile), hs[mt], lane);
+    const int w_off = T.w_off[l], b_off = T.b_off[l], in_w = T.in_w[l], out_w = T.out_w[l], ls_off = T.ls_off;
+    weight_grads<MTd, MTh>(dl, wave_tiles, tiles0, nw, invS * inv_xs, lane, [&](int row, int col, float v) {
+      if (col >= 0) { if (row < out_w && col < in_w) part[w_off + row * in_w + col] = v; }
+      else if (col == -1) {
+        if (row < out_w) part[b_off + row] = v;
+        if (ACTOR && head && row >= 8 && row < 8 + kPolOut) part[ls_off + (row - 8)] = v;
+      }
+    });
+  }
+#pragma unroll
+  for (int mt = 0; mt < MTh; ++mt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dl[mt][e] = nd[mt][e];
+}
+
+// layer 0: dW_0 = delta_0 . x^T with the staged observation rows as the forward pass reads them (times 2^10, clamped to +-63), db_0
+template <int MTd>
+__device__ __forceinline__ void input_step(const PpoMlpTable& T, float (&dl)[2][16], const float* rows, float* wave_tiles, const float* tiles0, int nw,
+                                           int lane, float* part) {
+  constexpr float xs = (float)(1 << kPolXShift), inv_xs = 1.0f / xs, xmax = 63.0f * xs;
+  const int r = lane & 31, h = lane >> 5;
+  float S, invS;
+  wave_scale(MTd == 2 ? fmaxf(tile_max(dl[0]), tile_max(dl[1])) : tile_max(dl[0]), S, invS);
+#pragma unroll
+  for (int mt = 0; mt < MTd; ++mt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dl[mt][e] *= S;
+  float xin[16];
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int f = (e & 3) + 8 * (e >> 2) + 4 * h;
+    const float v = f < kPolIn ? rows[r * kPolIn + f] : 0.0f;
+    const float cl = __builtin_amdgcn_fmed3f(v * xs, -xmax, xmax);
+    xin[e] = v != v ? v : cl;
+  }
+  stage_tile(reinterpret_cast<_Float16*>(wave_tiles), xin, lane);
+  const int w_off = T.w_off[0], b_off = T.b_off[0], out_w = T.out_w[0];
+  weight_grads<MTd, 1>(dl, wave_tiles, tiles0, nw, invS * inv_xs, lane, [&](int row, int col, float v) {
+    if (col >= 0) { if (row < out_w && col < kPolIn) part[w_off + row * kPolIn + col] = v; }
+    else if (col == -1 && row < out_w) part[b_off + row] = v;
+  });
+}
+
+// The workgroup has blockDim.x / 64 waves (T.waves), each 32 rows; trailing waves of the last workgroup have no rows and stay (barriers).
+template <int ACT, bool ACTOR>
+__global__ __launch_bounds__(kPolBlock) void ppo_mlp_net_kernel(const PpoMlpNetArgs A) {
+  extern __shared__ __attribute__((aligned(16))) float lds[];
+  const PpoMlpTable& T = A.T;
+  const int32_t* H = reinterpret_cast<const int32_t*>(A.block);
+  const int total = T.block_floats, L = T.L, nw = T.waves;
+  float* w = lds;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  float* rows = lds + total + wv * kPolObsStage;
+  float* tiles0 = lds + total + nw * kPolObsStage;
+  float* wave_tiles = tiles0 + wv * kWaveTiles;
+  float* red = tiles0 + nw * kWaveTiles;
+  const int64_t wave_base = ((int64_t)blockIdx.x * nw + wv) * kPolWaveEnvs;
+  const int64_t left = A.n - wave_base;
+  const int nrows = left < 0 ? 0 : (left < kPolWaveEnvs ? (int)left : kPolWaveEnvs);
+
+  for (int q = threadIdx.x; q < total / 4; q += nw * 64)
+    *reinterpret_cast<float4*>(w + 4 * q) = *reinterpret_cast<const float4*>(A.block + 4 * q);
+
+  // ---- the wave's observation rows (missing rows = 0: finite activations, and their errors are zero)
+  if (!A.indices && nrows > 0) {
+    stage_obs_rows(A.obs, wave_base, nrows, rows, lane);
+  } else {
+    for (int j = 0; j < 9; ++j) {
+      const int idx = j * 64 + lane;
+      if (idx < kPolObsStage) {
+        const int row = idx / kPolIn, col = idx - row * kPolIn;
+        rows[idx] = row < nrows ? A.obs[A.indices[wave_base + row] * kPolIn + col] : 0.0f;
+      }
+    }
+  }
+  const bool valid = r < nrows;
+  const int64_t src = valid ? (A.indices ? A.indices[wave_base + r] : wave_base + r) : 0;
+  __syncthreads();
+
+  float* part = A.parts + (size_t)blockIdx.x * T.part_floats;
+  f16x8 x[4][2];
+  float hs[2][16], dl[2][16];
+#pragma unroll
+  for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) { hs[mt][e] = 0.0f; dl[mt][e] = 0.0f; }
+
+#pragma nounroll
+  for (int l = L; l >= 1; --l) {
+    mlp_forward_keep<ACT>(w, H, rows, lane, l, x, hs);     // h_l, recomputed: the forward's own operations
+    const int32_t* rec = H + kMlpRec + kMlpRecStride * l;
+    if (l == L) {
+      // ---- the head and the loss terms of this lane's row: the head's error (times n) in registers 0..3 of the tile, the d log_std terms
+      // in registers 4..7 (actor), the scalar sums
+      float mean[4];
+      {
+        const float* wf = w + kMlpHdr;
+        const float* zerop = w + kMlpZero;
+        const float* biasp = w + rec[1];
+        const float inv = __int_as_float(rec[4]);
+        switch (rec[3]) {
+          case 1: mlp_head<1>(wf, zerop, rec[0], biasp, inv, lane, x, mean); break;
+          case 2: mlp_head<2>(wf, zerop, rec[0], biasp, inv, lane, x, mean); break;
+          default: mlp_head<4>(wf, zerop, rec[0], biasp, inv, lane, x, mean); break;
+        }
+      }
+      float d3[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ex[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      float sums[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+      if constexpr (ACTOR) {
+        const float* sd = w + kMlpStd;
+        float dm[4], dls[4], lp = 0.0f;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const bool comp = valid && (h == 0 || c < 2);                     // the upper half holds components 4, 5 only
+          const float act = comp ? A.actions[src * kPolOut + 4 * h + c] : mean[c];
+          const float sdv = comp ? sd[4 * h + c] : 1.0f, ls = comp ? sd[8 + 4 * h + c] : 0.0f;
+          const float var = sdv * sdv, d = act - mean[c], t = d * d / (2.0f * var);
+          lp += comp ? (-t - ls) : 0.0f;
+          dm[c] = comp ? d / var : 0.0f;                                   // d log_prob / d mean_c
+          dls[c] = comp ? 2.0f * t - 1.0f : 0.0f;                          // d log_prob / d log_std_c
+        }
+        lp = (lp + __shfl_xor(lp, 32)) - 5.5136312f;                        // - 6/2 log(2 pi)
+        float g = 0.0f;
+        if (valid) {
+          const float old = A.old_log_prob[src], adv = A.advantages[src];
+          const float diff = lp - old, ratio = expf(diff);
+          const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, A.clip_lo), A.clip_hi);
+          // PyTorch's backward of min(s1, s2) and clamp (the rule of include/rdv.h): a tie halves the gradient between the two, clamp passes it
+          // inside the inclusive limits; comparisons with a NaN are false, so a NaN row keeps its gradient path and poisons the sums
+          const float g1 = s1 == s2 ? 0.5f : (s1 > s2 ? 0.0f : 1.0f), g2 = s1 == s2 ? 0.5f : (s2 > s1 ? 0.0f : 1.0f);
+          const float gc = (ratio >= A.clip_lo && ratio <= A.clip_hi) ? 1.0f : 0.0f;
+          g = -(adv * (g1 + g2 * gc)) * ratio;                              // d (n policy_loss) / d log_prob
+          if (h == 0) {
+            sums[0] = -((s1 < s2 || s1 != s1) ? s1 : s2);
+            sums[1] = (ratio - 1.0f) - diff;
+            sums[2] = fabsf(ratio - 1.0f) > A.clip_range ? 1.0f : 0.0f;
+            if (A.out) A.out[wave_base + r] = lp;
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) { d3[c] = g * dm[c]; ex[c] = g * dls[c]; }
+      } else {
+        if (valid && h == 0) {
+          const float diff = mean[0] - A.returns[src];
+          d3[0] = A.vf2 * diff;
+          sums[3] = diff * diff;
+          if (A.out) A.out[wave_base + r] = mean[0];
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) sums[k] = wave_sum(sums[k]);
+      if (lane == 0) { red[wv * 4 + 0] = sums[0]; red[wv * 4 + 1] = sums[1]; red[wv * 4 + 2] = sums[2]; red[wv * 4 + 3] = sums[3]; }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) { dl[0][c] = d3[c]; dl[0][4 + c] = ex[c]; }   // features 4 h + c, and 8 + 4 h + c
+    }
+    const float inv_acc = __int_as_float(rec[4]);
+    const int MTh = T.mt[l - 1], KSd = l < L ? T.ks[l + 1] : 1;
+    switch (MTh * 8 + KSd) {
+      case 8 + 1: backward_step<ACT, ACTOR, 1, 1>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
+      case 8 + 2: backward_step<ACT, ACTOR, 1, 2>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
+      case 8 + 4: backward_step<ACT, ACTOR, 1, 4>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
+      case 16 + 1: backward_step<ACT, ACTOR, 2, 1>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
+      case 16 + 2: backward_step<ACT, ACTOR, 2, 2>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
+      default: backward_step<ACT, ACTOR, 2, 4>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
+    }
+    if (l == L) {
+      // the workgroup's scalar sums (red[] is behind a barrier by now), waves in order
+      if (threadIdx.x < 4 && (ACTOR ? threadIdx.x < 3 : threadIdx.x == 3)) {
+        float sum = 0.0f;
+        for (int k = 0; k < nw; ++k) sum += red[k * 4 + threadIdx.x];
+        part[T.part_floats - 4 + threadIdx.x] = sum;
+      }
+    }
+  }
+  if (T.mt[0] == 2) input_step<2>(T, dl, rows, wave_tiles, tiles0, nw, lane, part);
+  else input_step<1>(T, dl, rows, wave_tiles, tiles0, nw, lane, part);
+}
+
+// ---- 4. the workgroups' rows added in index order -> the gradients (divided by n; - ent_coef on d log_std) and the scalars
+struct PpoMlpFinishArgs {
+  const float *actor_parts, *critic_parts;
+  int64_t actor_groups, critic_groups, n;
+  int32_t actor_stride, critic_stride, actor_floats, critic_floats;
+  const float* actor_block;
+  float ent_coef, vf_coef;
+  float *actor_grad, *critic_grad, *scalars;
+};
+__global__ __launch_bounds__(256) void ppo_mlp_finish_kernel(const PpoMlpFinishArgs F) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  const float fn = (float)F.n;
+  if (i < F.actor_floats) {
+    float sum = 0.0f;
+    for (int64_t g = 0; g < F.actor_groups; ++g) sum += F.actor_parts[g * F.actor_stride + i];
+    float v = sum / fn;
+    if (i >= F.actor_floats - kPolOut) v -= F.ent_coef;
+    F.actor_grad[i] = v;
+  } else if (i < F.actor_floats + F.critic_floats) {
+    const int k = i - F.actor_floats;
+    float sum = 0.0f;
+    for (int64_t g = 0; g < F.critic_groups; ++g) sum += F.critic_parts[g * F.critic_stride + k];
+    F.critic_grad[k] = sum / fn;
+  } else if (i == F.actor_floats + F.critic_floats) {
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t g = 0; g < F.actor_groups; ++g)
+      for (int k = 0; k < 3; ++k) s[k] += (double)F.actor_parts[g * F.actor_stride + F.actor_stride - 4 + k];
+    for (int64_t g = 0; g < F.critic_groups; ++g) s[3] += (double)F.critic_parts[g * F.critic_stride + F.critic_stride - 1];
+    const double dn = (double)F.n, policy = s[0] / dn, value = s[3] / dn;
+    double entropy = 0.0;
+    for (int c = 0; c < kPolOut; ++c) entropy += 0.5 + 0.5 * 1.8378770664093453 + (double)F.actor_block[kMlpStd + 8 + c];
+    const double entropy_loss = -entropy;
+    F.scalars[0] = (float)(policy + (double)F.ent_coef * entropy_loss + (double)F.vf_coef * value);
+    F.scalars[1] = (float)policy; F.scalars[2] = (float)value; F.scalars[3] = (float)entropy_loss;
+    F.scalars[4] = (float)(s[1] / dn); F.scalars[5] = (float)(s[2] / dn); F.scalars[6] = 0.0f; F.scalars[7] = 0.0f;
+  }
+}
+
+template <bool ACTOR>
+static const void* net_kernel_of(int activation) {
+  switch (activation) {
+    case RDV_ACT_RELU: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_RELU, ACTOR>);
+    case RDV_ACT_SIGMOID: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_SIGMOID, ACTOR>);
+    default: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_TANH, ACTOR>);
+  }
+}
+
+hipError_t ppo_mlp_raise_lds_limit() {
+  for (int act = 0; act < 3; ++act) {
+    hipError_t err = hipFuncSetAttribute(net_kernel_of<true>(act), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMlpLdsLimit);
+    if (err == hipSuccess) err = hipFuncSetAttribute(net_kernel_of<false>(act), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMlpLdsLimit);
+    if (err != hipSuccess) return err;
+  }
+  return hipSuccess;
+}
+
+template <bool ACTOR>
+static void launch_net(int activation, const PpoMlpNetArgs& net, int64_t groups, hipStream_t s) {
+  const dim3 grid((unsigned)groups), block((unsigned)(net.T.waves * 64));
+  const int lds = ppo_mlp_lds_bytes(net.T);
+  switch (activation) {
+    case RDV_ACT_RELU: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_RELU, ACTOR>), grid, block, lds, s, net); break;
+    case RDV_ACT_SIGMOID: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_SIGMOID, ACTOR>), grid, block, lds, s, net); break;
+    default: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_TANH, ACTOR>), grid, block, lds, s, net); break;
+  }
+}
+
+void ppo_mlp_launch(const PpoMlpLaunch& a, hipStream_t s) {
+  const int64_t groups_a = ppo_mlp_workgroups(a.actor, a.n), groups_c = ppo_mlp_workgroups(a.critic, a.n);
+  float* parts_a = a.workspace + 2 * kPpoMlpBwdFloats;
+  float* parts_c = parts_a + groups_a * a.actor.part_floats;
+  hipLaunchKernelGGL(ppo_mlp_transpose_kernel, dim3(kPpoMlpBwdFrags + 1, 2), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace);
+  PpoMlpNetArgs net = {a.actor_block, a.workspace, a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, a.indices, a.n,
+                       a.clip_lo, a.clip_hi, a.clip_range, 2.0f * a.vf_coef, parts_a, a.log_prob, a.actor};
+  launch_net<true>(a.actor_act, net, groups_a, s);
+  net.block = a.critic_block; net.bwd = a.workspace + kPpoMlpBwdFloats; net.parts = parts_c; net.out = a.values; net.T = a.critic;
+  launch_net<false>(a.critic_act, net, groups_c, s);
+  const PpoMlpFinishArgs F = {parts_a, parts_c, groups_a, groups_c, a.n, a.actor.part_floats, a.critic.part_floats, a.actor.grad_floats,
+                              a.critic.grad_floats, a.actor_block, a.ent_coef, a.vf_coef, a.actor_grad, a.critic_grad, a.scalars};
+  const int total = a.actor.grad_floats + a.critic.grad_floats + 1;
+  hipLaunchKernelGGL(ppo_mlp_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, F);
+}
+
+}  // namespace rdv

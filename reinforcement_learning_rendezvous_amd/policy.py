@@ -468,9 +468,10 @@ class MlpPolicy(_HipHandles, torch.nn.Module):
         ``clip_grad_norm_(policy.parameters(), 0.5); optimizer.step(); policy.update_weights()`` follow unchanged.  Returns the scalars
         ``loss``, ``policy_loss``, ``value_loss``, ``entropy_loss``, ``approx_kl``, ``clip_fraction`` as 0-dim tensors on the rows'
         device: nothing synchronises.  ``check``: a caller's own ``indices`` are validated with one ``torch.aminmax`` (the kernel does not
-        range-check); pieces of ``ppo_minibatches`` for this row count skip it.  CUDA rows with the shipped 17-64-64 tanh actor and critic:
-        rdv_ppo_loss_grad on the current stream (differentiates the handles' weights as of stream order).  CPU rows,
-        ``backend="torch"`` or another architecture: the same expressions through autograd over these modules."""
+        range-check); pieces of ``ppo_minibatches`` for this row count skip it.  CUDA rows: rdv_ppo_loss_grad (the shipped 17-64-64 tanh actor and
+        critic) or rdv_ppo_mlp_loss_grad (every other architecture the GPU forward serves) on the current stream; both differentiate
+        the handles' weights as of stream order.  CPU rows or ``backend="torch"``: the same expressions through autograd over these
+        modules, as for the one pair the library refuses (one net 64-64 tanh, the other not: ``ppo.hip_route``)."""
         from . import ppo
         return ppo.ppo_grad(self, buf, indices, clip_range, ent_coef, vf_coef, normalize_advantage, check)
 
@@ -613,6 +614,6 @@ class PolicySet(_Members, _HipHandles):
         [P,5377] the set owns; member g's ``.grad`` tensors are views of row g, so per-member ``clip_grad_norm_``, one optimiser over
         all members' parameters and ``update_weights()`` follow unchanged.  Every member's gradients and scalars are bit for bit those
         of its own ``MlpPolicy.ppo_grad`` on the same buffer and indices.  CPU rows, ``backend="torch"`` or another architecture:
-        ``ppo.ppo_grad`` member by member.  Returns a list of P dicts of 0-dim tensors (the scalars of ``ppo_grad``)."""
+        ``ppo.ppo_grad`` member by member (on CUDA rows each member of another architecture takes rdv_ppo_mlp_loss_grad).  Returns a list of P dicts of 0-dim tensors (the scalars of ``ppo_grad``)."""
         from . import ppo
         return ppo.ppo_set_grads(self, buf, indices, clip_range, ent_coef, vf_coef, normalize_advantage, check)

@@ -10,11 +10,13 @@ its gradients (stable_baselines3/ppo/ppo.py, the body of the ``for rollout_data 
             optimizer.step()
             policy.update_weights()
 
-For CUDA rows and the shipped 17-64-64 tanh actor and critic the loss and the gradients are ONE call of the library (rdv_ppo_loss_grad,
-include/rdv.h "PPO minibatch gradients"; csrc/rdv_ppo.h): hand-written MFMA kernels on the current stream, no allocation, no
-synchronisation, legal inside a stream capture.  CPU rows, ``backend="torch"`` and every other architecture run the same expressions
-through autograd over the policy's own modules and fill the same ``.grad`` tensors.  Gradient clipping, the optimiser and its schedules are
-PyTorch's; ``update_weights`` repacks as it always did.
+For CUDA rows the loss and the gradients are ONE call of the library: rdv_ppo_loss_grad for the shipped 17-64-64 tanh actor and critic
+(include/rdv.h "PPO minibatch gradients"; csrc/rdv_ppo.h), rdv_ppo_mlp_loss_grad for every other architecture the GPU forward serves —
+1..4 hidden layers of 16 / 32 / 64, tanh, ReLU or sigmoid, actor and critic of different shapes included ("PPO minibatch gradients for
+every MLP architecture"; csrc/rdv_ppo_mlp.h): hand-written MFMA kernels on the current stream, no allocation, no synchronisation, legal
+inside a stream capture.  CPU rows and ``backend="torch"`` run the same expressions through autograd over the policy's own modules and
+fill the same ``.grad`` tensors; so does the one pair the library refuses, a 64-64 tanh net beside a net of another shape.  Gradient
+clipping, the optimiser and its schedules are PyTorch's; ``update_weights`` repacks as it always did.
 
 A sweep of P learners on one GPU (``PolicySet``, one grouped batch) takes the same step for all members at once:
 
@@ -114,6 +116,29 @@ def _params(policy):
     return actor, critic
 
 
+def _specs(policy):
+    """(actor spec, critic spec) as RdvMlpSpec."""
+    from . import _native as N
+    from .policy import ACTIVATIONS
+    act = ACTIVATIONS[policy.activation][0]
+    return N.MlpSpec.make(policy.pi_arch, act), N.MlpSpec.make(policy.vf_arch, act)
+
+
+def hip_route(policy):
+    """Which library call serves ``ppo_grad`` of this policy on CUDA rows: "shipped" (rdv_ppo_loss_grad: both nets 17-64-64 tanh),
+    "mlp" (rdv_ppo_mlp_loss_grad: both nets of another architecture the GPU forward serves) or None (autograd: a width or depth the
+    forward kernels do not serve, or exactly one net of the shipped shape, the pair rdv_ppo_mlp_loss_grad refuses)."""
+    if policy.l1.in_features != 17:
+        return None
+    served = lambda arch: 1 <= len(arch) <= 4 and all(w in (16, 32, 64) for w in arch)
+    default = [arch == [64, 64] and policy.activation == "tanh" for arch in (policy.pi_arch, policy.vf_arch)]
+    if all(default):
+        return "shipped"
+    if any(default) or not (served(policy.pi_arch) and served(policy.vf_arch)):
+        return None
+    return "mlp"
+
+
 def _state(policy, dev, n, rows):
     """The buffers the policy owns for ppo_grad on device ``dev``: two flat gradient buffers (the parameters' ``.grad`` are views of them
     when the modules live on ``dev``), the scalars, and — HIP path — the workspace and the advantage column, grown when a call needs more."""
@@ -126,7 +151,12 @@ def _state(policy, dev, n, rows):
         policy._ppo[dev] = st
     if n is not None and (st["workspace"] is None or st["n"] < n):
         from . import _native as N
-        st["workspace"] = torch.empty(int(N.lib().rdv_ppo_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        if hip_route(policy) == "mlp":
+            a, c = _specs(policy)
+            need = int(N.lib().rdv_ppo_mlp_workspace_bytes(C.byref(a), C.byref(c), n))
+        else:
+            need = int(N.lib().rdv_ppo_workspace_bytes(n))
+        st["workspace"] = torch.empty(need, dtype=torch.uint8, device=dev)
         st["n"] = n
     if rows is not None and (st["adv"] is None or st["adv"].numel() < rows):
         st["adv"] = torch.zeros(rows, dtype=torch.float32, device=dev)
@@ -192,7 +222,8 @@ def ppo_grad(policy, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.
             lo, hi = (int(x) for x in torch.aminmax(indices))
             if lo < 0 or hi >= rows:
                 raise IndexError(f"ppo_grad: indices span [{lo}, {hi}], the rollout has rows 0..{rows - 1}")
-    hip = policy.backend != "torch" and dev.type == "cuda" and policy.shipped_arch and policy.vf_arch == [64, 64]
+    route = hip_route(policy) if policy.backend != "torch" and dev.type == "cuda" else None
+    hip = route is not None
     take = (lambda t: t[:n]) if indices is None else (lambda t: t[indices])
     adv = take(cols["advantages"])
     if normalize_advantage and n > 1:
@@ -239,8 +270,9 @@ def ppo_grad(policy, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.
                   indices.data_ptr() if indices is not None else None, rows)
     o = N.PpoOut(st["actor"].data_ptr(), st["critic"].data_ptr(), st["scalars"].data_ptr(), None, None)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    N.check(N.lib().rdv_ppo_loss_grad(policy._hip_handle(dev), policy._critic_handle(dev), C.byref(r), n, float(clip_range), float(ent_coef),
-                                      float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    call = N.lib().rdv_ppo_loss_grad if route == "shipped" else N.lib().rdv_ppo_mlp_loss_grad
+    N.check(call(policy._hip_handle(dev), policy._critic_handle(dev), C.byref(r), n, float(clip_range), float(ent_coef),
+                 float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
     _bind_grads(policy, st, dev)
     s = st["scalars"].clone()
     return {name: s[k] for k, name in enumerate(SCALAR_NAMES)}
