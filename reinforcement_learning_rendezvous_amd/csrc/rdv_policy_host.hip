@@ -22,9 +22,10 @@ using namespace rdv;
 
 // the shipped architecture, which IS rdv_policy_create / rdv_critic_create: same block, same kernels, the persistent rollout kernel
 static const RdvMlpSpec kDefaultMlpSpec = {2, {64, 64, 0, 0}, RDV_ACT_TANH, 0};
+static bool is_default_spec(const RdvMlpSpec& spec) { return std::memcmp(&spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0; }
 static bool is_shipped(const RdvMlpSpec* spec) {
 #ifndef RDV_MLP_GENERAL_DEFAULT   // (diagnostic build, tools/mlp_arch_time.py: the shipped architecture through the general kernel, to time the two side by side)
-  return std::memcmp(spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0;
+  return is_default_spec(*spec);
 #else
   return false;
 #endif
@@ -602,7 +603,7 @@ int rdv_ppo_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_sp
   if (int rc = rdv_mlp_spec_check(critic_spec)) return rc;
   const struct { const RdvMlpSpec* s; const char* name; } nets[] = {{actor_spec, "actor"}, {critic_spec, "critic"}};
   for (const auto& a : nets)
-    if (std::memcmp(a.s, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) != 0)
+    if (!is_default_spec(*a.s))
       return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_loss_grad: the %s is not the shipped architecture (two hidden layers of 64, tanh): its gradients are not built", a.name);
   return RDV_OK;
 }
@@ -613,52 +614,94 @@ static int check_ppo_coefficients(const char* who, double clip_range, double ent
   if (!std::isfinite(vf_coef) || vf_coef < 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: vf_coef must be finite and not negative (got %g)", who, vf_coef);
   return RDV_OK;
 }
-// the dynamic-LDS limit of the PPO kernels, plain and set forms, once per device (a host-side attribute: no stream work); the caller's
-// DeviceGuard holds `device`
-static int raise_ppo_lds_limit(int device) {
-  static bool raised[64] = {};
+// The dynamic-LDS limit of one unit's PPO kernels (`raise`: ppo_raise_lds_limit, the plain and the set forms, or ppo_mlp_raise_lds_limit),
+// once per device (`raised`: that unit's flags; a host-side attribute: no stream work); the caller's DeviceGuard holds `device`
+static int raise_ppo_lds_limit(hipError_t (*raise)(), bool (&raised)[64], int device) {
   if (device >= 64 || !raised[device]) {
-    RDV_HIP(ppo_raise_lds_limit());
+    RDV_HIP(raise());
     if (device < 64) raised[device] = true;
   }
   return RDV_OK;
 }
+static bool g_ppo_lds_raised[64], g_ppo_mlp_lds_raised[64];
+
+extern "C++" {   // (two templates: RdvPpoOut / RdvPpoSetOut, and the entry points' own refusals as lambdas)
+// What the three PPO entry points check of their rows, outputs and workspace ahead of everything else, in this order: rows, out and
+// (set_form) counts_host non-null; every pointer the call needs (set_form: rows->indices too); n positive (the plain forms) or no
+// negative count among the `members` counts and a positive one (set_form, which has no n); rows->rows; n against rows->rows where a
+// plain form has no index vector; the two alignments.
+template <class Out>
+static int check_ppo_call(const char* who, const RdvPpoRows* rows, const Out* out, const void* workspace, bool set_form, int64_t n,
+                          int32_t members, const int64_t* counts_host) {
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
+  if (set_form && !counts_host) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host is null", who);
+  const struct { const void* p; const char* name; bool needed; } ptrs[] = {
+      {rows->obs, "rows->obs", true}, {rows->actions, "rows->actions", true}, {rows->old_log_prob, "rows->old_log_prob", true},
+      {rows->advantages, "rows->advantages", true}, {rows->returns, "rows->returns", true}, {rows->indices, "rows->indices", set_form},
+      {out->actor_grad, "out->actor_grad", true}, {out->critic_grad, "out->critic_grad", true}, {out->scalars, "out->scalars", true},
+      {workspace, "workspace", true}};
+  for (const auto& a : ptrs) if (a.needed && !a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
+  if (set_form) {
+    bool any = false;
+    for (int32_t g = 0; g < members; ++g) {
+      if (counts_host[g] < 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host[%d] = %lld is negative", who, g, (long long)counts_host[g]);
+      any = any || counts_host[g] > 0;
+    }
+    if (!any) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host holds no positive count (%d member%s)", who, members, members == 1 ? "" : "s");
+  } else if (n <= 0) {
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
+  }
+  if (rows->rows <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->rows must be positive (got %lld)", who, (long long)rows->rows);
+  if (!set_form && !rows->indices && n > rows->rows)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n = %lld exceeds rows->rows = %lld and rows->indices is null", who, (long long)n, (long long)rows->rows);
+  if (misaligned(rows->obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->obs must be 16-byte aligned", who);
+  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  return RDV_OK;
+}
+
+// The refusals the three entry points make of their pair of handles, in this order: an invalid handle; per net a recurrent one and
+// then what per_net(handle, name) refuses (the plain forms: a set); a swapped pair; what arch() refuses (an entry point's checks of the
+// architecture, made ahead of the devices'); two devices.  W: how this entry point names its two handles and who creates them.
+struct PpoHandleWords { bool set_form; const char *actor, *critic, *critic_creator, *actor_creator; };
+template <class PerNet, class Arch>
+static int check_ppo_handles(const char* who, rdv_policy actor, rdv_policy critic, const PpoHandleWords& W, PerNet per_net, Arch arch) {
+  RDV_CHECK_POLICY(actor);
+  RDV_CHECK_POLICY(critic);
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor, W.actor}, {critic, W.critic}};
+  for (const auto& a : nets) {
+    if (a.p->lstm_hidden)
+      return W.set_form ? fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is a recurrent policy or a recurrent set: its gradients are not built", who, a.name)
+                        : fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a recurrent policy: its gradients are not built", who, a.name);
+    if (int rc = per_net(a.p, a.name)) return rc;
+  }
+  if (actor->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is a critic handle (%s): actor and critic are swapped", who, W.actor, W.critic_creator);
+  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is an actor handle (%s): actor and critic are swapped", who, W.critic, W.actor_creator);
+  if (int rc = arch()) return rc;
+  if (actor->device != critic->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s on device %d, %s on device %d", who, W.actor, actor->device, W.critic, critic->device);
+  return RDV_OK;
+}
+}  // extern "C++"
 
 int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef, double vf_coef,
                       void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream) {
   const char* who = "rdv_ppo_loss_grad";
-  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
-  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
-  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"},
-                                                              {rows->advantages, "rows->advantages"}, {rows->returns, "rows->returns"},
-                                                              {out->actor_grad, "out->actor_grad"}, {out->critic_grad, "out->critic_grad"},
-                                                              {out->scalars, "out->scalars"}, {workspace, "workspace"}};
-  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
-  if (n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
-  if (rows->rows <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->rows must be positive (got %lld)", who, (long long)rows->rows);
-  if (!rows->indices && n > rows->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n = %lld exceeds rows->rows = %lld and rows->indices is null", who, (long long)n, (long long)rows->rows);
-  if (misaligned(rows->obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->obs must be 16-byte aligned", who);
-  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = check_ppo_call(who, rows, out, workspace, false, n, 0, nullptr)) return rc;
   if (workspace_bytes < ppo_workspace_bytes(n))
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, n = %lld needs %lld (rdv_ppo_workspace_bytes)", who, (long long)workspace_bytes, (long long)n, (long long)ppo_workspace_bytes(n));
   if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
-  RDV_CHECK_POLICY(actor);
-  RDV_CHECK_POLICY(critic);
-  const struct { rdv_policy p; const char* name; } nets[] = {{actor, "actor"}, {critic, "critic"}};
-  for (const auto& a : nets) {
-    if (a.p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a recurrent policy: its gradients are not built", who, a.name);
-    if (a.p->n_members > 1 || a.p->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a policy set: its gradients are not built", who, a.name);
-  }
-  if (actor->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor is a critic handle (rdv_critic_create): actor and critic are swapped", who);
-  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic is an actor handle (rdv_policy_create): actor and critic are swapped", who);
-  if (int rc = rdv_ppo_spec_check(&actor->spec, &critic->spec)) return rc;
-  if (!actor->shipped_arch || !critic->shipped_arch) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the handles do not run the shipped kernels", who);
-  if (actor->device != critic->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor on device %d, critic on device %d", who, actor->device, critic->device);
+  auto no_set = [&](rdv_policy p, const char* name) -> int {
+    return p->n_members > 1 || p->rows ? fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a policy set: its gradients are not built", who, name) : RDV_OK;
+  };
+  auto shipped = [&]() -> int {
+    if (int rc = rdv_ppo_spec_check(&actor->spec, &critic->spec)) return rc;
+    return !actor->shipped_arch || !critic->shipped_arch ? fail(RDV_ERR_INVALID_ARGUMENT, "%s: the handles do not run the shipped kernels", who) : RDV_OK;
+  };
+  if (int rc = check_ppo_handles(who, actor, critic, {false, "actor", "critic", "rdv_critic_create", "rdv_policy_create"}, no_set, shipped)) return rc;
   DeviceGuard guard(actor->device);
-  if (int rc = raise_ppo_lds_limit(actor->device)) return rc;
+  if (int rc = raise_ppo_lds_limit(ppo_raise_lds_limit, g_ppo_lds_raised, actor->device)) return rc;
   PpoLaunch a = {actor->weights, critic->weights, rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, n,
-                 (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)clip_range, (float)ent_coef, (float)vf_coef,
-                 static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
+                 ppo_coefs(clip_range, ent_coef, vf_coef), static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
   ppo_launch(a, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
@@ -678,7 +721,6 @@ int rdv_ppo_mlp_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* criti
 
 // (a bad spec: the two size queries answer -1; rdv_last_error holds rdv_mlp_spec_check's reason)
 static bool mlp_spec_ok(const RdvMlpSpec* spec) { return rdv_mlp_spec_check(spec) == RDV_OK; }
-static bool is_default_spec(const RdvMlpSpec& spec) { return std::memcmp(&spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) == 0; }
 
 int64_t rdv_ppo_mlp_grad_floats(const RdvMlpSpec* spec, int is_actor) {
   if (!mlp_spec_ok(spec)) return -1;
@@ -701,41 +743,15 @@ int64_t rdv_ppo_mlp_workspace_bytes(const RdvMlpSpec* actor_spec, const RdvMlpSp
   return ppo_mlp_bytes(*actor_spec, *critic_spec, n);
 }
 
-static int raise_ppo_mlp_lds_limit(int device) {
-  static bool raised[64] = {};
-  if (device >= 64 || !raised[device]) {
-    RDV_HIP(ppo_mlp_raise_lds_limit());
-    if (device < 64) raised[device] = true;
-  }
-  return RDV_OK;
-}
-
 int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef, double vf_coef,
                           void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream) {
   const char* who = "rdv_ppo_mlp_loss_grad";
-  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
-  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
-  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"},
-                                                              {rows->advantages, "rows->advantages"}, {rows->returns, "rows->returns"},
-                                                              {out->actor_grad, "out->actor_grad"}, {out->critic_grad, "out->critic_grad"},
-                                                              {out->scalars, "out->scalars"}, {workspace, "workspace"}};
-  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
-  if (n <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n must be positive (got %lld)", who, (long long)n);
-  if (rows->rows <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->rows must be positive (got %lld)", who, (long long)rows->rows);
-  if (!rows->indices && n > rows->rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: n = %lld exceeds rows->rows = %lld and rows->indices is null", who, (long long)n, (long long)rows->rows);
-  if (misaligned(rows->obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->obs must be 16-byte aligned", who);
-  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = check_ppo_call(who, rows, out, workspace, false, n, 0, nullptr)) return rc;
   if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
-  RDV_CHECK_POLICY(actor);
-  RDV_CHECK_POLICY(critic);
-  const struct { rdv_policy p; const char* name; } nets[] = {{actor, "actor"}, {critic, "critic"}};
-  for (const auto& a : nets) {
-    if (a.p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a recurrent policy: its gradients are not built", who, a.name);
-    if (a.p->n_members > 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a policy set of %d members: its gradients are not built (the shipped architecture: rdv_ppo_set_loss_grad)", who, a.name, a.p->n_members);
-  }
-  if (actor->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor is a critic handle (rdv_critic_create_mlp): actor and critic are swapped", who);
-  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic is an actor handle (rdv_policy_create_mlp): actor and critic are swapped", who);
-  if (actor->device != critic->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor on device %d, critic on device %d", who, actor->device, critic->device);
+  auto no_set = [&](rdv_policy p, const char* name) -> int {
+    return p->n_members > 1 ? fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a policy set of %d members: its gradients are not built (the shipped architecture: rdv_ppo_set_loss_grad)", who, name, p->n_members) : RDV_OK;
+  };
+  if (int rc = check_ppo_handles(who, actor, critic, {false, "actor", "critic", "rdv_critic_create_mlp", "rdv_policy_create_mlp"}, no_set, [] { return RDV_OK; })) return rc;
   if (actor->shipped_arch != critic->shipped_arch)
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle has the default spec (the shipped block and kernels), the %s handle another: the mixed pair is not built", who,
                 actor->shipped_arch ? "actor" : "critic", actor->shipped_arch ? "critic" : "actor");
@@ -744,20 +760,16 @@ int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows*
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, n = %lld and these specs need %lld (rdv_ppo_mlp_workspace_bytes)", who, (long long)workspace_bytes, (long long)n, (long long)need);
   // the default pair: the shipped blocks and the kernels of rdv_ppo_loss_grad, its bits
   if (actor->shipped_arch) return rdv_ppo_loss_grad(actor, critic, rows, n, clip_range, ent_coef, vf_coef, workspace, workspace_bytes, out, stream);
-  PpoMlpLaunch a = {};
-  ppo_mlp_table(actor->spec, true, a.actor);
-  ppo_mlp_table(critic->spec, false, a.critic);
-  if (a.actor.block_floats != actor->block_floats || a.critic.block_floats != critic->block_floats)
-    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor->block_floats, critic->block_floats, a.actor.block_floats, a.critic.block_floats);
+  PpoMlpTable ta, tc;
+  ppo_mlp_table(actor->spec, true, ta);
+  ppo_mlp_table(critic->spec, false, tc);
+  if (ta.block_floats != actor->block_floats || tc.block_floats != critic->block_floats)
+    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor->block_floats, critic->block_floats, ta.block_floats, tc.block_floats);
   DeviceGuard guard(actor->device);
-  if (int rc = raise_ppo_mlp_lds_limit(actor->device)) return rc;
-  a.actor_block = actor->weights; a.critic_block = critic->weights; a.actor_act = actor->spec.activation; a.critic_act = critic->spec.activation;
-  a.obs = rows->obs; a.actions = rows->actions; a.old_log_prob = rows->old_log_prob; a.advantages = rows->advantages; a.returns = rows->returns;
-  a.indices = rows->indices; a.n = n;
-  a.clip_lo = (float)(1.0 - clip_range); a.clip_hi = (float)(1.0 + clip_range); a.clip_range = (float)clip_range;
-  a.ent_coef = (float)ent_coef; a.vf_coef = (float)vf_coef;
-  a.workspace = static_cast<float*>(workspace);
-  a.actor_grad = out->actor_grad; a.critic_grad = out->critic_grad; a.scalars = out->scalars; a.log_prob = out->log_prob; a.values = out->values;
+  if (int rc = raise_ppo_lds_limit(ppo_mlp_raise_lds_limit, g_ppo_mlp_lds_raised, actor->device)) return rc;
+  PpoMlpLaunch a = {actor->weights, critic->weights, actor->spec.activation, critic->spec.activation, ta, tc,
+                    rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, n,
+                    ppo_coefs(clip_range, ent_coef, vf_coef), static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
   ppo_mlp_launch(a, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
@@ -777,52 +789,33 @@ int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_hos
 int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host, double clip_range,
                           double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoSetOut* out, void* stream) {
   const char* who = "rdv_ppo_set_loss_grad";
-  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
-  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
-  if (!counts_host) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host is null", who);
-  const struct { const void* p; const char* name; } ptrs[] = {{rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"},
-                                                              {rows->advantages, "rows->advantages"}, {rows->returns, "rows->returns"},
-                                                              {rows->indices, "rows->indices"}, {out->actor_grad, "out->actor_grad"},
-                                                              {out->critic_grad, "out->critic_grad"}, {out->scalars, "out->scalars"}, {workspace, "workspace"}};
-  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
   // counts_host has one entry per member of the handles; with an invalid actor handle (refused below, behind the host-only checks) it is
   // read as one member's.  A set larger than the cap is refused below, before anything past the cap is looked at.
   const bool valid = actor_set && actor_set->magic == kPolicyMagic;
   const int32_t P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
-  bool any = false;
-  for (int32_t g = 0; g < P; ++g) {
-    if (counts_host[g] < 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host[%d] = %lld is negative", who, g, (long long)counts_host[g]);
-    any = any || counts_host[g] > 0;
-  }
-  if (!any) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host holds no positive count (%d member%s)", who, P, P == 1 ? "" : "s");
-  if (rows->rows <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->rows must be positive (got %lld)", who, (long long)rows->rows);
-  if (misaligned(rows->obs, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->obs must be 16-byte aligned", who);
-  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = check_ppo_call(who, rows, out, workspace, true, 0, P, counts_host)) return rc;
   PpoSetLaunch L = {};
   const int64_t need = ppo_set_table(P, counts_host, &L.table, nullptr, &L.max_workgroups);
   if (workspace_bytes < need)
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, these counts need %lld (rdv_ppo_set_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
   if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
-  RDV_CHECK_POLICY(actor_set);
-  RDV_CHECK_POLICY(critic_set);
-  const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};
-  for (const auto& a : nets)
-    if (a.p->lstm_hidden) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is a recurrent policy or a recurrent set: its gradients are not built", who, a.name);
-  if (actor_set->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set is a critic handle (rdv_critic_set_create): actor and critic are swapped", who);
-  if (critic_set->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic_set is an actor handle (rdv_policy_set_create): actor and critic are swapped", who);
-  for (const auto& a : nets)
-    if (std::memcmp(&a.p->spec, &kDefaultMlpSpec, sizeof(RdvMlpSpec)) != 0 || !a.p->shipped_arch)
-      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not the shipped architecture (two hidden layers of 64, tanh): its gradients are not built", who, a.name);
-  if (actor_set->n_members != critic_set->n_members)
-    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, critic_set has %d", who, actor_set->n_members, critic_set->n_members);
-  if (actor_set->n_members > kPpoSetMaxMembers)
-    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, at most %d are served by one call (kPpoSetMaxMembers)", who, actor_set->n_members, kPpoSetMaxMembers);
-  if (actor_set->device != critic_set->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set on device %d, critic_set on device %d", who, actor_set->device, critic_set->device);
+  auto shipped_sets = [&]() -> int {
+    const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};
+    for (const auto& a : nets)
+      if (!is_default_spec(a.p->spec) || !a.p->shipped_arch)
+        return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not the shipped architecture (two hidden layers of 64, tanh): its gradients are not built", who, a.name);
+    if (actor_set->n_members != critic_set->n_members)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, critic_set has %d", who, actor_set->n_members, critic_set->n_members);
+    if (actor_set->n_members > kPpoSetMaxMembers)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, at most %d are served by one call (kPpoSetMaxMembers)", who, actor_set->n_members, kPpoSetMaxMembers);
+    return RDV_OK;
+  };
+  if (int rc = check_ppo_handles(who, actor_set, critic_set, {true, "actor_set", "critic_set", "rdv_critic_set_create", "rdv_policy_set_create"},
+                                 [](rdv_policy, const char*) { return RDV_OK; }, shipped_sets)) return rc;
   DeviceGuard guard(actor_set->device);
-  if (int rc = raise_ppo_lds_limit(actor_set->device)) return rc;
+  if (int rc = raise_ppo_lds_limit(ppo_raise_lds_limit, g_ppo_lds_raised, actor_set->device)) return rc;
   L.a = {actor_set->weights, critic_set->weights, rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, 0,
-         (float)(1.0 - clip_range), (float)(1.0 + clip_range), (float)clip_range, (float)ent_coef, (float)vf_coef,
-         static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
+         ppo_coefs(clip_range, ent_coef, vf_coef), static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
   L.n_members = P;
   ppo_set_launch(L, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());

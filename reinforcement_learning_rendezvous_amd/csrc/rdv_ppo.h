@@ -47,13 +47,16 @@ constexpr int kPpoBlockRows = 256;     // kPolBlockEnvs
 inline int64_t ppo_workgroups(int64_t n) { return (n + kPpoBlockRows - 1) / kPpoBlockRows; }
 inline int64_t ppo_workspace_bytes(int64_t n) { return (2 * (int64_t)kPpoBwdFloats + ppo_workgroups(n) * kPpoPartFloats) * (int64_t)sizeof(float); }
 
+// the coefficients of a call as the kernels take them, from the entry points' doubles: the clip limits' differences are taken in double
+struct PpoCoefs { float clip_lo, clip_hi, clip_range, ent_coef, vf_coef; };
+inline PpoCoefs ppo_coefs(double eps, double ent_coef, double vf_coef) { return {(float)(1.0 - eps), (float)(1.0 + eps), (float)eps, (float)ent_coef, (float)vf_coef}; }
+
 struct PpoLaunch {
   const float *actor_block, *critic_block;   // the handles' forward parameter blocks (device)
   const float *obs, *actions, *old_log_prob, *advantages, *returns;
   const int64_t* indices;                    // nullable
   int64_t n;
-  float clip_lo, clip_hi, clip_range;        // (float)(1 - eps), (float)(1 + eps), (float)eps: the differences taken in double
-  float ent_coef, vf_coef;
+  PpoCoefs k;
   float* workspace;
   float *actor_grad, *critic_grad, *scalars, *log_prob, *values;
 };

@@ -1,5 +1,7 @@
 // rdv_ppo.hip — the kernels of rdv_ppo.h and their launch, in a translation unit of its own (the objects of the other units do not change
-// when it does).  The exported rdv_ppo_* entry points are in rdv_policy_host.hip, with the other policy entry points.
+// when it does).  The exported rdv_ppo_* entry points are in rdv_policy_host.hip, with the other policy entry points.  This unit holds the
+// shipped architecture's own: its three layers, its forward pass with the activations kept, the set form, the launches.  The gather, the
+// loss terms, the weight-gradient contraction and the other pieces it has in common with rdv_ppo_mlp.hip are the functions of rdv_ppo_ops.h.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_ppo.h"
@@ -9,13 +11,12 @@
 
 namespace rdv {
 
-// LDS of ppo_net_kernel (floats): parameters | per wave: observation rows [32][17] | per wave: three operand tiles | per wave: 4 scalar sums.
-// An operand tile is [term hi, lo][feature 32][row 32] fp16 = 4 KiB = 1,024 floats; tiles 0, 1 of a wave hold the B operand (h_{l-1}, 64
-// features), tile 2 the A operand (32 features of delta_l) and then, as [32][32] fp32, the wave's product of that tile.
-constexpr int kPpoTile = 1024, kPpoWaveTiles = 3 * kPpoTile, kPpoWaves = kPolBlock / 64;
+// LDS of ppo_net_kernel (floats): parameters | per wave: observation rows [32][17] | per wave: three operand tiles | per wave: 4 scalar sums
+// (the tiles and a wave's share: rdv_ppo_ops.h)
+constexpr int kPpoWaves = kPolBlock / 64;
 constexpr int kPpoLdsObs = kPolFloats, kPpoLdsTiles = kPpoLdsObs + kPpoWaves * kPolObsStage, kPpoLdsRed = kPpoLdsTiles + kPpoWaves * kPpoWaveTiles;
-constexpr int kPpoLdsBytes = (kPpoLdsRed + kPpoWaves * 4) * 4;   // 149,328 B: one workgroup per CU
-static_assert(kPpoLdsBytes <= 160 * 1024, "the workgroup's LDS");
+constexpr int kPpoLdsBytes = (kPolFloats + kPpoWaves * kPpoWaveFloats) * 4;   // 149,328 B: one workgroup per CU
+static_assert(kPpoLdsBytes == (kPpoLdsRed + kPpoWaves * 4) * 4 && kPpoLdsBytes <= 160 * 1024, "the workgroup's LDS");
 static_assert(kPpoBlockRows == kPolBlockEnvs, "a workgroup owns 256 rows");
 
 // ---- 1. the transposed fragments.  Backward fragment b of a net, lane (r, h), element j (k order of an accumulator tile used as B
@@ -31,10 +32,9 @@ __device__ __forceinline__ void ppo_transpose_body(const uint16_t* __restrict__ 
   const bool head = b < kPpoBwdW2;
   const int bb = head ? b : b - kPpoBwdW2;
   const int q = head ? bb >> 1 : bb >> 3, mt = head ? bb & 1 : (bb >> 2) & 1, ks = head ? 0 : bb & 3;
-  const int o = 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3), i = 32 * mt + r;
-  const int ks_i = (i >> 5) * 2 + ((i >> 4) & 1), h_i = (i >> 2) & 1, j_i = ((i >> 3) & 1) * 4 + (i & 3);
-  const int frag = head ? kPolW3Frag + q * 4 + ks_i : kPolW2Frag + (q * 2 + (o >> 5)) * 4 + ks_i;
-  reinterpret_cast<uint16_t*>(dstf)[(b * 64 + lane) * 8 + j] = src[(frag * 64 + (o & 31) + 32 * h_i) * 8 + j_i];
+  const PpoTransposeIndex x = ppo_transpose_index(ks, h, j, mt, r);
+  const int frag = head ? kPolW3Frag + q * 4 + x.ks_i : kPolW2Frag + (q * 2 + (x.o >> 5)) * 4 + x.ks_i;
+  reinterpret_cast<uint16_t*>(dstf)[(b * 64 + lane) * 8 + j] = src[(frag * 64 + (x.o & 31) + 32 * x.h_i) * 8 + x.j_i];
 }
 __global__ __launch_bounds__(512) void ppo_transpose_kernel(const float* __restrict__ actor_block, const float* __restrict__ critic_block,
                                                             float* __restrict__ workspace) {
@@ -52,29 +52,10 @@ __global__ __launch_bounds__(512) void ppo_set_transpose_kernel(const float* __r
 // ---- 2, 3. one net's loss terms and gradients
 struct PpoNetArgs {
   const float *block, *bwd;      // forward parameter block, backward block (workspace)
-  const float *obs, *actions, *old_log_prob, *advantages, *returns;
-  const int64_t* indices;
-  int64_t n;
-  float clip_lo, clip_hi, clip_range, vf2;   // vf2 = 2 vf_coef
+  PpoRowArgs rows;
   float* parts;                  // [workgroups][kPpoPartFloats]
   float* out;                    // nullable [n]: log_prob (actor) or values (critic)
 };
-
-// tanh of a (scaled) accumulator tile as `activate` of rdv_policy.h takes it — the same operations in the same order — that also keeps the
-// activations (times 2^10) for the backward pass
-__device__ __forceinline__ void activate_keep(const f32x16& d, float kexp, f16x8 (&lo_step)[2], f16x8 (&hi_step)[2], float (&hs)[16]) {
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) tanh2_f32(d[j], d[j + 1], kexp, x[j], x[j + 1]);
-  split2(x, lo_step);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) hs[j] = x[j];
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) tanh2_f32(d[8 + j], d[9 + j], kexp, x[j], x[j + 1]);
-  split2(x, hi_step);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) hs[8 + j] = x[j];
-}
 
 // actor_means of rdv_policy.h with the hidden activations kept: hs1, hs2 [row tile][accumulator register], times 2^10
 __device__ __forceinline__ void ppo_forward(const float* w, const float* rows, int lane, float (&hs1)[2][16], float (&hs2)[2][16], float (&mean)[4]) {
@@ -85,83 +66,25 @@ __device__ __forceinline__ void ppo_forward(const float* w, const float* rows, i
   layer<2, 2>(w, kPolW1Frag, w + kPolB1, x0, lane, d1);
   f16x8 x1[4][2];
   const float k1 = two_log2e * w[kPolScale + 0];
-  activate_keep(d1[0], k1, x1[0], x1[1], hs1[0]);
-  activate_keep(d1[1], k1, x1[2], x1[3], hs1[1]);
+  ppo_activate_keep<RDV_ACT_TANH>(d1[0], k1, x1[0], x1[1], hs1[0]);
+  ppo_activate_keep<RDV_ACT_TANH>(d1[1], k1, x1[2], x1[3], hs1[1]);
   f32x16 d2[2];
   layer<2, 4>(w, kPolW2Frag, w + kPolB2, x1, lane, d2);
   f16x8 x2[4][2];
   const float k2 = two_log2e * w[kPolScale + 1];
-  activate_keep(d2[0], k2, x2[0], x2[1], hs2[0]);
-  activate_keep(d2[1], k2, x2[2], x2[3], hs2[1]);
+  ppo_activate_keep<RDV_ACT_TANH>(d2[0], k2, x2[0], x2[1], hs2[0]);
+  ppo_activate_keep<RDV_ACT_TANH>(d2[1], k2, x2[2], x2[3], hs2[1]);
   f32x16 d3[1];
   layer<1, 4>(w, kPolW3Frag, w + kPolB3, x2, lane, d3);
   const float s3 = w[kPolScale + 2];
   mean[0] = d3[0][0] * s3; mean[1] = d3[0][1] * s3; mean[2] = d3[0][2] * s3; mean[3] = d3[0][3] * s3;
 }
 
-// an error tile (accumulator order, already scaled) as the B fragments of the next backward layer's k-steps 2 t, 2 t + 1
-__device__ __forceinline__ void error_frags(const float (&v)[16], f16x8 (&lo_step)[2], f16x8 (&hi_step)[2]) {
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = v[j];
-  split2(x, lo_step);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = v[8 + j];
-  split2(x, hi_step);
-}
 // delta = pre o (1 - h^2) * unscale for one tile (hs = h * 2^10)
 __device__ __forceinline__ void error_tile(const f32x16& pre, const float (&hs)[16], float unscale, float (&delta)[16]) {
   constexpr float inv = 1.0f / (float)(1 << kPolXShift);
 #pragma unroll
   for (int e = 0; e < 16; ++e) { const float hv = hs[e] * inv; delta[e] = pre[e] * (1.0f - hv * hv) * unscale; }
-}
-
-// dW = delta . B^T for one layer: MT row tiles of delta (accumulator order, scaled by the wave's S), NT staged B tiles (this wave's tiles 0
-// .. NT-1, features times 2^10) and one more column tile of ones (times 2^10), whose column 0 holds the row sums (bias gradients).
-// Per (mt, nt): the wave's product, unscaled, -> its tile 2 as [32][32] fp32; barrier; the eight waves' tiles added in wave order, element
-// (m, c) handed to store(mt, nt, m, c, sum) (nt == NT: the ones tile); barrier.  Every wave of the workgroup takes part.
-template <int MT, int NT, class Store>
-__device__ __forceinline__ void weight_grads(const float (&delta)[MT][16], float* wave_tiles, const float* tiles0, float unscale, int lane, Store store) {
-  _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
-  float* prod = wave_tiles + 2 * kPpoTile;
-  const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    stage_tile(tb + 2 * (2 * kPpoTile), delta[mt], lane);
-    wave_fence();
-    f16x8 a[2][2];
-    load_frags(tb + 2 * (2 * kPpoTile), lane, a);
-#pragma unroll
-    for (int nt = 0; nt <= NT; ++nt) {
-      f16x8 b[2][2];
-      if (nt < NT) {
-        load_frags(tb + nt * (2 * kPpoTile), lane, b);
-      } else {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { b[s][0][j] = (_Float16)(float)(1 << kPolXShift); b[s][1][j] = (_Float16)0.0f; }
-      }
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-      acc = mfma3(a[0], b[0], acc);
-      acc = mfma3(a[1], b[1], acc);
-      wave_fence();
-#pragma unroll
-      for (int e = 0; e < 16; ++e) prod[((e & 3) + 8 * (e >> 2) + 4 * h) * 32 + c] = acc[e] * unscale;
-      __syncthreads();
-#pragma unroll
-      for (int k = 0; k < 2; ++k) {
-        const int el = (int)threadIdx.x + k * kPolBlock;
-        float sum = 0.0f;
-#pragma unroll
-        for (int wv = 0; wv < kPpoWaves; ++wv) sum += tiles0[wv * kPpoWaveTiles + 2 * kPpoTile + el];
-        store(mt, nt, el >> 5, el & 31, sum);
-      }
-      __syncthreads();
-    }
-  }
 }
 
 // The set form's arguments: `net` holds the set-wide pointers (block: the set's allocation; parts: the workspace; indices and out: all
@@ -182,8 +105,8 @@ __device__ __forceinline__ PpoNetArgs ppo_member_args(const std::conditional_t<S
     PpoNetArgs M = S.net;
     M.block = S.net.block + (size_t)g * kPolFloats;
     M.bwd = ws + (ACTOR ? 0 : kPpoBwdFloats);
-    M.indices = S.net.indices + off;
-    M.n = n;
+    M.rows.indices = S.net.rows.indices + off;
+    M.rows.n = n;
     M.parts = ws + 2 * kPpoBwdFloats;
     M.out = S.net.out ? S.net.out + off : nullptr;
     return M;
@@ -202,84 +125,27 @@ __global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const std::condition
   extern __shared__ __attribute__((aligned(16))) float lds[];
   constexpr int OUT = ACTOR ? kPolOut : 1;
   float* w = lds;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31;
   float* rows = lds + kPpoLdsObs + wv * kPolObsStage;
   float* tiles0 = lds + kPpoLdsTiles;
   float* wave_tiles = tiles0 + wv * kPpoWaveTiles;
   float* red = lds + kPpoLdsRed;
   const int64_t wave_base = ((int64_t)blockIdx.x * kPpoWaves + wv) * kPolWaveEnvs;
-  const int64_t left = A.n - wave_base;
+  const int64_t left = A.rows.n - wave_base;
   const int nrows = left < 0 ? 0 : (left < kPolWaveEnvs ? (int)left : kPolWaveEnvs);   // trailing waves: 0 rows, and they stay (barriers below)
 
   for (int q = threadIdx.x; q < kPolFloats / 4; q += kPolBlock)
     *reinterpret_cast<float4*>(w + 4 * q) = *reinterpret_cast<const float4*>(A.block + 4 * q);
 
-  // ---- the wave's observation rows (missing rows = 0: finite activations, and their errors are zero)
-  if (!A.indices && nrows > 0) {
-    stage_obs_rows(A.obs, wave_base, nrows, rows, lane);
-  } else {
-    for (int j = 0; j < 9; ++j) {
-      const int idx = j * 64 + lane;
-      if (idx < kPolObsStage) {
-        const int row = idx / kPolIn, col = idx - row * kPolIn;
-        rows[idx] = row < nrows ? A.obs[A.indices[wave_base + row] * kPolIn + col] : 0.0f;
-      }
-    }
-  }
-  const bool valid = r < nrows;
-  const int64_t src = valid ? (A.indices ? A.indices[wave_base + r] : wave_base + r) : 0;
+  bool valid;
+  const int64_t src = ppo_gather_rows(A.rows, wave_base, nrows, rows, lane, valid);
   __syncthreads();
 
   float hs1[2][16], hs2[2][16], mean[4];
   ppo_forward(w, rows, lane, hs1, hs2, mean);
 
-  // ---- the loss terms of this lane's row: the head's error (times n) in d3, the d log_std terms in ex (actor), the scalar sums
-  float d3[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ex[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  float sums[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if constexpr (ACTOR) {
-    const float* sd = w + kPolStd;
-    float dm[4], dl[4], lp = 0.0f;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      const bool comp = valid && (h == 0 || c < 2);                     // the upper half holds components 4, 5 only
-      const float act = comp ? A.actions[src * kPolOut + 4 * h + c] : mean[c];
-      const float sdv = comp ? sd[4 * h + c] : 1.0f, ls = comp ? sd[kPolLogStd - kPolStd + 4 * h + c] : 0.0f;
-      const float var = sdv * sdv, d = act - mean[c], t = d * d / (2.0f * var);
-      lp += comp ? (-t - ls) : 0.0f;
-      dm[c] = comp ? d / var : 0.0f;                                   // d log_prob / d mean_c
-      dl[c] = comp ? 2.0f * t - 1.0f : 0.0f;                           // d log_prob / d log_std_c
-    }
-    lp = (lp + __shfl_xor(lp, 32)) - 5.5136312f;                        // - 6/2 log(2 pi)
-    float g = 0.0f;
-    if (valid) {
-      const float old = A.old_log_prob[src], adv = A.advantages[src];
-      const float diff = lp - old, ratio = expf(diff);
-      const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, A.clip_lo), A.clip_hi);
-      // PyTorch's backward of min(s1, s2) and clamp (the rule of include/rdv.h): a tie halves the gradient between the two, clamp passes it
-      // inside the inclusive limits; comparisons with a NaN are false, so a NaN row keeps its gradient path and poisons the sums
-      const float g1 = s1 == s2 ? 0.5f : (s1 > s2 ? 0.0f : 1.0f), g2 = s1 == s2 ? 0.5f : (s2 > s1 ? 0.0f : 1.0f);
-      const float gc = (ratio >= A.clip_lo && ratio <= A.clip_hi) ? 1.0f : 0.0f;
-      g = -(adv * (g1 + g2 * gc)) * ratio;                              // d (n policy_loss) / d log_prob
-      if (h == 0) {
-        sums[0] = -((s1 < s2 || s1 != s1) ? s1 : s2);
-        sums[1] = (ratio - 1.0f) - diff;
-        sums[2] = fabsf(ratio - 1.0f) > A.clip_range ? 1.0f : 0.0f;
-        if (A.out) A.out[wave_base + r] = lp;
-      }
-    }
-#pragma unroll
-    for (int c = 0; c < 4; ++c) { d3[c] = g * dm[c]; ex[c] = g * dl[c]; }
-  } else {
-    if (valid && h == 0) {
-      const float diff = mean[0] - A.returns[src];
-      d3[0] = A.vf2 * diff;
-      sums[3] = diff * diff;
-      if (A.out) A.out[wave_base + r] = mean[0];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < 4; ++k) sums[k] = wave_sum(sums[k]);
-  if (lane == 0) { red[wv * 4 + 0] = sums[0]; red[wv * 4 + 1] = sums[1]; red[wv * 4 + 2] = sums[2]; red[wv * 4 + 3] = sums[3]; }
+  float d3[4], ex[4];
+  ppo_loss_terms<ACTOR>(A.rows, w + kPolStd, w + kPolLogStd, mean, valid, src, A.out, wave_base + r, lane, red + wv * 4, d3, ex);
 
   const float* bwd = A.bwd;
   float* part = A.parts + (size_t)blockIdx.x * kPpoPartFloats + (ACTOR ? 0 : kPpoPartCritic);
@@ -313,21 +179,16 @@ __global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const std::condition
     _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
     stage_tile(tb, hs2[0], lane);
     stage_tile(tb + 2 * kPpoTile, hs2[1], lane);
-    weight_grads<1, 2>(head, wave_tiles, tiles0, invS3 * inv_xs, lane, [&](int, int nt, int m, int c, float v) {
-      if (nt < 2) { if (m < OUT) part[kPpoW3 + m * kPolHid + 32 * nt + c] = v; }
-      else if (c == 0) {
-        if (m < OUT) part[kPpoW3 + OUT * kPolHid + m] = v;
-        if (ACTOR && m >= 8 && m < 8 + kPolOut) part[kPpoW3 + OUT * kPolHid + OUT + (m - 8)] = v;
+    weight_grads<1, 2, kPpoWaves>(head, wave_tiles, tiles0, 0, invS3 * inv_xs, lane, [&](int row, int col, float v) {
+      if (col >= 0) { if (row < OUT) part[kPpoW3 + row * kPolHid + col] = v; }
+      else if (col == -1) {
+        if (row < OUT) part[kPpoW3 + OUT * kPolHid + row] = v;
+        if (ACTOR && row >= 8 && row < 8 + kPolOut) part[kPpoW3 + OUT * kPolHid + OUT + (row - 8)] = v;
       }
     });
   }
-  // the workgroup's scalar sums (red[] is behind a barrier by now), waves in order
-  if (threadIdx.x < 4 && (ACTOR ? threadIdx.x < 3 : threadIdx.x == 3)) {
-    float sum = 0.0f;
-#pragma unroll
-    for (int k = 0; k < kPpoWaves; ++k) sum += red[k * 4 + threadIdx.x];
-    A.parts[(size_t)blockIdx.x * kPpoPartFloats + kPpoPartScalars + threadIdx.x] = sum;
-  }
+  // the workgroup's scalar sums (red[] is behind a barrier by now)
+  ppo_store_scalar_sums<ACTOR>(red, kPpoWaves, A.parts + (size_t)blockIdx.x * kPpoPartFloats + kPpoPartScalars);
 
   // ---- layer 2: delta_1 = (W2^T delta_2) o (1 - h1^2), dW2 / db2
   float S2, invS2;
@@ -339,8 +200,8 @@ __global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const std::condition
   float delta1[2][16];
   {
     f16x8 b2[4][2];
-    error_frags(delta2[0], b2[0], b2[1]);
-    error_frags(delta2[1], b2[2], b2[3]);
+#pragma unroll
+    for (int s = 0; s < 4; ++s) error_frags(delta2[s >> 1], s & 1, b2[s]);
     f32x16 pre[2];
     layer<2, 4>(bwd, kPpoBwdW2, bwd + kPpoBwdZero, b2, lane, pre);
     const float un = w[kPolScale + 1] * xs * invS2;
@@ -351,9 +212,9 @@ __global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const std::condition
     _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
     stage_tile(tb, hs1[0], lane);
     stage_tile(tb + 2 * kPpoTile, hs1[1], lane);
-    weight_grads<2, 2>(delta2, wave_tiles, tiles0, invS2 * inv_xs, lane, [&](int mt, int nt, int m, int c, float v) {
-      if (nt < 2) part[kPpoW2 + (32 * mt + m) * kPolHid + 32 * nt + c] = v;
-      else if (c == 0) part[kPpoB2 + 32 * mt + m] = v;
+    weight_grads<2, 2, kPpoWaves>(delta2, wave_tiles, tiles0, 0, invS2 * inv_xs, lane, [&](int row, int col, float v) {
+      if (col >= 0) part[kPpoW2 + row * kPolHid + col] = v;
+      else if (col == -1) part[kPpoB2 + row] = v;
     });
   }
 
@@ -364,22 +225,13 @@ __global__ __launch_bounds__(kPolBlock) void ppo_net_kernel(const std::condition
   for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
     for (int e = 0; e < 16; ++e) delta1[mt][e] *= S1;
-  {
-    constexpr float xmax = 63.0f * xs;
-    float xin[16];
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int f = (e & 3) + 8 * (e >> 2) + 4 * h;
-      const float v = f < kPolIn ? rows[r * kPolIn + f] : 0.0f;
-      const float cl = __builtin_amdgcn_fmed3f(v * xs, -xmax, xmax);
-      xin[e] = v != v ? v : cl;
-    }
-    stage_tile(reinterpret_cast<_Float16*>(wave_tiles), xin, lane);
-    weight_grads<2, 1>(delta1, wave_tiles, tiles0, invS1 * inv_xs, lane, [&](int mt, int nt, int m, int c, float v) {
-      if (nt < 1) { if (c < kPolIn) part[kPpoW1 + (32 * mt + m) * kPolIn + c] = v; }
-      else if (c == 0) part[kPpoB1 + 32 * mt + m] = v;
-    });
-  }
+  float xin[16];
+  ppo_input_tile(rows, lane, xin);
+  stage_tile(reinterpret_cast<_Float16*>(wave_tiles), xin, lane);
+  weight_grads<2, 1, kPpoWaves>(delta1, wave_tiles, tiles0, 0, invS1 * inv_xs, lane, [&](int row, int col, float v) {
+    if (col >= 0) { if (col < kPolIn) part[kPpoW1 + row * kPolIn + col] = v; }
+    else if (col == -1) part[kPpoB1 + row] = v;
+  });
 }
 
 // ---- 4. the workgroups' rows added in index order -> the gradients (divided by n; - ent_coef on d log_std) and the scalars
@@ -402,13 +254,7 @@ __device__ __forceinline__ void ppo_finish_body(const float* __restrict__ parts,
     double s[4] = {0.0, 0.0, 0.0, 0.0};
     for (int64_t g = 0; g < workgroups; ++g)
       for (int k = 0; k < 4; ++k) s[k] += (double)parts[g * kPpoPartFloats + kPpoPartScalars + k];
-    const double dn = (double)n, policy = s[0] / dn, value = s[3] / dn;
-    double entropy = 0.0;
-    for (int c = 0; c < kPolOut; ++c) entropy += 0.5 + 0.5 * 1.8378770664093453 + (double)actor_block[kPolLogStd + c];
-    const double entropy_loss = -entropy;
-    scalars[0] = (float)(policy + (double)ent_coef * entropy_loss + (double)vf_coef * value);
-    scalars[1] = (float)policy; scalars[2] = (float)value; scalars[3] = (float)entropy_loss;
-    scalars[4] = (float)(s[1] / dn); scalars[5] = (float)(s[2] / dn); scalars[6] = 0.0f; scalars[7] = 0.0f;
+    ppo_finish_scalars(s, n, actor_block + kPolLogStd, ent_coef, vf_coef, scalars);
   }
 }
 __global__ __launch_bounds__(256) void ppo_finish_kernel(const float* __restrict__ parts, int64_t workgroups, int64_t n, const float* __restrict__ actor_block,
@@ -439,13 +285,12 @@ void ppo_launch(const PpoLaunch& a, hipStream_t s) {
   const int64_t groups = ppo_workgroups(a.n);
   float* parts = a.workspace + 2 * kPpoBwdFloats;
   hipLaunchKernelGGL(ppo_transpose_kernel, dim3(kPpoBwdFrags + 1, 2), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace);
-  PpoNetArgs net = {a.actor_block, a.workspace, a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, a.indices, a.n,
-                    a.clip_lo, a.clip_hi, a.clip_range, 2.0f * a.vf_coef, parts, a.log_prob};
+  PpoNetArgs net = {a.actor_block, a.workspace, ppo_row_args(a), parts, a.log_prob};
   hipLaunchKernelGGL((ppo_net_kernel<true, false>), dim3((unsigned)groups), dim3(kPolBlock), kPpoLdsBytes, s, net);
   net.block = a.critic_block; net.bwd = a.workspace + kPpoBwdFloats; net.out = a.values;
   hipLaunchKernelGGL((ppo_net_kernel<false, false>), dim3((unsigned)groups), dim3(kPolBlock), kPpoLdsBytes, s, net);
   const int total = kPpoActorGrad + kPpoCriticGrad + 1;
-  hipLaunchKernelGGL(ppo_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, parts, groups, a.n, a.actor_block, a.ent_coef, a.vf_coef,
+  hipLaunchKernelGGL(ppo_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, parts, groups, a.n, a.actor_block, a.k.ent_coef, a.k.vf_coef,
                      a.actor_grad, a.critic_grad, a.scalars);
 }
 
@@ -453,13 +298,12 @@ void ppo_set_launch(const PpoSetLaunch& L, hipStream_t s) {
   const PpoLaunch& a = L.a;
   const unsigned P = (unsigned)L.n_members;
   hipLaunchKernelGGL(ppo_set_transpose_kernel, dim3(kPpoBwdFrags + 1, 2, P), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace, L.table);
-  PpoSetNetArgs S = {{a.actor_block, nullptr, a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, a.indices, 0,
-                      a.clip_lo, a.clip_hi, a.clip_range, 2.0f * a.vf_coef, a.workspace, a.log_prob}, L.table};
+  PpoSetNetArgs S = {{a.actor_block, nullptr, ppo_row_args(a), a.workspace, a.log_prob}, L.table};   // a.n is 0: the members' counts are the table's
   hipLaunchKernelGGL((ppo_net_kernel<true, true>), dim3((unsigned)L.max_workgroups, P), dim3(kPolBlock), kPpoLdsBytes, s, S);
   S.net.block = a.critic_block; S.net.out = a.values;
   hipLaunchKernelGGL((ppo_net_kernel<false, true>), dim3((unsigned)L.max_workgroups, P), dim3(kPolBlock), kPpoLdsBytes, s, S);
   const int total = kPpoActorGrad + kPpoCriticGrad + 1;
-  hipLaunchKernelGGL(ppo_set_finish_kernel, dim3((total + 255) / 256, P), dim3(256), 0, s, a.workspace, a.actor_block, a.ent_coef, a.vf_coef,
+  hipLaunchKernelGGL(ppo_set_finish_kernel, dim3((total + 255) / 256, P), dim3(256), 0, s, a.workspace, a.actor_block, a.k.ent_coef, a.k.vf_coef,
                      a.actor_grad, a.critic_grad, a.scalars, L.table);
 }
 

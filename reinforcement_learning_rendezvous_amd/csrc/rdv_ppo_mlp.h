@@ -3,8 +3,9 @@
 // gradients for every MLP architecture").  The kernels are in rdv_ppo_mlp.hip, a translation unit of its own; this header holds the sizes,
 // the layer table and the launch that the host unit (rdv_policy_host.hip) needs, and the description.  The scheme is rdv_ppo.h's: the
 // same four launches, the same operands (wave-scaled error tiles split into two fp16 terms, mfma3, the LDS operand tiles of dW), the same
-// sums (waves in order, workgroups in index order); what changes is that the layers are a table and not three lines of code.  The wave
-// reductions, the wave scale and the LDS operand tiles are the functions of rdv_ppo_ops.h, which rdv_ppo.hip uses too.
+// sums (waves in order, workgroups in index order); what changes is that the layers are a table and not three lines of code.  Everything
+// else — the row arguments, a wave's LDS share, the gather, the loss terms, the kept activation, the weight-gradient contraction, the
+// tail of the last kernel — is defined once, in rdv_ppo_ops.h, for this unit and rdv_ppo.hip.
 //
 //   1. ppo_mlp_transpose_kernel: for layers l = 1 .. L (L: the head) the A-operand fragments of W_l^T, derived from the handle's FORWARD
 //      block through its layer table (first fragment, MT, KS per layer) into the head of the workspace.  Fragment (q, mt, ks) of layer l,
@@ -37,13 +38,13 @@
 // a backward block kPpoMlpBwdFloats (the largest: 52 fragments and 64 zeros), part = grad floats rounded up to 4, plus 4 scalar sums.
 #pragma once
 
-#include "rdv_policy_mlp.h"
+#include "rdv_ppo.h"
+#include "rdv_ppo_ops.h"
 
 namespace rdv {
 
 constexpr int kPpoMlpBwdFrags = 4 + 3 * 16;                                  // head 2 x 2 x 1, three 64 -> 64 layers 2 x 2 x 4
 constexpr int kPpoMlpBwdZero = kPpoMlpBwdFrags * 256, kPpoMlpBwdFloats = kPpoMlpBwdZero + 64;   // 13,376 floats
-constexpr int kPpoMlpWaveFloats = kPolObsStage + 3 * 1024 + 4;               // observation rows, three operand tiles, four sums: 14,480 B
 constexpr int kPpoMlpLdsLimit = 160 * 1024;
 static_assert(kPpoMlpBwdFloats % 4 == 0, "the pieces of the workspace are 16-byte aligned");
 
@@ -66,9 +67,9 @@ inline int ppo_mlp_block_floats(const RdvMlpSpec& spec) {
   return kMlpHdr + frags * (kPolFragBytes / 4) + tiles * 32;
 }
 inline int ppo_mlp_waves(const RdvMlpSpec& spec) {
-  return (ppo_mlp_block_floats(spec) + 8 * kPpoMlpWaveFloats) * 4 <= kPpoMlpLdsLimit ? 8 : 4;
+  return (ppo_mlp_block_floats(spec) + 8 * kPpoWaveFloats) * 4 <= kPpoMlpLdsLimit ? 8 : 4;
 }
-inline int ppo_mlp_lds_bytes(const PpoMlpTable& t) { return (t.block_floats + t.waves * kPpoMlpWaveFloats) * 4; }
+inline int ppo_mlp_lds_bytes(const PpoMlpTable& t) { return (t.block_floats + t.waves * kPpoWaveFloats) * 4; }
 
 inline void ppo_mlp_table(const RdvMlpSpec& spec, bool actor, PpoMlpTable& t) {
   const int L = spec.n_hidden, out_dim = actor ? kPolOut : 1;
@@ -105,7 +106,7 @@ struct PpoMlpLaunch {
   const float *obs, *actions, *old_log_prob, *advantages, *returns;
   const int64_t* indices;                    // nullable
   int64_t n;
-  float clip_lo, clip_hi, clip_range, ent_coef, vf_coef;
+  PpoCoefs k;
   float* workspace;
   float *actor_grad, *critic_grad, *scalars, *log_prob, *values;
 };

@@ -1,18 +1,17 @@
 // rdv_ppo_mlp.hip — the kernels of rdv_ppo_mlp.h and their launch, in a translation unit of its own (the objects of the other units do
 // not change when it does).  The exported rdv_ppo_mlp_* entry points are in rdv_policy_host.hip, with the other policy entry points.
+// This unit holds what a table of layers needs: the transposed fragments, the recomputed forward pass, one backward step per (tiles,
+// k-steps) shape, the launches.  The gather, the loss terms, the weight-gradient contraction and the other pieces it has in common with
+// rdv_ppo.hip are the functions of rdv_ppo_ops.h.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_ppo_mlp.h"
-#include "rdv_ppo_ops.h"
 
 namespace rdv {
 
 // LDS of ppo_mlp_net_kernel (floats), W = waves of the workgroup (8 or 4, ppo_mlp_waves):
-//   parameter block | per wave: observation rows [32][17] | per wave: three operand tiles | per wave: 4 scalar sums.
-// An operand tile is [term hi, lo][feature 32][row 32] fp16 = 4 KiB = 1,024 floats, as in rdv_ppo.hip: tiles 0, 1 of a wave hold the B
-// operand (h_l, up to 64 features), tile 2 the A operand (32 features of delta_l) and then, as [32][32] fp32, the wave's product.
-constexpr int kTile = 1024, kWaveTiles = 3 * kTile;
-static_assert(kPolObsStage + kWaveTiles + 4 == kPpoMlpWaveFloats, "a wave's share of the LDS");
-static_assert((kMlpMaxFloats + 4 * kPpoMlpWaveFloats) * 4 <= kPpoMlpLdsLimit, "the largest block with four waves fits the CU's LDS");
+//   parameter block | per wave: observation rows [32][17] | per wave: three operand tiles | per wave: 4 scalar sums
+// (the tiles and a wave's share: rdv_ppo_ops.h)
+static_assert((kMlpMaxFloats + 4 * kPpoWaveFloats) * 4 <= kPpoMlpLdsLimit, "the largest block with four waves fits the CU's LDS");
 
 // ---- 1. the transposed fragments of one net.  Backward fragment (q, mt, ks) of layer l, lane (r, h), element j:
 //   W_l,q[o][i],  o = perm(ks, h, j) (the k order of an accumulator tile used as B operand),  i = 32 mt + r,
@@ -38,12 +37,11 @@ __global__ __launch_bounds__(512) void ppo_mlp_transpose_kernel(const float* __r
   const int frag0 = rec[0], MT = rec[2], KS = rec[3];
   const int bb = b - base, q = bb / (MTh * KSd), mt = (bb / KSd) % MTh, ks = bb % KSd;
   const int lane = t >> 3, j = t & 7, r = lane & 31, h = lane >> 5;
-  const int o = 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3), i = 32 * mt + r;
-  const int ks_i = (i >> 5) * 2 + ((i >> 4) & 1), h_i = (i >> 2) & 1, j_i = ((i >> 3) & 1) * 4 + (i & 3);
+  const PpoTransposeIndex x = ppo_transpose_index(ks, h, j, mt, r);
   uint16_t v = 0;
-  if ((o >> 5) < MT && ks_i < KS) {
+  if ((x.o >> 5) < MT && x.ks_i < KS) {
     const uint16_t* src = reinterpret_cast<const uint16_t*>(block + kMlpHdr);
-    v = src[((size_t)(frag0 + (q * MT + (o >> 5)) * KS + ks_i) * 64 + (size_t)((o & 31) + 32 * h_i)) * 8 + j_i];
+    v = src[((size_t)(frag0 + (q * MT + (x.o >> 5)) * KS + x.ks_i) * 64 + (size_t)((x.o & 31) + 32 * x.h_i)) * 8 + x.j_i];
   }
   reinterpret_cast<uint16_t*>(dstf)[((size_t)b * 64 + lane) * 8 + j] = v;
 }
@@ -51,30 +49,12 @@ __global__ __launch_bounds__(512) void ppo_mlp_transpose_kernel(const float* __r
 // ---- 2, 3. one net's loss terms and gradients
 struct PpoMlpNetArgs {
   const float *block, *bwd;      // forward parameter block, backward block (workspace)
-  const float *obs, *actions, *old_log_prob, *advantages, *returns;
-  const int64_t* indices;
-  int64_t n;
-  float clip_lo, clip_hi, clip_range, vf2;   // vf2 = 2 vf_coef
+  PpoRowArgs rows;
   float* parts;                  // [workgroups][T.part_floats]
   float* out;                    // nullable [n]: log_prob (actor) or values (critic)
   PpoMlpTable T;
 };
 
-// mlp_activate of rdv_policy_mlp.h — the same operations in the same order — that also keeps the activations (times 2^10)
-template <int ACT>
-__device__ __forceinline__ void mlp_activate_keep(const f32x16& d, float k, f16x8 (&lo_step)[2], f16x8 (&hi_step)[2], float (&hs)[16]) {
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) mlp_act2<ACT>(d[j], d[j + 1], k, x[j], x[j + 1]);
-  split2(x, lo_step);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) hs[j] = x[j];
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) mlp_act2<ACT>(d[8 + j], d[9 + j], k, x[j], x[j + 1]);
-  split2(x, hi_step);
-#pragma unroll
-  for (int j = 0; j < 8; ++j) hs[8 + j] = x[j];
-}
 // mlp_hidden with the activations of its MT tiles kept
 template <int ACT, int MT, int KS>
 __device__ __forceinline__ void mlp_hidden_keep(const float* wf, const float* zerop, int frag0, const float* biasp, float k, int lane, f16x8 (&x)[4][2],
@@ -87,7 +67,7 @@ __device__ __forceinline__ void mlp_hidden_keep(const float* wf, const float* ze
 #pragma unroll
   for (int mt = 0; mt < MT; ++mt) {
     mlp_add_bias(d[mt], biasp + (mt * 2 + (lane >> 5)) * 16);
-    mlp_activate_keep<ACT>(d[mt], k, x[2 * mt], x[2 * mt + 1], hs[mt]);
+    ppo_activate_keep<ACT>(d[mt], k, x[2 * mt], x[2 * mt + 1], hs[mt]);
   }
 }
 // mlp_means up to hidden layer `upto` (1 .. L): x <- the B fragments of h_upto, hs <- h_upto (times 2^10) in accumulator order
@@ -131,60 +111,6 @@ __device__ __forceinline__ float mlp_act_derivative(float hs) {
   return hv * (1.0f - hv);
 }
 
-// registers 8 s .. 8 s + 7 of an error tile (accumulator order, already scaled) as the B fragments of k-step s of the next backward layer
-__device__ __forceinline__ void error_frags(const float (&v)[16], int s, f16x8 (&step)[2]) {
-  float x[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) x[j] = v[8 * s + j];
-  split2(x, step);
-}
-
-// dW = delta . B^T for one layer: MT row tiles of delta (accumulator order, scaled by the wave's S), NT staged B tiles (this wave's tiles 0
-// .. NT-1, features times 2^10) and one more column tile of ones (times 2^10), whose column 0 holds the row sums (bias gradients).
-// Per (mt, nt): the wave's product, unscaled, -> its tile 2 as [32][32] fp32; barrier; the workgroup's `nw` waves' tiles added in wave
-// order, element (row 32 mt + m, column 32 nt + c) handed to store(row, col, sum) (the ones tile: store(row, -1 - c, sum)); barrier.
-// Every wave of the workgroup takes part.
-template <int MT, int NT, class Store>
-__device__ __forceinline__ void weight_grads(const float (&delta)[2][16], float* wave_tiles, const float* tiles0, int nw, float unscale, int lane, Store store) {
-  _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
-  float* prod = wave_tiles + 2 * kTile;
-  const int c = lane & 31, h = lane >> 5;
-#pragma unroll
-  for (int mt = 0; mt < MT; ++mt) {
-    stage_tile(tb + 2 * (2 * kTile), delta[mt], lane);
-    wave_fence();
-    f16x8 a[2][2];
-    load_frags(tb + 2 * (2 * kTile), lane, a);
-#pragma unroll
-    for (int nt = 0; nt <= NT; ++nt) {
-      f16x8 b[2][2];
-      if (nt < NT) {
-        load_frags(tb + nt * (2 * kTile), lane, b);
-      } else {
-#pragma unroll
-        for (int s = 0; s < 2; ++s)
-#pragma unroll
-          for (int j = 0; j < 8; ++j) { b[s][0][j] = (_Float16)(float)(1 << kPolXShift); b[s][1][j] = (_Float16)0.0f; }
-      }
-      f32x16 acc;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[e] = 0.0f;
-      acc = mfma3(a[0], b[0], acc);
-      acc = mfma3(a[1], b[1], acc);
-      wave_fence();
-#pragma unroll
-      for (int e = 0; e < 16; ++e) prod[((e & 3) + 8 * (e >> 2) + 4 * h) * 32 + c] = acc[e] * unscale;
-      __syncthreads();
-      for (int el = (int)threadIdx.x; el < kTile; el += nw * 64) {
-        float sum = 0.0f;
-        for (int wv = 0; wv < nw; ++wv) sum += tiles0[wv * kWaveTiles + 2 * kTile + el];
-        store(32 * mt + (el >> 5), nt < NT ? 32 * nt + (el & 31) : -1 - (el & 31), sum);
-      }
-      __syncthreads();
-    }
-  }
-}
-
 // One backward step, layer l >= 1 (l == L: the head), MTh tiles of h_l, KSd k-steps and MTd tiles of delta_l (KSd = 4 <=> MTd = 2):
 //   dl (delta_l times n, in) is scaled by the wave's S;  pre = W_l^T dl (the forward's `layer` on the transposed fragments);
 //   delta_{l-1} = pre o act'(h_l) 2^-s_l / S;  dW_l, db_l (the head of an actor: d log_std from tile rows 8..13) -> the workgroup's row;
@@ -224,9 +150,9 @@ __device__ __forceinline__ void backward_step(const PpoMlpTable& T, int l, const
   {
     _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
 #pragma unroll
-    for (int mt = 0; mt < MTh; ++mt) stage_tile(tb + mt * (2 * kTile), hs[mt], lane);
+    for (int mt = 0; mt < MTh; ++mt) stage_tile(tb + mt * (2 * kPpoTile), hs[mt], lane);
     const int w_off = T.w_off[l], b_off = T.b_off[l], in_w = T.in_w[l], out_w = T.out_w[l], ls_off = T.ls_off;
-    weight_grads<MTd, MTh>(dl, wave_tiles, tiles0, nw, invS * inv_xs, lane, [&](int row, int col, float v) {
+    weight_grads<MTd, MTh, 0>(dl, wave_tiles, tiles0, nw, invS * inv_xs, lane, [&](int row, int col, float v) {
       if (col >= 0) { if (row < out_w && col < in_w) part[w_off + row * in_w + col] = v; }
       else if (col == -1) {
         if (row < out_w) part[b_off + row] = v;
@@ -244,8 +170,7 @@ __device__ __forceinline__ void backward_step(const PpoMlpTable& T, int l, const
 template <int MTd>
 __device__ __forceinline__ void input_step(const PpoMlpTable& T, float (&dl)[2][16], const float* rows, float* wave_tiles, const float* tiles0, int nw,
                                            int lane, float* part) {
-  constexpr float xs = (float)(1 << kPolXShift), inv_xs = 1.0f / xs, xmax = 63.0f * xs;
-  const int r = lane & 31, h = lane >> 5;
+  constexpr float inv_xs = 1.0f / (float)(1 << kPolXShift);
   float S, invS;
   wave_scale(MTd == 2 ? fmaxf(tile_max(dl[0]), tile_max(dl[1])) : tile_max(dl[0]), S, invS);
 #pragma unroll
@@ -253,16 +178,10 @@ __device__ __forceinline__ void input_step(const PpoMlpTable& T, float (&dl)[2][
 #pragma unroll
     for (int e = 0; e < 16; ++e) dl[mt][e] *= S;
   float xin[16];
-#pragma unroll
-  for (int e = 0; e < 16; ++e) {
-    const int f = (e & 3) + 8 * (e >> 2) + 4 * h;
-    const float v = f < kPolIn ? rows[r * kPolIn + f] : 0.0f;
-    const float cl = __builtin_amdgcn_fmed3f(v * xs, -xmax, xmax);
-    xin[e] = v != v ? v : cl;
-  }
+  ppo_input_tile(rows, lane, xin);
   stage_tile(reinterpret_cast<_Float16*>(wave_tiles), xin, lane);
   const int w_off = T.w_off[0], b_off = T.b_off[0], out_w = T.out_w[0];
-  weight_grads<MTd, 1>(dl, wave_tiles, tiles0, nw, invS * inv_xs, lane, [&](int row, int col, float v) {
+  weight_grads<MTd, 1, 0>(dl, wave_tiles, tiles0, nw, invS * inv_xs, lane, [&](int row, int col, float v) {
     if (col >= 0) { if (row < out_w && col < kPolIn) part[w_off + row * kPolIn + col] = v; }
     else if (col == -1 && row < out_w) part[b_off + row] = v;
   });
@@ -276,32 +195,20 @@ __global__ __launch_bounds__(kPolBlock) void ppo_mlp_net_kernel(const PpoMlpNetA
   const int32_t* H = reinterpret_cast<const int32_t*>(A.block);
   const int total = T.block_floats, L = T.L, nw = T.waves;
   float* w = lds;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
+  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31;
   float* rows = lds + total + wv * kPolObsStage;
   float* tiles0 = lds + total + nw * kPolObsStage;
-  float* wave_tiles = tiles0 + wv * kWaveTiles;
-  float* red = tiles0 + nw * kWaveTiles;
+  float* wave_tiles = tiles0 + wv * kPpoWaveTiles;
+  float* red = tiles0 + nw * kPpoWaveTiles;
   const int64_t wave_base = ((int64_t)blockIdx.x * nw + wv) * kPolWaveEnvs;
-  const int64_t left = A.n - wave_base;
+  const int64_t left = A.rows.n - wave_base;
   const int nrows = left < 0 ? 0 : (left < kPolWaveEnvs ? (int)left : kPolWaveEnvs);
 
   for (int q = threadIdx.x; q < total / 4; q += nw * 64)
     *reinterpret_cast<float4*>(w + 4 * q) = *reinterpret_cast<const float4*>(A.block + 4 * q);
 
-  // ---- the wave's observation rows (missing rows = 0: finite activations, and their errors are zero)
-  if (!A.indices && nrows > 0) {
-    stage_obs_rows(A.obs, wave_base, nrows, rows, lane);
-  } else {
-    for (int j = 0; j < 9; ++j) {
-      const int idx = j * 64 + lane;
-      if (idx < kPolObsStage) {
-        const int row = idx / kPolIn, col = idx - row * kPolIn;
-        rows[idx] = row < nrows ? A.obs[A.indices[wave_base + row] * kPolIn + col] : 0.0f;
-      }
-    }
-  }
-  const bool valid = r < nrows;
-  const int64_t src = valid ? (A.indices ? A.indices[wave_base + r] : wave_base + r) : 0;
+  bool valid;
+  const int64_t src = ppo_gather_rows(A.rows, wave_base, nrows, rows, lane, valid);
   __syncthreads();
 
   float* part = A.parts + (size_t)blockIdx.x * T.part_floats;
@@ -331,52 +238,8 @@ __global__ __launch_bounds__(kPolBlock) void ppo_mlp_net_kernel(const PpoMlpNetA
           default: mlp_head<4>(wf, zerop, rec[0], biasp, inv, lane, x, mean); break;
         }
       }
-      float d3[4] = {0.0f, 0.0f, 0.0f, 0.0f}, ex[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      float sums[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-      if constexpr (ACTOR) {
-        const float* sd = w + kMlpStd;
-        float dm[4], dls[4], lp = 0.0f;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const bool comp = valid && (h == 0 || c < 2);                     // the upper half holds components 4, 5 only
-          const float act = comp ? A.actions[src * kPolOut + 4 * h + c] : mean[c];
-          const float sdv = comp ? sd[4 * h + c] : 1.0f, ls = comp ? sd[8 + 4 * h + c] : 0.0f;
-          const float var = sdv * sdv, d = act - mean[c], t = d * d / (2.0f * var);
-          lp += comp ? (-t - ls) : 0.0f;
-          dm[c] = comp ? d / var : 0.0f;                                   // d log_prob / d mean_c
-          dls[c] = comp ? 2.0f * t - 1.0f : 0.0f;                          // d log_prob / d log_std_c
-        }
-        lp = (lp + __shfl_xor(lp, 32)) - 5.5136312f;                        // - 6/2 log(2 pi)
-        float g = 0.0f;
-        if (valid) {
-          const float old = A.old_log_prob[src], adv = A.advantages[src];
-          const float diff = lp - old, ratio = expf(diff);
-          const float s1 = adv * ratio, s2 = adv * fminf(fmaxf(ratio, A.clip_lo), A.clip_hi);
-          // PyTorch's backward of min(s1, s2) and clamp (the rule of include/rdv.h): a tie halves the gradient between the two, clamp passes it
-          // inside the inclusive limits; comparisons with a NaN are false, so a NaN row keeps its gradient path and poisons the sums
-          const float g1 = s1 == s2 ? 0.5f : (s1 > s2 ? 0.0f : 1.0f), g2 = s1 == s2 ? 0.5f : (s2 > s1 ? 0.0f : 1.0f);
-          const float gc = (ratio >= A.clip_lo && ratio <= A.clip_hi) ? 1.0f : 0.0f;
-          g = -(adv * (g1 + g2 * gc)) * ratio;                              // d (n policy_loss) / d log_prob
-          if (h == 0) {
-            sums[0] = -((s1 < s2 || s1 != s1) ? s1 : s2);
-            sums[1] = (ratio - 1.0f) - diff;
-            sums[2] = fabsf(ratio - 1.0f) > A.clip_range ? 1.0f : 0.0f;
-            if (A.out) A.out[wave_base + r] = lp;
-          }
-        }
-#pragma unroll
-        for (int c = 0; c < 4; ++c) { d3[c] = g * dm[c]; ex[c] = g * dls[c]; }
-      } else {
-        if (valid && h == 0) {
-          const float diff = mean[0] - A.returns[src];
-          d3[0] = A.vf2 * diff;
-          sums[3] = diff * diff;
-          if (A.out) A.out[wave_base + r] = mean[0];
-        }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k) sums[k] = wave_sum(sums[k]);
-      if (lane == 0) { red[wv * 4 + 0] = sums[0]; red[wv * 4 + 1] = sums[1]; red[wv * 4 + 2] = sums[2]; red[wv * 4 + 3] = sums[3]; }
+      float d3[4], ex[4];
+      ppo_loss_terms<ACTOR>(A.rows, w + kMlpStd, w + kMlpStd + 8, mean, valid, src, A.out, wave_base + r, lane, red + wv * 4, d3, ex);
 #pragma unroll
       for (int c = 0; c < 4; ++c) { dl[0][c] = d3[c]; dl[0][4 + c] = ex[c]; }   // features 4 h + c, and 8 + 4 h + c
     }
@@ -390,14 +253,7 @@ __global__ __launch_bounds__(kPolBlock) void ppo_mlp_net_kernel(const PpoMlpNetA
       case 16 + 2: backward_step<ACT, ACTOR, 2, 2>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
       default: backward_step<ACT, ACTOR, 2, 4>(T, l, A.bwd, inv_acc, dl, hs, wave_tiles, tiles0, nw, lane, part); break;
     }
-    if (l == L) {
-      // the workgroup's scalar sums (red[] is behind a barrier by now), waves in order
-      if (threadIdx.x < 4 && (ACTOR ? threadIdx.x < 3 : threadIdx.x == 3)) {
-        float sum = 0.0f;
-        for (int k = 0; k < nw; ++k) sum += red[k * 4 + threadIdx.x];
-        part[T.part_floats - 4 + threadIdx.x] = sum;
-      }
-    }
+    if (l == L) ppo_store_scalar_sums<ACTOR>(red, nw, part + T.part_floats - 4);   // red[] is behind a barrier by now
   }
   if (T.mt[0] == 2) input_step<2>(T, dl, rows, wave_tiles, tiles0, nw, lane, part);
   else input_step<1>(T, dl, rows, wave_tiles, tiles0, nw, lane, part);
@@ -431,13 +287,7 @@ __global__ __launch_bounds__(256) void ppo_mlp_finish_kernel(const PpoMlpFinishA
     for (int64_t g = 0; g < F.actor_groups; ++g)
       for (int k = 0; k < 3; ++k) s[k] += (double)F.actor_parts[g * F.actor_stride + F.actor_stride - 4 + k];
     for (int64_t g = 0; g < F.critic_groups; ++g) s[3] += (double)F.critic_parts[g * F.critic_stride + F.critic_stride - 1];
-    const double dn = (double)F.n, policy = s[0] / dn, value = s[3] / dn;
-    double entropy = 0.0;
-    for (int c = 0; c < kPolOut; ++c) entropy += 0.5 + 0.5 * 1.8378770664093453 + (double)F.actor_block[kMlpStd + 8 + c];
-    const double entropy_loss = -entropy;
-    F.scalars[0] = (float)(policy + (double)F.ent_coef * entropy_loss + (double)F.vf_coef * value);
-    F.scalars[1] = (float)policy; F.scalars[2] = (float)value; F.scalars[3] = (float)entropy_loss;
-    F.scalars[4] = (float)(s[1] / dn); F.scalars[5] = (float)(s[2] / dn); F.scalars[6] = 0.0f; F.scalars[7] = 0.0f;
+    ppo_finish_scalars(s, F.n, F.actor_block + kMlpStd + 8, F.ent_coef, F.vf_coef, F.scalars);
   }
 }
 
@@ -475,13 +325,12 @@ void ppo_mlp_launch(const PpoMlpLaunch& a, hipStream_t s) {
   float* parts_a = a.workspace + 2 * kPpoMlpBwdFloats;
   float* parts_c = parts_a + groups_a * a.actor.part_floats;
   hipLaunchKernelGGL(ppo_mlp_transpose_kernel, dim3(kPpoMlpBwdFrags + 1, 2), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace);
-  PpoMlpNetArgs net = {a.actor_block, a.workspace, a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, a.indices, a.n,
-                       a.clip_lo, a.clip_hi, a.clip_range, 2.0f * a.vf_coef, parts_a, a.log_prob, a.actor};
+  PpoMlpNetArgs net = {a.actor_block, a.workspace, ppo_row_args(a), parts_a, a.log_prob, a.actor};
   launch_net<true>(a.actor_act, net, groups_a, s);
   net.block = a.critic_block; net.bwd = a.workspace + kPpoMlpBwdFloats; net.parts = parts_c; net.out = a.values; net.T = a.critic;
   launch_net<false>(a.critic_act, net, groups_c, s);
   const PpoMlpFinishArgs F = {parts_a, parts_c, groups_a, groups_c, a.n, a.actor.part_floats, a.critic.part_floats, a.actor.grad_floats,
-                              a.critic.grad_floats, a.actor_block, a.ent_coef, a.vf_coef, a.actor_grad, a.critic_grad, a.scalars};
+                              a.critic.grad_floats, a.actor_block, a.k.ent_coef, a.k.vf_coef, a.actor_grad, a.critic_grad, a.scalars};
   const int total = a.actor.grad_floats + a.critic.grad_floats + 1;
   hipLaunchKernelGGL(ppo_mlp_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, F);
 }
