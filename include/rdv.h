@@ -253,9 +253,11 @@ int rdv_set_reset_tape(rdv_handle h, const double* tape, int32_t depth);
 /* Tuning: force a kernel variant (RdvKernelVariant).  Results do not depend on it.  (Diagnostics only, read from the environment
  * at rdv_create: RDV_XCD_ORDER=0|1 forces the fused kernels' workgroup order — plain, or each XCD walking a contiguous eighth of
  * the batch, which is otherwise chosen by size; RDV_CHUNK_ALIGN / RDV_CHUNK_SKEW pad the state arrays of the workspace;
- * RDV_SPLIT_FORM=speculative|slots|slots_target forces the form of step_kernel_split<float, true> under RDV_ON_DONE_RESET — the next
- * initial state computed beside every step; prepared slots copied where an episode ends; or the slot form whose service waves also run
- * the target's side of the transition and hand it to the step waves (the default where it applies) — under the one kernel name.) */
+ * RDV_SPLIT_FORM=speculative|slots|slots_target|slots_target_obs forces the form of step_kernel_split<float, true> under
+ * RDV_ON_DONE_RESET — the next initial state computed beside every step; prepared slots copied where an episode ends; the slot form
+ * whose service waves also run the target's side of the transition and hand it to the step waves; or
+ * that form with the observation and its Box test on the service waves as well (the default where it applies) — under the one
+ * kernel name.) */
 int rdv_set_kernel_variant(rdv_handle h, int variant);
 
 /*

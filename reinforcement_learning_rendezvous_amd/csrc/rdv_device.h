@@ -878,7 +878,9 @@ __device__ __forceinline__ void step_target(const DevParams& P, double* qt, doub
 // kHanded (step_kernel_split_target): a partner wave ran the target's step, the rounding of qt and derive_target_head — e.qt arrives
 // canonical, with `rd_handed` = R(qt) rd — and the table entry c.att has had less time to travel: the reward, the only thing that
 // reads it, is formed LAST, behind the observation and the termination tests.  The pieces are the same in either order.
-template <typename ST, bool kLazy, bool kGeneral = false, bool kHanded = false, typename Sink>
+// kNoObs (step_kernel_split_obs): a partner wave forms the observation and its Box test; `sink` is not called, and r.done / r.reason
+// are those of the three tests left here (time, bubble, attitude) — the caller puts `outside` in front of them (reason 1).
+template <typename ST, bool kLazy, bool kGeneral = false, bool kHanded = false, bool kNoObs = false, typename Sink>
 __device__ __forceinline__ void step_env_finish(const DevParams& P, Env& e, StepResult& r, Derived& d, const StepCtx& c, Sink&& sink,
                                                 const double* rd_handed = nullptr) {
   const ST tag = ST(0);
@@ -921,10 +923,12 @@ __device__ __forceinline__ void step_env_finish(const DevParams& P, Env& e, Step
   if constexpr (!kHanded) reward();
   // :205, :355-386
   bool outside = false;
-  observation_to(P, e, [&](int j, float v) {
-    outside |= !(fabsf(v) <= 1.0f);                                                    // Box.contains; NaN -> outside
-    sink(j, v);
-  });
+  if constexpr (!kNoObs) {
+    observation_to(P, e, [&](int j, float v) {
+      outside |= !(fabsf(v) <= 1.0f);                                                  // Box.contains; NaN -> outside
+      sink(j, v);
+    });
+  }
   // norm(rc) > bubble_radius (:369): the bubble changes every step, so the sum of squares is compared with bubble^2 bracketed by its
   // rounding, and the correctly rounded square root decides inside the bracket (one wave in ~10^14 goes there)
   const double b2 = e.bubble * e.bubble;

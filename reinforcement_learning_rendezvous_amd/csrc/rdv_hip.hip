@@ -234,7 +234,7 @@ struct RdvEnvBatch {
   // False after whatever clears prepared_ok from outside and after every rdv_step launch of another kernel (they advance episodes in
   // registers); prepare_kernel then runs in front of the next slot-form launch.
   bool step_slots_ok;
-  int split_form;    // step_kernel_split, fp32 storage, RESET: 2 the slot form with the target's side on the service waves, 1 the slot form, 0 the speculative reset (RDV_SPLIT_FORM=slots_target|slots|speculative in the environment of rdv_create; default: split_slots_by_size, split_target_by_size)
+  int split_form;    // step_kernel_split, fp32 storage, RESET: 3 the target form with the observation on the service waves too, 2 the slot form with the target's side on the service waves, 1 the slot form, 0 the speculative reset (RDV_SPLIT_FORM=slots_target_obs|slots_target|slots|speculative in the environment of rdv_create; default: split_slots_by_size, split_target_by_size, split_obs_by_size)
 #ifdef RDV_STAMPS
   unsigned long long* stamps = nullptr;
 #endif
@@ -522,7 +522,7 @@ int rdv_create(const RdvParams* params, int64_t n_envs, int device, int storage,
   h->act_tmp = reinterpret_cast<float*>(base + L.act_tmp);
   h->obs_tmp = reinterpret_cast<float*>(base + L.obs_tmp);
   h->prepared_ok = false; h->step_slots_ok = false;
-  { const char* x = getenv("RDV_SPLIT_FORM"); h->split_form = (x && !strcmp(x, "slots_target")) ? 2 : (x && !strcmp(x, "slots")) ? 1 : (x && !strcmp(x, "speculative")) ? 0 : -1; }
+  { const char* x = getenv("RDV_SPLIT_FORM"); h->split_form = (x && !strcmp(x, "slots_target_obs")) ? 3 : (x && !strcmp(x, "slots_target")) ? 2 : (x && !strcmp(x, "slots")) ? 1 : (x && !strcmp(x, "speculative")) ? 0 : -1; }
   derive_block(h, *params, h->dev);
   // every step of the set-up reports itself: which call failed, and why
   const char* what = "hipMemset of the workspace";
@@ -773,8 +773,11 @@ int rdv_step(rdv_handle h, const float* actions, const RdvStepOut* out, void* st
     if (int rc = ensure_step_slots(h, s)) return rc;
     const unsigned step_wgs = (unsigned)((h->n + kSplitEnvs - 1) / kSplitEnvs);
     // ... and the target form of the slot form (step_kernel_split_target): the same grid, the same name on the handle
-    const bool target = h->split_form < 0 ? split_target_by_size(h->n) : h->split_form == 2;
-    if (target) hipLaunchKernelGGL((step_kernel_split_target<float>), dim3(2u * step_wgs), dim3(kSplitBlock), 0, s, RDV_HOT_ARGS(A, h->dev_params), A);
+    const bool target = h->split_form < 0 ? split_target_by_size(h->n) : h->split_form >= 2;
+    // ... and its observation form (step_kernel_split_obs), likewise
+    const bool obs = target && (h->split_form < 0 ? split_obs_by_size(h->n) : h->split_form == 3);
+    if (obs) hipLaunchKernelGGL((step_kernel_split_obs<float>), dim3(2u * step_wgs), dim3(kSplitBlock), 0, s, RDV_HOT_ARGS(A, h->dev_params), A);
+    else if (target) hipLaunchKernelGGL((step_kernel_split_target<float>), dim3(2u * step_wgs), dim3(kSplitBlock), 0, s, RDV_HOT_ARGS(A, h->dev_params), A);
     else hipLaunchKernelGGL((step_kernel_split<float, true, true>), dim3(2u * step_wgs), dim3(kSplitBlock), 0, s, RDV_HOT_ARGS(A, h->dev_params), A);
     h->last_kernel = "step_kernel_split<float, true>";
   } else if (split) {

@@ -65,6 +65,11 @@ static inline bool split_slots_by_size(int64_t n) { (void)n; return true; }
 // (step_kernel_split_target, rdv_step.h).  Measured (profiles/split_target_on_service.txt, us per launch, slot form -> target form):
 // 65,536 envs 5.93 -> 5.71, 32,768 5.59 -> 5.27, 16,384 5.10 -> 4.79, against a parent-to-parent spread of 0.01-0.02: on at every size.
 static inline bool split_target_by_size(int64_t n) { (void)n; return true; }
+// ... and, where the target form runs, whether the service waves also form the observation (step_kernel_split_obs, rdv_step.h).
+// Measured (profiles/split_obs_on_service.txt, us per launch, target form -> observation form, two sessions of this tree's build):
+// 65,536 envs 5.68 -> 5.61 and 5.70 -> 5.64 (7 and 9 times the largest parent-to-parent spread), 32,768 5.26 -> 5.06, 16,384 4.80 -> 4.60:
+// on at every size.
+static inline bool split_obs_by_size(int64_t n) { (void)n; return true; }
 enum { ST_STEPS = 0, ST_EPISODES, ST_SUCCESS, ST_COLLIDED, ST_REASON0, ST_REASON1, ST_REASON2, ST_REASON3,
        ST_SUM_LEN, ST_SUM_RET, ST_SUM_DV, ST_SUM_DW };
 

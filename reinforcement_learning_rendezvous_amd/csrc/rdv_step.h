@@ -282,15 +282,44 @@ __device__ __forceinline__ void refill_stale_slots(const StepArgs& A, const DevP
 // still waits for its state, and what fits there is free — 5.74 us per launch at 0 and at 1, 5.71 at 3 (65,536 envs, four children each)
 #define RDV_TARGET_SERVICE_PRIO 3
 #endif
+// The twelve requests of a slot record (fp32 storage: 12 vectors) as ONE statement under an exec mask it saves and restores itself; see the
+// service waves of the slot form.  A macro, not a function or a lambda: the statement stands at one of two places by form, and as a
+// lambda the older forms' register allocation changed (their instruction streams are held to the parent's: profiles/split_obs_isa_diff.md).
+#define RDV_REQUEST_RECORDS(rec, recp, mask, saved)                                                                                                  \
+  do {                                                                                                                                               \
+    _Pragma("unroll") for (int v_ = 0; v_ < 12; ++v_) asm volatile("" : "=v"(rec[v_]));   /* defined registers for the lanes that request nothing */   \
+    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"                                                                                                \
+                 "global_load_dwordx4 %[r0], %[p], off\n\t"                                                                                          \
+                 "global_load_dwordx4 %[r1], %[p], off offset:16\n\t"                                                                                \
+                 "global_load_dwordx4 %[r2], %[p], off offset:32\n\t"                                                                                \
+                 "global_load_dwordx4 %[r3], %[p], off offset:48\n\t"                                                                                \
+                 "global_load_dwordx4 %[r4], %[p], off offset:64\n\t"                                                                                \
+                 "global_load_dwordx4 %[r5], %[p], off offset:80\n\t"                                                                                \
+                 "global_load_dwordx4 %[r6], %[p], off offset:96\n\t"                                                                                \
+                 "global_load_dwordx4 %[r7], %[p], off offset:112\n\t"                                                                               \
+                 "global_load_dwordx4 %[r8], %[p], off offset:128\n\t"                                                                               \
+                 "global_load_dwordx4 %[r9], %[p], off offset:144\n\t"                                                                               \
+                 "global_load_dwordx4 %[r10], %[p], off offset:160\n\t"                                                                              \
+                 "global_load_dwordx4 %[r11], %[p], off offset:176\n\t"                                                                              \
+                 "s_mov_b64 exec, %[sv]"                                                                                                             \
+                 : [r0] "+v"(rec[0]), [r1] "+v"(rec[1]), [r2] "+v"(rec[2]), [r3] "+v"(rec[3]), [r4] "+v"(rec[4]), [r5] "+v"(rec[5]), [r6] "+v"(rec[6]), \
+                   [r7] "+v"(rec[7]), [r8] "+v"(rec[8]), [r9] "+v"(rec[9]), [r10] "+v"(rec[10]), [r11] "+v"(rec[11]), [sv] "=&s"(saved)               \
+                 : [p] "v"(recp), [m] "s"(mask)                                                                                                      \
+                 : "scc");                                                                                                                           \
+  } while (0)
 // The body of both kernels below.  kAll: on_done != HALT — every lane of the step waves runs the transition (advance_all).
 // stage / fin_mask: the kernel's LDS (observation rows [256][17]; per step wave, the lanes to reset).  hand_f / hand_d: the target form's
-// hand-over in LDS ([7][256] floats: qt, wt; [3][256] doubles: R(qt) rd), null otherwise.
-template <typename ST, bool kAll, bool kSlots, bool kTarget>
+// hand-over in LDS ([7][256] floats: qt, wt; [3][256] doubles: R(qt) rd), null otherwise.  hand_c / out_mask: the observation form's
+// hand-over the other way ([13][256] floats: the canonical rc, vc, qc, wc of the chaser half) and, per step wave, the service wave's ballot
+// of the lanes whose observation lies outside the Box; null otherwise.
+template <typename ST, bool kAll, bool kSlots, bool kTarget, bool kObs = false>
 __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_hot, const DevParams* Pp, int64_t n_hot, uint64_t* stats_hot, float* obs_hot,
-                                           float* reward_hot, const StepArgs& A_rest, float* stage, unsigned long long* fin_mask, float* hand_f, double* hand_d) {
+                                           float* reward_hot, const StepArgs& A_rest, float* stage, unsigned long long* fin_mask, float* hand_f, double* hand_d,
+                                           float* hand_c = nullptr, unsigned long long* out_mask = nullptr) {
   static_assert(!kTarget || kSlots, "the target form is a form of the slot form");
+  static_assert(!kObs || kTarget, "the observation form is a form of the target form");
   constexpr int kS = kTarget ? 1 : 0;   // stamps (diagnostic build): the target form has 2 = at the join, 3 = past it, and the later ones one up
-  (void)kS; (void)hand_f; (void)hand_d;
+  (void)kS; (void)hand_f; (void)hand_d; (void)hand_c; (void)out_mask;
   const StepArgs A = hot_args(A_rest, ws_hot, actions_hot, n_hot, stats_hot, obs_hot, reward_hot);
   using V = typename Vec4<ST>::type;
   const DevParams& P = *Pp;   // scalar loads: see step_kernel
@@ -370,6 +399,17 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
       Derived d;
       StepCtx c;
       step_env_chaser<ST, false, false, true>(P, e, a, d, c, actions_ready);   // (the table entry by a global load: the join must not wait for it)
+      if constexpr (kObs) {
+        // the chaser half is final here: canonical values, floats under fp32 storage, so the service wave's (double)(float) is exact
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+          hand_c[k * kSplitEnvs + slot_in_block] = (float)e.rc[k];
+          hand_c[(3 + k) * kSplitEnvs + slot_in_block] = (float)e.vc[k];
+          hand_c[(10 + k) * kSplitEnvs + slot_in_block] = (float)e.wc[k];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) hand_c[(6 + k) * kSplitEnvs + slot_in_block] = (float)e.qc[k];
+      }
       RDV_STAMP(2);
       __syncthreads();   // the join: the service waves have posted the target side of this workgroup's envs
       RDV_STAMP(3);
@@ -378,7 +418,8 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
       for (int k = 0; k < 4; ++k) e.qt[k] = (double)hand_f[k * kSplitEnvs + slot_in_block];   // canonical: (double)(float) as canon() forms it
 #pragma unroll
       for (int k = 0; k < 3; ++k) { e.wt[k] = (double)hand_f[(4 + k) * kSplitEnvs + slot_in_block]; rd_l[k] = hand_d[k * kSplitEnvs + slot_in_block]; }
-      step_env_finish<ST, true, false, true>(P, e, r, d, c, row_sink, rd_l);
+      if constexpr (kObs) step_env_finish<ST, true, false, true, true>(P, e, r, d, c, NoHook(), rd_l);   // r.done, r.reason: time | bubble | attitude
+      else step_env_finish<ST, true, false, true>(P, e, r, d, c, row_sink, rd_l);
       pack_env<ST>(e, packed);
       stepped = active;
     } else {
@@ -386,8 +427,8 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
       else stepped = advance<ST, false>(A, P, i, active, e, a, r, row_sink, NoHook(), kPack ? packed : nullptr);
       RDV_STAMP(2);
     }
-    const bool fin = stepped && r.done;
-    const bool to_reset = fin && resets;
+    bool fin = stepped && r.done;          // (kObs: by the three tests of this wave; the Box test's share arrives behind the barrier)
+    bool to_reset = fin && resets;
     const unsigned long long m_reset = __ballot(to_reset);
     if (lane == 0) fin_mask[wv] = m_reset;
     // The barrier comes HERE, as soon as the service waves have what they wait for (which envs ended, the observation rows), not at the
@@ -396,14 +437,31 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
     // The state of the envs that go on is stored BEFORE the barrier (round 3): the step waves reach it ~700 cycles ahead of the service
     // waves, and these 6 x 16-byte-per-lane stores drain inside that wait instead of after it (tools/lib_ab.py: 6.80 -> 6.73 us at
     // 65,536 envs, 5.35 -> 5.29 at 16,384; moving the reward / done / terminal-row stores there as well loses: 6.89).  Reset lanes: service wave.
-    halt_if_done<ST>(A, fin, e, kPack ? packed : nullptr);
-    if (stepped && !to_reset) { if (kPack) store_chunks<ST, true>(ws, A.cs, i, packed, false); else store_env<ST>(ws, A.cs, i, e, false); }
+    if constexpr (!kObs) {
+      halt_if_done<ST>(A, fin, e, kPack ? packed : nullptr);
+      if (stepped && !to_reset) { if (kPack) store_chunks<ST, true>(ws, A.cs, i, packed, false); else store_env<ST>(ws, A.cs, i, e, false); }
+    }
     RDV_STAMP(3 + kS);
     __syncthreads();
     RDV_STAMP(4 + kS);
+    if constexpr (kObs) {
+      // The termination decision is assembled from two waves: this one has posted the ballot of its three tests, the service wave the
+      // ballot of the Box test of the observation it formed (masked by `active`, as `stepped` is here).  Who goes on is known only now, so
+      // the state stores of those envs come behind the barrier, first of all.  (A third barrier in front of this decision, which keeps them
+      // in front of the last one as in the target form, measures 0.06 us slower: profiles/split_obs_on_service.txt.)
+      if ((out_mask[wv] >> lane) & 1ull) { r.done = 1; r.reason = 1; }       // :381 first true: outside comes first
+      fin = stepped && r.done;
+      to_reset = fin && resets;
+      halt_if_done<ST>(A, fin, e, packed);
+      if (stepped && !to_reset) store_chunks<ST, true>(ws, A.cs, i, packed, false);
+    }
     stats_update(slot, slot_pre, lane, stepped, fin, r.reason, e.flags, e.k, e.ep_ret, e.sum_dv, e.sum_dw);
-    store_step_outputs<true>(A, i, active, fin, r, e, obs_r);
-    if (m_reset == 0ull) store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
+    if constexpr (kObs) {
+      store_step_outputs<false>(A, i, active, fin, r, e, nullptr);            // terminal rows and observation rows: the service wave
+    } else {
+      store_step_outputs<true>(A, i, active, fin, r, e, obs_r);
+      if (m_reset == 0ull) store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
+    }
     RDV_STAMP(5 + kS);
     RDV_STAMP(6 + kS);
   } else if constexpr (kSlots) {
@@ -426,6 +484,12 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
     pin_f4 rec[kRecVecs];
     pin_f4 c5;
     uint32_t tag;
+    // observation form: the env this lane forms the observation of (rc, vc, qc, wc from the step wave's post, qt its own), the row in
+    // registers for the terminal rows (the staged row is overwritten by the reset observation), the Box test
+    Env obs_env;
+    float obs_r[RDV_OBS_DIM];
+    bool obs_outside = false;
+    (void)obs_env; (void)obs_r; (void)obs_outside;
     if constexpr (kTarget) {
       // the first stage also brings the target's chunks 4 (qt) and 6 (wt), which the step wave no longer requests; behind the wait the
       // target side of the transition runs here, beside the step wave's chaser half, and is posted for the join
@@ -446,6 +510,18 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
       for (int k = 0; k < 4; ++k) hand_f[k * kSplitEnvs + slot_in_block] = (float)qt[k];
 #pragma unroll
       for (int k = 0; k < 3; ++k) { hand_f[(4 + k) * kSplitEnvs + slot_in_block] = c6[k]; hand_d[k * kSplitEnvs + slot_in_block] = rd_l[k]; }
+      if constexpr (kObs) {
+        // the observation's last four elements are this wave's own canonical qt: formed here, in the wait for the join
+#pragma unroll
+        for (int k = 0; k < 4; ++k) obs_env.qt[k] = qt[k];
+        float* my_row = stage + slot_in_block * RDV_OBS_DIM;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const float v = (float)obs_env.qt[k];
+          obs_outside |= !(fabsf(v) <= 1.0f);
+          obs_r[13 + k] = v; my_row[13 + k] = v;
+        }
+      }
       if (RDV_TARGET_SERVICE_PRIO) __builtin_amdgcn_s_setprio(0);
     } else {
       asm volatile("global_load_dwordx4 %0, %2, off\n\tglobal_load_dword %1, %3, off"
@@ -455,35 +531,44 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
     }
     const uint32_t k_in = __float_as_uint(c5.y), episode_in = __float_as_uint(c5.w);
     const bool copy_ok = tag == episode_in + 1u && k_in >= 1u;
+    // The twelve record requests.  Slot and target form: behind the inputs / behind the join, with nothing but the barrier between them and their
+    // wait.  Observation form: in FRONT of the join, in the wait for the step wave (1,400 cycles in which this wave issues nothing), so
+    // that the observation arithmetic behind the join starts at once; the 48 record registers are then in flight, untracked, across the
+    // join and that arithmetic — the compiler sees them as live values and has no reason to touch them, and that it does not is read in
+    // the ISA (profiles/split_obs_on_service.txt: behind the join 5.79 us per launch at 65,536 envs, in front of it 5.72).
+    unsigned long long saved_exec;
+    if constexpr (kObs) RDV_REQUEST_RECORDS(rec, recp, __ballot(copy_ok), saved_exec);
     if constexpr (kTarget) {
-      // The join.  The record requests go out BEHIND it: nothing but the second barrier then stands between the untracked loads and
-      // their wait, as in the slot form, and they have the step waves' whole finish to land in.
+      // The join.  The target form's record requests go out BEHIND it: nothing but the second barrier then stands between the untracked
+      // loads and their wait, as in the slot form, and they have the step waves' whole finish to land in.
       RDV_STAMP(2);
       __syncthreads();
       RDV_STAMP(3);
     }
+    if constexpr (!kObs) RDV_REQUEST_RECORDS(rec, recp, __ballot(copy_ok), saved_exec);
+    if constexpr (kObs) {
+      // The observation, beside the step wave's finish: observation_to on the posted chaser values (elements 0..12; 13..16 are in the row
+      // already), every element into the env's staged row and into a register, the Box test as step_env_finish makes it, and the wave's
+      // ballot of it for the step wave.
 #pragma unroll
-    for (int v = 0; v < kRecVecs; ++v) asm volatile("" : "=v"(rec[v]));   // (defined registers for the lanes that request nothing)
-    unsigned long long saved_exec;
-    asm volatile("s_and_saveexec_b64 %[sv], %[m]\n\t"
-                 "global_load_dwordx4 %[r0], %[p], off\n\t"
-                 "global_load_dwordx4 %[r1], %[p], off offset:16\n\t"
-                 "global_load_dwordx4 %[r2], %[p], off offset:32\n\t"
-                 "global_load_dwordx4 %[r3], %[p], off offset:48\n\t"
-                 "global_load_dwordx4 %[r4], %[p], off offset:64\n\t"
-                 "global_load_dwordx4 %[r5], %[p], off offset:80\n\t"
-                 "global_load_dwordx4 %[r6], %[p], off offset:96\n\t"
-                 "global_load_dwordx4 %[r7], %[p], off offset:112\n\t"
-                 "global_load_dwordx4 %[r8], %[p], off offset:128\n\t"
-                 "global_load_dwordx4 %[r9], %[p], off offset:144\n\t"
-                 "global_load_dwordx4 %[r10], %[p], off offset:160\n\t"
-                 "global_load_dwordx4 %[r11], %[p], off offset:176\n\t"
-                 "s_mov_b64 exec, %[sv]"
-                 : [r0] "+v"(rec[0]), [r1] "+v"(rec[1]), [r2] "+v"(rec[2]), [r3] "+v"(rec[3]), [r4] "+v"(rec[4]), [r5] "+v"(rec[5]), [r6] "+v"(rec[6]),
-                   [r7] "+v"(rec[7]), [r8] "+v"(rec[8]), [r9] "+v"(rec[9]), [r10] "+v"(rec[10]), [r11] "+v"(rec[11]), [sv] "=&s"(saved_exec)
-                 : [p] "v"(recp), [m] "s"(__ballot(copy_ok))
-                 : "scc");
+      for (int k = 0; k < 3; ++k) {
+        obs_env.rc[k] = (double)hand_c[k * kSplitEnvs + slot_in_block];
+        obs_env.vc[k] = (double)hand_c[(3 + k) * kSplitEnvs + slot_in_block];
+        obs_env.wc[k] = (double)hand_c[(10 + k) * kSplitEnvs + slot_in_block];
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) obs_env.qc[k] = (double)hand_c[(6 + k) * kSplitEnvs + slot_in_block];
+      float* my_row = stage + slot_in_block * RDV_OBS_DIM;
+      observation_to(P, obs_env, [&](int j, float v) {
+        if (j >= 13) return;
+        obs_outside |= !(fabsf(v) <= 1.0f);                                                // Box.contains; NaN -> outside
+        obs_r[j] = v; my_row[j] = v;
+      });
+      const unsigned long long m_out = __ballot(active && obs_outside);
+      if (lane == 0) out_mask[wv - kSplitEnvs / kWave] = m_out;
+    }
 #ifdef RDV_STAMPS
+    if constexpr (!kObs)   // (the observation form's stamp at the barrier is "the Box test is posted": its records stay in flight, as in the product)
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]),
                  "+v"(rec[7]), "+v"(rec[8]), "+v"(rec[9]), "+v"(rec[10]), "+v"(rec[11]));   // stamps build only: stamp 2 is "the records have landed"
 #endif
@@ -494,10 +579,19 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
     // the compiler does not track these loads: every use of a record register it sees is of the value behind this wait
     asm volatile("s_waitcnt vmcnt(0)" : "+v"(rec[0]), "+v"(rec[1]), "+v"(rec[2]), "+v"(rec[3]), "+v"(rec[4]), "+v"(rec[5]), "+v"(rec[6]),
                  "+v"(rec[7]), "+v"(rec[8]), "+v"(rec[9]), "+v"(rec[10]), "+v"(rec[11]));
-    const unsigned long long m_reset = fin_mask[wv - kSplitEnvs / kWave];
+    unsigned long long m_reset = fin_mask[wv - kSplitEnvs / kWave];
+    if constexpr (kObs) m_reset |= out_mask[wv - kSplitEnvs / kWave];   // time | bubble | attitude by the step wave, the Box test by this one
     if (m_reset != 0ull) {   // wave-uniform: some env of the step wave we serve finished its episode
       float* wl = stage + (wv - kSplitEnvs / kWave) * (kWave * RDV_OBS_DIM);
       if (active && ((m_reset >> lane) & 1ull)) {
+        if constexpr (kObs) {
+          // the terminal row, from the registers: the staged row is about to take the next episode's first observation
+          if (A.terminal_obs) {
+            float* t = A.terminal_obs + i * RDV_OBS_DIM;
+#pragma unroll
+            for (int j = 0; j < RDV_OBS_DIM; ++j) t[j] = obs_r[j];
+          }
+        }
         if (copy_ok) {
           // copy path: the record is reset(seed, id, episode_in), state chunks in storage layout + observation
           if (__float_as_uint(rec[5].z) == kFlagsPending) {   // refilled by part (persistent kernels): the flags need the whole state
@@ -529,9 +623,16 @@ __device__ __forceinline__ void split_body(void* ws_hot, const float* actions_ho
           for (int j = 0; j < RDV_OBS_DIM; ++j) wl[lane * RDV_OBS_DIM + j] = robs[j];
         }
       }
+      if constexpr (!kObs) {
+        wave_lds_fence();
+        RDV_STAMP(5 + kS);
+        store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
+      }
+    }
+    if constexpr (kObs) {   // the rows are this wave's in every case: it staged them
       wave_lds_fence();
       RDV_STAMP(5 + kS);
-      store_obs_rows<true>(A.obs, wave_base, rows, lane, wl);
+      store_obs_rows<true>(A.obs, wave_base, rows, lane, stage + (wv - kSplitEnvs / kWave) * (kWave * RDV_OBS_DIM));
     }
     RDV_STAMP(6 + kS);
   } else {
@@ -595,6 +696,36 @@ __global__ __launch_bounds__(kSplitBlock) void step_kernel_split_target(void* ws
   __shared__ double hand_d[3 * kSplitEnvs];   // R(qt) rd, [component][env]
   __shared__ float hand_f[7 * kSplitEnvs];    // canonical qt, then wt
   split_body<ST, true, true, true>(ws_hot, actions_hot, Pp, n_hot, stats_hot, obs_hot, reward_hot, A_rest, stage, fin_mask, hand_f, hand_d);
+}
+
+// The observation form (kObs; the target form's conditions, refill workgroups, slot rules and reset paths unchanged) also gives the service
+// wave the observation, the largest piece of the step wave's finish that reads nothing the finish computes: nine normalized() elements,
+// eight conversions, seventeen row writes and seventeen Box tests, ~125 of its ~330 instructions.  The step wave posts its canonical rc,
+// vc, qc and wc at the end of the chaser half ([13][256] floats, 13,312 B more: 44,096 B per workgroup, a step and a refill workgroup still
+// share a CU); the service wave requests the records in its wait for the join and behind it runs observation_to on the posted values and
+// its own qt — the same function on the same inputs, the same bits — into the staged row and into registers, and posts the ballot of the
+// Box test.  The step wave runs step_env_finish without the observation and posts the ballot of its three tests; behind the barrier both
+// roles form the mask of the envs that ended, the step wave puts `outside` in front of its own reason and stores the state of the envs that
+// go on, the service wave stores the terminal rows from its registers, copies or resets as before, and stores the observation rows in
+// every case.  Every wave of a step workgroup executes exactly two barriers on every path.
+// Measured (profiles/split_obs_on_service.txt, tools/lib_ab.py, us per launch, target form -> this form, two sessions): 5.68 -> 5.61 and
+// 5.70 -> 5.64 at 65,536 envs, 5.26 -> 5.06 at 32,768, 4.80 -> 4.60 at 16,384.  Stamped, the step wave's stretch from the join to the
+// barrier shrinks from 2,680 to 1,280 cycles and the barrier is reached 900 cycles earlier; most of that is paid back at 65,536 envs: the
+// service wave's tail grows by the terminal rows (~570 cycles), and the refill waves, which run in the same SIMDs' issue gaps, leave
+// 400-900 ns later, last of the launch.  With the requests behind the join, as the target form has them, the form LOSES at 65,536 envs
+// (5.77 against 5.68: the service wave is then the last at the barrier by 590 cycles); a third barrier that keeps the state stores in
+// front of the last one loses 0.06 more; s_setprio 0, 1, 3 on the observation segment measure the same, none is set.  The default
+// wherever the target form runs (split_obs_by_size).
+template <typename ST>
+__global__ __launch_bounds__(kSplitBlock) void step_kernel_split_obs(void* ws_hot, const float* actions_hot, const DevParams* __restrict__ Pp, int64_t n_hot,
+                                                           uint64_t* stats_hot, float* obs_hot, float* reward_hot, const StepArgs A_rest) {
+  __shared__ __attribute__((aligned(16))) float stage[kSplitEnvs * RDV_OBS_DIM];   // observation rows
+  __shared__ unsigned long long fin_mask[kSplitEnvs / kWave];                        // per step wave: lanes that ended by time, bubble or attitude
+  __shared__ unsigned long long out_mask[kSplitEnvs / kWave];                        // per step wave: lanes whose observation is outside the Box
+  __shared__ double hand_d[3 * kSplitEnvs];   // R(qt) rd, [component][env]
+  __shared__ float hand_f[7 * kSplitEnvs];    // canonical qt, then wt
+  __shared__ float hand_c[13 * kSplitEnvs];   // canonical rc, vc, qc, wc: the chaser half, for the service wave
+  split_body<ST, true, true, true, true>(ws_hot, actions_hot, Pp, n_hot, stats_hot, obs_hot, reward_hot, A_rest, stage, fin_mask, hand_f, hand_d, hand_c, out_mask);
 }
 
 }  // namespace rdv

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Diagnostic: A/B of two builds of the library (the product .so against an experimental one) on the one-launch step at 65,536 envs
 and 524,288 envs: each build in its own child process, alternated, 256-launch graphs under sustained load.  AB_SIZES=65536,32768,16384 picks the sizes; the children inherit the
-environment (RDV_SPLIT_FORM=speculative|slots|slots_target: the form of step_kernel_split in the builds that have them).
+environment (RDV_SPLIT_FORM=speculative|slots|slots_target|slots_target_obs: the form of step_kernel_split in the builds that have them; a
+build from before a form runs its default under that form's name).  AB_REPS=4 sets the repetitions (default 2); a library named twice runs
+twice per repetition — two children of the parent's build are the noise measure of profiles/split_obs_on_service.txt.
     python tools/lib_ab.py tools/_nt.so"""
 import os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -54,7 +56,7 @@ for n in [int(x) for x in os.environ.get("AB_SIZES", "65536,32768").split(",")]:
 print()
 ''' % (ROOT, ROOT)
 others = sys.argv[1:]
-for rep in range(2):
+for rep in range(int(os.environ.get("AB_REPS", "2"))):
     for label, lib in [("product", "-")] + [(os.path.basename(o), o) for o in others]:
         r = subprocess.run([sys.executable, "-c", CHILD, lib], capture_output=True, text=True, timeout=300)
         print(f"{label:10s} us per launch  {r.stdout.strip()}" + ("" if r.returncode == 0 else " FAILED " + r.stderr[-300:]), flush=True)

@@ -7,7 +7,7 @@ Builds a -DRDV_STAMPS copy of the library into tools/_stamps.so, runs a few hund
 (service waves of the slot form: 1 chunk 5 and tag landed, record requests go out | 2 the records have landed — this build waits for them there)
 plus, from s_memrealtime (100 MHz, one counter for the whole chip): the shader clock, when waves enter and leave
 relative to the first wave of the launch, and the span of the launch as the waves see it.
-RDV_SPLIT_FORM=speculative|slots|slots_target picks the form (csrc/rdv_step.h); in the slot forms the second half of the grid is the refill workgroups;
+RDV_SPLIT_FORM=speculative|slots|slots_target|slots_target_obs picks the form (csrc/rdv_step.h); in the slot forms the second half of the grid is the refill workgroups;
 the lifetime of their wave 0 (it writes the largest part and the tags) is printed beside the two roles.  RDV_STAMPS_PREBUILT=1 uses tools/_stamps.so
 (or the library RDV_STAMPS_LIB names) as it stands.
 The target form (slots_target) has a join in front of the barrier, and its stamps are
@@ -15,6 +15,9 @@ The target form (slots_target) has a join in front of the barrier, and its stamp
   waves: target side posted) | 3 past the join | 4 at the barrier (service waves of this build: the records, requested behind the join, have
   landed) | 5 past it | 6 | 7 end
 so phase 2>3 is what a role waits at the join; the join's line is printed beside the barrier's.
+The observation form (slots_target_obs) has the target form's stamps; its service waves form the observation in phase 3>4 (this build
+does not wait for the records there: they are in flight across that arithmetic, as in the product), so "at the barrier" is when the
+service wave's `outside` post has landed, and its step waves store the state of the envs that go on in phase 5>6, behind the barrier.
 Never quote this build's run time: the stamps fence the scheduler."""
 import ctypes as C
 import os
@@ -32,7 +35,7 @@ def main():
     svc = 1          # service waves per step wave (round 3 also stamped a 12-wave workgroup with two: profiles/r03_split_service_waves_stamps.txt)
     wpg = 4 * (1 + svc)
     lib = os.environ.get("RDV_STAMPS_LIB") or os.path.join(ROOT, "tools", "_stamps.so")
-    target_form = os.environ.get("RDV_SPLIT_FORM", "slots_target") == "slots_target"      # the library's default form (a library from before it: RDV_SPLIT_FORM=slots)
+    target_form = os.environ.get("RDV_SPLIT_FORM", "slots_target") in ("slots_target", "slots_target_obs")      # the library's default form (a library from before it: RDV_SPLIT_FORM=slots)
     k_barrier = 4 if target_form else 3          # the stamp "at the barrier"
     from _build import build_variant
     if not os.environ.get("RDV_STAMPS_PREBUILT"):
