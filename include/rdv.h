@@ -772,6 +772,86 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
                           const RdvPpoSetOut* out, void* stream);
 
 /*
+ * Gradient clip, Adam and weight repack for policy sets (added within ABI 5: additive exports): what follows rdv_ppo_set_loss_grad in a
+ * learner's step — SB3's clip_grad_norm_ over the policy's parameters, torch.optim.Adam (no AMSGrad, no weight decay) and the refresh of the
+ * forward blocks — for all P members of an actor set and a critic set in ONE call of two launches (csrc/rdv_ppo_adam.h).  The fp32 master
+ * weights, the moments and the step counters are the caller's device arrays; the call reads member g's gradients, steps its parameters
+ * and rewrites its two forward blocks, with no host work beyond the argument checks.  One lr / betas / eps / max_grad_norm for all members.
+ *
+ * RdvAdamState (device pointers, the caller's): actor_param, actor_m, actor_v [P,5708] and critic_param, critic_m, critic_v [P,5377] in
+ *   the flat layout of RdvPpoOut's gradients, row g member g's, rows back to back; step [P] int64, the steps member g has taken so far;
+ *   coef [P,8], written by the call.  Every ARRAY (its first row) must be 16-byte aligned, the two gradient arrays too; rows are
+ *   5708 and 5377 floats apart, so a critic row is 4-byte aligned only, and the kernels read and write these arrays float by float.
+ * actor_grad [P,5708], critic_grad [P,5377]: RdvPpoSetOut's (a plain handle: RdvPpoOut's).
+ * active_mask: bit g set: member g takes the step.  A member whose bit is clear is INACTIVE: nothing of its rows — gradients, parameters,
+ *   moments, step, blocks, coef[g] — is read or written.
+ *
+ * For every active member g:
+ *   - Norm.  total_norm is the 2-norm of member g's 5708 + 5377 gradient entries: actor and critic form ONE norm, as
+ *     clip_grad_norm_(policy.parameters()) does.  The squares are added in double in an order fixed by the index alone (no floating-point
+ *     atomic), the square root is taken in double and rounded to float once.  clip_coef = min(1, float(max_grad_norm) / (total_norm + 1e-6f)),
+ *     PyTorch's expression on that float norm, evaluated in double and rounded to float once (within 1 ulp of PyTorch's own float
+ *     evaluation, and exactly 1 whenever that is); it is multiplied into the gradient even when it is 1.
+ *   - Step coefficients.  With t = step[g] + 1: step_size = float(lr / (1 - beta1^t)) and inv_sqrt_bc2 = float(1 / sqrt(1 - beta2^t)), both
+ *     computed in double.  coef[g] = total_norm, clip_coef, step_size, inv_sqrt_bc2, skipped (0 or 1), 0, 0, 0: the four floats the
+ *     elementwise step actually uses, which is stated in terms of them.
+ *   - Elementwise, for every entry of both nets, in float32 with every operation rounded on its own (no fused multiply-add), sqrt and the
+ *     division correctly rounded:
+ *         g' = g * clip_coef
+ *         m  <- m + (g' - m) * (1 - beta1)
+ *         v  <- v * beta2 + ((1 - beta2) * g') * g'
+ *         p  <- p - step_size * (m / (sqrt(v) * inv_sqrt_bc2 + eps))
+ *     beta1, beta2, 1 - beta1, 1 - beta2 (differences taken in double) and eps are each rounded from double to float once, on the host.
+ *     step[g] <- t.
+ *   - Repack.  After the step, member g's forward blocks on the device — the actor's at block g of actor_set, the critic's at block g of
+ *     critic_set — are the bytes that rdv_policy_create / rdv_critic_create pack from member g's new fp32 parameters: the per-layer shift
+ *     (the largest s <= 10, down to -20, with max|w| 2^s < 2^15; an all-zero layer: 10), the two fp16 terms rounded to nearest even with
+ *     fp16 subnormals kept, the fragment permutation, the biases in accumulator order times 2^(10 + s), log_std, the inverse scales, the
+ *     zero padding.  ONE EXCEPTION: the six exp(log_std) floats of an actor block.  The host packer takes them from the C library's expf,
+ *     which a device cannot reproduce bit for bit; the device writes the double-precision exp rounded to float, within 1 ulp of it.
+ *     What follows from the exception: after a device step the set sentence "row i of member g equals a stand-alone handle of member g's
+ *     weights" holds by equality for the deterministic action, the value and rdv_ppo_set_loss_grad (none of which reads exp(log_std));
+ *     SAMPLED actions and their log_prob may differ in the last bit from those of a handle packed on the host from the same weights.
+ *   - Non-finite gradients.  If total_norm is not finite (a NaN or an infinity among the gradients, or a norm beyond float's range),
+ *     member g is skipped whole: its parameters, moments, step and blocks are untouched, coef[g] = total_norm, 0, 0, 0, 1, 0, 0, 0.  The
+ *     other members are unaffected.  Parameters that leave the finite range through the step itself are NOT checked.
+ *
+ * The contract:
+ *   - Enqueued on `stream` only: no allocation, no synchronisation, no host-device copy; legal inside a stream capture.  The step counters
+ *     and the moments live in device memory, so each replay of a captured graph takes the NEXT step; lr and the other by-value arguments
+ *     are those of the capture.  Launches queued earlier on the stream read the old blocks, later ones the new blocks.
+ *   - Determinism: the same inputs give the same bits, eager or replayed.
+ *   - The caller's side of the bargain: actor_param / critic_param must hold the weights the blocks were packed from.  The call never reads
+ *     fp32 weights back out of a block; it overwrites the blocks with the pack of the stepped arrays.  The arrays must not alias one another.
+ *   - Shipped architecture only (17-64-64 tanh, the default RdvMlpSpec), sets of 1..64 members; a plain handle is a set of one.  No existing
+ *     call changes: rdv_policy_set_member_weights refreshes a block from host arrays as before (and knows nothing of the state arrays).
+ *   - A refused call enqueues nothing; the message names the argument.  RDV_ERR_INVALID_ARGUMENT, host-only and before the handles are
+ *     judged, for: a null state or pointer; a misaligned array; an lr or eps that is not finite or not positive; a beta outside [0, 1); a
+ *     max_grad_norm that is not positive (+inf is legal and means no clipping); an empty mask; a mask bit at or beyond the member count (that
+ *     of actor_set; with an invalid actor_set it is 1).  Then RDV_ERR_BAD_HANDLE for an invalid handle.  Then RDV_ERR_INVALID_ARGUMENT, in
+ *     the order of rdv_ppo_set_loss_grad, for: a recurrent handle or set, actor and critic swapped, any other architecture, different
+ *     member counts, more than 64 members, different devices.
+ *
+ * rdv_policy_block_floats: the floats of ONE member's parameter block of a handle (8372 for the shipped block); -1 for an invalid handle.
+ * rdv_policy_get_block: block `member` of the handle, as the kernels read it, into out_host [floats] (floats must equal
+ *   rdv_policy_block_floats).  A synchronous read-back for tests and checkpoints: it is ordered on `stream`, waits for it, and is refused
+ *   inside a stream capture.
+ */
+typedef struct RdvAdamState {        /* device pointers, the caller's; every array 16-byte aligned */
+  float*   actor_param;              /* [P,5708]  fp32 master weights, layout of RdvPpoOut.actor_grad  */
+  float*   critic_param;             /* [P,5377]                                                       */
+  float*   actor_m,  *actor_v;       /* [P,5708]  Adam moments                                         */
+  float*   critic_m, *critic_v;      /* [P,5377]                                                       */
+  int64_t* step;                     /* [P]       steps taken so far; the call increments an active member's */
+  float*   coef;                     /* [P,8]     out: total_norm, clip_coef, step_size, inv_sqrt_bc2, skipped (0/1), 0, 0, 0 */
+} RdvAdamState;
+int rdv_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state,
+                          const float* actor_grad, const float* critic_grad, uint64_t active_mask,
+                          double lr, double beta1, double beta2, double eps, double max_grad_norm, void* stream);
+int64_t rdv_policy_block_floats(rdv_policy p);
+int rdv_policy_get_block(rdv_policy p, int32_t member, float* out_host, int64_t floats, void* stream);
+
+/*
  * PPO minibatch gradients for every MLP architecture (added within ABI 5: additive exports): rdv_ppo_loss_grad for handles of ANY
  * RdvMlpSpec — 1..4 hidden layers of 16 / 32 / 64, tanh, ReLU or sigmoid, everything rdv_policy_create_mlp and rdv_critic_create_mlp
  * accept (csrc/rdv_ppo_mlp.h).  Actor and critic may differ in depth, widths and activation (SB3's net_arch = dict(pi=..., vf=...)).

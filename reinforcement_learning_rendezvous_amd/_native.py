@@ -46,6 +46,8 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            "rdv_ppo_workspace_bytes", "rdv_ppo_spec_check", "rdv_ppo_loss_grad",
            # PPO minibatch gradients for policy sets (added within ABI 5)
            "rdv_ppo_set_workspace_bytes", "rdv_ppo_set_loss_grad",
+           # gradient clip, Adam and weight repack for policy sets (added within ABI 5)
+           "rdv_ppo_set_adam_step", "rdv_policy_block_floats", "rdv_policy_get_block",
            # PPO minibatch gradients for every MLP architecture (added within ABI 5)
            "rdv_ppo_mlp_spec_check", "rdv_ppo_mlp_grad_floats", "rdv_ppo_mlp_workspace_bytes", "rdv_ppo_mlp_loss_grad"]
 
@@ -112,7 +114,17 @@ class PpoSetOut(C.Structure):
                 ("values", C.c_void_p)]
 
 
+class AdamState(C.Structure):
+    """RdvAdamState: device pointers of the fp32 master weights [P,5708] / [P,5377], the Adam moments, the step counters [P] (int64) and
+    the coefficient rows [P,8] that rdv_ppo_set_adam_step writes"""
+    _fields_ = [("actor_param", C.c_void_p), ("critic_param", C.c_void_p), ("actor_m", C.c_void_p), ("actor_v", C.c_void_p),
+                ("critic_m", C.c_void_p), ("critic_v", C.c_void_p), ("step", C.c_void_p), ("coef", C.c_void_p)]
+
+
 PPO_ACTOR_GRAD, PPO_CRITIC_GRAD, PPO_SCALARS = 5708, 5377, 8
+POLICY_BLOCK_FLOATS, POLICY_BLOCK_STD = 8372, 8352     # kPolFloats, kPolStd (csrc/rdv_policy.h): the shipped block and its six exp(log_std) floats
+ADAM_COEF = 8
+ADAM_COEF_NAMES = ("total_norm", "clip_coef", "step_size", "inv_sqrt_bc2", "skipped")
 PPO_SCALAR_NAMES = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction")
 
 ACT_TANH, ACT_RELU, ACT_SIGMOID = 0, 1, 2
@@ -154,7 +166,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the eleven translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip, rdv_ppo_mlp.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
+    """Compile the twelve translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip, rdv_ppo_mlp.hip, rdv_ppo_adam.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -256,6 +268,9 @@ def lib():
         "rdv_ppo_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), i64, C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoOut), vp]),
         "rdv_ppo_set_workspace_bytes": (i64, [i32, C.POINTER(i64)]),
         "rdv_ppo_set_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), C.POINTER(i64), C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoSetOut), vp]),
+        "rdv_ppo_set_adam_step": (C.c_int, [vp, vp, C.POINTER(AdamState), vp, vp, u64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+        "rdv_policy_block_floats": (i64, [vp]),
+        "rdv_policy_get_block": (C.c_int, [vp, i32, vp, i64, vp]),
         "rdv_ppo_mlp_spec_check": (C.c_int, [C.POINTER(MlpSpec), C.POINTER(MlpSpec)]),
         "rdv_ppo_mlp_grad_floats": (i64, [C.POINTER(MlpSpec), C.c_int]),
         "rdv_ppo_mlp_workspace_bytes": (i64, [C.POINTER(MlpSpec), C.POINTER(MlpSpec), i64]),

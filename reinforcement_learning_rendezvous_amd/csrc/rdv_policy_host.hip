@@ -1,8 +1,8 @@
 // rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
 // value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
-// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_*, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
+// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_*, rdv_ppo_set_adam_step, rdv_policy_get_block, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
-// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch), so an edit to an argument check recompiles no kernel.
+// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch, ppo_adam_launch), so an edit to an argument check recompiles no kernel.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
@@ -11,6 +11,7 @@
 #include "rdv_advantages.h"
 #include "rdv_ppo.h"
 #include "rdv_ppo_mlp.h"
+#include "rdv_ppo_adam.h"
 #include "rdv_host.h"
 
 #include <cstdio>
@@ -662,8 +663,9 @@ static int check_ppo_call(const char* who, const RdvPpoRows* rows, const Out* ou
 
 // The refusals the three entry points make of their pair of handles, in this order: an invalid handle; per net a recurrent one and
 // then what per_net(handle, name) refuses (the plain forms: a set); a swapped pair; what arch() refuses (an entry point's checks of the
-// architecture, made ahead of the devices'); two devices.  W: how this entry point names its two handles and who creates them.
-struct PpoHandleWords { bool set_form; const char *actor, *critic, *critic_creator, *actor_creator; };
+// architecture, made ahead of the devices'); two devices.  W: how this entry point names its two handles, who creates them, and what it
+// has not built for a recurrent set.
+struct PpoHandleWords { bool set_form; const char *actor, *critic, *critic_creator, *actor_creator; const char* not_built = "its gradients are not built"; };
 template <class PerNet, class Arch>
 static int check_ppo_handles(const char* who, rdv_policy actor, rdv_policy critic, const PpoHandleWords& W, PerNet per_net, Arch arch) {
   RDV_CHECK_POLICY(actor);
@@ -671,7 +673,7 @@ static int check_ppo_handles(const char* who, rdv_policy actor, rdv_policy criti
   const struct { rdv_policy p; const char* name; } nets[] = {{actor, W.actor}, {critic, W.critic}};
   for (const auto& a : nets) {
     if (a.p->lstm_hidden)
-      return W.set_form ? fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is a recurrent policy or a recurrent set: its gradients are not built", who, a.name)
+      return W.set_form ? fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is a recurrent policy or a recurrent set: %s", who, a.name, W.not_built)
                         : fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a recurrent policy: its gradients are not built", who, a.name);
     if (int rc = per_net(a.p, a.name)) return rc;
   }
@@ -786,6 +788,20 @@ int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_hos
   return any ? ppo_set_table(n_members, counts_host, nullptr) : -1;
 }
 
+// what the set entry points (rdv_ppo_set_loss_grad, rdv_ppo_set_adam_step) refuse of the architecture of two valid feed-forward sets, in this
+// order: another architecture than the shipped one, different member counts, more members than one call serves
+static int check_shipped_sets(const char* who, rdv_policy actor_set, rdv_policy critic_set, const char* not_built) {
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};
+  for (const auto& a : nets)
+    if (!is_default_spec(a.p->spec) || !a.p->shipped_arch)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not the shipped architecture (two hidden layers of 64, tanh): %s", who, a.name, not_built);
+  if (actor_set->n_members != critic_set->n_members)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, critic_set has %d", who, actor_set->n_members, critic_set->n_members);
+  if (actor_set->n_members > kPpoSetMaxMembers)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, at most %d are served by one call (kPpoSetMaxMembers)", who, actor_set->n_members, kPpoSetMaxMembers);
+  return RDV_OK;
+}
+
 int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host, double clip_range,
                           double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoSetOut* out, void* stream) {
   const char* who = "rdv_ppo_set_loss_grad";
@@ -799,17 +815,7 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
   if (workspace_bytes < need)
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, these counts need %lld (rdv_ppo_set_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
   if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
-  auto shipped_sets = [&]() -> int {
-    const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};
-    for (const auto& a : nets)
-      if (!is_default_spec(a.p->spec) || !a.p->shipped_arch)
-        return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not the shipped architecture (two hidden layers of 64, tanh): its gradients are not built", who, a.name);
-    if (actor_set->n_members != critic_set->n_members)
-      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, critic_set has %d", who, actor_set->n_members, critic_set->n_members);
-    if (actor_set->n_members > kPpoSetMaxMembers)
-      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, at most %d are served by one call (kPpoSetMaxMembers)", who, actor_set->n_members, kPpoSetMaxMembers);
-    return RDV_OK;
-  };
+  auto shipped_sets = [&]() -> int { return check_shipped_sets(who, actor_set, critic_set, "its gradients are not built"); };
   if (int rc = check_ppo_handles(who, actor_set, critic_set, {true, "actor_set", "critic_set", "rdv_critic_set_create", "rdv_policy_set_create"},
                                  [](rdv_policy, const char*) { return RDV_OK; }, shipped_sets)) return rc;
   DeviceGuard guard(actor_set->device);
@@ -819,6 +825,66 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
   L.n_members = P;
   ppo_set_launch(L, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- gradient clip, Adam and weight repack for policy sets (csrc/rdv_ppo_adam.h)
+int rdv_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
+                          uint64_t active_mask, double lr, double beta1, double beta2, double eps, double max_grad_norm, void* stream) {
+  const char* who = "rdv_ppo_set_adam_step";
+  if (!state) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: state is null", who);
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {state->actor_param, "state->actor_param"}, {state->critic_param, "state->critic_param"}, {state->actor_m, "state->actor_m"},
+      {state->actor_v, "state->actor_v"}, {state->critic_m, "state->critic_m"}, {state->critic_v, "state->critic_v"}, {state->step, "state->step"},
+      {state->coef, "state->coef"}, {actor_grad, "actor_grad"}, {critic_grad, "critic_grad"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
+  for (const auto& a : ptrs) if (misaligned(a.p, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s must be 16-byte aligned", who, a.name);
+  if (!std::isfinite(lr) || lr <= 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: lr must be finite and positive (got %g)", who, lr);
+  if (!std::isfinite(eps) || eps <= 0.0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: eps must be finite and positive (got %g)", who, eps);
+  if (!(beta1 >= 0.0 && beta1 < 1.0)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: beta1 must be in [0, 1) (got %g)", who, beta1);
+  if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: beta2 must be in [0, 1) (got %g)", who, beta2);
+  if (!(max_grad_norm > 0.0)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: max_grad_norm must be positive, +inf for no clipping (got %g)", who, max_grad_norm);
+  if (!active_mask) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: active_mask is empty: no member takes the step", who);
+  // the mask has one bit per member of the handles; with an invalid actor handle (refused below, behind the host-only checks) it is
+  // judged as one member's, and a set larger than the cap (refused below) as the cap's
+  const bool valid = actor_set && actor_set->magic == kPolicyMagic;
+  const int32_t P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
+  if (P < 64 && (active_mask >> P)) {
+    int bit = 63;
+    while (!((active_mask >> bit) & 1)) --bit;
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: active_mask has bit %d set, the set has %d member%s", who, bit, P, P == 1 ? "" : "s");
+  }
+  const char* not_built = "its optimiser step is not built";
+  auto shipped_sets = [&]() -> int { return check_shipped_sets(who, actor_set, critic_set, not_built); };
+  if (int rc = check_ppo_handles(who, actor_set, critic_set, {true, "actor_set", "critic_set", "rdv_critic_set_create", "rdv_policy_set_create", not_built},
+                                 [](rdv_policy, const char*) { return RDV_OK; }, shipped_sets)) return rc;
+  if (actor_set->block_floats != kPolFloats || critic_set->block_floats != kPolFloats)
+    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, the shipped block %d", who, actor_set->block_floats, critic_set->block_floats, kPolFloats);
+  DeviceGuard guard(actor_set->device);
+  PpoAdamLaunch a = {};
+  a.actor_block = actor_set->weights; a.critic_block = critic_set->weights;
+  a.actor_param = state->actor_param; a.critic_param = state->critic_param;
+  a.actor_m = state->actor_m; a.actor_v = state->actor_v; a.critic_m = state->critic_m; a.critic_v = state->critic_v;
+  a.step = state->step; a.coef = state->coef; a.actor_grad = actor_grad; a.critic_grad = critic_grad;
+  a.mask = active_mask; a.n_members = P;
+  ppo_adam_launch(ppo_adam_scalars(a, lr, beta1, beta2, eps, max_grad_norm), static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+int64_t rdv_policy_block_floats(rdv_policy p) { return (p && p->magic == kPolicyMagic) ? p->block_floats : -1; }
+
+int rdv_policy_get_block(rdv_policy p, int32_t member, float* out_host, int64_t floats, void* stream) {
+  const char* who = "rdv_policy_get_block";
+  RDV_CHECK_POLICY(p);
+  if (!out_host) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out_host is null", who);
+  if (member < 0 || member >= p->n_members) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: member %d of %d", who, member, p->n_members);
+  if (floats != p->block_floats) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: floats = %lld, the handle's block has %d (rdv_policy_block_floats)", who, (long long)floats, p->block_floats);
+  DeviceGuard guard(p->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (int rc = refuse_in_capture(who, s)) return rc;
+  RDV_HIP(hipMemcpyAsync(out_host, p->weights + (size_t)p->block_floats * (size_t)member, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost, s));
+  RDV_HIP(hipStreamSynchronize(s));
   return RDV_OK;
 }
 

@@ -260,7 +260,8 @@ class _Members:
         through rdv_policy_set_member_weights (a recurrent set: rdv_lstm_set_member_weights) on the current stream of its device:
         launches already queued there use the old weights, later ones the new; the other members' blocks, and a recurrent set's state,
         are not touched.  Not legal while the current stream is being captured (RdvError, nothing touched).  The noise key and the call
-        counter are unchanged."""
+        counter are unchanged.  (A ``PolicySet`` that has taken an ``adam_step`` on the device: the dicts are written through the members'
+        parameters into the master weights the set owns; the optimiser's moments and step counters are kept — ``reset_optimizer``.)"""
         P = len(self.policies)
         if (self._hip or self._hip_critic) and torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
             # refused before a module or a host copy is touched (either would invalidate the capture); the library refuses the same way
@@ -617,3 +618,38 @@ class PolicySet(_Members, _HipHandles):
         ``ppo.ppo_grad`` member by member (on CUDA rows each member of another architecture takes rdv_ppo_mlp_loss_grad).  Returns a list of P dicts of 0-dim tensors (the scalars of ``ppo_grad``)."""
         from . import ppo
         return ppo.ppo_set_grads(self, buf, indices, clip_range, ent_coef, vf_coef, normalize_advantage, check)
+
+    def adam_step(self, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5):
+        """What follows ``ppo_grads`` in a learner's step, for every member at once: SB3's ``clip_grad_norm_(policy.parameters(),
+        max_grad_norm)`` per member (actor and critic under ONE norm), ``torch.optim.Adam(eps=eps)`` and the refresh of the members'
+        forward weights (ppo.py; include/rdv.h "Gradient clip, Adam and weight repack for policy sets").  ``stepped``: the list
+        ``ppo_grads`` returned; a member whose entry is ``None`` sits out (its weights, moments and step count stay).  ``None``: all
+        members step.  One lr / betas / eps / max_grad_norm for all members; no weight decay, no AMSGrad.
+
+        After a ``ppo_grads`` that ran rdv_ppo_set_loss_grad (CUDA rows, the shipped 17-64-64 tanh architecture, at most 64 members,
+        ``backend != "torch"``) this is ONE call of rdv_ppo_set_adam_step on the current stream of that device: no allocation past the
+        first use, no synchronisation, no host copy, legal inside a stream capture (each replay takes the next step).  On first use the
+        set allocates the fp32 master weights [P,5708] / [P,5377], the moments and the step counters on that device, fills the weights
+        from the member modules and re-points the members' parameters at views of row g (the modules move to that device), as their
+        ``.grad`` are views of the gradient buffers.  So ``state_dict()`` and checkpoints see the stepped weights with no copy, and NO
+        ``update_weights()`` is needed: the call itself rewrites the members' forward blocks on the device — the bytes
+        ``update_weights()`` would pack, but for the six ``exp(log_std)`` floats of an actor block (within 1 ulp; sampled actions may
+        differ in the last bit from those of a freshly packed handle, deterministic actions, values and gradients do not).  A member
+        whose gradient norm is not finite is skipped whole and flagged.  ``update_weights(member=, weights=)`` writes through the views
+        and keeps the moments: ``reset_optimizer`` zeroes them.
+
+        CPU rows, ``backend="torch"`` or another architecture: per-member ``clip_grad_norm_`` and one ``torch.optim.Adam`` the set owns
+        over all members' parameters; the moments are then PyTorch's, a member with a non-finite norm is left out of that step, and
+        ``update_weights()`` follows as before.
+
+        Returns a dict of [P] tensors on the rows' device: ``total_norm``, ``clip_coef``, ``skipped`` (1.0: the member's norm was not
+        finite); the entries of a member that sat out are those of its last step (zero before the first)."""
+        from . import ppo
+        return ppo.set_adam_step(self, stepped, lr, betas, eps, max_grad_norm)
+
+    def reset_optimizer(self, member=None):
+        """Zero the Adam moments and the step counter of one member (``member`` = its index) or of all (None), on the device state and
+        in the fallback's optimiser alike; the weights are not touched.  For a member whose weights were replaced through
+        ``update_weights(member=, weights=)`` and should start its optimiser afresh."""
+        from . import ppo
+        return ppo.set_reset_optimizer(self, member)

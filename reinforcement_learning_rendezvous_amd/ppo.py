@@ -30,6 +30,17 @@ A sweep of P learners on one GPU (``PolicySet``, one grouped batch) takes the sa
 
 ``PolicySet.ppo_grads`` is ONE call of rdv_ppo_set_loss_grad (include/rdv.h "PPO minibatch gradients for policy sets"): the members'
 minibatches share four launches, and every member gets the bits of its own ``MlpPolicy.ppo_grad``.
+
+The three lines behind it can stay on the device too (the shipped architecture, CUDA rows):
+
+    for epoch in range(n_epochs):
+        for pieces in ppo_set_minibatches(learners, T, batch_size, generator):
+            stepped = learners.ppo_grads(buf, pieces, clip_range=0.2, ent_coef=0.0, vf_coef=0.5)
+            learners.adam_step(stepped, lr=3e-4, max_grad_norm=0.5)                           # clip, Adam and the new forward blocks
+
+``PolicySet.adam_step`` is ONE call of rdv_ppo_set_adam_step (include/rdv.h "Gradient clip, Adam and weight repack for policy sets"): the
+joint gradient norm of each member's actor and critic, Adam on fp32 master weights the set owns (the member modules' parameters are views
+of them), and the members' forward blocks repacked on the device: no ``update_weights``, no host copy, legal inside a stream capture.
 """
 import ctypes as C
 import math
@@ -370,9 +381,161 @@ def ppo_set_grads(pset, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     N.check(N.lib().rdv_ppo_set_loss_grad(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(r), counts, float(clip_range), float(ent_coef),
                                           float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    pset._ppo_last = dev
     s = st["scalars"].clone()
     out = [None] * P
     for g in live:
         _bind_grads(pset[g], dict(actor=st["actor"][g], critic=st["critic"][g]), dev)
         out[g] = {name: s[g, k] for k, name in enumerate(SCALAR_NAMES)}
     return out
+
+
+# ---------------------------------------------------------------------------------------------------- the optimiser step of a set
+def _check_adam(lr, betas, eps, max_grad_norm):
+    lr, eps, max_grad_norm = float(lr), float(eps), float(max_grad_norm)
+    b1, b2 = (float(b) for b in betas)
+    for name, v in (("lr", lr), ("eps", eps)):
+        if not math.isfinite(v) or v <= 0.0:
+            raise ValueError(f"adam_step: {name} = {v!r} must be finite and positive")
+    for name, v in (("betas[0]", b1), ("betas[1]", b2)):
+        if not 0.0 <= v < 1.0:
+            raise ValueError(f"adam_step: {name} = {v!r} must be in [0, 1)")
+    if not max_grad_norm > 0.0:
+        raise ValueError(f"adam_step: max_grad_norm = {max_grad_norm!r} must be positive (inf: no clipping)")
+    return lr, b1, b2, eps, max_grad_norm
+
+
+def _adam_device(pset):
+    """The device whose gradient buffers the last ``ppo_grads`` of this set filled through rdv_ppo_set_loss_grad, if the device step
+    serves the set: the shipped architecture, at most 64 members, ``backend != "torch"``; None: the PyTorch fallback."""
+    from . import _native as N
+    dev = getattr(pset, "_ppo_last", None)
+    if dev is None or pset.backend == "torch" or not (pset.shipped_arch and pset.vf_arch == [64, 64]) or len(pset) > 64:
+        return None
+    st = pset.__dict__.get("_ppo", {}).get(dev)
+    return dev if st is not None and tuple(st["actor"].shape) == (len(pset), N.PPO_ACTOR_GRAD) else None
+
+
+def _adam_views(pset, ad):
+    """The member modules' parameters <- views of row g of the master weights ``ad`` holds (filled from the modules first), so
+    ``state_dict()``, checkpoints and ``update_weights()`` see the stepped weights with no copy; ``.grad`` follows to the same device."""
+    dev = ad["actor_param"].device
+    grads = pset._ppo[dev]
+    with torch.no_grad():
+        for g, member in enumerate(pset.policies):
+            for flat, params in zip((ad["actor_param"][g], ad["critic_param"][g]), _params(member)):
+                flat.copy_(torch.cat([p.detach().reshape(-1).to(dev, torch.float32) for p in params]))
+                at = 0
+                for p in params:
+                    if p.device != dev:
+                        p.grad = None
+                    p.data = flat[at:at + p.numel()].view(p.shape)
+                    at += p.numel()
+            _bind_grads(member, dict(actor=grads["actor"][g], critic=grads["critic"][g]), dev)
+    ad["first"] = [m.l1.weight.data_ptr() for m in pset.policies]
+
+
+def _adam_state(pset, dev):
+    """The RdvAdamState buffers of a set on ``dev``, allocated on first use: master weights and moments [P,5708] / [P,5377], steps [P],
+    coef [P,8]."""
+    from . import _native as N
+    table = pset.__dict__.setdefault("_adam", {})
+    ad = table.get(dev)
+    if ad is None:
+        P = len(pset)
+        z = lambda n: torch.zeros((P, n), dtype=torch.float32, device=dev)
+        ad = dict(actor_param=z(N.PPO_ACTOR_GRAD), critic_param=z(N.PPO_CRITIC_GRAD), actor_m=z(N.PPO_ACTOR_GRAD), actor_v=z(N.PPO_ACTOR_GRAD),
+                  critic_m=z(N.PPO_CRITIC_GRAD), critic_v=z(N.PPO_CRITIC_GRAD), step=torch.zeros(P, dtype=torch.int64, device=dev),
+                  coef=z(N.ADAM_COEF), first=None)
+        ad["c"] = N.AdamState(*[ad[name].data_ptr() for name, _ in N.AdamState._fields_])
+        table[dev] = ad
+    # (a member moved with .to(), or given new Parameter objects, no longer aliases its row: the modules are the source of truth again)
+    if ad["first"] != [m.l1.weight.data_ptr() for m in pset.policies]:
+        _adam_views(pset, ad)
+    return ad
+
+
+def _adam_result(coef):
+    c = coef.clone()
+    return dict(total_norm=c[:, 0], clip_coef=c[:, 1], skipped=c[:, 4])
+
+
+def set_adam_step(pset, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5):
+    """See ``PolicySet.adam_step``."""
+    from .policy import PolicySet
+    if not isinstance(pset, PolicySet):
+        raise TypeError(f"adam_step: a {type(pset).__name__} is not offered: the device optimiser step is built for PolicySet alone")
+    P = len(pset)
+    if stepped is not None and (not isinstance(stepped, (list, tuple)) or len(stepped) != P):
+        raise ValueError(f"adam_step: stepped must be the list of {P} entries that ppo_grads returned (or None: all members step)")
+    lr, b1, b2, eps, max_grad_norm = _check_adam(lr, betas, eps, max_grad_norm)
+    live = [g for g in range(P) if stepped is None or stepped[g] is not None]
+    if not live:
+        raise ValueError("adam_step: every member sits out")
+    dev = _adam_device(pset)
+    if dev is not None:
+        from . import _native as N
+        ad = _adam_state(pset, dev)
+        grads = pset._ppo[dev]
+        mask = 0
+        for g in live:
+            mask |= 1 << g
+        N.check(N.lib().rdv_ppo_set_adam_step(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(ad["c"]), C.c_void_p(grads["actor"].data_ptr()),
+                                              C.c_void_p(grads["critic"].data_ptr()), C.c_uint64(mask), lr, b1, b2, eps, max_grad_norm,
+                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        return _adam_result(ad["coef"])
+
+    # ---- the fallback: per-member clip_grad_norm_ and ONE torch.optim.Adam over all members' parameters; the moments are PyTorch's
+    fb = pset.__dict__.get("_adam_torch")
+    params = [list(m.parameters()) for m in pset.policies]           # the order of INTEGRATION.md's clip_grad_norm_(member.parameters(), ...)
+    pdev = params[0][0].device
+    if fb is None or fb["ids"] != [id(p) for ps in params for p in ps]:
+        fb = dict(opt=torch.optim.Adam([p for ps in params for p in ps], lr=lr, betas=(b1, b2), eps=eps), ids=[id(p) for ps in params for p in ps],
+                  coef=torch.zeros((P, 8), dtype=torch.float32, device=pdev))
+        pset._adam_torch = fb
+    for group in fb["opt"].param_groups:
+        group["lr"], group["betas"], group["eps"] = lr, (b1, b2), eps
+    for g in live:
+        if any(p.grad is None for p in params[g]):
+            raise ValueError(f"adam_step: member {g} has no gradients (ppo_grads fills them)")
+    parked = {}
+    for g in range(P):
+        total = torch.nn.utils.clip_grad_norm_(params[g], max_grad_norm).to(torch.float32) if g in live else None
+        finite = total is not None and bool(torch.isfinite(total))
+        if total is not None:
+            row = fb["coef"][g]
+            row.zero_()
+            row[0] = total
+            if finite:
+                row[1] = torch.clamp(max_grad_norm / (total + 1e-6), max=1.0)
+            else:
+                row[4] = 1.0
+        if not finite:                                  # sits out or is skipped: the one optimiser passes over parameters without .grad
+            for p in params[g]:
+                parked[p] = p.grad
+                p.grad = None
+    try:
+        fb["opt"].step()
+    finally:
+        for p, grad in parked.items():
+            p.grad = grad
+    dst = getattr(pset, "_ppo_last", None)
+    return _adam_result(fb["coef"] if dst is None or pset.backend == "torch" else fb["coef"].to(dst))
+
+
+def set_reset_optimizer(pset, member=None):
+    """See ``PolicySet.reset_optimizer``."""
+    P = len(pset)
+    todo = list(range(P)) if member is None else [int(member)]
+    if not all(0 <= g < P for g in todo):
+        raise IndexError(f"reset_optimizer: member {member} of {P}")
+    with torch.no_grad():
+        for ad in pset.__dict__.get("_adam", {}).values():
+            for name in ("actor_m", "actor_v", "critic_m", "critic_v", "step"):
+                ad[name][todo] = 0
+    fb = pset.__dict__.get("_adam_torch")
+    if fb is not None:
+        for g in todo:
+            for part in _params(pset.policies[g]):
+                for p in part:
+                    fb["opt"].state.pop(p, None)

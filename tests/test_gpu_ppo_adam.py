@@ -1,0 +1,418 @@
+"""
+GPU: rdv_ppo_set_adam_step (include/rdv.h, "Gradient clip, Adam and weight repack for policy sets"; csrc/rdv_ppo_adam.h) and
+PolicySet.adam_step, held to the header by EQUALITY wherever it promises bits:
+
+    coef          total_norm within 1 float ulp of math.fsum over the squares (root in double); clip_coef, step_size, inv_sqrt_bc2 within
+                  1 ulp of the double expressions; clip_coef exactly 1 below max_grad_norm;
+    p, m, v, step bit-equal to the float32 restatement of tests/ppo_adam_reference.py fed with the read-back coef;
+    blocks        rdv_policy_get_block of every member of both sets equals, byte for byte outside the six exp(log_std) floats, the block
+                  of a stand-alone handle created from the read-back parameters (the library against itself across two code paths);
+    forward       rdv_policy_act (deterministic), rdv_policy_value and rdv_ppo_set_loss_grad on the stepped sets equal those handles'.
+
+Members are the dense random networks of tests/ppo_reference.py (seeds differ) and the corner members of ppo_adam_reference.corner_nets;
+gradients are dense vectors of a chosen 2-norm.  Every test takes a second or two: P <= 64 members of 11,085 parameters.
+"""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import policy_mlp_reference as M
+import ppo_adam_reference as A
+import ppo_reference as P
+import test_gpu_ppo_set_grad as G
+import test_ppo_set_grad as S
+from helpers import gpu_batch
+from reinforcement_learning_rendezvous_amd import _native as N
+from reinforcement_learning_rendezvous_amd import ppo_set_minibatches
+from reinforcement_learning_rendezvous_amd.policy import MlpPolicy, PolicySet
+from reinforcement_learning_rendezvous_amd.policy_lstm import LstmPolicy
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda:0"
+LR, BETAS, EPS = 3e-4, (0.9, 0.999), 1e-5
+INF = float("inf")
+STATE = [name for name, _ in N.AdamState._fields_]
+
+
+def policy_of(nets):
+    return MlpPolicy(M.weights_dict(*nets))
+
+
+def stream():
+    return C.c_void_p(torch.cuda.current_stream(DEV).cuda_stream)
+
+
+def get_block(handle, member):
+    out = np.empty(A.BLOCK_FLOATS, np.float32)
+    assert N.lib().rdv_policy_block_floats(handle) == A.BLOCK_FLOATS
+    N.check(N.lib().rdv_policy_get_block(handle, member, out.ctypes.data_as(C.c_void_p), A.BLOCK_FLOATS, stream()))
+    return out
+
+
+class Rig:
+    """P members as an actor set and a critic set (P = 1 with ``plain``: plain handles), the RdvAdamState arrays filled from the members'
+    weights, gradient arrays; ``step`` enqueues one rdv_ppo_set_adam_step on the current stream."""
+
+    def __init__(self, nets, plain=False, last=100):
+        self.P = len(nets)
+        sizes = [256] * (self.P - 1) + [last]
+        self.sizes = sizes
+        self.holder = policy_of(nets[0]) if plain else PolicySet([policy_of(n) for n in nets], sizes)
+        self.actor, self.critic = self.holder._hip_handle(DEV), self.holder._critic_handle(DEV)
+        dev = lambda a, dt=torch.float32: torch.from_numpy(np.ascontiguousarray(a)).to(DEV, dt)
+        self.t = dict(actor_param=dev(np.stack([A.flat(a) for a, _ in nets])), critic_param=dev(np.stack([A.flat(c) for _, c in nets])))
+        for name, n in (("actor_m", A.ACTOR), ("actor_v", A.ACTOR), ("critic_m", A.CRITIC), ("critic_v", A.CRITIC)):
+            self.t[name] = torch.zeros((self.P, n), device=DEV)
+        self.t["step"] = torch.zeros(self.P, dtype=torch.int64, device=DEV)
+        self.t["coef"] = torch.full((self.P, 8), -7.0, device=DEV)
+        self.state = N.AdamState(*[self.t[name].data_ptr() for name in STATE])
+        self.ga, self.gc = torch.zeros((self.P, A.ACTOR), device=DEV), torch.zeros((self.P, A.CRITIC), device=DEV)
+
+    def set_grads(self, grads):
+        self.ga.copy_(torch.from_numpy(np.stack([g[0] for g in grads])))
+        self.gc.copy_(torch.from_numpy(np.stack([g[1] for g in grads])))
+
+    def step(self, mask=None, lr=LR, betas=BETAS, eps=EPS, max_norm=0.5, handles=None):
+        mask = (1 << self.P) - 1 if mask is None else mask
+        a, c = handles or (self.actor, self.critic)
+        return N.lib().rdv_ppo_set_adam_step(a, c, C.byref(self.state), C.c_void_p(self.ga.data_ptr()), C.c_void_p(self.gc.data_ptr()),
+                                             C.c_uint64(mask), lr, betas[0], betas[1], eps, max_norm, stream())
+
+    def read(self):
+        """Every array on the host, and every member's two blocks"""
+        torch.cuda.synchronize()
+        out = {name: t.cpu().numpy().copy() for name, t in self.t.items()}
+        out["blocks"] = [(get_block(self.actor, g), get_block(self.critic, g)) for g in range(self.P)]
+        return out
+
+    def close(self):
+        self.holder.close()
+
+
+def same_member(x, y, g):
+    """member g's arrays, coef row and blocks of two reads are the same bits"""
+    return (all(np.array_equal(x[n][g:g + 1].view(np.uint8), y[n][g:g + 1].view(np.uint8)) for n in STATE)
+            and all(np.array_equal(a.view(np.uint32), b.view(np.uint32)) for a, b in zip(x["blocks"][g], y["blocks"][g])))
+
+
+def check_step(before, after, grads, live, max_norm, lr=LR, betas=BETAS, eps=EPS):
+    """One call's result against the header: coef, the restatement, the step counters, the blocks of stand-alone handles."""
+    for g in range(len(grads)):
+        if g not in live:
+            assert same_member(before, after, g), f"inactive member {g} was touched"
+            continue
+        ga, gc = grads[g]
+        t0 = int(before["step"][g])
+        coef = after["coef"][g]
+        want = A.coef64(ga, gc, t0, lr, *betas, max_norm)
+        for name, got, w in zip(N.ADAM_COEF_NAMES, coef, want):
+            assert A.within_ulps(got, w), (g, name, float(got), w)
+        assert np.array_equal(coef[4:], np.zeros(4, np.float32))
+        if want[0] < max_norm * (1 - 1e-6):
+            assert coef[1] == np.float32(1.0), (g, "clip_coef below max_grad_norm")
+        assert int(after["step"][g]) == t0 + 1
+        for net, grad in (("actor", ga), ("critic", gc)):
+            p, m, v = A.step32(before[f"{net}_param"][g], before[f"{net}_m"][g], before[f"{net}_v"][g], grad, coef, *betas, eps)
+            for name, x in (("param", p), ("m", m), ("v", v)):
+                assert np.array_equal(after[f"{net}_{name}"][g].view(np.uint32), x.view(np.uint32)), (g, net, name)
+        alone = policy_of((A.unflat(after["actor_param"][g], True), A.unflat(after["critic_param"][g], False)))
+        try:
+            for k, (actor, handle) in enumerate(((True, alone._hip_handle(DEV)), (False, alone._critic_handle(DEV)))):
+                msg = A.blocks_equal(after["blocks"][g][k], get_block(handle, 0), actor)
+                assert msg is None, (g, "actor" if actor else "critic", msg)
+        finally:
+            alone.close()
+
+
+def members(P, seed=100):
+    return [P_nets(seed + g) for g in range(P)]
+
+
+def P_nets(seed):
+    return P.random_nets(seed=seed)
+
+
+# gradient cases, in the order a rig takes them: the all-zero gradient first (with zero moments the parameters must not move), then
+# clipping active, inactive, and no clipping at all
+GRAD_CASES = [("zero", 0.0, 0.5), ("clipped", 3.0, 0.5), ("unclipped", 0.2, 0.5), ("no_clipping", 5.0, INF)]
+
+
+def case_grads(P, name, scale, seed):
+    if name == "zero":
+        return [(np.zeros(A.ACTOR, np.float32), np.zeros(A.CRITIC, np.float32)) for _ in range(P)]
+    return [A.gradients(seed + 17 * g, scale * (1.0 + 0.25 * g / P)) for g in range(P)]
+
+
+@pytest.mark.parametrize("config", ["P1-plain", "P3-member1-masked", "P64"])
+def test_coef_arrays_and_blocks_over_consecutive_steps(config):
+    """Four consecutive steps per configuration, one gradient case each (so members step from non-zero moments too); P = 3 keeps member 1
+    masked out for the first three and lets it in for the last: members at different step numbers in one call."""
+    P_ = {"P1-plain": 1, "P3-member1-masked": 3, "P64": 64}[config]
+    rig = Rig(members(P_), plain=config == "P1-plain")
+    try:
+        if config == "P1-plain":
+            assert N.lib().rdv_policy_num_members(rig.actor) == 1 and N.lib().rdv_policy_num_rows(rig.actor) == 0
+        before = rig.read()
+        for k, (name, scale, max_norm) in enumerate(GRAD_CASES):
+            live = [0, 2] if config == "P3-member1-masked" and k < 3 else list(range(P_))
+            grads = case_grads(P_, name, scale, seed=k)
+            rig.set_grads(grads)
+            N.check(rig.step(mask=sum(1 << g for g in live), max_norm=max_norm))
+            after = rig.read()
+            check_step(before, after, grads, live, max_norm)
+            for g in live:
+                moved = not np.array_equal(after["actor_param"][g], before["actor_param"][g])
+                assert moved == (name != "zero"), (name, g)            # an all-zero gradient on zero moments: the parameters do not move
+                if name == "clipped":
+                    assert after["coef"][g][1] < 0.2
+                if name == "no_clipping":
+                    assert after["coef"][g][0] > 4.0 and after["coef"][g][1] == 1.0
+            before = after
+        steps = before["step"].tolist()
+        assert steps == ([4, 1, 4] if config == "P3-member1-masked" else [4] * P_)
+        if P_ > 1:                                                      # members differ: a wrong member's row cannot pass
+            assert not np.array_equal(before["actor_param"][0], before["actor_param"][P_ - 1])
+    finally:
+        rig.close()
+
+
+def corner_rig():
+    """Four members, one packer corner each, and gradients that hold them there: "cross" is pushed up across 2^5, "tiny" keeps its
+    layer 1 (zero gradient there), "zero" keeps its all-zero head and its negative zero."""
+    nets = [A.corner_nets(w, seed=30 + k) for k, w in enumerate(A.CORNERS)]
+    grads = [list(A.gradients(50 + g, 0.4)) for g in range(4)]
+    cross = 1152 + 3 * 64 + 7                                          # w2[3, 7]
+    for k in range(2):
+        grads[0][k][cross] = -abs(grads[0][k][cross]) - np.float32(1e-3)   # Adam's first step is -lr sign(g): 32 - 1e-4 + 3e-4 > 32
+        grads[2][k][:1088] = 0.0
+        grads[3][k][5312:] = 0.0
+        grads[3][k][0] = 0.0
+    return Rig(nets), nets, [tuple(g) for g in grads]
+
+
+def test_blocks_at_the_corners_of_the_packer_and_the_forward_calls_on_them():
+    rig, nets, grads = corner_rig()
+    alone = []
+    try:
+        rig.set_grads(grads)
+        before = rig.read()
+        scale = lambda r, g, k, layer: float(r["blocks"][g][k][A.BLOCK_STD + 16 + layer])
+        assert scale(before, 0, 0, 1) == 2.0 ** -20 and scale(before, 1, 0, 0) == 2.0 ** -19 and scale(before, 1, 0, 1) == 2.0 ** -13
+        N.check(rig.step())
+        after = rig.read()
+        check_step(before, after, grads, [0, 1, 2, 3], 0.5)
+        for k in range(2):
+            assert float(np.abs(after[("actor_param", "critic_param")[k]][0][1152:5248]).max()) > 32.0
+            assert scale(after, 0, k, 1) == 2.0 ** -19, "the shift of layer 2 changes as max |w| crosses 2^5"
+            assert scale(after, 1, k, 0) == 2.0 ** -19 and scale(after, 1, k, 1) == 2.0 ** -13     # weights >= 32: shifts 9 and 3
+            tiny = after[("actor_param", "critic_param")[k]][2][:1088]
+            assert 0 < float(np.abs(tiny).max()) < 2.0 ** -17
+            lo = after["blocks"][2][k].view(np.uint16)[4 * 512:8 * 512]        # layer 1's lo fragments: fp16-subnormal or zero
+            assert bool(((lo & 0x7c00) == 0).all()) and bool((lo & 0x03ff).any())
+            zero = after[("actor_param", "critic_param")[k]][3]
+            assert not zero[5312:5312 + (390 if k == 0 else 65)].any() and scale(after, 3, k, 2) == 2.0 ** -20      # all-zero head: shift 10
+            assert zero[:1].view(np.uint32)[0] == 0x80000000                    # the negative zero is still one
+        # forward: the set against stand-alone handles of the read-back weights
+        alone = [policy_of((A.unflat(after["actor_param"][g], True), A.unflat(after["critic_param"][g], False))) for g in range(4)]
+        n = sum(rig.sizes)
+        obs = torch.from_numpy(np.random.default_rng(3).uniform(-1, 1, size=(n, 17)).astype(np.float32)).to(DEV)
+        acts, values = rig.holder.act(obs, deterministic=True), rig.holder.value(obs)
+        for g, sl in enumerate(rig.holder.group_slices):
+            assert torch.equal(acts[sl], alone[g].act(obs[sl].contiguous(), deterministic=True)), g
+            assert torch.equal(values[sl], alone[g].value(obs[sl].contiguous())), g
+        # rdv_ppo_set_loss_grad on the stepped sets against rdv_ppo_loss_grad on those handles
+        cols = {k: torch.from_numpy(np.array(v)).to(DEV) for k, v in S.set_columns().items()}
+        counts = (33, 129, 257, 128)
+        idx = [torch.as_tensor(P.index_vector(c, seed=9 + g), device=DEV) for g, c in enumerate(counts)]
+        call = G.SetCall(cols, counts, idx)
+        N.check(call.run(rig.actor, rig.critic))
+        torch.cuda.synchronize()
+        G.assert_members_equal_alone(call.outs, alone, cols, counts, idx)
+    finally:
+        rig.close()
+        for p in alone:
+            p.close()
+
+
+def test_members_with_a_nan_or_an_infinite_gradient_are_skipped_whole_and_flagged():
+    rig = Rig(members(3, seed=60))
+    try:
+        warm = case_grads(3, "clipped", 3.0, seed=1)
+        rig.set_grads(warm)
+        N.check(rig.step())                                             # moments and steps are not zero when the bad gradients arrive
+        before = rig.read()
+        grads = [list(g) for g in case_grads(3, "unclipped", 0.2, seed=2)]
+        grads[0][1][5000] = np.float32("nan")
+        grads[1][0][17] = np.float32("-inf")
+        grads = [tuple(g) for g in grads]
+        rig.set_grads(grads)
+        N.check(rig.step())
+        after = rig.read()
+        keep = dict(before); keep["coef"] = after["coef"]                # a skipped member's coef row is written, nothing else of it
+        for g, bad in ((0, np.isnan), (1, np.isinf)):
+            coef = after["coef"][g]
+            assert bad(coef[0]) and coef[4] == 1.0 and not coef[1:4].any() and not coef[5:].any()
+            assert same_member(keep, after, g), f"skipped member {g} was touched"
+        check_step(keep, after, grads, [2], 0.5)
+        assert int(after["step"][2]) == 2 and after["step"][:2].tolist() == [1, 1]
+    finally:
+        rig.close()
+
+
+def test_an_act_queued_before_the_step_sees_the_old_block_and_one_after_the_new():
+    nets = members(3, seed=70)
+    rig = Rig(nets)
+    old, new = [policy_of(n) for n in nets], []
+    try:
+        rig.set_grads(case_grads(3, "clipped", 3.0, seed=4))
+        n = sum(rig.sizes)
+        obs = torch.from_numpy(np.random.default_rng(5).uniform(-1, 1, size=(n, 17)).astype(np.float32)).to(DEV)
+        torch.cuda.synchronize()
+        first = rig.holder.act(obs, deterministic=True)                 # three launches on one stream, nothing waited for in between
+        N.check(rig.step())
+        second = rig.holder.act(obs, deterministic=True)
+        after = rig.read()
+        new = [policy_of((A.unflat(after["actor_param"][g], True), A.unflat(after["critic_param"][g], False))) for g in range(3)]
+        for g, sl in enumerate(rig.holder.group_slices):
+            assert torch.equal(first[sl], old[g].act(obs[sl].contiguous(), deterministic=True)), g
+            assert torch.equal(second[sl], new[g].act(obs[sl].contiguous(), deterministic=True)), g
+            assert not torch.equal(first[sl], second[sl])
+    finally:
+        rig.close()
+        for p in old + new:
+            p.close()
+
+
+def test_three_replays_of_a_captured_update_equal_three_eager_iterations():
+    """[rdv_ppo_set_loss_grad, rdv_ppo_set_adam_step] captured once on a non-default stream: the step counters and the moments live on
+    the device, so replay k takes step k, on the gradients of the blocks that replay k - 1 packed."""
+    nets = members(3, seed=80)
+    eager, graph = Rig(nets), Rig(nets)
+    cols = {k: torch.from_numpy(np.array(v)).to(DEV) for k, v in S.set_columns().items()}
+    counts = (128, 257, 33)
+    idx = [torch.as_tensor(P.index_vector(c, seed=9 + g), device=DEV) for g, c in enumerate(counts)]
+
+    def iteration(rig, call):
+        N.check(call.run(rig.actor, rig.critic))
+        N.check(N.lib().rdv_ppo_set_adam_step(rig.actor, rig.critic, C.byref(rig.state), C.c_void_p(call.outs[0].data_ptr()),
+                                              C.c_void_p(call.outs[1].data_ptr()), C.c_uint64(7), LR, *BETAS, EPS, 0.5, stream()))
+    try:
+        call = G.SetCall(cols, counts, idx)
+        N.check(call.run(eager.actor, eager.critic))                    # (the LDS limits are raised outside the capture)
+        torch.cuda.synchronize()
+        start = eager.read()
+        for _ in range(3):
+            iteration(eager, call)
+        want = eager.read()
+        gcall = G.SetCall(cols, counts, idx)
+        side = torch.cuda.Stream()
+        with torch.cuda.stream(side):
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g, stream=side):
+                iteration(graph, gcall)
+            side.synchronize()
+            assert same_member(start, graph.read(), 0), "a capture runs nothing"
+            for _ in range(3):
+                g.replay()
+            side.synchronize()
+        got = graph.read()
+        assert all(same_member(want, got, m) for m in range(3))
+        assert got["step"].tolist() == [3, 3, 3] and not same_member(start, got, 0)
+        for x, y in zip(call.outs, gcall.outs):
+            assert G.bits_equal(x, y)
+    finally:
+        eager.close(); graph.close()
+
+
+def test_three_update_steps_of_ppo_grads_and_adam_step_on_a_collected_buffer():
+    """The loop of INTEGRATION.md: P = 3 members of 256 envs, T = 4; each step's gradients (read back) go through the float64 reference
+    too, and the parameters stay within the bound of tests/test_ppo_adam.py.  state_dict() shows the stepped weights; update_weights()
+    afterwards changes no block outside the six exp(log_std) floats."""
+    nets = members(3, seed=90)
+    pset = PolicySet([policy_of(n) for n in nets], [256, 256, 256])
+    env = gpu_batch(768, seed=11)
+    try:
+        env.reset()
+        buf = env.collect(pset, 4, gamma=0.99, gae_lambda=0.95)
+        refs = [A.Reference64(A.flat(a), A.flat(c), LR, BETAS, EPS, 0.5) for a, c in nets]
+        steps = ppo_set_minibatches(pset, 4, 400, torch.Generator(device=DEV).manual_seed(3))
+        assert len(steps) == 3
+        for pieces in steps:
+            stepped = pset.ppo_grads(buf, pieces, clip_range=0.2, ent_coef=0.0, vf_coef=0.5)
+            st = pset._ppo[torch.device(DEV)]
+            ga, gc = st["actor"].cpu().numpy().copy(), st["critic"].cpu().numpy().copy()
+            out = pset.adam_step(stepped, lr=LR, betas=BETAS, eps=EPS, max_grad_norm=0.5)
+            assert set(out) == {"total_norm", "clip_coef", "skipped"} and all(t.shape == (3,) and t.device.type == "cuda" for t in out.values())
+            assert not bool(out["skipped"].any()) and bool((out["total_norm"] > 0).all())
+            for g in range(3):
+                refs[g].step(ga[g], gc[g])
+        ad = pset._adam[torch.device(DEV)]
+        assert ad["step"].tolist() == [3, 3, 3]
+        pa, pc = ad["actor_param"].cpu().numpy(), ad["critic_param"].cpu().numpy()
+        for g in range(3):
+            worst = refs[g].worst(pa[g], pc[g])
+            print(f"member {g}: max |p32 - p64| / bound = {worst:.3f}")
+            assert worst <= 1.0
+            assert float(np.abs(pa[g] - A.flat(nets[g][0])).max()) > 5e-4
+            sd = pset[g].state_dict()
+            flat_sd = np.concatenate([sd[k].cpu().numpy().reshape(-1) for k in ("l1.weight", "l1.bias", "l2.weight", "l2.bias", "l3.weight", "l3.bias", "log_std")])
+            assert np.array_equal(flat_sd, pa[g])                       # the modules' parameters are views of the master weights
+        a, c = pset._hip_handle(DEV), pset._critic_handle(DEV)
+        torch.cuda.synchronize()
+        blocks = [(get_block(a, g), get_block(c, g)) for g in range(3)]
+        pset.update_weights()                                           # the host packer on the same weights
+        torch.cuda.synchronize()
+        for g in range(3):
+            for k, handle in enumerate((a, c)):
+                msg = A.blocks_equal(blocks[g][k], get_block(handle, g), k == 0)
+                assert msg is None, (g, k, msg)
+    finally:
+        pset.close(); env.close()
+
+
+def test_refusals_that_need_handles_enqueue_nothing():
+    nets = members(3, seed=95)
+    rig = Rig(nets)
+    wide_nets = (M.dense([32, 32], "tanh"), M.critic_of(M.dense([32, 32], "tanh")))
+    wide = PolicySet([MlpPolicy(M.weights_dict(*wide_nets)) for _ in range(3)], rig.sizes)
+    two = PolicySet([policy_of(n) for n in nets[:2]], [256, 100])
+    lstm = LstmPolicy(lstm_hidden_size=32, net_arch=[64, 64], n_rows=64)
+    try:
+        rig.set_grads(case_grads(3, "clipped", 3.0, seed=6))
+        before = rig.read()
+        a, c = rig.actor, rig.critic
+        lone = lstm._hip_handle(DEV)
+        cases = [((lone, c), ("actor_set", "recurrent")), ((a, lstm._critic_handle(DEV)), ("critic_set", "recurrent")),
+                 ((wide._hip_handle(DEV), c), ("actor_set", "shipped architecture")), ((a, wide._critic_handle(DEV)), ("critic_set", "shipped architecture")),
+                 ((c, a), ("swapped",)), ((a, two._critic_handle(DEV)), ("actor_set has 3 members", "critic_set has 2"))]
+        for handles, words in cases:
+            # (the mask is judged on the host against actor_set's member count, before the handles are: one bit for the lone recurrent actor)
+            rc = rig.step(handles=handles, mask=1 if handles[0] is lone else None)
+            msg = N.lib().rdv_last_error().decode()
+            assert rc == -1 and all(w in msg for w in words) and msg.startswith("rdv_ppo_set_adam_step: "), (words, rc, msg)
+        rc = rig.step(mask=0b1000)                                      # a mask bit beyond the three members: host-only, against P
+        assert rc == -1 and "bit 3 set, the set has 3 members" in N.lib().rdv_last_error().decode()
+        assert all(same_member(before, rig.read(), g) for g in range(3))     # a refused call enqueues nothing
+        bad = np.empty(4, np.float32)
+        assert N.lib().rdv_policy_get_block(a, 3, bad.ctypes.data_as(C.c_void_p), A.BLOCK_FLOATS, None) == -1
+        assert N.lib().rdv_policy_get_block(a, 0, bad.ctypes.data_as(C.c_void_p), 4, None) == -1 and "8372" in N.lib().rdv_last_error().decode()
+        N.check(rig.step())                                             # the handles are still usable
+        assert not same_member(before, rig.read(), 0)
+    finally:
+        for p in (rig, wide, two, lstm):
+            p.close()
+
+
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two visible devices")
+def test_sets_on_two_devices_are_refused():
+    nets = members(1, seed=97)
+    rig = Rig(nets, plain=True)
+    other = policy_of(nets[0])
+    try:
+        rc = rig.step(handles=(rig.actor, other._critic_handle("cuda:1")))
+        assert rc == -1 and "on device 0" in N.lib().rdv_last_error().decode() and "on device 1" in N.lib().rdv_last_error().decode()
+    finally:
+        rig.close(); other.close()
