@@ -900,6 +900,69 @@ int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows*
                           double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream);
 
 /*
+ * PPO minibatch gradients for policy sets of every MLP architecture (added within ABI 5: additive exports): rdv_ppo_set_loss_grad for
+ * an actor set and a critic set of ANY pair of RdvMlpSpec (one spec per set; csrc/rdv_ppo_mlp.h, "the set form").  The four launches of
+ * rdv_ppo_mlp_loss_grad serve all P members: the member is taken from the grid, and the members' counts, offsets and workspace pieces
+ * travel by value in the kernel arguments, hence the cap of 64 members.  rdv_ppo_set_loss_grad and rdv_ppo_mlp_loss_grad are unchanged.
+ *
+ * rdv_ppo_mlp_set_spec_check (host-only): RDV_OK for a pair of specs the call below serves; a null pointer is
+ *   RDV_ERR_INVALID_ARGUMENT naming the argument, a bad spec the message of rdv_mlp_spec_check behind "actor_set: " or "critic_set: ",
+ *   the mixed pair (exactly one default spec) the message of the call.
+ * rdv_ppo_mlp_set_workspace_bytes (host-only): the sum of rdv_ppo_mlp_workspace_bytes (actor spec, critic spec, counts_host[g]) over
+ *   the positive counts; -1 for a bad spec, n_members outside 1..64, null counts, a negative count or no positive one; monotone in every
+ *   count, a multiple of 16.
+ * rdv_ppo_mlp_set_loss_grad: rows, counts_host and out as in rdv_ppo_set_loss_grad; row g of out->actor_grad / out->critic_grad is
+ *   rdv_ppo_mlp_grad_floats (actor spec, 1) / (critic spec, 0) floats long, the rows back to back (4-byte aligned only), in the layout
+ *   of rdv_ppo_mlp_loss_grad.
+ *
+ * The contract, by equality: every output of member g — gradients, scalars, log_prob, values — is bit for bit what
+ * rdv_ppo_mlp_loss_grad writes for stand-alone handles of member g's weights and the sets' two specs, given the same rows,
+ * indices + off_g (off_g: the sum of the earlier counts), n = counts_host[g] and the same coefficients.  A member's partition into
+ * workgroups (256 or 128 rows, per net), its wave order and its index-order sum are the stand-alone call's.  The rest is the contract
+ * of rdv_ppo_set_loss_grad: nothing of a member with count 0 is written; one clip_range / ent_coef / vf_coef for all members; weights as
+ * of stream order (a call behind rdv_policy_set_member_weights differentiates the new block); no floating-point atomic; the same bits
+ * eager or replayed; enqueue only, legal inside a capture; a plain general-spec handle pair is a set of one member.
+ *   - Two sets of the default spec: the call IS rdv_ppo_set_loss_grad, its bits and its refusals.  One default-spec set beside a general
+ *     one is refused (RDV_ERR_INVALID_ARGUMENT).
+ *   - Order of checks: the host-only ones of rdv_ppo_set_loss_grad, naming the argument, then the three coefficients; RDV_ERR_BAD_HANDLE
+ *     for an invalid handle; RDV_ERR_INVALID_ARGUMENT for a recurrent handle, swapped handles, the mixed pair, different member counts,
+ *     more than 64 members, two devices, and — it depends on the handles' specs — a short workspace.  A refused call enqueues nothing.
+ */
+int rdv_ppo_mlp_set_spec_check(const RdvMlpSpec* actor_spec_host, const RdvMlpSpec* critic_spec_host);
+int64_t rdv_ppo_mlp_set_workspace_bytes(const RdvMlpSpec* actor_spec_host, const RdvMlpSpec* critic_spec_host, int32_t n_members,
+                                        const int64_t* counts_host);
+int rdv_ppo_mlp_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host,
+                              double clip_range, double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes,
+                              const RdvPpoSetOut* out, void* stream);
+
+/*
+ * Gradient clip, Adam and weight repack for policy sets of every MLP architecture (added within ABI 5: additive export):
+ * rdv_ppo_set_adam_step for an actor set and a critic set of ANY pair of RdvMlpSpec (csrc/rdv_ppo_adam.h, "every MLP architecture"),
+ * what follows rdv_ppo_mlp_set_loss_grad in a sweep's update step.  RdvAdamState is reused as it is; its rows, and those of actor_grad /
+ * critic_grad, are Ga = rdv_ppo_mlp_grad_floats (actor spec, 1) and Gc = rdv_ppo_mlp_grad_floats (critic spec, 0) floats long, back to
+ * back, in the layout of rdv_ppo_mlp_loss_grad (the base pointers 16-byte aligned, the rows 4-byte aligned only).
+ *
+ * The contract is that of rdv_ppo_set_adam_step, restated for any pair of specs:
+ *   - One norm per member over its Ga + Gc entries: squares added in double (thread t adds entries t, t + 256, .. of [actor | critic],
+ *     then a fixed tree), the square root in double rounded to float once; clip_coef, the two step coefficients, coef[g] and step[g] as
+ *     in rdv_ppo_set_adam_step; a member whose norm is not finite is skipped whole (coef[g][4] = 1).
+ *   - The elementwise step: the same four float32 lines, every operation rounded on its own.
+ *   - Member g's two forward blocks become the bytes pack_mlp_weights (what rdv_policy_create_mlp / rdv_critic_create_mlp pack) gives from
+ *     the new fp32 parameters — the per-layer shift, the two fp16 terms rounded to nearest even with subnormals kept, the fragment order,
+ *     zero fragments for the rows and k-steps a 16- or 32-wide layer does not have, the head's rows >= out_dim zero, the biases in
+ *     accumulator order, each layer's inverse accumulator scale, log_std — but for the six exp(log_std) floats of an actor block: the
+ *     double-precision exp rounded to float, within 1 ulp of the host's.
+ *   - Two launches, no workspace, nothing read back from a block; a member whose mask bit is clear has nothing read or written; no
+ *     floating-point atomic; the same bits eager or replayed; enqueue only, legal inside a capture (each replay takes the next step).
+ *   - Two sets of the default spec: the call IS rdv_ppo_set_adam_step, its bits and its refusals.  One default-spec set beside a general
+ *     one is refused.  Order of checks and messages: those of rdv_ppo_set_adam_step (host-only checks naming the argument, then
+ *     RDV_ERR_BAD_HANDLE, then recurrent / swapped / the mixed pair / member counts / more than 64 members / two devices).
+ */
+int rdv_ppo_mlp_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state,
+                              const float* actor_grad, const float* critic_grad, uint64_t active_mask,
+                              double lr, double beta1, double beta2, double eps, double max_grad_norm, void* stream);
+
+/*
  * The recurrent policy (added within ABI 5: additive exports): what the reference's main_rnn.py trains and tune_policy.py:80, :140-148
  * and tune_algorithm.py:68 build — sb3-contrib RecurrentPPO("MlpLstmPolicy"), i.e. RecurrentActorCriticPolicy with ONE LSTM layer of
  * lstm_hidden_size H in front of the mlp_extractor trunk, and separate LSTMs for actor and critic (shared_lstm = False,

@@ -49,7 +49,11 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # gradient clip, Adam and weight repack for policy sets (added within ABI 5)
            "rdv_ppo_set_adam_step", "rdv_policy_block_floats", "rdv_policy_get_block",
            # PPO minibatch gradients for every MLP architecture (added within ABI 5)
-           "rdv_ppo_mlp_spec_check", "rdv_ppo_mlp_grad_floats", "rdv_ppo_mlp_workspace_bytes", "rdv_ppo_mlp_loss_grad"]
+           "rdv_ppo_mlp_spec_check", "rdv_ppo_mlp_grad_floats", "rdv_ppo_mlp_workspace_bytes", "rdv_ppo_mlp_loss_grad",
+           # PPO minibatch gradients for policy sets of every MLP architecture (added within ABI 5)
+           "rdv_ppo_mlp_set_spec_check", "rdv_ppo_mlp_set_workspace_bytes", "rdv_ppo_mlp_set_loss_grad",
+           # gradient clip, Adam and weight repack for policy sets of every MLP architecture (added within ABI 5)
+           "rdv_ppo_mlp_set_adam_step"]
 
 
 class RdvError(RuntimeError):
@@ -275,6 +279,10 @@ def lib():
         "rdv_ppo_mlp_grad_floats": (i64, [C.POINTER(MlpSpec), C.c_int]),
         "rdv_ppo_mlp_workspace_bytes": (i64, [C.POINTER(MlpSpec), C.POINTER(MlpSpec), i64]),
         "rdv_ppo_mlp_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), i64, C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoOut), vp]),
+        "rdv_ppo_mlp_set_spec_check": (C.c_int, [C.POINTER(MlpSpec), C.POINTER(MlpSpec)]),
+        "rdv_ppo_mlp_set_workspace_bytes": (i64, [C.POINTER(MlpSpec), C.POINTER(MlpSpec), i32, C.POINTER(i64)]),
+        "rdv_ppo_mlp_set_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), C.POINTER(i64), C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoSetOut), vp]),
+        "rdv_ppo_mlp_set_adam_step": (C.c_int, [vp, vp, C.POINTER(AdamState), vp, vp, u64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

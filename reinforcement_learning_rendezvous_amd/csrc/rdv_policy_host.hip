@@ -1,6 +1,6 @@
 // rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
 // value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
-// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_*, rdv_ppo_set_adam_step, rdv_policy_get_block, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
+// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_* (the set form rdv_ppo_mlp_set_* among them), rdv_ppo_set_adam_step, rdv_policy_get_block, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
 // mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch, ppo_adam_launch), so an edit to an argument check recompiles no kernel.
 #define RDV_POLICY_FUNCTIONS_ONLY
@@ -788,6 +788,14 @@ int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_hos
   return any ? ppo_set_table(n_members, counts_host, nullptr) : -1;
 }
 
+// different member counts, more members than one call serves: every set entry point's last two refusals of the architecture
+static int check_set_members(const char* who, rdv_policy actor_set, rdv_policy critic_set) {
+  if (actor_set->n_members != critic_set->n_members)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, critic_set has %d", who, actor_set->n_members, critic_set->n_members);
+  if (actor_set->n_members > kPpoSetMaxMembers)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, at most %d are served by one call (kPpoSetMaxMembers)", who, actor_set->n_members, kPpoSetMaxMembers);
+  return RDV_OK;
+}
 // what the set entry points (rdv_ppo_set_loss_grad, rdv_ppo_set_adam_step) refuse of the architecture of two valid feed-forward sets, in this
 // order: another architecture than the shipped one, different member counts, more members than one call serves
 static int check_shipped_sets(const char* who, rdv_policy actor_set, rdv_policy critic_set, const char* not_built) {
@@ -795,11 +803,7 @@ static int check_shipped_sets(const char* who, rdv_policy actor_set, rdv_policy 
   for (const auto& a : nets)
     if (!is_default_spec(a.p->spec) || !a.p->shipped_arch)
       return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not the shipped architecture (two hidden layers of 64, tanh): %s", who, a.name, not_built);
-  if (actor_set->n_members != critic_set->n_members)
-    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, critic_set has %d", who, actor_set->n_members, critic_set->n_members);
-  if (actor_set->n_members > kPpoSetMaxMembers)
-    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set has %d members, at most %d are served by one call (kPpoSetMaxMembers)", who, actor_set->n_members, kPpoSetMaxMembers);
-  return RDV_OK;
+  return check_set_members(who, actor_set, critic_set);
 }
 
 int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host, double clip_range,
@@ -828,10 +832,101 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
   return RDV_OK;
 }
 
+// ---- PPO minibatch gradients for policy sets of every MLP architecture (csrc/rdv_ppo_mlp.h, "the set form")
+int rdv_ppo_mlp_set_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec) {
+  if (!actor_spec || !critic_spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_mlp_set_spec_check: null %s", !actor_spec ? "actor_spec" : "critic_spec");
+  const struct { const RdvMlpSpec* s; const char* name; } nets[] = {{actor_spec, "actor_set"}, {critic_spec, "critic_set"}};
+  for (const auto& a : nets)
+    if (int rc = rdv_mlp_spec_check(a.s)) {
+      const std::string why = rdv_last_error();
+      return fail(rc, "rdv_ppo_mlp_set_spec_check: %s: %s", a.name, why.c_str());
+    }
+  // (is_shipped: the predicate that gives a handle its shipped block and kernels, i.e. what check_mlp_sets reads off the handles)
+  if (is_shipped(actor_spec) != is_shipped(critic_spec))
+    return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_mlp_set_loss_grad, rdv_ppo_mlp_set_adam_step: %s has the default spec (the shipped block and kernels), %s another: the mixed pair is not built",
+                is_shipped(actor_spec) ? "actor_set" : "critic_set", is_shipped(actor_spec) ? "critic_set" : "actor_set");
+  return RDV_OK;
+}
+
+static bool ppo_counts_ok(int32_t n_members, const int64_t* counts_host) {
+  if (n_members < 1 || n_members > kPpoSetMaxMembers || !counts_host) return false;
+  bool any = false;
+  for (int32_t g = 0; g < n_members; ++g) {
+    if (counts_host[g] < 0) return false;
+    any = any || counts_host[g] > 0;
+  }
+  return any;
+}
+
+// the general layout's table and bytes for a pair of general specs
+static int64_t ppo_mlp_set_bytes(const RdvMlpSpec& actor_spec, const RdvMlpSpec& critic_spec, int32_t n_members, const int64_t* counts, PpoMlpSetLaunch* L) {
+  PpoMlpTable a, c;
+  ppo_mlp_table(actor_spec, true, a);
+  ppo_mlp_table(critic_spec, false, c);
+  if (L) { L->a.actor = a; L->a.critic = c; }
+  return ppo_mlp_set_table(a, c, n_members, counts, L ? &L->table : nullptr, L ? &L->max_groups_a : nullptr, L ? &L->max_groups_c : nullptr);
+}
+int64_t rdv_ppo_mlp_set_workspace_bytes(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec, int32_t n_members, const int64_t* counts_host) {
+  if (!mlp_spec_ok(actor_spec) || !mlp_spec_ok(critic_spec) || !ppo_counts_ok(n_members, counts_host)) return -1;
+  // member by member what rdv_ppo_mlp_workspace_bytes answers for one (for the default pair the larger of the two layouts): the sum rule
+  int64_t bytes = 0;
+  for (int32_t g = 0; g < n_members; ++g)
+    if (counts_host[g] > 0) bytes += ppo_mlp_bytes(*actor_spec, *critic_spec, counts_host[g]);
+  return bytes;
+}
+
+// both handles valid feed-forward sets (or plain handles) of the default spec on the shipped kernels: the set calls of rdv_ppo.h / rdv_ppo_adam.h serve them
+static bool shipped_pair(rdv_policy a, rdv_policy c) {
+  const auto ok = [](rdv_policy p) { return p && p->magic == kPolicyMagic && !p->lstm_hidden && p->shipped_arch && is_default_spec(p->spec); };
+  return ok(a) && ok(c);
+}
+// what the two general set entry points refuse of the architecture of two valid feed-forward sets: the mixed pair, then check_set_members
+static int check_mlp_sets(const char* who, rdv_policy actor_set, rdv_policy critic_set) {
+  if (actor_set->shipped_arch != critic_set->shipped_arch)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s has the default spec (the shipped block and kernels), %s another: the mixed pair is not built", who,
+                actor_set->shipped_arch ? "actor_set" : "critic_set", actor_set->shipped_arch ? "critic_set" : "actor_set");
+  return check_set_members(who, actor_set, critic_set);
+}
+
+int rdv_ppo_mlp_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host, double clip_range,
+                              double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoSetOut* out, void* stream) {
+  const char* who = "rdv_ppo_mlp_set_loss_grad";
+  // two sets of the default spec: the call IS rdv_ppo_set_loss_grad, its bits and its refusals
+  if (shipped_pair(actor_set, critic_set))
+    return rdv_ppo_set_loss_grad(actor_set, critic_set, rows, counts_host, clip_range, ent_coef, vf_coef, workspace, workspace_bytes, out, stream);
+  // (counts_host: one entry per member of the handles, read as rdv_ppo_set_loss_grad reads it)
+  const bool valid = actor_set && actor_set->magic == kPolicyMagic;
+  const int32_t P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
+  if (int rc = check_ppo_call(who, rows, out, workspace, true, 0, P, counts_host)) return rc;
+  if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
+  auto sets = [&]() -> int { return check_mlp_sets(who, actor_set, critic_set); };
+  if (int rc = check_ppo_handles(who, actor_set, critic_set, {true, "actor_set", "critic_set", "rdv_critic_set_create", "rdv_policy_set_create"},
+                                 [](rdv_policy, const char*) { return RDV_OK; }, sets)) return rc;
+  PpoMlpSetLaunch L = {};
+  const int64_t need = ppo_mlp_set_bytes(actor_set->spec, critic_set->spec, P, counts_host, &L);
+  if (workspace_bytes < need)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, these counts and specs need %lld (rdv_ppo_mlp_set_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
+  const PpoMlpTable ta = L.a.actor, tc = L.a.critic;
+  if (ta.block_floats != actor_set->block_floats || tc.block_floats != critic_set->block_floats)
+    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor_set->block_floats, critic_set->block_floats, ta.block_floats, tc.block_floats);
+  DeviceGuard guard(actor_set->device);
+  if (int rc = raise_ppo_lds_limit(ppo_mlp_raise_lds_limit, g_ppo_mlp_lds_raised, actor_set->device)) return rc;
+  L.a = {actor_set->weights, critic_set->weights, actor_set->spec.activation, critic_set->spec.activation, ta, tc,
+         rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, 0,
+         ppo_coefs(clip_range, ent_coef, vf_coef), static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
+  L.n_members = P;
+  ppo_mlp_set_launch(L, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
 // ---- gradient clip, Adam and weight repack for policy sets (csrc/rdv_ppo_adam.h)
-int rdv_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
-                          uint64_t active_mask, double lr, double beta1, double beta2, double eps, double max_grad_norm, void* stream) {
-  const char* who = "rdv_ppo_set_adam_step";
+extern "C++" {
+// The host-only checks of the two optimiser entry points, in this order: state and every pointer non-null, 16-byte aligned; the five
+// scalars; the mask (one bit per member of the handles; with an invalid actor handle, refused behind these checks, it is judged as one
+// member's, and a set larger than the cap as the cap's).  P: that member count.
+static int check_adam_call(const char* who, rdv_policy actor_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
+                           uint64_t active_mask, double lr, double beta1, double beta2, double eps, double max_grad_norm, int32_t& P) {
   if (!state) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: state is null", who);
   const struct { const void* p; const char* name; } ptrs[] = {
       {state->actor_param, "state->actor_param"}, {state->critic_param, "state->critic_param"}, {state->actor_m, "state->actor_m"},
@@ -848,12 +943,21 @@ int rdv_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const Rdv
   // the mask has one bit per member of the handles; with an invalid actor handle (refused below, behind the host-only checks) it is
   // judged as one member's, and a set larger than the cap (refused below) as the cap's
   const bool valid = actor_set && actor_set->magic == kPolicyMagic;
-  const int32_t P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
+  P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
   if (P < 64 && (active_mask >> P)) {
     int bit = 63;
     while (!((active_mask >> bit) & 1)) --bit;
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: active_mask has bit %d set, the set has %d member%s", who, bit, P, P == 1 ? "" : "s");
   }
+  return RDV_OK;
+}
+}  // extern "C++"
+
+int rdv_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
+                          uint64_t active_mask, double lr, double beta1, double beta2, double eps, double max_grad_norm, void* stream) {
+  const char* who = "rdv_ppo_set_adam_step";
+  int32_t P;
+  if (int rc = check_adam_call(who, actor_set, state, actor_grad, critic_grad, active_mask, lr, beta1, beta2, eps, max_grad_norm, P)) return rc;
   const char* not_built = "its optimiser step is not built";
   auto shipped_sets = [&]() -> int { return check_shipped_sets(who, actor_set, critic_set, not_built); };
   if (int rc = check_ppo_handles(who, actor_set, critic_set, {true, "actor_set", "critic_set", "rdv_critic_set_create", "rdv_policy_set_create", not_built},
@@ -868,6 +972,38 @@ int rdv_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const Rdv
   a.step = state->step; a.coef = state->coef; a.actor_grad = actor_grad; a.critic_grad = critic_grad;
   a.mask = active_mask; a.n_members = P;
   ppo_adam_launch(ppo_adam_scalars(a, lr, beta1, beta2, eps, max_grad_norm), static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- gradient clip, Adam and weight repack for policy sets of every MLP architecture (csrc/rdv_ppo_adam.h, "every MLP architecture")
+int rdv_ppo_mlp_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
+                              uint64_t active_mask, double lr, double beta1, double beta2, double eps, double max_grad_norm, void* stream) {
+  const char* who = "rdv_ppo_mlp_set_adam_step";
+  // two sets of the default spec: the call IS rdv_ppo_set_adam_step, its bits and its refusals
+  if (shipped_pair(actor_set, critic_set))
+    return rdv_ppo_set_adam_step(actor_set, critic_set, state, actor_grad, critic_grad, active_mask, lr, beta1, beta2, eps, max_grad_norm, stream);
+  int32_t P;
+  if (int rc = check_adam_call(who, actor_set, state, actor_grad, critic_grad, active_mask, lr, beta1, beta2, eps, max_grad_norm, P)) return rc;
+  const char* not_built = "its optimiser step is not built";
+  auto sets = [&]() -> int { return check_mlp_sets(who, actor_set, critic_set); };
+  if (int rc = check_ppo_handles(who, actor_set, critic_set, {true, "actor_set", "critic_set", "rdv_critic_set_create", "rdv_policy_set_create", not_built},
+                                 [](rdv_policy, const char*) { return RDV_OK; }, sets)) return rc;
+  PpoMlpAdamLaunch A = {};
+  ppo_mlp_table(actor_set->spec, true, A.T[0]);
+  ppo_mlp_table(critic_set->spec, false, A.T[1]);
+  if (A.T[0].block_floats != actor_set->block_floats || A.T[1].block_floats != critic_set->block_floats)
+    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor_set->block_floats, critic_set->block_floats,
+                A.T[0].block_floats, A.T[1].block_floats);
+  DeviceGuard guard(actor_set->device);
+  PpoAdamLaunch& a = A.a;
+  a.actor_block = actor_set->weights; a.critic_block = critic_set->weights;
+  a.actor_param = state->actor_param; a.critic_param = state->critic_param;
+  a.actor_m = state->actor_m; a.actor_v = state->actor_v; a.critic_m = state->critic_m; a.critic_v = state->critic_v;
+  a.step = state->step; a.coef = state->coef; a.actor_grad = actor_grad; a.critic_grad = critic_grad;
+  a.mask = active_mask; a.n_members = P;
+  a = ppo_adam_scalars(a, lr, beta1, beta2, eps, max_grad_norm);
+  ppo_mlp_adam_launch(A, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }

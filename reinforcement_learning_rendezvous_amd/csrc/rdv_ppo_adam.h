@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "rdv_ppo.h"
+#include "rdv_ppo_mlp.h"
 
 namespace rdv {
 
@@ -55,5 +56,32 @@ inline PpoAdamLaunch ppo_adam_scalars(PpoAdamLaunch a, double lr, double beta1, 
 }
 
 __attribute__((visibility("hidden"))) void ppo_adam_launch(const PpoAdamLaunch& a, hipStream_t s);
+
+// ---- every MLP architecture (rdv_ppo_mlp_set_adam_step, include/rdv.h "Gradient clip, Adam and weight repack for policy sets of every
+// MLP architecture"): the same two launches for an actor set and a critic set of ANY pair of RdvMlpSpec, the layers taken from the two
+// PpoMlpTable (rdv_ppo_mlp.h) that travel by value in the kernel arguments.  Rows are Ga / Gc floats long (rdv_ppo_mlp_grad_floats), back
+// to back, hence 4-byte aligned only: every access to them is one float.
+//   1. ppo_mlp_adam_norm_kernel    grid (P): ppo_adam_norm_kernel with the two lengths as arguments — the same double sums (thread t adds
+//      entries t, t + 256, .. of [actor | critic], the fixed tree), the same coefficients, the same skip of a non-finite norm.
+//   2. ppo_mlp_adam_update_kernel  grid (2, P), 256 threads, workgroup (net, g):
+//        step    the four float32 lines of ppo_adam_update_kernel; the new parameters stay in LDS: 14,028 floats for the largest net
+//                (4 x 64, actor) = 56,112 B, plus 20 maxima and 5 shifts: 56,212 B static LDS;
+//        shifts  max |w| per layer, then pol_layer_shift's rule;
+//        repack  the forward block of pack_mlp_weights (rdv_policy_mlp.h) from LDS: thread q builds the 16 bytes that lane (q & 63) of
+//                fragment (q >> 6) reads — fragment order [term][mt][ks] per layer, layer 0 in natural k order, later layers in the
+//                accumulator's; rows >= the layer's width and k >= its input width are zero, so a 16- or 32-wide layer's missing rows
+//                and k-steps and the head's rows >= out_dim are zero fragments — then the biases in accumulator order times
+//                2^(10 + s) (padded rows zero), record word 4 of each layer (2^-(10 + s)), and an actor's exp(log_std) (the
+//                double-precision exp rounded to float) and log_std.  The block's integer header, the other record words and floats
+//                64..127 are constants of the spec: they are left as rdv_policy_set_create wrote them.
+// The shipped kernels above stay as they are beside these (their instruction streams are the parent's: profiles/ppo_mlp_set_isa_diff.md);
+// the shipped block's layout (biases before the scales, no header) is another one, not a case of this table.
+constexpr int kPpoMlpAdamMaxFloats = 17 * 64 + 64 + 3 * (64 * 64 + 64) + 6 * 64 + 6 + 6;   // 14,028
+struct PpoMlpAdamLaunch {
+  PpoAdamLaunch a;                 // the blocks: member g at g * T[net].block_floats; the rows [P, Ga] / [P, Gc]
+  PpoMlpTable T[2];                // actor, critic
+};
+static_assert(sizeof(PpoMlpAdamLaunch) <= 4096, "the arguments fit the 4 KiB kernel-argument segment");
+__attribute__((visibility("hidden"))) void ppo_mlp_adam_launch(const PpoMlpAdamLaunch& a, hipStream_t s);
 
 }  // namespace rdv

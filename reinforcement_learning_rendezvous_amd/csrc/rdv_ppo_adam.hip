@@ -6,6 +6,7 @@
 #pragma clang fp contract(off)
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
+#include "rdv_policy_mlp.h"
 #include "rdv_ppo_adam.h"
 
 namespace rdv {
@@ -169,6 +170,147 @@ __global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_update_kernel(const 
     o.w = ppo_adam_tail(w, 4 * t + 3, actor, out_dim, sh[0], sh[1], sh[2]);
     *reinterpret_cast<float4*>(block + kPolF32 + 4 * t) = o;
   }
+}
+
+// ---- every MLP architecture: the same two kernels on the layers of a table
+static_assert(kPpoMlpAdamMaxFloats * 4 + 25 * 4 <= 64 * 1024, "the largest net's parameters fit the static LDS");
+
+__global__ __launch_bounds__(kPpoAdamThreads) void ppo_mlp_adam_norm_kernel(const PpoMlpAdamLaunch A) {
+  const PpoAdamLaunch& a = A.a;
+  const int g = blockIdx.x, t = threadIdx.x;
+  if (!((a.mask >> g) & 1)) return;                                // (workgroup-uniform) an inactive member: nothing read, nothing written
+  __shared__ double part[kPpoAdamThreads];
+  const int na = A.T[0].grad_floats, nc = A.T[1].grad_floats;
+  const float* ga = a.actor_grad + (size_t)g * na;
+  const float* gc = a.critic_grad + (size_t)g * nc;
+  double s = 0.0;
+  for (int i = t; i < na + nc; i += kPpoAdamThreads) {
+    const double x = (double)(i < na ? ga[i] : gc[i - na]);
+    s += x * x;
+  }
+  part[t] = s;
+  for (int w = kPpoAdamThreads / 2; w > 0; w >>= 1) {              // the fixed tree of ppo_adam_norm_kernel
+    __syncthreads();
+    if (t < w) part[t] += part[t + w];
+  }
+  if (t != 0) return;
+  const float total = (float)sqrt(part[0]);
+  float4* c = reinterpret_cast<float4*>(a.coef + (size_t)g * kPpoAdamCoef);
+  if (!(fabsf(total) <= 3.402823466e+38f)) {                       // inf or NaN: the member is skipped whole
+    c[0] = make_float4(total, 0.0f, 0.0f, 0.0f);
+    c[1] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  const float clip = (float)fmin(1.0, (double)a.max_grad_norm / ((double)total + (double)1e-6f));
+  const int64_t tt = a.step[g] + 1;
+  const double bc1 = 1.0 - pow(a.beta1, (double)tt), bc2 = 1.0 - pow(a.beta2, (double)tt);
+  c[0] = make_float4(total, clip, (float)(a.lr / bc1), (float)(1.0 / sqrt(bc2)));
+  c[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  a.step[g] = tt;
+}
+
+__global__ __launch_bounds__(kPpoAdamThreads) void ppo_mlp_adam_update_kernel(const PpoMlpAdamLaunch A) {
+  const PpoAdamLaunch& a = A.a;
+  const int net = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
+  if (!((a.mask >> g) & 1)) return;                                // (both tests are workgroup-uniform and ahead of every barrier)
+  const float4 c = *reinterpret_cast<const float4*>(a.coef + (size_t)g * kPpoAdamCoef);
+  if (a.coef[(size_t)g * kPpoAdamCoef + 4] != 0.0f) return;        // a non-finite norm: the member is skipped whole
+  const float clip = c.y, step_size = c.z, isb2 = c.w;
+
+  __shared__ __attribute__((aligned(16))) float w[kPpoMlpAdamMaxFloats];
+  __shared__ float red[(kPpoAdamThreads / 64) * kMlpLayers];
+  __shared__ int shs[kMlpLayers];
+  const bool actor = net == 0;
+  const PpoMlpTable& T = A.T[net];
+  const int count = T.grad_floats, L = T.L;
+  const size_t row = (size_t)g * (size_t)count;
+  const float* gr = (actor ? a.actor_grad : a.critic_grad) + row;
+  float* p = (actor ? a.actor_param : a.critic_param) + row;
+  float* m = (actor ? a.actor_m : a.critic_m) + row;
+  float* v = (actor ? a.actor_v : a.critic_v) + row;
+
+  for (int i = t; i < count; i += kPpoAdamThreads) {
+    const float gp = gr[i] * clip;
+    const float mo = m[i];
+    const float mn = mo + (gp - mo) * a.omb1;
+    const float vn = v[i] * a.b2 + (a.omb2 * gp) * gp;
+    const float pn = p[i] - step_size * (mn / (sqrtf(vn) * isb2 + a.eps));
+    m[i] = mn; v[i] = vn; p[i] = pn;
+    w[i] = pn;
+  }
+  __syncthreads();
+
+  // max |w| per layer: the thread's, the wave's, the workgroup's (a maximum does not depend on the order)
+  for (int l = 0; l <= L; ++l) {
+    const int n = T.out_w[l] * T.in_w[l], at = T.w_off[l];
+    float mx = 0.0f;
+    for (int i = t; i < n; i += kPpoAdamThreads) mx = fmaxf(mx, fabsf(w[at + i]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
+    if ((t & 63) == 0) red[(t >> 6) * kMlpLayers + l] = mx;
+  }
+  __syncthreads();
+  if (t <= L) {
+    float all = red[t];
+#pragma unroll
+    for (int wv = 1; wv < kPpoAdamThreads / 64; ++wv) all = fmaxf(all, red[wv * kMlpLayers + t]);
+    shs[t] = adam_shift(all);
+  }
+  __syncthreads();
+
+  float* block = (actor ? a.actor_block : a.critic_block) + (size_t)g * T.block_floats;
+  int frags = 0, tiles = 0;
+  for (int l = 0; l <= L; ++l) { frags += 2 * T.mt[l] * T.ks[l]; tiles += T.mt[l]; }
+
+  // the fp16 section: one 16-byte store per (fragment, lane); fragment frag0_l + (term MT + mt) KS + ks of layer l
+  for (int q = t; q < frags * 64; q += kPpoAdamThreads) {
+    const int frag = q >> 6, lane = q & 63, r = lane & 31, h = lane >> 5;
+    int l = 0, f0 = 0;
+    for (int k = 0, at = 0; k <= L; ++k) {
+      const int n = 2 * T.mt[k] * T.ks[k];
+      if (frag >= at && frag < at + n) { l = k; f0 = at; }
+      at += n;
+    }
+    const int MT = T.mt[l], KS = T.ks[l], in_w = T.in_w[l], out_w = T.out_w[l], at = T.w_off[l], sft = shs[l];
+    const int f = frag - f0, term = f / (MT * KS), mt = (f / KS) % MT, ks = f % KS;
+    const int orow = 32 * mt + r;
+    f16x8 out;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      // layer 0: natural k order (its B operand is built from obs rows); later layers: the k order of an accumulator tile
+      const int k = l == 0 ? 16 * ks + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+      const float x = (orow < out_w && k < in_w) ? w[at + orow * in_w + k] : 0.0f;
+      const float ws = ldexpf(x, sft);
+      const _Float16 hi = (_Float16)ws;                            // round to nearest even, subnormals kept
+      out[j] = term == 0 ? hi : (_Float16)(ws - (float)hi);        // (the difference is exact in fp32)
+    }
+    *reinterpret_cast<f16x8*>(block + kMlpHdr + 4 * q) = out;
+  }
+  // the biases in accumulator order, [mt][h][16] per layer, times the accumulator's scale; padded rows zero
+  float* biases = block + kMlpHdr + frags * (kPolFragBytes / 4);
+  for (int i = t; i < tiles * 32; i += kPpoAdamThreads) {
+    const int tile = i >> 5;
+    int l = 0, t0 = 0;
+    for (int k = 0, at = 0; k <= L; ++k) {
+      if (tile >= at && tile < at + T.mt[k]) { l = k; t0 = at; }
+      at += T.mt[k];
+    }
+    const int mt = tile - t0, h = (i >> 4) & 1, e = i & 15;
+    const int orow = 32 * mt + (e & 3) + 8 * (e >> 2) + 4 * h;
+    biases[i] = orow < T.out_w[l] ? w[T.b_off[l] + orow] * ldexpf(1.0f, kPolXShift + shs[l]) : 0.0f;
+  }
+  // record word 4 of each layer: the inverse accumulator scale (a power of two: exact); an actor's exp(log_std) and log_std
+  if (t <= L) block[kMlpRec + kMlpRecStride * t + 4] = ldexpf(1.0f, -(kPolXShift + shs[t]));
+  if (actor && t >= 64 && t < 64 + kPolOut) {
+    const float ls = w[T.ls_off + (t - 64)];
+    block[kMlpStd + (t - 64)] = (float)exp((double)ls);
+    block[kMlpStd + 8 + (t - 64)] = ls;
+  }
+}
+
+void ppo_mlp_adam_launch(const PpoMlpAdamLaunch& A, hipStream_t s) {
+  hipLaunchKernelGGL(ppo_mlp_adam_norm_kernel, dim3((unsigned)A.a.n_members), dim3(kPpoAdamThreads), 0, s, A);
+  hipLaunchKernelGGL(ppo_mlp_adam_update_kernel, dim3(2, (unsigned)A.a.n_members), dim3(kPpoAdamThreads), 0, s, A);
 }
 
 void ppo_adam_launch(const PpoAdamLaunch& a, hipStream_t s) {

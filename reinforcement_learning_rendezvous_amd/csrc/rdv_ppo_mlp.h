@@ -111,7 +111,45 @@ struct PpoMlpLaunch {
   float *actor_grad, *critic_grad, *scalars, *log_prob, *values;
 };
 
-__attribute__((visibility("hidden"))) hipError_t ppo_mlp_raise_lds_limit();
+// ---- the set form (rdv_ppo_mlp_set_loss_grad, include/rdv.h "PPO minibatch gradients for policy sets of every MLP architecture"): P
+// members of ONE pair of specs in the same four launches, as rdv_ppo.h gives the shipped kernels a set form — the same bodies, the member
+// taken from the grid, PpoSetTable (count, off, ws per member) BY VALUE in the kernel arguments, hence the same cap of 64 members.
+//   ppo_mlp_set_transpose_kernel   grid (53, 2, P)                                 member z, net y
+//   ppo_mlp_net_kernel<.., true>   grid (max_g workgroups_net(counts[g]), P)       workgroup (x, y) is workgroup x of member y's stand-alone
+//                                  launch; it returns before its first barrier when it has no rows of that member (workgroup-uniform)
+//   ppo_mlp_set_finish_kernel      grid (ceil((Ga + Gc + 1) / 256), P)             member y
+// Member y's forward block is set base + y * block_floats (a set allocation holds exactly the bytes of stand-alone handles); its piece of
+// the workspace, at table.ws[y], is the stand-alone layout above for n = count[y] (members with count 0 have none); `indices`, log_prob
+// and values are advanced by off[y].  The workgroup size stays ppo_mlp_waves of each net's spec, so actor and critic may cut a member's
+// rows differently (256 or 128 per workgroup) and their grids differ in x: per member the partition, the wave-order sums and the
+// index-order sum of the last kernel are exactly the stand-alone call's, and so is every bit of its outputs.
+// Fills `t` for counts[0 .. n_members) (all >= 0, n_members <= kPpoSetMaxMembers) -> the workspace's size in bytes.
+inline int64_t ppo_mlp_set_table(const PpoMlpTable& a, const PpoMlpTable& c, int32_t n_members, const int64_t* counts, PpoSetTable* t,
+                                 int64_t* max_groups_a = nullptr, int64_t* max_groups_c = nullptr) {
+  int64_t off = 0, ws = 0, most_a = 0, most_c = 0;
+  for (int g = 0; g < kPpoSetMaxMembers; ++g) {
+    const int64_t n = g < n_members ? counts[g] : 0;
+    if (t) { t->count[g] = n; t->off[g] = off; t->ws[g] = ws; }
+    off += n;
+    if (n > 0) ws += ppo_mlp_workspace_floats(a, c, n);
+    if (ppo_mlp_workgroups(a, n) > most_a) most_a = ppo_mlp_workgroups(a, n);
+    if (ppo_mlp_workgroups(c, n) > most_c) most_c = ppo_mlp_workgroups(c, n);
+  }
+  if (max_groups_a) *max_groups_a = most_a;
+  if (max_groups_c) *max_groups_c = most_c;
+  return ws * (int64_t)sizeof(float);
+}
+
+struct PpoMlpSetLaunch {
+  PpoMlpLaunch a;         // actor_block, critic_block: the sets' allocations; n unused; indices required; actor_grad [P, Ga], critic_grad
+                          // [P, Gc], scalars [P, 8]; log_prob, values [sum of counts], nullable
+  int32_t n_members;
+  int64_t max_groups_a, max_groups_c;
+  PpoSetTable table;
+};
+
+__attribute__((visibility("hidden"))) hipError_t ppo_mlp_raise_lds_limit();   // the plain and the set instantiations
 __attribute__((visibility("hidden"))) void ppo_mlp_launch(const PpoMlpLaunch& a, hipStream_t s);
+__attribute__((visibility("hidden"))) void ppo_mlp_set_launch(const PpoMlpSetLaunch& a, hipStream_t s);
 
 }  // namespace rdv

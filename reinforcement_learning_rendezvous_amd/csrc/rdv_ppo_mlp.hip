@@ -6,6 +6,8 @@
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_ppo_mlp.h"
 
+#include <type_traits>
+
 namespace rdv {
 
 // LDS of ppo_mlp_net_kernel (floats), W = waves of the workgroup (8 or 4, ppo_mlp_waves):
@@ -17,10 +19,7 @@ static_assert((kMlpMaxFloats + 4 * kPpoWaveFloats) * 4 <= kPpoMlpLdsLimit, "the 
 //   W_l,q[o][i],  o = perm(ks, h, j) (the k order of an accumulator tile used as B operand),  i = 32 mt + r,
 // read from where the forward block keeps it: fragment frag0_l + (q MT_l + (o >> 5)) KS_l + ks(i), lane (o & 31, h(i)), element j(i) — the
 // inverse of perm — or zero where the forward layer has no such tile row or k-step (a 16-wide neighbour).
-__global__ __launch_bounds__(512) void ppo_mlp_transpose_kernel(const float* __restrict__ actor_block, const float* __restrict__ critic_block,
-                                                                float* __restrict__ workspace) {
-  const float* block = blockIdx.y == 0 ? actor_block : critic_block;
-  float* dstf = workspace + (size_t)blockIdx.y * kPpoMlpBwdFloats;
+__device__ __forceinline__ void ppo_mlp_transpose_body(const float* __restrict__ block, float* __restrict__ dstf) {
   const int b = blockIdx.x, t = threadIdx.x;
   if (b == kPpoMlpBwdFrags) { if (t < 64) dstf[kPpoMlpBwdZero + t] = 0.0f; return; }
   const int32_t* H = reinterpret_cast<const int32_t*>(block);
@@ -44,6 +43,19 @@ __global__ __launch_bounds__(512) void ppo_mlp_transpose_kernel(const float* __r
     v = src[((size_t)(frag0 + (q * MT + (x.o >> 5)) * KS + x.ks_i) * 64 + (size_t)((x.o & 31) + 32 * x.h_i)) * 8 + x.j_i];
   }
   reinterpret_cast<uint16_t*>(dstf)[((size_t)b * 64 + lane) * 8 + j] = v;
+}
+__global__ __launch_bounds__(512) void ppo_mlp_transpose_kernel(const float* __restrict__ actor_block, const float* __restrict__ critic_block,
+                                                                float* __restrict__ workspace) {
+  ppo_mlp_transpose_body(blockIdx.y == 0 ? actor_block : critic_block, workspace + (size_t)blockIdx.y * kPpoMlpBwdFloats);
+}
+// the set form: member blockIdx.z of the sets' allocations -> the head of its piece of the workspace; a member without samples is skipped
+__global__ __launch_bounds__(512) void ppo_mlp_set_transpose_kernel(const float* __restrict__ actor_set, const float* __restrict__ critic_set,
+                                                                    float* __restrict__ workspace, int actor_floats, int critic_floats,
+                                                                    const PpoSetTable T) {
+  const int g = blockIdx.z;
+  if (T.count[g] == 0) return;
+  const float* block = blockIdx.y == 0 ? actor_set + (size_t)g * actor_floats : critic_set + (size_t)g * critic_floats;
+  ppo_mlp_transpose_body(block, workspace + T.ws[g] + (size_t)blockIdx.y * kPpoMlpBwdFloats);
 }
 
 // ---- 2, 3. one net's loss terms and gradients
@@ -187,11 +199,56 @@ __device__ __forceinline__ void input_step(const PpoMlpTable& T, float (&dl)[2][
   });
 }
 
+// The set form's arguments: `net` holds the set-wide values (block: the set's allocation; parts: the workspace; rows.indices and out: all
+// members'; bwd and rows.n unused; T: the one table of this net); ppo_mlp_member derives member blockIdx.y's own WITHOUT the table, which
+// stays in the kernel-argument segment (a private copy indexed by the layer would be scratch).  skip_shift, skip_part: a critic's rows of
+// partial sums lie behind the actor's, ((n + 2^skip_shift - 1) >> skip_shift) rows of skip_part floats.  `idle`: workgroup x has no rows
+// of that member (it has fewer workgroups than the widest member, or no samples) — workgroup-uniform, taken before the first barrier.
+struct PpoMlpSetNetArgs {
+  PpoMlpNetArgs net;
+  int32_t skip_shift, skip_part;
+  PpoSetTable table;
+};
+static_assert(sizeof(PpoMlpSetNetArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+struct PpoMlpMember {
+  const float *block, *bwd;
+  PpoRowArgs rows;
+  float *parts, *out;
+};
+template <bool SET> using PpoMlpKernelArgs = std::conditional_t<SET, PpoMlpSetNetArgs, PpoMlpNetArgs>;
+__host__ __device__ __forceinline__ const PpoMlpTable& ppo_mlp_table_of(const PpoMlpNetArgs& S) { return S.T; }
+__host__ __device__ __forceinline__ const PpoMlpTable& ppo_mlp_table_of(const PpoMlpSetNetArgs& S) { return S.net.T; }
+template <bool ACTOR, bool SET>
+__device__ __forceinline__ decltype(auto) ppo_mlp_member(const PpoMlpKernelArgs<SET>& S, bool& idle) {
+  if constexpr (SET) {
+    const int g = blockIdx.y;
+    const int64_t n = S.table.count[g], off = S.table.off[g];
+    idle = (int64_t)blockIdx.x * (S.net.T.waves * kPolWaveEnvs) >= n;
+    float* ws = S.net.parts + S.table.ws[g];
+    PpoMlpMember M;
+    M.block = S.net.block + (size_t)g * S.net.T.block_floats;
+    M.bwd = ws + (ACTOR ? 0 : kPpoMlpBwdFloats);
+    M.rows = S.net.rows;
+    M.rows.indices = S.net.rows.indices + off;
+    M.rows.n = n;
+    M.parts = ws + 2 * kPpoMlpBwdFloats + (ACTOR ? (int64_t)0 : ((n + ((int64_t)1 << S.skip_shift) - 1) >> S.skip_shift) * S.skip_part);
+    M.out = S.net.out ? S.net.out + off : nullptr;
+    return M;
+  } else {
+    idle = false;
+    return (S);                                            // the arguments themselves: the plain kernel is the code it was
+  }
+}
 // The workgroup has blockDim.x / 64 waves (T.waves), each 32 rows; trailing waves of the last workgroup have no rows and stay (barriers).
-template <int ACT, bool ACTOR>
-__global__ __launch_bounds__(kPolBlock) void ppo_mlp_net_kernel(const PpoMlpNetArgs A) {
+// SET = false: the kernel of rdv_ppo_mlp_loss_grad (profiles/ppo_mlp_set_isa_diff.md).  SET = true: workgroup (x, y) is workgroup x of
+// member y's stand-alone launch: the same body on the member's arguments.
+template <int ACT, bool ACTOR, bool SET>
+__global__ __launch_bounds__(kPolBlock) void ppo_mlp_net_kernel(const PpoMlpKernelArgs<SET> S) {
+  bool idle;
+  const auto& A = ppo_mlp_member<ACTOR, SET>(S, idle);
+  if (SET && idle) return;
   extern __shared__ __attribute__((aligned(16))) float lds[];
-  const PpoMlpTable& T = A.T;
+  const PpoMlpTable& T = ppo_mlp_table_of(S);
   const int32_t* H = reinterpret_cast<const int32_t*>(A.block);
   const int total = T.block_floats, L = T.L, nw = T.waves;
   float* w = lds;
@@ -268,7 +325,7 @@ struct PpoMlpFinishArgs {
   float ent_coef, vf_coef;
   float *actor_grad, *critic_grad, *scalars;
 };
-__global__ __launch_bounds__(256) void ppo_mlp_finish_kernel(const PpoMlpFinishArgs F) {
+__device__ __forceinline__ void ppo_mlp_finish_body(const PpoMlpFinishArgs& F) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   const float fn = (float)F.n;
   if (i < F.actor_floats) {
@@ -291,32 +348,62 @@ __global__ __launch_bounds__(256) void ppo_mlp_finish_kernel(const PpoMlpFinishA
   }
 }
 
-template <bool ACTOR>
+__global__ __launch_bounds__(256) void ppo_mlp_finish_kernel(const PpoMlpFinishArgs F) { ppo_mlp_finish_body(F); }
+// the set form: member blockIdx.y's rows of the workspace -> row blockIdx.y of the outputs; nothing of a member without samples is
+// written.  `F` holds the set-wide values (actor_parts: the workspace; actor_block: the actor set's allocation; the outputs' row 0;
+// critic_parts, the group counts and n unused).
+struct PpoMlpSetFinishArgs {
+  PpoMlpFinishArgs F;
+  int32_t actor_shift, critic_shift, block_floats;     // rows per workgroup of either net as a shift; the actor's block
+  PpoSetTable table;
+};
+static_assert(sizeof(PpoMlpSetFinishArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+__global__ __launch_bounds__(256) void ppo_mlp_set_finish_kernel(const PpoMlpSetFinishArgs S) {
+  const int g = blockIdx.y;
+  const int64_t n = S.table.count[g];
+  if (n == 0) return;
+  PpoMlpFinishArgs F = S.F;
+  F.n = n;
+  F.actor_groups = (n + ((int64_t)1 << S.actor_shift) - 1) >> S.actor_shift;
+  F.critic_groups = (n + ((int64_t)1 << S.critic_shift) - 1) >> S.critic_shift;
+  F.actor_parts = S.F.actor_parts + S.table.ws[g] + 2 * kPpoMlpBwdFloats;
+  F.critic_parts = F.actor_parts + F.actor_groups * F.actor_stride;
+  F.actor_block = S.F.actor_block + (size_t)g * S.block_floats;
+  F.actor_grad = S.F.actor_grad + (size_t)g * F.actor_floats;
+  F.critic_grad = S.F.critic_grad + (size_t)g * F.critic_floats;
+  F.scalars = S.F.scalars + (size_t)g * kPpoScalars;
+  ppo_mlp_finish_body(F);
+}
+
+template <bool ACTOR, bool SET>
 static const void* net_kernel_of(int activation) {
   switch (activation) {
-    case RDV_ACT_RELU: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_RELU, ACTOR>);
-    case RDV_ACT_SIGMOID: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_SIGMOID, ACTOR>);
-    default: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_TANH, ACTOR>);
+    case RDV_ACT_RELU: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_RELU, ACTOR, SET>);
+    case RDV_ACT_SIGMOID: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_SIGMOID, ACTOR, SET>);
+    default: return reinterpret_cast<const void*>(ppo_mlp_net_kernel<RDV_ACT_TANH, ACTOR, SET>);
   }
 }
 
 hipError_t ppo_mlp_raise_lds_limit() {
   for (int act = 0; act < 3; ++act) {
-    hipError_t err = hipFuncSetAttribute(net_kernel_of<true>(act), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMlpLdsLimit);
-    if (err == hipSuccess) err = hipFuncSetAttribute(net_kernel_of<false>(act), hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMlpLdsLimit);
-    if (err != hipSuccess) return err;
+    const void* kernels[] = {net_kernel_of<true, false>(act), net_kernel_of<false, false>(act), net_kernel_of<true, true>(act), net_kernel_of<false, true>(act)};
+    for (const void* k : kernels) {
+      hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kPpoMlpLdsLimit);
+      if (err != hipSuccess) return err;
+    }
   }
   return hipSuccess;
 }
 
-template <bool ACTOR>
-static void launch_net(int activation, const PpoMlpNetArgs& net, int64_t groups, hipStream_t s) {
-  const dim3 grid((unsigned)groups), block((unsigned)(net.T.waves * 64));
-  const int lds = ppo_mlp_lds_bytes(net.T);
+template <bool ACTOR, bool SET>
+static void launch_net(int activation, const PpoMlpKernelArgs<SET>& net, dim3 grid, hipStream_t s) {
+  const PpoMlpTable& T = ppo_mlp_table_of(net);
+  const dim3 block((unsigned)(T.waves * 64));
+  const int lds = ppo_mlp_lds_bytes(T);
   switch (activation) {
-    case RDV_ACT_RELU: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_RELU, ACTOR>), grid, block, lds, s, net); break;
-    case RDV_ACT_SIGMOID: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_SIGMOID, ACTOR>), grid, block, lds, s, net); break;
-    default: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_TANH, ACTOR>), grid, block, lds, s, net); break;
+    case RDV_ACT_RELU: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_RELU, ACTOR, SET>), grid, block, lds, s, net); break;
+    case RDV_ACT_SIGMOID: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_SIGMOID, ACTOR, SET>), grid, block, lds, s, net); break;
+    default: hipLaunchKernelGGL((ppo_mlp_net_kernel<RDV_ACT_TANH, ACTOR, SET>), grid, block, lds, s, net); break;
   }
 }
 
@@ -326,13 +413,33 @@ void ppo_mlp_launch(const PpoMlpLaunch& a, hipStream_t s) {
   float* parts_c = parts_a + groups_a * a.actor.part_floats;
   hipLaunchKernelGGL(ppo_mlp_transpose_kernel, dim3(kPpoMlpBwdFrags + 1, 2), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace);
   PpoMlpNetArgs net = {a.actor_block, a.workspace, ppo_row_args(a), parts_a, a.log_prob, a.actor};
-  launch_net<true>(a.actor_act, net, groups_a, s);
+  launch_net<true, false>(a.actor_act, net, dim3((unsigned)groups_a), s);
   net.block = a.critic_block; net.bwd = a.workspace + kPpoMlpBwdFloats; net.parts = parts_c; net.out = a.values; net.T = a.critic;
-  launch_net<false>(a.critic_act, net, groups_c, s);
+  launch_net<false, false>(a.critic_act, net, dim3((unsigned)groups_c), s);
   const PpoMlpFinishArgs F = {parts_a, parts_c, groups_a, groups_c, a.n, a.actor.part_floats, a.critic.part_floats, a.actor.grad_floats,
                               a.critic.grad_floats, a.actor_block, a.k.ent_coef, a.k.vf_coef, a.actor_grad, a.critic_grad, a.scalars};
   const int total = a.actor.grad_floats + a.critic.grad_floats + 1;
   hipLaunchKernelGGL(ppo_mlp_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, F);
+}
+
+// rows per workgroup (256 or 128) as a shift
+static int rows_shift(const PpoMlpTable& t) { return t.waves == 8 ? 8 : 7; }
+
+void ppo_mlp_set_launch(const PpoMlpSetLaunch& L, hipStream_t s) {
+  const PpoMlpLaunch& a = L.a;
+  const unsigned P = (unsigned)L.n_members;
+  hipLaunchKernelGGL(ppo_mlp_set_transpose_kernel, dim3(kPpoMlpBwdFrags + 1, 2, P), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace,
+                     a.actor.block_floats, a.critic.block_floats, L.table);
+  PpoMlpSetNetArgs S = {{a.actor_block, nullptr, ppo_row_args(a), a.workspace, a.log_prob, a.actor}, 0, 0, L.table};   // a.n is 0: the counts are the table's
+  launch_net<true, true>(a.actor_act, S, dim3((unsigned)L.max_groups_a, P), s);
+  S.net.block = a.critic_block; S.net.out = a.values; S.net.T = a.critic;
+  S.skip_shift = rows_shift(a.actor); S.skip_part = a.actor.part_floats;
+  launch_net<false, true>(a.critic_act, S, dim3((unsigned)L.max_groups_c, P), s);
+  const PpoMlpSetFinishArgs F = {{a.workspace, nullptr, 0, 0, 0, a.actor.part_floats, a.critic.part_floats, a.actor.grad_floats, a.critic.grad_floats,
+                                  a.actor_block, a.k.ent_coef, a.k.vf_coef, a.actor_grad, a.critic_grad, a.scalars},
+                                 rows_shift(a.actor), rows_shift(a.critic), a.actor.block_floats, L.table};
+  const int total = a.actor.grad_floats + a.critic.grad_floats + 1;
+  hipLaunchKernelGGL(ppo_mlp_set_finish_kernel, dim3((total + 255) / 256, P), dim3(256), 0, s, F);
 }
 
 }  // namespace rdv

@@ -614,8 +614,11 @@ class PolicySet(_Members, _HipHandles):
         the set owns, and ONE rdv_ppo_set_loss_grad runs on the current stream.  The gradients land in two buffers [P,5708] and
         [P,5377] the set owns; member g's ``.grad`` tensors are views of row g, so per-member ``clip_grad_norm_``, one optimiser over
         all members' parameters and ``update_weights()`` follow unchanged.  Every member's gradients and scalars are bit for bit those
-        of its own ``MlpPolicy.ppo_grad`` on the same buffer and indices.  CPU rows, ``backend="torch"`` or another architecture:
-        ``ppo.ppo_grad`` member by member (on CUDA rows each member of another architecture takes rdv_ppo_mlp_loss_grad).  Returns a list of P dicts of 0-dim tensors (the scalars of ``ppo_grad``)."""
+        of its own ``MlpPolicy.ppo_grad`` on the same buffer and indices.  A set of another architecture the forward kernels serve
+        (``ppo.hip_set_route`` answers "mlp": 1..4 hidden layers of 16 / 32 / 64, tanh, ReLU or sigmoid, at most 64 members) takes
+        the same path through ONE rdv_ppo_mlp_set_loss_grad, its buffers [P,Ga] and [P,Gc] of the architecture's gradient lengths,
+        with the same equality.  CPU rows, ``backend="torch"``, an unserved width or exactly one net of the shipped shape:
+        ``ppo.ppo_grad`` member by member.  Returns a list of P dicts of 0-dim tensors (the scalars of ``ppo_grad``)."""
         from . import ppo
         return ppo.ppo_set_grads(self, buf, indices, clip_range, ent_coef, vf_coef, normalize_advantage, check)
 
@@ -638,7 +641,11 @@ class PolicySet(_Members, _HipHandles):
         whose gradient norm is not finite is skipped whole and flagged.  ``update_weights(member=, weights=)`` writes through the views
         and keeps the moments: ``reset_optimizer`` zeroes them.
 
-        CPU rows, ``backend="torch"`` or another architecture: per-member ``clip_grad_norm_`` and one ``torch.optim.Adam`` the set owns
+        A set of another architecture the forward kernels serve, after a ``ppo_grads`` that ran rdv_ppo_mlp_set_loss_grad, takes ONE
+        rdv_ppo_mlp_set_adam_step under the same contract: master weights, moments and views of the architecture's lengths [P,Ga] /
+        [P,Gc], the forward blocks the bytes ``update_weights()`` would pack but for the six ``exp(log_std)`` floats.
+
+        CPU rows, ``backend="torch"``, an unserved width or exactly one net of the shipped shape: per-member ``clip_grad_norm_`` and one ``torch.optim.Adam`` the set owns
         over all members' parameters; the moments are then PyTorch's, a member with a non-finite norm is left out of that step, and
         ``update_weights()`` follows as before.
 

@@ -29,16 +29,19 @@ A sweep of P learners on one GPU (``PolicySet``, one grouped batch) takes the sa
             learners.update_weights()
 
 ``PolicySet.ppo_grads`` is ONE call of rdv_ppo_set_loss_grad (include/rdv.h "PPO minibatch gradients for policy sets"): the members'
-minibatches share four launches, and every member gets the bits of its own ``MlpPolicy.ppo_grad``.
+minibatches share four launches, and every member gets the bits of its own ``MlpPolicy.ppo_grad``.  A set of another architecture the
+forward kernels serve takes ONE rdv_ppo_mlp_set_loss_grad in the same way ("PPO minibatch gradients for policy sets of every MLP
+architecture"; ``hip_set_route``); and the same ``adam_step`` (rdv_ppo_mlp_set_adam_step).
 
-The three lines behind it can stay on the device too (the shipped architecture, CUDA rows):
+The three lines behind it can stay on the device too (CUDA rows, every architecture the forward kernels serve):
 
     for epoch in range(n_epochs):
         for pieces in ppo_set_minibatches(learners, T, batch_size, generator):
             stepped = learners.ppo_grads(buf, pieces, clip_range=0.2, ent_coef=0.0, vf_coef=0.5)
             learners.adam_step(stepped, lr=3e-4, max_grad_norm=0.5)                           # clip, Adam and the new forward blocks
 
-``PolicySet.adam_step`` is ONE call of rdv_ppo_set_adam_step (include/rdv.h "Gradient clip, Adam and weight repack for policy sets"): the
+``PolicySet.adam_step`` is ONE call of rdv_ppo_set_adam_step (include/rdv.h "Gradient clip, Adam and weight repack for policy sets";
+rdv_ppo_mlp_set_adam_step for a set of another architecture): the
 joint gradient norm of each member's actor and critic, Adam on fp32 master weights the set owns (the member modules' parameters are views
 of them), and the members' forward blocks repacked on the device: no ``update_weights``, no host copy, legal inside a stream capture.
 """
@@ -148,6 +151,20 @@ def hip_route(policy):
     if any(default) or not (served(policy.pi_arch) and served(policy.vf_arch)):
         return None
     return "mlp"
+
+
+def hip_set_route(pset):
+    """Which library call serves ``PolicySet.ppo_grads`` (and, behind it, ``adam_step``) of this set on CUDA rows: "shipped"
+    (rdv_ppo_set_loss_grad), "mlp" (rdv_ppo_mlp_set_loss_grad: one spec per set, both nets of another architecture the GPU forward
+    serves) or None (member by member): the rules of ``hip_route`` for the members' common architecture, plus ``backend != "torch"``
+    and at most 64 members.  A shipped set of more than 64 members still answers "shipped": ``ppo_grads`` of such a set is refused by
+    the library's own cap (ValueError), as it always was, and its ``adam_step`` is the PyTorch fallback."""
+    if pset.backend == "torch":
+        return None
+    route = hip_route(pset.policies[0])
+    if len(pset) > 64 and route == "mlp":
+        return None
+    return route
 
 
 def _state(policy, dev, n, rows):
@@ -289,24 +306,38 @@ def ppo_grad(policy, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.
     return {name: s[k] for k, name in enumerate(SCALAR_NAMES)}
 
 
-def _set_state(pset, dev, P, total, rows, counts):
-    """The buffers a PolicySet owns for ppo_grads on device ``dev``: the gradients [P,5708] and [P,5377] (row g: member g's flat buffers,
-    of which its parameters' ``.grad`` are views), the scalars [P,8], the concatenated indices, the advantage column and the workspace,
-    the last three grown when a call needs more."""
+def _set_grad_floats(pset, route):
+    """(Ga, Gc): the lengths of a member's flat actor and critic gradients."""
+    from . import _native as N
+    if route != "mlp":
+        return N.PPO_ACTOR_GRAD, N.PPO_CRITIC_GRAD
+    a, c = _specs(pset.policies[0])
+    return int(N.lib().rdv_ppo_mlp_grad_floats(C.byref(a), 1)), int(N.lib().rdv_ppo_mlp_grad_floats(C.byref(c), 0))
+
+
+def _set_state(pset, dev, P, total, rows, counts, route="shipped"):
+    """The buffers a PolicySet owns for ppo_grads on device ``dev``: the gradients [P,Ga] and [P,Gc] (5708 and 5377 for the shipped
+    architecture; row g: member g's flat buffers, of which its parameters' ``.grad`` are views), the scalars [P,8], the concatenated
+    indices, the advantage column and the workspace, the last three grown when a call needs more."""
     from . import _native as N
     st = pset.__dict__.setdefault("_ppo", {}).get(dev)
     if st is None:
-        st = dict(actor=torch.zeros((P, N.PPO_ACTOR_GRAD), dtype=torch.float32, device=dev),
-                  critic=torch.zeros((P, N.PPO_CRITIC_GRAD), dtype=torch.float32, device=dev),
+        Ga, Gc = _set_grad_floats(pset, route)
+        st = dict(actor=torch.zeros((P, Ga), dtype=torch.float32, device=dev),
+                  critic=torch.zeros((P, Gc), dtype=torch.float32, device=dev),
                   scalars=torch.zeros((P, N.PPO_SCALARS), dtype=torch.float32, device=dev), idx=None, adv=None, workspace=None)
         pset._ppo[dev] = st
     if st["idx"] is None or st["idx"].numel() < total:
         st["idx"] = torch.zeros(total, dtype=torch.int64, device=dev)
     if st["adv"] is None or st["adv"].numel() < rows:
         st["adv"] = torch.zeros(rows, dtype=torch.float32, device=dev)
-    need = int(N.lib().rdv_ppo_set_workspace_bytes(P, counts))
+    if route == "mlp":
+        a, c = _specs(pset.policies[0])
+        need = int(N.lib().rdv_ppo_mlp_set_workspace_bytes(C.byref(a), C.byref(c), P, counts))
+    else:
+        need = int(N.lib().rdv_ppo_set_workspace_bytes(P, counts))
     if need < 0:
-        raise ValueError(f"ppo_grads: a set of {P} members is not served by one call (rdv_ppo_set_workspace_bytes)")
+        raise ValueError(f"ppo_grads: a set of {P} members is not served by one call (rdv_ppo_{'mlp_' if route == 'mlp' else ''}set_workspace_bytes)")
     if st["workspace"] is None or st["workspace"].numel() < need:
         st["workspace"] = torch.empty(need, dtype=torch.uint8, device=dev)
     return st
@@ -346,8 +377,8 @@ def ppo_set_grads(pset, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
                 raise IndexError(f"ppo_grads: indices[{g}] reach env columns [{lo}, {hi}], member {g} owns {sl.start}..{sl.stop - 1}")
         indices[g] = idx.contiguous()
 
-    hip = pset.backend != "torch" and dev.type == "cuda" and pset.shipped_arch and pset.vf_arch == [64, 64]
-    if not hip:
+    route = hip_set_route(pset) if dev.type == "cuda" else None
+    if route is None:
         out = [None] * P
         for g in live:
             member = pset[g]
@@ -363,7 +394,7 @@ def ppo_set_grads(pset, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
     from . import _native as N
     counts = (C.c_int64 * P)(*[int(indices[g].numel()) if indices[g] is not None else 0 for g in range(P)])
     total = sum(counts)
-    st = _set_state(pset, dev, P, total, rows, counts)
+    st = _set_state(pset, dev, P, total, rows, counts, route)
     with torch.no_grad():
         torch.cat([indices[g] for g in live], out=st["idx"][:total])
         if normalize_advantage and max(counts) > 1:
@@ -379,8 +410,9 @@ def ppo_set_grads(pset, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
                   st["idx"].data_ptr(), rows)
     o = N.PpoSetOut(st["actor"].data_ptr(), st["critic"].data_ptr(), st["scalars"].data_ptr(), None, None)
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-    N.check(N.lib().rdv_ppo_set_loss_grad(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(r), counts, float(clip_range), float(ent_coef),
-                                          float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    call = N.lib().rdv_ppo_set_loss_grad if route == "shipped" else N.lib().rdv_ppo_mlp_set_loss_grad
+    N.check(call(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(r), counts, float(clip_range), float(ent_coef),
+                 float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
     pset._ppo_last = dev
     s = st["scalars"].clone()
     out = [None] * P
@@ -406,14 +438,14 @@ def _check_adam(lr, betas, eps, max_grad_norm):
 
 
 def _adam_device(pset):
-    """The device whose gradient buffers the last ``ppo_grads`` of this set filled through rdv_ppo_set_loss_grad, if the device step
-    serves the set: the shipped architecture, at most 64 members, ``backend != "torch"``; None: the PyTorch fallback."""
-    from . import _native as N
+    """The device whose gradient buffers the last ``ppo_grads`` of this set filled through rdv_ppo_set_loss_grad or
+    rdv_ppo_mlp_set_loss_grad, if the device step serves the set (``hip_set_route``, at most 64 members); None: the PyTorch fallback."""
     dev = getattr(pset, "_ppo_last", None)
-    if dev is None or pset.backend == "torch" or not (pset.shipped_arch and pset.vf_arch == [64, 64]) or len(pset) > 64:
+    route = hip_set_route(pset)
+    if dev is None or route is None or len(pset) > 64:
         return None
     st = pset.__dict__.get("_ppo", {}).get(dev)
-    return dev if st is not None and tuple(st["actor"].shape) == (len(pset), N.PPO_ACTOR_GRAD) else None
+    return dev if st is not None and tuple(st["actor"].shape) == (len(pset), _set_grad_floats(pset, route)[0]) else None
 
 
 def _adam_views(pset, ad):
@@ -436,16 +468,17 @@ def _adam_views(pset, ad):
 
 
 def _adam_state(pset, dev):
-    """The RdvAdamState buffers of a set on ``dev``, allocated on first use: master weights and moments [P,5708] / [P,5377], steps [P],
-    coef [P,8]."""
+    """The RdvAdamState buffers of a set on ``dev``, allocated on first use: master weights and moments [P,Ga] / [P,Gc] (the shapes of
+    the set's gradient buffers: 5708 / 5377 for the shipped architecture), steps [P], coef [P,8]."""
     from . import _native as N
     table = pset.__dict__.setdefault("_adam", {})
     ad = table.get(dev)
     if ad is None:
         P = len(pset)
+        Ga, Gc = int(pset._ppo[dev]["actor"].shape[1]), int(pset._ppo[dev]["critic"].shape[1])
         z = lambda n: torch.zeros((P, n), dtype=torch.float32, device=dev)
-        ad = dict(actor_param=z(N.PPO_ACTOR_GRAD), critic_param=z(N.PPO_CRITIC_GRAD), actor_m=z(N.PPO_ACTOR_GRAD), actor_v=z(N.PPO_ACTOR_GRAD),
-                  critic_m=z(N.PPO_CRITIC_GRAD), critic_v=z(N.PPO_CRITIC_GRAD), step=torch.zeros(P, dtype=torch.int64, device=dev),
+        ad = dict(actor_param=z(Ga), critic_param=z(Gc), actor_m=z(Ga), actor_v=z(Ga),
+                  critic_m=z(Gc), critic_v=z(Gc), step=torch.zeros(P, dtype=torch.int64, device=dev),
                   coef=z(N.ADAM_COEF), first=None)
         ad["c"] = N.AdamState(*[ad[name].data_ptr() for name, _ in N.AdamState._fields_])
         table[dev] = ad
@@ -480,9 +513,10 @@ def set_adam_step(pset, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max
         mask = 0
         for g in live:
             mask |= 1 << g
-        N.check(N.lib().rdv_ppo_set_adam_step(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(ad["c"]), C.c_void_p(grads["actor"].data_ptr()),
-                                              C.c_void_p(grads["critic"].data_ptr()), C.c_uint64(mask), lr, b1, b2, eps, max_grad_norm,
-                                              C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        call = N.lib().rdv_ppo_set_adam_step if hip_set_route(pset) == "shipped" else N.lib().rdv_ppo_mlp_set_adam_step
+        N.check(call(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(ad["c"]), C.c_void_p(grads["actor"].data_ptr()),
+                     C.c_void_p(grads["critic"].data_ptr()), C.c_uint64(mask), lr, b1, b2, eps, max_grad_norm,
+                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
         return _adam_result(ad["coef"])
 
     # ---- the fallback: per-member clip_grad_norm_ and ONE torch.optim.Adam over all members' parameters; the moments are PyTorch's
