@@ -710,15 +710,19 @@ int rdv_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* row
 }
 
 // ---- PPO minibatch gradients for every MLP architecture (csrc/rdv_ppo_mlp.h)
-int rdv_ppo_mlp_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec) {
-  if (!actor_spec || !critic_spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_mlp_spec_check: null %s", !actor_spec ? "actor_spec" : "critic_spec");
-  const struct { const RdvMlpSpec* s; const char* name; } nets[] = {{actor_spec, "actor"}, {critic_spec, "critic"}};
+// what the two spec checks of the general calls share: both specs non-null, then rdv_mlp_spec_check's refusal of either under its name
+static int check_spec_pair(const char* who, const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec, const char* actor, const char* critic) {
+  if (!actor_spec || !critic_spec) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null %s", who, !actor_spec ? "actor_spec" : "critic_spec");
+  const struct { const RdvMlpSpec* s; const char* name; } nets[] = {{actor_spec, actor}, {critic_spec, critic}};
   for (const auto& a : nets)
     if (int rc = rdv_mlp_spec_check(a.s)) {
       const std::string why = rdv_last_error();
-      return fail(rc, "rdv_ppo_mlp_spec_check: %s: %s", a.name, why.c_str());
+      return fail(rc, "%s: %s: %s", who, a.name, why.c_str());
     }
   return RDV_OK;
+}
+int rdv_ppo_mlp_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec) {
+  return check_spec_pair("rdv_ppo_mlp_spec_check", actor_spec, critic_spec, "actor", "critic");
 }
 
 // (a bad spec: the two size queries answer -1; rdv_last_error holds rdv_mlp_spec_check's reason)
@@ -745,6 +749,13 @@ int64_t rdv_ppo_mlp_workspace_bytes(const RdvMlpSpec* actor_spec, const RdvMlpSp
   return ppo_mlp_bytes(*actor_spec, *critic_spec, n);
 }
 
+// the blocks of two general handles have the sizes of their specs' tables (they were packed from those specs: anything else is a bug)
+static int check_block_floats(const char* who, rdv_policy actor, rdv_policy critic, const PpoMlpTable& ta, const PpoMlpTable& tc) {
+  if (ta.block_floats != actor->block_floats || tc.block_floats != critic->block_floats)
+    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor->block_floats, critic->block_floats, ta.block_floats, tc.block_floats);
+  return RDV_OK;
+}
+
 int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows* rows, int64_t n, double clip_range, double ent_coef, double vf_coef,
                           void* workspace, int64_t workspace_bytes, const RdvPpoOut* out, void* stream) {
   const char* who = "rdv_ppo_mlp_loss_grad";
@@ -765,8 +776,7 @@ int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows*
   PpoMlpTable ta, tc;
   ppo_mlp_table(actor->spec, true, ta);
   ppo_mlp_table(critic->spec, false, tc);
-  if (ta.block_floats != actor->block_floats || tc.block_floats != critic->block_floats)
-    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor->block_floats, critic->block_floats, ta.block_floats, tc.block_floats);
+  if (int rc = check_block_floats(who, actor, critic, ta, tc)) return rc;
   DeviceGuard guard(actor->device);
   if (int rc = raise_ppo_lds_limit(ppo_mlp_raise_lds_limit, g_ppo_mlp_lds_raised, actor->device)) return rc;
   PpoMlpLaunch a = {actor->weights, critic->weights, actor->spec.activation, critic->spec.activation, ta, tc,
@@ -778,14 +788,26 @@ int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows*
 }
 
 // ---- PPO minibatch gradients for policy sets (csrc/rdv_ppo.h, "the set form")
-int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_host) {
-  if (n_members < 1 || n_members > kPpoSetMaxMembers || !counts_host) return -1;
+// 1 .. kPpoSetMaxMembers counts, none negative, one positive
+static bool ppo_counts_ok(int32_t n_members, const int64_t* counts_host) {
+  if (n_members < 1 || n_members > kPpoSetMaxMembers || !counts_host) return false;
   bool any = false;
   for (int32_t g = 0; g < n_members; ++g) {
-    if (counts_host[g] < 0) return -1;
+    if (counts_host[g] < 0) return false;
     any = any || counts_host[g] > 0;
   }
-  return any ? ppo_set_table(n_members, counts_host, nullptr) : -1;
+  return any;
+}
+int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_host) {
+  return ppo_counts_ok(n_members, counts_host) ? ppo_set_table(n_members, counts_host, nullptr) : -1;
+}
+
+// The member count that the host-only checks of a set entry point judge counts_host or the mask by: one entry or bit per member of the
+// handles.  With an invalid actor handle (refused behind those checks) it is one member's; a set larger than the cap (refused behind them
+// too, before anything past the cap is looked at) counts as the cap's.
+static int32_t capped_members(rdv_policy actor_set) {
+  const bool valid = actor_set && actor_set->magic == kPolicyMagic;
+  return valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
 }
 
 // different member counts, more members than one call serves: every set entry point's last two refusals of the architecture
@@ -809,10 +831,7 @@ static int check_shipped_sets(const char* who, rdv_policy actor_set, rdv_policy 
 int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvPpoRows* rows, const int64_t* counts_host, double clip_range,
                           double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes, const RdvPpoSetOut* out, void* stream) {
   const char* who = "rdv_ppo_set_loss_grad";
-  // counts_host has one entry per member of the handles; with an invalid actor handle (refused below, behind the host-only checks) it is
-  // read as one member's.  A set larger than the cap is refused below, before anything past the cap is looked at.
-  const bool valid = actor_set && actor_set->magic == kPolicyMagic;
-  const int32_t P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
+  const int32_t P = capped_members(actor_set);
   if (int rc = check_ppo_call(who, rows, out, workspace, true, 0, P, counts_host)) return rc;
   PpoSetLaunch L = {};
   const int64_t need = ppo_set_table(P, counts_host, &L.table, nullptr, &L.max_workgroups);
@@ -834,28 +853,12 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
 
 // ---- PPO minibatch gradients for policy sets of every MLP architecture (csrc/rdv_ppo_mlp.h, "the set form")
 int rdv_ppo_mlp_set_spec_check(const RdvMlpSpec* actor_spec, const RdvMlpSpec* critic_spec) {
-  if (!actor_spec || !critic_spec) return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_mlp_set_spec_check: null %s", !actor_spec ? "actor_spec" : "critic_spec");
-  const struct { const RdvMlpSpec* s; const char* name; } nets[] = {{actor_spec, "actor_set"}, {critic_spec, "critic_set"}};
-  for (const auto& a : nets)
-    if (int rc = rdv_mlp_spec_check(a.s)) {
-      const std::string why = rdv_last_error();
-      return fail(rc, "rdv_ppo_mlp_set_spec_check: %s: %s", a.name, why.c_str());
-    }
+  if (int rc = check_spec_pair("rdv_ppo_mlp_set_spec_check", actor_spec, critic_spec, "actor_set", "critic_set")) return rc;
   // (is_shipped: the predicate that gives a handle its shipped block and kernels, i.e. what check_mlp_sets reads off the handles)
   if (is_shipped(actor_spec) != is_shipped(critic_spec))
     return fail(RDV_ERR_INVALID_ARGUMENT, "rdv_ppo_mlp_set_loss_grad, rdv_ppo_mlp_set_adam_step: %s has the default spec (the shipped block and kernels), %s another: the mixed pair is not built",
                 is_shipped(actor_spec) ? "actor_set" : "critic_set", is_shipped(actor_spec) ? "critic_set" : "actor_set");
   return RDV_OK;
-}
-
-static bool ppo_counts_ok(int32_t n_members, const int64_t* counts_host) {
-  if (n_members < 1 || n_members > kPpoSetMaxMembers || !counts_host) return false;
-  bool any = false;
-  for (int32_t g = 0; g < n_members; ++g) {
-    if (counts_host[g] < 0) return false;
-    any = any || counts_host[g] > 0;
-  }
-  return any;
 }
 
 // the general layout's table and bytes for a pair of general specs
@@ -894,9 +897,7 @@ int rdv_ppo_mlp_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const
   // two sets of the default spec: the call IS rdv_ppo_set_loss_grad, its bits and its refusals
   if (shipped_pair(actor_set, critic_set))
     return rdv_ppo_set_loss_grad(actor_set, critic_set, rows, counts_host, clip_range, ent_coef, vf_coef, workspace, workspace_bytes, out, stream);
-  // (counts_host: one entry per member of the handles, read as rdv_ppo_set_loss_grad reads it)
-  const bool valid = actor_set && actor_set->magic == kPolicyMagic;
-  const int32_t P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
+  const int32_t P = capped_members(actor_set);
   if (int rc = check_ppo_call(who, rows, out, workspace, true, 0, P, counts_host)) return rc;
   if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
   auto sets = [&]() -> int { return check_mlp_sets(who, actor_set, critic_set); };
@@ -907,8 +908,7 @@ int rdv_ppo_mlp_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const
   if (workspace_bytes < need)
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, these counts and specs need %lld (rdv_ppo_mlp_set_workspace_bytes)", who, (long long)workspace_bytes, (long long)need);
   const PpoMlpTable ta = L.a.actor, tc = L.a.critic;
-  if (ta.block_floats != actor_set->block_floats || tc.block_floats != critic_set->block_floats)
-    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor_set->block_floats, critic_set->block_floats, ta.block_floats, tc.block_floats);
+  if (int rc = check_block_floats(who, actor_set, critic_set, ta, tc)) return rc;
   DeviceGuard guard(actor_set->device);
   if (int rc = raise_ppo_lds_limit(ppo_mlp_raise_lds_limit, g_ppo_mlp_lds_raised, actor_set->device)) return rc;
   L.a = {actor_set->weights, critic_set->weights, actor_set->spec.activation, critic_set->spec.activation, ta, tc,
@@ -923,8 +923,7 @@ int rdv_ppo_mlp_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const
 // ---- gradient clip, Adam and weight repack for policy sets (csrc/rdv_ppo_adam.h)
 extern "C++" {
 // The host-only checks of the two optimiser entry points, in this order: state and every pointer non-null, 16-byte aligned; the five
-// scalars; the mask (one bit per member of the handles; with an invalid actor handle, refused behind these checks, it is judged as one
-// member's, and a set larger than the cap as the cap's).  P: that member count.
+// scalars; the mask, against P = capped_members(actor_set).
 static int check_adam_call(const char* who, rdv_policy actor_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
                            uint64_t active_mask, double lr, double beta1, double beta2, double eps, double max_grad_norm, int32_t& P) {
   if (!state) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: state is null", who);
@@ -940,16 +939,24 @@ static int check_adam_call(const char* who, rdv_policy actor_set, const RdvAdamS
   if (!(beta2 >= 0.0 && beta2 < 1.0)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: beta2 must be in [0, 1) (got %g)", who, beta2);
   if (!(max_grad_norm > 0.0)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: max_grad_norm must be positive, +inf for no clipping (got %g)", who, max_grad_norm);
   if (!active_mask) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: active_mask is empty: no member takes the step", who);
-  // the mask has one bit per member of the handles; with an invalid actor handle (refused below, behind the host-only checks) it is
-  // judged as one member's, and a set larger than the cap (refused below) as the cap's
-  const bool valid = actor_set && actor_set->magic == kPolicyMagic;
-  P = valid ? (actor_set->n_members < kPpoSetMaxMembers ? actor_set->n_members : kPpoSetMaxMembers) : 1;
+  P = capped_members(actor_set);
   if (P < 64 && (active_mask >> P)) {
     int bit = 63;
     while (!((active_mask >> bit) & 1)) --bit;
     return fail(RDV_ERR_INVALID_ARGUMENT, "%s: active_mask has bit %d set, the set has %d member%s", who, bit, P, P == 1 ? "" : "s");
   }
   return RDV_OK;
+}
+// the launch of either entry point: the handles' blocks, the caller's arrays with rows of ga / gc floats, the mask and the scalars
+static PpoAdamLaunch adam_launch_args(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
+                                      uint64_t active_mask, int32_t P, int32_t ga, int32_t gc, double lr, double beta1, double beta2, double eps, double max_grad_norm) {
+  PpoAdamLaunch a = {};
+  a.actor_block = actor_set->weights; a.critic_block = critic_set->weights;
+  a.actor_param = state->actor_param; a.critic_param = state->critic_param;
+  a.actor_m = state->actor_m; a.actor_v = state->actor_v; a.critic_m = state->critic_m; a.critic_v = state->critic_v;
+  a.step = state->step; a.coef = state->coef; a.actor_grad = actor_grad; a.critic_grad = critic_grad;
+  a.mask = active_mask; a.n_members = P; a.ga = ga; a.gc = gc;
+  return ppo_adam_scalars(a, lr, beta1, beta2, eps, max_grad_norm);
 }
 }  // extern "C++"
 
@@ -965,13 +972,8 @@ int rdv_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const Rdv
   if (actor_set->block_floats != kPolFloats || critic_set->block_floats != kPolFloats)
     return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, the shipped block %d", who, actor_set->block_floats, critic_set->block_floats, kPolFloats);
   DeviceGuard guard(actor_set->device);
-  PpoAdamLaunch a = {};
-  a.actor_block = actor_set->weights; a.critic_block = critic_set->weights;
-  a.actor_param = state->actor_param; a.critic_param = state->critic_param;
-  a.actor_m = state->actor_m; a.actor_v = state->actor_v; a.critic_m = state->critic_m; a.critic_v = state->critic_v;
-  a.step = state->step; a.coef = state->coef; a.actor_grad = actor_grad; a.critic_grad = critic_grad;
-  a.mask = active_mask; a.n_members = P;
-  ppo_adam_launch(ppo_adam_scalars(a, lr, beta1, beta2, eps, max_grad_norm), static_cast<hipStream_t>(stream));
+  ppo_adam_launch(adam_launch_args(actor_set, critic_set, state, actor_grad, critic_grad, active_mask, P, kPpoActorGrad, kPpoCriticGrad, lr, beta1, beta2, eps, max_grad_norm),
+                  static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }
@@ -992,17 +994,9 @@ int rdv_ppo_mlp_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const
   PpoMlpAdamLaunch A = {};
   ppo_mlp_table(actor_set->spec, true, A.T[0]);
   ppo_mlp_table(critic_set->spec, false, A.T[1]);
-  if (A.T[0].block_floats != actor_set->block_floats || A.T[1].block_floats != critic_set->block_floats)
-    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor_set->block_floats, critic_set->block_floats,
-                A.T[0].block_floats, A.T[1].block_floats);
+  if (int rc = check_block_floats(who, actor_set, critic_set, A.T[0], A.T[1])) return rc;
   DeviceGuard guard(actor_set->device);
-  PpoAdamLaunch& a = A.a;
-  a.actor_block = actor_set->weights; a.critic_block = critic_set->weights;
-  a.actor_param = state->actor_param; a.critic_param = state->critic_param;
-  a.actor_m = state->actor_m; a.actor_v = state->actor_v; a.critic_m = state->critic_m; a.critic_v = state->critic_v;
-  a.step = state->step; a.coef = state->coef; a.actor_grad = actor_grad; a.critic_grad = critic_grad;
-  a.mask = active_mask; a.n_members = P;
-  a = ppo_adam_scalars(a, lr, beta1, beta2, eps, max_grad_norm);
+  A.a = adam_launch_args(actor_set, critic_set, state, actor_grad, critic_grad, active_mask, P, A.T[0].grad_floats, A.T[1].grad_floats, lr, beta1, beta2, eps, max_grad_norm);
   ppo_mlp_adam_launch(A, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;

@@ -63,8 +63,8 @@ constexpr int kMlpMaxLdsBytes = (kMlpMaxFloats + kMlpStageFloats) * 4;   // 90,7
 static_assert(kMlpMaxLdsBytes <= 160 * 1024, "the largest network's workgroup must fit the CU's 160 KiB of LDS");
 inline int mlp_lds_bytes(int block_floats) { return (block_floats + kMlpStageFloats) * 4; }
 
-inline int mlp_tiles(int width) { return width == 64 ? 2 : 1; }
-inline int mlp_ksteps(int width) { return width / 16; }            // 16 -> 1, 32 -> 2, 64 -> 4
+constexpr int mlp_tiles(int width) { return width == 64 ? 2 : 1; }
+constexpr int mlp_ksteps(int width) { return width / 16; }           // 16 -> 1, 32 -> 2, 64 -> 4
 
 // Host: the parameter block of a network of `spec` (checked by the caller) with out_dim <= 6 output rows; weights[l] / biases[l] in
 // SB3's layout, hidden layers first, the head last.  Scaling, splitting and fragment order are pack_policy_weights'.

@@ -1,5 +1,6 @@
 // rdv_ppo_adam.hip — the kernels of rdv_ppo_adam.h and their launch, in a translation unit of its own (the objects of the other units do
-// not change when it does).  The exported rdv_ppo_set_adam_step is in rdv_policy_host.hip, with the other policy entry points.
+// not change when it does).  The exported rdv_ppo_set_adam_step and rdv_ppo_mlp_set_adam_step are in rdv_policy_host.hip, with the other
+// policy entry points.
 //
 // The elementwise contract of include/rdv.h is float32 with every operation rounded on its own: nothing in this unit may be contracted
 // into an fma.  `/` and sqrtf are hipcc's correctly rounded ones (its default; the v_fma of their expansions are theirs).
@@ -9,24 +10,59 @@
 #include "rdv_policy_mlp.h"
 #include "rdv_ppo_adam.h"
 
+#include <type_traits>
+
 namespace rdv {
 
-constexpr int kAdamAll = kPpoActorGrad + kPpoCriticGrad;          // 11,085 entries under one norm
-constexpr int kAdamLogStd = kPpoW3 + kPolOut * kPolHid + kPolOut;   // 5702: log_std inside the actor's flat vector
-static_assert(kAdamLogStd + kPolOut == kPpoActorGrad && kPpoW3 + kPolHid + 1 == kPpoCriticGrad, "the flat layouts of RdvPpoOut");
-static_assert(kPolF32 == 32 * 64 * 4 && kPolFloats - kPolF32 == 180 && kPolB1 == kPolF32 && kPolB3 == kPolF32 + 128 && kPolStd == kPolF32 + 160 &&
-              kPolLogStd == kPolF32 + 168 && kPolScale == kPolF32 + 176, "the fp32 section as ppo_adam_tail lays it out");
+// ---- the shipped block as a case of the layer table: the default spec's table, and where the two blocks keep what the update writes
+constexpr RdvMlpSpec kAdamShippedSpec = {2, {kPolHid, kPolHid, 0, 0}, RDV_ACT_TANH, 0};
+constexpr PpoMlpTable adam_shipped_table(bool actor) {
+  PpoMlpTable t{};
+  ppo_mlp_table(kAdamShippedSpec, actor, t);
+  return t;
+}
+constexpr int adam_frags(const PpoMlpTable& t, int layers) {      // the fragments / the bias tiles of layers 0 .. layers - 1
+  int n = 0;
+  for (int l = 0; l < layers; ++l) n += 2 * t.mt[l] * t.ks[l];
+  return n;
+}
+constexpr int adam_tiles(const PpoMlpTable& t, int layers) {
+  int n = 0;
+  for (int l = 0; l < layers; ++l) n += t.mt[l];
+  return n;
+}
+// float indices inside a block: the fp16 section (the biases follow it), exp(log_std), log_std, layer l's inverse scale at scale + stride l
+struct AdamBlockAt { int frags, std, log_std, scale, scale_stride; };
+constexpr AdamBlockAt kAdamShippedAt = {0, kPolStd, kPolLogStd, kPolScale, 1};
+constexpr AdamBlockAt kAdamMlpAt = {kMlpHdr, kMlpStd, kMlpStd + 8, kMlpRec + 4, kMlpRecStride};
+
+constexpr bool adam_shipped_layout(bool actor) {
+  const PpoMlpTable t = adam_shipped_table(actor);
+  const int out_dim = actor ? kPolOut : 1;
+  return t.L == 2 && t.w_off[0] == kPpoW1 && t.b_off[0] == kPpoB1 && t.w_off[1] == kPpoW2 && t.b_off[1] == kPpoB2 && t.w_off[2] == kPpoW3 &&
+         t.b_off[2] == kPpoW3 + out_dim * kPolHid && t.grad_floats == (actor ? kPpoActorGrad : kPpoCriticGrad) &&
+         t.ls_off == (actor ? kPpoActorGrad - kPolOut : -1) &&
+         // the fragments [term][mt][ks] per layer from kPolW1Frag, kPolW2Frag, kPolW3Frag, the fp32 section right behind them
+         adam_frags(t, 0) == kPolW1Frag && adam_frags(t, 1) == kPolW2Frag && adam_frags(t, 2) == kPolW3Frag && adam_frags(t, 3) == kPolFrags &&
+         kPolF32 == kPolFrags * (kPolFragBytes / 4) &&
+         // the biases [mt][h][16] per layer at kPolB1, kPolB2, kPolB3, then exp(log_std) [8], log_std [8], the scales [4]
+         kPolB1 == kPolF32 && kPolB2 == kPolF32 + 32 * adam_tiles(t, 1) && kPolB3 == kPolF32 + 32 * adam_tiles(t, 2) &&
+         kPolStd == kPolF32 + 32 * adam_tiles(t, 3) && kPolLogStd == kPolStd + 8 && kPolScale == kPolLogStd + 8 && kPolFloats == kPolScale + 4;
+}
+static_assert(adam_shipped_layout(true) && adam_shipped_layout(false), "the shipped block and RdvPpoOut's flat layouts are the default spec's row of the layer table");
+static_assert(kPpoMlpAdamMaxFloats * 4 + 25 * 4 <= 64 * 1024 && kPpoActorGrad <= kPpoMlpAdamMaxFloats, "the largest net's parameters fit the static LDS");
 
 // ---- 1. one norm, one clip coefficient and the two step coefficients per member
 __global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_norm_kernel(const PpoAdamLaunch a) {
   const int g = blockIdx.x, t = threadIdx.x;
   if (!((a.mask >> g) & 1)) return;                                // (workgroup-uniform) an inactive member: nothing read, nothing written
   __shared__ double part[kPpoAdamThreads];
-  const float* ga = a.actor_grad + (size_t)g * kPpoActorGrad;
-  const float* gc = a.critic_grad + (size_t)g * kPpoCriticGrad;
+  const int na = a.ga, nc = a.gc;
+  const float* ga = a.actor_grad + (size_t)g * na;
+  const float* gc = a.critic_grad + (size_t)g * nc;
   double s = 0.0;
-  for (int i = t; i < kAdamAll; i += kPpoAdamThreads) {
-    const double x = (double)(i < kPpoActorGrad ? ga[i] : gc[i - kPpoActorGrad]);
+  for (int i = t; i < na + nc; i += kPpoAdamThreads) {
+    const double x = (double)(i < na ? ga[i] : gc[i - na]);
     s += x * x;                                                    // (the product of two floats is exact in double)
   }
   part[t] = s;
@@ -58,170 +94,30 @@ __device__ __forceinline__ int adam_shift(float mx) {
   return sft;
 }
 
-// float f (0 .. 179) of the block's fp32 section, from the net's new parameters `w` (LDS, the flat layout)
-__device__ __forceinline__ float ppo_adam_tail(const float* w, int f, bool actor, int out_dim, int sh1, int sh2, int sh3) {
-  if (f < 160) {                                                   // the biases in accumulator order, times the accumulator's scale
-    const int layer = f >> 6, i = f & 63, mt = i >> 5, h = (i >> 4) & 1, e = i & 15;
-    const int row = (e & 3) + 8 * (e >> 2) + 4 * h;
-    if (layer == 2) return (mt == 0 && row < out_dim) ? w[kPpoW3 + out_dim * kPolHid + row] * ldexpf(1.0f, kPolXShift + sh3) : 0.0f;
-    return w[(layer ? kPpoB2 : kPpoB1) + 32 * mt + row] * ldexpf(1.0f, kPolXShift + (layer ? sh2 : sh1));
-  }
-  if (f < 176) {                                                   // exp(log_std) [8], log_std [8]; a critic's are zero
-    const int j = (f - 160) & 7;
-    if (!actor || j >= kPolOut) return 0.0f;
-    const float ls = w[kAdamLogStd + j];
-    return f < 168 ? (float)exp((double)ls) : ls;
-  }
-  const int l = f - 176;                                           // the inverse scales (powers of two: exact), one zero
-  return l == 3 ? 0.0f : ldexpf(1.0f, -(kPolXShift + (l == 0 ? sh1 : l == 1 ? sh2 : sh3)));
-}
+// ---- 2. the step and the repack of one member's net.  SHIPPED: the arguments are the PpoAdamLaunch alone and the layers those of the
+// default spec — ppo_mlp_table is constexpr and the spec a constant, so every entry is a literal or a select on the net, the layer loops
+// unroll and the fragment arithmetic folds to shifts; otherwise the two tables travel in the arguments.
+template <bool SHIPPED> using PpoAdamArgs = std::conditional_t<SHIPPED, PpoAdamLaunch, PpoMlpAdamLaunch>;
+__host__ __device__ __forceinline__ const PpoAdamLaunch& ppo_adam_launch_of(const PpoAdamLaunch& A) { return A; }
+__host__ __device__ __forceinline__ const PpoAdamLaunch& ppo_adam_launch_of(const PpoMlpAdamLaunch& A) { return A.a; }
+__device__ __forceinline__ PpoMlpTable ppo_adam_table_of(const PpoAdamLaunch&, int net) { return adam_shipped_table(net == 0); }
+__device__ __forceinline__ const PpoMlpTable& ppo_adam_table_of(const PpoMlpAdamLaunch& A, int net) { return A.T[net]; }
 
-// ---- 2. the step and the repack of one member's net
-__global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_update_kernel(const PpoAdamLaunch a) {
+template <bool SHIPPED>
+__global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_update_kernel(const PpoAdamArgs<SHIPPED> A) {
+  const PpoAdamLaunch& a = ppo_adam_launch_of(A);
   const int net = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
   if (!((a.mask >> g) & 1)) return;                                // (both tests are workgroup-uniform and ahead of every barrier)
   const float4 c = *reinterpret_cast<const float4*>(a.coef + (size_t)g * kPpoAdamCoef);
   if (a.coef[(size_t)g * kPpoAdamCoef + 4] != 0.0f) return;        // a non-finite norm: the member is skipped whole
   const float clip = c.y, step_size = c.z, isb2 = c.w;
 
-  __shared__ __attribute__((aligned(16))) float w[kPpoActorGrad];
-  __shared__ float red[(kPpoAdamThreads / 64) * 3];
-  const bool actor = net == 0;
-  const int count = actor ? kPpoActorGrad : kPpoCriticGrad, out_dim = actor ? kPolOut : 1;
-  const size_t row = (size_t)g * (size_t)count;
-  const float* gr = (actor ? a.actor_grad : a.critic_grad) + row;
-  float* p = (actor ? a.actor_param : a.critic_param) + row;
-  float* m = (actor ? a.actor_m : a.critic_m) + row;
-  float* v = (actor ? a.actor_v : a.critic_v) + row;
-
-  for (int i = t; i < count; i += kPpoAdamThreads) {
-    const float gp = gr[i] * clip;
-    const float mo = m[i];
-    const float mn = mo + (gp - mo) * a.omb1;
-    const float vn = v[i] * a.b2 + (a.omb2 * gp) * gp;
-    const float pn = p[i] - step_size * (mn / (sqrtf(vn) * isb2 + a.eps));
-    m[i] = mn; v[i] = vn; p[i] = pn;
-    w[i] = pn;
-  }
-  __syncthreads();
-
-  // max |w| per layer: the thread's, the wave's, the workgroup's (a maximum does not depend on the order)
-  float mx[3] = {0.0f, 0.0f, 0.0f};
-  for (int i = t; i < kPolHid * kPolIn; i += kPpoAdamThreads) mx[0] = fmaxf(mx[0], fabsf(w[kPpoW1 + i]));
-  for (int i = t; i < kPolHid * kPolHid; i += kPpoAdamThreads) mx[1] = fmaxf(mx[1], fabsf(w[kPpoW2 + i]));
-  for (int i = t; i < out_dim * kPolHid; i += kPpoAdamThreads) mx[2] = fmaxf(mx[2], fabsf(w[kPpoW3 + i]));
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) mx[k] = fmaxf(mx[k], __shfl_xor(mx[k], o));
-    if ((t & 63) == 0) red[(t >> 6) * 3 + k] = mx[k];
-  }
-  __syncthreads();
-  int sh[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    float all = red[k];
-#pragma unroll
-    for (int wv = 1; wv < kPpoAdamThreads / 64; ++wv) all = fmaxf(all, red[wv * 3 + k]);
-    sh[k] = adam_shift(all);
-  }
-
-  // the fp16 section: 32 fragments x 64 lanes x 16 bytes, one 16-byte store per (fragment, lane)
-  float* block = (actor ? a.actor_block : a.critic_block) + (size_t)g * kPolFloats;
-  for (int q = t; q < kPolFrags * 64; q += kPpoAdamThreads) {
-    const int frag = q >> 6, lane = q & 63, r = lane & 31, h = lane >> 5;
-    int term, sft;
-    float x[8];
-    if (frag < kPolW2Frag) {                                       // layer 1: fragment (term*2 + mt)*2 + s, natural k order, k >= 17 zero
-      term = frag >> 2; sft = sh[0];
-      const int mt = (frag >> 1) & 1, s = frag & 1;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 16 * s + 8 * h + j;
-        x[j] = k < kPolIn ? w[kPpoW1 + (32 * mt + r) * kPolIn + k] : 0.0f;
-      }
-    } else {                                                       // layer 2: 8 + (term*2 + mt)*4 + ks; head: 24 + term*4 + ks, rows >= out_dim zero
-      const bool head = frag >= kPolW3Frag;
-      const int f = frag - (head ? kPolW3Frag : kPolW2Frag), ks = f & 3;
-      term = head ? f >> 2 : f >> 3; sft = head ? sh[2] : sh[1];
-      const int base = head ? kPpoW3 + r * kPolHid : kPpoW2 + (32 * ((f >> 2) & 1) + r) * kPolHid;
-      const bool live = !head || r < out_dim;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        const int k = 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-        x[j] = live ? w[base + k] : 0.0f;
-      }
-    }
-    f16x8 out;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      const float ws = ldexpf(x[j], sft);
-      const _Float16 hi = (_Float16)ws;                            // round to nearest even, subnormals kept
-      out[j] = term == 0 ? hi : (_Float16)(ws - (float)hi);        // (the difference is exact in fp32)
-    }
-    *reinterpret_cast<f16x8*>(block + 4 * q) = out;
-  }
-  // the fp32 section: 180 floats, four per thread
-  if (t < (kPolFloats - kPolF32) / 4) {
-    float4 o;
-    o.x = ppo_adam_tail(w, 4 * t + 0, actor, out_dim, sh[0], sh[1], sh[2]);
-    o.y = ppo_adam_tail(w, 4 * t + 1, actor, out_dim, sh[0], sh[1], sh[2]);
-    o.z = ppo_adam_tail(w, 4 * t + 2, actor, out_dim, sh[0], sh[1], sh[2]);
-    o.w = ppo_adam_tail(w, 4 * t + 3, actor, out_dim, sh[0], sh[1], sh[2]);
-    *reinterpret_cast<float4*>(block + kPolF32 + 4 * t) = o;
-  }
-}
-
-// ---- every MLP architecture: the same two kernels on the layers of a table
-static_assert(kPpoMlpAdamMaxFloats * 4 + 25 * 4 <= 64 * 1024, "the largest net's parameters fit the static LDS");
-
-__global__ __launch_bounds__(kPpoAdamThreads) void ppo_mlp_adam_norm_kernel(const PpoMlpAdamLaunch A) {
-  const PpoAdamLaunch& a = A.a;
-  const int g = blockIdx.x, t = threadIdx.x;
-  if (!((a.mask >> g) & 1)) return;                                // (workgroup-uniform) an inactive member: nothing read, nothing written
-  __shared__ double part[kPpoAdamThreads];
-  const int na = A.T[0].grad_floats, nc = A.T[1].grad_floats;
-  const float* ga = a.actor_grad + (size_t)g * na;
-  const float* gc = a.critic_grad + (size_t)g * nc;
-  double s = 0.0;
-  for (int i = t; i < na + nc; i += kPpoAdamThreads) {
-    const double x = (double)(i < na ? ga[i] : gc[i - na]);
-    s += x * x;
-  }
-  part[t] = s;
-  for (int w = kPpoAdamThreads / 2; w > 0; w >>= 1) {              // the fixed tree of ppo_adam_norm_kernel
-    __syncthreads();
-    if (t < w) part[t] += part[t + w];
-  }
-  if (t != 0) return;
-  const float total = (float)sqrt(part[0]);
-  float4* c = reinterpret_cast<float4*>(a.coef + (size_t)g * kPpoAdamCoef);
-  if (!(fabsf(total) <= 3.402823466e+38f)) {                       // inf or NaN: the member is skipped whole
-    c[0] = make_float4(total, 0.0f, 0.0f, 0.0f);
-    c[1] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-    return;
-  }
-  const float clip = (float)fmin(1.0, (double)a.max_grad_norm / ((double)total + (double)1e-6f));
-  const int64_t tt = a.step[g] + 1;
-  const double bc1 = 1.0 - pow(a.beta1, (double)tt), bc2 = 1.0 - pow(a.beta2, (double)tt);
-  c[0] = make_float4(total, clip, (float)(a.lr / bc1), (float)(1.0 / sqrt(bc2)));
-  c[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  a.step[g] = tt;
-}
-
-__global__ __launch_bounds__(kPpoAdamThreads) void ppo_mlp_adam_update_kernel(const PpoMlpAdamLaunch A) {
-  const PpoAdamLaunch& a = A.a;
-  const int net = blockIdx.x, g = blockIdx.y, t = threadIdx.x;
-  if (!((a.mask >> g) & 1)) return;                                // (both tests are workgroup-uniform and ahead of every barrier)
-  const float4 c = *reinterpret_cast<const float4*>(a.coef + (size_t)g * kPpoAdamCoef);
-  if (a.coef[(size_t)g * kPpoAdamCoef + 4] != 0.0f) return;        // a non-finite norm: the member is skipped whole
-  const float clip = c.y, step_size = c.z, isb2 = c.w;
-
-  __shared__ __attribute__((aligned(16))) float w[kPpoMlpAdamMaxFloats];
+  __shared__ __attribute__((aligned(16))) float w[SHIPPED ? kPpoActorGrad : kPpoMlpAdamMaxFloats];
   __shared__ float red[(kPpoAdamThreads / 64) * kMlpLayers];
   __shared__ int shs[kMlpLayers];
+  constexpr AdamBlockAt at = SHIPPED ? kAdamShippedAt : kAdamMlpAt;
   const bool actor = net == 0;
-  const PpoMlpTable& T = A.T[net];
+  const auto& T = ppo_adam_table_of(A, net);
   const int count = T.grad_floats, L = T.L;
   const size_t row = (size_t)g * (size_t)count;
   const float* gr = (actor ? a.actor_grad : a.critic_grad) + row;
@@ -242,9 +138,9 @@ __global__ __launch_bounds__(kPpoAdamThreads) void ppo_mlp_adam_update_kernel(co
 
   // max |w| per layer: the thread's, the wave's, the workgroup's (a maximum does not depend on the order)
   for (int l = 0; l <= L; ++l) {
-    const int n = T.out_w[l] * T.in_w[l], at = T.w_off[l];
+    const int n = T.out_w[l] * T.in_w[l], at_w = T.w_off[l];
     float mx = 0.0f;
-    for (int i = t; i < n; i += kPpoAdamThreads) mx = fmaxf(mx, fabsf(w[at + i]));
+    for (int i = t; i < n; i += kPpoAdamThreads) mx = fmaxf(mx, fabsf(w[at_w + i]));
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o));
     if ((t & 63) == 0) red[(t >> 6) * kMlpLayers + l] = mx;
@@ -258,64 +154,53 @@ __global__ __launch_bounds__(kPpoAdamThreads) void ppo_mlp_adam_update_kernel(co
   }
   __syncthreads();
 
-  float* block = (actor ? a.actor_block : a.critic_block) + (size_t)g * T.block_floats;
-  int frags = 0, tiles = 0;
-  for (int l = 0; l <= L; ++l) { frags += 2 * T.mt[l] * T.ks[l]; tiles += T.mt[l]; }
-
-  // the fp16 section: one 16-byte store per (fragment, lane); fragment frag0_l + (term MT + mt) KS + ks of layer l
-  for (int q = t; q < frags * 64; q += kPpoAdamThreads) {
-    const int frag = q >> 6, lane = q & 63, r = lane & 31, h = lane >> 5;
-    int l = 0, f0 = 0;
-    for (int k = 0, at = 0; k <= L; ++k) {
-      const int n = 2 * T.mt[k] * T.ks[k];
-      if (frag >= at && frag < at + n) { l = k; f0 = at; }
-      at += n;
-    }
-    const int MT = T.mt[l], KS = T.ks[l], in_w = T.in_w[l], out_w = T.out_w[l], at = T.w_off[l], sft = shs[l];
-    const int f = frag - f0, term = f / (MT * KS), mt = (f / KS) % MT, ks = f % KS;
-    const int orow = 32 * mt + r;
-    f16x8 out;
+  float* block = (actor ? a.actor_block : a.critic_block) + (size_t)g * (SHIPPED ? kPolFloats : T.block_floats);
+  // the fp16 section, layer by layer: one 16-byte store per (fragment, lane); fragment (term MT + mt) KS + ks of the layer's 2 MT KS
+  float* out = block + at.frags;
+  for (int l = 0; l <= L; ++l) {
+    const int MT = T.mt[l], KS = T.ks[l], in_w = T.in_w[l], out_w = T.out_w[l], at_w = T.w_off[l], sft = shs[l];
+    for (int q = t; q < 2 * MT * KS * 64; q += kPpoAdamThreads) {
+      const int f = q >> 6, lane = q & 63, r = lane & 31, h = lane >> 5;
+      const int term = f / (MT * KS), mt = (f / KS) % MT, ks = f % KS;
+      const int orow = 32 * mt + r;
+      f16x8 o;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      // layer 0: natural k order (its B operand is built from obs rows); later layers: the k order of an accumulator tile
-      const int k = l == 0 ? 16 * ks + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
-      const float x = (orow < out_w && k < in_w) ? w[at + orow * in_w + k] : 0.0f;
-      const float ws = ldexpf(x, sft);
-      const _Float16 hi = (_Float16)ws;                            // round to nearest even, subnormals kept
-      out[j] = term == 0 ? hi : (_Float16)(ws - (float)hi);        // (the difference is exact in fp32)
+      for (int j = 0; j < 8; ++j) {
+        // layer 0: natural k order (its B operand is built from obs rows); later layers: the k order of an accumulator tile
+        const int k = l == 0 ? 16 * ks + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+        const float x = (orow < out_w && k < in_w) ? w[at_w + orow * in_w + k] : 0.0f;
+        const float ws = ldexpf(x, sft);
+        const _Float16 hi = (_Float16)ws;                          // round to nearest even, subnormals kept
+        o[j] = term == 0 ? hi : (_Float16)(ws - (float)hi);        // (the difference is exact in fp32)
+      }
+      *reinterpret_cast<f16x8*>(out + 4 * q) = o;
     }
-    *reinterpret_cast<f16x8*>(block + kMlpHdr + 4 * q) = out;
+    out += 2 * MT * KS * (kPolFragBytes / 4);
   }
   // the biases in accumulator order, [mt][h][16] per layer, times the accumulator's scale; padded rows zero
-  float* biases = block + kMlpHdr + frags * (kPolFragBytes / 4);
-  for (int i = t; i < tiles * 32; i += kPpoAdamThreads) {
-    const int tile = i >> 5;
-    int l = 0, t0 = 0;
-    for (int k = 0, at = 0; k <= L; ++k) {
-      if (tile >= at && tile < at + T.mt[k]) { l = k; t0 = at; }
-      at += T.mt[k];
+  for (int l = 0; l <= L; ++l) {
+    if (t < T.mt[l] * 32) {
+      const int orow = 32 * (t >> 5) + (t & 3) + 8 * ((t & 15) >> 2) + 4 * ((t >> 4) & 1);
+      out[t] = orow < T.out_w[l] ? w[T.b_off[l] + orow] * ldexpf(1.0f, kPolXShift + shs[l]) : 0.0f;
     }
-    const int mt = tile - t0, h = (i >> 4) & 1, e = i & 15;
-    const int orow = 32 * mt + (e & 3) + 8 * (e >> 2) + 4 * h;
-    biases[i] = orow < T.out_w[l] ? w[T.b_off[l] + orow] * ldexpf(1.0f, kPolXShift + shs[l]) : 0.0f;
+    out += T.mt[l] * 32;
   }
-  // record word 4 of each layer: the inverse accumulator scale (a power of two: exact); an actor's exp(log_std) and log_std
-  if (t <= L) block[kMlpRec + kMlpRecStride * t + 4] = ldexpf(1.0f, -(kPolXShift + shs[t]));
+  // each layer's inverse accumulator scale (a power of two: exact); an actor's exp(log_std) and log_std
+  if (t <= L) block[at.scale + at.scale_stride * t] = ldexpf(1.0f, -(kPolXShift + shs[t]));
   if (actor && t >= 64 && t < 64 + kPolOut) {
     const float ls = w[T.ls_off + (t - 64)];
-    block[kMlpStd + (t - 64)] = (float)exp((double)ls);
-    block[kMlpStd + 8 + (t - 64)] = ls;
+    block[at.std + (t - 64)] = (float)exp((double)ls);
+    block[at.log_std + (t - 64)] = ls;
   }
 }
 
-void ppo_mlp_adam_launch(const PpoMlpAdamLaunch& A, hipStream_t s) {
-  hipLaunchKernelGGL(ppo_mlp_adam_norm_kernel, dim3((unsigned)A.a.n_members), dim3(kPpoAdamThreads), 0, s, A);
-  hipLaunchKernelGGL(ppo_mlp_adam_update_kernel, dim3(2, (unsigned)A.a.n_members), dim3(kPpoAdamThreads), 0, s, A);
-}
-
-void ppo_adam_launch(const PpoAdamLaunch& a, hipStream_t s) {
+template <bool SHIPPED>
+static void adam_launch(const PpoAdamArgs<SHIPPED>& A, hipStream_t s) {
+  const PpoAdamLaunch& a = ppo_adam_launch_of(A);
   hipLaunchKernelGGL(ppo_adam_norm_kernel, dim3((unsigned)a.n_members), dim3(kPpoAdamThreads), 0, s, a);
-  hipLaunchKernelGGL(ppo_adam_update_kernel, dim3(2, (unsigned)a.n_members), dim3(kPpoAdamThreads), 0, s, a);
+  hipLaunchKernelGGL(ppo_adam_update_kernel<SHIPPED>, dim3(2, (unsigned)a.n_members), dim3(kPpoAdamThreads), 0, s, A);
 }
+void ppo_adam_launch(const PpoAdamLaunch& a, hipStream_t s) { adam_launch<true>(a, s); }
+void ppo_mlp_adam_launch(const PpoMlpAdamLaunch& A, hipStream_t s) { adam_launch<false>(A, s); }
 
 }  // namespace rdv

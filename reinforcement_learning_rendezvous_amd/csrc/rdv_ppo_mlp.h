@@ -58,7 +58,7 @@ struct PpoMlpTable {
 };
 
 // the floats of pack_mlp_weights' block for `spec` (the head is one tile whatever out_dim)
-inline int ppo_mlp_block_floats(const RdvMlpSpec& spec) {
+constexpr int ppo_mlp_block_floats(const RdvMlpSpec& spec) {
   int frags = 0, tiles = 0;
   for (int l = 0; l <= spec.n_hidden; ++l) {
     const int mt = l < spec.n_hidden ? mlp_tiles(spec.hidden[l]) : 1, ks = l == 0 ? 2 : mlp_ksteps(spec.hidden[l - 1]);
@@ -66,12 +66,13 @@ inline int ppo_mlp_block_floats(const RdvMlpSpec& spec) {
   }
   return kMlpHdr + frags * (kPolFragBytes / 4) + tiles * 32;
 }
-inline int ppo_mlp_waves(const RdvMlpSpec& spec) {
+constexpr int ppo_mlp_waves(const RdvMlpSpec& spec) {
   return (ppo_mlp_block_floats(spec) + 8 * kPpoWaveFloats) * 4 <= kPpoMlpLdsLimit ? 8 : 4;
 }
 inline int ppo_mlp_lds_bytes(const PpoMlpTable& t) { return (t.block_floats + t.waves * kPpoWaveFloats) * 4; }
 
-inline void ppo_mlp_table(const RdvMlpSpec& spec, bool actor, PpoMlpTable& t) {
+// (constexpr: rdv_ppo_adam.hip takes the default spec's table at compile time)
+constexpr void ppo_mlp_table(const RdvMlpSpec& spec, bool actor, PpoMlpTable& t) {
   const int L = spec.n_hidden, out_dim = actor ? kPolOut : 1;
   t = PpoMlpTable{};
   t.L = L; t.waves = ppo_mlp_waves(spec); t.block_floats = ppo_mlp_block_floats(spec);

@@ -6,7 +6,9 @@ References of rdv_ppo_set_adam_step (include/rdv.h, "Gradient clip, Adam and wei
   - ``coef64`` / ``coef32``: the double expressions of total_norm, clip_coef, step_size and inv_sqrt_bc2, and their float roundings;
   - ``step64``: the whole step in float64 — clip_grad_norm_ over actor and critic together, then torch.optim.Adam's update — and
     ``bound``, the error a float32 step may show against it, derived by counting roundings;
-  - the flat layouts [5708] / [5377] of a network, the corner members that reach the packer's branches, and the block comparison.
+  - the flat layouts [5708] / [5377] of a network, the corner members that reach the packer's branches, and what the GPU tests of both
+    entry points (the shipped call and rdv_ppo_mlp_set_adam_step) and the timing tools share: the gradient cases, dense gradients of any
+    pair of lengths, the block reader and the block comparison.
 
 The bound.  One step moves p by dp = step_size m / (sqrt(v) inv_sqrt_bc2 + eps).  In float32, with u = 2^-24:
   g' = g clip_coef carries 4 u (total_norm, clip_coef rounded once each from double, the product, and the gradient's own scale is exact);
@@ -33,6 +35,7 @@ import policy_mlp_reference as M
 
 ACTOR, CRITIC = 5708, 5377
 BLOCK_FLOATS, BLOCK_STD = 8372, 8352          # kPolFloats, kPolStd of csrc/rdv_policy.h
+MLP_STD = 48                                  # kMlpStd of csrc/rdv_policy_mlp.h: exp(log_std) [8], then log_std [8], as from kPolStd on
 U = 2.0 ** -24
 WRONG = ("eps_in_sqrt", "no_bias_correction", "actor_norm_only", "unclamped_clip")
 f32 = np.float32
@@ -40,10 +43,11 @@ f32 = np.float32
 
 # ------------------------------------------------------------------------------------------------------------ layouts
 def flat(net):
-    """w1 b1 w2 b2 w3 b3 [log_std] of a policy_mlp_reference network, the layout of RdvPpoOut's gradients (an actor has 6 head rows)."""
+    """A policy_mlp_reference network of any depth in the flat layout of rdv_ppo_mlp_grad_floats (the shipped one: RdvPpoOut's
+    w1 b1 w2 b2 w3 b3 [log_std]): per layer w then b, an actor's log_std (6 head rows) last."""
     parts = [a.reshape(-1) for w, b in zip(net["w"], net["b"]) for a in (w, b)]
     if net["w"][-1].shape[0] == 6:
-        parts.append(net["log_std"])
+        parts.append(net["log_std"].reshape(-1))
     return np.concatenate(parts).astype(np.float32)
 
 
@@ -162,12 +166,20 @@ class Reference64:
 
 
 # ------------------------------------------------------------------------------------------------------------ inputs
-def gradients(seed, scale):
-    """(ga, gc): dense float32 gradients of 2-norm ``scale`` over the 11,085 entries together (a gradient has no structure the step reads)."""
+# gradient cases (name, 2-norm, max_grad_norm), in the order a test takes them as consecutive steps: the all-zero gradient first (with
+# zero moments the parameters must not move), then clipping active, inactive, and no clipping at all
+GRAD_CASES = [("zero", 0.0, 0.5), ("clipped", 3.0, 0.5), ("unclipped", 0.2, 0.5), ("no_clipping", 5.0, float("inf"))]
+
+
+def gradients(seed, scale, ga=ACTOR, gc=CRITIC):
+    """(actor, critic): dense float32 gradients of 2-norm ``scale`` over the ga + gc entries together (a gradient has no structure the
+    step reads); ``scale`` 0: all zeros."""
+    if scale == 0.0:
+        return np.zeros(ga, np.float32), np.zeros(gc, np.float32)
     rng = np.random.default_rng([seed, 411])
-    g = rng.standard_normal(ACTOR + CRITIC) * np.exp(rng.uniform(-2.0, 2.0, size=ACTOR + CRITIC))
+    g = rng.standard_normal(ga + gc) * np.exp(rng.uniform(-2.0, 2.0, size=ga + gc))
     g = (g * (scale / np.linalg.norm(g))).astype(np.float32)
-    return g[:ACTOR].copy(), g[ACTOR:].copy()
+    return g[:ga].copy(), g[ga:].copy()
 
 
 def corner_nets(which, seed=5):
@@ -198,19 +210,30 @@ def corner_nets(which, seed=5):
 CORNERS = ("cross", "big", "tiny", "zero")
 
 
-def blocks_equal(got, want, actor):
-    """Two parameter blocks [8372] (float32 arrays) compared as the header states: byte for byte outside the six exp(log_std) floats of
-    an actor block; those within 1 ulp of np.exp in float64 of the block's own log_std.  Returns a message, or None when equal."""
-    a, b = np.asarray(got, np.float32).view(np.uint32), np.asarray(want, np.float32).view(np.uint32)
-    assert a.shape == b.shape == (BLOCK_FLOATS,)
+def read_block(handle, member, stream=None):
+    """Block ``member`` of a policy handle (rdv_policy_block_floats, rdv_policy_get_block) as a float32 array"""
+    import ctypes as C
+    from reinforcement_learning_rendezvous_amd import _native as N
+    out = np.empty(int(N.lib().rdv_policy_block_floats(handle)), np.float32)
+    N.check(N.lib().rdv_policy_get_block(handle, member, out.ctypes.data_as(C.c_void_p), out.size, stream))
+    return out
+
+
+def blocks_equal(got, want, actor, std_at=BLOCK_STD):
+    """Two parameter blocks (float32 arrays; ``std_at``: the float index of exp(log_std), BLOCK_STD in a shipped block, MLP_STD in one of
+    pack_mlp_weights) compared as the header states: byte for byte outside the six exp(log_std) floats of an actor block; those within
+    1 ulp of np.exp in float64 of the block's own log_std.  Returns a message, or None when equal."""
+    got = np.asarray(got, np.float32)
+    a, b = got.view(np.uint32), np.asarray(want, np.float32).view(np.uint32)
+    assert a.shape == b.shape and (std_at != BLOCK_STD or a.shape == (BLOCK_FLOATS,))
     same = a == b
     if actor:
-        same[BLOCK_STD:BLOCK_STD + 6] = True
+        same[std_at:std_at + 6] = True
     if not same.all():
         at = np.flatnonzero(~same)
         return f"{at.size} words differ, first at float {int(at[0])}: {a[at[0]]:#010x} != {b[at[0]]:#010x}"
     if actor:
-        std, log_std = np.asarray(got, np.float32)[BLOCK_STD:BLOCK_STD + 6], np.asarray(got, np.float32)[BLOCK_STD + 8:BLOCK_STD + 14]
+        std, log_std = got[std_at:std_at + 6], got[std_at + 8:std_at + 14]
         want64 = np.exp(log_std.astype(np.float64))
         if not (np.abs(std.astype(np.float64) - want64) <= ulp(want64.astype(np.float32))).all():
             return f"exp(log_std) {std} is not within 1 ulp of {want64}"

@@ -1,6 +1,6 @@
 """
 What the tests of the general set form (rdv_ppo_mlp_set_loss_grad) share: the spec pairs, the members of a
-set of one pair, the rows, and tests/ppo_adam_reference.py's ``flat`` generalised to a spec.
+set of one pair, the rows, and (``flat``) tests/ppo_adam_reference.py's flat layout of a net.
 
 Members: dense random nets of tests/ppo_mlp_reference.py (``nets``), seed 5 + 2 g for member g, so a wrong member's block cannot pass by
 accident.  Rows: the 1,200 rows of ``ppo_mlp_reference.make_case`` for the pair (drawn for member 0; the comparisons are by equality of
@@ -13,6 +13,7 @@ import torch
 import policy_mlp_reference as M
 import ppo_mlp_reference as Q
 import ppo_reference as P
+from ppo_adam_reference import flat  # noqa: F401  (H.flat: the flat layout of rdv_ppo_mlp_grad_floats)
 from reinforcement_learning_rendezvous_amd import _native as N
 from reinforcement_learning_rendezvous_amd.policy import ACTIVATIONS, MlpPolicy, PolicySet
 
@@ -65,10 +66,3 @@ def member_indices(g, n, seed=4):
         idx[n // 2] = idx[1]
     return torch.from_numpy(idx)
 
-
-def flat(net):
-    """A net's parameters in the flat layout of rdv_ppo_mlp_grad_floats: per layer w then b, an actor's log_std last."""
-    parts = [t.reshape(-1) for w, b in zip(net["w"], net["b"]) for t in (w, b)]
-    if net["w"][-1].shape[0] == 6:
-        parts.append(net["log_std"].reshape(-1))
-    return np.concatenate(parts).astype(np.float32)

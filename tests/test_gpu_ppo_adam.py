@@ -33,7 +33,6 @@ pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 LR, BETAS, EPS = 3e-4, (0.9, 0.999), 1e-5
-INF = float("inf")
 STATE = [name for name, _ in N.AdamState._fields_]
 
 
@@ -46,9 +45,8 @@ def stream():
 
 
 def get_block(handle, member):
-    out = np.empty(A.BLOCK_FLOATS, np.float32)
-    assert N.lib().rdv_policy_block_floats(handle) == A.BLOCK_FLOATS
-    N.check(N.lib().rdv_policy_get_block(handle, member, out.ctypes.data_as(C.c_void_p), A.BLOCK_FLOATS, stream()))
+    out = A.read_block(handle, member, stream())
+    assert out.shape == (A.BLOCK_FLOATS,)
     return out
 
 
@@ -75,11 +73,11 @@ class Rig:
         self.ga.copy_(torch.from_numpy(np.stack([g[0] for g in grads])))
         self.gc.copy_(torch.from_numpy(np.stack([g[1] for g in grads])))
 
-    def step(self, mask=None, lr=LR, betas=BETAS, eps=EPS, max_norm=0.5, handles=None):
+    def step(self, mask=None, lr=LR, betas=BETAS, eps=EPS, max_norm=0.5, handles=None, call="rdv_ppo_set_adam_step"):
         mask = (1 << self.P) - 1 if mask is None else mask
         a, c = handles or (self.actor, self.critic)
-        return N.lib().rdv_ppo_set_adam_step(a, c, C.byref(self.state), C.c_void_p(self.ga.data_ptr()), C.c_void_p(self.gc.data_ptr()),
-                                             C.c_uint64(mask), lr, betas[0], betas[1], eps, max_norm, stream())
+        return getattr(N.lib(), call)(a, c, C.byref(self.state), C.c_void_p(self.ga.data_ptr()), C.c_void_p(self.gc.data_ptr()),
+                                      C.c_uint64(mask), lr, betas[0], betas[1], eps, max_norm, stream())
 
     def read(self):
         """Every array on the host, and every member's two blocks"""
@@ -135,14 +133,10 @@ def P_nets(seed):
     return P.random_nets(seed=seed)
 
 
-# gradient cases, in the order a rig takes them: the all-zero gradient first (with zero moments the parameters must not move), then
-# clipping active, inactive, and no clipping at all
-GRAD_CASES = [("zero", 0.0, 0.5), ("clipped", 3.0, 0.5), ("unclipped", 0.2, 0.5), ("no_clipping", 5.0, INF)]
+GRAD_CASES = A.GRAD_CASES
 
 
 def case_grads(P, name, scale, seed):
-    if name == "zero":
-        return [(np.zeros(A.ACTOR, np.float32), np.zeros(A.CRITIC, np.float32)) for _ in range(P)]
     return [A.gradients(seed + 17 * g, scale * (1.0 + 0.25 * g / P)) for g in range(P)]
 
 

@@ -30,10 +30,8 @@ pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 D = torch.device(DEV)
 ENT, VF = 0.01, 0.5
-INF = float("inf")
 LR, B1, B2, EPS = 3e-4, 0.9, 0.999, 1e-5
-MLP_STD = 48                                    # kMlpStd (csrc/rdv_policy_mlp.h): exp(log_std) [8], then log_std [8]
-GRAD_CASES = [("zero", 0.0, 0.5), ("clipped", 3.0, 0.5), ("unclipped", 0.2, 0.5), ("no_clipping", 5.0, INF)]
+GRAD_CASES = A.GRAD_CASES
 NAMES = ("actor_param", "critic_param", "actor_m", "actor_v", "critic_m", "critic_v")
 
 
@@ -49,14 +47,7 @@ def columns(pair):
     return {k: torch.from_numpy(np.array(v)).to(DEV) for k, v in H.columns(pair).items()}
 
 
-def gradients(seed, scale, ga, gc):
-    """ppo_adam_reference.gradients for any pair of lengths: dense float32 gradients of 2-norm ``scale`` over the ga + gc entries"""
-    if scale == 0.0:
-        return np.zeros(ga, np.float32), np.zeros(gc, np.float32)
-    rng = np.random.default_rng([seed, 411])
-    g = rng.standard_normal(ga + gc) * np.exp(rng.uniform(-2.0, 2.0, size=ga + gc))
-    g = (g * (scale / np.linalg.norm(g))).astype(np.float32)
-    return g[:ga].copy(), g[ga:].copy()
+gradients = A.gradients
 
 
 def ready(pset, cols, counts=(64, 40, 64)):
@@ -74,32 +65,13 @@ def snapshot(pset, ad):
 
 
 def blocks(pset, g):
-    """(actor block, critic block) of member g of the set's handles"""
-    out = []
-    for h in (pset._hip_handle(DEV), pset._critic_handle(DEV)):
-        b = np.empty(int(N.lib().rdv_policy_block_floats(h)), np.float32)
-        N.check(N.lib().rdv_policy_get_block(h, g, b.ctypes.data_as(C.c_void_p), b.size, None))
-        out.append(b)
-    return out
+    """[actor block, critic block] of member g of the set's handles"""
+    return [A.read_block(h, g) for h in (pset._hip_handle(DEV), pset._critic_handle(DEV))]
 
 
 def blocks_equal(got, want, actor):
-    """ppo_adam_reference.blocks_equal's rule for a block of pack_mlp_weights: byte for byte outside the six exp(log_std) floats of an
-    actor block; those within 1 ulp of np.exp in float64 of the block's own log_std.  A message, or None when equal."""
-    a, b = got.view(np.uint32), want.view(np.uint32)
-    assert a.shape == b.shape
-    same = a == b
-    if actor:
-        same[MLP_STD:MLP_STD + 6] = True
-    if not same.all():
-        at = np.flatnonzero(~same)
-        return f"{at.size} words differ, first at float {int(at[0])}: {a[at[0]]:#010x} != {b[at[0]]:#010x}"
-    if actor:
-        std, log_std = got[MLP_STD:MLP_STD + 6], got[MLP_STD + 8:MLP_STD + 14]
-        want64 = np.exp(log_std.astype(np.float64))
-        if not (np.abs(std.astype(np.float64) - want64) <= A.ulp(want64.astype(np.float32))).all():
-            return f"exp(log_std) {std} is not within 1 ulp of {want64}"
-    return None
+    """ppo_adam_reference.blocks_equal's rule for a block of pack_mlp_weights"""
+    return A.blocks_equal(got, want, actor, A.MLP_STD)
 
 
 def fresh(member):

@@ -153,23 +153,14 @@ def main():
         if worst[0] > 1.0:
             sys.exit(f"ppo_mlp_set_step_time.py: {name}: the device step leaves the float64 reference's bound: {worst[0]:.3f} (PyTorch's float32 step: {worst[1]:.3f})")
 
-        def blocks(x):
-            out = []
-            for h in (x._hip_handle(DEV), x._critic_handle(DEV)):
-                for g in range(P):
-                    b = np.empty(int(N.lib().rdv_policy_block_floats(h)), np.float32)
-                    N.check(N.lib().rdv_policy_get_block(h, g, b.ctypes.data_as(C.c_void_p), b.size, None))
-                    out.append(b.view(np.uint32).copy())
-            return out
+        blocks = lambda x: [A.read_block(h, g) for h in (x._hip_handle(DEV), x._critic_handle(DEV)) for g in range(P)]
         packed_on_device = blocks(dset)
         dset.update_weights()                                           # the host packer on the same weights
         torch.cuda.synchronize()
         for k, (got, want) in enumerate(zip(packed_on_device, blocks(dset))):
-            same = got == want
-            if k < P:
-                same[48:54] = True                                      # an actor's six exp(log_std) floats (within 1 ulp: the tests)
-            if not same.all():
-                sys.exit(f"ppo_mlp_set_step_time.py: {name}: a block packed on the device differs from the host packer's (block {k})")
+            msg = A.blocks_equal(got, want, k < P, A.MLP_STD)
+            if msg:
+                sys.exit(f"ppo_mlp_set_step_time.py: {name}: a block packed on the device differs from the host packer's (block {k}): {msg}")
         bound = f"{worst[0]:.3f},{worst[1]:.3f}"
 
         ad = dset._adam[torch.device(DEV)]

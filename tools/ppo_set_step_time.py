@@ -43,13 +43,7 @@ def flat_params(pset):
 
 def blocks(pset):
     """[(block, is_actor)] of every member of both set handles"""
-    out = []
-    for actor, h in ((True, pset._hip_handle(DEV)), (False, pset._critic_handle(DEV))):
-        for g in range(len(pset)):
-            b = np.empty(N.POLICY_BLOCK_FLOATS, np.float32)
-            N.check(N.lib().rdv_policy_get_block(h, g, b.ctypes.data_as(C.c_void_p), b.size, None))
-            out.append((b, actor))
-    return out
+    return [(A.read_block(h, g), actor) for actor, h in ((True, pset._hip_handle(DEV)), (False, pset._critic_handle(DEV))) for g in range(len(pset))]
 
 
 def main():
