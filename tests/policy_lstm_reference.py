@@ -7,9 +7,11 @@ RecurrentActorCriticPolicy with one LSTM layer and separate actor / critic LSTMs
     c'     =  sigmoid(a_f) c + sigmoid(a_i) tanh(a_g);   h' = sigmoid(a_o) tanh(c')
     out    =  head(trunk(h'))
 
-in float64 and in plain float32, the network classes, the defect restatements, the routing probes and the error budget that
-tests/test_gpu_policy_lstm.py asserts.  The trunk, its activations and their constants are tests/policy_mlp_reference.py's.  Runs on
-the CPU; pinned against torch.nn.LSTM by tests/test_policy_lstm.py.
+in float64 and in plain float32, the network classes, the defect restatements, the routing probes and the error budgets that
+tests/test_gpu_policy_lstm.py asserts: budget() along a run from the zero state, local_budget() for ONE step from a given state.  Where
+h enters the recurrent product, and nowhere else, it is clamped to +-63 (rdv.h; +-inf counts as +-63, as for an observation): no effect
+on a state the cell produced.  The trunk, its activations and their constants are tests/policy_mlp_reference.py's.  Runs on the CPU;
+pinned against torch.nn.LSTM by tests/test_policy_lstm.py.
 """
 import numpy as np
 
@@ -22,6 +24,9 @@ HIDDEN_SIZES = (32, 64, 128, 256)
 BATCH_SIZES = M.BATCH_SIZES                       # (1, 31, 32, 33, 255, 256, 257, 1000)
 T_STEPS = 6
 DEFECTS = ("gate_order_ifog", "no_reset", "no_b_hh", "c_is_h")
+# h_not_clamped: the state corners alone show it.  lo_term_dropped, shift_is_max: wrong restatements of the cell's weight quantisation.
+QUANT_DEFECTS = ("lo_term_dropped", "shift_is_max")
+H_CLAMP = 63.0                   # rdv.h: the state enters the matrix cores clamped to +-63
 EXTRA_TRUNKS = (([16], "relu"), ([32, 32, 32], "sigmoid"), ([64, 64, 64, 64], "tanh"))
 
 
@@ -64,15 +69,49 @@ def _sigmoid(x):
         return (1 / (1 + np.exp(-x))).astype(x.dtype)
 
 
+def clamp_h(h):
+    """The state as the recurrent product reads it: clamped to +-63, NaN kept (np.clip keeps NaN)."""
+    return np.clip(h, -H_CLAMP, H_CLAMP)
+
+
+def cell_shift(net, defect=None):
+    """rdv.h: W_ih and W_hh share ONE power-of-two scale, the smaller of their documented shifts."""
+    s_ih, s_hh = R.documented_shift(net["w_ih"]), R.documented_shift(net["w_hh"])
+    return max(s_ih, s_hh) if defect == "shift_is_max" else min(s_ih, s_hh)
+
+
+def quantised(w, s, lo_term=True):
+    """rdv_policy.h: w 2^s = hi + lo, hi = float16(w 2^s), lo = float16(w 2^s - hi) (the subtraction is exact in float32), both rounded
+    to nearest even, subnormals kept -> (hi + lo) 2^-s in float64: the weight the matrix cores see.  |w| 2^s >= 65520 rounds to inf."""
+    ws = np.ldexp(np.asarray(w, np.float32), s).astype(np.float32)
+    with np.errstate(over="ignore", invalid="ignore"):
+        hi = ws.astype(np.float16)
+        lo = (ws - hi.astype(np.float32)).astype(np.float16)
+        q = hi.astype(np.float64) + (lo.astype(np.float64) if lo_term else 0.0)
+    return np.ldexp(q, -s)
+
+
+def cell_weights(net, defect=None):
+    """(W_ih, W_hh) of the cell as quantised under the shared shift, float64; `defect` in QUANT_DEFECTS restates the rule wrongly."""
+    s = cell_shift(net, defect)
+    return tuple(quantised(net[k], s, lo_term=defect != "lo_term_dropped") for k in ("w_ih", "w_hh"))
+
+
 def cell(net, x, h, c, s, dt, defect=None, parts=None):
     """One step in dtype dt.  x [n,17] (clamped by the caller), h, c [n,H], s [n] in {0, 1} -> (h', c').  `defect`: one of DEFECTS,
-    the wrong restatements the budget must tell apart.  `parts`, a dict, receives the gates and the reset c."""
+    "h_not_clamped" or QUANT_DEFECTS, the wrong restatements the budgets must tell apart.  `parts`, a dict, receives the gates, the
+    reset c and the clamped h of the recurrent product."""
     H = hidden_of(net)
     p = {k: net[k].astype(dt) for k in ("w_ih", "w_hh", "b_ih", "b_hh")}
-    keep = (1 - np.asarray(s)).astype(dt)[:, None]
+    if defect in QUANT_DEFECTS:
+        p["w_ih"], p["w_hh"] = (w.astype(dt) for w in cell_weights(net, defect))
+    h, c = np.asarray(h, dt), np.asarray(c, dt)
     if defect != "no_reset":
-        h, c = h * keep, c * keep
-    a = x.astype(dt) @ p["w_ih"].T + p["b_ih"] + h @ p["w_hh"].T
+        keep = (np.asarray(s) == 0)[:, None]
+        h, c = np.where(keep, h, dt(0)), np.where(keep, c, dt(0))          # (1 - s) h with 0 inf = 0: a started row reads no state
+    hp = h if defect == "h_not_clamped" else clamp_h(h)
+    with np.errstate(invalid="ignore", over="ignore"):
+        a = x.astype(dt) @ p["w_ih"].T + p["b_ih"] + hp @ p["w_hh"].T
     if defect != "no_b_hh":
         a = a + p["b_hh"]
     order = (0, 1, 3, 2) if defect == "gate_order_ifog" else (0, 1, 2, 3)
@@ -82,7 +121,7 @@ def cell(net, x, h, c, s, dt, defect=None, parts=None):
     h1 = o * np.tanh(c1)
     assert h1.dtype == dt and c1.dtype == dt
     if parts is not None:
-        parts.update(i=i, f=f, g=g, o=o, c=c, c1=c1)
+        parts.update(i=i, f=f, g=g, o=o, c=c, c1=c1, hp=hp)
     return h1, c1
 
 
@@ -130,23 +169,83 @@ def budget(net, obs_seq, starts):
     d_h, d_c = np.zeros((n, H)), np.zeros((n, H))
     h, c = np.zeros((n, H)), np.zeros((n, H))
     A_out, A_h, A_c = [], [], []
-    lip, d_act = M.LIP[net["act"]], M.D_ACT[net["act"]]
     for t in range(T):
         keep = (1 - np.asarray(starts[t])).astype(f8)[:, None]
         d_h, d_c = d_h * keep, d_c * keep
         parts = {}
         h, c = cell(net, R.clamp_obs(np.asarray(obs_seq[t], np.float32)), h, c, starts[t], f8, parts=parts)
-        d_a = d_h @ aw_hh.T
-        d_i, d_f, d_g, d_o = (SIGMOID_ABS_ERR + d_a[:, 0:H] / 4, SIGMOID_ABS_ERR + d_a[:, H:2 * H] / 4, TANH_ABS_ERR + d_a[:, 2 * H:3 * H],
-                              SIGMOID_ABS_ERR + d_a[:, 3 * H:] / 4)
-        d_c = d_f * np.abs(parts["c"]) + parts["f"] * d_c + d_i * np.abs(parts["g"]) + parts["i"] * d_g
-        d_h = d_o * np.abs(np.tanh(parts["c1"])) + parts["o"] * (TANH_ABS_ERR + d_c)
-        a = d_h
-        for w in net["w"][:-1]:
-            a = lip * (a @ np.abs(w.astype(f8)).T) + d_act + SUBNORMAL_ABS_ERR
-        A_out.append((a @ np.abs(net["w"][-1].astype(f8)).T).max(axis=1)); A_h.append(d_h.max(axis=1)); A_c.append(d_c.max(axis=1))
+        d_h, d_c, a_out = _budget_step(net, parts, d_h @ aw_hh.T, d_c)
+        A_out.append(a_out.max(axis=1)); A_h.append(d_h.max(axis=1)); A_c.append(d_c.max(axis=1))
     res.update(A_out=np.asarray(A_out), A_h=np.asarray(A_h), A_c=np.asarray(A_c))
     return res
+
+
+def _budget_step(net, parts, d_a, d_c):
+    """One step of budget()'s recursion from the error d_a of the pre-activations and d_c of the state read: (d_h', d_c', A of the outputs)."""
+    H = hidden_of(net)
+    f8 = np.float64
+    d_i, d_f, d_g, d_o = (SIGMOID_ABS_ERR + d_a[:, 0:H] / 4, SIGMOID_ABS_ERR + d_a[:, H:2 * H] / 4, TANH_ABS_ERR + d_a[:, 2 * H:3 * H],
+                          SIGMOID_ABS_ERR + d_a[:, 3 * H:] / 4)
+    d_c = d_f * np.abs(parts["c"]) + parts["f"] * d_c + d_i * np.abs(parts["g"]) + parts["i"] * d_g
+    d_h = d_o * np.abs(np.tanh(parts["c1"])) + parts["o"] * (TANH_ABS_ERR + d_c)
+    lip, d_act = M.LIP[net["act"]], M.D_ACT[net["act"]]
+    a = d_h
+    for w in net["w"][:-1]:
+        a = lip * (a @ np.abs(w.astype(f8)).T) + d_act + SUBNORMAL_ABS_ERR
+    return d_h, d_c, a @ np.abs(net["w"][-1].astype(f8)).T
+
+
+def local_budget(net, obs, starts, h0, c0):
+    """The budget of ONE step from the state (h0, c0), float32 arrays [n, H] (exact in float64), observations [n, 17] and episode starts
+    [n] (None: no row starts): budget()'s recursion taken for one step with d_h = d_c = 0 at its start, plus what the documented
+    quantisation of the cell's weights leaves,
+
+        d_a = |W_ih - Q(W_ih)| |x| + |W_hh - Q(W_hh)| |clamp(h)|        Q: quantised() under cell_shift(), computed exactly
+
+    (with s_ih = s_hh = 10 the residual is 2^-22 |w| at most; when one matrix's outlier lowers the shared shift, the other's lo terms
+    lose bits and this term carries the bound).  It does not grow with the number of steps before it: a check of every step along the
+    device's own trajectory asserts the same thing at step 60 as at step 0.  Returns dict(out64 [n, out_dim], h64, c64 [n, H] float64;
+    e32_out, e32_h, e32_c [n] = max|float32 step - float64 step| per row; A_out, A_h, A_c [n]).  Tolerance: local_tolerance()."""
+    f8 = np.float64
+    h0, c0 = np.asarray(h0, np.float32), np.asarray(c0, np.float32)
+    n = h0.shape[0]
+    s = np.zeros(n, np.uint8) if starts is None else np.asarray(starts)
+    x = R.clamp_obs(np.asarray(obs, np.float32))
+    parts = {}
+    h64, c64 = cell(net, x, h0, c0, s, f8, parts=parts)
+    h32, c32 = cell(net, x, h0, c0, s, np.float32)
+    with np.errstate(invalid="ignore"):
+        e = lambda a32, a64: np.abs(a32.astype(f8) - a64).max(axis=1)
+        out64 = trunk(net, h64, f8)
+        res = dict(out64=out64, h64=h64, c64=c64, e32_out=e(trunk(net, h32, np.float32), out64), e32_h=e(h32, h64), e32_c=e(c32, c64))
+    q_ih, q_hh = cell_weights(net)
+    d_a = np.abs(x.astype(f8)) @ np.abs(net["w_ih"].astype(f8) - q_ih).T + np.abs(parts["hp"]) @ np.abs(net["w_hh"].astype(f8) - q_hh).T
+    d_h, d_c, a_out = _budget_step(net, parts, d_a, np.zeros_like(d_a[:, :hidden_of(net)]))
+    res.update(A_out=a_out.max(axis=1), A_h=d_h.max(axis=1), A_c=d_c.max(axis=1))
+    return res
+
+
+def local_tolerance(bud, what, rows=None):
+    """1.5 e32 + A of `what` in ("out", "h", "c") of a local_budget over `rows` (None: all), e32 and A each at their maximum over them."""
+    rows = slice(None) if rows is None else rows
+    return float(1.5 * bud[f"e32_{what}"][rows].max() + bud[f"A_{what}"][rows].max())
+
+
+def local_defect_factor(net, obs, starts, h0, c0, defect, bud=None, rows=None):
+    """By how much ONE step of the wrong restatement `defect` from (h0, c0) leaves the local tolerance: the largest of the three ratios
+    |defect step - reference| / (1.5 e32 + A) of the outputs, h' and c' — the three comparisons the GPU tests make after every step (the
+    trunk's own allowance hides from the outputs what h' shows).  A non-finite value (an unclamped inf, a weight scaled out of float16's
+    range) counts as inf.  `rows`: the rows looked at (None: all).  Returns (factor, which of "out", "h", "c" gave it)."""
+    bud = local_budget(net, obs, starts, h0, c0) if bud is None else bud
+    s = np.zeros(len(obs), np.uint8) if starts is None else np.asarray(starts)
+    h1, c1 = cell(net, R.clamp_obs(np.asarray(obs, np.float32)), np.asarray(h0, np.float32), np.asarray(c0, np.float32), s, np.float64, defect)
+    best = (0.0, "")
+    rows = slice(None) if rows is None else rows
+    with np.errstate(invalid="ignore"):
+        for what, got in (("out", trunk(net, h1, np.float64)), ("h", h1), ("c", c1)):
+            err = np.abs(got - bud[f"{what}64"])[rows]
+            best = max(best, (float(np.where(np.isfinite(err), err, np.inf).max() / local_tolerance(bud, what, rows)), what))
+    return best
 
 
 def tolerance(bud, what, n=None):
@@ -195,6 +294,61 @@ def hot(H, arch=(64, 64), act="tanh", seed=51):
 CLASSES = {"default_init": default_init, "hot": hot}
 
 
+def _with_cell(net, **cell_arrays):
+    p = dict(net, **cell_arrays)
+    return make_net(p["w_ih"], p["w_hh"], p["b_ih"], p["b_hh"], p["w"], p["b"], p["act"])
+
+
+def _outliers(w, rng, count, lo, hi, signed):
+    """`count` entries of w, each in a row and a column of its own, set to U[lo, hi) (times +-1 when signed)."""
+    w = w.copy()
+    rows, cols = rng.choice(w.shape[0], count, replace=False), rng.choice(w.shape[1], count, replace=False)
+    w[rows, cols] = rng.uniform(lo, hi, count) * (rng.choice([-1.0, 1.0], count) if signed else 1.0)
+    return w
+
+
+def hh_shift9(H, arch=(64, 64), act="tanh", seed=51):
+    """hot with eight entries of W_hh at +-[33, 60): s_hh = 9 < s_ih = 10, the cell's shift is W_hh's."""
+    net = hot(H, arch, act, seed)
+    return _with_cell(net, w_hh=_outliers(net["w_hh"], np.random.default_rng([seed, H, 9]), 8, 33.0, 60.0, True))
+
+
+def ih_shift3(H, arch=(64, 64), act="tanh", seed=51):
+    """hot with four entries of W_ih at 3000: s_ih = 3 < s_hh = 10, the min takes the other side."""
+    net = hot(H, arch, act, seed)
+    return _with_cell(net, w_ih=_outliers(net["w_ih"], np.random.default_rng([seed, H, 3]), 4, 3000.0, 3000.0, False))
+
+
+def hh_shift3(H, arch=(64, 64), act="tanh", seed=51):
+    """hot with four entries of W_hh at 3000: s_hh = 3, and W_ih's lo terms lose bits under it (local_budget's residual term)."""
+    net = hot(H, arch, act, seed)
+    return _with_cell(net, w_hh=_outliers(net["w_hh"], np.random.default_rng([seed, H, 33]), 4, 3000.0, 3000.0, False))
+
+
+def big_bias(H, arch=(64, 64), act="tanh", seed=51):
+    """hot with b_ih shifted by U(-30, 30) on half of the 4H rows: gates exactly 0 and 1 beside live ones; |c| grows by up to 1 a step."""
+    net = hot(H, arch, act, seed)
+    rng = np.random.default_rng([seed, H, 30])
+    b_ih = net["b_ih"].copy()
+    rows = rng.choice(4 * H, 2 * H, replace=False)
+    b_ih[rows] += rng.uniform(-30.0, 30.0, 2 * H)
+    return _with_cell(net, b_ih=b_ih)
+
+
+def long_memory(H, arch=(64, 64), act="tanh", seed=51):
+    """default_init with W_hh times 0.25, W_ih times 3 and the forget-gate bias + 3: c integrates its inputs over about 20 steps."""
+    net = default_init(H, arch, act, seed)
+    b_ih = net["b_ih"].copy(); b_ih[H:2 * H] += 3.0
+    return _with_cell(net, w_ih=3.0 * net["w_ih"], w_hh=0.25 * net["w_hh"], b_ih=b_ih)
+
+
+# the classes of the scaling and state corners: the shifts (s_ih, s_hh) each is built to have
+NEW_CLASSES = {"hh_shift9": hh_shift9, "ih_shift3": ih_shift3, "hh_shift3": hh_shift3, "big_bias": big_bias, "long_memory": long_memory}
+CLASS_SHIFTS = {"default_init": (10, 10), "hot": (10, 10), "hh_shift9": (10, 9), "ih_shift3": (3, 10), "hh_shift3": (10, 3), "big_bias": (10, 10),
+                "long_memory": (10, 10)}
+ALL_CLASSES = dict(CLASSES, **NEW_CLASSES)
+
+
 def route_probe(H, m, seed=52):
     """One-path network number m: row u of gate q reads ONE input feature and ONE state unit,
         W_ih[q H + u, (u + 5 q + m) % 17] = +-0.9,   W_hh[q H + u, (7 u + 3 q + 37 m + 1) % H] = +-1.4
@@ -229,6 +383,39 @@ ROUTE_PROBES = 3
 def obs_sequence(n, T=T_STEPS, seed=60):
     """[T, n, 17] distinct observation rows inside the Box, another set per step."""
     return np.stack([R.distinct_rows(n, seed=seed + t) for t in range(T)])
+
+
+FAR_T = 48
+
+
+def far_state(net, n):
+    """(the observations of step FAR_T, the state (h, c) a float32 run of FAR_T steps from zero reaches in front of it): where big_bias has
+    |c| near 48 and long_memory has integrated its inputs — states the six-step runs never see."""
+    obs, starts = obs_sequence(n, FAR_T + 1), episode_starts(n, FAR_T + 1)
+    _, hs, cs = run(net, obs[:FAR_T], starts[:FAR_T], np.float32)
+    return obs[FAR_T], hs[-1], cs[-1]
+
+
+H_CORNERS = (0.999, 1.0, -1.0, 5.0, -5.0, 62.9, -62.9, 63.0, -63.0, 64.0, -64.0, 1e3, -1e3, np.inf, -np.inf, -0.0)
+C_CORNERS = (50.0, -50.0, 1e4, -1e4, 1e30, -1e30, 1e-30, -0.0)
+
+
+def state_corners(net, n=33):
+    """States that only rdv_lstm_set_state can put there.  The ordinary state is what a float32 run of T_STEPS steps reaches.  Rows 0, 4,
+    8, .. keep it; each other row r takes one corner value (H_CORNERS in h, then C_CORNERS in c, in row order) on its units u with
+    (u + r) % 4 == 0 and the ordinary state on the rest, so that a corner row's gates are not all saturated.  c stays finite.
+    Returns dict(obs [n, 17], h_ord, c_ord, h, c [n, H] float32, ordinary = the rows that keep the ordinary state, kind[r] = "h=63", ..)."""
+    H = hidden_of(net)
+    assert n == 1 + 4 * ((len(H_CORNERS) + len(C_CORNERS)) // 3)
+    _, hs, cs = run(net, obs_sequence(n), episode_starts(n), np.float32)
+    h_ord, c_ord = hs[-1], cs[-1]
+    h, c = h_ord.copy(), c_ord.copy()
+    corner_rows = [r for r in range(n) if r % 4]
+    kind = {r: "ordinary" for r in range(n)}
+    for r, (what, v) in zip(corner_rows, [("h", v) for v in H_CORNERS] + [("c", v) for v in C_CORNERS]):
+        (h if what == "h" else c)[r, (np.arange(H) + r) % 4 == 0] = v
+        kind[r] = f"{what}={v:g}"
+    return dict(obs=obs_sequence(n, 1, seed=75)[0], h_ord=h_ord, c_ord=c_ord, h=h, c=c, ordinary=[r for r in range(n) if r % 4 == 0], kind=kind)
 
 
 def episode_starts(n, T=T_STEPS):

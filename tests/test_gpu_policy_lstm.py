@@ -6,8 +6,12 @@ steps 0, 2 and 3, means / values and the state (h, c) after every step within
     e_hip <= 1.5 e32 + A            e32 = max|float32 run - float64 run|, A = the first-order entrywise budget through the cell and the
                                     trunk (policy_lstm_reference.budget), both from the reference alone, over the rows of the case
 
-then the noise, the state calls, rdv_rollout and rdv_rollout_advantages against the loops they are defined by, the NaN rule and the
-refusals.
+and, since that budget grows with every step it is carried through (at 64 steps it asserts nothing), the LOCAL check: (h, c) is
+downloaded before a step, and the step's output and new state are held to the float64 reference of that ONE step from that downloaded
+state, within policy_lstm_reference.local_budget's 1.5 e32 + A — the same at step 60 as at step 0, along the device's own trajectory.
+It carries the classes of the scaling corners (s_ih != s_hh), saturated gates and large |c|, a 64-step trajectory and the states that
+only rdv_lstm_set_state can put there.  Then the noise, the state calls, rdv_rollout and rdv_rollout_advantages against the loops they
+are defined by, the NaN rule and the refusals.
 """
 import ctypes as C
 
@@ -33,12 +37,34 @@ def _policy(net, critic, n_rows, seed=0):
     return p
 
 
-def _check_steps(tag, pol, kind, net, bud, obs, starts, n, worst, failures):
-    """T steps of the actor (deterministic) or critic on the first n rows; every step's output and state against the budget's slice."""
+def _state(pol, kind):
+    h, c = pol.state if kind == "actor" else pol.critic_state
+    return h.cpu().numpy(), c.cpu().numpy()
+
+
+def _check_local(tag, kind, net, obs_t, starts_t, before, got, after, t, worst, failures):
+    """One step against the float64 reference of that step from the state `before` = (h, c) as downloaded in front of it: the output
+    `got` [n, out_dim] (an actor's is clipped, and so is the reference's: the clip is 1-Lipschitz) and the state `after`, each within
+    the one-step tolerance over the rows of the call.  `worst` = [ratio, err, tol, where] keeps the largest ratio seen."""
+    bud = L.local_budget(net, obs_t, starts_t, before[0], before[1])
+    want = np.clip(bud["out64"], -1.0, 1.0) if kind == "actor" else bud["out64"]
+    for what, g, w in (("out", got, want), ("h", after[0].astype(np.float64), bud["h64"]), ("c", after[1].astype(np.float64), bud["c64"])):
+        err, tol = float(np.abs(g - w).max()), L.local_tolerance(bud, what)
+        if not err / tol < worst[0]:
+            worst[:] = [err / tol, err, tol, f"{tag}/step {t}/{what}"]
+        if not err <= tol:
+            failures.append((tag, "local", t, what, err, tol, "row", int(np.abs(g - w).max(axis=1).argmax())))
+    return bud
+
+
+def _check_steps(tag, pol, kind, net, bud, obs, starts, n, worst, failures, local=None):
+    """T steps of the actor (deterministic) or critic on the first n rows; every step's output and state against the budget's slice.
+    `local`: a `worst` list of its own — the local check of every step (_check_local) on top."""
     T = obs.shape[0]
     tol = {w: L.tolerance(bud, w, n) for w in ("out", "h", "c")}
     for t in range(T):
         o, s = _dev(obs[t, :n]), starts[t, :n]
+        before = _state(pol, kind) if local is not None else None
         if kind == "actor":
             got = pol.act(o, episode_start=s, deterministic=True).cpu().numpy().astype(np.float64)
             want = np.clip(bud["out64"][t, :n], -1.0, 1.0)
@@ -56,25 +82,168 @@ def _check_steps(tag, pol, kind, net, bud, obs, starts, n, worst, failures):
                 worst[:] = [ratio, err, float(tol[what][t]), f"{tag}/step {t}/{what}"]
             if not err <= tol[what][t]:
                 failures.append((tag, t, what, err, float(tol[what][t]), "row", int(np.abs(g - w).max(axis=1).argmax())))
+        if local is not None:
+            _check_local(tag, kind, net, obs[t, :n], s, before, got, (h.cpu().numpy(), c.cpu().numpy()), t, local, failures)
 
 
 @pytest.mark.parametrize("H", L.HIDDEN_SIZES)
 def test_steps_against_fp64(H):
-    """[64, 64] tanh trunk; both network classes; rows on both sides of the 32-env wave tile and the 256-env workgroup; actor and critic."""
+    """[64, 64] tanh trunk; both network classes; rows on both sides of the 32-env wave tile and the 256-env workgroup; actor and critic.
+    At n = 257 every step is also held to the one-step reference from the state in front of it: steps 3 to 5 of `hot`, where the global
+    tolerance on the means has passed the clip's width, assert something."""
     obs, starts = L.obs_sequence(N_MAX), L.episode_starts(N_MAX)
     failures = []
     for cid, make in L.CLASSES.items():
         net, critic = make(H), L.critic_of(make(H, seed=77))
         buds = {"actor": L.budget(net, obs, starts), "critic": L.budget(critic, obs, starts)}
         worst = {"actor": [0.0, 0.0, 0.0, ""], "critic": [0.0, 0.0, 0.0, ""]}
+        local = {"actor": [0.0, 0.0, 0.0, ""], "critic": [0.0, 0.0, 0.0, ""]}
         for n in L.BATCH_SIZES:
             pol = _policy(net, critic, n)
             for kind, nn in (("actor", net), ("critic", critic)):
-                _check_steps(f"{cid}/n{n}/{kind}", pol, kind, nn, buds[kind], obs, starts, n, worst[kind], failures)
+                _check_steps(f"{cid}/n{n}/{kind}", pol, kind, nn, buds[kind], obs, starts, n, worst[kind], failures, local[kind] if n == 257 else None)
             pol.close()
         for kind, w in worst.items():
             print(f"TABLE H {H:3d} {cid:12s} {kind:6s} e_hip {w[1]:.3g}  bound {w[2]:.3g}  ({w[3]}: {w[0]:.2f} of its bound)")
+            print(f"TABLE H {H:3d} {cid:12s} {kind:6s} local e_hip {local[kind][1]:.3g}  bound {local[kind][2]:.3g}  ({local[kind][3]}: {local[kind][0]:.2f} of its bound)")
     assert not failures, failures[:8]
+
+
+# ------------------------------------------------------------------------------- scaling corners, long runs, state corners
+LOCAL_ROWS = 65                                  # two full 32-row wave tiles and one row of a third
+
+
+@pytest.mark.parametrize("cid", list(L.NEW_CLASSES))
+@pytest.mark.parametrize("H", L.HIDDEN_SIZES)
+def test_new_classes_against_fp64(H, cid):
+    """The classes whose cell has s_ih != s_hh, gates at 0 and 1 and a large |c|: 6 steps, actor and critic, the budget along the run and
+    the one-step reference at every step; then ONE step from the state a float32 run reaches after 48 steps (big_bias: |c| near 48), put
+    there by set_state."""
+    n = LOCAL_ROWS
+    obs, starts = L.obs_sequence(n), L.episode_starts(n)
+    make = L.NEW_CLASSES[cid]
+    net, critic = make(H), L.critic_of(make(H, seed=77))
+    pol = _policy(net, critic, n)
+    failures = []
+    for kind, nn in (("actor", net), ("critic", critic)):
+        worst, local = [0.0, 0.0, 0.0, ""], [0.0, 0.0, 0.0, ""]
+        _check_steps(f"{cid}/{kind}", pol, kind, nn, L.budget(nn, obs, starts), obs, starts, n, worst, failures, local)
+        far_obs, h0, c0 = L.far_state(nn, n)
+        if kind == "actor":
+            pol.state = (_dev(h0), _dev(c0))
+            got = pol.act(_dev(far_obs), deterministic=True).cpu().numpy().astype(np.float64)
+        else:
+            pol.critic_state = (_dev(h0), _dev(c0))
+            got = pol.value(_dev(far_obs)).cpu().numpy().astype(np.float64)[:, None]
+        _check_local(f"{cid}/{kind}", kind, nn, far_obs, None, (h0, c0), got, _state(pol, kind), L.FAR_T, local, failures)
+        print(f"TABLE H {H:3d} {cid:12s} {kind:6s} local e_hip {local[1]:.3g}  bound {local[2]:.3g}  ({local[3]}: {local[0]:.2f} of its bound)")
+    pol.close()
+    assert not failures, failures[:8]
+
+
+LONG_T = 64
+
+
+def _long_starts(n, T=LONG_T, seed=63):
+    """([T, n] episode starts: Bernoulli(0.1) per row and step, every row at steps 0 and 40; the steps called with episode_start=None)"""
+    s = (np.random.default_rng(seed).random((T, n)) < 0.1).astype(np.uint8)
+    s[0] = s[40] = 1
+    none = [t for t in range(T) if t % 9 == 5]
+    s[none] = 0
+    return s, none
+
+
+@pytest.mark.parametrize("cid", ("hot", "long_memory"))
+@pytest.mark.parametrize("H", (32, 256))
+def test_a_trajectory_of_64_steps(H, cid):
+    """64 steps of actor and critic along the device's own trajectory, every step held to the one-step reference from the state in front
+    of it (a lost or stale commit of h' or c' is an error of the size of the state); every eighth critic step is preceded by a
+    commit=False peek on another observation, which leaves the state — and, against a twin that never peeks, every later value —
+    bit-equal.  The error against the free-running float64 run is only required to stay finite: its budget is 1e39 by now."""
+    n, T = LOCAL_ROWS, LONG_T
+    obs = L.obs_sequence(n, T)
+    starts, none = _long_starts(n)
+    make = L.ALL_CLASSES[cid]
+    net, critic = make(H), L.critic_of(make(H, seed=77))
+    pol, twin = _policy(net, critic, n), _policy(net, critic, n)
+    free = {"actor": L.run(net, obs, starts)[0], "critic": L.run(critic, obs, starts)[0]}
+    failures, peeks = [], 0
+    worst = {"actor": [0.0, 0.0, 0.0, ""], "critic": [0.0, 0.0, 0.0, ""]}
+    drift = {"actor": 0.0, "critic": 0.0}
+    for t in range(T):
+        o, s = _dev(obs[t]), (None if t in none else starts[t])
+        for kind, nn in (("actor", net), ("critic", critic)):
+            before = _state(pol, kind)
+            if kind == "critic" and t % 8 == 3:
+                other = obs[(t + 7) % T]
+                peek = pol.value(_dev(other), episode_start=s, commit=False).cpu().numpy().astype(np.float64)[:, None]
+                held = _state(pol, kind)
+                assert np.array_equal(before[0], held[0]) and np.array_equal(before[1], held[1]), (t, "the peek wrote the state")
+                ref = L.local_budget(nn, other, starts[t], before[0], before[1])
+                assert np.abs(peek - ref["out64"]).max() <= L.local_tolerance(ref, "out"), (t, "peek")
+                peeks += 1
+            if kind == "actor":
+                got = pol.act(o, episode_start=s, deterministic=True).cpu().numpy().astype(np.float64)
+                assert (np.abs(got) < 1.0).any(), (t, "every mean is clipped")
+                want = np.clip(free[kind][t], -1.0, 1.0)
+            else:
+                v = pol.value(o, episode_start=s)
+                assert torch.equal(v, twin.value(o, episode_start=s)), (t, "a peek changed the trajectory")
+                got = v.cpu().numpy().astype(np.float64)[:, None]
+                want = free[kind][t]
+            _check_local(f"{cid}/{kind}", kind, nn, obs[t], starts[t], before, got, _state(pol, kind), t, worst[kind], failures)
+            assert np.isfinite(got).all(), (t, kind)
+            drift[kind] = max(drift[kind], float(np.abs(got - want).max()))
+    for x, y in zip(pol.critic_state, twin.critic_state):
+        assert torch.equal(x, y)
+    for kind, w in worst.items():
+        print(f"TABLE H {H:3d} {cid:12s} {kind:6s} {T} steps  worst local ratio {w[0]:.2f} at {w[3]} (e_hip {w[1]:.3g}, bound {w[2]:.3g})  "
+              f"global drift {drift[kind]:.3g}")
+    pol.close(); twin.close()
+    assert peeks == 8 and len(none) >= 5 and np.isfinite(list(drift.values())).all()
+    assert not failures, failures[:8]
+
+
+def test_state_corners_through_set_state():
+    """|h| at and beyond the +-63 clamp, +-inf, -0.0, and |c| up to 1e30 (policy_lstm_reference.state_corners), put there by
+    rdv_lstm_set_state: one step of actor and critic, every row held to the one-step reference — which clamps h where it enters W_hh h
+    and nowhere else — within that ROW's tolerance (a row with c = 1e30 has a tolerance of its own size); and the rows that keep the
+    ordinary state have the bits they have when every row is ordinary."""
+    H = 64
+    net, critic = L.hot(H), L.critic_of(L.hot(H, seed=77))
+    failures = []
+    for kind, nn in (("actor", net), ("critic", critic)):
+        sc = L.state_corners(nn)
+        n = len(sc["obs"])
+        o = _dev(sc["obs"])
+        step = (lambda p: p.act(o, deterministic=True)) if kind == "actor" else (lambda p: p.value(o)[:, None])
+        results = {}
+        for name, (h0, c0) in (("corners", (sc["h"], sc["c"])), ("ordinary", (sc["h_ord"], sc["c_ord"]))):
+            pol = _policy(net, critic, n)
+            state = (_dev(h0), _dev(c0))
+            if kind == "actor":
+                pol.state = state
+            else:
+                pol.critic_state = state
+            back = _state(pol, kind)
+            assert np.array_equal(back[0], h0, equal_nan=True) and np.array_equal(back[1], c0) and np.array_equal(np.signbit(back[0]), np.signbit(h0))
+            got = step(pol).cpu().numpy()
+            results[name] = (got,) + _state(pol, kind)
+            pol.close()
+        got, h1, c1 = results["corners"]
+        bud = L.local_budget(nn, sc["obs"], None, sc["h"], sc["c"])
+        want = np.clip(bud["out64"], -1.0, 1.0) if kind == "actor" else bud["out64"]
+        for r in range(n):
+            line = [f"TABLE corner {kind:6s} row {r:2d} {sc['kind'][r]:9s}"]
+            for what, g, w in (("out", got, want), ("h", h1, bud["h64"]), ("c", c1, bud["c64"])):
+                err, tol = float(np.abs(g[r].astype(np.float64) - w[r]).max()), L.local_tolerance(bud, what, [r])
+                line.append(f"{what} {err:.3g} / {tol:.3g}")
+                if not err <= tol:
+                    failures.append((kind, r, sc["kind"][r], what, err, tol))
+            print("  ".join(line))
+        for a, b in zip(results["corners"], results["ordinary"]):
+            assert np.array_equal(a[sc["ordinary"]], b[sc["ordinary"]]), (kind, "an ordinary row beside a corner row changed")
+    assert not failures, failures
 
 
 @pytest.mark.parametrize("arch,act", L.EXTRA_TRUNKS, ids=[f"{'x'.join(map(str, a))}-{f}" for a, f in L.EXTRA_TRUNKS])

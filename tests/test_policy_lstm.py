@@ -1,10 +1,12 @@
 """
 CPU tests of the recurrent policy: tests/policy_lstm_reference.py pinned against torch.nn.LSTM in float64, the error budget and its power
-to tell wrong restatements apart, the routing probes' coverage, the host-only spec checks and refusals of include/rdv.h ("The recurrent
+to tell wrong restatements apart, the one-step budget (its tolerance against what it guards, its defects, the state corners and the
+clamp on h, the classes' shifts), the routing probes' coverage, the host-only spec checks and refusals of include/rdv.h ("The recurrent
 policy"), LstmPolicy's state-dict inference and its PyTorch fallback.  tests/test_gpu_policy_lstm.py holds the kernels to the same
 reference.
 """
 import ctypes as C
+import functools
 import io
 import json
 import zipfile
@@ -66,6 +68,125 @@ def test_budget_tells_the_wrong_restatements_apart(H, cid):
     for d in L.DEFECTS:
         f = L.defect_factor(net, obs, starts, d, bud)
         assert f >= 10.0, (H, cid, d, f)
+
+
+# ------------------------------------------------------------------------------------- the one-step budget and the new classes
+LOCAL_ROWS = 65
+
+
+@functools.lru_cache(maxsize=None)
+def _far_state(cid, H):
+    """(net, obs of step 48, (h, c) a float32 run reaches after 48 steps, the one-step budget from there): computed once per class and H."""
+    net = L.ALL_CLASSES[cid](H)
+    obs, h, c = L.far_state(net, LOCAL_ROWS)
+    return net, obs, h, c, L.local_budget(net, obs, None, h, c)
+
+
+@pytest.mark.parametrize("cid", list(L.ALL_CLASSES))
+@pytest.mark.parametrize("H", L.HIDDEN_SIZES)
+def test_classes_have_the_shifts_they_are_built_for(H, cid):
+    net = L.ALL_CLASSES[cid](H)
+    assert (R.documented_shift(net["w_ih"]), R.documented_shift(net["w_hh"])) == L.CLASS_SHIFTS[cid]
+    assert L.cell_shift(net) == min(L.CLASS_SHIFTS[cid]) and L.cell_shift(net, "shift_is_max") == max(L.CLASS_SHIFTS[cid])
+    base = L.hot(H)
+    for k in ("w", "b"):                                                 # the change is to the cell only
+        assert all(np.array_equal(x, y) for x, y in zip(net[k], base[k]))
+
+
+def test_quantised_is_the_documented_two_term_split():
+    """hi + lo carries w 2^s to 22 bits where both terms are normal; under a low shift the lo term goes subnormal and loses bits; a
+    scaled weight of 65520 or more has no float16."""
+    w = np.asarray([0.3751234, -0.0123457, 3000.0, 1e-5, 0.0, -59.99], np.float32)
+    q10 = L.quantised(w[[0, 1, 3, 4]], 10)
+    w10 = w[[0, 1, 3, 4]].astype(np.float64)
+    assert (np.abs(q10 - w10) <= np.maximum(2.0 ** -22 * np.abs(w10), 2.0 ** -25 * 2.0 ** -10)).all() and q10[3] == 0.0
+    assert L.quantised(w[[2, 5]], 3)[0] == 3000.0 and abs(L.quantised(w[[5]], 9)[0] - float(w[5])) <= 2.0 ** -22 * 60
+    r3, r10 = (np.abs(L.quantised(w[:2], s) - w[:2].astype(np.float64)) for s in (3, 10))
+    assert (r3 <= 2.0 ** -25).all() and r3[1] > 8 * r10[1] >= 0                     # -0.0123 x 2^3: its lo term is on the subnormal grid 2^-24
+    assert (np.abs(L.quantised(w[:2], 10, lo_term=False) - w[:2]) > 100 * r10).all()
+    assert not np.isfinite(L.quantised(w[[2]], 10)).any()
+
+
+@pytest.mark.parametrize("cid", list(L.ALL_CLASSES))
+@pytest.mark.parametrize("H", (32, 256))
+def test_local_tolerance_is_a_hundredth_of_what_it_guards(H, cid):
+    """48 steps from zero, then one: the one-step tolerance on the means is at most 1 % of the spread of the reference's means over the
+    rows of that step (the condition that keeps the local check from asserting nothing), the means are inside the clip, the float32
+    step is inside its own budget, and the state is where the class is meant to take it."""
+    net, obs, h0, c0, bud = _far_state(cid, H)
+    tol = {w: L.local_tolerance(bud, w) for w in ("out", "h", "c")}
+    spread = float((bud["out64"].max(axis=0) - bud["out64"].min(axis=0)).min())
+    print(f"TABLE H {H:3d} {cid:12s} tol out {tol['out']:.3g} h {tol['h']:.3g} c {tol['c']:.3g}  spread {spread:.3g}  tol/spread {tol['out'] / spread:.2g}  max|c| {np.abs(c0).max():.3g}")
+    assert 0 < tol["out"] <= 0.01 * spread, (tol, spread)
+    assert (np.abs(bud["out64"]) < 0.999).all() and np.isfinite(bud["A_out"]).all()
+    assert tol["h"] < 2e-5 and (bud["e32_out"] <= bud["A_out"]).all()
+    lo, hi = {"big_bias": (40.0, 48.0), "long_memory": (4.0, 12.0)}.get(cid, (0.0, 48.0))
+    assert lo <= float(np.abs(c0).max()) <= hi
+    if cid == "big_bias":                                                # gates at 0 and exactly 1 beside live ones
+        parts = {}
+        L.cell(net, R.clamp_obs(obs), h0, c0, np.zeros(len(obs), np.uint8), np.float32, parts=parts)
+        g = np.concatenate([parts[k] for k in "ifo"], axis=1)
+        assert (g < 1e-9).mean() > 0.05 and (g == 1).mean() > 0.05 and ((g > 0.05) & (g < 0.95)).mean() > 0.2    # (1 / (1 + e^30) is 9e-14)
+
+
+@pytest.mark.parametrize("cid", list(L.ALL_CLASSES))
+@pytest.mark.parametrize("H", (32, 256))
+def test_local_budget_tells_the_wrong_restatements_apart(H, cid):
+    """One step from the state after 48: every present defect (no_reset on a step where every third row starts), the cell's weights
+    rounded to their hi term alone, and — where it moves a scaled outlier out of float16's range, 3000 x 2^10 — the larger shift for the
+    smaller, each leave the one-step tolerance by a factor of at least 10 in one of the three comparisons the GPU tests make (outputs,
+    h', c').  With outliers below 64 (hh_shift9) the larger shift still fits float16 (60 x 2^10 < 65504) and with equal shifts it is
+    the same shift: no defect there."""
+    net, obs, h0, c0, bud = _far_state(cid, H)
+    some = (np.arange(LOCAL_ROWS) % 3 == 0).astype(np.uint8)
+    found = {}
+    for d in L.DEFECTS + L.QUANT_DEFECTS:
+        if d == "shift_is_max" and min(L.CLASS_SHIFTS[cid]) > 3:
+            continue
+        found[d] = L.local_defect_factor(net, obs, some, h0, c0, d) if d == "no_reset" else L.local_defect_factor(net, obs, None, h0, c0, d, bud)
+    print(f"TABLE H {H:3d} {cid:12s} " + "  ".join(f"{d} {f:.3g} ({w})" for d, (f, w) in found.items()))
+    assert all(f >= 10.0 for f, _ in found.values()), found
+    if cid in ("ih_shift3", "hh_shift3"):
+        assert "shift_is_max" in found
+
+
+def test_local_budget_from_zero_is_the_first_step_of_the_global_one():
+    """The same reference values; the same budget plus the residual of the weights' quantisation, which at shift 10 adds little."""
+    net = L.hot(64)
+    obs, starts = L.obs_sequence(40, 1), L.episode_starts(40, 1)
+    g, z = L.budget(net, obs, starts), np.zeros((40, 64), np.float32)
+    loc = L.local_budget(net, obs[0], starts[0], z, z)
+    for k in ("out64", "h64", "c64", "e32_out", "e32_h", "e32_c"):
+        np.testing.assert_array_equal(loc[k], g[k][0])
+    for k in ("A_out", "A_h", "A_c"):
+        assert (loc[k] >= g[k][0]).all() and (loc[k] <= 1.25 * g[k][0]).all()
+
+
+def test_state_corners_and_the_clamp():
+    """|h| up to the clamp and past it, large |c|: the reference clamps h where it enters W_hh h and nowhere else (+-inf counts as +-63),
+    a started row reads no state at all, and not clamping leaves the tolerance of every row beyond +-63 by a factor of at least 10."""
+    net = L.hot(64)
+    sc = L.state_corners(net)
+    n = len(sc["obs"])
+    bud = L.local_budget(net, sc["obs"], None, sc["h"], sc["c"])
+    assert all(np.isfinite(bud[k]).all() for k in ("out64", "h64", "c64", "e32_out", "A_out", "A_h", "A_c"))
+    kind = sc["kind"]
+    clamped = L.local_budget(net, sc["obs"], None, np.clip(sc["h"], -63.0, 63.0), sc["c"])          # 64, 1e3 and inf all count as 63
+    for k in ("out64", "h64", "c64"):
+        np.testing.assert_array_equal(clamped[k], bud[k])
+    ordinary = L.local_budget(net, sc["obs"], None, sc["h_ord"], sc["c_ord"])
+    for r in sc["ordinary"]:
+        np.testing.assert_array_equal(bud["out64"][r], ordinary["out64"][r])
+    for r in range(n):
+        f, what = L.local_defect_factor(net, sc["obs"], None, sc["h"], sc["c"], "h_not_clamped", bud, rows=[r])
+        beyond = kind[r] in ("h=64", "h=-64", "h=1000", "h=-1000", "h=inf", "h=-inf")
+        if beyond:
+            print(f"TABLE h_not_clamped  row {r:2d} {kind[r]:8s} {f:.3g} ({what})")
+        assert (f >= 10.0) if beyond else (f == 0.0), (r, kind[r], f)
+    starts = np.ones(n, np.uint8)
+    fresh = L.local_budget(net, sc["obs"], starts, sc["h"], sc["c"])
+    zero = L.local_budget(net, sc["obs"], starts, np.zeros_like(sc["h"]), np.zeros_like(sc["c"]))
+    np.testing.assert_array_equal(fresh["out64"], zero["out64"])
 
 
 def test_the_recursion_matters_in_the_hot_class():
