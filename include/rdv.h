@@ -20,13 +20,20 @@
  *   - rdv_step performs no allocation.
  *   - quaternions are scalar-first (reference utils/quaternions.py:2).
  *
- * Stream capture (HIP graphs; tests/test_gpu_graphs.py)
+ * Stream capture (HIP graphs; tests/test_gpu_graphs.py, tests/test_gpu_lstm_graphs.py)
  *   Every call that only enqueues work on `stream` may be recorded into a graph (hipStreamBeginCapture ... EndCapture, torch.cuda.graph) and
  *   replayed; the tests pin rdv_step (every variant, the evaluator build, groups, general bodies), rdv_step_many, rdv_rollout (the
  *   persistent kernel and the loop forms), rdv_get_state, rdv_snapshot, rdv_policy_act, rdv_policy_value, rdv_gae,
- *   rdv_rollout_advantages, and the setters rdv_set_params, rdv_set_group_params and rdv_set_rigid_body.  A replay computes bit for bit
+ *   rdv_rollout_advantages, and the setters rdv_set_params, rdv_set_group_params and rdv_set_rigid_body; and the recurrent calls
+ *   rdv_lstm_act, rdv_lstm_value (committing and not), rdv_lstm_get_state, rdv_lstm_set_state, rdv_lstm_reset_state, rdv_rollout and
+ *   rdv_rollout_advantages with a recurrent handle, each with a plain handle and with a set.  A replay computes bit for bit
  *   what the same calls compute eagerly.  Make the calls once eagerly before recording them (lazily created handles and module loading
  *   stay out of the capture), and record on one stream.
+ *   A recurrent handle's state (h, c), its pending episode-start flags and its scratch rows live in the handle's DEVICE allocation, and
+ *   every call reads and writes them there, on `stream`: a graph freezes none of them.  A replay therefore continues from whatever the
+ *   call before it — a replay or an eager call on the replaying stream (rdv_lstm_act, rdv_lstm_value, rdv_lstm_set_state,
+ *   rdv_lstm_reset_state) — left there; rdv_lstm_set_weights and rdv_lstm_set_member_weights, made eagerly between replays, rewrite the
+ *   block inside the handle's allocation, so the graph stays valid and its later replays use the new weights.
  *   WHAT A GRAPH FREEZES.  The library decides on the host, at call time, what a launch will be; a graph keeps those decisions:
  *     - the kernel chosen (variant, storage, on_done, diag / eval outputs, general bodies, groups, the first step after rdv_set_state);
  *     - whether a prepare launch goes in front of rdv_step_many / rdv_rollout (it does when something since the last one — rdv_step, a
@@ -39,8 +46,8 @@
  *   between general and non-general bodies.
  *   Calls that REFUSE inside a capture (RDV_ERR_INVALID_ARGUMENT, the message says "stream capture"; asked before anything touches the
  *   stream, so the capture stays valid): rdv_get_stats, rdv_get_group_stats, rdv_eval_summary, rdv_eval_group_summary, rdv_restore,
- *   rdv_set_param_groups (they synchronise or allocate), rdv_policy_set_weights and rdv_policy_set_member_weights (their staging
- *   buffer is reused).  rdv_create,
+ *   rdv_set_param_groups (they synchronise or allocate), rdv_policy_set_weights, rdv_policy_set_member_weights, rdv_lstm_set_weights
+ *   and rdv_lstm_set_member_weights (their staging buffer is reused).  rdv_create,
  *   rdv_destroy and the policy create / destroy calls allocate and are not to be made while a capture is open either.
  *   SUPPORTED between replays, eagerly, on the stream that replays: rdv_step (the persistent kernels of a graph find the prepared states
  *   of the envs whose episodes it ended out of date by their tags and refill them before their first use) and rdv_set_params (it

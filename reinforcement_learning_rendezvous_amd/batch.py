@@ -286,8 +286,8 @@ class RendezvousBatch:
         N.check(self._lib.rdv_rollout(self._h, policy._hip_handle(dev), T, C.byref(ro), int(bool(deterministic)),
                                       C.c_uint64(policy.noise_seed), C.c_uint64(policy._calls), self._stream()))
         policy._calls += T
-        if recurrent:
-            policy._pending["l"] = out["done"][T - 1].clone()
+        if recurrent:       # in place, on the device: a recorded rollout leaves every replay's flags where the next one reads them
+            policy._set_pending("l", out["done"][T - 1], dev)
         # the batch's current observation / last rewards / dones, as after step(): copied on first access
         self._defer(obs=out["last_obs"], reward=out["reward"][T - 1], done=out["done"][T - 1])
         return out

@@ -46,7 +46,7 @@ def check_lstm_config(lstm_hidden_size, n_lstm_layers=1, shared_lstm=False, enab
 class _LstmRows(_HipHandles):
     """What LstmPolicy and LstmPolicySet share: the rows whose state (h, c) a recurrent handle owns, the pending episode-start flags and their
     mirror, and the act / value / advantages calls on the handles of ``_create_handle``.  The class gives ``lstm_hidden_size``, ``n_rows``,
-    ``backend``, ``noise_seed``, ``noise_env_offset``, ``_calls``, ``_state``, ``_pending``, and for the PyTorch path ``_module_device``,
+    ``backend``, ``noise_seed``, ``noise_env_offset``, ``_calls``, ``_state``, ``_pending``, ``_dev_pending``, and for the PyTorch path ``_module_device``,
     ``_forward_torch(prefix, obs, start, commit)`` (one step of the modules: means [n, 6] or values [n, 1]) and
     ``_sample_torch(mean, deterministic, generator, log_prob_out)`` (the unclipped action; ``log_prob_out`` [n] or None is filled)."""
 
@@ -68,12 +68,36 @@ class _LstmRows(_HipHandles):
         self._state[prefix] = st
         return st
 
+    def _device_flags(self, prefix, device):
+        """The mirror of a HIP handle's pending flags ON THE DEVICE: ONE uint8 [rows] tensor per prefix and device, allocated when the
+        handle is created (outside any stream capture) and only ever written in place.  Work recorded into a HIP graph therefore reads
+        the flags that the replay or the eager call before it left, not the tensor of the recording.  None: no handle on ``device``."""
+        device = torch.device(device)
+        if device.type != "cuda":
+            return None
+        return self._dev_pending.get((prefix, device.index if device.index is not None else torch.cuda.current_device()))
+
     def _pending_flags(self, prefix, device):
-        """The pending episode-start flags as a uint8 [rows] tensor."""
+        """The pending episode-start flags as a uint8 [rows] tensor: the handle's mirror on ``device`` itself where there is one."""
+        flags = self._device_flags(prefix, device)
+        if flags is not None:
+            return flags
         p = self._pending[prefix]
         if isinstance(p, torch.Tensor):
             return p.to(device)
         return torch.full((self.n_rows,), 1 if p else 0, dtype=torch.uint8, device=device)
+
+    def _set_pending(self, prefix, value, device=None):
+        """What a call leaves pending: True (every row), False (none) or a uint8 [rows] tensor (``done[T-1]`` of a rollout).  Written in
+        place into the mirror of the handle on ``device``; the host value ``_pending[prefix]`` is the PyTorch path's, and that of the time
+        before a handle exists."""
+        flags = None if device is None else self._device_flags(prefix, device)
+        if flags is None:
+            self._pending[prefix] = value.clone() if isinstance(value, torch.Tensor) else value
+        elif isinstance(value, torch.Tensor):
+            flags.copy_(value)
+        else:
+            flags.fill_(1 if value else 0)
 
     def state_at_start(self, prefix="l", device=None):
         """``(h, c)`` as the next rollout's first step will see it: the state, zero where an episode start is pending — what
@@ -88,7 +112,16 @@ class _LstmRows(_HipHandles):
     def _handle(self, prefix, device):
         if self.n_rows is None:
             raise ValueError("the number of rows is not known yet: pass n_rows or evaluate the policy once")
-        return super()._handle(prefix, device)
+        h = super()._handle(prefix, device)
+        device = torch.device(device)
+        key = (prefix, device.index if device.index is not None else torch.cuda.current_device())
+        if key not in self._dev_pending:          # with the handle: the mirror of its flags starts from the host value (every row, as created)
+            self._dev_pending[key] = self._pending_flags(prefix, torch.device("cuda", key[1])).clone()
+        return h
+
+    def close(self):
+        super().close()
+        self._dev_pending = {}
 
     def _get_state(self, prefix, device=None):
         table = self._hip if prefix == "l" else self._hip_critic
@@ -110,7 +143,7 @@ class _LstmRows(_HipHandles):
             self._rows(h.shape[0])
             h, c = h.to(torch.float32).contiguous(), c.to(torch.float32).contiguous()
             N.check(N.lib().rdv_lstm_set_state(self._handle(prefix, h.device), C.c_void_p(h.data_ptr()), C.c_void_p(c.data_ptr()), self._stream(h.device)))
-            self._pending[prefix] = False
+            self._set_pending(prefix, False, h.device)
             return
         h = torch.as_tensor(h, dtype=torch.float32)
         c = torch.as_tensor(c, dtype=torch.float32)
@@ -170,7 +203,9 @@ class _LstmRows(_HipHandles):
     def act(self, obs, episode_start=None, deterministic=True, generator=None, out=None, env_id_offset=None, raw_out=None, log_prob_out=None):
         """One step of the actor on observations [n, 17], n the policy's rows: the clipped action; the state advances.
         ``episode_start``: [n] flags (None: no row starts an episode).  HIP backend: noise keyed by (noise_seed, env_id_offset + i,
-        call counter), as ``MlpPolicy.act``; ``raw_out`` [n, 6] / ``log_prob_out`` [n] receive the unclipped sample and its log-density."""
+        call counter), as ``MlpPolicy.act``; ``raw_out`` [n, 6] / ``log_prob_out`` [n] receive the unclipped sample and its log-density.
+        Inside a stream capture (a HIP graph) pass ``episode_start`` as a device tensor made before the recording: a NumPy array or a
+        CPU tensor becomes a host-to-device copy, which does not belong in a capture."""
         n = self._rows(obs.shape[0])
         if self._use_hip(obs):
             from . import _native as N
@@ -186,7 +221,7 @@ class _LstmRows(_HipHandles):
                                          int(bool(deterministic)), C.c_uint64(self.noise_seed), C.c_uint64(self._calls), C.c_uint64(offset),
                                          self._stream(obs.device)))
             self._calls += 1
-            self._pending["l"] = False
+            self._set_pending("l", False, obs.device)
             return out
         mean = self._forward_torch("l", obs, self._flags(episode_start, n, obs.device))
         a = self._sample_torch(mean, deterministic, generator, log_prob_out)
@@ -201,7 +236,8 @@ class _LstmRows(_HipHandles):
     @torch.no_grad()
     def value(self, obs, episode_start=None, commit=True, out=None):
         """One step of the critic on observations [n, 17]: values [n].  ``commit=False`` evaluates without writing the critic's state
-        (sb3-contrib's ``predict_values`` for the value of the last observation)."""
+        (sb3-contrib's ``predict_values`` for the value of the last observation).  Inside a stream capture ``episode_start`` is a device
+        tensor made before the recording, as for ``act``."""
         n = self._rows(obs.shape[0])
         if self._use_hip(obs):
             from . import _native as N
@@ -212,7 +248,7 @@ class _LstmRows(_HipHandles):
             N.check(N.lib().rdv_lstm_value(self._handle("v", obs.device), C.c_void_p(obs.data_ptr()), None if flags is None else C.c_void_p(flags.data_ptr()),
                                            C.c_void_p(out.data_ptr()), n, int(bool(commit)), self._stream(obs.device)))
             if commit:
-                self._pending["v"] = False
+                self._set_pending("v", False, obs.device)
             return out
         v = self._forward_torch("v", obs, self._flags(episode_start, n, obs.device), commit=commit)[:, 0]
         if out is not None:
@@ -247,7 +283,7 @@ class _LstmRows(_HipHandles):
             ao = N.AdvantageOut(*[ro[f].data_ptr() for f, _ in N.AdvantageOut._fields_])
             N.check(N.lib().rdv_rollout_advantages(self._handle("v", dev), C.byref(rows), T, n, float(gamma), float(gae_lambda), C.byref(ao),
                                                    self._stream(dev)))
-            self._pending["v"] = ro["done"][T - 1].clone()
+            self._set_pending("v", ro["done"][T - 1], dev)
             return ro
         for t in range(T):
             flags = self._pending_flags("v", dev) if t == 0 else ro["done"][t - 1]
@@ -305,9 +341,11 @@ class LstmPolicy(_LstmRows, torch.nn.Module):
             p.requires_grad_(False)
         self.n_rows = None if n_rows is None else int(n_rows)
         self._state = {}                # torch backend: "l" / "v" -> [h, c] once the rows are known
-        # the handles' pending episode-start flags, mirrored: True (every row, as created), False (none) or the uint8 [rows] tensor a
-        # rollout left (done[T-1]); the torch backend's own flags
+        # the pending episode-start flags of the PyTorch path, and of the time before a HIP handle exists: True (every row, as created),
+        # False (none) or the uint8 [rows] tensor a rollout left (done[T-1]).  A HIP handle's flags are mirrored on ITS device, in
+        # _dev_pending[(prefix, device index)]: one uint8 [rows] tensor, written in place (_LstmRows._device_flags)
         self._pending = {"l": True, "v": True}
+        self._dev_pending = {}
 
     # ------------------------------------------------------------------------------------------------ weights
     def _layers(self, prefix):
@@ -488,6 +526,7 @@ class LstmPolicySet(_Members, _LstmRows):
         self.has_critic = True
         self._state = {}
         self._pending = {"l": True, "v": True}
+        self._dev_pending = {}
 
     # ------------------------------------------------------------------------------------------------ handles
     def _create_handle(self, prefix, idx):

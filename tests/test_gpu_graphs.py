@@ -100,12 +100,22 @@ class Twin:
         self.calls += 1
 
 
-def _replay_equals_eager(make, fn, before_record=None, between=None, replays=REPLAYS, kernel=None):
-    """The frame of every case in A and B.  `make()` -> a Twin; `fn(twin)` makes the calls and returns its output tensors (nested);
-    `before_record(twin)`: eager calls between warm-up and recording; `between(twin, r)`: eager calls in front of replay r >= 1."""
+def _policy_states(pol):
+    """(h, c) of the actor and of the critic of a recurrent policy or set, each where its handle exists"""
+    return {name: getattr(pol, name) for name, table in (("state", pol._hip), ("critic_state", pol._hip_critic)) if table}
+
+
+def _replay_equals_eager(make, fn, before_record=None, between=None, replays=REPLAYS, kernel=None, poison=False, after_replay=None):
+    """The frame of every case in A and B (and of tests/test_gpu_lstm_graphs.py).  `make()` -> a Twin; `fn(twin)` makes the calls and
+    returns its output tensors (nested); `before_record(twin)`: eager calls between warm-up and recording; `between(twin, r)`: eager calls
+    in front of replay r >= 1.  `poison`: the recorded floating-point outputs are filled with NaN in front of every replay (the replay,
+    not the warm-up, wrote what is compared); `after_replay(r, got, want)` runs behind the comparison of replay r (the graph is the
+    graphed twin's `graph`: a callback that replays it once more makes the eager twin's calls too).  At the end the env
+    handles are compared (_assert_final), and the states of a recurrent policy; a twin whose `env` is None is a policy alone, and the
+    final comparison is then the policies' states."""
     graphed, eager = make(), make()
     rec = {}
-    g = capture(lambda: rec.update(out=fn(graphed)), (lambda: before_record(graphed)) if before_record else None)
+    g = graphed.graph = capture(lambda: rec.update(out=fn(graphed)), (lambda: before_record(graphed)) if before_record else None)
     fn(eager)
     if before_record:
         before_record(eager)
@@ -113,15 +123,27 @@ def _replay_equals_eager(make, fn, before_record=None, between=None, replays=REP
         if between and r:
             between(graphed, r)
             between(eager, r)
+        if poison:
+            for _, x in _flat(rec["out"]):
+                if x.is_floating_point():
+                    x.fill_(float("nan"))
         g.replay()
         want = fn(eager)
         torch.cuda.synchronize()
         _assert_same(rec["out"], want, f"replay {r}")
-    stats = _assert_final(graphed.env, eager.env, kernel)
-    for t in (graphed, eager):
-        t.env.close()
-        if getattr(t, "pol", None) is not None:
-            t.pol.close()
+        if after_replay:
+            after_replay(r, rec["out"], want)
+    pols = [getattr(t, "pol", None) for t in (graphed, eager)]
+    recurrent = getattr(pols[0], "lstm_hidden_size", None) is not None
+    assert graphed.env is not None or recurrent, "a twin without an env handle is a recurrent policy alone"
+    if recurrent:
+        _assert_same(_policy_states(pols[0]), _policy_states(pols[1]), "final policy states")
+    stats = _assert_final(graphed.env, eager.env, kernel) if graphed.env is not None else None
+    for t, pol in zip((graphed, eager), pols):
+        if t.env is not None:
+            t.env.close()
+        if pol is not None:
+            pol.close()
     return stats
 
 

@@ -362,3 +362,38 @@ def test_fallback_advantages_are_the_critic_loop_plus_gae32():
         np.testing.assert_array_equal(got["returns"].numpy(), ret)
         for x, y in zip(pol.critic_state, twin.critic_state):
             assert torch.equal(x, y)
+
+
+def test_state_at_start_on_the_torch_backend_follows_the_host_flags():
+    """Two rollouts and an act on the PyTorch path: the flags are the host value ``_pending`` (True, False, or a copy of done[T-1]) and
+    no device mirror exists.  Actor: what RendezvousBatch.rollout leaves through ``_set_pending``; critic: ``advantages`` itself.
+    ``state_at_start`` is the state, zero on exactly the rows the last rollout ended on, and the whole state behind an act / a value."""
+    H, T, n = 32, 4, 12
+    net, critic = L.hot(H), L.critic_of(L.hot(H, seed=3))
+    pol = _policy(net, critic, backend="torch", n_rows=n)
+    rng = np.random.default_rng(6)
+    obs = torch.from_numpy(L.obs_sequence(n, T + 1, seed=80))
+    for call in range(2):
+        done = torch.from_numpy((rng.random((T, n)) < 0.4).astype(np.uint8))
+        assert 0 < int(done[T - 1].sum()) < n
+        for t in range(T):                                                        # the act + step loop a rollout is defined by
+            pol.act(obs[t], episode_start=pol._pending_flags("l", obs.device) if t == 0 else done[t - 1])
+        pol._set_pending("l", done[T - 1], obs.device)
+        pol.advantages(dict(obs=obs[:T], reward=torch.zeros(T, n), done=done, last_obs=obs[T]))
+        last = done[T - 1].clone()
+        done[T - 1] = 1 - done[T - 1]                                             # the flags are a copy: the caller's buffer may move on
+        for prefix, state in (("l", pol.state), ("v", pol.critic_state)):
+            assert isinstance(pol._pending[prefix], torch.Tensor) and torch.equal(pol._pending[prefix], last)
+            assert torch.equal(pol._pending_flags(prefix, obs.device), last)
+            h0, c0 = pol.state_at_start(prefix)
+            keep = last == 0
+            assert (h0[~keep] == 0).all() and (c0[~keep] == 0).all() and torch.equal(h0[keep], state[0][keep]) and torch.equal(c0[keep], state[1][keep])
+            assert float(h0[keep].abs().min(dim=1).values.max()) > 0.0
+    pol.act(obs[T])
+    pol.value(obs[T], commit=False)
+    assert pol._pending == {"l": False, "v": pol._pending["v"]} and isinstance(pol._pending["v"], torch.Tensor)    # a peek commits nothing
+    pol.value(obs[T])
+    assert pol._pending == {"l": False, "v": False} and pol._dev_pending == {}
+    for prefix, state in (("l", pol.state), ("v", pol.critic_state)):
+        for x, y in zip(pol.state_at_start(prefix), state):
+            assert torch.equal(x, y)
