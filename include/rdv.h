@@ -814,11 +814,14 @@ int rdv_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const Rdv
  *     critic_set — are the bytes that rdv_policy_create / rdv_critic_create pack from member g's new fp32 parameters: the per-layer shift
  *     (the largest s <= 10, down to -20, with max|w| 2^s < 2^15; an all-zero layer: 10), the two fp16 terms rounded to nearest even with
  *     fp16 subnormals kept, the fragment permutation, the biases in accumulator order times 2^(10 + s), log_std, the inverse scales, the
- *     zero padding.  ONE EXCEPTION: the six exp(log_std) floats of an actor block.  The host packer takes them from the C library's expf,
- *     which a device cannot reproduce bit for bit; the device writes the double-precision exp rounded to float, within 1 ulp of it.
+ *     zero padding.  ONE EXCEPTION: the six exp(log_std) floats of an actor block.  Host packer and device both write the
+ *     double-precision exp rounded to float, but through two libraries' exp: the floats are promised within 1 ulp of each other, and are
+ *     equal unless the two double results straddle a float rounding boundary (a chance of about 2^-29 per value).  (The host packer took
+ *     the C library's expf before, which is not correctly rounded and differed from the device's float in about one value of a thousand.)
  *     What follows from the exception: after a device step the set sentence "row i of member g equals a stand-alone handle of member g's
- *     weights" holds by equality for the deterministic action, the value and rdv_ppo_set_loss_grad (none of which reads exp(log_std));
- *     SAMPLED actions and their log_prob may differ in the last bit from those of a handle packed on the host from the same weights.
+ *     weights" holds by equality for the deterministic action and the value, which do not read exp(log_std); SAMPLED actions, their
+ *     log_prob and rdv_ppo_set_loss_grad read it from the block, and equal those of a handle packed on the host from the same weights
+ *     wherever the two floats are equal.
  *   - Non-finite gradients.  If total_norm is not finite (a NaN or an infinity among the gradients, or a norm beyond float's range),
  *     member g is skipped whole: its parameters, moments, step and blocks are untouched, coef[g] = total_norm, 0, 0, 0, 1, 0, 0, 0.  The
  *     other members are unaffected.  Parameters that leave the finite range through the step itself are NOT checked.

@@ -113,6 +113,12 @@ inline void pol_put(uint16_t* frags, int frag0, int mt_count, int ks_count, int 
   for (int q = 0; q < 2; ++q) frags[((size_t)(frag0 + (q * mt_count + mt) * ks_count + ks) * 64 + (size_t)lane) * 8 + (size_t)j] = term[q];
 }
 
+// Host: exp(log_std) as a block holds it — the double-precision exp rounded to float, the expression of the device repack
+// (rdv_ppo_adam.hip), so that a block packed here and one repacked on the device from the same log_std hold the same float.  (libm's expf
+// is within 0.502 ulp, not correctly rounded: it differs from this in about one value of a thousand, and the sampling, log_prob and
+// gradient kernels all read this float.)
+inline float pol_std(float log_std) { return (float)std::exp((double)log_std); }
+
 // Host: the parameter block of a 17-64-64-out_dim tanh MLP of the checkpoint (out_dim <= 6, finite weights) — weight fragments in MFMA
 // A-operand order, each weight scaled by its layer's power of two and split into two fp16 terms (w * 2^s = hi + lo to 22 bits), then
 // the biases in accumulator order (times the accumulator's scale), exp(log_std), log_std and the inverse scales.  SB3 stores
@@ -154,7 +160,7 @@ inline void pack_policy_weights(const float* w1, const float* b1, const float* w
         if (mt == 0) packed[kPolB3 + h * 16 + e] = row < out_dim ? b3[row] * acc3 : 0.0f;
       }
   packed[kPolScale + 0] = 1.0f / acc1; packed[kPolScale + 1] = 1.0f / acc2; packed[kPolScale + 2] = 1.0f / acc3;
-  if (log_std) for (int j = 0; j < out_dim; ++j) { packed[kPolStd + j] = std::exp(log_std[j]); packed[kPolLogStd + j] = log_std[j]; }
+  if (log_std) for (int j = 0; j < out_dim; ++j) { packed[kPolStd + j] = pol_std(log_std[j]); packed[kPolLogStd + j] = log_std[j]; }
 }
 
 // tanh in fp32 as 1 - 2 / (2^(2 log2(e) x) + 1), two at a time: v_exp_f32 + v_rcp_f32 (1 ulp each) per value and one packed multiply,

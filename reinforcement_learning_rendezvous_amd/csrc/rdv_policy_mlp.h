@@ -114,7 +114,7 @@ inline void pack_mlp_weights(const RdvMlpSpec& spec, int out_dim, const float* c
     packed[(size_t)(kMlpRec + kMlpRecStride * l + 4)] = 1.0f / acc;
     bias_at += mt_n[l] * 32;
   }
-  if (log_std) for (int j = 0; j < out_dim; ++j) { packed[kMlpStd + j] = std::exp(log_std[j]); packed[kMlpStd + 8 + j] = log_std[j]; }
+  if (log_std) for (int j = 0; j < out_dim; ++j) { packed[kMlpStd + j] = pol_std(log_std[j]); packed[kMlpStd + 8 + j] = log_std[j]; }
 }
 
 // The launches (rdv_policy_mlp.hip: the kernels have a translation unit of their own, so rdv_hip.hip's objects stay what they were).

@@ -39,8 +39,8 @@
 //      log_std[6..7], scale[3], a critic's sixteen std floats) and the general block's integer header, other record words and floats
 //      64..127 are what the host packer wrote — zeros or constants of the spec — at creation and at every update_weights(), which
 //      upload the whole block; nothing else writes a block.
-//      The block is the host packer's byte for byte but for exp(log_std): the host takes libm's expf, the device the double-precision
-//      exp rounded to float.
+//      The block is the host packer's byte for byte; exp(log_std) is the double-precision exp rounded to float on both sides (pol_std,
+//      rdv_policy.h), two libraries' exp: held to 1 ulp, equal unless the two doubles straddle a float rounding boundary.
 // No floating-point atomic, no workspace, nothing read from the forward blocks: the fp32 master weights are the caller's arrays.
 #pragma once
 

@@ -636,8 +636,9 @@ class PolicySet(_Members, _HipHandles):
         from the member modules and re-points the members' parameters at views of row g (the modules move to that device), as their
         ``.grad`` are views of the gradient buffers.  So ``state_dict()`` and checkpoints see the stepped weights with no copy, and NO
         ``update_weights()`` is needed: the call itself rewrites the members' forward blocks on the device — the bytes
-        ``update_weights()`` would pack, but for the six ``exp(log_std)`` floats of an actor block (within 1 ulp; sampled actions may
-        differ in the last bit from those of a freshly packed handle, deterministic actions, values and gradients do not).  A member
+        ``update_weights()`` would pack, but for the six ``exp(log_std)`` floats of an actor block: the double-precision exp rounded
+        to float on both sides, through two libraries' exp — promised within 1 ulp, and equal but for a double result next to a float
+        rounding boundary; deterministic actions and values do not read them, sampled actions and gradients do.  A member
         whose gradient norm is not finite is skipped whole and flagged.  ``update_weights(member=, weights=)`` writes through the views
         and keeps the moments: ``reset_optimizer`` zeroes them.
 
@@ -647,7 +648,9 @@ class PolicySet(_Members, _HipHandles):
 
         CPU rows, ``backend="torch"``, an unserved width or exactly one net of the shipped shape: per-member ``clip_grad_norm_`` and one ``torch.optim.Adam`` the set owns
         over all members' parameters; the moments are then PyTorch's, a member with a non-finite norm is left out of that step, and
-        ``update_weights()`` follows as before.
+        ``update_weights()`` follows as before.  Which of the two runs is decided by the LAST ``ppo_grads``: behind one that went member
+        by member, a set that has stepped on the device takes the PyTorch step too (on its parameters, the views of the master weights);
+        the device moments and step counters are left as they are, and a later device ``ppo_grads`` + ``adam_step`` continues from them.
 
         Returns a dict of [P] tensors on the rows' device: ``total_norm``, ``clip_coef``, ``skipped`` (1.0: the member's norm was not
         finite); the entries of a member that sat out are those of its last step (zero before the first)."""

@@ -389,6 +389,8 @@ def ppo_set_grads(pset, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
                 out[g] = ppo_grad(member, buf, indices[g], clip_range, ent_coef, vf_coef, normalize_advantage, check=False)
             finally:
                 member.backend = backend
+        # the gradients are now in the members' own buffers, not in the set's rows: the adam_step behind this call is the PyTorch one
+        pset.__dict__.pop("_ppo_last", None)
         return out
 
     from . import _native as N
@@ -464,7 +466,13 @@ def _adam_views(pset, ad):
                     p.data = flat[at:at + p.numel()].view(p.shape)
                     at += p.numel()
             _bind_grads(member, dict(actor=grads["actor"][g], critic=grads["critic"][g]), dev)
-    ad["first"] = [m.l1.weight.data_ptr() for m in pset.policies]
+    ad["views"] = _adam_pointers(pset)
+
+
+def _adam_pointers(pset):
+    """The addresses of every parameter of every member (13 x P for the shipped architecture): what ``_adam_state`` compares to see
+    whether each of them still is the view of its master row that ``_adam_views`` made."""
+    return [p.data_ptr() for m in pset.policies for part in _params(m) for p in part]
 
 
 def _adam_state(pset, dev):
@@ -479,11 +487,12 @@ def _adam_state(pset, dev):
         z = lambda n: torch.zeros((P, n), dtype=torch.float32, device=dev)
         ad = dict(actor_param=z(Ga), critic_param=z(Gc), actor_m=z(Ga), actor_v=z(Ga),
                   critic_m=z(Gc), critic_v=z(Gc), step=torch.zeros(P, dtype=torch.int64, device=dev),
-                  coef=z(N.ADAM_COEF), first=None)
+                  coef=z(N.ADAM_COEF), views=None)
         ad["c"] = N.AdamState(*[ad[name].data_ptr() for name, _ in N.AdamState._fields_])
         table[dev] = ad
-    # (a member moved with .to(), or given new Parameter objects, no longer aliases its row: the modules are the source of truth again)
-    if ad["first"] != [m.l1.weight.data_ptr() for m in pset.policies]:
+    # (a member moved with .to(), or with new storage or a new Parameter object for ANY of its parameters, no longer aliases its row:
+    # the modules are the source of truth again)
+    if ad["views"] != _adam_pointers(pset):
         _adam_views(pset, ad)
     return ad
 
