@@ -1093,6 +1093,96 @@ int rdv_lstm_set_member_weights(rdv_policy p, int32_t member, const float* w_ih_
                                 const float* b_hh_host, const float* const* weights_host, const float* const* biases_host,
                                 const float* log_std_host, void* stream);
 
+/*
+ * Recurrent PPO minibatch gradients (added within ABI 5: additive exports): the loss of SB3's PPO.train() for one minibatch of a
+ * recurrent rollout and its gradients for every parameter of a stand-alone recurrent actor and critic — LSTM and trunk of each —
+ * back-propagated through time in hand-written HIP (csrc/rdv_ppo_lstm.h).  It is what sb3-contrib's RecurrentPPO.train() computes for a
+ * minibatch that RecurrentRolloutBuffer cuts on env boundaries: B whole env columns of a [T, N] rollout, all T steps of each, so the loss
+ * means run over the n = T B entries (t, b) and nothing is padded.
+ *
+ * The function.  For column b (env e = envs[b], or b when envs is NULL), actor and critic each with an LSTM, a trunk and an (h0, c0) of
+ * their own:
+ *     (h, c)_{-1} = state0[e]        the state as step 0 of the rollout saw it — zero where an episode start was pending
+ *                                    (LstmPolicy.state_at_start); a constant of the minibatch: no gradient flows into it
+ *     s_t         = 0 for t = 0 (state0 is already zeroed), else done[t-1, e]
+ *     (h, c)     <- (1 - s_t) (h, c)_{t-1};   a = W_ih x_t + b_ih + W_hh h + b_hh            x_t = obs[t, e]
+ *     c_t         = sig(a_f) c + sig(a_i) tanh(a_g);   h_t = sig(a_o) tanh(c_t);   h_t -> trunk -> mean_t [6] / value_t
+ *   The loss is the expression of rdv_ppo_loss_grad above over the rows (t, b), with its log_prob, entropy, ratio, policy_loss,
+ *   value_loss, entropy_loss, approx_kl and clip_fraction, PyTorch's min / clamp sub-gradient rule, the float-rounded clip limits,
+ *   clip_range_vf = None and the NaN rule (a NaN in a sampled row reaches the gradients and the scalars).
+ *   Gradients: the recurrence carries them back in time; an episode start cuts them — nothing flows from step t into step t - 1 when
+ *   done[t-1, e] = 1, and such a step adds nothing to dW_hh through h_{t-1}; nothing flows into state0; b_ih and b_hh get the same
+ *   gradient.  What is differentiated is the function the forward kernels compute: the two-term fp16 weights of the handles' blocks as
+ *   of stream order, observations clamped to +-63 (also in the contraction that gives dW_ih), h_{t-1} as the cell reads it, biases added
+ *   behind the products, the trunk's activation derivatives taken from the forward's own activations (csrc/rdv_ppo_mlp.h), the cell's
+ *   from its own gate activations.
+ *
+ * rdv_lstm_ppo_spec_check (host only): each spec judged by rdv_lstm_spec_check, its message behind "actor: " / "critic: "; then both must
+ *   have the same hidden_size (RDV_ERR_INVALID_ARGUMENT).  Trunks may differ.
+ * rdv_lstm_ppo_grad_floats (host only): the length of a net's flat gradient, -1 for a bad spec.  The layout: w_ih[4H,17] w_hh[4H,H]
+ *   b_ih[4H] b_hh[4H] (nn.LSTM's arrays, gate order i, f, g, o), then the trunk as rdv_ppo_mlp_grad_floats lays a net out with layer 0 =
+ *   [hidden[0], H] (per layer w[out, in] then b[out], the head last), log_std[6] last for an actor.
+ * rdv_lstm_ppo_workspace_bytes (host only): -1 for a bad pair of specs or n_steps or n_seq <= 0; monotone in both sizes; a multiple of 16.
+ *   Per row (t, b) and net the workspace keeps h_t, c_t, the four gate activations (later d loss / d a_t in their place) and
+ *   d loss / d h_t: 28 H bytes (csrc/rdv_ppo_lstm.h says why the gates are kept and not recomputed).
+ * RdvLstmPpoRows: device pointers.  obs [T,N,17], actions [T,N,6] (the UNCLIPPED samples), old_log_prob, advantages (as they ENTER the
+ *   loss: the call never normalises), returns [T,N], done [T,N] uint8, actor_h0, actor_c0, critic_h0, critic_c0 [N,H]; envs [n_seq] int64,
+ *   nullable: the columns (NULL: columns 0 .. n_seq-1, then n_seq <= n_envs); not range-checked on the device: an entry outside
+ *   [0, n_envs) reads outside the arrays; a duplicate counts once per occurrence.  n_envs = N, n_steps = T, n_seq = B.  No array needs
+ *   more than its element's alignment: the columns are gathered into the workspace, which must be 16-byte aligned.
+ * RdvLstmPpoOut: actor_grad, critic_grad (rdv_lstm_ppo_grad_floats floats each), scalars [8] in the order of RdvPpoOut; log_prob and
+ *   values [T, n_seq] (both nullable): entry (t, b) is the log-density of actions[t, e] under the CURRENT actor and the current critic's
+ *   value.
+ *
+ * The contract:
+ *   - Enqueue only: no allocation, no synchronisation, no host-to-device copy; legal inside a stream capture.  4 T + 8 launches, fixed by
+ *     the specs, T and n_seq: three (gather, the two transposes), per net T cell steps, one trunk kernel, T backward steps and one
+ *     weight-gradient kernel, and one finishing kernel.
+ *   - Deterministic: the same inputs give the same bits in every output, eager or replayed from a captured graph.  No floating-point
+ *     atomic: per-wave sums are added in wave order, per-workgroup sums go through the workspace and are added in index order.
+ *   - Handles: their state and pending flags are neither read nor written; the weights are the blocks as of stream order (a call behind
+ *     rdv_lstm_set_weights on the same stream differentiates the new weights).  The forward half restates the rollout's cell and trunk operation for operation: with
+ *     unchanged weights out->values equals, bit for bit, what rdv_rollout_advantages wrote for those columns.
+ *   - Accuracy: tests/test_gpu_ppo_lstm_grad.py holds every gradient tensor to err = max|G - G64| / max|G64| <= 32 max(e32, 2^-23) and
+ *     every scalar to 128 max(e32, 2^-23), e32 the error of PyTorch's own float32 autograd against an fp64 reference on the same case;
+ *     profiles/lstm_ppo_grad_accuracy.csv holds the measured ratios.
+ *   - Order of checks.  Host only, the message naming the argument, RDV_ERR_INVALID_ARGUMENT: a null rows, out or required pointer
+ *     (everything but rows->envs, out->log_prob, out->values), n_envs, n_steps or n_seq <= 0, n_seq > n_envs without envs, more than 2^31
+ *     rows, a misaligned workspace, a clip_range that is not finite or not positive, an ent_coef or vf_coef that is not finite or
+ *     negative.  Then RDV_ERR_BAD_HANDLE for an invalid handle.  Then RDV_ERR_INVALID_ARGUMENT for a handle that is not recurrent, a
+ *     recurrent set of more than one member, actor and critic swapped, different hidden sizes, different devices, a short workspace.
+ *     A refused call enqueues nothing and leaves the handles as they were.
+ *   - The existing rdv_ppo_* calls keep refusing a recurrent handle.
+ * Not in this call: recurrent sets (LstmPolicySet.ppo_grads keeps refusing), a device Adam step for recurrent nets (clip, optimiser and
+ * rdv_lstm_set_weights stay the caller's), minibatches that start mid-column from stored states, clip_range_vf, one persistent launch.
+ */
+typedef struct RdvLstmPpoRows {      /* device pointers: the [T,N,...] columns of a recurrent rollout */
+  const float*   obs;                /* [T,N,17]                                            */
+  const float*   actions;            /* [T,N,6]  the UNCLIPPED samples                      */
+  const float*   old_log_prob;       /* [T,N]                                               */
+  const float*   advantages;         /* [T,N]    as they ENTER the loss                     */
+  const float*   returns;            /* [T,N]                                               */
+  const uint8_t* done;               /* [T,N]                                               */
+  const float*   actor_h0;           /* [N,H]    the actor's state as step 0 saw it         */
+  const float*   actor_c0;           /* [N,H]                                               */
+  const float*   critic_h0;          /* [N,H]    the critic's                               */
+  const float*   critic_c0;          /* [N,H]                                               */
+  const int64_t* envs;               /* [n_seq]  the minibatch's columns; NULL: 0..n_seq-1  */
+  int64_t        n_envs, n_steps, n_seq;
+} RdvLstmPpoRows;
+typedef struct RdvLstmPpoOut {       /* device pointers */
+  float* actor_grad;                 /* [rdv_lstm_ppo_grad_floats(actor spec, 1)]  required */
+  float* critic_grad;                /* [rdv_lstm_ppo_grad_floats(critic spec, 0)] required */
+  float* scalars;                    /* [8]          required */
+  float* log_prob;                   /* [T, n_seq]   nullable */
+  float* values;                     /* [T, n_seq]   nullable */
+} RdvLstmPpoOut;
+int rdv_lstm_ppo_spec_check(const RdvLstmSpec* actor_spec_host, const RdvLstmSpec* critic_spec_host);
+int64_t rdv_lstm_ppo_grad_floats(const RdvLstmSpec* spec_host, int is_actor);
+int64_t rdv_lstm_ppo_workspace_bytes(const RdvLstmSpec* actor_spec_host, const RdvLstmSpec* critic_spec_host, int64_t n_steps, int64_t n_seq);
+int rdv_lstm_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvLstmPpoRows* rows, double clip_range, double ent_coef,
+                           double vf_coef, void* workspace, int64_t workspace_bytes, const RdvLstmPpoOut* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

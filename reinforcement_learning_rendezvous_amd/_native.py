@@ -53,7 +53,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # PPO minibatch gradients for policy sets of every MLP architecture (added within ABI 5)
            "rdv_ppo_mlp_set_spec_check", "rdv_ppo_mlp_set_workspace_bytes", "rdv_ppo_mlp_set_loss_grad",
            # gradient clip, Adam and weight repack for policy sets of every MLP architecture (added within ABI 5)
-           "rdv_ppo_mlp_set_adam_step"]
+           "rdv_ppo_mlp_set_adam_step",
+           # recurrent PPO minibatch gradients (added within ABI 5)
+           "rdv_lstm_ppo_spec_check", "rdv_lstm_ppo_grad_floats", "rdv_lstm_ppo_workspace_bytes", "rdv_lstm_ppo_loss_grad"]
 
 
 class RdvError(RuntimeError):
@@ -108,6 +110,20 @@ class PpoRows(C.Structure):
 
 class PpoOut(C.Structure):
     """RdvPpoOut: device pointers of what rdv_ppo_loss_grad / rdv_ppo_mlp_loss_grad write (log_prob and values nullable)"""
+    _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
+class LstmPpoRows(C.Structure):
+    """RdvLstmPpoRows: device pointers of a recurrent rollout's [T,N,...] columns, the two state0 pairs [N,H] and the minibatch's env
+    columns (nullable)"""
+    _fields_ = [("obs", C.c_void_p), ("actions", C.c_void_p), ("old_log_prob", C.c_void_p), ("advantages", C.c_void_p), ("returns", C.c_void_p),
+                ("done", C.c_void_p), ("actor_h0", C.c_void_p), ("actor_c0", C.c_void_p), ("critic_h0", C.c_void_p), ("critic_c0", C.c_void_p),
+                ("envs", C.c_void_p), ("n_envs", C.c_int64), ("n_steps", C.c_int64), ("n_seq", C.c_int64)]
+
+
+class LstmPpoOut(C.Structure):
+    """RdvLstmPpoOut: device pointers of what rdv_lstm_ppo_loss_grad writes (log_prob and values [T, n_seq] nullable)"""
     _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
                 ("values", C.c_void_p)]
 
@@ -170,7 +186,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the twelve translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip, rdv_ppo_mlp.hip, rdv_ppo_adam.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
+    """Compile the thirteen translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip, rdv_ppo_mlp.hip, rdv_ppo_lstm.hip, rdv_ppo_adam.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -283,6 +299,10 @@ def lib():
         "rdv_ppo_mlp_set_workspace_bytes": (i64, [C.POINTER(MlpSpec), C.POINTER(MlpSpec), i32, C.POINTER(i64)]),
         "rdv_ppo_mlp_set_loss_grad": (C.c_int, [vp, vp, C.POINTER(PpoRows), C.POINTER(i64), C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(PpoSetOut), vp]),
         "rdv_ppo_mlp_set_adam_step": (C.c_int, [vp, vp, C.POINTER(AdamState), vp, vp, u64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, vp]),
+        "rdv_lstm_ppo_spec_check": (C.c_int, [C.POINTER(LstmSpec), C.POINTER(LstmSpec)]),
+        "rdv_lstm_ppo_grad_floats": (i64, [C.POINTER(LstmSpec), C.c_int]),
+        "rdv_lstm_ppo_workspace_bytes": (i64, [C.POINTER(LstmSpec), C.POINTER(LstmSpec), i64, i64]),
+        "rdv_lstm_ppo_loss_grad": (C.c_int, [vp, vp, C.POINTER(LstmPpoRows), C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(LstmPpoOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

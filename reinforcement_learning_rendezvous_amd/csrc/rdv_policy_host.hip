@@ -1,8 +1,8 @@
 // rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
 // value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
-// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_* (the set form rdv_ppo_mlp_set_* among them), rdv_ppo_set_adam_step, rdv_policy_get_block, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
+// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_* (the set form rdv_ppo_mlp_set_* among them), rdv_lstm_ppo_*, rdv_ppo_set_adam_step, rdv_policy_get_block, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
-// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch, ppo_adam_launch), so an edit to an argument check recompiles no kernel.
+// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch, lstm_ppo_launch, ppo_adam_launch), so an edit to an argument check recompiles no kernel.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
@@ -11,6 +11,7 @@
 #include "rdv_advantages.h"
 #include "rdv_ppo.h"
 #include "rdv_ppo_mlp.h"
+#include "rdv_ppo_lstm.h"
 #include "rdv_ppo_adam.h"
 #include "rdv_host.h"
 
@@ -783,6 +784,98 @@ int rdv_ppo_mlp_loss_grad(rdv_policy actor, rdv_policy critic, const RdvPpoRows*
                     rows->obs, rows->actions, rows->old_log_prob, rows->advantages, rows->returns, rows->indices, n,
                     ppo_coefs(clip_range, ent_coef, vf_coef), static_cast<float*>(workspace), out->actor_grad, out->critic_grad, out->scalars, out->log_prob, out->values};
   ppo_mlp_launch(a, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- recurrent PPO minibatch gradients (csrc/rdv_ppo_lstm.h): a stand-alone recurrent actor and critic, whole env columns, back through time
+int rdv_lstm_ppo_spec_check(const RdvLstmSpec* actor_spec, const RdvLstmSpec* critic_spec) {
+  const char* who = "rdv_lstm_ppo_spec_check";
+  if (!actor_spec || !critic_spec) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: null %s", who, !actor_spec ? "actor_spec" : "critic_spec");
+  const struct { const RdvLstmSpec* s; const char* name; } nets[] = {{actor_spec, "actor"}, {critic_spec, "critic"}};
+  for (const auto& a : nets)
+    if (int rc = rdv_lstm_spec_check(a.s)) {
+      const std::string why = rdv_last_error();
+      return fail(rc, "%s: %s: %s", who, a.name, why.c_str());
+    }
+  if (actor_spec->hidden_size != critic_spec->hidden_size)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the actor's LSTM has %d units, the critic's %d: one hidden_size for both is served", who,
+                actor_spec->hidden_size, critic_spec->hidden_size);
+  return RDV_OK;
+}
+int64_t rdv_lstm_ppo_grad_floats(const RdvLstmSpec* spec, int is_actor) {
+  if (rdv_lstm_spec_check(spec) != RDV_OK) return -1;
+  LstmPpoNet n;
+  lstm_ppo_net(spec->hidden_size, spec->trunk, is_actor != 0, n);
+  return n.grad_floats;
+}
+static int64_t lstm_ppo_bytes(int H, const RdvMlpSpec& actor_trunk, const RdvMlpSpec& critic_trunk, int64_t n_steps, int64_t n_seq) {
+  LstmPpoNet a, c;
+  lstm_ppo_net(H, actor_trunk, true, a);
+  lstm_ppo_net(H, critic_trunk, false, c);
+  LstmPpoWs w;
+  lstm_ppo_workspace(a, c, n_steps, n_seq, w);
+  return w.total * (int64_t)sizeof(float);
+}
+int64_t rdv_lstm_ppo_workspace_bytes(const RdvLstmSpec* actor_spec, const RdvLstmSpec* critic_spec, int64_t n_steps, int64_t n_seq) {
+  if (n_steps <= 0 || n_seq <= 0 || rdv_lstm_ppo_spec_check(actor_spec, critic_spec) != RDV_OK) return -1;
+  return lstm_ppo_bytes(actor_spec->hidden_size, actor_spec->trunk, critic_spec->trunk, n_steps, n_seq);
+}
+static bool g_lstm_ppo_lds_raised[64];
+
+int rdv_lstm_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvLstmPpoRows* rows, double clip_range, double ent_coef, double vf_coef,
+                           void* workspace, int64_t workspace_bytes, const RdvLstmPpoOut* out, void* stream) {
+  const char* who = "rdv_lstm_ppo_loss_grad";
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"}, {rows->advantages, "rows->advantages"},
+      {rows->returns, "rows->returns"}, {rows->done, "rows->done"}, {rows->actor_h0, "rows->actor_h0"}, {rows->actor_c0, "rows->actor_c0"},
+      {rows->critic_h0, "rows->critic_h0"}, {rows->critic_c0, "rows->critic_c0"}, {out->actor_grad, "out->actor_grad"},
+      {out->critic_grad, "out->critic_grad"}, {out->scalars, "out->scalars"}, {workspace, "workspace"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
+  if (rows->n_envs <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_envs must be positive (got %lld)", who, (long long)rows->n_envs);
+  if (rows->n_steps <= 0 || rows->n_steps > (1 << 20))
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_steps must be in 1..2^20 (got %lld)", who, (long long)rows->n_steps);
+  if (rows->n_seq <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_seq must be positive (got %lld)", who, (long long)rows->n_seq);
+  if (!rows->envs && rows->n_seq > rows->n_envs)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_seq = %lld exceeds rows->n_envs = %lld and rows->envs is null", who, (long long)rows->n_seq, (long long)rows->n_envs);
+  if (rows->n_steps * rows->n_seq > (int64_t)1 << 31)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_steps x rows->n_seq = %lld rows: at most 2^31 in one call", who, (long long)(rows->n_steps * rows->n_seq));
+  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
+  RDV_CHECK_POLICY(actor);
+  RDV_CHECK_POLICY(critic);
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor, "actor"}, {critic, "critic"}};
+  for (const auto& a : nets) {
+    if (!a.p->lstm_hidden)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is not a recurrent policy (rdv_lstm_policy_create / rdv_lstm_critic_create): rdv_ppo_mlp_loss_grad serves it", who, a.name);
+    if (a.p->n_members > 1)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the %s handle is a recurrent set of %d members: its gradients are not built", who, a.name, a.p->n_members);
+  }
+  if (actor->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor is a critic handle (rdv_lstm_critic_create): actor and critic are swapped", who);
+  if (critic->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic is an actor handle (rdv_lstm_policy_create): actor and critic are swapped", who);
+  if (actor->lstm_hidden != critic->lstm_hidden)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the actor's LSTM has %d units, the critic's %d: one hidden_size for both is served", who, actor->lstm_hidden, critic->lstm_hidden);
+  if (actor->device != critic->device) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor on device %d, critic on device %d", who, actor->device, critic->device);
+  const int64_t need = lstm_ppo_bytes(actor->lstm_hidden, actor->spec, critic->spec, rows->n_steps, rows->n_seq);
+  if (workspace_bytes < need)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, n_steps = %lld, n_seq = %lld and these specs need %lld (rdv_lstm_ppo_workspace_bytes)", who,
+                (long long)workspace_bytes, (long long)rows->n_steps, (long long)rows->n_seq, (long long)need);
+  DeviceGuard guard(actor->device);
+  if (int rc = raise_ppo_lds_limit(lstm_ppo_raise_lds_limit, g_lstm_ppo_lds_raised, actor->device)) return rc;
+  LstmPpoLaunch a = {};
+  a.actor_block = actor->weights; a.critic_block = critic->weights;
+  a.actor_act = actor->spec.activation; a.critic_act = critic->spec.activation;
+  lstm_ppo_net(actor->lstm_hidden, actor->spec, true, a.actor);
+  lstm_ppo_net(critic->lstm_hidden, critic->spec, false, a.critic);
+  a.obs = rows->obs; a.actions = rows->actions; a.old_log_prob = rows->old_log_prob; a.advantages = rows->advantages; a.returns = rows->returns;
+  a.done = rows->done; a.actor_h0 = rows->actor_h0; a.actor_c0 = rows->actor_c0; a.critic_h0 = rows->critic_h0; a.critic_c0 = rows->critic_c0;
+  a.envs = rows->envs; a.n_envs = rows->n_envs; a.n_steps = rows->n_steps; a.n_seq = rows->n_seq;
+  a.k = ppo_coefs(clip_range, ent_coef, vf_coef);
+  a.workspace = static_cast<float*>(workspace);
+  a.actor_grad = out->actor_grad; a.critic_grad = out->critic_grad; a.scalars = out->scalars; a.log_prob = out->log_prob; a.values = out->values;
+  lstm_ppo_launch(a, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }

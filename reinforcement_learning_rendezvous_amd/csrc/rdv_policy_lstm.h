@@ -151,7 +151,6 @@ struct LstmSetBlocks {
 void lstm_launch_reset(float* h, float* c, const uint8_t* mask, int64_t n, int H, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------------------------- device
-#ifdef RDV_LSTM_KERNELS   // (rdv_policy_lstm.hip alone takes the kernels; rdv_hip.hip takes the packing and the launches above)
 // The B fragments (two fp16 terms) of one k-step of h for this lane's env: 8 floats of its state row (nullptr: a row beyond n, or an
 // episode start — zeros), times 2^10, clamped to +-63; `keep` receives the 8 floats as read (the trunk kernel commits them).
 __device__ __forceinline__ void lstm_h_frag(const float* row8, f16x8 (&b)[2], pol_f4 (&keep)[2]) {
@@ -168,6 +167,7 @@ __device__ __forceinline__ void lstm_h_frag(const float* row8, f16x8 (&b)[2], po
   split2(x, b);
 }
 
+#ifdef RDV_LSTM_KERNELS   // (rdv_policy_lstm.hip alone takes the kernels; the other units take the packing, the launches and lstm_h_frag)
 // The set forms of the two kernels are the same templates with ONE more argument, a LstmSetBlocks: lstm_cell_kernel<H, LstmSetBlocks> and
 // lstm_trunk_kernel<ACT, CRITIC, LstmSetBlocks>.  A workgroup owns 256 consecutive rows, which never span two members (every size but the
 // last is a multiple of 256), and reads its member's block at W + tile_member[blockIdx.x] * block_floats: one wave-uniform load more, no

@@ -72,16 +72,17 @@ constexpr int ppo_mlp_waves(const RdvMlpSpec& spec) {
 inline int ppo_mlp_lds_bytes(const PpoMlpTable& t) { return (t.block_floats + t.waves * kPpoWaveFloats) * 4; }
 
 // (constexpr: rdv_ppo_adam.hip takes the default spec's table at compile time)
-constexpr void ppo_mlp_table(const RdvMlpSpec& spec, bool actor, PpoMlpTable& t) {
+// in0: the width of layer 0's input — the 17 observations, or H for the trunk of a recurrent policy (rdv_ppo_lstm.h: H / 16 k-steps)
+constexpr void ppo_mlp_table(const RdvMlpSpec& spec, bool actor, PpoMlpTable& t, int in0 = kPolIn) {
   const int L = spec.n_hidden, out_dim = actor ? kPolOut : 1;
   t = PpoMlpTable{};
   t.L = L; t.waves = ppo_mlp_waves(spec); t.block_floats = ppo_mlp_block_floats(spec);
   int at = 0;
   for (int l = 0; l <= L; ++l) {
-    t.in_w[l] = l == 0 ? kPolIn : spec.hidden[l - 1];
+    t.in_w[l] = l == 0 ? in0 : spec.hidden[l - 1];
     t.out_w[l] = l < L ? spec.hidden[l] : out_dim;
     t.mt[l] = l < L ? mlp_tiles(t.out_w[l]) : 1;
-    t.ks[l] = l == 0 ? 2 : mlp_ksteps(t.in_w[l]);
+    t.ks[l] = l == 0 ? (in0 == kPolIn ? 2 : in0 / 16) : mlp_ksteps(t.in_w[l]);
     t.w_off[l] = at; at += t.out_w[l] * t.in_w[l];
     t.b_off[l] = at; at += t.out_w[l];
   }
@@ -152,5 +153,129 @@ struct PpoMlpSetLaunch {
 __attribute__((visibility("hidden"))) hipError_t ppo_mlp_raise_lds_limit();   // the plain and the set instantiations
 __attribute__((visibility("hidden"))) void ppo_mlp_launch(const PpoMlpLaunch& a, hipStream_t s);
 __attribute__((visibility("hidden"))) void ppo_mlp_set_launch(const PpoMlpSetLaunch& a, hipStream_t s);
+// launch 1 alone (the transposed fragments of layers 1 .. L of two blocks -> workspace, 2 kPpoMlpBwdFloats floats): rdv_ppo_lstm.hip's trunks
+__attribute__((visibility("hidden"))) void ppo_mlp_launch_transpose(const float* actor_block, const float* critic_block, float* workspace, hipStream_t s);
+
+
+// ---------------------------------------------------------------------------------------------------------------- device
+// The steps of a net kernel that do not depend on what layer 0 reads: the kept forward layers and one backward step.  rdv_ppo_mlp.hip
+// (layer 0 over the observation rows) and rdv_ppo_lstm.hip (the trunk of a recurrent policy: layer 0 over h_t) both take them.
+// mlp_hidden with the activations of its MT tiles kept
+template <int ACT, int MT, int KS>
+__device__ __forceinline__ void mlp_hidden_keep(const float* wf, const float* zerop, int frag0, const float* biasp, float k, int lane, f16x8 (&x)[4][2],
+                                                float (&hs)[2][16]) {
+  f16x8 xin[KS][2];
+#pragma unroll
+  for (int ks = 0; ks < KS; ++ks) { xin[ks][0] = x[ks][0]; xin[ks][1] = x[ks][1]; }
+  f32x16 d[MT];
+  layer<MT, KS>(wf, frag0, zerop, xin, lane, d);
+#pragma unroll
+  for (int mt = 0; mt < MT; ++mt) {
+    mlp_add_bias(d[mt], biasp + (mt * 2 + (lane >> 5)) * 16);
+    ppo_activate_keep<ACT>(d[mt], k, x[2 * mt], x[2 * mt + 1], hs[mt]);
+  }
+}
+// hidden layers `from` .. `upto` - 1 of the block at `w` on x (the B fragments of layer `from`'s input): x <- the B fragments of h_upto,
+// hs <- h_upto (times 2^10) in accumulator order
+template <int ACT>
+__device__ __forceinline__ void mlp_layers_keep(const float* w, const int32_t* __restrict__ H, int lane, int from, int upto, f16x8 (&x)[4][2],
+                                                float (&hs)[2][16]) {
+  const float* wf = w + kMlpHdr;
+  const float* zerop = w + kMlpZero;
+#pragma nounroll
+  for (int l = from; l < upto; ++l) {
+    const int32_t* rec = H + kMlpRec + kMlpRecStride * l;
+    const int frag0 = rec[0];
+    const float* biasp = w + rec[1];
+    const float k = mlp_act_const<ACT>(__int_as_float(rec[4]));
+    switch (rec[2] * 8 + rec[3]) {
+      case 8 + 1: mlp_hidden_keep<ACT, 1, 1>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 8 + 2: mlp_hidden_keep<ACT, 1, 2>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 8 + 4: mlp_hidden_keep<ACT, 1, 4>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 16 + 1: mlp_hidden_keep<ACT, 2, 1>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      case 16 + 2: mlp_hidden_keep<ACT, 2, 2>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+      default: mlp_hidden_keep<ACT, 2, 4>(wf, zerop, frag0, biasp, k, lane, x, hs); break;
+    }
+  }
+}
+// mlp_means up to hidden layer `upto` (1 .. L): x <- the B fragments of h_upto, hs <- h_upto (times 2^10) in accumulator order
+template <int ACT>
+__device__ __forceinline__ void mlp_forward_keep(const float* w, const int32_t* __restrict__ H, const float* rows, int lane, int upto, f16x8 (&x)[4][2],
+                                                 float (&hs)[2][16]) {
+  {
+    f16x8 x0[2][2];
+    actor_inputs(rows, lane, x0);
+#pragma unroll
+    for (int q = 0; q < 2; ++q) { x[0][q] = x0[0][q]; x[1][q] = x0[1][q]; x[2][q] = (f16x8)(0); x[3][q] = (f16x8)(0); }
+  }
+  mlp_layers_keep<ACT>(w, H, lane, 0, upto, x, hs);
+}
+
+// The derivative of the activation from the forward's own activation (hs = h 2^10): tanh 1 - h^2; sigmoid h (1 - h); ReLU 1 where
+// 0 < h < 63 — PyTorch's 0 at the kink, and 0 where the kernel's [0, 63] cap acted.  A NaN activation gives 0 for the ReLU; the error it
+// multiplies is a NaN already (the NaN reached the head), and NaN x 0 stays NaN.
+template <int ACT>
+__device__ __forceinline__ float mlp_act_derivative(float hs) {
+  constexpr float one = (float)(1 << kPolXShift), inv = 1.0f / one;
+  if (ACT == RDV_ACT_RELU) return (hs > 0.0f && hs < 63.0f * one) ? 1.0f : 0.0f;
+  const float hv = hs * inv;
+  if (ACT == RDV_ACT_TANH) return 1.0f - hv * hv;
+  return hv * (1.0f - hv);
+}
+
+// One backward step, layer l >= 1 (l == L: the head), MTh tiles of h_l, KSd k-steps and MTd tiles of delta_l (KSd = 4 <=> MTd = 2):
+//   dl (delta_l times n, in) is scaled by the wave's S;  pre = W_l^T dl (the forward's `layer` on the transposed fragments);
+//   delta_{l-1} = pre o act'(h_l) 2^-s_l / S;  dW_l, db_l (the head of an actor: d log_std from tile rows 8..13) -> the workgroup's row;
+//   dl <- delta_{l-1}.
+template <int ACT, bool ACTOR, int MTh, int KSd>
+__device__ __forceinline__ void backward_step(const PpoMlpTable& T, int l, const float* bwd, float inv_acc, float (&dl)[2][16], const float (&hs)[2][16],
+                                              float* wave_tiles, const float* tiles0, int nw, int lane, float* part) {
+  constexpr int MTd = KSd == 4 ? 2 : 1;
+  constexpr float xs = (float)(1 << kPolXShift), inv_xs = 1.0f / xs;
+  const bool head = l == T.L;
+  float S, invS;
+  wave_scale(MTd == 2 ? fmaxf(tile_max(dl[0]), tile_max(dl[1])) : tile_max(dl[0]), S, invS);
+#pragma unroll
+  for (int mt = 0; mt < MTd; ++mt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dl[mt][e] *= S;
+  float nd[MTh][16];
+  {
+    f16x8 b[KSd][2];
+    if constexpr (KSd == 1) {
+      float x[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) x[j] = (head && j >= 4) ? 0.0f : dl[0][j];   // the head's d log_std terms stay out of the product
+      split2(x, b[0]);
+    } else {
+#pragma unroll
+      for (int s = 0; s < KSd; ++s) error_frags(dl[s >> 1], s & 1, b[s]);
+    }
+    f32x16 pre[MTh];
+    layer<MTh, KSd>(bwd, T.bfrag[l], bwd + kPpoMlpBwdZero, b, lane, pre);
+    const float un = inv_acc * xs * invS;                                      // 2^-s_l / S
+#pragma unroll
+    for (int mt = 0; mt < MTh; ++mt)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) nd[mt][e] = pre[mt][e] * mlp_act_derivative<ACT>(hs[mt][e]) * un;
+  }
+  {
+    _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
+#pragma unroll
+    for (int mt = 0; mt < MTh; ++mt) stage_tile(tb + mt * (2 * kPpoTile), hs[mt], lane);
+    const int w_off = T.w_off[l], b_off = T.b_off[l], in_w = T.in_w[l], out_w = T.out_w[l], ls_off = T.ls_off;
+    weight_grads<MTd, MTh, 0>(dl, wave_tiles, tiles0, nw, invS * inv_xs, lane, [&](int row, int col, float v) {
+      if (col >= 0) { if (row < out_w && col < in_w) part[w_off + row * in_w + col] = v; }
+      else if (col == -1) {
+        if (row < out_w) part[b_off + row] = v;
+        if (ACTOR && head && row >= 8 && row < 8 + kPolOut) part[ls_off + (row - 8)] = v;
+      }
+    });
+  }
+#pragma unroll
+  for (int mt = 0; mt < MTh; ++mt)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) dl[mt][e] = nd[mt][e];
+}
 
 }  // namespace rdv

@@ -259,7 +259,9 @@ class _LstmRows(_HipHandles):
     @torch.no_grad()
     def advantages(self, ro, gamma=0.99, gae_lambda=0.95, out=None):
         """``MlpPolicy.advantages`` for the recurrent critic: T committing critic steps in time order over ``ro["obs"]`` (episode starts:
-        the critic's pending flags, then ``ro["done"][t-1]``), one non-committing step on ``ro["last_obs"]`` with ``done[T-1]``, GAE."""
+        the critic's pending flags, then ``ro["done"][t-1]``), one non-committing step on ``ro["last_obs"]`` with ``done[T-1]``, GAE.
+        Also records ``ro["lstm_critic_state0"]``, the critic's ``(h, c)`` as step 0 sees it (``state_at_start("v")``), as ``rollout``
+        records the actor's ``lstm_state0``: ``ppo_sequence_grad`` starts from both."""
         from . import advantages as A
         obs = ro["obs"]
         if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
@@ -271,6 +273,9 @@ class _LstmRows(_HipHandles):
         A.check_tensor(ro["done"], "done", (T, n), torch.uint8, dev)
         A.check_tensor(ro["last_obs"], "last_obs", (n, 17), torch.float32, dev)
         A.check_discounts(gamma, gae_lambda)
+        if self.backend != "torch" and obs.is_cuda:
+            self._handle("v", dev)
+        ro["lstm_critic_state0"] = self.state_at_start("v", dev)
         src = out if out is not None else ro
         for name, shape in dict(values=(T, n), last_value=(n,), advantages=(T, n), returns=(T, n)).items():
             t = src.get(name)
@@ -482,6 +487,23 @@ class LstmPolicy(_LstmRows, torch.nn.Module):
         """Not offered for a recurrent policy: ``MlpPolicy.ppo_grad`` serves the feed-forward shipped actor and critic."""
         from . import ppo
         return ppo.ppo_grad(self, *args, **kwargs)
+
+    def ppo_sequence_grad(self, buf, envs=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True, state0=None,
+                          critic_state0=None):
+        """The PPO loss of one minibatch of whole env columns of a recurrent rollout and its gradients, back-propagated through time —
+        the body of sb3-contrib's ``RecurrentPPO.train()`` loop for a minibatch that falls on env boundaries (``clip_range_vf=None``).
+        ``buf``: what ``RendezvousBatch.collect(policy, T)`` returns.  ``envs``: a 1-d int64 tensor of columns (``ppo_sequence_minibatches``
+        yields them), None for all.  Each column starts from ``buf["lstm_state0"]`` / ``buf["lstm_critic_state0"]`` (``state0=`` /
+        ``critic_state0=`` override them: pairs ``(h, c)`` of [N, H]), a constant of the minibatch; ``done[t-1]`` resets the state in front
+        of step t and cuts the gradient there.  Advantages are normalised with SB3's expression over the T * B entries of the minibatch.
+        Fills ``.grad`` of every parameter — both LSTMs, both trunks, ``log_std`` — as views of two flat buffers the policy owns, and
+        returns the six scalars as 0-dim tensors plus ``log_prob`` and ``values`` [T, B] of the current networks.  CUDA rows: ONE call of
+        rdv_lstm_ppo_loss_grad (include/rdv.h "Recurrent PPO minibatch gradients"; hand-written MFMA kernels, 4 T + 8 launches on the
+        current stream, legal inside a stream capture; the policy's state and pending flags are untouched).  CPU rows or
+        ``backend="torch"``: float32 autograd through the modules over the T steps, with the same masking."""
+        from . import ppo
+        return ppo.ppo_sequence_grad(self, buf, envs, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
+                                     normalize_advantage=normalize_advantage, check=check, state0=state0, critic_state0=critic_state0)
 
     def update_weights(self, weights=None):
         """New weights for the modules (a dict with the constructor's keys; None: push the modules' current parameters) and for every

@@ -191,9 +191,10 @@ def _state(policy, dev, n, rows):
     return st
 
 
-def _bind_grads(policy, st, dev):
-    """``.grad`` of every parameter <- its piece of the flat buffers: a view when the parameter lives on ``dev``, a copy otherwise."""
-    for flat, params in zip((st["actor"], st["critic"]), _params(policy)):
+def _bind_grads(policy, st, dev, params=None):
+    """``.grad`` of every parameter <- its piece of the flat buffers: a view when the parameter lives on ``dev``, a copy otherwise.
+    ``params``: (actor list, critic list) in the buffers' order; None: ``_params(policy)``."""
+    for flat, params in zip((st["actor"], st["critic"]), params or _params(policy)):
         at = 0
         for p in params:
             piece = flat[at:at + p.numel()].view(p.shape)
@@ -304,6 +305,182 @@ def ppo_grad(policy, buf, indices=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.
     _bind_grads(policy, st, dev)
     s = st["scalars"].clone()
     return {name: s[k] for k, name in enumerate(SCALAR_NAMES)}
+
+
+# ---------------------------------------------------------------------------------------------------- the recurrent policy
+def ppo_sequence_minibatches(n_envs, envs_per_batch, generator=None, device=None):
+    """One epoch over the env columns of a recurrent rollout: a ``torch.randperm(n_envs)`` cut into consecutive pieces of
+    ``envs_per_batch`` columns (the last may be short) — what sb3-contrib's ``RecurrentRolloutBuffer`` yields when its split falls on env
+    boundaries.  Every column appears exactly once.  The tensors are marked as in range for ``n_envs``, so
+    ``LstmPolicy.ppo_sequence_grad`` does not check them again."""
+    n_envs, envs_per_batch = int(n_envs), int(envs_per_batch)
+    if n_envs <= 0 or envs_per_batch <= 0:
+        raise ValueError(f"ppo_sequence_minibatches: n_envs = {n_envs} and envs_per_batch = {envs_per_batch} must be positive")
+    if device is None:
+        device = generator.device if generator is not None else "cpu"
+    perm = torch.randperm(n_envs, generator=generator, device=device)
+    parts = list(torch.split(perm, envs_per_batch))
+    for p in parts:
+        p._rdv_ppo_envs = n_envs
+    return parts
+
+
+def _sequence_params(policy):
+    """The parameters of an ``LstmPolicy`` in the order of rdv_lstm_ppo_grad_floats: per net the LSTM's w_ih, w_hh, b_ih, b_hh, then the
+    trunk's layers, ``log_std`` last for the actor."""
+    from .policy_lstm import _LSTM_KEYS
+    actor, critic = _params(policy)
+    return ([getattr(policy.lstm_actor, k) for k in _LSTM_KEYS] + actor, [getattr(policy.lstm_critic, k) for k in _LSTM_KEYS] + critic)
+
+
+def _lstm_specs(policy):
+    from . import _native as N
+    from .policy import ACTIVATIONS
+    act = ACTIVATIONS[policy.activation][0]
+    return (N.LstmSpec.make(policy.lstm_hidden_size, policy.pi_arch, act), N.LstmSpec.make(policy.lstm_hidden_size, policy.vf_arch, act))
+
+
+def sequence_latents(lstm, obs, start, h0, c0):
+    """``h_t`` [T, B, H] of one ``torch.nn.LSTM`` layer stepped over ``obs`` [T, B, 17] from the constant ``(h0, c0)`` [B, H], the state
+    multiplied by ``1 - start[t]`` ([T, B], row 0 zeros: state0 is given as step 0 sees it) in front of step t."""
+    h, c, out = h0, c0, []
+    for t in range(obs.shape[0]):
+        keep = (1.0 - start[t])[:, None]
+        _, (h1, c1) = lstm(obs[t][None], ((h * keep)[None], (c * keep)[None]))
+        h, c = h1[0], c1[0]
+        out.append(h)
+    return torch.stack(out)
+
+
+def _sequence_state(policy, dev, T, B, N):
+    st = policy.__dict__.setdefault("_ppo_seq", {}).get(dev)
+    actor, critic = _sequence_params(policy)
+    if st is None:
+        st = dict(actor=torch.zeros(sum(p.numel() for p in actor), dtype=torch.float32, device=dev),
+                  critic=torch.zeros(sum(p.numel() for p in critic), dtype=torch.float32, device=dev),
+                  scalars=torch.zeros(8, dtype=torch.float32, device=dev), workspace=None, adv=None, need=0)
+        policy._ppo_seq[dev] = st
+    if T is not None:
+        from . import _native as Nat
+        a, c = _lstm_specs(policy)
+        need = int(Nat.lib().rdv_lstm_ppo_workspace_bytes(C.byref(a), C.byref(c), T, B))
+        if need < 0:
+            raise ValueError("ppo_sequence_grad: " + Nat.lib().rdv_last_error().decode("utf-8", "replace"))
+        if st["workspace"] is None or st["need"] < need:
+            st["workspace"] = torch.empty(need, dtype=torch.uint8, device=dev)
+            st["need"] = need
+        if st["adv"] is None or st["adv"].numel() < T * N:
+            st["adv"] = torch.zeros(T * N, dtype=torch.float32, device=dev)
+    return st
+
+
+def ppo_sequence_grad(policy, buf, envs=None, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True, state0=None,
+                      critic_state0=None):
+    """See ``LstmPolicy.ppo_sequence_grad``."""
+    from .policy_lstm import LstmPolicy
+    if not isinstance(policy, LstmPolicy):
+        raise TypeError(f"ppo_sequence_grad: a {type(policy).__name__} is not offered: it serves one LstmPolicy (MlpPolicy has ppo_grad; "
+                        "an LstmPolicySet keeps SB3 / PyTorch for the update)")
+    _check_coefficients("ppo_sequence_grad", clip_range, ent_coef, vf_coef)
+    obs = buf.get("obs")
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
+        raise ValueError(f"ppo_sequence_grad: buf['obs']: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
+    T, N, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+    cols = {}
+    for name, shape, dtype in (("obs", (T, N, 17), torch.float32), ("actions", (T, N, 6), torch.float32), ("log_prob", (T, N), torch.float32),
+                               ("advantages", (T, N), torch.float32), ("returns", (T, N), torch.float32), ("done", (T, N), torch.uint8)):
+        t = buf.get(name)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"ppo_sequence_grad: buf[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev} "
+                             "(what RendezvousBatch.collect returns)")
+        cols[name] = t
+    H = policy.lstm_hidden_size
+    states = []
+    for given, key, kw in ((state0, "lstm_state0", "state0"), (critic_state0, "lstm_critic_state0", "critic_state0")):
+        pair = given if given is not None else buf.get(key)
+        if pair is None:
+            raise ValueError(f"ppo_sequence_grad: buf holds no {key!r} (RendezvousBatch.collect records it) and {kw}= is not given")
+        pair = tuple(pair)
+        if len(pair) != 2 or any(not isinstance(x, torch.Tensor) or tuple(x.shape) != (N, H) for x in pair):
+            raise ValueError(f"ppo_sequence_grad: {kw} must be a pair (h, c) of [{N}, {H}] tensors")
+        states.append(tuple(x.to(dev, torch.float32).contiguous() for x in pair))
+    if envs is None:
+        B = N
+    else:
+        if not isinstance(envs, torch.Tensor) or envs.dtype != torch.int64 or envs.dim() != 1 or envs.device != dev or envs.numel() == 0:
+            raise ValueError(f"ppo_sequence_grad: envs must be a non-empty 1-d int64 tensor on {dev}")
+        envs = envs.contiguous()
+        B = int(envs.numel())
+        if check and getattr(envs, "_rdv_ppo_envs", None) != N:
+            lo, hi = (int(x) for x in torch.aminmax(envs))
+            if lo < 0 or hi >= N:
+                raise IndexError(f"ppo_sequence_grad: envs span [{lo}, {hi}], the rollout has columns 0..{N - 1}")
+    take = (lambda t: t) if envs is None else (lambda t: t[:, envs])
+    adv = take(cols["advantages"])
+    if normalize_advantage and T * B > 1:
+        adv = normalize_advantages(adv)
+    hip = policy.backend != "torch" and dev.type == "cuda"
+    actor, critic = _sequence_params(policy)
+
+    if not hip:
+        pdev = policy.log_std.device
+        st = _sequence_state(policy, pdev, None, None, None)
+        params = actor + critic
+        flags = [p.requires_grad for p in params]
+        try:
+            for p in params:
+                p.requires_grad_(True)
+            with torch.enable_grad():
+                o = take(cols["obs"]).to(pdev)
+                start = torch.cat([torch.zeros_like(cols["done"][:1]), cols["done"][:-1]], dim=0)
+                start = take(start).to(pdev, torch.float32)
+                pick = (lambda x: x) if envs is None else (lambda x: x[envs])
+                lat_a = sequence_latents(policy.lstm_actor, o, start, pick(states[0][0]).to(pdev), pick(states[0][1]).to(pdev))
+                lat_c = sequence_latents(policy.lstm_critic, o, start, pick(states[1][0]).to(pdev), pick(states[1][1]).to(pdev))
+                mean = policy._trunk_torch("l", lat_a).reshape(T * B, 6)
+                values = policy._trunk_torch("v", lat_c).reshape(T * B)
+                flat = lambda t: take(t).to(pdev).reshape((T * B,) + tuple(t.shape[2:]))
+                loss, scalars, log_prob = ppo_loss_terms(mean, policy.log_std, values, flat(cols["actions"]), flat(cols["log_prob"]),
+                                                         adv.to(pdev).reshape(T * B), flat(cols["returns"]), float(clip_range), float(ent_coef), float(vf_coef))
+                grads = torch.autograd.grad(loss, params)
+        finally:
+            for p, f in zip(params, flags):
+                p.requires_grad_(f)
+        with torch.no_grad():
+            torch.cat([g.reshape(-1) for g in grads[:len(actor)]], out=st["actor"])
+            torch.cat([g.reshape(-1) for g in grads[len(actor):]], out=st["critic"])
+        _bind_grads(policy, st, pdev, (actor, critic))
+        scalars["log_prob"] = log_prob.detach().reshape(T, B)
+        scalars["values"] = values.detach().reshape(T, B)
+        return scalars
+
+    from . import _native as Nat
+    st = _sequence_state(policy, dev, T, B, N)
+    with torch.no_grad():
+        if normalize_advantage and T * B > 1:
+            # the normalised advantages go back to their columns of a [T, N] array the policy owns (a duplicate column writes the same
+            # values twice): the C call reads every column through the same list
+            adv_col = st["adv"][:T * N].view(T, N)
+            if envs is None:
+                adv_col.copy_(adv)
+            else:
+                adv_col.index_copy_(1, envs, adv)
+        else:
+            adv_col = cols["advantages"]
+    log_prob = torch.empty((T, B), dtype=torch.float32, device=dev)
+    values = torch.empty((T, B), dtype=torch.float32, device=dev)
+    r = Nat.LstmPpoRows(cols["obs"].data_ptr(), cols["actions"].data_ptr(), cols["log_prob"].data_ptr(), adv_col.data_ptr(), cols["returns"].data_ptr(),
+                        cols["done"].data_ptr(), states[0][0].data_ptr(), states[0][1].data_ptr(), states[1][0].data_ptr(), states[1][1].data_ptr(),
+                        envs.data_ptr() if envs is not None else None, N, T, B)
+    o = Nat.LstmPpoOut(st["actor"].data_ptr(), st["critic"].data_ptr(), st["scalars"].data_ptr(), log_prob.data_ptr(), values.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    Nat.check(Nat.lib().rdv_lstm_ppo_loss_grad(policy._handle("l", dev), policy._handle("v", dev), C.byref(r), float(clip_range), float(ent_coef),
+                                               float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    _bind_grads(policy, st, dev, (actor, critic))
+    s = st["scalars"].clone()
+    res = {name: s[k] for k, name in enumerate(SCALAR_NAMES)}
+    res["log_prob"], res["values"] = log_prob, values
+    return res
 
 
 def _set_grad_floats(pset, route):
