@@ -1153,8 +1153,9 @@ int rdv_lstm_set_member_weights(rdv_policy p, int32_t member, const float* w_ih_
  *     recurrent set of more than one member, actor and critic swapped, different hidden sizes, different devices, a short workspace.
  *     A refused call enqueues nothing and leaves the handles as they were.
  *   - The existing rdv_ppo_* calls keep refusing a recurrent handle.
- * Not in this call: recurrent sets (LstmPolicySet.ppo_grads keeps refusing), a device Adam step for recurrent nets (clip, optimiser and
- * rdv_lstm_set_weights stay the caller's), minibatches that start mid-column from stored states, clip_range_vf, one persistent launch.
+ * Recurrent sets have a call of their own, rdv_lstm_ppo_set_loss_grad below (this call keeps refusing a set of more than one member).
+ * Not in this call: a device Adam step for recurrent nets (clip, optimiser and rdv_lstm_set_weights stay the caller's), minibatches that
+ * start mid-column from stored states, clip_range_vf, one persistent launch.
  */
 typedef struct RdvLstmPpoRows {      /* device pointers: the [T,N,...] columns of a recurrent rollout */
   const float*   obs;                /* [T,N,17]                                            */
@@ -1182,6 +1183,57 @@ int64_t rdv_lstm_ppo_grad_floats(const RdvLstmSpec* spec_host, int is_actor);
 int64_t rdv_lstm_ppo_workspace_bytes(const RdvLstmSpec* actor_spec_host, const RdvLstmSpec* critic_spec_host, int64_t n_steps, int64_t n_seq);
 int rdv_lstm_ppo_loss_grad(rdv_policy actor, rdv_policy critic, const RdvLstmPpoRows* rows, double clip_range, double ent_coef,
                            double vf_coef, void* workspace, int64_t workspace_bytes, const RdvLstmPpoOut* out, void* stream);
+
+/*
+ * Recurrent PPO minibatch gradients for recurrent sets (added within ABI 5: additive exports): the call above for every member of a
+ * recurrent set (rdv_lstm_policy_set_create / rdv_lstm_critic_set_create) at once — the members' minibatches of whole env columns share
+ * the launches (csrc/rdv_ppo_lstm.h, "the set form").
+ *
+ * Specification, by equality (the rule of rdv_ppo_set_loss_grad and rdv_ppo_mlp_set_loss_grad): every output of member g — both flat
+ * gradients, the eight scalars, log_prob, values — is bit for bit what rdv_lstm_ppo_loss_grad writes for stand-alone handles holding
+ * member g's weights, the same [T, N] columns and state0 arrays, envs + off_g, n_seq = counts[g] and the same coefficients, off_g the sum
+ * of the earlier counts.  Each member keeps the stand-alone call's partition into waves and workgroups, its wave_scale values, its
+ * lstm_ppo_splits(T B_g) and its wave-order and index-order sums; accuracy against fp64 is the stand-alone call's.
+ *
+ * rdv_lstm_ppo_set_workspace_bytes (host only): the sum of rdv_lstm_ppo_workspace_bytes(actor_spec, critic_spec, n_steps, counts_host[g])
+ *   over the positive counts; -1 for a bad pair of specs, n_steps <= 0, n_members outside 1..64, null counts, a negative count or no
+ *   positive count.  Monotone in every count; a multiple of 16.
+ * rdv_lstm_ppo_set_loss_grad:
+ *   actor_set, critic_set: recurrent sets of the same member count P <= 64, the same hidden size and the same device; a plain recurrent
+ *     handle pair is a set of one member.  The sets' row ranges play no part: membership of a column is given by the counts alone.
+ *   counts_host [P] (host): counts_host[g] >= 0 is B_g, member g's number of columns; at least one is positive.  Nothing of a member
+ *     with count 0 is written: no gradient row, no scalars, no log_prob, no values.
+ *   rows: RdvLstmPpoRows as above, but rows->envs is REQUIRED — a device array of sum B_g entries, member g's at off_g — and
+ *     rows->n_seq must equal sum B_g.  The state0 arrays are the set's [N, H], shared by all members.
+ *   RdvLstmPpoSetOut: actor_grad [P, Ga], critic_grad [P, Gc] (Ga, Gc: rdv_lstm_ppo_grad_floats; the rows lie back to back), scalars
+ *     [P, 8]; log_prob and values (nullable): member g's [T, B_g] block is contiguous at float offset T off_g.
+ * The contract is the stand-alone call's:
+ *   - Enqueue only: no allocation, no synchronisation, no host-to-device copy (count, off and the workspace start of every member
+ *     travel by value in the kernel arguments: hence the cap of 64); legal inside a stream capture.  4 T + 8 launches WHATEVER P: each is
+ *     the stand-alone launch over the widest member's grid times the members.
+ *   - Deterministic, no floating-point atomic, the same bits eager or replayed.
+ *   - Handles: state and pending flags neither read nor written; weights as of stream order, so a call behind
+ *     rdv_lstm_set_member_weights differentiates that member's new block and no other member's bits move.
+ *   - One clip_range / ent_coef / vf_coef for all members.
+ *   - Order of checks.  Host only, the message naming the argument, RDV_ERR_INVALID_ARGUMENT: a null rows, out, counts_host or required
+ *     pointer (rows->envs among them; everything but out->log_prob, out->values), a negative count or none positive, rows->n_seq != the
+ *     sum of the counts, n_envs or n_steps <= 0, more than 2^31 rows in a member, a misaligned workspace, the coefficients.  (counts_host
+ *     is read for the actor set's members, at most 64; one entry with an invalid handle.)  Then RDV_ERR_BAD_HANDLE.  Then
+ *     RDV_ERR_INVALID_ARGUMENT for a handle that is not recurrent, swapped sets, different member counts, more than 64 members,
+ *     different hidden sizes, different devices, a short workspace.  A refused call enqueues nothing.
+ */
+typedef struct RdvLstmPpoSetOut {    /* device pointers */
+  float* actor_grad;                 /* [P, rdv_lstm_ppo_grad_floats(actor spec, 1)]  required */
+  float* critic_grad;                /* [P, rdv_lstm_ppo_grad_floats(critic spec, 0)] required */
+  float* scalars;                    /* [P, 8]       required */
+  float* log_prob;                   /* [T sum B_g]  nullable: member g's [T, B_g] at T off_g */
+  float* values;                     /* [T sum B_g]  nullable */
+} RdvLstmPpoSetOut;
+int64_t rdv_lstm_ppo_set_workspace_bytes(const RdvLstmSpec* actor_spec_host, const RdvLstmSpec* critic_spec_host, int64_t n_steps,
+                                         int32_t n_members, const int64_t* counts_host);
+int rdv_lstm_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvLstmPpoRows* rows, const int64_t* counts_host,
+                               double clip_range, double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes,
+                               const RdvLstmPpoSetOut* out, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ behind the reference's Gym / SB3-VecEnv API.  See DESIGN.md and include/rdv.h.
 from .params import EnvParams, make_params, params_from_config  # noqa: F401
 from ._native import RdvError, build  # noqa: F401
 
-__all__ = ["EnvParams", "make_params", "params_from_config", "RdvError", "build", "RendezvousBatch", "RendezvousVecEnv", "RendezvousEnv", "MlpPolicy", "PolicySet", "LstmPolicy", "LstmPolicySet", "gae", "ppo_minibatches", "ppo_grad", "ppo_set_minibatches", "ppo_sequence_minibatches"]
+__all__ = ["EnvParams", "make_params", "params_from_config", "RdvError", "build", "RendezvousBatch", "RendezvousVecEnv", "RendezvousEnv", "MlpPolicy", "PolicySet", "LstmPolicy", "LstmPolicySet", "gae", "ppo_minibatches", "ppo_grad", "ppo_set_minibatches", "ppo_sequence_minibatches", "ppo_sequence_set_minibatches"]
 
 
 def __getattr__(name):   # torch is imported only when the device classes are used
@@ -34,7 +34,7 @@ def __getattr__(name):   # torch is imported only when the device classes are us
     if name == "gae":
         from .advantages import gae
         return gae
-    if name in ("ppo_minibatches", "ppo_grad", "ppo_set_minibatches", "ppo_sequence_minibatches"):
+    if name in ("ppo_minibatches", "ppo_grad", "ppo_set_minibatches", "ppo_sequence_minibatches", "ppo_sequence_set_minibatches"):
         from . import ppo
         return getattr(ppo, name)
     raise AttributeError(name)

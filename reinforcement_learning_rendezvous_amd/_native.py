@@ -55,7 +55,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # gradient clip, Adam and weight repack for policy sets of every MLP architecture (added within ABI 5)
            "rdv_ppo_mlp_set_adam_step",
            # recurrent PPO minibatch gradients (added within ABI 5)
-           "rdv_lstm_ppo_spec_check", "rdv_lstm_ppo_grad_floats", "rdv_lstm_ppo_workspace_bytes", "rdv_lstm_ppo_loss_grad"]
+           "rdv_lstm_ppo_spec_check", "rdv_lstm_ppo_grad_floats", "rdv_lstm_ppo_workspace_bytes", "rdv_lstm_ppo_loss_grad",
+           # recurrent PPO minibatch gradients for recurrent sets (added within ABI 5)
+           "rdv_lstm_ppo_set_workspace_bytes", "rdv_lstm_ppo_set_loss_grad"]
 
 
 class RdvError(RuntimeError):
@@ -124,6 +126,13 @@ class LstmPpoRows(C.Structure):
 
 class LstmPpoOut(C.Structure):
     """RdvLstmPpoOut: device pointers of what rdv_lstm_ppo_loss_grad writes (log_prob and values [T, n_seq] nullable)"""
+    _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
+                ("values", C.c_void_p)]
+
+
+class LstmPpoSetOut(C.Structure):
+    """RdvLstmPpoSetOut: device pointers of what rdv_lstm_ppo_set_loss_grad writes: [P,Ga], [P,Gc], [P,8]; log_prob and values: member g's
+    [T, B_g] block at float T off_g, nullable"""
     _fields_ = [("actor_grad", C.c_void_p), ("critic_grad", C.c_void_p), ("scalars", C.c_void_p), ("log_prob", C.c_void_p),
                 ("values", C.c_void_p)]
 
@@ -303,6 +312,9 @@ def lib():
         "rdv_lstm_ppo_grad_floats": (i64, [C.POINTER(LstmSpec), C.c_int]),
         "rdv_lstm_ppo_workspace_bytes": (i64, [C.POINTER(LstmSpec), C.POINTER(LstmSpec), i64, i64]),
         "rdv_lstm_ppo_loss_grad": (C.c_int, [vp, vp, C.POINTER(LstmPpoRows), C.c_double, C.c_double, C.c_double, vp, i64, C.POINTER(LstmPpoOut), vp]),
+        "rdv_lstm_ppo_set_workspace_bytes": (i64, [C.POINTER(LstmSpec), C.POINTER(LstmSpec), i64, C.c_int32, C.POINTER(i64)]),
+        "rdv_lstm_ppo_set_loss_grad": (C.c_int, [vp, vp, C.POINTER(LstmPpoRows), C.POINTER(i64), C.c_double, C.c_double, C.c_double, vp, i64,
+                                                 C.POINTER(LstmPpoSetOut), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

@@ -891,6 +891,85 @@ static bool ppo_counts_ok(int32_t n_members, const int64_t* counts_host) {
   }
   return any;
 }
+static int32_t capped_members(rdv_policy actor_set);
+static int check_set_members(const char* who, rdv_policy actor_set, rdv_policy critic_set);
+
+// ---- recurrent PPO minibatch gradients for recurrent sets (csrc/rdv_ppo_lstm.h, "the set form")
+int64_t rdv_lstm_ppo_set_workspace_bytes(const RdvLstmSpec* actor_spec, const RdvLstmSpec* critic_spec, int64_t n_steps, int32_t n_members,
+                                         const int64_t* counts_host) {
+  if (n_steps <= 0 || !ppo_counts_ok(n_members, counts_host) || rdv_lstm_ppo_spec_check(actor_spec, critic_spec) != RDV_OK) return -1;
+  // member by member what rdv_lstm_ppo_workspace_bytes answers for one: the sum rule
+  int64_t bytes = 0;
+  for (int32_t g = 0; g < n_members; ++g)
+    if (counts_host[g] > 0) bytes += lstm_ppo_bytes(actor_spec->hidden_size, actor_spec->trunk, critic_spec->trunk, n_steps, counts_host[g]);
+  return bytes;
+}
+
+int rdv_lstm_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvLstmPpoRows* rows, const int64_t* counts_host, double clip_range,
+                               double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes, const RdvLstmPpoSetOut* out, void* stream) {
+  const char* who = "rdv_lstm_ppo_set_loss_grad";
+  if (!rows) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows is null", who);
+  if (!out) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: out is null", who);
+  if (!counts_host) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host is null", who);
+  const struct { const void* p; const char* name; } ptrs[] = {
+      {rows->obs, "rows->obs"}, {rows->actions, "rows->actions"}, {rows->old_log_prob, "rows->old_log_prob"}, {rows->advantages, "rows->advantages"},
+      {rows->returns, "rows->returns"}, {rows->done, "rows->done"}, {rows->actor_h0, "rows->actor_h0"}, {rows->actor_c0, "rows->actor_c0"},
+      {rows->critic_h0, "rows->critic_h0"}, {rows->critic_c0, "rows->critic_c0"}, {rows->envs, "rows->envs"}, {out->actor_grad, "out->actor_grad"},
+      {out->critic_grad, "out->critic_grad"}, {out->scalars, "out->scalars"}, {workspace, "workspace"}};
+  for (const auto& a : ptrs) if (!a.p) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is null", who, a.name);
+  const int32_t P = capped_members(actor_set);
+  int64_t total = 0, most = 0;
+  for (int32_t g = 0; g < P; ++g) {
+    if (counts_host[g] < 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host[%d] = %lld is negative", who, g, (long long)counts_host[g]);
+    total = counts_host[g] > INT64_MAX - total ? INT64_MAX : total + counts_host[g];
+    if (counts_host[g] > most) most = counts_host[g];
+  }
+  if (total == 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: counts_host holds no positive count (%d member%s)", who, P, P == 1 ? "" : "s");
+  if (rows->n_seq != total)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_seq = %lld, counts_host sums to %lld", who, (long long)rows->n_seq, (long long)total);
+  if (rows->n_envs <= 0) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_envs must be positive (got %lld)", who, (long long)rows->n_envs);
+  if (rows->n_steps <= 0 || rows->n_steps > (1 << 20))
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_steps must be in 1..2^20 (got %lld)", who, (long long)rows->n_steps);
+  if (most > ((int64_t)1 << 31) / rows->n_steps)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: rows->n_steps = %lld x the largest count %lld: at most 2^31 rows in a member", who, (long long)rows->n_steps, (long long)most);
+  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  if (int rc = check_ppo_coefficients(who, clip_range, ent_coef, vf_coef)) return rc;
+  RDV_CHECK_POLICY(actor_set);
+  RDV_CHECK_POLICY(critic_set);
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};
+  for (const auto& a : nets)
+    if (!a.p->lstm_hidden)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not a recurrent policy or a recurrent set (rdv_lstm_policy_set_create / rdv_lstm_critic_set_create): rdv_ppo_mlp_set_loss_grad serves it", who, a.name);
+  if (actor_set->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set is a critic handle (rdv_lstm_critic_set_create): actor and critic are swapped", who);
+  if (critic_set->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic_set is an actor handle (rdv_lstm_policy_set_create): actor and critic are swapped", who);
+  if (int rc = check_set_members(who, actor_set, critic_set)) return rc;
+  if (actor_set->lstm_hidden != critic_set->lstm_hidden)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the actors' LSTM has %d units, the critics' %d: one hidden_size for both is served", who, actor_set->lstm_hidden, critic_set->lstm_hidden);
+  if (actor_set->device != critic_set->device)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set on device %d, critic_set on device %d", who, actor_set->device, critic_set->device);
+  LstmPpoSetLaunch L = {};
+  LstmPpoLaunch& a = L.a;
+  lstm_ppo_net(actor_set->lstm_hidden, actor_set->spec, true, a.actor);
+  lstm_ppo_net(critic_set->lstm_hidden, critic_set->spec, false, a.critic);
+  const int64_t need = lstm_ppo_set_table(a.actor, a.critic, rows->n_steps, P, counts_host, &L.table, &L.max_count);
+  if (workspace_bytes < need)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, n_steps = %lld, these counts and specs need %lld (rdv_lstm_ppo_set_workspace_bytes)", who,
+                (long long)workspace_bytes, (long long)rows->n_steps, (long long)need);
+  DeviceGuard guard(actor_set->device);
+  if (int rc = raise_ppo_lds_limit(lstm_ppo_raise_lds_limit, g_lstm_ppo_lds_raised, actor_set->device)) return rc;
+  a.actor_block = actor_set->weights; a.critic_block = critic_set->weights;
+  a.actor_act = actor_set->spec.activation; a.critic_act = critic_set->spec.activation;
+  a.obs = rows->obs; a.actions = rows->actions; a.old_log_prob = rows->old_log_prob; a.advantages = rows->advantages; a.returns = rows->returns;
+  a.done = rows->done; a.actor_h0 = rows->actor_h0; a.actor_c0 = rows->actor_c0; a.critic_h0 = rows->critic_h0; a.critic_c0 = rows->critic_c0;
+  a.envs = rows->envs; a.n_envs = rows->n_envs; a.n_steps = rows->n_steps; a.n_seq = rows->n_seq;
+  a.k = ppo_coefs(clip_range, ent_coef, vf_coef);
+  a.workspace = static_cast<float*>(workspace);
+  a.actor_grad = out->actor_grad; a.critic_grad = out->critic_grad; a.scalars = out->scalars; a.log_prob = out->log_prob; a.values = out->values;
+  L.n_members = P; L.actor_block_floats = actor_set->block_floats; L.critic_block_floats = critic_set->block_floats;
+  lstm_ppo_set_launch(L, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
 int64_t rdv_ppo_set_workspace_bytes(int32_t n_members, const int64_t* counts_host) {
   return ppo_counts_ok(n_members, counts_host) ? ppo_set_table(n_members, counts_host, nullptr) : -1;
 }

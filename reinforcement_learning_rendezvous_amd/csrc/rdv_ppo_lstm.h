@@ -35,7 +35,8 @@
 //      partial sums.  b_ih and b_hh get the same gradient.
 //   5. (once) lstm_ppo_finish_kernel: per gradient element the trunk rows in workgroup order or the cell rows in split order, divided by
 //      n; - ent_coef on d log_std; the scalars in double (ppo_finish_scalars).
-// Launches: 4 T + 8 (3 + 2 (T + 1 + T + 1) + 1), fixed by the specs, T and B.
+// Launches: 4 T + 8 (3 + 2 (T + 1 + T + 1) + 1), fixed by the specs, T and B.  The set form below (rdv_lstm_ppo_set_loss_grad): the same
+// 4 T + 8 whatever the number of members.
 //
 // Decisions:
 //   Kept or recomputed: the gate activations are KEPT.  Per row and net the workspace holds h, c (2 H floats), the gates (4 H, later da
@@ -83,41 +84,57 @@ inline void lstm_ppo_net(int H, const RdvMlpSpec& trunk, bool actor, LstmPpoNet&
   n.whht_floats = 2 * (H / 32) * (4 * H / 16) * (kPolFragBytes / 4);
   n.grad_floats = n.cell_floats + n.T.grad_floats;
 }
-inline int64_t lstm_ppo_up4(int64_t x) { return (x + 3) / 4 * 4; }
-inline int lstm_ppo_splits(int64_t n) {
+__host__ __device__ inline int64_t lstm_ppo_up4(int64_t x) { return (x + 3) / 4 * 4; }
+__host__ __device__ inline int lstm_ppo_splits(int64_t n) {
   const int64_t chunks = (n + 31) / 32, s = (chunks + 63) / 64;
   return (int)(s < 1 ? 1 : (s > kLstmPpoMaxSplits ? kLstmPpoMaxSplits : s));
 }
+// the trunk kernel's workgroups for n rows: eight waves of 32 rows (ppo_mlp_workgroups of a table with waves = 8)
+__host__ __device__ inline int64_t lstm_ppo_trunk_groups(int64_t n) { return (n + 8 * kPolWaveEnvs - 1) / (8 * kPolWaveEnvs); }
 
 // The workspace (floats; every piece starts at a multiple of 4): [actor trunk bwd | critic trunk bwd] (ppo_mlp_transpose_kernel's pair),
 // obs_g, start_g, then per net: w0t, whht, h0_g, c0_g, hs, cs, gates, dh, dcc, dscale, trunk rows, cell rows.
+// LstmPpoDims: what the layout needs of the two nets (index 0 actor, 1 critic), small enough to travel by value: the set form evaluates
+// the layout of each member's piece on the device from (T, B_g).  One definition, host and device.
+struct LstmPpoDims { int32_t H[2], w0t[2], whht[2], tpart[2], cpart[2]; };   // units; floats of W_0^T, of W_hh^T, of a trunk row, of a cell row
 struct LstmPpoNetWs { int64_t w0t, whht, h0, c0, hs, cs, gates, dh, dcc, dscale, tparts, cparts; };
+struct LstmPpoHeadWs { int64_t obs, start, obs_stride, end; };
 struct LstmPpoWs { int64_t obs, start, total; int64_t obs_stride; LstmPpoNetWs net[2]; };
-inline void lstm_ppo_workspace(const LstmPpoNet& a, const LstmPpoNet& c, int64_t T, int64_t B, LstmPpoWs& w) {
-  const int64_t n = T * B;
+inline LstmPpoDims lstm_ppo_dims(const LstmPpoNet& a, const LstmPpoNet& c) {
+  return {{a.H, c.H}, {a.w0t_floats, c.w0t_floats}, {a.whht_floats, c.whht_floats}, {a.T.part_floats, c.T.part_floats},
+          {(int32_t)lstm_ppo_up4(a.cell_part), (int32_t)lstm_ppo_up4(c.cell_part)}};
+}
+__host__ __device__ inline LstmPpoHeadWs lstm_ppo_head_layout(int64_t T, int64_t B) {
+  LstmPpoHeadWs h;
   int64_t at = 2 * (int64_t)kPpoMlpBwdFloats;
-  w.obs_stride = lstm_ppo_up4(B * kPolIn);
-  w.obs = at; at += T * w.obs_stride;
-  w.start = at; at += lstm_ppo_up4((n + 3) / 4);
-  const LstmPpoNet* nets[2] = {&a, &c};
-  for (int k = 0; k < 2; ++k) {
-    const LstmPpoNet& N = *nets[k];
-    LstmPpoNetWs& o = w.net[k];
-    const int64_t H = N.H;
-    o.w0t = at; at += N.w0t_floats;
-    o.whht = at; at += N.whht_floats;
-    o.h0 = at; at += B * H;
-    o.c0 = at; at += B * H;
-    o.hs = at; at += n * H;
-    o.cs = at; at += n * H;
-    o.gates = at; at += n * 4 * H;
-    o.dh = at; at += n * H;
-    o.dcc = at; at += B * H;
-    o.dscale = at; at += lstm_ppo_up4(T * ((B + 31) / 32));
-    o.tparts = at; at += ppo_mlp_workgroups(N.T, n) * N.T.part_floats;
-    o.cparts = at; at += (int64_t)lstm_ppo_splits(n) * lstm_ppo_up4(N.cell_part);
-  }
-  w.total = at;
+  h.obs_stride = lstm_ppo_up4(B * kPolIn);
+  h.obs = at; at += T * h.obs_stride;
+  h.start = at; at += lstm_ppo_up4((T * B + 3) / 4);
+  h.end = at;
+  return h;
+}
+// net k's pieces from float `at` on -> where the next net's start
+__host__ __device__ inline int64_t lstm_ppo_net_layout(const LstmPpoDims& d, int k, int64_t T, int64_t B, int64_t at, LstmPpoNetWs& o) {
+  const int64_t n = T * B, H = d.H[k];
+  o.w0t = at; at += d.w0t[k];
+  o.whht = at; at += d.whht[k];
+  o.h0 = at; at += B * H;
+  o.c0 = at; at += B * H;
+  o.hs = at; at += n * H;
+  o.cs = at; at += n * H;
+  o.gates = at; at += n * 4 * H;
+  o.dh = at; at += n * H;
+  o.dcc = at; at += B * H;
+  o.dscale = at; at += lstm_ppo_up4(T * ((B + 31) / 32));
+  o.tparts = at; at += lstm_ppo_trunk_groups(n) * d.tpart[k];
+  o.cparts = at; at += (int64_t)lstm_ppo_splits(n) * d.cpart[k];
+  return at;
+}
+inline void lstm_ppo_workspace(const LstmPpoNet& a, const LstmPpoNet& c, int64_t T, int64_t B, LstmPpoWs& w) {
+  const LstmPpoDims d = lstm_ppo_dims(a, c);
+  const LstmPpoHeadWs h = lstm_ppo_head_layout(T, B);
+  w.obs = h.obs; w.start = h.start; w.obs_stride = h.obs_stride;
+  w.total = lstm_ppo_net_layout(d, 1, T, B, lstm_ppo_net_layout(d, 0, T, B, h.end, w.net[0]), w.net[1]);
 }
 
 struct LstmPpoLaunch {
@@ -136,5 +153,52 @@ struct LstmPpoLaunch {
 
 __attribute__((visibility("hidden"))) hipError_t lstm_ppo_raise_lds_limit();
 __attribute__((visibility("hidden"))) void lstm_ppo_launch(const LstmPpoLaunch& a, hipStream_t s);
+
+// ---- the set form (rdv_lstm_ppo_set_loss_grad, include/rdv.h "Recurrent PPO minibatch gradients for recurrent sets"): P members'
+// minibatches of whole columns in the same 4 T + 8 launches.  Every kernel above has a SET form (the cell step: lstm_cell_keep_set_kernel on
+// the same lstm_cell_rows; the trunks' layers 1 .. L: ppo_mlp_set_transpose_kernel as it is): the member is taken from the grid — blockIdx.y,
+// blockIdx.z where y is taken, blockIdx.z / the widest member's splits in the weight-gradient kernel — and the body runs on that member's
+// arguments, so workgroup (x, member) IS workgroup x of the member's stand-alone launch: its partition into waves and workgroups, its
+// wave_scale values, its lstm_ppo_splits(T B_g) and its wave-order and index-order sums.  Hence member g's outputs are, bit for bit, what
+// rdv_lstm_ppo_loss_grad writes for stand-alone handles with its weights, envs + off_g and n_seq = B_g.  A workgroup beyond the member's
+// own count (a narrower member, a split index >= its splits, a member without columns) returns before the first barrier; the condition
+// is workgroup-uniform.  Member g's forward block is the set's allocation + g block_floats; its piece of the workspace is the stand-alone
+// layout for (T, B_g) at table.ws[g], member after member (members of count 0 left out), evaluated on the device (lstm_ppo_head_layout,
+// lstm_ppo_net_layout: scalar arithmetic on kernel arguments).  count, off (in columns) and ws travel BY VALUE (PpoSetTable, rdv_ppo.h):
+// no device table, no copy, hence the same cap of 64 members.  Outputs: row g of actor_grad [P, Ga], critic_grad [P, Gc], scalars [P, 8];
+// log_prob and values: member g's [T, B_g] block at float T off_g.  Nothing of a member without columns is written.
+struct LstmPpoSetCommon {
+  const float* block[2];     // the sets' allocations (actor, critic)
+  int32_t block_floats[2];   // a member's forward block
+  float* ws;                 // the workspace
+  int64_t T;
+  LstmPpoDims d;
+  PpoSetTable table;
+};
+struct LstmPpoSetLaunch {
+  LstmPpoLaunch a;           // actor_block, critic_block: the sets' allocations; envs required, all members'; n_seq unused; the outputs' row 0
+  int32_t n_members, actor_block_floats, critic_block_floats;
+  int64_t max_count;         // the widest member's columns
+  PpoSetTable table;
+};
+// fills `t` for counts[0 .. n_members) (all >= 0, n_members <= kPpoSetMaxMembers) -> the workspace's size in bytes: the sum of the members'
+inline int64_t lstm_ppo_set_table(const LstmPpoNet& a, const LstmPpoNet& c, int64_t T, int32_t n_members, const int64_t* counts, PpoSetTable* t,
+                                  int64_t* max_count = nullptr) {
+  int64_t off = 0, ws = 0, most = 0;
+  for (int g = 0; g < kPpoSetMaxMembers; ++g) {
+    const int64_t B = g < n_members ? counts[g] : 0;
+    if (t) { t->count[g] = B; t->off[g] = off; t->ws[g] = ws; }
+    off += B;
+    if (B > 0) {
+      LstmPpoWs w;
+      lstm_ppo_workspace(a, c, T, B, w);
+      ws += w.total;
+    }
+    if (B > most) most = B;
+  }
+  if (max_count) *max_count = most;
+  return ws * (int64_t)sizeof(float);
+}
+__attribute__((visibility("hidden"))) void lstm_ppo_set_launch(const LstmPpoSetLaunch& L, hipStream_t s);
 
 }  // namespace rdv

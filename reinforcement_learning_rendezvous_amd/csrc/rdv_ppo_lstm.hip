@@ -5,7 +5,21 @@
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_ppo_lstm.h"
 
+#include <type_traits>
+
 namespace rdv {
+
+// ---- the set form: what every SET kernel derives of its member from the by-value arguments (rdv_ppo_lstm.h, "the set form")
+// member g's piece of the workspace: where it starts and, for net k (0 actor, 1 critic), the stand-alone layout of (T, B_g)
+__device__ __forceinline__ float* lstm_ppo_member_ws(const LstmPpoSetCommon& c, int g, int k, int64_t B, LstmPpoHeadWs& hd, LstmPpoNetWs& o) {
+  hd = lstm_ppo_head_layout(c.T, B);
+  const int64_t end0 = lstm_ppo_net_layout(c.d, 0, c.T, B, hd.end, o);
+  if (k == 1) lstm_ppo_net_layout(c.d, 1, c.T, B, end0, o);
+  return c.ws + c.table.ws[g];
+}
+__device__ __forceinline__ const float* lstm_ppo_member_block(const LstmPpoSetCommon& c, int g, int k) {
+  return c.block[k] + (size_t)g * c.block_floats[k];
+}
 
 // a value as an MFMA operand reads it: times 2^10, clamped to +-63, a NaN kept (actor_inputs, lstm_h_frag)
 __device__ __forceinline__ float lstm_ppo_operand(float v) {
@@ -26,9 +40,38 @@ struct LstmPpoGatherArgs {
   int64_t N, B, T, obs_stride;
   int32_t Ha, Hc;
 };
-__global__ __launch_bounds__(256) void lstm_ppo_gather_kernel(const LstmPpoGatherArgs A) {
+// the set form's arguments: `g` holds the set-wide values (envs: all members'; obs_g, start_g, st_g, B, obs_stride unused)
+struct LstmPpoSetGatherArgs {
+  LstmPpoGatherArgs g;
+  LstmPpoSetCommon c;
+};
+static_assert(sizeof(LstmPpoSetGatherArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+template <bool SET> using LstmPpoGatherKernelArgs = std::conditional_t<SET, LstmPpoSetGatherArgs, LstmPpoGatherArgs>;
+__device__ __forceinline__ const LstmPpoGatherArgs& lstm_ppo_gather_args(const LstmPpoGatherArgs& S, const LstmPpoGatherArgs&) { return S; }
+__device__ __forceinline__ const LstmPpoGatherArgs& lstm_ppo_gather_args(const LstmPpoSetGatherArgs&, const LstmPpoGatherArgs& M) { return M; }
+// SET = false: the kernel of rdv_lstm_ppo_loss_grad.  SET = true: workgroup (x, y, z) is workgroup (x, y) of member z's stand-alone launch.
+template <bool SET>
+__global__ __launch_bounds__(256) void lstm_ppo_gather_kernel(const LstmPpoGatherKernelArgs<SET> S) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int y = blockIdx.y;
+  [[maybe_unused]] LstmPpoGatherArgs M;                   // SET: the member's scalars (its two arrays of pointers are not read: they
+  [[maybe_unused]] float* st_set = nullptr;               // stay in the kernel arguments; st_set: where state0 array y - 2 goes)
+  if constexpr (SET) {
+    const int g = blockIdx.z;
+    const int64_t B = S.c.table.count[g];
+    if (B == 0) return;
+    LstmPpoHeadWs hd;
+    LstmPpoNetWs o;
+    float* ws = lstm_ppo_member_ws(S.c, g, y >= 4 ? 1 : 0, B, hd, o);
+    M.obs = S.g.obs; M.done = S.g.done; M.N = S.g.N; M.T = S.g.T;
+    M.envs = S.g.envs + S.c.table.off[g];
+    M.B = B;
+    M.obs_stride = hd.obs_stride;
+    M.obs_g = ws + hd.obs;
+    M.start_g = reinterpret_cast<uint8_t*>(ws + hd.start);
+    st_set = ws + ((y & 1) ? o.c0 : o.h0);
+  }
+  const LstmPpoGatherArgs& A = lstm_ppo_gather_args(S, M);
   if (y == 0) {
     const int64_t per = A.B * kPolIn;
     if (i >= A.T * per) return;
@@ -41,11 +84,14 @@ __global__ __launch_bounds__(256) void lstm_ppo_gather_kernel(const LstmPpoGathe
     const int64_t env = A.envs ? A.envs[b] : b;
     A.start_g[i] = t == 0 ? (uint8_t)0 : (uint8_t)(A.done[(t - 1) * A.N + env] != 0);
   } else {
-    const int k = y - 2, H = k < 2 ? A.Ha : A.Hc;
+    const int k = y - 2;
+    int H;
+    if constexpr (SET) H = k < 2 ? S.g.Ha : S.g.Hc; else H = k < 2 ? S.Ha : S.Hc;   // (a value of the kernel arguments themselves, as it was)
     if (i >= A.B * H) return;
     const int64_t b = i / H, u = i - b * H;
     const int64_t env = A.envs ? A.envs[b] : b;
-    A.st_g[k][i] = A.st[k][env * H + u];
+    if constexpr (SET) st_set[i] = S.g.st[k][env * H + u];
+    else A.st_g[k][i] = A.st[k][env * H + u];
   }
 }
 
@@ -59,9 +105,27 @@ struct LstmPpoTransposeArgs {
   float* whht[2];
   float* w0t[2];
 };
-__global__ __launch_bounds__(512) void lstm_ppo_transpose_kernel(const LstmPpoTransposeArgs A) {
+// SET = false: the kernel of rdv_lstm_ppo_loss_grad.  SET = true (the arguments: LstmPpoSetCommon alone): member blockIdx.z's block of the
+// sets' allocations -> its piece of the workspace; a member without columns is skipped.
+static_assert(sizeof(LstmPpoSetCommon) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+template <bool SET>
+__global__ __launch_bounds__(512) void lstm_ppo_transpose_kernel(const std::conditional_t<SET, LstmPpoSetCommon, LstmPpoTransposeArgs> A) {
   const int net = blockIdx.y, b = blockIdx.x, t = threadIdx.x;
-  const float* block = A.block[net];
+  [[maybe_unused]] float *whht_set = nullptr, *w0t_set = nullptr;
+  if constexpr (SET) {
+    const int g = blockIdx.z;
+    const int64_t B = A.table.count[g];
+    if (B == 0) return;
+    LstmPpoHeadWs hd;
+    LstmPpoNetWs o;
+    float* ws = lstm_ppo_member_ws(A, g, net, B, hd, o);
+    whht_set = ws + o.whht;
+    w0t_set = ws + o.w0t;
+  }
+  auto whht = [&]() -> float* { if constexpr (SET) return whht_set; else return A.whht[net]; };
+  auto w0t = [&]() -> float* { if constexpr (SET) return w0t_set; else return A.w0t[net]; };
+  const float* block;
+  if constexpr (SET) block = lstm_ppo_member_block(A, blockIdx.z, net); else block = A.block[net];
   const int32_t* Hd = reinterpret_cast<const int32_t*>(block);
   const int H = Hd[4], NB = H / 32, KSB = H / 4;
   const int KSd = Hd[kMlpRec + kMlpRecStride + 3];                        // the k-steps of layer 1's input: hidden[0] / 16
@@ -73,7 +137,7 @@ __global__ __launch_bounds__(512) void lstm_ppo_transpose_kernel(const LstmPpoTr
     const int tile = (R / H) * NB + (R % H) / 32, rp = (R % H) % 32, ksp = 2 + C / 16, hp = (C % 16) / 8, jp = C % 8;
     const int TILES = 4 * NB, KS = 2 + H / 16;
     const uint16_t* src = reinterpret_cast<const uint16_t*>(block + Hd[5] + kLstmCellHdr);
-    reinterpret_cast<uint16_t*>(A.whht[net])[((size_t)b * 64 + lane) * 8 + j] =
+    reinterpret_cast<uint16_t*>(whht())[((size_t)b * 64 + lane) * 8 + j] =
         src[((size_t)((term * TILES + tile) * KS + ksp) * 64 + (size_t)(rp + 32 * hp)) * 8 + jp];
   } else if (b - nW < n0) {
     const int b2 = b - nW;
@@ -86,7 +150,7 @@ __global__ __launch_bounds__(512) void lstm_ppo_transpose_kernel(const LstmPpoTr
       const uint16_t* src = reinterpret_cast<const uint16_t*>(block + kMlpHdr);
       v = src[((size_t)(frag0 + (term * MT0 + (o >> 5)) * KS0 + i / 16) * 64 + (size_t)((o & 31) + 32 * ((i % 16) / 8))) * 8 + (i % 8)];
     }
-    reinterpret_cast<uint16_t*>(A.w0t[net])[((size_t)b2 * 64 + lane) * 8 + j] = v;
+    reinterpret_cast<uint16_t*>(w0t())[((size_t)b2 * 64 + lane) * 8 + j] = v;
   }
 }
 
@@ -199,6 +263,30 @@ __global__ __launch_bounds__(kPolBlock) void lstm_cell_keep_kernel(const float* 
   __shared__ __attribute__((aligned(16))) float stage[(kPolBlock / 64) * kPolObsStage];
   lstm_cell_rows<H, true>(W, obs, start, h_in, c_in, h_next, c_out, gates, n, stage);
 }
+// the set form: workgroup (x, y) is workgroup x of member y's stand-alone launch of step t for net k — lstm_cell_rows on the pointers
+// that lstm_ppo_launch passes, derived from the member's piece (the plain kernel keeps its nine arguments and so its code).  A wave
+// beyond the member's columns returns in lstm_cell_rows, which has no workgroup barrier.
+struct LstmPpoSetCellArgs {
+  LstmPpoSetCommon c;
+  int32_t k, t;
+};
+static_assert(sizeof(LstmPpoSetCellArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+template <int H>
+__global__ __launch_bounds__(kPolBlock) void lstm_cell_keep_set_kernel(const LstmPpoSetCellArgs S) {
+  __shared__ __attribute__((aligned(16))) float stage[(kPolBlock / 64) * kPolObsStage];
+  const int g = blockIdx.y;
+  const int64_t B = S.c.table.count[g];
+  if ((int64_t)blockIdx.x * kPolBlockEnvs >= B) return;
+  LstmPpoHeadWs hd;
+  LstmPpoNetWs o;
+  float* ws = lstm_ppo_member_ws(S.c, g, S.k, B, hd, o);
+  const int64_t t = S.t;
+  const float* h_in = t == 0 ? ws + o.h0 : ws + o.hs + (t - 1) * B * H;
+  const float* c_in = t == 0 ? ws + o.c0 : ws + o.cs + (t - 1) * B * H;
+  const uint8_t* start = t == 0 ? nullptr : reinterpret_cast<const uint8_t*>(ws + hd.start) + t * B;
+  lstm_cell_rows<H, true>(lstm_ppo_member_block(S.c, g, S.k), ws + hd.obs + t * hd.obs_stride, start, h_in, c_in, ws + o.hs + t * B * H,
+                          ws + o.cs + t * B * H, ws + o.gates + t * B * 4 * H, B, stage);
+}
 
 // ---- 2. the trunk over all T B rows
 struct LstmPpoTrunkArgs {
@@ -210,6 +298,57 @@ struct LstmPpoTrunkArgs {
   int32_t H;
   PpoMlpTable T;
 };
+// The set form's arguments: `net` holds the set-wide values (the [T, N] columns, envs and out: all members'; N, H, T: the one table of
+// this net; the other pointers, B and rows.n unused); lstm_ppo_trunk_member derives member blockIdx.y's own WITHOUT the table, which stays
+// in the kernel-argument segment (a private copy indexed by the layer would be scratch).  `idle`: workgroup x has no rows of that member
+// (it has fewer workgroups than the widest member, or no columns) — workgroup-uniform, taken before the first barrier.
+struct LstmPpoSetTrunkArgs {
+  LstmPpoTrunkArgs net;
+  LstmPpoSetCommon c;
+};
+static_assert(sizeof(LstmPpoSetTrunkArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+struct LstmPpoTrunkMember {
+  const float *block, *bwd, *hs;
+  PpoRowArgs rows;
+  const int64_t* envs;
+  int64_t N, B;
+  float *parts, *out;
+  int32_t H, k;
+  const LstmPpoSetCommon* c;     // (the kernel arguments: W_0^T and dh are derived from them where layer 0's step starts)
+};
+template <bool SET> using LstmPpoTrunkKernelArgs = std::conditional_t<SET, LstmPpoSetTrunkArgs, LstmPpoTrunkArgs>;
+__host__ __device__ __forceinline__ const PpoMlpTable& lstm_ppo_table_of(const LstmPpoTrunkArgs& S) { return S.T; }
+__host__ __device__ __forceinline__ const PpoMlpTable& lstm_ppo_table_of(const LstmPpoSetTrunkArgs& S) { return S.net.T; }
+template <bool ACTOR, bool SET>
+__device__ __forceinline__ decltype(auto) lstm_ppo_trunk_member(const LstmPpoTrunkKernelArgs<SET>& S, bool& idle) {
+  if constexpr (SET) {
+    constexpr int k = ACTOR ? 0 : 1;
+    const int g = blockIdx.y;
+    const int64_t B = S.c.table.count[g], n = S.c.T * B, off = S.c.table.off[g];
+    idle = (int64_t)blockIdx.x * kPolBlockEnvs >= n;
+    LstmPpoHeadWs hd;
+    LstmPpoNetWs o;
+    float* ws = lstm_ppo_member_ws(S.c, g, k, B, hd, o);
+    LstmPpoTrunkMember M;
+    M.block = lstm_ppo_member_block(S.c, g, k);
+    M.bwd = ws + (size_t)k * kPpoMlpBwdFloats;
+    M.hs = ws + o.hs;
+    M.rows = S.net.rows;
+    M.rows.n = n;
+    M.envs = S.net.envs + off;
+    M.N = S.net.N;
+    M.B = B;
+    M.parts = ws + o.tparts;
+    M.out = S.net.out ? S.net.out + S.c.T * off : nullptr;
+    M.H = S.net.H;
+    M.k = k;
+    M.c = &S.c;
+    return M;
+  } else {
+    idle = false;
+    return (S);                                            // the arguments themselves: the plain kernel is the code it was
+  }
+}
 
 // lstm_trunk_first of rdv_policy_lstm.h, the same operations in the same order, with the activations of its MT tiles kept
 template <int ACT, int MT>
@@ -249,13 +388,29 @@ __device__ __forceinline__ void lstm_ppo_h_tile(const float* row, int nt, int hh
   }
 }
 
+// W_0^T and dh, which only layer 0's step reads.  The set form derives them HERE from the kernel arguments, behind an opaque copy of the
+// member's column count, and not with the member's other pointers ahead of the layers' loop: the actor kernel has no scalar register left
+// for two more pointers that live across that loop (they would spill, through a vector register it does not have either, to scratch).
+struct LstmPpoFirstPointers { const float* w0t; float* dh; };
+__device__ __forceinline__ const LstmPpoTrunkArgs& lstm_ppo_first_pointers(const LstmPpoTrunkArgs& A) { return A; }   // (read where they are used, as they were)
+__device__ __forceinline__ LstmPpoFirstPointers lstm_ppo_first_pointers(const LstmPpoTrunkMember& A) {
+  const int g = blockIdx.y;
+  int64_t B = A.c->table.count[g];
+  asm volatile("" : "+s"(B));
+  LstmPpoHeadWs hd;
+  LstmPpoNetWs o;
+  float* ws = lstm_ppo_member_ws(*A.c, g, A.k, B, hd, o);
+  return {ws + o.w0t, ws + o.dh};
+}
+
 // layer 0 of the trunk: d loss / d h_t = W_0^T delta_0 -> dh; dW_0 = delta_0 h_t^T (two column tiles of h_t at a time) and db_0
-template <int KSd>
-__device__ __forceinline__ void lstm_ppo_first_step(const LstmPpoTrunkArgs& A, float inv_acc, float (&dl)[2][16], bool valid, int64_t m, float* wave_tiles,
+template <int KSd, class Member>
+__device__ __forceinline__ void lstm_ppo_first_step(const Member& A, const PpoMlpTable& T, float inv_acc, float (&dl)[2][16], bool valid, int64_t m, float* wave_tiles,
                                                     const float* tiles0, int lane, float* part) {
   constexpr int MTd = KSd == 4 ? 2 : 1;
   constexpr float xs = (float)(1 << kPolXShift), inv_xs = 1.0f / xs;
   const int H = A.H, NB = H / 32, hh = lane >> 5;
+  const auto& P0 = lstm_ppo_first_pointers(A);
   float S, invS;
   wave_scale(MTd == 2 ? fmaxf(tile_max(dl[0]), tile_max(dl[1])) : tile_max(dl[0]), S, invS);
 #pragma unroll
@@ -273,7 +428,7 @@ __device__ __forceinline__ void lstm_ppo_first_step(const LstmPpoTrunkArgs& A, f
 #pragma unroll
       for (int s = 0; s < KSd; ++s) error_frags(dl[s >> 1], s & 1, b[s]);
     }
-    const f16x8* w8 = reinterpret_cast<const f16x8*>(A.w0t) + lane;
+    const f16x8* w8 = reinterpret_cast<const f16x8*>(P0.w0t) + lane;
     const float un = inv_acc * xs * invS;
 #pragma unroll 1
     for (int mt = 0; mt < NB; ++mt) {
@@ -288,14 +443,14 @@ __device__ __forceinline__ void lstm_ppo_first_step(const LstmPpoTrunkArgs& A, f
       if (valid) {
 #pragma unroll
         for (int e4 = 0; e4 < 4; ++e4)
-          *reinterpret_cast<pol_f4*>(A.dh + m * H + 32 * mt + 8 * e4 + 4 * hh) =
+          *reinterpret_cast<pol_f4*>(P0.dh + m * H + 32 * mt + 8 * e4 + 4 * hh) =
               pol_f4{pre[4 * e4] * un, pre[4 * e4 + 1] * un, pre[4 * e4 + 2] * un, pre[4 * e4 + 3] * un};
       }
     }
   }
   _Float16* tb = reinterpret_cast<_Float16*>(wave_tiles);
   const float* hrow = valid ? A.hs + m * H : nullptr;
-  const int w_off = A.T.w_off[0], b_off = A.T.b_off[0], out_w = A.T.out_w[0];
+  const int w_off = T.w_off[0], b_off = T.b_off[0], out_w = T.out_w[0];
 #pragma unroll 1
   for (int nt0 = 0; nt0 < NB; nt0 += 2) {
     float hv[16];
@@ -315,11 +470,16 @@ __device__ __forceinline__ void lstm_ppo_first_step(const LstmPpoTrunkArgs& A, f
 }
 
 // Eight waves, each 32 rows; trailing waves of the last workgroup have no rows and stay (barriers).
-template <int ACT, bool ACTOR>
-__global__ __launch_bounds__(kPolBlock) void lstm_ppo_trunk_kernel(const LstmPpoTrunkArgs A) {
+// SET = false: the kernel of rdv_lstm_ppo_loss_grad (profiles/lstm_ppo_set_isa_diff.md).  SET = true: workgroup (x, y) is workgroup x of
+// member y's stand-alone launch: the same body on the member's arguments.
+template <int ACT, bool ACTOR, bool SET>
+__global__ __launch_bounds__(kPolBlock) void lstm_ppo_trunk_kernel(const LstmPpoTrunkKernelArgs<SET> S) {
+  bool idle;
+  const auto& A = lstm_ppo_trunk_member<ACTOR, SET>(S, idle);
+  if (SET && idle) return;
   extern __shared__ __attribute__((aligned(16))) float lstm_ppo_lds[];
   constexpr int nw = kPolBlock / 64;
-  const PpoMlpTable& T = A.T;
+  const PpoMlpTable& T = lstm_ppo_table_of(S);
   const float* w = A.block;
   const int32_t* Hd = reinterpret_cast<const int32_t*>(A.block);
   const int L = T.L, H = A.H;
@@ -392,9 +552,9 @@ __global__ __launch_bounds__(kPolBlock) void lstm_ppo_trunk_kernel(const LstmPpo
   }
   const float inv0 = __int_as_float(Hd[kMlpRec + 4]);
   switch (T.ks[1]) {
-    case 1: lstm_ppo_first_step<1>(A, inv0, dl, valid, (int64_t)mrow, wave_tiles, tiles0, lane, part); break;
-    case 2: lstm_ppo_first_step<2>(A, inv0, dl, valid, (int64_t)mrow, wave_tiles, tiles0, lane, part); break;
-    default: lstm_ppo_first_step<4>(A, inv0, dl, valid, (int64_t)mrow, wave_tiles, tiles0, lane, part); break;
+    case 1: lstm_ppo_first_step<1>(A, T, inv0, dl, valid, (int64_t)mrow, wave_tiles, tiles0, lane, part); break;
+    case 2: lstm_ppo_first_step<2>(A, T, inv0, dl, valid, (int64_t)mrow, wave_tiles, tiles0, lane, part); break;
+    default: lstm_ppo_first_step<4>(A, T, inv0, dl, valid, (int64_t)mrow, wave_tiles, tiles0, lane, part); break;
   }
 }
 
@@ -406,8 +566,32 @@ struct LstmPpoBpttArgs {
   int64_t B;
   int32_t T, t;
 };
-template <int H>
-__global__ __launch_bounds__(kPolBlock) void lstm_ppo_bptt_kernel(const LstmPpoBpttArgs A) {
+// the set form's arguments and member blockIdx.y's own: the arguments lstm_ppo_launch passes for (T, B_g) and the member's piece.  A wave
+// beyond the member's columns returns (`nrows <= 0`; the kernel has no barrier).
+struct LstmPpoSetBpttArgs {
+  LstmPpoSetCommon c;
+  int32_t k, t;
+};
+static_assert(sizeof(LstmPpoSetBpttArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+template <bool SET> using LstmPpoBpttKernelArgs = std::conditional_t<SET, LstmPpoSetBpttArgs, LstmPpoBpttArgs>;
+template <bool SET>
+__device__ __forceinline__ decltype(auto) lstm_ppo_bptt_member(const LstmPpoBpttKernelArgs<SET>& S) {
+  if constexpr (SET) {
+    const int g = blockIdx.y;
+    const int64_t B = S.c.table.count[g];
+    LstmPpoHeadWs hd;
+    LstmPpoNetWs o;
+    float* ws = lstm_ppo_member_ws(S.c, g, S.k, B, hd, o);
+    const LstmPpoBpttArgs M = {lstm_ppo_member_block(S.c, g, S.k), ws + o.whht, ws + o.cs, ws + o.c0, ws + o.dh, ws + o.gates, ws + o.dcc, ws + o.dscale,
+                               reinterpret_cast<const uint8_t*>(ws + hd.start), B, (int32_t)S.c.T, S.t};
+    return M;
+  } else {
+    return (S);                                            // the arguments themselves: the plain kernel is the code it was
+  }
+}
+template <int H, bool SET>
+__global__ __launch_bounds__(kPolBlock) void lstm_ppo_bptt_kernel(const LstmPpoBpttKernelArgs<SET> K) {
+  const auto& A = lstm_ppo_bptt_member<SET>(K);
   constexpr int NB = H / 32, KSB = H / 4, G = 4 * H;
   constexpr float xs = (float)(1 << kPolXShift), down = 1.0f / xs;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
@@ -492,11 +676,46 @@ struct LstmPpoWgradArgs {
   int64_t n, B, obs_stride;
   int32_t H, part_stride, splits;
 };
-__global__ __launch_bounds__(kPolBlock) void lstm_ppo_wgrad_kernel(const LstmPpoWgradArgs A) {
+// The set form: all three grid dimensions are taken, so the member is folded into z: blockIdx.z = member x max_splits + split, max_splits
+// the widest member's lstm_ppo_splits.  `idle`: a split index >= the member's own lstm_ppo_splits(T B_g), or a member without columns —
+// workgroup-uniform, taken before the barrier.
+struct LstmPpoSetWgradArgs {
+  LstmPpoSetCommon c;
+  int32_t k, max_splits;
+};
+static_assert(sizeof(LstmPpoSetWgradArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+template <bool SET> using LstmPpoWgradKernelArgs = std::conditional_t<SET, LstmPpoSetWgradArgs, LstmPpoWgradArgs>;
+template <bool SET>
+__device__ __forceinline__ int lstm_ppo_wgrad_split(const LstmPpoWgradKernelArgs<SET>& S) {
+  if constexpr (SET) return (int)blockIdx.z % S.max_splits; else return blockIdx.z;
+}
+template <bool SET>
+__device__ __forceinline__ decltype(auto) lstm_ppo_wgrad_member(const LstmPpoWgradKernelArgs<SET>& S, bool& idle) {
+  if constexpr (SET) {
+    const int g = (int)blockIdx.z / S.max_splits, sp = lstm_ppo_wgrad_split<SET>(S);
+    const int64_t B = S.c.table.count[g], n = S.c.T * B;
+    const int splits = lstm_ppo_splits(n);
+    idle = B == 0 || sp >= splits;
+    LstmPpoHeadWs hd;
+    LstmPpoNetWs o;
+    float* ws = lstm_ppo_member_ws(S.c, g, S.k, B, hd, o);
+    const LstmPpoWgradArgs M = {ws + o.gates, ws + hd.obs, ws + o.hs, ws + o.h0, reinterpret_cast<const uint8_t*>(ws + hd.start), ws + o.cparts,
+                                n, B, hd.obs_stride, S.c.d.H[S.k], S.c.d.cpart[S.k], splits};
+    return M;
+  } else {
+    idle = false;
+    return (S);                                            // the arguments themselves: the plain kernel is the code it was
+  }
+}
+template <bool SET>
+__global__ __launch_bounds__(kPolBlock) void lstm_ppo_wgrad_kernel(const LstmPpoWgradKernelArgs<SET> K) {
+  bool idle;
+  const auto& A = lstm_ppo_wgrad_member<SET>(K, idle);
+  if (SET && idle) return;
   __shared__ __attribute__((aligned(16))) float tiles[(kPolBlock / 64) * 2 * kPpoTile];   // per wave: the A tile (then its sum), the B tile
   constexpr float xs = (float)(1 << kPolXShift), inv_xs = 1.0f / xs;
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, r = lane & 31, hh = lane >> 5;
-  const int mt = blockIdx.x, nt = blockIdx.y, sp = blockIdx.z;
+  const int mt = blockIdx.x, nt = blockIdx.y, sp = lstm_ppo_wgrad_split<SET>(K);
   const int H = A.H, G = 4 * H;
   float* mine = tiles + wv * 2 * kPpoTile;
   _Float16* ta = reinterpret_cast<_Float16*>(mine);
@@ -589,7 +808,46 @@ __device__ __forceinline__ float lstm_ppo_finish_one(const LstmPpoFinishNet& N, 
   }
   return sum;
 }
-__global__ __launch_bounds__(256) void lstm_ppo_finish_kernel(const LstmPpoFinishArgs F) {
+// the set form: member blockIdx.y's rows of its piece -> row blockIdx.y of the outputs; nothing of a member without columns is written.
+// `F` holds the set-wide values (the strides and sizes; grad and scalars: the outputs' row 0; the parts, groups, splits, n and
+// actor_block unused).
+struct LstmPpoSetFinishArgs {
+  LstmPpoFinishArgs F;
+  LstmPpoSetCommon c;
+};
+static_assert(sizeof(LstmPpoSetFinishArgs) <= 4096, "the set form's arguments fit the 4 KiB kernel-argument segment");
+template <bool SET> using LstmPpoFinishKernelArgs = std::conditional_t<SET, LstmPpoSetFinishArgs, LstmPpoFinishArgs>;
+template <bool SET>
+__device__ __forceinline__ decltype(auto) lstm_ppo_finish_member(const LstmPpoFinishKernelArgs<SET>& S, bool& idle) {
+  if constexpr (SET) {
+    const int g = blockIdx.y;
+    const int64_t B = S.c.table.count[g], n = S.c.T * B;
+    idle = B == 0;
+    LstmPpoHeadWs hd;
+    LstmPpoNetWs oa, oc;
+    float* ws = lstm_ppo_member_ws(S.c, g, 0, B, hd, oa);
+    lstm_ppo_member_ws(S.c, g, 1, B, hd, oc);
+    LstmPpoFinishArgs F = S.F;
+    F.n = n;
+    F.net[0].tparts = ws + oa.tparts; F.net[0].cparts = ws + oa.cparts;
+    F.net[1].tparts = ws + oc.tparts; F.net[1].cparts = ws + oc.cparts;
+    F.net[0].groups = F.net[1].groups = lstm_ppo_trunk_groups(n);
+    F.net[0].splits = F.net[1].splits = lstm_ppo_splits(n);
+    F.net[0].grad = S.F.net[0].grad + (size_t)g * S.F.net[0].grad_floats;
+    F.net[1].grad = S.F.net[1].grad + (size_t)g * S.F.net[1].grad_floats;
+    F.actor_block = lstm_ppo_member_block(S.c, g, 0);
+    F.scalars = S.F.scalars + (size_t)g * kPpoScalars;
+    return F;
+  } else {
+    idle = false;
+    return (S);                                            // the arguments themselves: the plain kernel is the code it was
+  }
+}
+template <bool SET>
+__global__ __launch_bounds__(256) void lstm_ppo_finish_kernel(const LstmPpoFinishKernelArgs<SET> S) {
+  bool idle;
+  const auto& F = lstm_ppo_finish_member<SET>(S, idle);
+  if (SET && idle) return;
   const int i = blockIdx.x * 256 + threadIdx.x;
   const float fn = (float)F.n;
   const int Ga = F.net[0].grad_floats, Gc = F.net[1].grad_floats;
@@ -623,37 +881,61 @@ static void lstm_launch_cell_keep(int H, const float* W, const float* obs, const
   }
 }
 
-template <bool ACTOR>
+static void lstm_launch_cell_keep_set(int H, const LstmPpoSetCellArgs& A, dim3 grid, hipStream_t s) {
+  switch (H) {
+    case 32: hipLaunchKernelGGL(lstm_cell_keep_set_kernel<32>, grid, dim3(kPolBlock), 0, s, A); break;
+    case 64: hipLaunchKernelGGL(lstm_cell_keep_set_kernel<64>, grid, dim3(kPolBlock), 0, s, A); break;
+    case 128: hipLaunchKernelGGL(lstm_cell_keep_set_kernel<128>, grid, dim3(kPolBlock), 0, s, A); break;
+    default: hipLaunchKernelGGL(lstm_cell_keep_set_kernel<256>, grid, dim3(kPolBlock), 0, s, A); break;
+  }
+}
+
+template <bool ACTOR, bool SET>
 static const void* trunk_kernel_of(int activation) {
   switch (activation) {
-    case RDV_ACT_RELU: return reinterpret_cast<const void*>(lstm_ppo_trunk_kernel<RDV_ACT_RELU, ACTOR>);
-    case RDV_ACT_SIGMOID: return reinterpret_cast<const void*>(lstm_ppo_trunk_kernel<RDV_ACT_SIGMOID, ACTOR>);
-    default: return reinterpret_cast<const void*>(lstm_ppo_trunk_kernel<RDV_ACT_TANH, ACTOR>);
+    case RDV_ACT_RELU: return reinterpret_cast<const void*>(lstm_ppo_trunk_kernel<RDV_ACT_RELU, ACTOR, SET>);
+    case RDV_ACT_SIGMOID: return reinterpret_cast<const void*>(lstm_ppo_trunk_kernel<RDV_ACT_SIGMOID, ACTOR, SET>);
+    default: return reinterpret_cast<const void*>(lstm_ppo_trunk_kernel<RDV_ACT_TANH, ACTOR, SET>);
   }
 }
 hipError_t lstm_ppo_raise_lds_limit() {
   for (int act = 0; act < 3; ++act)
-    for (const void* k : {trunk_kernel_of<true>(act), trunk_kernel_of<false>(act)}) {
+    for (const void* k : {trunk_kernel_of<true, false>(act), trunk_kernel_of<false, false>(act), trunk_kernel_of<true, true>(act), trunk_kernel_of<false, true>(act)}) {
       hipError_t err = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, kLstmPpoTrunkLds);
       if (err != hipSuccess) return err;
     }
   return hipSuccess;
 }
-template <bool ACTOR>
-static void launch_trunk(int activation, const LstmPpoTrunkArgs& A, dim3 grid, hipStream_t s) {
+template <bool ACTOR, bool SET>
+static void launch_trunk(int activation, const LstmPpoTrunkKernelArgs<SET>& A, dim3 grid, hipStream_t s) {
   switch (activation) {
-    case RDV_ACT_RELU: hipLaunchKernelGGL((lstm_ppo_trunk_kernel<RDV_ACT_RELU, ACTOR>), grid, dim3(kPolBlock), kLstmPpoTrunkLds, s, A); break;
-    case RDV_ACT_SIGMOID: hipLaunchKernelGGL((lstm_ppo_trunk_kernel<RDV_ACT_SIGMOID, ACTOR>), grid, dim3(kPolBlock), kLstmPpoTrunkLds, s, A); break;
-    default: hipLaunchKernelGGL((lstm_ppo_trunk_kernel<RDV_ACT_TANH, ACTOR>), grid, dim3(kPolBlock), kLstmPpoTrunkLds, s, A); break;
+    case RDV_ACT_RELU: hipLaunchKernelGGL((lstm_ppo_trunk_kernel<RDV_ACT_RELU, ACTOR, SET>), grid, dim3(kPolBlock), kLstmPpoTrunkLds, s, A); break;
+    case RDV_ACT_SIGMOID: hipLaunchKernelGGL((lstm_ppo_trunk_kernel<RDV_ACT_SIGMOID, ACTOR, SET>), grid, dim3(kPolBlock), kLstmPpoTrunkLds, s, A); break;
+    default: hipLaunchKernelGGL((lstm_ppo_trunk_kernel<RDV_ACT_TANH, ACTOR, SET>), grid, dim3(kPolBlock), kLstmPpoTrunkLds, s, A); break;
   }
 }
-static void launch_bptt(int H, const LstmPpoBpttArgs& A, dim3 grid, hipStream_t s) {
+template <bool SET>
+static void launch_bptt(int H, const LstmPpoBpttKernelArgs<SET>& A, dim3 grid, hipStream_t s) {
   switch (H) {
-    case 32: hipLaunchKernelGGL(lstm_ppo_bptt_kernel<32>, grid, dim3(kPolBlock), 0, s, A); break;
-    case 64: hipLaunchKernelGGL(lstm_ppo_bptt_kernel<64>, grid, dim3(kPolBlock), 0, s, A); break;
-    case 128: hipLaunchKernelGGL(lstm_ppo_bptt_kernel<128>, grid, dim3(kPolBlock), 0, s, A); break;
-    default: hipLaunchKernelGGL(lstm_ppo_bptt_kernel<256>, grid, dim3(kPolBlock), 0, s, A); break;
+    case 32: hipLaunchKernelGGL((lstm_ppo_bptt_kernel<32, SET>), grid, dim3(kPolBlock), 0, s, A); break;
+    case 64: hipLaunchKernelGGL((lstm_ppo_bptt_kernel<64, SET>), grid, dim3(kPolBlock), 0, s, A); break;
+    case 128: hipLaunchKernelGGL((lstm_ppo_bptt_kernel<128, SET>), grid, dim3(kPolBlock), 0, s, A); break;
+    default: hipLaunchKernelGGL((lstm_ppo_bptt_kernel<256, SET>), grid, dim3(kPolBlock), 0, s, A); break;
   }
+}
+// the workgroups of lstm_ppo_transpose_kernel: the fragments of the net that has more
+static unsigned lstm_ppo_transpose_frags(const LstmPpoNet& a, const LstmPpoNet& c) {
+  int frags = 0;
+  for (const LstmPpoNet* N : {&a, &c}) {
+    const int f = (N->whht_floats + N->w0t_floats) / (kPolFragBytes / 4);
+    if (f > frags) frags = f;
+  }
+  return (unsigned)frags;
+}
+// the x-workgroups of lstm_ppo_gather_kernel for B columns of T steps
+static unsigned lstm_ppo_gather_groups(int64_t T, int64_t B) {
+  const int64_t n = T * B, most = n * kPolIn > B * kLstmMaxH ? n * kPolIn : B * kLstmMaxH;
+  return (unsigned)((most + 255) / 256);
 }
 
 void lstm_ppo_launch(const LstmPpoLaunch& a, hipStream_t s) {
@@ -671,16 +953,10 @@ void lstm_ppo_launch(const LstmPpoLaunch& a, hipStream_t s) {
   {
     LstmPpoGatherArgs g = {a.obs, a.done, {a.actor_h0, a.actor_c0, a.critic_h0, a.critic_c0}, a.envs, ws + W.obs, start_g,
                            {ws + W.net[0].h0, ws + W.net[0].c0, ws + W.net[1].h0, ws + W.net[1].c0}, a.n_envs, B, T, W.obs_stride, a.actor.H, a.critic.H};
-    const int64_t most = n * kPolIn > B * kLstmMaxH ? n * kPolIn : B * kLstmMaxH;
-    hipLaunchKernelGGL(lstm_ppo_gather_kernel, dim3((unsigned)((most + 255) / 256), 6), dim3(256), 0, s, g);
+    hipLaunchKernelGGL(lstm_ppo_gather_kernel<false>, dim3(lstm_ppo_gather_groups(T, B), 6), dim3(256), 0, s, g);
     ppo_mlp_launch_transpose(a.actor_block, a.critic_block, ws, s);
     LstmPpoTransposeArgs tr = {{a.actor_block, a.critic_block}, {ws + W.net[0].whht, ws + W.net[1].whht}, {ws + W.net[0].w0t, ws + W.net[1].w0t}};
-    int frags = 0;
-    for (const LstmPpoNet* N : nets) {
-      const int f = (N->whht_floats + N->w0t_floats) / (kPolFragBytes / 4);
-      if (f > frags) frags = f;
-    }
-    hipLaunchKernelGGL(lstm_ppo_transpose_kernel, dim3((unsigned)frags, 2), dim3(512), 0, s, tr);
+    hipLaunchKernelGGL(lstm_ppo_transpose_kernel<false>, dim3(lstm_ppo_transpose_frags(a.actor, a.critic), 2), dim3(512), 0, s, tr);
   }
   const PpoRowArgs rows = {a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, nullptr, n, a.k.clip_lo, a.k.clip_hi, a.k.clip_range, 2.0f * a.k.vf_coef};
   for (int k = 0; k < 2; ++k) {
@@ -698,16 +974,16 @@ void lstm_ppo_launch(const LstmPpoLaunch& a, hipStream_t s) {
     const int64_t groups = ppo_mlp_workgroups(N.T, n);
     LstmPpoTrunkArgs tr = {blocks[k], ws + (size_t)k * kPpoMlpBwdFloats, ws + o.w0t, ws + o.hs, rows, a.envs, a.n_envs, B, ws + o.tparts,
                            k == 0 ? a.log_prob : a.values, ws + o.dh, H, N.T};
-    if (k == 0) launch_trunk<true>(acts[k], tr, dim3((unsigned)groups), s);
-    else launch_trunk<false>(acts[k], tr, dim3((unsigned)groups), s);
+    if (k == 0) launch_trunk<true, false>(acts[k], tr, dim3((unsigned)groups), s);
+    else launch_trunk<false, false>(acts[k], tr, dim3((unsigned)groups), s);
     // 3. back through time
     for (int64_t t = T - 1; t >= 0; --t) {
       LstmPpoBpttArgs bp = {blocks[k], ws + o.whht, ws + o.cs, ws + o.c0, ws + o.dh, ws + o.gates, ws + o.dcc, ws + o.dscale, start_g, B, (int32_t)T, (int32_t)t};
-      launch_bptt(H, bp, dim3((unsigned)((B + kPolBlockEnvs - 1) / kPolBlockEnvs)), s);
+      launch_bptt<false>(H, bp, dim3((unsigned)((B + kPolBlockEnvs - 1) / kPolBlockEnvs)), s);
     }
     // 4. the cell's weight gradients
     LstmPpoWgradArgs wg = {ws + o.gates, ws + W.obs, ws + o.hs, ws + o.h0, start_g, ws + o.cparts, n, B, W.obs_stride, H, (int32_t)lstm_ppo_up4(N.cell_part), splits};
-    hipLaunchKernelGGL(lstm_ppo_wgrad_kernel, dim3((unsigned)(4 * H / 32), (unsigned)(1 + H / 32), (unsigned)splits), dim3(kPolBlock), 0, s, wg);
+    hipLaunchKernelGGL(lstm_ppo_wgrad_kernel<false>, dim3((unsigned)(4 * H / 32), (unsigned)(1 + H / 32), (unsigned)splits), dim3(kPolBlock), 0, s, wg);
   }
   // 5. the sums
   LstmPpoFinishArgs F;
@@ -719,7 +995,56 @@ void lstm_ppo_launch(const LstmPpoLaunch& a, hipStream_t s) {
   }
   F.n = n; F.actor_block = a.actor_block; F.ent_coef = a.k.ent_coef; F.vf_coef = a.k.vf_coef; F.scalars = a.scalars;
   const int total = a.actor.grad_floats + a.critic.grad_floats + 1;
-  hipLaunchKernelGGL(lstm_ppo_finish_kernel, dim3((total + 255) / 256), dim3(256), 0, s, F);
+  hipLaunchKernelGGL(lstm_ppo_finish_kernel<false>, dim3((total + 255) / 256), dim3(256), 0, s, F);
+}
+
+// The set form: the launches of lstm_ppo_launch, 4 T + 8 whatever the member count, each over the widest member's grid times the members.
+void lstm_ppo_set_launch(const LstmPpoSetLaunch& L, hipStream_t s) {
+  const LstmPpoLaunch& a = L.a;
+  const unsigned P = (unsigned)L.n_members;
+  const int64_t T = a.n_steps, Bmax = L.max_count, nmax = T * Bmax;
+  const int acts[2] = {a.actor_act, a.critic_act};
+  const LstmPpoNet* nets[2] = {&a.actor, &a.critic};
+  const int max_splits = lstm_ppo_splits(nmax);
+  const LstmPpoSetCommon c = {{a.actor_block, a.critic_block}, {L.actor_block_floats, L.critic_block_floats}, a.workspace, T, lstm_ppo_dims(a.actor, a.critic), L.table};
+
+  // 0. the gathered columns and the transposed fragments
+  {
+    LstmPpoSetGatherArgs g = {{a.obs, a.done, {a.actor_h0, a.actor_c0, a.critic_h0, a.critic_c0}, a.envs, nullptr, nullptr, {nullptr, nullptr, nullptr, nullptr},
+                               a.n_envs, 0, T, 0, a.actor.H, a.critic.H}, c};
+    hipLaunchKernelGGL(lstm_ppo_gather_kernel<true>, dim3(lstm_ppo_gather_groups(T, Bmax), 6, P), dim3(256), 0, s, g);
+    ppo_mlp_launch_set_transpose(a.actor_block, a.critic_block, a.workspace, L.actor_block_floats, L.critic_block_floats, L.n_members, L.table, s);
+    hipLaunchKernelGGL(lstm_ppo_transpose_kernel<true>, dim3(lstm_ppo_transpose_frags(a.actor, a.critic), 2, P), dim3(512), 0, s, c);
+  }
+  const PpoRowArgs rows = {a.obs, a.actions, a.old_log_prob, a.advantages, a.returns, nullptr, 0, a.k.clip_lo, a.k.clip_hi, a.k.clip_range, 2.0f * a.k.vf_coef};
+  const dim3 columns((unsigned)((Bmax + kPolBlockEnvs - 1) / kPolBlockEnvs), P);
+  for (int k = 0; k < 2; ++k) {
+    const LstmPpoNet& N = *nets[k];
+    const int H = N.H;
+    // 1. the forward replay
+    for (int64_t t = 0; t < T; ++t) lstm_launch_cell_keep_set(H, {c, k, (int32_t)t}, columns, s);
+    // 2. the trunk
+    LstmPpoSetTrunkArgs tr = {{nullptr, nullptr, nullptr, nullptr, rows, a.envs, a.n_envs, 0, nullptr, k == 0 ? a.log_prob : a.values, nullptr, H, N.T}, c};
+    const dim3 groups((unsigned)lstm_ppo_trunk_groups(nmax), P);
+    if (k == 0) launch_trunk<true, true>(acts[k], tr, groups, s);
+    else launch_trunk<false, true>(acts[k], tr, groups, s);
+    // 3. back through time
+    for (int64_t t = T - 1; t >= 0; --t) launch_bptt<true>(H, {c, k, (int32_t)t}, columns, s);
+    // 4. the cell's weight gradients
+    LstmPpoSetWgradArgs wg = {c, k, max_splits};
+    hipLaunchKernelGGL(lstm_ppo_wgrad_kernel<true>, dim3((unsigned)(4 * H / 32), (unsigned)(1 + H / 32), (unsigned)max_splits * P), dim3(kPolBlock), 0, s, wg);
+  }
+  // 5. the sums
+  LstmPpoSetFinishArgs F;
+  float* grads[2] = {a.actor_grad, a.critic_grad};
+  for (int k = 0; k < 2; ++k) {
+    const LstmPpoNet& N = *nets[k];
+    F.F.net[k] = {nullptr, nullptr, 0, N.T.part_floats, N.T.grad_floats, (int32_t)lstm_ppo_up4(N.cell_part), 0, N.H, N.grad_floats, grads[k]};
+  }
+  F.F.n = 0; F.F.actor_block = nullptr; F.F.ent_coef = a.k.ent_coef; F.F.vf_coef = a.k.vf_coef; F.F.scalars = a.scalars;
+  F.c = c;
+  const int total = a.actor.grad_floats + a.critic.grad_floats + 1;
+  hipLaunchKernelGGL(lstm_ppo_finish_kernel<true>, dim3((total + 255) / 256, P), dim3(256), 0, s, F);
 }
 
 }  // namespace rdv

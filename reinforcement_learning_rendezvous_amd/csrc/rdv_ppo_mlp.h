@@ -155,6 +155,10 @@ __attribute__((visibility("hidden"))) void ppo_mlp_launch(const PpoMlpLaunch& a,
 __attribute__((visibility("hidden"))) void ppo_mlp_set_launch(const PpoMlpSetLaunch& a, hipStream_t s);
 // launch 1 alone (the transposed fragments of layers 1 .. L of two blocks -> workspace, 2 kPpoMlpBwdFloats floats): rdv_ppo_lstm.hip's trunks
 __attribute__((visibility("hidden"))) void ppo_mlp_launch_transpose(const float* actor_block, const float* critic_block, float* workspace, hipStream_t s);
+// ppo_mlp_set_transpose_kernel on its own (rdv_ppo_lstm.hip: the trunks of a recurrent set): member g's blocks, actor_floats / critic_floats
+// apart in the sets' allocations -> the backward pair at workspace + table.ws[g]; a member of count 0 is skipped
+__attribute__((visibility("hidden"))) void ppo_mlp_launch_set_transpose(const float* actor_set, const float* critic_set, float* workspace, int actor_floats,
+                                                                        int critic_floats, int32_t n_members, const PpoSetTable& table, hipStream_t s);
 
 
 // ---------------------------------------------------------------------------------------------------------------- device

@@ -300,6 +300,12 @@ void ppo_mlp_launch_transpose(const float* actor_block, const float* critic_bloc
   hipLaunchKernelGGL(ppo_mlp_transpose_kernel, dim3(kPpoMlpBwdFrags + 1, 2), dim3(512), 0, s, actor_block, critic_block, workspace);
 }
 
+void ppo_mlp_launch_set_transpose(const float* actor_set, const float* critic_set, float* workspace, int actor_floats, int critic_floats, int32_t n_members,
+                                  const PpoSetTable& table, hipStream_t s) {
+  hipLaunchKernelGGL(ppo_mlp_set_transpose_kernel, dim3(kPpoMlpBwdFrags + 1, 2, (unsigned)n_members), dim3(512), 0, s, actor_set, critic_set, workspace,
+                     actor_floats, critic_floats, table);
+}
+
 void ppo_mlp_launch(const PpoMlpLaunch& a, hipStream_t s) {
   const int64_t groups_a = ppo_mlp_workgroups(a.actor, a.n), groups_c = ppo_mlp_workgroups(a.critic, a.n);
   float* parts_a = a.workspace + 2 * kPpoMlpBwdFloats;
@@ -321,8 +327,7 @@ static int rows_shift(const PpoMlpTable& t) { return t.waves == 8 ? 8 : 7; }
 void ppo_mlp_set_launch(const PpoMlpSetLaunch& L, hipStream_t s) {
   const PpoMlpLaunch& a = L.a;
   const unsigned P = (unsigned)L.n_members;
-  hipLaunchKernelGGL(ppo_mlp_set_transpose_kernel, dim3(kPpoMlpBwdFrags + 1, 2, P), dim3(512), 0, s, a.actor_block, a.critic_block, a.workspace,
-                     a.actor.block_floats, a.critic.block_floats, L.table);
+  ppo_mlp_launch_set_transpose(a.actor_block, a.critic_block, a.workspace, a.actor.block_floats, a.critic.block_floats, L.n_members, L.table, s);
   PpoMlpSetNetArgs S = {{a.actor_block, nullptr, ppo_row_args(a), a.workspace, a.log_prob, a.actor}, 0, 0, L.table};   // a.n is 0: the counts are the table's
   launch_net<true, true>(a.actor_act, S, dim3((unsigned)L.max_groups_a, P), s);
   S.net.block = a.critic_block; S.net.out = a.values; S.net.T = a.critic;

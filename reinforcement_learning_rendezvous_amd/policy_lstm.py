@@ -598,6 +598,22 @@ class LstmPolicySet(_Members, _LstmRows):
         return ppo.ppo_grad(self, *args, **kwargs)
 
     def ppo_grads(self, *args, **kwargs):
-        """Not offered for a recurrent set: ``PolicySet.ppo_grads`` serves sets of the feed-forward shipped actor and critic."""
+        """Not offered for a recurrent set: ``PolicySet.ppo_grads`` serves sets of the feed-forward shipped actor and critic
+        (``ppo_sequence_grads`` is the recurrent set's)."""
         from . import ppo
         return ppo.ppo_set_grads(self, *args, **kwargs)
+
+    def ppo_sequence_grads(self, buf, pieces, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
+        """``LstmPolicy.ppo_sequence_grad`` for every member at once: member g's minibatch is the whole env columns ``pieces[g]`` (a 1-d
+        int64 tensor of GLOBAL columns inside ``group_slices[g]``; ``None``: the member sits the call out; a duplicate counts once per
+        occurrence; ``ppo_sequence_set_minibatches`` yields such lists) of ``buf``, what ``RendezvousBatch.collect(set, T)`` returns with
+        ``N == num_rows``.  Each member's advantages are normalised with SB3's expression over its own T * B_g entries.  Fills ``.grad``
+        of every parameter of every present member, as views of member g's rows of [P, Ga] and [P, Gc] buffers the set owns, and returns
+        a list of P dicts (``None`` for absent members): the six scalars as 0-dim tensors plus ``log_prob`` and ``values`` [T, B_g].
+        CUDA rows: ONE call of rdv_lstm_ppo_set_loss_grad (include/rdv.h "Recurrent PPO minibatch gradients for recurrent sets"): the
+        members share 4 T + 8 launches, and every member gets the bits of a stand-alone ``LstmPolicy.ppo_sequence_grad`` with its
+        weights on the same buffer.  CPU rows or ``backend="torch"``: the members' own autograd fallback one by one.  Clipping, the
+        optimiser and ``update_weights(member=g)`` stay the caller's."""
+        from . import ppo
+        return ppo.ppo_sequence_set_grads(self, buf, pieces, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
+                                          normalize_advantage=normalize_advantage, check=check)

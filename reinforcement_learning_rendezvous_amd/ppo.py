@@ -44,6 +44,16 @@ The three lines behind it can stay on the device too (CUDA rows, every architect
 rdv_ppo_mlp_set_adam_step for a set of another architecture): the
 joint gradient norm of each member's actor and critic, Adam on fp32 master weights the set owns (the member modules' parameters are views
 of them), and the members' forward blocks repacked on the device: no ``update_weights``, no host copy, legal inside a stream capture.
+
+A recurrent learner (``LstmPolicy``) takes ``ppo_sequence_grad`` on minibatches of whole env columns (rdv_lstm_ppo_loss_grad, include/rdv.h
+"Recurrent PPO minibatch gradients"); a sweep of them (``LstmPolicySet``) takes ``ppo_sequence_grads`` for all members in ONE call of
+rdv_lstm_ppo_set_loss_grad, every member with the bits of its own ``ppo_sequence_grad``:
+
+    for pieces in ppo_sequence_set_minibatches(learners, envs_per_batch, generator):          # step k: one tensor of columns per member
+        stats = learners.ppo_sequence_grads(buf, pieces, clip_range=0.2, ent_coef=0.0, vf_coef=0.5)
+        for g, member in enumerate(learners):                                                 # clipping and the optimiser: PyTorch's
+            if pieces[g] is not None:
+                torch.nn.utils.clip_grad_norm_(member.parameters(), 0.5); optimizers[g].step(); learners.update_weights(member=g)
 """
 import ctypes as C
 import math
@@ -352,6 +362,32 @@ def sequence_latents(lstm, obs, start, h0, c0):
     return torch.stack(out)
 
 
+def _sequence_columns(who, buf, H, state0=None, critic_state0=None):
+    """The [T, N] columns of a recurrent rollout and its two state0 pairs, checked: (cols, [(h, c) actor, (h, c) critic], T, N, device)."""
+    obs = buf.get("obs")
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
+        raise ValueError(f"{who}: buf['obs']: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
+    T, N, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
+    cols = {}
+    for name, shape, dtype in (("obs", (T, N, 17), torch.float32), ("actions", (T, N, 6), torch.float32), ("log_prob", (T, N), torch.float32),
+                               ("advantages", (T, N), torch.float32), ("returns", (T, N), torch.float32), ("done", (T, N), torch.uint8)):
+        t = buf.get(name)
+        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
+            raise ValueError(f"{who}: buf[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev} "
+                             "(what RendezvousBatch.collect returns)")
+        cols[name] = t
+    states = []
+    for given, key, kw in ((state0, "lstm_state0", "state0"), (critic_state0, "lstm_critic_state0", "critic_state0")):
+        pair = given if given is not None else buf.get(key)
+        if pair is None:
+            raise ValueError(f"{who}: buf holds no {key!r} (RendezvousBatch.collect records it) and {kw}= is not given")
+        pair = tuple(pair)
+        if len(pair) != 2 or any(not isinstance(x, torch.Tensor) or tuple(x.shape) != (N, H) for x in pair):
+            raise ValueError(f"{who}: {kw} must be a pair (h, c) of [{N}, {H}] tensors")
+        states.append(tuple(x.to(dev, torch.float32).contiguous() for x in pair))
+    return cols, states, T, N, dev
+
+
 def _sequence_state(policy, dev, T, B, N):
     st = policy.__dict__.setdefault("_ppo_seq", {}).get(dev)
     actor, critic = _sequence_params(policy)
@@ -380,30 +416,9 @@ def ppo_sequence_grad(policy, buf, envs=None, clip_range=0.2, ent_coef=0.0, vf_c
     from .policy_lstm import LstmPolicy
     if not isinstance(policy, LstmPolicy):
         raise TypeError(f"ppo_sequence_grad: a {type(policy).__name__} is not offered: it serves one LstmPolicy (MlpPolicy has ppo_grad; "
-                        "an LstmPolicySet keeps SB3 / PyTorch for the update)")
+                        "an LstmPolicySet has ppo_sequence_grads for all its members at once)")
     _check_coefficients("ppo_sequence_grad", clip_range, ent_coef, vf_coef)
-    obs = buf.get("obs")
-    if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[2] != 17:
-        raise ValueError(f"ppo_sequence_grad: buf['obs']: expected a [T,N,17] tensor, got {tuple(getattr(obs, 'shape', ()))}")
-    T, N, dev = int(obs.shape[0]), int(obs.shape[1]), obs.device
-    cols = {}
-    for name, shape, dtype in (("obs", (T, N, 17), torch.float32), ("actions", (T, N, 6), torch.float32), ("log_prob", (T, N), torch.float32),
-                               ("advantages", (T, N), torch.float32), ("returns", (T, N), torch.float32), ("done", (T, N), torch.uint8)):
-        t = buf.get(name)
-        if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != dev or not t.is_contiguous() or tuple(t.shape) != shape:
-            raise ValueError(f"ppo_sequence_grad: buf[{name!r}] must be a contiguous {dtype} tensor of shape {shape} on {dev} "
-                             "(what RendezvousBatch.collect returns)")
-        cols[name] = t
-    H = policy.lstm_hidden_size
-    states = []
-    for given, key, kw in ((state0, "lstm_state0", "state0"), (critic_state0, "lstm_critic_state0", "critic_state0")):
-        pair = given if given is not None else buf.get(key)
-        if pair is None:
-            raise ValueError(f"ppo_sequence_grad: buf holds no {key!r} (RendezvousBatch.collect records it) and {kw}= is not given")
-        pair = tuple(pair)
-        if len(pair) != 2 or any(not isinstance(x, torch.Tensor) or tuple(x.shape) != (N, H) for x in pair):
-            raise ValueError(f"ppo_sequence_grad: {kw} must be a pair (h, c) of [{N}, {H}] tensors")
-        states.append(tuple(x.to(dev, torch.float32).contiguous() for x in pair))
+    cols, states, T, N, dev = _sequence_columns("ppo_sequence_grad", buf, policy.lstm_hidden_size, state0, critic_state0)
     if envs is None:
         B = N
     else:
@@ -483,6 +498,133 @@ def ppo_sequence_grad(policy, buf, envs=None, clip_range=0.2, ent_coef=0.0, vf_c
     return res
 
 
+# ---------------------------------------------------------------------------------------------------- the recurrent set
+def ppo_sequence_set_minibatches(lset, envs_per_batch, generator=None, device=None):
+    """One epoch for all members of an ``LstmPolicySet`` over the env columns of a recurrent rollout: member g gets a
+    ``torch.randperm(size_g)`` of its own columns, drawn in member order from the one generator, shifted to the GLOBAL columns
+    ``start_g + ..`` and cut into pieces of ``envs_per_batch`` as ``ppo_sequence_minibatches`` cuts (the last may be short).  Returns a
+    list of steps; step k is a list of P int64 tensors, ``None`` for a member whose pieces have run out (a smaller member).  Every column
+    of every member appears exactly once.  The tensors are marked as inside their member's columns of this set, so
+    ``LstmPolicySet.ppo_sequence_grads`` does not check them again."""
+    envs_per_batch = int(envs_per_batch)
+    if envs_per_batch <= 0:
+        raise ValueError(f"ppo_sequence_set_minibatches: envs_per_batch = {envs_per_batch} must be positive")
+    if device is None:
+        device = generator.device if generator is not None else "cpu"
+    N = int(lset.num_rows)
+    per = []
+    for sl in lset.group_slices:
+        perm = torch.randperm(sl.stop - sl.start, generator=generator, device=device) + sl.start
+        pieces = list(torch.split(perm, envs_per_batch))
+        for p in pieces:
+            p._rdv_ppo_seq_set = (N, sl.start, sl.stop)
+        per.append(pieces)
+    return [[pieces[k] if k < len(pieces) else None for pieces in per] for k in range(max(len(pieces) for pieces in per))]
+
+
+def _sequence_set_state(lset, dev, P, T, N, total, counts):
+    """The buffers an LstmPolicySet owns for ppo_sequence_grads on device ``dev``: the gradients [P, Ga] and [P, Gc] (row g: member g's
+    flat buffers, of which its parameters' ``.grad`` are views), the scalars [P, 8], the concatenated columns, the [T, N] advantage array
+    and the workspace, the last three grown when a call needs more."""
+    from . import _native as Nat
+    a, c = _lstm_specs(lset.policies[0])
+    st = lset.__dict__.setdefault("_ppo_seq", {}).get(dev)
+    if st is None:
+        Ga, Gc = int(Nat.lib().rdv_lstm_ppo_grad_floats(C.byref(a), 1)), int(Nat.lib().rdv_lstm_ppo_grad_floats(C.byref(c), 0))
+        st = dict(actor=torch.zeros((P, Ga), dtype=torch.float32, device=dev), critic=torch.zeros((P, Gc), dtype=torch.float32, device=dev),
+                  scalars=torch.zeros((P, Nat.PPO_SCALARS), dtype=torch.float32, device=dev), envs=None, adv=None, workspace=None)
+        lset._ppo_seq[dev] = st
+    if st["envs"] is None or st["envs"].numel() < total:
+        st["envs"] = torch.zeros(total, dtype=torch.int64, device=dev)
+    if st["adv"] is None or st["adv"].numel() < T * N:
+        st["adv"] = torch.zeros(T * N, dtype=torch.float32, device=dev)
+    need = int(Nat.lib().rdv_lstm_ppo_set_workspace_bytes(C.byref(a), C.byref(c), T, P, counts))
+    if need < 0:
+        raise ValueError(f"ppo_sequence_grads: a set of {P} members is not served by one call (rdv_lstm_ppo_set_workspace_bytes)")
+    if st["workspace"] is None or st["workspace"].numel() < need:
+        st["workspace"] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return st
+
+
+def ppo_sequence_set_grads(lset, buf, pieces, clip_range=0.2, ent_coef=0.0, vf_coef=0.5, normalize_advantage=True, check=True):
+    """See ``LstmPolicySet.ppo_sequence_grads``."""
+    from .policy_lstm import LstmPolicySet
+    if not isinstance(lset, LstmPolicySet):
+        raise TypeError(f"ppo_sequence_grads: a {type(lset).__name__} is not offered: it serves an LstmPolicySet (one LstmPolicy has "
+                        "ppo_sequence_grad, a PolicySet ppo_grads)")
+    P = len(lset)
+    if not isinstance(pieces, (list, tuple)) or len(pieces) != P:
+        raise ValueError(f"ppo_sequence_grads: pieces must be a list of {P} tensors (or None), one per member")
+    _check_coefficients("ppo_sequence_grads", clip_range, ent_coef, vf_coef)
+    cols, states, T, N, dev = _sequence_columns("ppo_sequence_grads", buf, lset.lstm_hidden_size)
+    if N != lset.num_rows:
+        raise ValueError(f"ppo_sequence_grads: buf['obs'] is {tuple(buf['obs'].shape)}, expected [T, {lset.num_rows}, 17]: N must be the set's rows")
+    live = [g for g in range(P) if pieces[g] is not None]
+    if not live:
+        raise ValueError("ppo_sequence_grads: every member's piece is None")
+    pieces = list(pieces)
+    for g in live:
+        e, sl = pieces[g], lset.group_slices[g]
+        if not isinstance(e, torch.Tensor) or e.dtype != torch.int64 or e.dim() != 1 or e.device != dev or e.numel() == 0:
+            raise ValueError(f"ppo_sequence_grads: pieces[{g}] must be a non-empty 1-d int64 tensor on {dev} (or None)")
+        if check and getattr(e, "_rdv_ppo_seq_set", None) != (N, sl.start, sl.stop):
+            lo, hi = (int(x) for x in torch.aminmax(e))
+            if lo < 0 or hi >= N:
+                raise IndexError(f"ppo_sequence_grads: pieces[{g}] span [{lo}, {hi}], the rollout has columns 0..{N - 1}")
+            if lo < sl.start or hi >= sl.stop:
+                raise IndexError(f"ppo_sequence_grads: pieces[{g}] reach env columns [{lo}, {hi}], member {g} owns {sl.start}..{sl.stop - 1}")
+        pieces[g] = e.contiguous()
+
+    if lset.backend == "torch" or dev.type != "cuda":
+        out = [None] * P
+        for g in live:
+            member = lset[g]
+            backend = member.backend
+            member.backend = "torch"
+            try:
+                out[g] = ppo_sequence_grad(member, buf, pieces[g], clip_range, ent_coef, vf_coef, normalize_advantage, check=False)
+            finally:
+                member.backend = backend
+        return out
+
+    from . import _native as Nat
+    counts = (C.c_int64 * P)(*[int(pieces[g].numel()) if pieces[g] is not None else 0 for g in range(P)])
+    total = sum(counts)
+    st = _sequence_set_state(lset, dev, P, T, N, total, counts)
+    with torch.no_grad():
+        torch.cat([pieces[g] for g in live], out=st["envs"][:total])
+        if normalize_advantage and T * max(counts) > 1:
+            # SB3's expression per member over its own [T, B_g] entries (the expression of ppo_sequence_grad: the same bits), written back
+            # to the member's columns of the one [T, N] array the set owns (members own disjoint columns; a duplicate column writes the
+            # same values twice); a lone entry keeps its raw advantage, as SB3 leaves it
+            adv_col = st["adv"][:T * N].view(T, N)
+            for g in live:
+                adv = cols["advantages"][:, pieces[g]]
+                adv_col.index_copy_(1, pieces[g], normalize_advantages(adv) if T * counts[g] > 1 else adv)
+        else:
+            adv_col = cols["advantages"]
+    log_prob = torch.empty(T * total, dtype=torch.float32, device=dev)
+    values = torch.empty(T * total, dtype=torch.float32, device=dev)
+    r = Nat.LstmPpoRows(cols["obs"].data_ptr(), cols["actions"].data_ptr(), cols["log_prob"].data_ptr(), adv_col.data_ptr(), cols["returns"].data_ptr(),
+                        cols["done"].data_ptr(), states[0][0].data_ptr(), states[0][1].data_ptr(), states[1][0].data_ptr(), states[1][1].data_ptr(),
+                        st["envs"].data_ptr(), N, T, total)
+    o = Nat.LstmPpoSetOut(st["actor"].data_ptr(), st["critic"].data_ptr(), st["scalars"].data_ptr(), log_prob.data_ptr(), values.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    Nat.check(Nat.lib().rdv_lstm_ppo_set_loss_grad(lset._handle("l", dev), lset._handle("v", dev), C.byref(r), counts, float(clip_range), float(ent_coef),
+                                                   float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    s = st["scalars"].clone()
+    out, off = [None] * P, 0
+    for g in range(P):
+        B = counts[g]
+        if B:
+            _bind_grads(lset[g], dict(actor=st["actor"][g], critic=st["critic"][g]), dev, _sequence_params(lset[g]))
+            out[g] = {name: s[g, k] for k, name in enumerate(SCALAR_NAMES)}
+            out[g]["log_prob"] = log_prob[T * off:T * (off + B)].view(T, B)
+            out[g]["values"] = values[T * off:T * (off + B)].view(T, B)
+        off += B
+    return out
+
+
 def _set_grad_floats(pset, route):
     """(Ga, Gc): the lengths of a member's flat actor and critic gradients."""
     from . import _native as N
@@ -525,7 +667,7 @@ def ppo_set_grads(pset, buf, indices, clip_range=0.2, ent_coef=0.0, vf_coef=0.5,
     from .policy import PolicySet
     if not isinstance(pset, PolicySet):
         raise TypeError(f"ppo_grads: a {type(pset).__name__} is not offered: the set form of the PPO minibatch gradients is built for "
-                        "PolicySet alone (LstmPolicySet keeps SB3 / PyTorch for the update)")
+                        "PolicySet alone (an LstmPolicySet has ppo_sequence_grads)")
     P = len(pset)
     if not isinstance(indices, (list, tuple)) or len(indices) != P:
         raise ValueError(f"ppo_grads: indices must be a list of {P} tensors (or None), one per member")
