@@ -1154,8 +1154,8 @@ int rdv_lstm_set_member_weights(rdv_policy p, int32_t member, const float* w_ih_
  *     A refused call enqueues nothing and leaves the handles as they were.
  *   - The existing rdv_ppo_* calls keep refusing a recurrent handle.
  * Recurrent sets have a call of their own, rdv_lstm_ppo_set_loss_grad below (this call keeps refusing a set of more than one member).
- * Not in this call: a device Adam step for recurrent nets (clip, optimiser and rdv_lstm_set_weights stay the caller's), minibatches that
- * start mid-column from stored states, clip_range_vf, one persistent launch.
+ * The optimiser half of the step is rdv_lstm_ppo_set_adam_step at the end of this header (a plain handle pair is a set of one member).
+ * Not in this call: minibatches that start mid-column from stored states, clip_range_vf, one persistent launch.
  */
 typedef struct RdvLstmPpoRows {      /* device pointers: the [T,N,...] columns of a recurrent rollout */
   const float*   obs;                /* [T,N,17]                                            */
@@ -1234,6 +1234,68 @@ int64_t rdv_lstm_ppo_set_workspace_bytes(const RdvLstmSpec* actor_spec_host, con
 int rdv_lstm_ppo_set_loss_grad(rdv_policy actor_set, rdv_policy critic_set, const RdvLstmPpoRows* rows, const int64_t* counts_host,
                                double clip_range, double ent_coef, double vf_coef, void* workspace, int64_t workspace_bytes,
                                const RdvLstmPpoSetOut* out, void* stream);
+
+/*
+ * Gradient clip, Adam and weight repack for recurrent policy sets (added within ABI 5: additive exports): rdv_ppo_set_adam_step for a
+ * recurrent actor set and a recurrent critic set — what follows rdv_lstm_ppo_set_loss_grad (or rdv_lstm_ppo_loss_grad) in a learner's
+ * step, for all P members in ONE call of FOUR launches, fixed by nothing but the call itself: the same four whatever P, H and the trunks
+ * (csrc/rdv_ppo_lstm_adam.h).  A plain recurrent handle pair is a set of one member.  rdv_ppo_set_adam_step and rdv_ppo_mlp_set_adam_step
+ * keep refusing recurrent handles.
+ *
+ * RdvAdamState as above, with rows of Ga = rdv_lstm_ppo_grad_floats(actor spec, 1) and Gc = rdv_lstm_ppo_grad_floats(critic spec, 0)
+ * floats, back to back, in the layout of rdv_lstm_ppo_loss_grad's gradients: w_ih [4H,17], w_hh [4H,H], b_ih [4H], b_hh [4H], the trunk's
+ * layers (w [out,in] then b [out], the head last), log_std [6] last for an actor.  actor_grad [P,Ga], critic_grad [P,Gc]:
+ * RdvLstmPpoSetOut's (a plain pair: RdvLstmPpoOut's).  Base pointers 16-byte aligned; rows are 4-byte aligned only and every access to
+ * them is one float.  The arrays must not alias one another, and the parameter rows must hold the weights the blocks were packed from.
+ *
+ * The contract is that of rdv_ppo_set_adam_step, restated.  For every active member g (bit g of active_mask):
+ *   - Norm.  ONE 2-norm over the member's Ga + Gc gradient entries.  The squares are added in double, in an order fixed by the index
+ *     alone, with no floating-point atomic: the concatenation [actor row | critic row] is cut into chunks of 4096 entries (the last may
+ *     be short); within chunk c thread t of 256 adds the squares of entries 4096 c + t, + 256, .. in index order, and the 256 sums are
+ *     added by the halving tree (t += t + 128, then + 64, .. + 1); the chunk sums are then added in chunk order.  The square root is
+ *     taken in double and rounded to float once.
+ *   - clip_coef, step_size, inv_sqrt_bc2, coef[g] (8 floats) and step[g] <- step[g] + 1: exactly as stated under rdv_ppo_set_adam_step.
+ *   - Elementwise: the same four float32 lines (g', m, v, p), every operation rounded on its own, `/` and sqrt correctly rounded.
+ *   - Non-finite.  A member whose total_norm is not finite is skipped whole: its parameters, moments, step and both blocks are
+ *     untouched, coef[g] = total_norm, 0, 0, 0, 1, 0, 0, 0; the other members are unaffected.
+ *   - Repack.  After the step member g's two forward blocks [trunk block | cell block] are the bytes that rdv_lstm_policy_create /
+ *     rdv_lstm_critic_create pack from its new fp32 parameters.  Trunk block: the fragments with layer 0 = [hidden[0], H] in natural k
+ *     order over H / 16 k-steps and later layers in accumulator order, zero fragments and rows for 16- and 32-wide layers and for the
+ *     head's rows >= out_dim, the biases in accumulator order times 2^(10 + s), each layer's inverse scale in its record, log_std.  Cell
+ *     block: ONE shift for [W_ih | W_hh] — min(s_ih, s_hh), which is the shift of the larger of the two maxima since the rule is monotone
+ *     — its inverse scale at float 0, the fragments [term][tile = q H / 32 + j][ks] (k-steps 0 and 1: the 17 inputs zero-padded, then the
+ *     H / 16 k-steps of h), b_ih then b_hh, each [tile][lane half][16], times the accumulator's scale.  Only live floats are written:
+ *     the header words, the H word of the cell header, the 64 zero floats and the records' integers are the host packer's and stay.
+ *     Nothing is read back from a block: the fp32 master rows are the source.
+ *     ONE EXCEPTION: the six exp(log_std) floats of an actor block.  The device writes the double-precision exp rounded to float; the host
+ *     packer of the recurrent blocks writes the C library's exp on the float (unchanged by this call's introduction).  The device's float
+ *     is within 1 ulp of the correctly rounded float(exp(log_std)), hence within 2 ulp of the host packer's.  What follows: after a device
+ *     step "row i of member g equals a stand-alone handle of member g's weights" holds by equality for the deterministic action and the
+ *     value, which do not read exp(log_std) (and for the state h, c, which no trunk float enters); SAMPLED actions, their log_prob and
+ *     the rdv_lstm_ppo_* gradients read it from the block and equal those of a handle packed on the host from the same weights wherever
+ *     the two floats are equal, and differ by the noise times at most 2 ulp of std otherwise.
+ *   - An inactive member (mask bit clear): nothing of it is read or written — rows, blocks, coef[g], step[g], nor its slice of the workspace.
+ *
+ * The call:
+ *   - The handles' LSTM state (h, c) and pending flags are neither read nor written.
+ *   - Enqueue only: no allocation, no synchronisation, no host-device copy; legal inside a stream capture, and each replay of a captured
+ *     graph takes the NEXT step.  Launches queued earlier on the stream read the old blocks, later ones the new blocks.  Deterministic:
+ *     the same bits eager or replayed.  4 launches: chunk sums; coefficients; step and per-layer partial maxima; repack.
+ *   - workspace: the caller's, 16-byte aligned, rdv_lstm_ppo_adam_workspace_bytes(specs, P) bytes: per member the chunk sums (doubles)
+ *     and the partial maxima of |p| per (net, layer, chunk).  Its contents mean nothing between calls.
+ *   - rdv_lstm_ppo_adam_workspace_bytes (host only): -1 for a bad pair of specs (rdv_lstm_ppo_spec_check: different hidden sizes
+ *     included) or n_members outside 1..64; otherwise a multiple of 16, monotone in n_members.
+ *   - Order of checks.  The host-only checks of rdv_ppo_set_adam_step with the same messages under this call's name (null state or
+ *     pointer, misaligned array, lr, eps, the betas, max_grad_norm, an empty mask, a mask bit at or beyond the member count); a null, then
+ *     a misaligned workspace; RDV_ERR_BAD_HANDLE for an invalid handle; then RDV_ERR_INVALID_ARGUMENT, in the order of
+ *     rdv_lstm_ppo_set_loss_grad, for a handle that is not recurrent, swapped sets, different member counts, more than 64 members,
+ *     different hidden sizes, different devices, a short workspace.  A refused call enqueues nothing.
+ */
+int64_t rdv_lstm_ppo_adam_workspace_bytes(const RdvLstmSpec* actor_spec_host, const RdvLstmSpec* critic_spec_host, int32_t n_members);
+int rdv_lstm_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state,
+                               const float* actor_grad, const float* critic_grad, uint64_t active_mask,
+                               double lr, double beta1, double beta2, double eps, double max_grad_norm,
+                               void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

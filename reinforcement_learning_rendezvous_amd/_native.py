@@ -57,7 +57,9 @@ SYMBOLS = ["rdv_version", "rdv_last_error", "rdv_device_error_code", "rdv_debug_
            # recurrent PPO minibatch gradients (added within ABI 5)
            "rdv_lstm_ppo_spec_check", "rdv_lstm_ppo_grad_floats", "rdv_lstm_ppo_workspace_bytes", "rdv_lstm_ppo_loss_grad",
            # recurrent PPO minibatch gradients for recurrent sets (added within ABI 5)
-           "rdv_lstm_ppo_set_workspace_bytes", "rdv_lstm_ppo_set_loss_grad"]
+           "rdv_lstm_ppo_set_workspace_bytes", "rdv_lstm_ppo_set_loss_grad",
+           # gradient clip, Adam and weight repack for recurrent policy sets (added within ABI 5)
+           "rdv_lstm_ppo_adam_workspace_bytes", "rdv_lstm_ppo_set_adam_step"]
 
 
 class RdvError(RuntimeError):
@@ -195,7 +197,7 @@ class RigidBody(C.Structure):
 
 
 def build(force=False, quiet=True):
-    """Compile the thirteen translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip, rdv_ppo_mlp.hip, rdv_ppo_lstm.hip, rdv_ppo_adam.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
+    """Compile the fourteen translation units of csrc/ (rdv_hip.hip, rdv_tiles.hip, rdv_general.hip, rdv_groups.hip, rdv_policy_mlp.hip, rdv_policy_lstm.hip, rdv_policy_sets.hip, rdv_advantages.hip, rdv_ppo.hip, rdv_ppo_mlp.hip, rdv_ppo_lstm.hip, rdv_ppo_adam.hip, rdv_ppo_lstm_adam.hip and the host-only rdv_policy_host.hip) for gfx950 and link librdv_hip.so
     (hipcc cross-compiles without a GPU).  `make` owns the dependency list (every header of csrc/ and include/rdv.h): it is always
     asked, and rebuilds only what is out of date."""
     cmd = ["make", "-C", CSRC, "-j4"] + (["-B"] if force else [])
@@ -315,6 +317,9 @@ def lib():
         "rdv_lstm_ppo_set_workspace_bytes": (i64, [C.POINTER(LstmSpec), C.POINTER(LstmSpec), i64, C.c_int32, C.POINTER(i64)]),
         "rdv_lstm_ppo_set_loss_grad": (C.c_int, [vp, vp, C.POINTER(LstmPpoRows), C.POINTER(i64), C.c_double, C.c_double, C.c_double, vp, i64,
                                                  C.POINTER(LstmPpoSetOut), vp]),
+        "rdv_lstm_ppo_adam_workspace_bytes": (i64, [C.POINTER(LstmSpec), C.POINTER(LstmSpec), C.c_int32]),
+        "rdv_lstm_ppo_set_adam_step": (C.c_int, [vp, vp, C.POINTER(AdamState), vp, vp, u64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                                 vp, i64, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(L, name, None)

@@ -1,8 +1,8 @@
 // rdv_policy_host.hip — the host side of the policy handles of include/rdv.h: RdvPolicyNet (rdv_host.h) and its create / destroy / act /
 // value / set-weights entry points, policy sets, the recurrent policy and its sets (rdv_lstm_*), rdv_mlp_spec_*, rdv_lstm_spec_check, rdv_gae,
-// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_* (the set form rdv_ppo_mlp_set_* among them), rdv_lstm_ppo_*, rdv_ppo_set_adam_step, rdv_policy_get_block, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
+// rdv_rollout_advantages, rdv_ppo_*, rdv_ppo_mlp_* (the set form rdv_ppo_mlp_set_* among them), rdv_lstm_ppo_* (rdv_lstm_ppo_set_adam_step among them), rdv_ppo_set_adam_step, rdv_policy_get_block, and policy_act_step, the act half of rdv_rollout's act + step loop (the loop, which owns the env handle, is in
 // rdv_hip.hip).  HOST ONLY: no kernel is defined here; they are reached through the launch functions of the headers below (shipped_*,
-// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch, lstm_ppo_launch, ppo_adam_launch), so an edit to an argument check recompiles no kernel.
+// mlp_*, sets_*, lstm_*, gae_launch, ppo_launch, ppo_set_launch, ppo_mlp_launch, lstm_ppo_launch, ppo_adam_launch, lstm_adam_launch), so an edit to an argument check recompiles no kernel.
 #define RDV_POLICY_FUNCTIONS_ONLY
 #include "rdv_policy.h"
 #include "rdv_policy_mlp.h"
@@ -13,6 +13,7 @@
 #include "rdv_ppo_mlp.h"
 #include "rdv_ppo_lstm.h"
 #include "rdv_ppo_adam.h"
+#include "rdv_ppo_lstm_adam.h"
 #include "rdv_host.h"
 
 #include <cstdio>
@@ -1170,6 +1171,54 @@ int rdv_ppo_mlp_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const
   DeviceGuard guard(actor_set->device);
   A.a = adam_launch_args(actor_set, critic_set, state, actor_grad, critic_grad, active_mask, P, A.T[0].grad_floats, A.T[1].grad_floats, lr, beta1, beta2, eps, max_grad_norm);
   ppo_mlp_adam_launch(A, static_cast<hipStream_t>(stream));
+  RDV_HIP(hipGetLastError());
+  return RDV_OK;
+}
+
+// ---- gradient clip, Adam and weight repack for recurrent policy sets (csrc/rdv_ppo_lstm_adam.h)
+int64_t rdv_lstm_ppo_adam_workspace_bytes(const RdvLstmSpec* actor_spec, const RdvLstmSpec* critic_spec, int32_t n_members) {
+  if (n_members < 1 || n_members > kPpoSetMaxMembers || rdv_lstm_ppo_spec_check(actor_spec, critic_spec) != RDV_OK) return -1;
+  LstmAdamLaunch L = {};
+  lstm_adam_net(actor_spec->hidden_size, actor_spec->trunk, true, L.net[0]);
+  lstm_adam_net(critic_spec->hidden_size, critic_spec->trunk, false, L.net[1]);
+  return lstm_adam_workspace(L, n_members);
+}
+
+int rdv_lstm_ppo_set_adam_step(rdv_policy actor_set, rdv_policy critic_set, const RdvAdamState* state, const float* actor_grad, const float* critic_grad,
+                               uint64_t active_mask, double lr, double beta1, double beta2, double eps, double max_grad_norm, void* workspace,
+                               int64_t workspace_bytes, void* stream) {
+  const char* who = "rdv_lstm_ppo_set_adam_step";
+  int32_t P;
+  if (int rc = check_adam_call(who, actor_set, state, actor_grad, critic_grad, active_mask, lr, beta1, beta2, eps, max_grad_norm, P)) return rc;
+  if (!workspace) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace is null", who);
+  if (misaligned(workspace, 16)) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace must be 16-byte aligned", who);
+  RDV_CHECK_POLICY(actor_set);
+  RDV_CHECK_POLICY(critic_set);
+  const struct { rdv_policy p; const char* name; } nets[] = {{actor_set, "actor_set"}, {critic_set, "critic_set"}};
+  for (const auto& a : nets)
+    if (!a.p->lstm_hidden)
+      return fail(RDV_ERR_INVALID_ARGUMENT, "%s: %s is not a recurrent policy or a recurrent set (rdv_lstm_policy_set_create / rdv_lstm_critic_set_create): rdv_ppo_mlp_set_adam_step serves it", who, a.name);
+  if (actor_set->out_dim != kPolOut) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set is a critic handle (rdv_lstm_critic_set_create): actor and critic are swapped", who);
+  if (critic_set->out_dim != 1) return fail(RDV_ERR_INVALID_ARGUMENT, "%s: critic_set is an actor handle (rdv_lstm_policy_set_create): actor and critic are swapped", who);
+  if (int rc = check_set_members(who, actor_set, critic_set)) return rc;
+  if (actor_set->lstm_hidden != critic_set->lstm_hidden)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: the actors' LSTM has %d units, the critics' %d: one hidden_size for both is served", who, actor_set->lstm_hidden, critic_set->lstm_hidden);
+  if (actor_set->device != critic_set->device)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: actor_set on device %d, critic_set on device %d", who, actor_set->device, critic_set->device);
+  LstmAdamLaunch L = {};
+  lstm_adam_net(actor_set->lstm_hidden, actor_set->spec, true, L.net[0]);
+  lstm_adam_net(critic_set->lstm_hidden, critic_set->spec, false, L.net[1]);
+  const int64_t need = lstm_adam_workspace(L, P);
+  if (workspace_bytes < need)
+    return fail(RDV_ERR_INVALID_ARGUMENT, "%s: workspace_bytes = %lld, %d member%s of these specs need %lld (rdv_lstm_ppo_adam_workspace_bytes)", who,
+                (long long)workspace_bytes, P, P == 1 ? "" : "s", (long long)need);
+  if (L.net[0].block_floats != actor_set->block_floats || L.net[1].block_floats != critic_set->block_floats)
+    return fail(RDV_ERR_HIP, "%s: the handles' blocks have %d and %d floats, their specs say %d and %d", who, actor_set->block_floats, critic_set->block_floats,
+                L.net[0].block_floats, L.net[1].block_floats);
+  DeviceGuard guard(actor_set->device);
+  L.a = adam_launch_args(actor_set, critic_set, state, actor_grad, critic_grad, active_mask, P, L.net[0].grad_floats, L.net[1].grad_floats, lr, beta1, beta2, eps, max_grad_norm);
+  L.ws = static_cast<char*>(workspace);
+  lstm_adam_launch(L, static_cast<hipStream_t>(stream));
   RDV_HIP(hipGetLastError());
   return RDV_OK;
 }

@@ -79,6 +79,58 @@ struct PpoMlpAdamLaunch {
 };
 static_assert(sizeof(PpoMlpAdamLaunch) <= 4096, "the arguments fit the 4 KiB kernel-argument segment");
 
+// ---- device pieces that the kernels of rdv_ppo_adam.hip and of rdv_ppo_lstm_adam.hip (the recurrent nets' step, rdv_ppo_lstm_adam.h) share.
+// Both units are compiled with contraction off; every function here is inlined into its kernel.
+// pol_layer_shift's rule on the layer's max |w|
+__device__ __forceinline__ int adam_shift(float mx) {
+  int sft = 10;
+  while (sft > -20 && ldexpf(mx, sft) >= 32768.0f) --sft;
+  return sft;
+}
+// member g's coefficients from its sum of squares (one thread of the member's norm workgroup): the square root in double, rounded to float
+// once; a norm that is not finite flags the member and leaves step[g] alone
+__device__ __forceinline__ void adam_member_coef(const PpoAdamLaunch& a, int g, double sumsq) {
+  const float total = (float)sqrt(sumsq);
+  float4* c = reinterpret_cast<float4*>(a.coef + (size_t)g * kPpoAdamCoef);
+  if (!(fabsf(total) <= 3.402823466e+38f)) {                       // inf or NaN: the member is skipped whole
+    c[0] = make_float4(total, 0.0f, 0.0f, 0.0f);
+    c[1] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
+    return;
+  }
+  // PyTorch's expression on the stored float norm, taken in double and rounded to float once, as the two step coefficients are
+  const float clip = (float)fmin(1.0, (double)a.max_grad_norm / ((double)total + (double)1e-6f));
+  const int64_t tt = a.step[g] + 1;
+  const double bc1 = 1.0 - pow(a.beta1, (double)tt), bc2 = 1.0 - pow(a.beta2, (double)tt);
+  c[0] = make_float4(total, clip, (float)(a.lr / bc1), (float)(1.0 / sqrt(bc2)));
+  c[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  a.step[g] = tt;
+}
+// the elementwise step of entry i of a net's rows (the four float32 lines of include/rdv.h) -> the new parameter
+__device__ __forceinline__ float adam_element(const PpoAdamLaunch& a, const float* gr, float* m, float* v, float* p, int i, float clip, float step_size,
+                                              float isb2) {
+  const float gp = gr[i] * clip;
+  const float mo = m[i];
+  const float mn = mo + (gp - mo) * a.omb1;
+  const float vn = v[i] * a.b2 + (a.omb2 * gp) * gp;
+  const float pn = p[i] - step_size * (mn / (sqrtf(vn) * isb2 + a.eps));
+  m[i] = mn; v[i] = vn; p[i] = pn;
+  return pn;
+}
+// the input column that element j of lane half h of k-step ks of a weight fragment holds.  Natural order: a layer whose B operand is built
+// from rows in memory (an MLP's layer 0, a recurrent trunk's layer 0, the LSTM cell); accumulator order: the k order of an accumulator tile
+// used as the B operand (later layers).  (Two functions, the choice left to the kernel: as one function with the layer as an argument the
+// instruction streams of ppo_adam_update_kernel change, profiles/lstm_adam_isa_diff.md.)
+__device__ __forceinline__ int adam_k_natural(int ks, int h, int j) { return 16 * ks + 8 * h + j; }
+__device__ __forceinline__ int adam_k_accumulator(int ks, int h, int j) { return 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3); }
+// term 0 / 1 of the two-term fp16 split of x 2^sft
+__device__ __forceinline__ _Float16 adam_split_term(float x, int sft, int term) {
+  const float ws = ldexpf(x, sft);
+  const _Float16 hi = (_Float16)ws;                                // round to nearest even, subnormals kept
+  return term == 0 ? hi : (_Float16)(ws - (float)hi);              // (the difference is exact in fp32)
+}
+// the output row that float t of a layer's biases [mt][h][16] holds (accumulator order)
+__device__ __forceinline__ int adam_bias_row(int t) { return 32 * (t >> 5) + (t & 3) + 8 * ((t & 15) >> 2) + 4 * ((t >> 4) & 1); }
+
 __attribute__((visibility("hidden"))) void ppo_adam_launch(const PpoAdamLaunch& a, hipStream_t s);          // the shipped blocks
 __attribute__((visibility("hidden"))) void ppo_mlp_adam_launch(const PpoMlpAdamLaunch& a, hipStream_t s);   // the blocks of a.T
 

@@ -70,28 +70,7 @@ __global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_norm_kernel(const Pp
     __syncthreads();
     if (t < w) part[t] += part[t + w];
   }
-  if (t != 0) return;
-  const float total = (float)sqrt(part[0]);
-  float4* c = reinterpret_cast<float4*>(a.coef + (size_t)g * kPpoAdamCoef);
-  if (!(fabsf(total) <= 3.402823466e+38f)) {                       // inf or NaN: the member is skipped whole
-    c[0] = make_float4(total, 0.0f, 0.0f, 0.0f);
-    c[1] = make_float4(1.0f, 0.0f, 0.0f, 0.0f);
-    return;
-  }
-  // PyTorch's expression on the stored float norm, taken in double and rounded to float once, as the two step coefficients are
-  const float clip = (float)fmin(1.0, (double)a.max_grad_norm / ((double)total + (double)1e-6f));
-  const int64_t tt = a.step[g] + 1;
-  const double bc1 = 1.0 - pow(a.beta1, (double)tt), bc2 = 1.0 - pow(a.beta2, (double)tt);
-  c[0] = make_float4(total, clip, (float)(a.lr / bc1), (float)(1.0 / sqrt(bc2)));
-  c[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  a.step[g] = tt;
-}
-
-// pol_layer_shift's rule on the layer's max |w|
-__device__ __forceinline__ int adam_shift(float mx) {
-  int sft = 10;
-  while (sft > -20 && ldexpf(mx, sft) >= 32768.0f) --sft;
-  return sft;
+  if (t == 0) adam_member_coef(a, g, part[0]);
 }
 
 // ---- 2. the step and the repack of one member's net.  SHIPPED: the arguments are the PpoAdamLaunch alone and the layers those of the
@@ -126,13 +105,7 @@ __global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_update_kernel(const 
   float* v = (actor ? a.actor_v : a.critic_v) + row;
 
   for (int i = t; i < count; i += kPpoAdamThreads) {
-    const float gp = gr[i] * clip;
-    const float mo = m[i];
-    const float mn = mo + (gp - mo) * a.omb1;
-    const float vn = v[i] * a.b2 + (a.omb2 * gp) * gp;
-    const float pn = p[i] - step_size * (mn / (sqrtf(vn) * isb2 + a.eps));
-    m[i] = mn; v[i] = vn; p[i] = pn;
-    w[i] = pn;
+    w[i] = adam_element(a, gr, m, v, p, i, clip, step_size, isb2);
   }
   __syncthreads();
 
@@ -167,11 +140,9 @@ __global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_update_kernel(const 
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         // layer 0: natural k order (its B operand is built from obs rows); later layers: the k order of an accumulator tile
-        const int k = l == 0 ? 16 * ks + 8 * h + j : 32 * (ks >> 1) + 16 * (ks & 1) + 8 * (j >> 2) + 4 * h + (j & 3);
+        const int k = l == 0 ? adam_k_natural(ks, h, j) : adam_k_accumulator(ks, h, j);
         const float x = (orow < out_w && k < in_w) ? w[at_w + orow * in_w + k] : 0.0f;
-        const float ws = ldexpf(x, sft);
-        const _Float16 hi = (_Float16)ws;                          // round to nearest even, subnormals kept
-        o[j] = term == 0 ? hi : (_Float16)(ws - (float)hi);        // (the difference is exact in fp32)
+        o[j] = adam_split_term(x, sft, term);
       }
       *reinterpret_cast<f16x8*>(out + 4 * q) = o;
     }
@@ -180,7 +151,7 @@ __global__ __launch_bounds__(kPpoAdamThreads) void ppo_adam_update_kernel(const 
   // the biases in accumulator order, [mt][h][16] per layer, times the accumulator's scale; padded rows zero
   for (int l = 0; l <= L; ++l) {
     if (t < T.mt[l] * 32) {
-      const int orow = 32 * (t >> 5) + (t & 3) + 8 * ((t & 15) >> 2) + 4 * ((t >> 4) & 1);
+      const int orow = adam_bias_row(t);
       out[t] = orow < T.out_w[l] ? w[T.b_off[l] + orow] * ldexpf(1.0f, kPolXShift + shs[l]) : 0.0f;
     }
     out += T.mt[l] * 32;

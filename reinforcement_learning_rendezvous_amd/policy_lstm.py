@@ -505,6 +505,22 @@ class LstmPolicy(_LstmRows, torch.nn.Module):
         return ppo.ppo_sequence_grad(self, buf, envs, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
                                      normalize_advantage=normalize_advantage, check=check, state0=state0, critic_state0=critic_state0)
 
+    def adam_step(self, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5):
+        """What follows ``ppo_sequence_grad``: ``LstmPolicySet.sequence_adam_step`` on this policy as a set of one — behind a
+        ``ppo_sequence_grad`` that ran rdv_lstm_ppo_loss_grad, ONE rdv_lstm_ppo_set_adam_step on the plain handle pair, on the buffers
+        that call filled (the parameters become views of a master row the policy owns; no ``update_weights()`` is needed); otherwise
+        ``clip_grad_norm_`` and a ``torch.optim.Adam`` the policy owns, and ``update_weights()`` follows.  Returns the dict of [1]
+        tensors ``total_norm``, ``clip_coef``, ``skipped``."""
+        from . import ppo
+        return ppo.lstm_adam_step(self, None, lr, betas, eps, max_grad_norm)
+
+    sequence_adam_step = adam_step       # the name the set gives it
+
+    def reset_optimizer(self):
+        """Zero the Adam moments and the step counter (device state and fallback optimiser alike); the weights are not touched."""
+        from . import ppo
+        return ppo.set_reset_optimizer(self, None)
+
     def update_weights(self, weights=None):
         """New weights for the modules (a dict with the constructor's keys; None: push the modules' current parameters) and for every
         live HIP handle, through rdv_lstm_set_weights on the current stream of its device; the recurrent state is kept."""
@@ -612,8 +628,36 @@ class LstmPolicySet(_Members, _LstmRows):
         a list of P dicts (``None`` for absent members): the six scalars as 0-dim tensors plus ``log_prob`` and ``values`` [T, B_g].
         CUDA rows: ONE call of rdv_lstm_ppo_set_loss_grad (include/rdv.h "Recurrent PPO minibatch gradients for recurrent sets"): the
         members share 4 T + 8 launches, and every member gets the bits of a stand-alone ``LstmPolicy.ppo_sequence_grad`` with its
-        weights on the same buffer.  CPU rows or ``backend="torch"``: the members' own autograd fallback one by one.  Clipping, the
-        optimiser and ``update_weights(member=g)`` stay the caller's."""
+        weights on the same buffer.  CPU rows or ``backend="torch"``: the members' own autograd fallback one by one.  ``sequence_adam_step``
+        is what follows: clip, Adam and the refresh of the members' forward blocks, on the device behind a call that took the C path."""
         from . import ppo
         return ppo.ppo_sequence_set_grads(self, buf, pieces, clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef,
                                           normalize_advantage=normalize_advantage, check=check)
+
+    def sequence_adam_step(self, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5):
+        """``PolicySet.adam_step`` for a recurrent set (named beside ``ppo_sequence_grads``; the set has no method called ``adam_step``) — what follows ``ppo_sequence_grads`` in a learner's step, for every member at
+        once: ``clip_grad_norm_`` per member over both LSTMs, both trunks and ``log_std`` under ONE norm, ``torch.optim.Adam(eps=eps)``
+        and the refresh of the members' forward blocks.  ``stepped``: the list ``ppo_sequence_grads`` returned (a ``None`` entry sits
+        out); ``None``: all members step.  Same semantics and return value as ``PolicySet.adam_step``.
+
+        Behind a ``ppo_sequence_grads`` that ran rdv_lstm_ppo_set_loss_grad (CUDA rows, ``backend != "torch"``, at most 64 members):
+        ONE rdv_lstm_ppo_set_adam_step on the current stream (include/rdv.h "Gradient clip, Adam and weight repack for recurrent policy
+        sets"; four launches whatever P, no allocation past the first use, no synchronisation, no host copy, legal inside a stream
+        capture, each replay taking the next step).  On first use the set allocates master weights [P,Ga] / [P,Gc], moments, step
+        counters, coef and the workspace on that device and re-points every parameter of every member — the ``nn.LSTM`` weights
+        included — at views of row g, in the order of the gradient rows; ``.grad`` stays bound to the gradient rows.  NO
+        ``update_weights()`` is needed: the call rewrites the members' blocks [trunk | cell] with the bytes ``update_weights`` would
+        pack, but for the six ``exp(log_std)`` floats of an actor block (within 1 ulp of the correctly rounded float, within 2 ulp of the
+        host packer's; deterministic actions, values and the state do not read them).  A member with a non-finite norm is skipped whole.
+        The set's state (h, c) and pending flags are untouched.
+
+        CPU rows, ``backend="torch"`` or more than 64 members: per-member ``clip_grad_norm_`` and one ``torch.optim.Adam`` over all
+        members' parameters, as ``PolicySet.adam_step`` falls back; ``update_weights()`` then follows as before."""
+        from . import ppo
+        return ppo.lstm_adam_step(self, stepped, lr, betas, eps, max_grad_norm)
+
+    def reset_optimizer(self, member=None):
+        """Zero the Adam moments and the step counter of one member or of all (None), on the device state and in the fallback's
+        optimiser alike; the weights are not touched (``PolicySet.reset_optimizer``)."""
+        from . import ppo
+        return ppo.set_reset_optimizer(self, member)

@@ -465,6 +465,7 @@ def ppo_sequence_grad(policy, buf, envs=None, clip_range=0.2, ent_coef=0.0, vf_c
             torch.cat([g.reshape(-1) for g in grads[:len(actor)]], out=st["actor"])
             torch.cat([g.reshape(-1) for g in grads[len(actor):]], out=st["critic"])
         _bind_grads(policy, st, pdev, (actor, critic))
+        policy.__dict__.pop("_ppo_seq_last", None)       # the gradients are autograd's: the adam_step behind this call is the PyTorch one
         scalars["log_prob"] = log_prob.detach().reshape(T, B)
         scalars["values"] = values.detach().reshape(T, B)
         return scalars
@@ -492,6 +493,7 @@ def ppo_sequence_grad(policy, buf, envs=None, clip_range=0.2, ent_coef=0.0, vf_c
     Nat.check(Nat.lib().rdv_lstm_ppo_loss_grad(policy._handle("l", dev), policy._handle("v", dev), C.byref(r), float(clip_range), float(ent_coef),
                                                float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
     _bind_grads(policy, st, dev, (actor, critic))
+    policy.__dict__["_ppo_seq_last"] = dev
     s = st["scalars"].clone()
     res = {name: s[k] for k, name in enumerate(SCALAR_NAMES)}
     res["log_prob"], res["values"] = log_prob, values
@@ -585,6 +587,8 @@ def ppo_sequence_set_grads(lset, buf, pieces, clip_range=0.2, ent_coef=0.0, vf_c
                 out[g] = ppo_sequence_grad(member, buf, pieces[g], clip_range, ent_coef, vf_coef, normalize_advantage, check=False)
             finally:
                 member.backend = backend
+        # the gradients are now in the members' own buffers, not in the set's rows: the adam_step behind this call is the PyTorch one
+        lset.__dict__.pop("_ppo_seq_last", None)
         return out
 
     from . import _native as Nat
@@ -612,6 +616,7 @@ def ppo_sequence_set_grads(lset, buf, pieces, clip_range=0.2, ent_coef=0.0, vf_c
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     Nat.check(Nat.lib().rdv_lstm_ppo_set_loss_grad(lset._handle("l", dev), lset._handle("v", dev), C.byref(r), counts, float(clip_range), float(ent_coef),
                                                    float(vf_coef), C.c_void_p(st["workspace"].data_ptr()), st["workspace"].numel(), C.byref(o), stream))
+    lset._ppo_seq_last = dev
     s = st["scalars"].clone()
     out, off = [None] * P, 0
     for g in range(P):
@@ -758,25 +763,99 @@ def _check_adam(lr, betas, eps, max_grad_norm):
     return lr, b1, b2, eps, max_grad_norm
 
 
+class _MlpAdam:
+    """What the optimiser step of a ``PolicySet`` takes from the set: its members, a member's (actor, critic) parameter lists in the order
+    of its gradient rows, the set's gradient buffers on a device, and the device call."""
+    what = "ppo_grads"
+
+    @staticmethod
+    def members(pset):
+        return pset.policies
+
+    params = staticmethod(_params)
+
+    @staticmethod
+    def grads(pset, dev):
+        return pset._ppo[dev]
+
+    @staticmethod
+    def device(pset):
+        dev = getattr(pset, "_ppo_last", None)
+        route = hip_set_route(pset)
+        if dev is None or route is None or len(pset) > 64:
+            return None
+        st = pset.__dict__.get("_ppo", {}).get(dev)
+        return dev if st is not None and tuple(st["actor"].shape) == (len(pset), _set_grad_floats(pset, route)[0]) else None
+
+    @staticmethod
+    def call(pset, dev, ad, grads, mask, scalars):
+        from . import _native as N
+        call = N.lib().rdv_ppo_set_adam_step if hip_set_route(pset) == "shipped" else N.lib().rdv_ppo_mlp_set_adam_step
+        N.check(call(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(ad["c"]), C.c_void_p(grads["actor"].data_ptr()),
+                     C.c_void_p(grads["critic"].data_ptr()), C.c_uint64(mask), *scalars, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+class _LstmAdam:
+    """The same for an ``LstmPolicySet`` or, as a set of one, an ``LstmPolicy``: rows in the layout of rdv_lstm_ppo_grad_floats
+    (``_sequence_params``), the buffers that ``ppo_sequence_grads`` / ``ppo_sequence_grad`` filled, rdv_lstm_ppo_set_adam_step."""
+    what = "ppo_sequence_grads"
+
+    @staticmethod
+    def members(pset):
+        return pset.policies if hasattr(pset, "policies") else [pset]
+
+    params = staticmethod(_sequence_params)
+
+    @staticmethod
+    def grads(pset, dev):
+        st = pset._ppo_seq[dev]
+        # (a stand-alone policy keeps flat buffers: row 0 of a set of one)
+        return st if st["actor"].dim() == 2 else dict(actor=st["actor"].view(1, -1), critic=st["critic"].view(1, -1))
+
+    @staticmethod
+    def device(pset):
+        dev = getattr(pset, "_ppo_seq_last", None)
+        if dev is None or pset.backend == "torch" or len(_LstmAdam.members(pset)) > 64:
+            return None
+        return dev if pset.__dict__.get("_ppo_seq", {}).get(dev) is not None else None
+
+    @staticmethod
+    def call(pset, dev, ad, grads, mask, scalars):
+        from . import _native as N
+        if ad.get("workspace") is None:
+            a, c = _lstm_specs(_LstmAdam.members(pset)[0])
+            need = int(N.lib().rdv_lstm_ppo_adam_workspace_bytes(C.byref(a), C.byref(c), len(_LstmAdam.members(pset))))
+            if need < 0:
+                raise ValueError("adam_step: " + N.lib().rdv_last_error().decode("utf-8", "replace"))
+            ad["workspace"] = torch.empty(need, dtype=torch.uint8, device=dev)
+        N.check(N.lib().rdv_lstm_ppo_set_adam_step(pset._handle("l", dev), pset._handle("v", dev), C.byref(ad["c"]), C.c_void_p(grads["actor"].data_ptr()),
+                                                   C.c_void_p(grads["critic"].data_ptr()), C.c_uint64(mask), *scalars,
+                                                   C.c_void_p(ad["workspace"].data_ptr()), ad["workspace"].numel(),
+                                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+
+
+def _adam_kind(pset):
+    from .policy import PolicySet
+    return _MlpAdam if isinstance(pset, PolicySet) else _LstmAdam
+
+
 def _adam_device(pset):
     """The device whose gradient buffers the last ``ppo_grads`` of this set filled through rdv_ppo_set_loss_grad or
-    rdv_ppo_mlp_set_loss_grad, if the device step serves the set (``hip_set_route``, at most 64 members); None: the PyTorch fallback."""
-    dev = getattr(pset, "_ppo_last", None)
-    route = hip_set_route(pset)
-    if dev is None or route is None or len(pset) > 64:
-        return None
-    st = pset.__dict__.get("_ppo", {}).get(dev)
-    return dev if st is not None and tuple(st["actor"].shape) == (len(pset), _set_grad_floats(pset, route)[0]) else None
+    rdv_ppo_mlp_set_loss_grad, if the device step serves the set (``hip_set_route``, at most 64 members); None: the PyTorch fallback.
+    A recurrent set or policy: the device whose buffers the last ``ppo_sequence_grads`` / ``ppo_sequence_grad`` filled through the C call."""
+    return _adam_kind(pset).device(pset)
 
 
 def _adam_views(pset, ad):
     """The member modules' parameters <- views of row g of the master weights ``ad`` holds (filled from the modules first), so
     ``state_dict()``, checkpoints and ``update_weights()`` see the stepped weights with no copy; ``.grad`` follows to the same device."""
+    kind = _adam_kind(pset)
     dev = ad["actor_param"].device
-    grads = pset._ppo[dev]
+    grads = kind.grads(pset, dev)
     with torch.no_grad():
-        for g, member in enumerate(pset.policies):
-            for flat, params in zip((ad["actor_param"][g], ad["critic_param"][g]), _params(member)):
+        for g, member in enumerate(kind.members(pset)):
+            parts = kind.params(member)
+            for flat, params in zip((ad["actor_param"][g], ad["critic_param"][g]), parts):
                 flat.copy_(torch.cat([p.detach().reshape(-1).to(dev, torch.float32) for p in params]))
                 at = 0
                 for p in params:
@@ -784,25 +863,28 @@ def _adam_views(pset, ad):
                         p.grad = None
                     p.data = flat[at:at + p.numel()].view(p.shape)
                     at += p.numel()
-            _bind_grads(member, dict(actor=grads["actor"][g], critic=grads["critic"][g]), dev)
+            _bind_grads(member, dict(actor=grads["actor"][g], critic=grads["critic"][g]), dev, parts)
     ad["views"] = _adam_pointers(pset)
 
 
 def _adam_pointers(pset):
     """The addresses of every parameter of every member (13 x P for the shipped architecture): what ``_adam_state`` compares to see
     whether each of them still is the view of its master row that ``_adam_views`` made."""
-    return [p.data_ptr() for m in pset.policies for part in _params(m) for p in part]
+    kind = _adam_kind(pset)
+    return [p.data_ptr() for m in kind.members(pset) for part in kind.params(m) for p in part]
 
 
 def _adam_state(pset, dev):
     """The RdvAdamState buffers of a set on ``dev``, allocated on first use: master weights and moments [P,Ga] / [P,Gc] (the shapes of
     the set's gradient buffers: 5708 / 5377 for the shipped architecture), steps [P], coef [P,8]."""
     from . import _native as N
+    kind = _adam_kind(pset)
     table = pset.__dict__.setdefault("_adam", {})
     ad = table.get(dev)
     if ad is None:
-        P = len(pset)
-        Ga, Gc = int(pset._ppo[dev]["actor"].shape[1]), int(pset._ppo[dev]["critic"].shape[1])
+        grads = kind.grads(pset, dev)
+        P = len(kind.members(pset))
+        Ga, Gc = int(grads["actor"].shape[1]), int(grads["critic"].shape[1])
         z = lambda n: torch.zeros((P, n), dtype=torch.float32, device=dev)
         ad = dict(actor_param=z(Ga), critic_param=z(Gc), actor_m=z(Ga), actor_v=z(Ga),
                   critic_m=z(Gc), critic_v=z(Gc), step=torch.zeros(P, dtype=torch.int64, device=dev),
@@ -826,30 +908,39 @@ def set_adam_step(pset, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max
     from .policy import PolicySet
     if not isinstance(pset, PolicySet):
         raise TypeError(f"adam_step: a {type(pset).__name__} is not offered: the device optimiser step is built for PolicySet alone")
-    P = len(pset)
+    return _adam_step(pset, stepped, lr, betas, eps, max_grad_norm)
+
+
+def lstm_adam_step(pset, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max_grad_norm=0.5):
+    """See ``LstmPolicySet.sequence_adam_step`` and ``LstmPolicy.adam_step``."""
+    from .policy_lstm import LstmPolicy, LstmPolicySet
+    if not isinstance(pset, (LstmPolicy, LstmPolicySet)):
+        raise TypeError(f"adam_step: a {type(pset).__name__} is not offered: the recurrent optimiser step serves LstmPolicySet and LstmPolicy")
+    return _adam_step(pset, stepped, lr, betas, eps, max_grad_norm)
+
+
+def _adam_step(pset, stepped, lr, betas, eps, max_grad_norm):
+    kind = _adam_kind(pset)
+    members = kind.members(pset)
+    P = len(members)
     if stepped is not None and (not isinstance(stepped, (list, tuple)) or len(stepped) != P):
-        raise ValueError(f"adam_step: stepped must be the list of {P} entries that ppo_grads returned (or None: all members step)")
+        raise ValueError(f"adam_step: stepped must be the list of {P} entries that {kind.what} returned (or None: all members step)")
     lr, b1, b2, eps, max_grad_norm = _check_adam(lr, betas, eps, max_grad_norm)
     live = [g for g in range(P) if stepped is None or stepped[g] is not None]
     if not live:
         raise ValueError("adam_step: every member sits out")
-    dev = _adam_device(pset)
+    dev = kind.device(pset)
     if dev is not None:
-        from . import _native as N
         ad = _adam_state(pset, dev)
-        grads = pset._ppo[dev]
         mask = 0
         for g in live:
             mask |= 1 << g
-        call = N.lib().rdv_ppo_set_adam_step if hip_set_route(pset) == "shipped" else N.lib().rdv_ppo_mlp_set_adam_step
-        N.check(call(pset._hip_handle(dev), pset._critic_handle(dev), C.byref(ad["c"]), C.c_void_p(grads["actor"].data_ptr()),
-                     C.c_void_p(grads["critic"].data_ptr()), C.c_uint64(mask), lr, b1, b2, eps, max_grad_norm,
-                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+        kind.call(pset, dev, ad, kind.grads(pset, dev), mask, (lr, b1, b2, eps, max_grad_norm))
         return _adam_result(ad["coef"])
 
     # ---- the fallback: per-member clip_grad_norm_ and ONE torch.optim.Adam over all members' parameters; the moments are PyTorch's
     fb = pset.__dict__.get("_adam_torch")
-    params = [list(m.parameters()) for m in pset.policies]           # the order of INTEGRATION.md's clip_grad_norm_(member.parameters(), ...)
+    params = [list(m.parameters()) for m in members]                 # the order of INTEGRATION.md's clip_grad_norm_(member.parameters(), ...)
     pdev = params[0][0].device
     if fb is None or fb["ids"] != [id(p) for ps in params for p in ps]:
         fb = dict(opt=torch.optim.Adam([p for ps in params for p in ps], lr=lr, betas=(b1, b2), eps=eps), ids=[id(p) for ps in params for p in ps],
@@ -859,7 +950,7 @@ def set_adam_step(pset, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max
         group["lr"], group["betas"], group["eps"] = lr, (b1, b2), eps
     for g in live:
         if any(p.grad is None for p in params[g]):
-            raise ValueError(f"adam_step: member {g} has no gradients (ppo_grads fills them)")
+            raise ValueError(f"adam_step: member {g} has no gradients ({kind.what} fills them)")
     parked = {}
     for g in range(P):
         total = torch.nn.utils.clip_grad_norm_(params[g], max_grad_norm).to(torch.float32) if g in live else None
@@ -881,13 +972,15 @@ def set_adam_step(pset, stepped=None, lr=3e-4, betas=(0.9, 0.999), eps=1e-5, max
     finally:
         for p, grad in parked.items():
             p.grad = grad
-    dst = getattr(pset, "_ppo_last", None)
+    dst = getattr(pset, "_ppo_last" if kind is _MlpAdam else "_ppo_seq_last", None)
     return _adam_result(fb["coef"] if dst is None or pset.backend == "torch" else fb["coef"].to(dst))
 
 
 def set_reset_optimizer(pset, member=None):
     """See ``PolicySet.reset_optimizer``."""
-    P = len(pset)
+    kind = _adam_kind(pset)
+    members = kind.members(pset)
+    P = len(members)
     todo = list(range(P)) if member is None else [int(member)]
     if not all(0 <= g < P for g in todo):
         raise IndexError(f"reset_optimizer: member {member} of {P}")
@@ -898,6 +991,6 @@ def set_reset_optimizer(pset, member=None):
     fb = pset.__dict__.get("_adam_torch")
     if fb is not None:
         for g in todo:
-            for part in _params(pset.policies[g]):
+            for part in kind.params(members[g]):
                 for p in part:
                     fb["opt"].state.pop(p, None)
